@@ -5,13 +5,21 @@ One STEP = one batched launch of the hot path over `--frames` synthetic 64-mic x
 (190 windows = one second of audio at 48828 Hz, PC/src/config.json:4,16), every window steered to all
 101 x 101 directions (BASELINE.json configs[1]).  Inputs and tables are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]      (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                      (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 N > 1 (north_star): the direction grid is sharded over the ranks, every rank steers ALL
 frames of the (N x larger) global batch to its own contiguous shard of directions -- per-GPU work is fixed, i.e.
 weak scaling -- and one RCCL all-gather per step assembles the full heat-maps on every rank.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 with a `roofline` object derived from the timed steps themselves.  A plain run does
+nothing else: it sets up, warms up, times the steps, writes the outputs of the last timed step if --dump-outputs is
+given, and prints.  --full adds the side measurements: the one-core / all-core CPU baseline (`cpu_baseline`) and, for
+cfg2 on one GPU, the other BASELINE configs (`extra`: MVDR, frequency-domain DAS, fused detector step, ...).
+
+--dump-outputs DIR writes what the timed path returned in its last step: DIR/heatmaps.npy, float32 [frames, directions]
+(the assembled maps on rank 0 for N > 1), beam power per steering direction in row-major MAX_RES_X x MAX_RES_Y order.
+Inputs are seeded (synth.frame_batch), so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -245,17 +253,44 @@ def extras(torch, nat, delays, mics, dev):
     return out
 
 
-def main():
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much; larger outputs are a seeded sample of frames
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=190, help="windows per GPU per step")
     ap.add_argument("--workload", default="cfg2", choices=list(WORKLOADS))
     ap.add_argument("--algo", default="lerp", choices=["pad", "lerp", "hybrid", "fir_vec", "fir_naive"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the MVDR / fused-detector side measurements")
-    args = ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the heat-maps of the last step to DIR/heatmaps.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: the CPU baseline and, for cfg2 on one GPU, the other BASELINE configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the MVDR / fused-detector side measurements")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir, maps):
+    """maps: float32 [frames, directions] on the host.  Above DUMP_LIMIT_BYTES a fixed (seed 0) sample of frames is written,
+    with the sampled frame indices beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    maps = np.ascontiguousarray(maps, dtype=np.float32)
+    if maps.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // (maps.shape[1] * 4 + 8))
+        rows = np.sort(np.random.default_rng(0).choice(maps.shape[0], size=keep, replace=False))
+        maps = maps[rows]
+        np.save(os.path.join(out_dir, "heatmaps_frame_index.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "heatmaps.npy"), maps)
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -267,7 +302,7 @@ def main():
 
     # the CPU baseline forks replicas: run it before anything initialises the GPU in this process
     cpu_line = None
-    if world == 1 and not args.no_cpu_baseline and args.algo in ("pad", "lerp", "hybrid"):
+    if args.full and world == 1 and not args.no_cpu_baseline and args.algo in ("pad", "lerp", "hybrid"):
         cpu_line = cpu_baseline(args.workload, args.algo)
 
     import torch
@@ -401,6 +436,16 @@ def main():
         mine = d_full[last][rank * frames_global:(rank + 1) * frames_global, : hi - lo]
         assert torch.equal(mine, d_part[last][:, : hi - lo]), "all-gather returned a different shard"
 
+    if args.dump_outputs and rank == 0:
+        # the heat-maps of the last timed step, as a caller of this path receives them (all ranks' shards, in direction order)
+        if world > 1:
+            full = d_full[(args.steps - 1) % nbuf]
+            spans = [multi_gpu.shard_range(D, world, r) for r in range(world)]
+            maps = torch.cat([full[r * frames_global:(r + 1) * frames_global, : b - a] for r, (a, b) in enumerate(spans)], dim=1)
+        else:
+            maps = d_part[0][:, :D]
+        dump_outputs(args.dump_outputs, maps.cpu().numpy())
+
     if rank == 0:
         fps = frames_global * args.steps / elapsed
         # per-launch algorithmic bytes of THIS rank's kernel: all frames, its direction shard
@@ -452,7 +497,7 @@ def main():
         }
         if cpu_line is not None:
             line["cpu_baseline"] = cpu_line
-        if world == 1 and not args.no_extras and args.workload == "cfg2":
+        if args.full and world == 1 and not args.no_extras and args.workload == "cfg2":
             try:
                 line["extra"] = extras(torch, nat, delays, mics, dev)
             except Exception as e:      # side measurements must never take the headline line down

@@ -5,7 +5,7 @@ On the GPU box, in ONE lease so that the numbers nest (a plain bench line first,
 MI355X_MICROARCH.md prescribes for HBM counters):
 
     python3 scripts/profile_round.py run  --tag r01 --workload cfg2 --algo lerp      # writes gpurun_out/<tag>_*/
-    python3 scripts/profile_round.py extras --tag r03                                 # the default bench with its side measurements: kernel
+    python3 scripts/profile_round.py extras --tag r03                                 # the --full bench with its side measurements: kernel
                                                                                       # statistics + MFMA-busy counters of the config-3 / config-4 kernels
 
 Back in the repo (parses what gpurun merged into gpurun_out/ and writes the tracked summaries):
@@ -52,11 +52,11 @@ def run(a):
 
 
 def extras(a):
-    """Kernel statistics and MFMA-pipe counters of everything the default bench line runs (config 2 headline + config 3 MVDR /
+    """Kernel statistics and MFMA-pipe counters of everything the --full bench line runs (config 2 headline + config 3 MVDR /
     frequency-domain DAS + config 4 fused step and detector), plus the plain line itself, same lease."""
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
-    cmd = ["python3", os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "10", "--warmup", "2"]
+    cmd = ["python3", os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "10", "--warmup", "2"]
     line = subprocess.run(cmd, env=env, cwd=ROOT, timeout=900, capture_output=True, text=True)
     js = [l for l in line.stdout.splitlines() if l.startswith("{")]
     if line.returncode != 0 or not js:

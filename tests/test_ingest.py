@@ -46,16 +46,13 @@ def test_oracle_matches_golden_hash(oracle_lib):
         assert hashlib.sha256(out.tobytes()).hexdigest() == gold["frame_sha256"][str(n_arrays)]
 
 
-def test_oracle_matches_real_receiver_over_udp(oracle_lib):
-    path = os.path.join(util.ROOT, "oracle", "_ref", "libref_receiver_shipped.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    ref = C.CDLL(path)
+def receive_over_udp(ref, pk, n_arrays):
+    """The reference's own receive_to_buffer (a loaded oracle/_ref receiver library) fed the datagrams `pk` over a UDP
+    loopback socket -> float32 frame, or None where the replay socket cannot be bound."""
     ref.create_msg.restype = C.c_void_p
     fd = ref.create_and_bind_socket(C.c_bool(True))          # 127.0.0.1:21844 (UDP_REPLAY_IP, config.json:28)
     if fd < 0:
-        pytest.skip("cannot bind the replay socket")
-    pk = datagrams()
+        return None
     tx = socket.socket(socket.AF_INET, socket.SOCK_DGRAM)
 
     def send():
@@ -68,10 +65,26 @@ def test_oracle_matches_real_receiver_over_udp(oracle_lib):
     th = threading.Thread(target=send)
     th.start()
     got = np.zeros(M * N, dtype=np.float32)
-    ref.receive_to_buffer(C.c_int(fd), got.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(ref.create_msg()), C.c_int(3))
+    ref.receive_to_buffer(C.c_int(fd), got.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(ref.create_msg()), C.c_int(n_arrays))
     th.join()
+    tx.close()
     ref.close_socket(C.c_int(fd))
-    assert np.array_equal(got, oracle_frame(oracle_lib, pk, 3))
+    return got
+
+
+def test_oracle_matches_real_receiver_over_udp(oracle_lib):
+    """The oracle's frame against the reference's real receiver fed over UDP: against the SHA-256 of the frame it produced,
+    recorded in tests/golden/refc_hashes.json (oracle/gen_golden_refhash.py), and live where oracle/_ref has been built."""
+    rec = json.load(open(os.path.join(util.GOLDEN, "refc_hashes.json")))["receiver_shipped"]
+    pk = datagrams(rec["seed"])
+    assert hashlib.sha256(pk.tobytes()).hexdigest() == rec["packets_sha256"]
+    want = oracle_frame(oracle_lib, pk, rec["n_arrays"])
+    assert hashlib.sha256(want.tobytes()).hexdigest() == rec["frame_sha256"]
+    path = os.path.join(util.ROOT, "oracle", "_ref", "libref_receiver_shipped.so")
+    if os.path.exists(path):
+        got = receive_over_udp(C.CDLL(path), pk, rec["n_arrays"])
+        if got is not None:
+            assert np.array_equal(got, want)
 
 
 @pytest.mark.gpu

@@ -1,5 +1,7 @@
 """CPU: the oracle (oracle/directions_np.py + oracle/das_oracle.c) against the golden vectors that
 oracle/gen_golden.py produced by running the compiled reference.  This is what pins the oracle."""
+import os
+
 import numpy as np
 import pytest
 
@@ -125,33 +127,42 @@ def test_refc_convolve_naive(oracle_lib, name):
 
 # ---- the oracle against oracle/_ref directly ("equals it bit for bit")
 
-@pytest.mark.parametrize("name", ["cfg1", "shipped"])
-def test_oracle_equals_compiled_reference(oracle_lib, name):
-    """Same random block through both CPU engines: every entry point the two share, whole images, bit for bit.
-    Skipped where oracle/_ref has not been built (it needs /root/reference: oracle/build_ref.py)."""
-    if not oracle_lib.RefLib.available(name):
-        pytest.skip("oracle/_ref/libref_%s.so not built" % name)
+def shared_entry_points(eng, name):
+    """Every entry point the oracle and the compiled reference share, on one seeded random block: key -> output array
+    (whole images and the tables the loaders build).  oracle/gen_golden_refhash.py records the reference's side of it."""
     c = CONFIGS[name]
-    ref = oracle_lib.RefLib(name)
-    orc = oracle_lib.Oracle(c["N"], c["X"], c["Y"], c["T"])
     rng = np.random.default_rng(17)
     sig = (rng.standard_normal((c["M"], c["N"])) * 0.25).astype(np.float32)
     mics = np.arange(c["M"], dtype=np.int32)
     d = util.oracle_delays(name)
     whole, d32 = util.table_for("pad", name), np.float32(d)
-    assert orc.mimo_pad(sig, whole, mics).tobytes() == ref.mimo_pad(sig, whole, mics).tobytes()
-    assert orc.mimo_lerp(sig, d32, mics).tobytes() == ref.mimo_lerp(sig, d32, mics).tobytes()
-    assert orc.mimo_hybrid(sig, d32, mics).tobytes() == ref.mimo_hybrid(sig, d32, mics).tobytes()
-    ow, oh = orc.lerp_tables(d32.ravel())
-    rw, rh = ref.lerp_tables(d32.ravel())
-    assert np.array_equal(ow, rw) and oh.tobytes() == rh.tobytes()
-    ow, ot = orc.hybrid_tables(d32.ravel())
-    rw, rt = ref.hybrid_tables(d32.ravel())
-    assert np.array_equal(ow, rw) and ot.tobytes() == rt.tobytes()
+    out = {"mimo_pad": eng.mimo_pad(sig, whole, mics), "mimo_lerp": eng.mimo_lerp(sig, d32, mics),
+           "mimo_hybrid": eng.mimo_hybrid(sig, d32, mics)}
+    out["lerp_tables/whole"], out["lerp_tables/frac"] = eng.lerp_tables(d32.ravel())
+    out["hybrid_tables/whole"], out["hybrid_tables/taps"] = eng.hybrid_tables(d32.ravel())
     off = (c["X"] * c["Y"] // 3) * c["M"]
-    assert orc.miso_pad(sig, whole, mics, off).tobytes() == ref.miso_pad(sig, whole, mics, off).tobytes()
-    assert orc.miso_lerp(sig, d32, mics, off).tobytes() == ref.miso_lerp(sig, d32, mics, off).tobytes()
+    out["miso_pad"] = eng.miso_pad(sig, whole, mics, off)
+    out["miso_lerp"] = eng.miso_lerp(sig, d32, mics, off)
     if name == "cfg1":
         taps = np.ascontiguousarray(util.table_for("fir_vec", name), dtype=np.float32)
         for vec in (False, True):
-            assert orc.mimo_convolve(sig, taps, mics, vectorized=vec).tobytes() == ref.mimo_convolve(sig, taps, mics, vectorized=vec).tobytes()
+            out["mimo_convolve/vectorized=%d" % vec] = eng.mimo_convolve(sig, taps, mics, vectorized=vec)
+    return out
+
+
+@pytest.mark.parametrize("name", ["cfg1", "shipped"])
+def test_oracle_equals_compiled_reference(oracle_lib, name):
+    """Same random block through both CPU engines: every entry point the two share, whole images, bit for bit -- against
+    the SHA-256 of the compiled reference's outputs recorded in tests/golden/refc_hashes.json (oracle/gen_golden_refhash.py),
+    and against the compiled reference itself where oracle/_ref has been built (oracle/build_ref.py)."""
+    import json
+    c = CONFIGS[name]
+    got = shared_entry_points(oracle_lib.Oracle(c["N"], c["X"], c["Y"], c["T"]), name)
+    rec = json.load(open(os.path.join(util.GOLDEN, "refc_hashes.json")))["entry_points"][name]
+    assert sorted(got) == sorted(rec)
+    for key, a in got.items():
+        assert sha(a) == rec[key], (name, key)
+    if oracle_lib.RefLib.available(name):
+        want = shared_entry_points(oracle_lib.RefLib(name), name)
+        for key, a in got.items():
+            assert a.dtype == want[key].dtype and a.tobytes() == want[key].tobytes(), (name, key)
