@@ -127,15 +127,12 @@ void bf_clear_error(void);
 /* 1 when a gfx9xx GPU is usable by this process, else 0 (never initialises a context as a side effect of
  * loading the library). */
 int bf_gpu_available(void);
-/* Kernel family of the last delay-and-sum launch: 0 strided, 1 quad + DPP, 2 shifted copies (sweep), 3 shifted copies
+/* Kernel family of the last delay-and-sum launch: 0 strided, 1 retired (was quad + DPP), 2 shifted copies (sweep), 3 shifted copies
  * (direction-outer, chosen for tables without structure), 4 shifted copies (8-tap FIR), 5 shifted copies (sweep, two
  * frames per workgroup: batched launches of pad / lerp), 6 shifted copies for long blocks (256 < N_SAMPLES <= 1024: LDS image in
  * two halves, conflict-free lane mapping), 7 hybrid sweep with shared windows, two frames per workgroup (batched launches of the
  * 8-tap FIR flavours), 8 the two-frame sweep on frame-interleaved rows (batched lerp); -1 before the first launch. */
 int bf_last_das_variant(void);
-/* Planner A/B switches (the bits of $BF_DEBUG, das_kernels.hip plan_das) at run time, for tests and profiling; -1 returns to
- * the environment's value. */
-void bf_set_debug(int flags);
 /* Profiling builds only (hipcc -DBF_STAMPS, scripts/dev/phase_stamps.py): per-phase wave time of the batched pad / lerp kernel,
  * summed over all waves since the last clear: out16[0..7] = sweep, wait, staging, wait, wait, parking, wait, ordered power sum
  * (s_memtime ticks), out16[8] = waves counted.  All zero in the production build.  Returns 0 or -1. */

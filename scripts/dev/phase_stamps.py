@@ -2,7 +2,7 @@
 """Dev tool: where the waves of the batched pad / lerp kernel spend their time.
 
   build (here or on the GPU box):  python3 scripts/dev/phase_stamps.py build     -> scripts/dev/bin/libbeamformer_hip_stamps.so
-  run (GPU box):                   python3 scripts/dev/phase_stamps.py run [lerp|pad] [workload] [frames] [BF_DEBUG]
+  run (GPU box):                   python3 scripts/dev/phase_stamps.py run [lerp|pad] [workload] [frames]
 
 The profiling library is the production source compiled with -DBF_STAMPS: every wave of das_pair_kernel reads s_memtime at
 its phase boundaries (all next to barriers) and the per-phase totals are summed over the launch."""
@@ -24,9 +24,8 @@ def build():
     print("built", OUT)
 
 
-def run(algo="lerp", workload="cfg2", frames=190, debug=0):
+def run(algo="lerp", workload="cfg2", frames=190):
     os.environ["BF_NATIVE_LIB"] = OUT
-    os.environ["BF_DEBUG"] = str(debug)
     import ctypes as C
     import numpy as np
     import torch
@@ -69,7 +68,7 @@ def run(algo="lerp", workload="cfg2", frames=190, debug=0):
     v = [int(x) for x in buf]
     names = ["sweep", "wait (chunk free)", "staging", "wait (chunk staged)", "wait (rows free)", "parking", "wait (rows parked)", "ordered sum (+ its idle)"]
     tot = sum(v[:8])
-    print("%s %s %d frames BF_DEBUG=%d: %.4f ms per launch (%.0f frames/s), %d waves stamped per launch" % (algo, workload, frames, debug, ms, frames / ms * 1e3, v[8] // reps))
+    print("%s %s %d frames: %.4f ms per launch (%.0f frames/s), %d waves stamped per launch" % (algo, workload, frames, ms, frames / ms * 1e3, v[8] // reps))
     for n, x in zip(names, v[:8]):
         print("  %-26s %6.2f %%" % (n, 100.0 * x / max(tot, 1)))
     print("  mean wave lifetime %.1f ticks; ticks per ms of launch per wave slot: %.0f" % (tot / max(v[8], 1), tot / reps / ms / 4096.0))
@@ -80,4 +79,4 @@ if __name__ == "__main__":
         build()
     else:
         a = sys.argv[2:] if len(sys.argv) > 1 and sys.argv[1] == "run" else sys.argv[1:]
-        run(a[0] if a else "lerp", a[1] if len(a) > 1 else "cfg2", int(a[2]) if len(a) > 2 else 190, int(a[3]) if len(a) > 3 else 0)
+        run(a[0] if a else "lerp", a[1] if len(a) > 1 else "cfg2", int(a[2]) if len(a) > 2 else 190)

@@ -4,6 +4,7 @@ flow graph of every das_copies_kernel / das_pair_kernel instantiation (out-of-li
 included), runs the in-flight data-flow over every path, and reads spill / scratch sizes from the code-object metadata."""
 import importlib.util
 import os
+import re
 
 import pytest
 
@@ -64,21 +65,21 @@ def test_no_register_with_a_read_in_flight_is_touched(chk, asm):
     assert not bad, bad[:5]
 
 
-def test_every_launchable_instantiation_is_scanned_and_none_that_pipelines_reads_spills(chk, asm):
-    """launch_nc (das_kernels.hip) can pick: the pair kernel (pad, lerp); the one-frame sweep for 1 / 2 / 4 segments with the fixed or
+def test_every_default_plan_instantiation_is_scanned_and_none_that_pipelines_reads_spills(chk, asm):
+    """launch_copies (das_kernels.hip) can pick: the pair kernel (pad) and its frame-interleaved successor (lerp); the one-frame sweep for 1 / 2 / 4 segments with the fixed or
     the run-time row stride, 16 waves -- one segment also with 8 waves -- and its direction-outer (DIRECT) twin; the three 8-tap FIR
     flavours.  The instantiations that keep LDS reads in flight across asm statements (pair kernel; one-segment sweep; the long-row
     kernel, whose lerp sweep issues a mic's reads behind its predecessor's last step) must not use scratch: a spilled register with a read in flight is reloaded before the data lands."""
     md = chk.metadata(asm)
     names = [n for n in md if any(k in n for k in ("das_copies_kernel", "das_pair_kernel", "das_pair2_kernel", "das_long_kernel", "das_hybrid_pair_kernel"))]
     short = dict(zip(chk.demangle(names), names))
-    want = ["bf::copies::das_pair_kernel<%d>" % a for a in (0, 1)]
+    want = ["bf::copies::das_pair_kernel<0>"]
     for a in (0, 1):
         want += ["bf::copies::das_copies_kernel<%d, 1, %d, %d, %s>" % (a, rs, w, d) for rs in (312, 0) for w, d in ((16, "false"), (8, "false"), (16, "true"))]
         want += ["bf::copies::das_copies_kernel<%d, %d, %d, 16, %s>" % (a, seg, rs, d) for seg, fixed in ((2, 576), (4, 1088)) for rs in (fixed, 0) for d in ("false", "true")]
     want += ["bf::copies::das_copies_kernel<%d, 1, %d, 16, false>" % (a, rs) for a in (2, 3, 4) for rs in (320, 0)]
     want += ["bf::copies::das_long_kernel<%d, %d, %d>" % (a, seg, rs) for a in (0, 1) for seg, fixed in ((2, 576), (4, 1088)) for rs in (fixed, 0)]
-    want += ["bf::copies::das_hybrid_pair_kernel<%d>" % a for a in (2, 3, 4)] + ["bf::copies::das_pair2_kernel<0>", "bf::copies::das_pair2_kernel<1>"]
+    want += ["bf::copies::das_hybrid_pair_kernel<%d>" % a for a in (2, 3, 4)] + ["bf::copies::das_pair2_kernel<1>"]
     missing = [w for w in want if w not in short]
     assert not missing, missing
     kernels, _ = chk.scan(asm)
@@ -86,11 +87,21 @@ def test_every_launchable_instantiation_is_scanned_and_none_that_pipelines_reads
     pipelined = [w for w in want if "bf::copies::das_pair_kernel" in w or "bf::copies::das_long_kernel" in w or "bf::copies::das_pair2_kernel" in w or
                  "bf::copies::das_hybrid_pair_kernel" in w or
                  (w.startswith("bf::copies::das_copies_kernel<0, 1,") or w.startswith("bf::copies::das_copies_kernel<1, 1,")) and w.endswith("false>")]
-    assert len(pipelined) == 2 + 8 + 2 * 4 + 2 + 3     # (das_kernels.hip refuses to launch any of these from a build that uses scratch)
+    assert len(pipelined) == 1 + 8 + 2 * 4 + 1 + 3     # (das_kernels.hip refuses to launch any of these from a build that uses scratch)
     for w in pipelined:
         m = md[short[w]]
         assert m["spill"] == 0 and m["scratch"] == 0, (w, m)
         assert m["vgprs"] <= 128                        # 16 waves per CU
+
+
+def test_no_instantiation_outside_the_default_plan_is_compiled(chk, asm):
+    """Nothing plan_das cannot choose is compiled: the other algorithm of each pair kernel (das_pair_kernel is pad, das_pair2_kernel
+    lerp), the quad + DPP strided kernel, and the strided kernel for pad / lerp beyond 128 samples (4 / 8 / 16 segments)."""
+    every = chk.demangle(list(chk.metadata(asm)))
+    retired = [n for n in every if n in ("bf::copies::das_pair_kernel<1>", "bf::copies::das_pair2_kernel<0>") or
+               n.startswith("bf::das_mimo_kernel<") and (n.endswith(", true>") or re.match(r"bf::das_mimo_kernel<[01], (4|8|16),", n))]
+    assert not retired, retired
+    assert "bf::das_mimo_kernel<0, 2, 1>" in every and "bf::das_mimo_kernel<2, 4, 1>" in every   # (the names are matched as demangled)
 
 
 def test_hardwired_quads_survive_between_the_two_statements_of_a_mic(chk, asm):
@@ -98,7 +109,7 @@ def test_hardwired_quads_survive_between_the_two_statements_of_a_mic(chk, asm):
     as clobbers, so the compiler may use them in between -- where only the scalar table requests belong.  No instruction in any
     S1 -> S2 gap of the generated code may name one of those registers."""
     pairs, bad = chk.hardwired_gaps(asm)
-    assert pairs >= 2 * 5          # pad and lerp, five mic bodies each (three in the trip loop, two after it)
+    assert pairs >= 2 * 5          # five mic bodies of das_pair2_kernel (three in the trip loop, two after it), the rest das_long_kernel's
     assert not bad, bad[:5]
 
 

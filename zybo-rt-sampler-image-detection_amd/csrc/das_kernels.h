@@ -42,9 +42,6 @@ struct DasLaunch {
     int dir_begin, dir_end;  // shard of the direction grid handled by this launch
     int image_stride, image_origin;
     int frames;
-    int force_layout;        // tests/bench ($BF_LAYOUT): -1 = planner's choice, else 0 / 1 / 2 for pad and lerp at N <= 256
-    int debug;               // profiling / A-B switches ($BF_DEBUG), 0 in production: bit 0 skip the power sum (strided kernel), bit 1 run-time row stride (copies kernel),
-                             // bit 2 8-wave workgroups, bit 3 16-mic chunks, bit 4 one frame per workgroup, bits 8..11 tile size in wave groups
 };
 
 // Plan chosen on the host for a launch (exposed so tests can check LDS sizing without a GPU).
@@ -58,8 +55,7 @@ struct DasPlan {
     int scratch_off; // float offset of the per-wave power scratch in LDS
     int srow;        // scratch row stride in floats (64*nc + 4)
     int pbw;         // scratch rows (finished directions) per wave
-    int quad;        // 1: lane owns 4 consecutive samples (ds_read_b128 + DPP), 0: lane-strided samples (ds_read_b32)
-    int layout;      // 0 strided, 1 quad + DPP, 2 shifted copies (pad / lerp, N <= 256)
+    int layout;      // 0 strided (lane-strided samples), 2 shifted copies (pad / lerp at N > 128, the 8-tap FIR flavours at 128 < N <= 256)
     int dpw;         // directions a wave carries across mic chunks
     int nf;          // frames a workgroup carries (2: das_pair_kernel -- pad / lerp at N <= 256 with the fixed row stride, a multiple of 16 mics and two or more frames)
     int interleaved; // 1: two-frame kernels whose LDS rows hold both frames interleaved sample by sample (das_pair2_kernel, das_hybrid_pair_kernel)

@@ -18,8 +18,8 @@
 //     over the wave's 8 directions and re-read its quad from LDS only when the delay changes from one direction to the
 //     next (two copies, 8-byte reads); the FIR flavours and the direction-outer variant for tables without structure read
 //     at every step (four copies, 16-byte reads).
-//   * copies::das_pair_kernel: the same sweep with TWO frames per workgroup -- batched pad / lerp launches at N <= 256,
-//     what the bench and every multi-frame caller run: the per-step scalar work is shared by both frames.
+//   * copies::das_pair_kernel (pad) / das_pair2_kernel (lerp): the same sweep with TWO frames per workgroup -- batched launches
+//     at N <= 256, what the bench and every multi-frame caller run: the per-step scalar work is shared by both frames.
 // Workgroup id -> (tile, frame): with large tables the tile count is padded to a multiple of 8 so that tile % 8 == id % 8,
 // i.e. all frames' workgroups of one direction tile land on one XCD and re-read that tile's table slice from the XCD's
 // own L2; tables that fit every L2 spread their tiles over all XCDs (plan_das sizes the tiles by the rounds either costs).
@@ -46,7 +46,6 @@ struct KArgs {
     int scratch_off, srow, pbw;           // per-wave power scratch: float offset in LDS, row stride, rows per wave
     int n_is_pow2;
     float inv_n;
-    int debug;   // profiling only (BF_DEBUG): bit 0 = skip the ordered power sum (wrong images)
     int n_frames;   // frames of the launch (das_pair_kernel: whether a workgroup's second frame exists)
     int wg_frames, frame_inner;   // workgroup id -> (tile, frame [pair]): see tile_and_frame()
     long long digest_h_off;   // shifted-copies pad / lerp: where the grouped lerp weights start in the digest buffer (floats)
@@ -296,181 +295,6 @@ __device__ __forceinline__ void accumulate(float (&acc)[NC], const float* lds, c
     }
 }
 
-// ---- "quad" layout for blocks of up to 256 samples (the reference's N_SAMPLES) ------------------------------
-// Lane l owns the four CONSECUTIVE samples 4l .. 4l+3, so one conflict-free ds_read_b128 per (direction, mic)
-// brings all 256 samples of a mic row into the wave: a quarter of the LDS cycles of the strided layout above.
-// A delay p = 4q + r shifts the row by q whole quads (folded into the 16-byte-aligned LDS address) and by r
-// samples inside the quad: those r leading values come from the previous lane's quad through DPP (wave_shr:1,
-// lane 0 receives 0 = the zero prefix), and r is wave-uniform, so the four register alignments are four
-// scalar-branch targets -- no per-lane select.  Mic order and operation order are unchanged.
-__device__ __forceinline__ float lane_prev(float x)
-{
-    // wave_shr:1 (0x138), all rows/banks, bound_ctrl: lane 0 reads 0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, true));
-}
-
-// One (direction, mic) step on a quad, as ONE inline-asm statement: a two-level scalar branch on r = p & 3
-// selects one of four straight-line bodies.  Written in asm because (a) the previous lane's values are consumed
-// through the DPP operand of the instruction that uses them (no v_mov), (b) the accumulators stay in the same
-// four VGPRs on every path (hipcc's structurizer otherwise turns the wave-uniform switch into "flow" blocks
-// with register copies), and (c) the branch is a plain s_cbranch_scc on an SGPR.
-// DPP control: wave_shr:1 = src0 comes from lane-1; bound_ctrl:1 = lane 0 reads 0 (the row's zero prefix).
-// The DPP sources are written by ds_read, not by a VALU instruction, so no VALU->DPP wait states are owed; a
-// v_mov_b32_dpp result is consumed by ordinary (non-DPP) reads, which need none either.
-#define BF_DPP " wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-
-template <int ALGO>
-__device__ __forceinline__ void quad_one(float (&acc)[4], const float4 Q, int p, float h, int lane)
-{
-    int tmp;
-    if constexpr (ALGO == ALGO_PAD) {
-        // out[k] += s[k - p]:   acc[t] += W[4 - r + t],  W = [previous lane's quad | Q]
-        asm volatile(
-            "s_and_b32 %[t], %[p], 3\n\t"
-            "s_cmp_lt_u32 %[t], 2\n\t"
-            "s_cbranch_scc1 .Lbf_lo_%=\n\t"
-            "s_cmp_eq_u32 %[t], 2\n\t"
-            "s_cbranch_scc1 .Lbf_r2_%=\n\t"
-            /* r = 3 */
-            "v_add_f32_dpp %[a0], %[qy], %[a0]" BF_DPP
-            "v_add_f32_dpp %[a1], %[qz], %[a1]" BF_DPP
-            "v_add_f32_dpp %[a2], %[qw], %[a2]" BF_DPP
-            "v_add_f32 %[a3], %[a3], %[qx]\n\t"
-            "s_branch .Lbf_end_%=\n"
-            ".Lbf_r2_%=:\n\t"
-            "v_add_f32_dpp %[a0], %[qz], %[a0]" BF_DPP
-            "v_add_f32_dpp %[a1], %[qw], %[a1]" BF_DPP
-            "v_add_f32 %[a2], %[a2], %[qx]\n\t"
-            "v_add_f32 %[a3], %[a3], %[qy]\n\t"
-            "s_branch .Lbf_end_%=\n"
-            ".Lbf_lo_%=:\n\t"
-            "s_cmp_eq_u32 %[t], 0\n\t"
-            "s_cbranch_scc1 .Lbf_r0_%=\n\t"
-            /* r = 1 */
-            "v_add_f32_dpp %[a0], %[qw], %[a0]" BF_DPP
-            "v_add_f32 %[a1], %[a1], %[qx]\n\t"
-            "v_add_f32 %[a2], %[a2], %[qy]\n\t"
-            "v_add_f32 %[a3], %[a3], %[qz]\n\t"
-            "s_branch .Lbf_end_%=\n"
-            ".Lbf_r0_%=:\n\t"
-            "v_add_f32 %[a0], %[a0], %[qx]\n\t"
-            "v_add_f32 %[a1], %[a1], %[qy]\n\t"
-            "v_add_f32 %[a2], %[a2], %[qz]\n\t"
-            "v_add_f32 %[a3], %[a3], %[qw]\n"
-            ".Lbf_end_%=:"
-            : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [a2] "+v"(acc[2]), [a3] "+v"(acc[3]), [t] "=&s"(tmp)
-            : [p] "s"(p), [qx] "v"(Q.x), [qy] "v"(Q.y), [qz] "v"(Q.z), [qw] "v"(Q.w)
-            : "scc");
-    } else {
-        // out[k] += a + h * (b - a),  a = s[k - p - 1], b = s[k - p];  nothing for k <= p.
-        // With p = 4q + r and W = [previous lane's quad | Q]:  a_t = W[3 - r + t], b_t = W[4 - r + t], always inside W.
-        // With the zero prefix the only sample that would wrongly receive something is k == p (a = 0, b = s[0]):
-        // lane q, element r -- cleared by the v_and with `keep`.
-        // Per element, in the reference's order: d = b - a;  v = fma(h, d, a);  acc += v.
-        const int keep = (lane != (p >> 2)) ? -1 : 0;
-        float w0, w1, w2, w3, t0, t1, t2, t3;
-        asm volatile(
-            "s_and_b32 %[t], %[p], 3\n\t"
-            "s_cmp_lt_u32 %[t], 2\n\t"
-            "s_cbranch_scc1 .Lbf_lo_%=\n\t"
-            "s_cmp_eq_u32 %[t], 2\n\t"
-            "s_cbranch_scc1 .Lbf_r2_%=\n\t"
-            /* r = 3: w = [pQx, pQy, pQz, pQw, Qx] */
-            "v_mov_b32_dpp %[w0], %[qx]" BF_DPP
-            "v_mov_b32_dpp %[w1], %[qy]" BF_DPP
-            "v_mov_b32_dpp %[w2], %[qz]" BF_DPP
-            "v_mov_b32_dpp %[w3], %[qw]" BF_DPP
-            "v_sub_f32 %[t0], %[w1], %[w0]\n\tv_sub_f32 %[t1], %[w2], %[w1]\n\tv_sub_f32 %[t2], %[w3], %[w2]\n\tv_sub_f32 %[t3], %[qx], %[w3]\n\t"
-            "v_fma_f32 %[t0], %[h], %[t0], %[w0]\n\tv_fma_f32 %[t1], %[h], %[t1], %[w1]\n\tv_fma_f32 %[t2], %[h], %[t2], %[w2]\n\tv_fma_f32 %[t3], %[h], %[t3], %[w3]\n\t"
-            "v_and_b32 %[t3], %[t3], %[keep]\n\t"
-            "s_branch .Lbf_end_%=\n"
-            ".Lbf_r2_%=:\n\t"
-            /* r = 2: w = [pQy, pQz, pQw, Qx, Qy] */
-            "v_mov_b32_dpp %[w0], %[qy]" BF_DPP
-            "v_mov_b32_dpp %[w1], %[qz]" BF_DPP
-            "v_mov_b32_dpp %[w2], %[qw]" BF_DPP
-            "v_sub_f32 %[t0], %[w1], %[w0]\n\tv_sub_f32 %[t1], %[w2], %[w1]\n\tv_sub_f32 %[t2], %[qx], %[w2]\n\tv_sub_f32 %[t3], %[qy], %[qx]\n\t"
-            "v_fma_f32 %[t0], %[h], %[t0], %[w0]\n\tv_fma_f32 %[t1], %[h], %[t1], %[w1]\n\tv_fma_f32 %[t2], %[h], %[t2], %[w2]\n\tv_fma_f32 %[t3], %[h], %[t3], %[qx]\n\t"
-            "v_and_b32 %[t2], %[t2], %[keep]\n\t"
-            "s_branch .Lbf_end_%=\n"
-            ".Lbf_lo_%=:\n\t"
-            "s_cmp_eq_u32 %[t], 0\n\t"
-            "s_cbranch_scc1 .Lbf_r0_%=\n\t"
-            /* r = 1: w = [pQz, pQw, Qx, Qy, Qz] */
-            "v_mov_b32_dpp %[w0], %[qz]" BF_DPP
-            "v_mov_b32_dpp %[w1], %[qw]" BF_DPP
-            "v_sub_f32 %[t0], %[w1], %[w0]\n\tv_sub_f32 %[t1], %[qx], %[w1]\n\tv_sub_f32 %[t2], %[qy], %[qx]\n\tv_sub_f32 %[t3], %[qz], %[qy]\n\t"
-            "v_fma_f32 %[t0], %[h], %[t0], %[w0]\n\tv_fma_f32 %[t1], %[h], %[t1], %[w1]\n\tv_fma_f32 %[t2], %[h], %[t2], %[qx]\n\tv_fma_f32 %[t3], %[h], %[t3], %[qy]\n\t"
-            "v_and_b32 %[t1], %[t1], %[keep]\n\t"
-            "s_branch .Lbf_end_%=\n"
-            ".Lbf_r0_%=:\n\t"
-            /* r = 0: w = [pQw, Qx, Qy, Qz, Qw] */
-            "v_mov_b32_dpp %[w0], %[qw]" BF_DPP
-            "v_sub_f32 %[t0], %[qx], %[w0]\n\tv_sub_f32 %[t1], %[qy], %[qx]\n\tv_sub_f32 %[t2], %[qz], %[qy]\n\tv_sub_f32 %[t3], %[qw], %[qz]\n\t"
-            "v_fma_f32 %[t0], %[h], %[t0], %[w0]\n\tv_fma_f32 %[t1], %[h], %[t1], %[qx]\n\tv_fma_f32 %[t2], %[h], %[t2], %[qy]\n\tv_fma_f32 %[t3], %[h], %[t3], %[qz]\n\t"
-            "v_and_b32 %[t0], %[t0], %[keep]\n"
-            ".Lbf_end_%=:\n\t"
-            "v_add_f32 %[a0], %[a0], %[t0]\n\tv_add_f32 %[a1], %[a1], %[t1]\n\tv_add_f32 %[a2], %[a2], %[t2]\n\tv_add_f32 %[a3], %[a3], %[t3]"
-            : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [a2] "+v"(acc[2]), [a3] "+v"(acc[3]), [t] "=&s"(tmp),
-              [w0] "=&v"(w0), [w1] "=&v"(w1), [w2] "=&v"(w2), [w3] "=&v"(w3), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3)
-            : [p] "s"(p), [h] "s"(h), [keep] "v"(keep), [qx] "v"(Q.x), [qy] "v"(Q.y), [qz] "v"(Q.z), [qw] "v"(Q.w)
-            : "scc");
-    }
-}
-
-template <int ALGO>
-__device__ __forceinline__ void accumulate_quad(float (&acc)[4], const float* lds, const KArgs& a, const int32_t* __restrict__ whole,
-                                                const float* __restrict__ frac, size_t row_base, int m0, int mc, int lane,
-                                                const RowHead head = RowHead())
-{
-    static_assert(ALGO == ALGO_PAD || ALGO == ALGO_LERP, "quad layout: pad and lerp");
-    const size_t row = row_base + m0;
-    const int rs = a.row_stride;
-    const int32_t* __restrict__ wrow = whole + row;
-    const float* __restrict__ hrow = frac + row;
-    const float* base = lds + a.lead + 4 * lane;
-    // table rows: one coalesced vector load per 64 mics, entries scalarised with v_readlane (see accumulate())
-    int vp = head.p;
-    float vh = head.h;
-    if (!head.valid) {
-        vp = (lane < mc) ? wrow[lane] : 0;
-        if constexpr (ALGO == ALGO_LERP) vh = (lane < mc) ? hrow[lane] : 0.0f;
-    }
-    for (int b0 = 0; b0 < mc; b0 += kWave) {
-        const int bn = min(kWave, mc - b0);
-        int vp_next = 0;
-        float vh_next = 0.0f;
-        if (b0 + kWave < mc) {
-            vp_next = (b0 + kWave + lane < mc) ? wrow[b0 + kWave + lane] : 0;
-            if constexpr (ALGO == ALGO_LERP) vh_next = (b0 + kWave + lane < mc) ? hrow[b0 + kWave + lane] : 0.0f;
-        }
-        int u = 0;
-        for (; u + 4 <= bn; u += 4) {
-            int p[4];
-            float h[4];
-            float4 Q[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                p[i] = __builtin_amdgcn_readlane(vp, u + i);
-                h[i] = 0.f;
-                if constexpr (ALGO == ALGO_LERP) h[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vh), u + i));
-                Q[i] = *reinterpret_cast<const float4*>(base + (b0 + u + i) * rs - (p[i] & ~3));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) quad_one<ALGO>(acc, Q[i], p[i], h[i], lane);
-        }
-        for (; u < bn; ++u) {
-            const int p = __builtin_amdgcn_readlane(vp, u);
-            float h = 0.f;
-            if constexpr (ALGO == ALGO_LERP) h = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vh), u));
-            const float4 Q = *reinterpret_cast<const float4*>(base + (b0 + u) * rs - (p & ~3));
-            quad_one<ALGO>(acc, Q, p, h, lane);
-        }
-        vp = vp_next;
-        vh = vh_next;
-    }
-}
-
 // ---- mean power, in the reference's summation order ------------------------------------------------------
 // The reference finishes a direction with (pad_and_sum.c:122-131)
 //     for k: out[k] /= n; sum += out[k]^2          (gcc: vdivps, vmulps, then one vaddss per k, in k order)
@@ -479,7 +303,7 @@ __device__ __forceinline__ void accumulate_quad(float (&acc)[4], const float* ld
 // at N = 1024), which is more than the 1e-5 parity bar.  So the squares are summed in k order here too:
 // every wave parks the squares of `pbw` finished directions as rows of a private LDS scratch, then lanes
 // 0..pbw-1 each walk one row front to back (ds_read_b128, four ordered adds per read).
-template <int NC, bool QUAD>
+template <int NC>
 __device__ __forceinline__ void park_squares(const float (&acc)[NC], float* scratch_row, const KArgs& a, int d, int lane)
 {
     float sq[NC];
@@ -489,13 +313,8 @@ __device__ __forceinline__ void park_squares(const float (&acc)[NC], float* scra
         const float o = a.n_is_pow2 ? acc[c] * a.inv_n : acc[c] / (float)a.n_mics;
         sq[c] = o * o;
     }
-    if constexpr (QUAD) {
-        // lane l owns samples 4l..4l+3: one aligned 16-byte store (entries past N are never summed)
-        *reinterpret_cast<float4*>(scratch_row + 4 * lane) = make_float4(sq[0], sq[1], sq[2], sq[3]);
-    } else {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) scratch_row[lane + c * kWave] = sq[c];
-    }
+    for (int c = 0; c < NC; ++c) scratch_row[lane + c * kWave] = sq[c];
     if (lane == 0) scratch_row[a.srow - 4] = __int_as_float(d);   // the pad column carries the direction id
 }
 
@@ -520,7 +339,7 @@ __device__ __forceinline__ void flush_powers(const float* scratch, int filled, f
     }
 }
 
-template <int ALGO, int NC, int DPW, bool QUAD>
+template <int ALGO, int NC, int DPW>
 __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -582,24 +401,14 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
                     const int nm0 = nch * a.mic_chunk;
                     head = request_row_head<ALGO>(whole, frac, (size_t)nd * a.n_mics + nm0, min(a.mic_chunk, a.n_mics - nm0), lane);
                 }
-                if (d < tile_end) {
-                    if constexpr (QUAD) accumulate_quad<ALGO>(acc[j], lds, a, whole, frac, (size_t)d * a.n_mics, m0, mc, lane, cur);
-                    else accumulate<ALGO, NC>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
-                }
+                if (d < tile_end) accumulate<ALGO, NC>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
             }
         }
 #pragma unroll
         for (int j = 0; j < DPW; ++j) {
             const int d = g0 + j * nwaves + wave;
             if (d < tile_end) {
-                if (a.debug & 1) {   // profiling only
-                    float t = 0.f;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) t += acc[j][c];
-                    if (lane == 0) img[d - a.image_origin] = t;
-                    continue;
-                }
-                park_squares<NC, QUAD>(acc[j], scratch + filled * a.srow, a, d, lane);
+                park_squares<NC>(acc[j], scratch + filled * a.srow, a, d, lane);
                 if (++filled == a.pbw) { flush_powers(scratch, filled, img, a, lane); filled = 0; }
             }
         }
@@ -1564,29 +1373,27 @@ __global__ void __launch_bounds__(W * 64, 4) das_copies_kernel(BF_TABLE_PARAMS, 
 
 
 // ==================================================================================================
-// Two frames per workgroup (pad / lerp, N <= 256, fixed row stride, mic count a multiple of 16, two or more frames).
+// Two frames per workgroup (pad, N <= 256, fixed row stride, mic count a multiple of 16, two or more frames; lerp runs
+// das_pair2_kernel below).
 //
-// The sweep above is bound by the number of instructions a SIMD issues, and per (direction, mic) step only 2 (pad) / 4
-// (lerp) of them are arithmetic: the rest -- table loads, the address, the offset tests, waits -- depends on the tables
-// alone.  A wave that carries its eight directions through TWO frames pays that part once per 4 / 8 packed operations.
-// Same layout as das_copies_kernel<.., NSEG = 1, RS = kRs, W = 16> (two shifted copies, difference rows for lerp), with the
-// two frames' rows of a mic next to each other: frame 1's quads sit kFoff bytes after frame 0's, an immediate offset off the
-// same address.  16 mics x 2 frames per chunk; the 64 accumulator registers leave no room for quads in flight across a
-// mic, so a mic's first quads are read (and waited for) in place -- the other three waves of the SIMD cover that.
+// The sweep above is bound by the number of instructions a SIMD issues, and per (direction, mic) step only 2 of them (pad) are
+// arithmetic: the rest -- table loads, the address, the offset tests, waits -- depends on the tables alone.  A wave that
+// carries its eight directions through TWO frames pays that part once per 4 packed operations.
+// Same layout as das_copies_kernel<pad, NSEG = 1, RS = kRs, W = 16> (two shifted copies), with the two frames' rows of a mic
+// next to each other: frame 1's quads sit kFoff bytes after frame 0's, an immediate offset off the same address.  16 mics x 2
+// frames per chunk; the 64 accumulator registers leave no room for quads in flight across a mic, so a mic's first quads are
+// read (and waited for) in place -- the other three waves of the SIMD cover that.
 // Mic order and operation order per frame are those of the one-frame kernel: bit-identical maps.
-template <int ALGO>
 struct PairGeo {
-    static constexpr bool kLerp = ALGO == ALGO_LERP;
-    static constexpr int kA = kLerp ? 2 : 1, kC = 2, kRs = Geo<1>::kRs, kLead = Geo<1>::kLead;
-    static constexpr int kSlot = kA * kC * kRs;          // floats per staged (mic, frame)
+    static constexpr int kC = 2, kRs = Geo<1>::kRs, kLead = Geo<1>::kLead;
+    static constexpr int kSlot = kC * kRs;               // floats per staged (mic, frame)
     static constexpr int kFoff = kSlot * 4;              // bytes from a frame-0 quad to the same quad of frame 1
-    static constexpr int kDoff = kC * kRs * 4;           // bytes from a sample quad to its difference quad
     static constexpr int kMc = 16;                       // mics per LDS image (the digest's slot count) ...
     static constexpr int kHalf = 8;                      // ... swept and re-staged in halves of 8
 };
 
 #define BF_P_ACC(n, j, f) [a##n##0] "+v"(acc[j][f][0]), [a##n##1] "+v"(acc[j][f][1])
-// pad: two direction steps x two frames; a0/a1 = step A frame 0/1, a2/a3 = step B frame 0/1
+// two direction steps x two frames; a0/a1 = step A frame 0/1, a2/a3 = step B frame 0/1
 #define BF_P_PAD_STEP(n0, n1)                                                                             \
     "v_pk_add_f32 %[a" #n0 "0], %[a" #n0 "0], %[s0l]\n\tv_pk_add_f32 %[a" #n0 "1], %[a" #n0 "1], %[s0h]\n\t" \
     "v_pk_add_f32 %[a" #n1 "0], %[a" #n1 "0], %[s1l]\n\tv_pk_add_f32 %[a" #n1 "1], %[a" #n1 "1], %[s1h]\n\t"
@@ -1594,87 +1401,36 @@ struct PairGeo {
     "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"                         \
     "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\t"                 \
     "s_waitcnt lgkmcnt(0)\n\t"
-// lerp: frame 0's products through v[120:123], frame 1's through v[124:127] (clobbers), so that each add is four
-// instructions behind its product
-#define BF_P_LERP_STEP(n0, n1, mods)                                                                      \
-    "v_pk_fma_f32 v[120:121], %[h], %[d0l], %[s0l] " mods "\n\tv_pk_fma_f32 v[122:123], %[h], %[d0h], %[s0h] " mods "\n\t" \
-    "v_pk_fma_f32 v[124:125], %[h], %[d1l], %[s1l] " mods "\n\tv_pk_fma_f32 v[126:127], %[h], %[d1h], %[s1h] " mods "\n\t" \
-    "v_pk_add_f32 %[a" #n0 "0], %[a" #n0 "0], v[120:121]\n\tv_pk_add_f32 %[a" #n0 "1], %[a" #n0 "1], v[122:123]\n\t"         \
-    "v_pk_add_f32 %[a" #n1 "0], %[a" #n1 "0], v[124:125]\n\tv_pk_add_f32 %[a" #n1 "1], %[a" #n1 "1], v[126:127]\n\t"
-#define BF_P_LERP_READ                                                                                    \
-    "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"                         \
-    "ds_read_b64 %[d0l], %[ad] offset:%[g0]\n\tds_read_b64 %[d0h], %[ad] offset:%[g8]\n\t"                 \
-    "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\t"                 \
-    "ds_read_b64 %[d1l], %[ad] offset:%[k0]\n\tds_read_b64 %[d1h], %[ad] offset:%[k8]\n\t"                 \
-    "s_waitcnt lgkmcnt(0)\n\t"
 #define BF_P_ADDR(e) "v_add_u32 %[ad], %[" #e "], %[lb]\n\t"
 #define BF_P_CHECK(n, ep, ec) "s_cmp_lg_u32 %[" #ec "], %[" #ep "]\n\ts_cbranch_scc1 .Lr" #n "_%=\n.Lb" #n "_%=:\n\t"
 #define BF_P_STUB(n, ec, READ) ".Lr" #n "_%=:\n\t" BF_P_ADDR(ec) READ "s_branch .Lb" #n "_%=\n"
 
-// Direction steps 2 Q and 2 Q + 1 of a mic for both frames.  Q = 0 reads the mic's first quads in place (offset eb; ea is
-// unused) before step 0; the others test ea -> eb before their first step; all test eb -> ec before their second.
-template <int ALGO, int Q>
-__device__ __forceinline__ void pair_steps(f32x2 (&acc)[8][2][2], Quad& S0, Quad& D0, Quad& S1, Quad& D1, int ea, int eb, int ec,
-                                           unsigned long long h, int lbase)
+// Direction steps 0 and 1 of a mic for both frames: the mic's first quads are read in place (offset eb) before step 0, step 1
+// tests eb -> ec first.
+__device__ __forceinline__ void pair_pad_first(f32x2 (&acc)[8][2][2], Quad& S0, Quad& S1, int eb, int ec, int lbase)
 {
-    using G = PairGeo<ALGO>;
-    constexpr int JA = 2 * Q, JB = 2 * Q + 1;
+    using G = PairGeo;
     int ad;
-    if constexpr (ALGO == ALGO_PAD) {
-        // pad_and_sum.c:41-47   out[k] += s[k - p]
-        if constexpr (Q == 0) {
-            // (step 0: each frame's adds wait only for that frame's two reads -- LDS returns in order)
-            asm volatile(BF_P_ADDR(eb)
-                         "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"
-                         "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\ts_waitcnt lgkmcnt(2)\n\t"
-                         "v_pk_add_f32 %[a00], %[a00], %[s0l]\n\tv_pk_add_f32 %[a01], %[a01], %[s0h]\n\ts_waitcnt lgkmcnt(0)\n\t"
-                         "v_pk_add_f32 %[a10], %[a10], %[s1l]\n\tv_pk_add_f32 %[a11], %[a11], %[s1h]\n\t"
-                         BF_P_CHECK(1, eb, ec) BF_P_PAD_STEP(2, 3)
-                         ".subsection 1\n" BF_P_STUB(1, ec, BF_P_PAD_READ) "\t.subsection 0"
-                         // (the quads are pure outputs here: as in-out operands they are carried around the mic loop -- and copied at its back-edge)
-                         : BF_P_ACC(0, JA, 0), BF_P_ACC(1, JA, 1), BF_P_ACC(2, JB, 0), BF_P_ACC(3, JB, 1), [s0l] "=&v"(S0.lo), [s0h] "=&v"(S0.hi),
-                           [s1l] "=&v"(S1.lo), [s1h] "=&v"(S1.hi), [ad] "=&v"(ad)
-                         : [eb] "s"(eb), [ec] "s"(ec), [lb] "v"(lbase), [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8) : "scc");
-        } else {
-            asm volatile(BF_P_CHECK(0, ea, eb) BF_P_PAD_STEP(0, 1) BF_P_CHECK(1, eb, ec) BF_P_PAD_STEP(2, 3)
-                         ".subsection 1\n" BF_P_STUB(0, eb, BF_P_PAD_READ) BF_P_STUB(1, ec, BF_P_PAD_READ) "\t.subsection 0"
-                         : BF_P_ACC(0, JA, 0), BF_P_ACC(1, JA, 1), BF_P_ACC(2, JB, 0), BF_P_ACC(3, JB, 1), [s0l] "+v"(S0.lo), [s0h] "+v"(S0.hi),
-                           [s1l] "+v"(S1.lo), [s1h] "+v"(S1.hi), [ad] "=&v"(ad)
-                         : [ea] "s"(ea), [eb] "s"(eb), [ec] "s"(ec), [lb] "v"(lbase), [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8) : "scc");
-        }
-    } else {
-        // lerp_and_sum.c:50-56  out[k] += s[i] + h * (s[i+1] - s[i]),  i = k - p - 1   (gcc contracts it into one fma)
-#define BF_P_LERP_OUTS                                                                                                         \
-        BF_P_ACC(0, JA, 0), BF_P_ACC(1, JA, 1), BF_P_ACC(2, JB, 0), BF_P_ACC(3, JB, 1), [s0l] "+v"(S0.lo), [s0h] "+v"(S0.hi),    \
-        [d0l] "+v"(D0.lo), [d0h] "+v"(D0.hi), [s1l] "+v"(S1.lo), [s1h] "+v"(S1.hi), [d1l] "+v"(D1.lo), [d1h] "+v"(D1.hi), [ad] "=&v"(ad)
-#define BF_P_LERP_IMMS                                                                                                         \
-        [g0] "n"(G::kDoff), [g8] "n"(G::kDoff + 8), [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8), [k0] "n"(G::kFoff + G::kDoff),   \
-        [k8] "n"(G::kFoff + G::kDoff + 8)
-        if constexpr (Q == 0) {
-            asm volatile(BF_P_ADDR(eb) BF_P_LERP_READ BF_P_LERP_STEP(0, 1, "op_sel_hi:[0,1,1]") BF_P_CHECK(1, eb, ec)
-                         BF_P_LERP_STEP(2, 3, "op_sel:[1,0,0] op_sel_hi:[1,1,1]")
-                         ".subsection 1\n" BF_P_STUB(1, ec, BF_P_LERP_READ) "\t.subsection 0"
-                         : BF_P_LERP_OUTS
-                         : [eb] "s"(eb), [ec] "s"(ec), [h] "s"(h), [lb] "v"(lbase), BF_P_LERP_IMMS
-                         : "scc", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
-        } else {
-            asm volatile(BF_P_CHECK(0, ea, eb) BF_P_LERP_STEP(0, 1, "op_sel_hi:[0,1,1]") BF_P_CHECK(1, eb, ec)
-                         BF_P_LERP_STEP(2, 3, "op_sel:[1,0,0] op_sel_hi:[1,1,1]")
-                         ".subsection 1\n" BF_P_STUB(0, eb, BF_P_LERP_READ) BF_P_STUB(1, ec, BF_P_LERP_READ) "\t.subsection 0"
-                         : BF_P_LERP_OUTS
-                         : [ea] "s"(ea), [eb] "s"(eb), [ec] "s"(ec), [h] "s"(h), [lb] "v"(lbase), BF_P_LERP_IMMS
-                         : "scc", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
-        }
-#undef BF_P_LERP_OUTS
-#undef BF_P_LERP_IMMS
-    }
+    // pad_and_sum.c:41-47   out[k] += s[k - p]
+    // (step 0: each frame's adds wait only for that frame's two reads -- LDS returns in order)
+    asm volatile(BF_P_ADDR(eb)
+                 "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"
+                 "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\ts_waitcnt lgkmcnt(2)\n\t"
+                 "v_pk_add_f32 %[a00], %[a00], %[s0l]\n\tv_pk_add_f32 %[a01], %[a01], %[s0h]\n\ts_waitcnt lgkmcnt(0)\n\t"
+                 "v_pk_add_f32 %[a10], %[a10], %[s1l]\n\tv_pk_add_f32 %[a11], %[a11], %[s1h]\n\t"
+                 BF_P_CHECK(1, eb, ec) BF_P_PAD_STEP(2, 3)
+                 ".subsection 1\n" BF_P_STUB(1, ec, BF_P_PAD_READ) "\t.subsection 0"
+                 // (the quads are pure outputs here: as in-out operands they are carried around the mic loop -- and copied at its back-edge)
+                 : BF_P_ACC(0, 0, 0), BF_P_ACC(1, 0, 1), BF_P_ACC(2, 1, 0), BF_P_ACC(3, 1, 1), [s0l] "=&v"(S0.lo), [s0h] "=&v"(S0.hi),
+                   [s1l] "=&v"(S1.lo), [s1h] "=&v"(S1.hi), [ad] "=&v"(ad)
+                 : [eb] "s"(eb), [ec] "s"(ec), [lb] "v"(lbase), [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8) : "scc");
 }
 
 // pad, direction steps 2..7 of a mic for both frames as ONE statement (between two statements the hazard recogniser puts an s_nop:
 // three issue slots per mic with one statement per pair of steps).
 __device__ __forceinline__ void pair_pad_rest(f32x2 (&acc)[8][2][2], Quad& S0, Quad& S1, const int (&e)[8], int lbase)
 {
-    using G = PairGeo<ALGO_PAD>;
+    using G = PairGeo;
     int ad;
 #define BF_P_ACC2(n, j) [a##n##0] "+v"(acc[j][0][0]), [a##n##1] "+v"(acc[j][0][1]), [b##n##0] "+v"(acc[j][1][0]), [b##n##1] "+v"(acc[j][1][1])
 #define BF_P_PAD1(n) "v_pk_add_f32 %[a" #n "0], %[a" #n "0], %[s0l]\n\tv_pk_add_f32 %[a" #n "1], %[a" #n "1], %[s0h]\n\t" \
@@ -1708,12 +1464,12 @@ __device__ unsigned long long g_stamps[64 * 16];         // (sums over all waves
 #define BF_STAMP_FLUSH
 #endif
 
-template <int ALGO>
+template <int ALGO>   // (pad only: the parameter keeps the kernel's symbol, which the profiles and ISA checks name)
 __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArgs a)
 {
-    using G = PairGeo<ALGO>;
-    constexpr bool kLerp = G::kLerp;
-    constexpr int A = G::kA, C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
+    static_assert(ALGO == ALGO_PAD, "das_pair_kernel: pad (lerp runs das_pair2_kernel)");
+    using G = PairGeo;
+    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1749,20 +1505,14 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
     };
     auto stage = [&](int h, const float4 v, bool wipe) {
         float* row0 = lds + (((h & 1) * W) + wave) * G::kSlot;  // slot (h & 1) * 8 + (wave >> 1), frame wave & 1
-        const float py = dpp_prev(v.y), pz = dpp_prev(v.z), pw = dpp_prev(v.w), nx = dpp_next(v.x);
+        const float py = dpp_prev(v.y), pz = dpp_prev(v.z), pw = dpp_prev(v.w);
         write_copies<C>(row0, RS, LEAD, lane, v, py, pz, pw);
-        if constexpr (kLerp) {
-            // D[i] = s[i+1] - s[i], the reference's own subtraction (lerp_and_sum.c:54); D[-1] stays 0 (prefix)
-            const float4 dq = make_float4(v.y - v.x, v.z - v.y, v.w - v.z, nx - v.w);
-            const float dy = dpp_prev(dq.y), dz = dpp_prev(dq.z), dw = dpp_prev(dq.w);
-            write_copies<C>(row0 + C * RS, RS, LEAD, lane, dq, dy, dz, dw);
-        }
         if (wipe) {
             // the zero prefix: nothing but the parked rows of the power pass ever overwrites it, so only a group's first
-            // visit of a half restores it -- one store: lane -> (copy row lane / 14, quad lane % 14) of the C * A rows
-            static_assert((LEAD >> 2) * C * A <= kWave, "one lane per prefix quad");
+            // visit of a half restores it -- one store: lane -> (copy row lane / 14, quad lane % 14) of the C rows
+            static_assert((LEAD >> 2) * C <= kWave, "one lane per prefix quad");
             constexpr int PQ = LEAD >> 2;
-            if (lane < PQ * C * A) reinterpret_cast<float4*>(row0 + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (lane < PQ * C) reinterpret_cast<float4*>(row0 + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
 
@@ -1798,42 +1548,30 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
             if (dw0 < tile_end) {
                 const size_t grp = (size_t)(dw0 - a.dir_begin) / DW;
                 const int32_t* __restrict__ et = dig + (grp * M + (size_t)h * HC) * DW;
-                const float* __restrict__ ht = reinterpret_cast<const float*>(dig) + a.digest_h_off + (grp * M + (size_t)h * HC) * DW;
-                struct Entries { int e[DW]; unsigned long long hp[DW / 2]; };
+                struct Entries { int e[DW]; };
                 auto request = [&](Entries& t, int m) {
                     // (reads past the half's last mic stay inside the slack-padded table and are dropped)
 #pragma unroll
                     for (int j = 0; j < DW; ++j) t.e[j] = et[m * DW + j];
-#pragma unroll
-                    for (int j = 0; j < DW / 2; ++j) {
-                        t.hp[j] = 0;
-                        if constexpr (kLerp) t.hp[j] = *reinterpret_cast<const unsigned long long*>(ht + m * DW + 2 * j);
-                    }
                 };
                 Entries E[3];
-                Quad S0, D0, S1, D1;
-                S0.lo = S0.hi = D0.lo = D0.hi = S1.lo = S1.hi = D1.lo = D1.hi = f32x2{0.0f, 0.0f};
+                Quad S0, S1;
+                S0.lo = S0.hi = S1.lo = S1.hi = f32x2{0.0f, 0.0f};
                 request(E[0], 0);
                 request(E[1], 1);
                 auto mic = [&](int m, auto kc) {
                     constexpr int K = decltype(kc)::value, K2 = (K + 2) % 3;
                     const Entries& cur = E[K];
-                    pair_steps<ALGO, 0>(acc, S0, D0, S1, D1, cur.e[0], cur.e[0], cur.e[1], cur.hp[0], lb);
+                    pair_pad_first(acc, S0, S1, cur.e[0], cur.e[1], lb);
                     request(E[K2], m + 2);      // after the first statement's wait, so that it does not sit on these loads
-                    if constexpr (ALGO == ALGO_PAD) {
-                        pair_pad_rest(acc, S0, S1, cur.e, lb);
-                        return;
-                    }
-                    pair_steps<ALGO, 1>(acc, S0, D0, S1, D1, cur.e[1], cur.e[2], cur.e[3], cur.hp[1], lb);
-                    pair_steps<ALGO, 2>(acc, S0, D0, S1, D1, cur.e[3], cur.e[4], cur.e[5], cur.hp[2], lb);
-                    pair_steps<ALGO, 3>(acc, S0, D0, S1, D1, cur.e[5], cur.e[6], cur.e[7], cur.hp[3], lb);
+                    pair_pad_rest(acc, S0, S1, cur.e, lb);
                 };
                 using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
                 static_assert(HC == 8, "eight mics: two trips of three and two more");
 #pragma unroll 1
                 for (int t = 0; t < 2; ++t) {
                     mic(0, I0{}); mic(1, I1{}); mic(2, I2{});
-                    et += 3 * DW; ht += 3 * DW;
+                    et += 3 * DW;
                 }
                 mic(0, I0{});
                 mic(1, I1{});
@@ -1896,56 +1634,45 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
 #undef BF_P_ACC
 #undef BF_P_PAD_STEP
 #undef BF_P_PAD_READ
-#undef BF_P_LERP_STEP
-#undef BF_P_LERP_READ
 #undef BF_P_ADDR
 #undef BF_P_CHECK
 #undef BF_P_STUB
 
 // ==================================================================================================
-// Two frames per workgroup, frames INTERLEAVED sample by sample in the LDS rows (pad / lerp, N <= 256; das_pair_kernel's successor).
+// Two frames per workgroup, frames INTERLEAVED sample by sample in the LDS rows (lerp, N <= 256; das_pair_kernel's successor).
 //
 // Every instruction costs a SIMD a quad-cycle, so what is left to gain on the sweep is instruction count.  With the
 // row of a mic holding (f0 s0, f1 s0, f0 s1, f1 s1, ..):
-//   * one ds_read_b128 brings two samples of BOTH frames: a (re)load is 2 (pad) / 4 (lerp) LDS instructions instead of 4 / 8, and
-//     with lane l owning the sample pairs (2l, 2l+1) and (128+2l, 128+2l+1) every read covers 1 KiB of contiguous LDS (no bank
-//     conflicts; the 16-byte lane stride of ds_read_b64 pairs was a two-way conflict on every read);
-//   * a register pair is (frame 0, frame 1) of one sample, so the packed operations are the same 4 (pad) / 8 (lerp) per
-//     direction step, the lerp weight still one scalar operand for both lanes;
+//   * one ds_read_b128 brings two samples of BOTH frames: a (re)load is 4 LDS instructions instead of 8, and with lane l owning
+//     the sample pairs (2l, 2l+1) and (128+2l, 128+2l+1) every read covers 1 KiB of contiguous LDS (no bank conflicts; the
+//     16-byte lane stride of ds_read_b64 pairs was a two-way conflict on every read);
+//   * a register pair is (frame 0, frame 1) of one sample, so the packed operations are the same 8 per direction step, the
+//     lerp weight still one scalar operand for both lanes;
 //   * the quads live in HARD-WIRED registers v[96:111] (+ products v[112:119], address v120), named as clobbers: 16-byte reads
 //     need 4-register tuples whose halves the packed operations address, which inline-asm operands cannot express.  A mic is
 //     two statements -- S1: address, reads, wait, step 0;  S2: steps 1..7 with their tests and out-of-line re-reads -- and the
 //     quads must survive from S1 to S2 across the table requests the compiler places between them (scalar instructions only;
 //     tests/test_isa_hazards.py checks that nothing between the two markers touches a vector register).
 // Halves of 8 mics staged under the sweep, power pass, digest: as das_pair_kernel (digest offsets scaled for the 2-float samples).
-template <int ALGO>
+// (pad, which reads half as much to begin with, measured 2 % slower on interleaved rows: it runs das_pair_kernel)
 struct Pair2Geo {
-    static constexpr bool kLerp = ALGO == ALGO_LERP;
-    static constexpr int kA = kLerp ? 2 : 1, kC = 2, kLead = Geo<1>::kLead, kRs = 2 * Geo<1>::kRs, kMc = 16, kHalf = 8;
-    static constexpr int kSlot = kA * kC * kRs;          // floats per staged mic (both frames)
+    static constexpr int kC = 2, kLead = Geo<1>::kLead, kRs = 2 * Geo<1>::kRs, kMc = 16, kHalf = 8;
+    static constexpr int kSlot = 2 * kC * kRs;           // floats per staged mic (both frames): samples and differences
     static constexpr int kDoff = kC * kRs * 4;           // bytes from a sample quad to its difference quad
 };
 
 #define BF_I_ACC(n, j) [a##n##0] "+v"(acc[j][0]), [a##n##1] "+v"(acc[j][1]), [a##n##2] "+v"(acc[j][2]), [a##n##3] "+v"(acc[j][3])
-#define BF_I_READ_PAD "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[100:103], v120 offset:1024\n\ts_waitcnt lgkmcnt(0)\n\t"
-#define BF_I_READ_LERP                                                                              \
+#define BF_I_READ                                                                                   \
     "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[100:103], v120 offset:1024\n\t"                   \
     "ds_read_b128 v[104:107], v120 offset:%[g0]\n\tds_read_b128 v[108:111], v120 offset:%[g1]\n\ts_waitcnt lgkmcnt(0)\n\t"
-#define BF_I_PAD_STEP(n)                                                                            \
-    "v_pk_add_f32 %[a" #n "0], %[a" #n "0], v[96:97]\n\tv_pk_add_f32 %[a" #n "1], %[a" #n "1], v[98:99]\n\t" \
-    "v_pk_add_f32 %[a" #n "2], %[a" #n "2], v[100:101]\n\tv_pk_add_f32 %[a" #n "3], %[a" #n "3], v[102:103]\n\t"
-#define BF_I_LERP_STEP(n, h, mods)                                                                  \
+#define BF_I_STEP(n, h, mods)                                                                       \
     "v_pk_fma_f32 v[112:113], %[" #h "], v[104:105], v[96:97] " mods "\n\tv_pk_fma_f32 v[114:115], %[" #h "], v[106:107], v[98:99] " mods "\n\t" \
     "v_pk_fma_f32 v[116:117], %[" #h "], v[108:109], v[100:101] " mods "\n\tv_pk_fma_f32 v[118:119], %[" #h "], v[110:111], v[102:103] " mods "\n\t" \
     "v_pk_add_f32 %[a" #n "0], %[a" #n "0], v[112:113]\n\tv_pk_add_f32 %[a" #n "1], %[a" #n "1], v[114:115]\n\t" \
     "v_pk_add_f32 %[a" #n "2], %[a" #n "2], v[116:117]\n\tv_pk_add_f32 %[a" #n "3], %[a" #n "3], v[118:119]\n\t"
 // A mic's first reads with direction step 0 behind them, each half of the step waiting only for its own reads (LDS returns in order;
 // a counted wait bounds the outstanding operations of any kind, hence the outstanding reads).
-#define BF_I_FIRST_PAD                                                                              \
-    "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[100:103], v120 offset:1024\n\ts_waitcnt lgkmcnt(1)\n\t"  \
-    "v_pk_add_f32 %[a00], %[a00], v[96:97]\n\tv_pk_add_f32 %[a01], %[a01], v[98:99]\n\ts_waitcnt lgkmcnt(0)\n\t" \
-    "v_pk_add_f32 %[a02], %[a02], v[100:101]\n\tv_pk_add_f32 %[a03], %[a03], v[102:103]\n\t"
-#define BF_I_FIRST_LERP(h, mods)                                                                    \
+#define BF_I_FIRST(h, mods)                                                                         \
     "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[104:107], v120 offset:%[g0]\n\t"                \
     "ds_read_b128 v[100:103], v120 offset:1024\n\tds_read_b128 v[108:111], v120 offset:%[g1]\n\ts_waitcnt lgkmcnt(2)\n\t" \
     "v_pk_fma_f32 v[112:113], %[" #h "], v[104:105], v[96:97] " mods "\n\tv_pk_fma_f32 v[114:115], %[" #h "], v[106:107], v[98:99] " mods "\n\t" \
@@ -1955,76 +1682,50 @@ struct Pair2Geo {
 #define BF_I_EVEN "op_sel_hi:[0,1,1]"
 #define BF_I_ODD "op_sel:[1,0,0] op_sel_hi:[1,1,1]"
 #define BF_I_CHECK(n, ep, ec) "s_cmp_lg_u32 %[" #ec "], %[" #ep "]\n\ts_cbranch_scc1 .Lr" #n "_%=\n.Lb" #n "_%=:\n\t"
-#define BF_I_STUB(n, ec, READ) ".Lr" #n "_%=:\n\tv_add_u32 v120, %[" #ec "], %[lb]\n\t" READ "s_branch .Lb" #n "_%=\n"
+#define BF_I_STUB(n, ec) ".Lr" #n "_%=:\n\tv_add_u32 v120, %[" #ec "], %[lb]\n\t" BF_I_READ "s_branch .Lb" #n "_%=\n"
 #define BF_I_CLOB "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", \
                   "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120"
 
 // S1: a mic's first quads, read in place, and direction step 0
-template <int ALGO>
+// lerp_and_sum.c:50-56  out[k] += s[i] + h * (s[i+1] - s[i]),  i = k - p - 1   (gcc contracts it into one fma)
 __device__ __forceinline__ void pair2_first(f32x2 (&acc)[8][4], int e0, unsigned long long h01, int lbase)
 {
-    using G = Pair2Geo<ALGO>;
-    if constexpr (ALGO == ALGO_PAD) {
-        // pad_and_sum.c:41-47   out[k] += s[k - p]
-        asm volatile("v_add_u32 v120, %[e0], %[lb]\n\t" BF_I_FIRST_PAD ";BF_S1_END"
-                     : BF_I_ACC(0, 0) : [e0] "s"(e0), [lb] "v"(lbase) : BF_I_CLOB);
-    } else {
-        // lerp_and_sum.c:50-56  out[k] += s[i] + h * (s[i+1] - s[i]),  i = k - p - 1   (gcc contracts it into one fma)
-        asm volatile("v_add_u32 v120, %[e0], %[lb]\n\t" BF_I_FIRST_LERP(h01, BF_I_EVEN) ";BF_S1_END"
-                     : BF_I_ACC(0, 0) : [e0] "s"(e0), [h01] "s"(h01), [lb] "v"(lbase), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024) : BF_I_CLOB);
-    }
+    using G = Pair2Geo;
+    asm volatile("v_add_u32 v120, %[e0], %[lb]\n\t" BF_I_FIRST(h01, BF_I_EVEN) ";BF_S1_END"
+                 : BF_I_ACC(0, 0) : [e0] "s"(e0), [h01] "s"(h01), [lb] "v"(lbase), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024) : BF_I_CLOB);
 }
 // S2: direction steps 1..7, each behind the test of its LDS offset against the previous step's
-template <int ALGO>
 __device__ __forceinline__ void pair2_rest(f32x2 (&acc)[8][4], const int (&e)[8], const unsigned long long (&hp)[4], int lbase)
 {
-    using G = Pair2Geo<ALGO>;
-#define BF_I_S2_ACCS BF_I_ACC(1, 1), BF_I_ACC(2, 2), BF_I_ACC(3, 3), BF_I_ACC(4, 4), BF_I_ACC(5, 5), BF_I_ACC(6, 6), BF_I_ACC(7, 7)
-#define BF_I_S2_E [e0] "s"(e[0]), [e1] "s"(e[1]), [e2] "s"(e[2]), [e3] "s"(e[3]), [e4] "s"(e[4]), [e5] "s"(e[5]), [e6] "s"(e[6]), [e7] "s"(e[7]), [lb] "v"(lbase)
-    if constexpr (ALGO == ALGO_PAD) {
-        asm volatile(";BF_S2_BEGIN\n\t"
-                     BF_I_CHECK(1, e0, e1) BF_I_PAD_STEP(1) BF_I_CHECK(2, e1, e2) BF_I_PAD_STEP(2) BF_I_CHECK(3, e2, e3) BF_I_PAD_STEP(3)
-                     BF_I_CHECK(4, e3, e4) BF_I_PAD_STEP(4) BF_I_CHECK(5, e4, e5) BF_I_PAD_STEP(5) BF_I_CHECK(6, e5, e6) BF_I_PAD_STEP(6)
-                     BF_I_CHECK(7, e6, e7) BF_I_PAD_STEP(7)
-                     ".subsection 1\n" BF_I_STUB(1, e1, BF_I_READ_PAD) BF_I_STUB(2, e2, BF_I_READ_PAD) BF_I_STUB(3, e3, BF_I_READ_PAD)
-                     BF_I_STUB(4, e4, BF_I_READ_PAD) BF_I_STUB(5, e5, BF_I_READ_PAD) BF_I_STUB(6, e6, BF_I_READ_PAD) BF_I_STUB(7, e7, BF_I_READ_PAD)
-                     "\t.subsection 0"
-                     : BF_I_S2_ACCS : BF_I_S2_E : "scc", BF_I_CLOB);
-    } else {
-        asm volatile(";BF_S2_BEGIN\n\t"
-                     BF_I_CHECK(1, e0, e1) BF_I_LERP_STEP(1, h01, BF_I_ODD) BF_I_CHECK(2, e1, e2) BF_I_LERP_STEP(2, h23, BF_I_EVEN)
-                     BF_I_CHECK(3, e2, e3) BF_I_LERP_STEP(3, h23, BF_I_ODD) BF_I_CHECK(4, e3, e4) BF_I_LERP_STEP(4, h45, BF_I_EVEN)
-                     BF_I_CHECK(5, e4, e5) BF_I_LERP_STEP(5, h45, BF_I_ODD) BF_I_CHECK(6, e5, e6) BF_I_LERP_STEP(6, h67, BF_I_EVEN)
-                     BF_I_CHECK(7, e6, e7) BF_I_LERP_STEP(7, h67, BF_I_ODD)
-                     ".subsection 1\n" BF_I_STUB(1, e1, BF_I_READ_LERP) BF_I_STUB(2, e2, BF_I_READ_LERP) BF_I_STUB(3, e3, BF_I_READ_LERP)
-                     BF_I_STUB(4, e4, BF_I_READ_LERP) BF_I_STUB(5, e5, BF_I_READ_LERP) BF_I_STUB(6, e6, BF_I_READ_LERP) BF_I_STUB(7, e7, BF_I_READ_LERP)
-                     "\t.subsection 0"
-                     : BF_I_S2_ACCS
-                     : BF_I_S2_E, [h01] "s"(hp[0]), [h23] "s"(hp[1]), [h45] "s"(hp[2]), [h67] "s"(hp[3]), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024)
-                     : "scc", BF_I_CLOB);
-    }
-#undef BF_I_S2_ACCS
-#undef BF_I_S2_E
+    using G = Pair2Geo;
+    asm volatile(";BF_S2_BEGIN\n\t"
+                 BF_I_CHECK(1, e0, e1) BF_I_STEP(1, h01, BF_I_ODD) BF_I_CHECK(2, e1, e2) BF_I_STEP(2, h23, BF_I_EVEN)
+                 BF_I_CHECK(3, e2, e3) BF_I_STEP(3, h23, BF_I_ODD) BF_I_CHECK(4, e3, e4) BF_I_STEP(4, h45, BF_I_EVEN)
+                 BF_I_CHECK(5, e4, e5) BF_I_STEP(5, h45, BF_I_ODD) BF_I_CHECK(6, e5, e6) BF_I_STEP(6, h67, BF_I_EVEN)
+                 BF_I_CHECK(7, e6, e7) BF_I_STEP(7, h67, BF_I_ODD)
+                 ".subsection 1\n" BF_I_STUB(1, e1) BF_I_STUB(2, e2) BF_I_STUB(3, e3) BF_I_STUB(4, e4) BF_I_STUB(5, e5) BF_I_STUB(6, e6) BF_I_STUB(7, e7)
+                 "\t.subsection 0"
+                 : BF_I_ACC(1, 1), BF_I_ACC(2, 2), BF_I_ACC(3, 3), BF_I_ACC(4, 4), BF_I_ACC(5, 5), BF_I_ACC(6, 6), BF_I_ACC(7, 7)
+                 : [e0] "s"(e[0]), [e1] "s"(e[1]), [e2] "s"(e[2]), [e3] "s"(e[3]), [e4] "s"(e[4]), [e5] "s"(e[5]), [e6] "s"(e[6]), [e7] "s"(e[7]), [lb] "v"(lbase),
+                   [h01] "s"(hp[0]), [h23] "s"(hp[1]), [h45] "s"(hp[2]), [h67] "s"(hp[3]), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024)
+                 : "scc", BF_I_CLOB);
 }
 #undef BF_I_ACC
-#undef BF_I_READ_PAD
-#undef BF_I_FIRST_PAD
-#undef BF_I_FIRST_LERP
-#undef BF_I_READ_LERP
-#undef BF_I_PAD_STEP
-#undef BF_I_LERP_STEP
+#undef BF_I_READ
+#undef BF_I_FIRST
+#undef BF_I_STEP
 #undef BF_I_EVEN
 #undef BF_I_ODD
 #undef BF_I_CHECK
 #undef BF_I_STUB
 #undef BF_I_CLOB
 
-template <int ALGO>
+template <int ALGO>   // (lerp only: the parameter keeps the kernel's symbol, which the profiles and ISA checks name)
 __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KArgs a)
 {
-    using G = Pair2Geo<ALGO>;
-    constexpr bool kLerp = G::kLerp;
-    constexpr int A = G::kA, C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
+    static_assert(ALGO == ALGO_LERP, "das_pair2_kernel: lerp (pad runs das_pair_kernel)");
+    using G = Pair2Geo;
+    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane_ = threadIdx.x & (kWave - 1), lane = lane_;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -2044,8 +1745,8 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
     float* __restrict__ img1 = images + (size_t)f1 * a.image_stride;
     const int32_t* __restrict__ dig = reinterpret_cast<const int32_t*>(taps);   // the digest rides in the unused `taps` slot
 
-    // Staging: waves w and w + 8 share mic (w & 7) of every half (both fetch its two frames): part 0 writes the sample rows
-    // (lerp) / copy 0 (pad), part 1 the difference rows (lerp) / copy 1 (pad).  Lane c holds half c's mic id (first 64 halves).
+    // Staging: waves w and w + 8 share mic (w & 7) of every half (both fetch its two frames): part 0 writes the sample rows, part 1
+    // the difference rows.  Lane c holds half c's mic id (first 64 halves).
     const int my_mic = wave & 7, part = wave >> 3;
     const int vmic = (lane < n_half) ? mics[lane * HC + my_mic] : 0;
     struct Staged2 { float4 v0, v1; };
@@ -2055,24 +1756,19 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
         st.v0 = make_float4(0.f, 0.f, 0.f, 0.f);
         st.v1 = st.v0;
         if (4 * lane < N) {
-            if constexpr (kLerp) {
-                // scalar row base + one 32-bit lane offset (global_load saddr form): the per-lane 64-bit pointers of the two frames, hoisted out
-                // of the group loop, used to be spilled around the sweep (16 bytes of scratch per lane, stored once per workgroup and
-                // reloaded per group: WRITE_SIZE 5x the image bytes)
-                unsigned voff = 16u * (unsigned)lane;
-                asm volatile("" : "+v"(voff));                  // (opaque: or hipcc folds it back into two hoisted 64-bit lane pointers)
-                const char* r0 = reinterpret_cast<const char*>(sig0 + (size_t)mic * N);
-                const char* r1 = reinterpret_cast<const char*>(sig1 + (size_t)mic * N);
-                st.v0 = *reinterpret_cast<const float4*>(r0 + voff);
-                st.v1 = *reinterpret_cast<const float4*>(r1 + voff);
-            } else {
-                st.v0 = *reinterpret_cast<const float4*>(sig0 + (size_t)mic * N + 4 * lane);
-                st.v1 = *reinterpret_cast<const float4*>(sig1 + (size_t)mic * N + 4 * lane);
-            }
+            // scalar row base + one 32-bit lane offset (global_load saddr form): the per-lane 64-bit pointers of the two frames, hoisted out
+            // of the group loop, used to be spilled around the sweep (16 bytes of scratch per lane, stored once per workgroup and
+            // reloaded per group: WRITE_SIZE 5x the image bytes)
+            unsigned voff = 16u * (unsigned)lane;
+            asm volatile("" : "+v"(voff));                      // (opaque: or hipcc folds it back into two hoisted 64-bit lane pointers)
+            const char* r0 = reinterpret_cast<const char*>(sig0 + (size_t)mic * N);
+            const char* r1 = reinterpret_cast<const char*>(sig1 + (size_t)mic * N);
+            st.v0 = *reinterpret_cast<const float4*>(r0 + voff);
+            st.v1 = *reinterpret_cast<const float4*>(r1 + voff);
         }
         return st;
     };
-    // rows of a mic: [s copy 0][s copy 1] ([d copy 0][d copy 1]); copy c holds sample i - c at position i; position i = floats 2 i, 2 i + 1
+    // rows of a mic: [s copy 0][s copy 1][d copy 0][d copy 1]; copy c holds sample i - c at position i; position i = floats 2 i, 2 i + 1
     auto write_row = [&](float* row, const float4 x0, const float4 x1, float p0, float p1, bool shifted, int lane) {
         float4* q = reinterpret_cast<float4*>(row + 2 * LEAD) + 2 * lane;
         if (!shifted) {
@@ -2088,36 +1784,21 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
         asm volatile("" : "+v"(lane));
         float* slot = lds + ((h & 1) * HC + my_mic) * G::kSlot;
         float4 x0 = st.v0, x1 = st.v1;
-        float* rows;                                            // the two rows this wave writes
-        bool both_copies = true;
-        if constexpr (kLerp) {
-            rows = slot + part * C * RS;
-            if (part == 1) {
-                // D[i] = s[i+1] - s[i], the reference's own subtraction (lerp_and_sum.c:54); D[-1] stays 0 (prefix)
-                const float n0 = dpp_next(x0.x), n1 = dpp_next(x1.x);
-                x0 = make_float4(x0.y - x0.x, x0.z - x0.y, x0.w - x0.z, n0 - x0.w);
-                x1 = make_float4(x1.y - x1.x, x1.z - x1.y, x1.w - x1.z, n1 - x1.w);
-            }
-        } else {
-            rows = slot + part * RS;                            // pad: one copy per wave
-            both_copies = false;
+        float* rows = slot + part * C * RS;                     // the two rows this wave writes
+        if (part == 1) {
+            // D[i] = s[i+1] - s[i], the reference's own subtraction (lerp_and_sum.c:54); D[-1] stays 0 (prefix)
+            const float n0 = dpp_next(x0.x), n1 = dpp_next(x1.x);
+            x0 = make_float4(x0.y - x0.x, x0.z - x0.y, x0.w - x0.z, n0 - x0.w);
+            x1 = make_float4(x1.y - x1.x, x1.z - x1.y, x1.w - x1.z, n1 - x1.w);
         }
         const float p0 = dpp_prev(x0.w), p1 = dpp_prev(x1.w);   // the previous lane's last sample (0 in lane 0: the prefix)
-        if (both_copies) {
-            write_row(rows, x0, x1, p0, p1, false, lane);
-            write_row(rows + RS, x0, x1, p0, p1, true, lane);
-        } else {
-            write_row(rows, x0, x1, p0, p1, part == 1, lane);
-        }
+        write_row(rows, x0, x1, p0, p1, false, lane);
+        write_row(rows + RS, x0, x1, p0, p1, true, lane);
         if (wipe) {
             // the zero prefix (56 samples x 2 frames = 28 quads per row): only the parked rows of the power pass overwrite it
             constexpr int PQ = LEAD >> 1;
             static_assert(2 * PQ <= kWave, "one lane per prefix quad of two rows");
-            if (both_copies) {
-                if (lane < 2 * PQ) reinterpret_cast<float4*>(rows + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                if (lane < PQ) reinterpret_cast<float4*>(rows)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+            if (lane < 2 * PQ) reinterpret_cast<float4*>(rows + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
 
@@ -2160,10 +1841,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
 #pragma unroll
                     for (int j = 0; j < DW; ++j) t.e[j] = et[m * DW + j];
 #pragma unroll
-                    for (int j = 0; j < DW / 2; ++j) {
-                        t.hp[j] = 0;
-                        if constexpr (kLerp) t.hp[j] = *reinterpret_cast<const unsigned long long*>(ht + m * DW + 2 * j);
-                    }
+                    for (int j = 0; j < DW / 2; ++j) t.hp[j] = *reinterpret_cast<const unsigned long long*>(ht + m * DW + 2 * j);
                 };
                 Entries E[3];
                 request(E[0], 0);
@@ -2171,9 +1849,9 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
                 auto mic = [&](int m, auto kc) {
                     constexpr int K = decltype(kc)::value, K2 = (K + 2) % 3;
                     const Entries& cur = E[K];
-                    pair2_first<ALGO>(acc, cur.e[0], cur.hp[0], lb);
+                    pair2_first(acc, cur.e[0], cur.hp[0], lb);
                     request(E[K2], m + 2);      // after the first statement's wait, so that it does not sit on these loads
-                    pair2_rest<ALGO>(acc, cur.e, cur.hp, lb);
+                    pair2_rest(acc, cur.e, cur.hp, lb);
                 };
                 using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
                 static_assert(HC == 8, "eight mics: two trips of three and two more");
@@ -3118,145 +2796,131 @@ static hipError_t refuse_scratch(K kernel, int* cached)
 #endif
 }
 
-template <int ALGO, int NC>
-hipError_t launch_nc(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
+// Shifted-copies layout (plan.layout == 2): pad / lerp at NSEG = 1, 2, 4 segments of 256 samples, the 8-tap FIR flavours at NSEG = 1.
+template <int ALGO, int NSEG>
+hipError_t launch_copies(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
 {
     const dim3 grid((unsigned)plan.n_tiles * (unsigned)frames);
     const dim3 block((unsigned)plan.waves * kWave);
-    auto go = [&](auto kernel) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)plan.lds_bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a);
-        return hipGetLastError();
-    };
     constexpr bool kFir = ALGO == ALGO_HYBRID || ALGO == ALGO_FIR_NAIVE || ALGO == ALGO_FIR_VEC;
-    if constexpr ((NC >= 4 && !kFir) || (NC == 4 && kFir)) {
-        if (plan.layout == 2) {
-            constexpr bool kNeedsDigest = ALGO != ALGO_FIR_NAIVE && ALGO != ALGO_FIR_VEC;
-            if (kNeedsDigest && L.tab.digest == nullptr) return hipErrorInvalidValue;   // launch_digest first
-            if (kFir && L.n_taps != 8) return hipErrorInvalidValue;
-            constexpr int NSEG = NC / 4;
-            if constexpr (!kFir && NSEG == 1) {
-                if (plan.nf == 2) {
-                    if (L.tab.digest == nullptr || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != copies::PairGeo<ALGO>::kMc ||
-                        (!plan.interleaved && plan.row_stride != copies::PairGeo<ALGO>::kRs) || plan.lead != copies::PairGeo<ALGO>::kLead || (L.n_mics % 16) != 0)
-                        return hipErrorInvalidValue;
-                    if (plan.interleaved) {
-                        if (plan.row_stride != copies::Pair2Geo<ALGO>::kRs) return hipErrorInvalidValue;
-                        auto kernel2 = copies::das_pair2_kernel<ALGO>;
-                        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-                        if (e2 != hipSuccess) return e2;
-                        static int pair2_scratch = -1;
-                        if ((e2 = refuse_scratch(kernel2, &pair2_scratch)) != hipSuccess) return e2;
-                        const dim3 grid2((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
-                        hipLaunchKernelGGL(kernel2, grid2, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
-                                           reinterpret_cast<const float*>(L.tab.digest), a);
-                        return hipGetLastError();
-                    }
-                    auto kernel = copies::das_pair_kernel<ALGO>;
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-                    if (e != hipSuccess) return e;
-                    static int pair_scratch = -1;             // (asm statements pass registers to each other: refuse a build that spills)
-                    if (pair_scratch < 0) {
-                        hipFuncAttributes fa{};
-                        e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
-                        if (e != hipSuccess) return e;
-                        pair_scratch = (int)fa.localSizeBytes;
-                    }
-                    if (pair_scratch != 0) return hipErrorInvalidDeviceFunction;
-                    const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
-                    hipLaunchKernelGGL(kernel, pair_grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
-                                       reinterpret_cast<const float*>(L.tab.digest), a);
-                    return hipGetLastError();
-                }
-            }
-            if constexpr (kFir) {
-                if (plan.nf == 2) {                             // das_hybrid_pair_kernel<hybrid | fir_naive | fir_vec>
-                    using HG = copies::HybridGeo;
-                    if (L.tab.digest == nullptr || plan.waves != copies::kWaves || plan.mic_chunk != HG::kMc || plan.row_stride != HG::kRs ||
-                        plan.lead != HG::kLead || (L.n_mics % 16) != 0 || L.n_taps != 8)
-                        return hipErrorInvalidValue;
-                    auto kernel = copies::das_hybrid_pair_kernel<ALGO>;
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-                    if (e != hipSuccess) return e;
-                    static int hybrid_scratch = -1;
-                    if ((e = refuse_scratch(kernel, &hybrid_scratch)) != hipSuccess) return e;
-                    const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
-                    hipLaunchKernelGGL(kernel, pair_grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole,
-                                       reinterpret_cast<const float*>(L.tab.digest), L.tab.taps, a);
-                    return hipGetLastError();
-                }
-            }
-            if constexpr (!kFir && (NSEG == 2 || NSEG == 4)) {
-                if (plan.long_rows) {                           // das_long_kernel
-                    using LG = copies::LongGeo<ALGO, NSEG>;
-                    if (L.tab.digest == nullptr || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != LG::kMc ||
-                        (L.n_mics % LG::kHalf) != 0 || plan.dpw != LG::kDw)
-                        return hipErrorInvalidValue;
-                    const bool fixed_rs = plan.row_stride == (LG::kLerp ? 2 : 1) * copies::Geo<NSEG>::kRs && plan.lead == copies::Geo<NSEG>::kLead;
-                    auto kernel = fixed_rs ? copies::das_long_kernel<ALGO, NSEG, copies::Geo<NSEG>::kRs> : copies::das_long_kernel<ALGO, NSEG, 0>;
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-                    if (e != hipSuccess) return e;
-                    static int long_scratch[2] = {-1, -1};
-                    if ((e = refuse_scratch(kernel, &long_scratch[fixed_rs ? 1 : 0])) != hipSuccess) return e;
-                    hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
-                                       reinterpret_cast<const float*>(L.tab.digest), a);
-                    return hipGetLastError();
-                }
-            }
-            using G = copies::Geo<NSEG>;
-            constexpr int kRs = kFir ? G::kRsFir : G::kRs;
-            const bool fixed = plan.row_stride == kRs && plan.lead == G::kLead;
-            auto kernel = fixed ? copies::das_copies_kernel<ALGO, NSEG, kRs, copies::kWaves> : copies::das_copies_kernel<ALGO, NSEG, 0, copies::kWaves>;
-            if constexpr (!kFir && NSEG == 1) {
-                if (plan.waves == 8) kernel = fixed ? copies::das_copies_kernel<ALGO, NSEG, kRs, 8> : copies::das_copies_kernel<ALGO, NSEG, 0, 8>;
-            }
-            bool direct = false;
-            if constexpr (!kFir) {
-                if (L.tab.digest_direct) {
-                    if (plan.waves != copies::kWaves) return hipErrorInvalidValue;      // the DIRECT variant exists for 16 waves only
-                    kernel = fixed ? copies::das_copies_kernel<ALGO, NSEG, kRs, copies::kWaves, true> : copies::das_copies_kernel<ALGO, NSEG, 0, copies::kWaves, true>;
-                    direct = true;
-                }
-            }
-            if (plan.waves != copies::kWaves && !(plan.waves == 8 && !kFir && NSEG == 1)) return hipErrorInvalidValue;
+    constexpr bool kNeedsDigest = ALGO != ALGO_FIR_NAIVE && ALGO != ALGO_FIR_VEC;
+    if (kNeedsDigest && L.tab.digest == nullptr) return hipErrorInvalidValue;   // launch_digest first
+    if (kFir && L.n_taps != 8) return hipErrorInvalidValue;
+    if constexpr (!kFir && NSEG == 1) {
+        if (plan.nf == 2) {                             // das_pair_kernel (pad) / das_pair2_kernel (lerp: frames interleaved in the rows)
+            constexpr bool kLerp = ALGO == ALGO_LERP;
+            using PG = std::conditional_t<kLerp, copies::Pair2Geo, copies::PairGeo>;
+            if (L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != PG::kMc || plan.row_stride != PG::kRs ||
+                plan.lead != PG::kLead || plan.interleaved != (kLerp ? 1 : 0) || (L.n_mics % 16) != 0)
+                return hipErrorInvalidValue;
+            auto kernel = [] { if constexpr (kLerp) return copies::das_pair2_kernel<ALGO>; else return copies::das_pair_kernel<ALGO>; }();
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
             if (e != hipSuccess) return e;
-            if constexpr (!kFir && NSEG == 1) if (!direct) {
-                // This variant keeps LDS reads in flight across asm statements (issue_quads / await_quads): sound only while
-                // the compiler neither spills nor copies those registers.  Spilling is checkable: refuse to run a build that
-                // uses scratch (copies would show in the bit-exact parity tests).
-                static int scratch_bytes[4] = {-1, -1, -1, -1};
-                int& sb = scratch_bytes[(fixed ? 1 : 0) + (plan.waves == 8 ? 2 : 0)];
-                if (sb < 0) {
-                    hipFuncAttributes fa{};
-                    e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
-                    if (e != hipSuccess) return e;
-                    sb = (int)fa.localSizeBytes;
-                }
-                if (sb != 0) return hipErrorInvalidDeviceFunction;
-            }
-            // the digest rides in a pointer slot the algorithm does not use: taps (pad, lerp) or frac (hybrid)
-            const float* dig = reinterpret_cast<const float*>(L.tab.digest);
-            hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, kFir ? dig : L.tab.frac,
-                               kFir ? L.tab.taps : dig, a);
+            static int pair_scratch = -1;
+            if ((e = refuse_scratch(kernel, &pair_scratch)) != hipSuccess) return e;
+            const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
+            hipLaunchKernelGGL(kernel, pair_grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
+                               reinterpret_cast<const float*>(L.tab.digest), a);
             return hipGetLastError();
         }
     }
-    if constexpr (NC == 4 && (ALGO == ALGO_PAD || ALGO == ALGO_LERP)) {
-        if (plan.quad) {
-            switch (plan.dpw) {
-                case 1: return go(das_mimo_kernel<ALGO, 4, 1, true>);
-                case 4: return go(das_mimo_kernel<ALGO, 4, 4, true>);
-                default: return hipErrorInvalidValue;
-            }
+    if constexpr (kFir) {
+        if (plan.nf == 2) {                             // das_hybrid_pair_kernel<hybrid | fir_naive | fir_vec>
+            using HG = copies::HybridGeo;
+            if (L.tab.digest == nullptr || plan.waves != copies::kWaves || plan.mic_chunk != HG::kMc || plan.row_stride != HG::kRs ||
+                plan.lead != HG::kLead || (L.n_mics % 16) != 0 || L.n_taps != 8)
+                return hipErrorInvalidValue;
+            auto kernel = copies::das_hybrid_pair_kernel<ALGO>;
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+            if (e != hipSuccess) return e;
+            static int hybrid_scratch = -1;
+            if ((e = refuse_scratch(kernel, &hybrid_scratch)) != hipSuccess) return e;
+            const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
+            hipLaunchKernelGGL(kernel, pair_grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole,
+                               reinterpret_cast<const float*>(L.tab.digest), L.tab.taps, a);
+            return hipGetLastError();
         }
     }
-    switch (plan.dpw) {
-        case 1: return go(das_mimo_kernel<ALGO, NC, 1, false>);
-        case 4: return go(das_mimo_kernel<ALGO, NC, 4, false>);
-        default: return hipErrorInvalidValue;
+    if constexpr (!kFir && (NSEG == 2 || NSEG == 4)) {
+        if (plan.long_rows) {                           // das_long_kernel
+            using LG = copies::LongGeo<ALGO, NSEG>;
+            if (L.tab.digest == nullptr || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != LG::kMc ||
+                (L.n_mics % LG::kHalf) != 0 || plan.dpw != LG::kDw)
+                return hipErrorInvalidValue;
+            const bool fixed_rs = plan.row_stride == (LG::kLerp ? 2 : 1) * copies::Geo<NSEG>::kRs && plan.lead == copies::Geo<NSEG>::kLead;
+            auto kernel = fixed_rs ? copies::das_long_kernel<ALGO, NSEG, copies::Geo<NSEG>::kRs> : copies::das_long_kernel<ALGO, NSEG, 0>;
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+            if (e != hipSuccess) return e;
+            static int long_scratch[2] = {-1, -1};
+            if ((e = refuse_scratch(kernel, &long_scratch[fixed_rs ? 1 : 0])) != hipSuccess) return e;
+            hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
+                               reinterpret_cast<const float*>(L.tab.digest), a);
+            return hipGetLastError();
+        }
+    }
+    using G = copies::Geo<NSEG>;
+    constexpr int kRs = kFir ? G::kRsFir : G::kRs;
+    const bool fixed = plan.row_stride == kRs && plan.lead == G::kLead;
+    auto kernel = fixed ? copies::das_copies_kernel<ALGO, NSEG, kRs, copies::kWaves> : copies::das_copies_kernel<ALGO, NSEG, 0, copies::kWaves>;
+    if constexpr (!kFir && NSEG == 1) {
+        if (plan.waves == 8) kernel = fixed ? copies::das_copies_kernel<ALGO, NSEG, kRs, 8> : copies::das_copies_kernel<ALGO, NSEG, 0, 8>;
+    }
+    bool direct = false;
+    if constexpr (!kFir) {
+        if (L.tab.digest_direct) {
+            if (plan.waves != copies::kWaves) return hipErrorInvalidValue;      // the DIRECT variant exists for 16 waves only
+            kernel = fixed ? copies::das_copies_kernel<ALGO, NSEG, kRs, copies::kWaves, true> : copies::das_copies_kernel<ALGO, NSEG, 0, copies::kWaves, true>;
+            direct = true;
+        }
+    }
+    if (plan.waves != copies::kWaves && !(plan.waves == 8 && !kFir && NSEG == 1)) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+    if (e != hipSuccess) return e;
+    if constexpr (!kFir && NSEG == 1) if (!direct) {
+        // This variant keeps LDS reads in flight across asm statements (issue_quads / await_quads): sound only while
+        // the compiler neither spills nor copies those registers.  Spilling is checkable: refuse to run a build that
+        // uses scratch (copies would show in the bit-exact parity tests).
+        static int scratch_bytes[4] = {-1, -1, -1, -1};
+        int& sb = scratch_bytes[(fixed ? 1 : 0) + (plan.waves == 8 ? 2 : 0)];
+        if (sb < 0) {
+            hipFuncAttributes fa{};
+            e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
+            if (e != hipSuccess) return e;
+            sb = (int)fa.localSizeBytes;
+        }
+        if (sb != 0) return hipErrorInvalidDeviceFunction;
+    }
+    // the digest rides in a pointer slot the algorithm does not use: taps (pad, lerp) or frac (hybrid)
+    const float* dig = reinterpret_cast<const float*>(L.tab.digest);
+    hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, kFir ? dig : L.tab.frac,
+                       kFir ? L.tab.taps : dig, a);
+    return hipGetLastError();
+}
+
+template <int ALGO, int NC>
+hipError_t launch_nc(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
+{
+    constexpr bool kFir = ALGO == ALGO_HYBRID || ALGO == ALGO_FIR_NAIVE || ALGO == ALGO_FIR_VEC;
+    if constexpr (!kFir && NC >= 4) {
+        // pad / lerp beyond 128 samples: shifted copies only (plan_das gives them no other layout)
+        return plan.layout == 2 ? launch_copies<ALGO, NC / 4>(L, a, plan, frames, stream) : hipErrorInvalidValue;
+    } else {
+        if constexpr (NC == 4) {                        // the 8-tap FIR flavours; other tap counts take the strided kernel
+            if (plan.layout == 2) return launch_copies<ALGO, 1>(L, a, plan, frames, stream);
+        }
+        auto go = [&](auto kernel) -> hipError_t {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)plan.lds_bytes);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)plan.n_tiles * (unsigned)frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream,
+                               L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a);
+            return hipGetLastError();
+        };
+        switch (plan.dpw) {
+            case 1: return go(das_mimo_kernel<ALGO, NC, 1>);
+            case 4: return go(das_mimo_kernel<ALGO, NC, 4>);
+            default: return hipErrorInvalidValue;
+        }
     }
 }
 
@@ -3311,7 +2975,6 @@ KArgs make_args(const DasLaunch& L, const DasPlan& plan)
     a.scratch_off = plan.scratch_off; a.srow = plan.srow; a.pbw = plan.pbw;
     a.n_is_pow2 = (L.n_mics & (L.n_mics - 1)) == 0;
     a.inv_n = 1.0f / (float)L.n_mics;
-    a.debug = L.debug;
     a.n_frames = L.frames;
     a.wg_frames = plan.nf == 2 ? (L.frames + 1) / 2 : L.frames;
     a.frame_inner = plan.frame_inner;
@@ -3366,13 +3029,11 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
         p.mic_chunk = mc; p.n_chunks = (L.n_mics + mc - 1) / mc;
         p.dpw = p.n_chunks > 1 ? 4 : 1;
     }
-    // Layout for pad / lerp at 128 < N <= 1024 and for the 8-tap FIR flavours at 128 < N <= 256: 2 = shifted copies
-    // (default), 0 = strided; pad / lerp at N <= 256 only: 1 = quad + DPP.
+    // Layout: 2 = shifted copies for pad / lerp at 128 < N <= 1024 and for the 8-tap FIR flavours at 128 < N <= 256, 0 = strided
+    // everywhere else.
     const bool plain = L.algo == ALGO_PAD || L.algo == ALGO_LERP;
     const bool copies_ok = plain ? p.nc >= 4 : (p.nc == 4 && L.n_taps == 8);
-    p.layout = copies_ok ? (L.force_layout >= 0 ? L.force_layout : 2) : 0;
-    if (p.layout == 1 && !(plain && p.nc == 4)) p.layout = 0;
-    p.quad = p.layout == 1 ? 1 : 0;
+    p.layout = copies_ok ? 2 : 0;
     if (p.layout == 2) {
         const int nseg = p.nc / 4, arrays = (L.algo == ALGO_LERP) ? 2 : 1;
         const int fixed_lead = nseg == 1 ? copies::Geo<1>::kLead : copies::Geo<4>::kLead;   // Geo<2> == Geo<4> here
@@ -3380,7 +3041,7 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
         // zero prefix: the furthest look-back is the delay (+1 for lerp, +1 + T/2 for hybrid, T/2 for the plain FIRs)
         const int back = L.algo == ALGO_HYBRID ? L.tab.max_whole + 1 + L.n_taps / 2 : fir ? L.n_taps / 2 : L.tab.max_whole + 1;
         p.lead = round_up(back + 1, 4);
-        if (p.lead <= fixed_lead && !(L.debug & 2)) p.lead = fixed_lead;   // compile-time row stride
+        if (p.lead <= fixed_lead) p.lead = fixed_lead;   // compile-time row stride
         p.row_stride = p.lead + nseg * 256 + (fir ? copies::Geo<1>::kFirTail : 0);
         p.copies = copies::copies_of(L.algo, L.tab.digest_direct);
         const size_t slot_bytes = (size_t)arrays * p.copies * p.row_stride * sizeof(float);
@@ -3390,31 +3051,31 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
         // One 16-wave workgroup per CU with (nearly) the whole LDS.  pad / lerp at N <= 256 also come as 8-wave workgroups
         // (two per CU, 78 KiB each): twice the staging per direction, so only for grids too coarse to fill 16 waves' 128
         // directions (cfg1: 121 directions, 637K -> 961K frames/s).  (cfg2, 190 frames: 16 waves 80.0K, 8 waves 72.0K.)
-        const int waves = (plain && nseg == 1 && ((L.dir_end - L.dir_begin) < 256 || (L.debug & 4))) ? 8 : copies::kWaves;   // debug bit 2: A/B switch
+        const int waves = (plain && nseg == 1 && (L.dir_end - L.dir_begin) < 256) ? 8 : copies::kWaves;
         const size_t budget = waves == 8 ? (size_t)78 * 1024 : (size_t)156 * 1024;
-        if (plain && nseg == 1 && waves == copies::kWaves && !L.tab.digest_direct && !(L.debug & 8)) stage_pairs = 32;   // debug bit 3: A/B switch
+        if (plain && nseg == 1 && waves == copies::kWaves && !L.tab.digest_direct) stage_pairs = 32;
         int mc = (int)(budget / slot_bytes);
         if (mc > stage_pairs / nseg) mc = stage_pairs / nseg;
         mc = mc >= 32 ? 32 : mc >= 16 ? 16 : mc >= 8 ? 8 : mc >= 4 ? 4 : mc >= 2 ? 2 : mc;
         if (mc < 1) return fail(3);
         if (mc > L.n_mics) mc = L.n_mics;
         // Two frames per workgroup (das_pair_kernel) where its fixed geometry applies: the per-step scalar work is then shared
-        // by both frames.  (debug bit 4: A/B switch)
+        // by both frames.
         p.nf = 1;
         if (plain && nseg == 1 && waves == copies::kWaves && !L.tab.digest_direct && p.lead == fixed_lead && (L.n_mics % 16) == 0 &&
-            (L.n_samples % 4) == 0 && L.frames >= 2 && !(L.debug & 16)) {
+            (L.n_samples % 4) == 0 && L.frames >= 2) {
             p.nf = 2;
             mc = 16;
             // frames interleaved in the rows (das_pair2_kernel) for lerp: 4 instead of 8 LDS reads per (re)load, +1.5 %; pad reads
-            // half as much to begin with and measured 2 % slower that way  (debug bit 15: A/B switch, the other kernel)
-            if ((L.algo == ALGO_LERP) != ((L.debug & 32768) != 0)) {
+            // half as much to begin with and measured 2 % slower that way
+            if (L.algo == ALGO_LERP) {
                 p.interleaved = 1;
                 p.row_stride = 2 * copies::Geo<1>::kRs;         // the two frames of a mic share a row, sample by sample
             }
         }
-        // The hybrid beamformer's two-frame sweep (das_hybrid_pair_kernel) under the same conditions.  (debug bit 13: A/B switch)
+        // The hybrid beamformer's two-frame sweep (das_hybrid_pair_kernel) under the same conditions.
         if (fir && nseg == 1 && L.n_taps == 8 && waves == copies::kWaves && p.lead == fixed_lead && (L.n_mics % 16) == 0 &&
-            (L.n_samples % 4) == 0 && L.frames >= 2 && !(L.debug & 8192)) {
+            (L.n_samples % 4) == 0 && L.frames >= 2) {
             p.nf = 2;
             mc = copies::HybridGeo::kMc;                        // 32 mic slots: two frames interleaved per row, two shifted copies
             p.copies = copies::HybridGeo::kC;
@@ -3423,9 +3084,9 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
         }
         const bool hybrid_pair = fir && p.nf == 2;
         // Long rows (2 / 4 segments): das_long_kernel where its LDS image -- two halves of 16 / nseg mics -- fits and the mic count is
-        // a whole number of halves.  (debug bit 12: A/B switch back to das_copies_kernel)
+        // a whole number of halves.
         p.long_rows = 0;
-        if (plain && nseg > 1 && !L.tab.digest_direct && !(L.debug & 4096)) {
+        if (plain && nseg > 1 && !L.tab.digest_direct) {
             const int half = 16 / nseg;
             if ((L.n_mics % half) == 0 && (L.n_samples % 4) == 0 && slot_bytes * (size_t)(2 * half) <= (size_t)160 * 1024) {
                 p.long_rows = 1;
@@ -3477,9 +3138,9 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
         //     a rank of the 8-GPU shape at 63 % of the one-GPU rate.
         // Ties go to the first of 2, 3, .., 8, 1.
         const size_t table_bytes = (size_t)dirs * (size_t)L.n_mics * 4u * ((L.algo == ALGO_LERP ? 2u : 1u) + (fir ? (size_t)L.n_taps : 0u));
-        spread = (table_bytes <= ((size_t)3 << 20) && !(L.debug & 32)) || (L.debug & 64);   // debug bits 5 / 6: A/B switches (never / always)
-        // an XCD's share of the table beyond its L2: all frames of a tile back to back (tile_and_frame); debug bit 7: never
-        p.frame_inner = (!spread && p.layout == 2 && table_bytes > ((size_t)16 << 20) && wg_frames > 1 && !(L.debug & 128)) ? 1 : 0;
+        spread = table_bytes <= ((size_t)3 << 20);
+        // an XCD's share of the table beyond its L2: all frames of a tile back to back (tile_and_frame)
+        p.frame_inner = (!spread && p.layout == 2 && table_bytes > ((size_t)16 << 20) && wg_frames > 1) ? 1 : 0;
         const int wg_per_cu = 1;
         const int xcds = 8, cus_per_xcd = (n_cus >= xcds ? n_cus / xcds : 1) * wg_per_cu;
         long long best_cost = -1;
@@ -3494,7 +3155,6 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_k = k; }
         }
         td = (long long)best_k * group;
-        if ((L.debug >> 8) & 15) td = (long long)((L.debug >> 8) & 15) * group;   // debug bits 8..11: tile size in groups (A/B)
     }
     p.tile_dirs = (int)td;
     p.n_tiles = spread ? (int)((dirs + td - 1) / td) : round_up((int)((dirs + td - 1) / td), 8);
