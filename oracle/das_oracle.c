@@ -20,6 +20,7 @@ static int g_nsamp = 256, g_resx = 57, g_resy = 32, g_taps = 8;
 
 /* tables, one set per process like the reference's file-scope globals */
 static int *g_pad_whole;     /* pad_and_sum.c:29  */
+static int *g_pad2_whole;    /* pad_and_sum.c:30, indexed by microphone id */
 static int *g_lerp_whole;    /* lerp_and_sum.c:33 */
 static float *g_lerp_h;      /* lerp_and_sum.c:34 */
 static float *g_fir_taps;    /* convolve_and_sum.c:40 */
@@ -63,6 +64,22 @@ void oracle_miso_pad(const float *signals, float *out, const int *mics, int n, i
     memset(out, 0, (size_t)g_nsamp * sizeof(float));
     for (int m = 0; m < n; m++)
         oracle_pad_delay(signals + (size_t)mics[m] * g_nsamp, out, g_pad_whole[offset + m]);
+}
+
+void oracle_load_coefficients_pad2(const int *whole_by_mic, int n)   /* pad_and_sum.c:153-157 */
+{
+    free(g_pad2_whole);
+    g_pad2_whole = (int *)malloc((size_t)n * sizeof(int));
+    memcpy(g_pad2_whole, whole_by_mic, (size_t)n * sizeof(int));
+}
+
+/* pad_and_sum.c:77-92: the delay of list entry m is looked up by its MICROPHONE id, not by m; `offset` is not read */
+void oracle_miso_pad2(const float *signals, float *out, const int *mics, int n, int offset)
+{
+    (void)offset;
+    memset(out, 0, (size_t)g_nsamp * sizeof(float));
+    for (int m = 0; m < n; m++)
+        oracle_pad_delay(signals + (size_t)mics[m] * g_nsamp, out, g_pad2_whole[mics[m]]);
 }
 
 void oracle_mimo_pad(const float *signals, float *image, const int *mics, int n)           /* :100-143 */
@@ -167,6 +184,37 @@ void oracle_convolve_delay_vectorized_add(const float *sig, const float *h, floa
     free(p);
 }
 
+/* convolve_and_sum.c:73-87: the naive chain of convolve_delay_naive with (signal, h, out) argument order */
+void oracle_convolve_delay_naive_add(const float *sig, const float *h, float *out)
+{
+    oracle_convolve_delay_naive(sig, out, h);
+}
+
+/* convolve_and_sum.c:92-128: two AVX accumulators of 8 samples each, reset to zero per 16-sample block; per sample that
+ * is ONE fma chain over the taps in order, starting at 0, and the result is stored (out is overwritten, not added to).
+ * The reference writes whole 16-sample blocks, so for N % 16 != 0 it stores past out[N - 1] (and reads past its padded
+ * copy); only out[0..N-1] is defined here. */
+__attribute__((optimize("fp-contract=off")))
+void oracle_convolve_delay_vectorized(const float *sig, const float *h, float *out)
+{
+    float *p = padded_copy(sig);
+    for (int i = 0; i < g_nsamp; i++) {
+        float acc = 0.0f;
+        for (int k = 0; k < g_taps; k++)
+            acc = fmaf(p[i + k], h[k], acc);
+        out[i] = acc;
+    }
+    free(p);
+}
+
+/* convolve_and_sum.c:276-292: `offset` counts floats of the tap table (d * n * N_TAPS); mic m uses taps offset + m*N_TAPS */
+void oracle_miso_convolve_vectorized(const float *signals, float *out, const int *mics, int n, int offset)
+{
+    memset(out, 0, (size_t)g_nsamp * sizeof(float));
+    for (int m = 0; m < n; m++)
+        oracle_convolve_delay_vectorized_add(signals + (size_t)mics[m] * g_nsamp, g_fir_taps + (size_t)offset + (size_t)m * g_taps, out);
+}
+
 static void mimo_convolve(const float *signals, float *image, const int *mics, int n, int vectorized)
 {
     float *out = (float *)malloc((size_t)g_nsamp * sizeof(float));
@@ -235,6 +283,16 @@ void oracle_convolve_hybrid_delay_add(const float *sig, const float *h, int shif
         for (int k = 0; k < g_taps; k++)
             out[shift + i + 1] += h[k] * p[i + k];
     free(p);
+}
+
+/* hybrid_convolve_and_sum.c:66-90: `offset` counts (direction, mic) entries (d * n); entry offset + m holds the pad
+ * and, N_TAPS floats apart, the fractional taps */
+void oracle_miso_convolve_hybrid(const float *signals, float *out, const int *mics, int n, int offset)
+{
+    memset(out, 0, (size_t)g_nsamp * sizeof(float));
+    for (int m = 0; m < n; m++)
+        oracle_convolve_hybrid_delay_add(signals + (size_t)mics[m] * g_nsamp, g_hyb_taps + ((size_t)offset + m) * g_taps,
+                                         g_hyb_whole[(size_t)offset + m], out);
 }
 
 void oracle_mimo_convolve_hybrid(const float *signals, float *image, const int *mics, int n)   /* :88-121 */
@@ -314,7 +372,7 @@ void oracle_mimo_range(int algo, const float *signals, float *image, const int *
 
 void oracle_unload_all(void)
 {
-    free(g_pad_whole); free(g_lerp_whole); free(g_lerp_h); free(g_fir_taps); free(g_hyb_whole); free(g_hyb_taps);
-    g_pad_whole = g_lerp_whole = g_hyb_whole = NULL;
+    free(g_pad_whole); free(g_pad2_whole); free(g_lerp_whole); free(g_lerp_h); free(g_fir_taps); free(g_hyb_whole); free(g_hyb_taps);
+    g_pad_whole = g_pad2_whole = g_lerp_whole = g_hyb_whole = NULL;
     g_lerp_h = g_fir_taps = g_hyb_taps = NULL;
 }

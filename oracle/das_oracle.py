@@ -7,7 +7,10 @@
 Both expose the same methods so tests can run one against the other:
   mimo_pad(signals, whole_i32, mics) / mimo_lerp(signals, delays_f32, mics) /
   mimo_convolve(signals, taps_f32, mics, vectorized) / mimo_hybrid(signals, delays_f32, mics)
-returning float32 [X, Y] images (the reference views image[D] as (MAX_RES_X, MAX_RES_Y), main.pyx:190).
+returning float32 [X, Y] images (the reference views image[D] as (MAX_RES_X, MAX_RES_Y), main.pyx:190), the one-direction
+  miso_pad / miso_pad2 / miso_lerp / miso_hybrid / miso_convolve_vectorized(signals, table, mics, offset)
+returning the raw steered block float32 [N], and the seven single-signal helpers (pad_delay, lerp_delay, convolve_delay_*,
+convolve_hybrid_delay_add) returning the new contents of their `out`.
 """
 import ctypes as C
 import os
@@ -86,6 +89,68 @@ class _Base:
         self._fn("load_coefficients_lerp")(_f(d), C.c_int(d.size))
         self._fn("miso_lerp")(_f(s), _f(out), _i(m), C.c_int(m.size), C.c_int(offset))
         return out
+
+    def miso_pad2(self, signals, whole_by_mic, mics, offset):
+        """pad2: the delay table is indexed by microphone id (load_coefficients_pad2), `offset` is passed but not read."""
+        s, m = _prep(signals, mics)
+        w = np.ascontiguousarray(whole_by_mic, dtype=np.int32).ravel()
+        out = np.zeros(self.N, dtype=np.float32)
+        self._fn("load_coefficients_pad2")(_i(w), C.c_int(w.size))
+        self._fn("miso_pad2")(_f(s), _f(out), _i(m), C.c_int(m.size), C.c_int(offset))
+        return out
+
+    def miso_convolve_vectorized(self, signals, taps, mics, offset):
+        """`offset` counts floats of the tap table (d * n * T), as the reference's does."""
+        s, m = _prep(signals, mics)
+        h = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        out = np.zeros(self.N, dtype=np.float32)
+        self._fn("load_coefficients_convolve")(_f(h), C.c_int(h.size))
+        self._fn("miso_convolve_vectorized")(_f(s), _f(out), _i(m), C.c_int(m.size), C.c_int(offset))
+        return out
+
+    def miso_hybrid(self, signals, delays_f32, mics, offset):
+        s, m = _prep(signals, mics)
+        d = np.ascontiguousarray(delays_f32, dtype=np.float32).ravel()
+        out = np.zeros(self.N, dtype=np.float32)
+        self._fn("load_coefficients_convolve_hybrid")(_f(d), C.c_int(d.size))
+        self._fn("miso_convolve_hybrid")(_f(s), _f(out), _i(m), C.c_int(m.size), C.c_int(offset))
+        return out
+
+    # ---- the single-signal helpers, argument order as in the reference.  `out` is the buffer they start from (it is not
+    # modified); each returns a new float32 [N].  The C side gets 16 spare floats: the reference's convolve_delay_vectorized
+    # stores whole 16-sample blocks.
+
+    def _helper(self, name, sig, out, taps, args):
+        """`args`: the C argument list, with "sig", "out" and "taps" standing for the three arrays."""
+        x = np.ascontiguousarray(sig, dtype=np.float32).ravel()
+        h = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        assert x.size == self.N and (h is None or h.size == self.T)
+        buf = np.zeros(self.N + 16, dtype=np.float32)
+        buf[:self.N] = out
+        arrays = {"sig": _f(x), "out": _f(buf), "taps": None if h is None else _f(h)}
+        self._fn(name)(*[arrays[a] if isinstance(a, str) else a for a in args])
+        return buf[:self.N].copy()
+
+    def pad_delay(self, sig, out, shift):
+        return self._helper("pad_delay", sig, out, None, ["sig", "out", C.c_int(shift)])
+
+    def lerp_delay(self, sig, out, h, shift):
+        return self._helper("lerp_delay", sig, out, None, ["sig", "out", C.c_float(h), C.c_int(shift)])
+
+    def convolve_delay_naive(self, sig, out, h):
+        return self._helper("convolve_delay_naive", sig, out, h, ["sig", "out", "taps"])
+
+    def convolve_delay_naive_add(self, sig, h, out):
+        return self._helper("convolve_delay_naive_add", sig, out, h, ["sig", "taps", "out"])
+
+    def convolve_delay_vectorized(self, sig, h, out):
+        return self._helper("convolve_delay_vectorized", sig, out, h, ["sig", "taps", "out"])
+
+    def convolve_delay_vectorized_add(self, sig, h, out):
+        return self._helper("convolve_delay_vectorized_add", sig, out, h, ["sig", "taps", "out"])
+
+    def convolve_hybrid_delay_add(self, sig, h, shift, out):
+        return self._helper("convolve_hybrid_delay_add", sig, out, h, ["sig", "taps", C.c_int(shift), "out"])
 
 
 class Oracle(_Base):

@@ -8,7 +8,10 @@ TEST INFRASTRUCTURE ONLY.  Run where the reference lies:
 
 Writes tests/golden/refc_hashes.json (data only):
   entry_points/{cfg1,shipped}/<key>   every entry point the oracle and the compiled reference share, on the seeded block of
-                                      tests/test_oracle_golden.py::shared_entry_points (images and loader tables)
+                                      tests/test_oracle_golden.py::shared_entry_points (images, loader tables, MISO
+                                      outputs and the single-signal helpers)
+  miso_small_table/cfg5/<key>         tests/test_oracle_golden.py::miso_small_table: MISO outputs and helpers at N = 1024
+                                      on a five-direction seeded table
   receiver_shipped                    the frame the reference's receive_to_buffer builds from the seeded datagrams of
                                       tests/test_ingest.py, fed over a UDP loopback socket (n_arrays = 3)
 Each recorded value is checked against the oracle before the file is written.
@@ -42,6 +45,15 @@ def main():
             assert ref[key].dtype == orc[key].dtype and ref[key].tobytes() == orc[key].tobytes(), (name, key)
         out["entry_points"][name] = {key: sha(a) for key, a in sorted(ref.items())}
         print(name, "%d entry points recorded" % len(ref), flush=True)
+    out["miso_small_table"] = {}
+    for name in ("cfg5",):
+        c = CONFIGS[name]
+        ref = test_oracle_golden.miso_small_table(das_oracle.RefLib(name), name)
+        orc = test_oracle_golden.miso_small_table(das_oracle.Oracle(c["N"], c["X"], c["Y"], c["T"]), name)
+        for key in ref:
+            assert ref[key].dtype == orc[key].dtype and ref[key].tobytes() == orc[key].tobytes(), (name, key)
+        out["miso_small_table"][name] = {key: sha(a) for key, a in sorted(ref.items())}
+        print(name, "%d MISO / helper outputs on a small table recorded" % len(ref), flush=True)
 
     seed, n_arrays = 42, 3
     pk = test_ingest.datagrams(seed)

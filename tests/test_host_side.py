@@ -181,3 +181,27 @@ def test_visual_host_helpers(native):
     want = np.zeros_like(img, dtype=bool)
     want[1, 1] = want[2, 2] = True
     assert np.array_equal(visual.local_max(img, 0.5), want)
+
+
+def test_miso_cases_reach_every_kernel_instantiation(native):
+    """test_miso_parity.MISO_CASES, planned as run_miso_host plans a miso_* call (one frame, one direction, the loaded table's
+    largest whole delay): every algorithm reaches das_miso_kernel<ALGO, NC> for every NC in {1, 2, 4, 8, 16}, and chunked
+    staging (n_chunks > 1).  Editing the table cannot silently drop a kernel instantiation from the GPU tests."""
+    from test_miso_parity import MISO_ALGOS, MISO_CASES, miso_max_whole
+    ids = {"pad": native.PAD, "lerp": native.LERP, "hybrid": native.HYBRID, "convolve_vectorized": native.FIR_VEC, "pad2": native.PAD}
+    out = (C.c_longlong * 10)()
+    reached = {a: set() for a in MISO_ALGOS}
+    chunked = {a: 0 for a in MISO_ALGOS}
+    for case in MISO_CASES:
+        M_total, n, N, T, D = case[:5]
+        assert native.lib.bf_configure(M_total, N, D, 1, T) == 0
+        for algo in MISO_ALGOS:
+            assert native.lib.bf_plan_das(ids[algo], n, 1, 0, 1, miso_max_whole(algo, case), 256, out) == 0, (algo, case)
+            nc, n_chunks, mic_chunk = out[0], out[4], out[3]
+            assert n_chunks * mic_chunk >= n and nc * 64 >= N > (nc // 2) * 64
+            reached[algo].add(nc)
+            chunked[algo] += n_chunks > 1
+    for algo in MISO_ALGOS:
+        assert reached[algo] == {1, 2, 4, 8, 16}, algo
+        assert chunked[algo] >= 1, algo
+    util.configure("cfg1")

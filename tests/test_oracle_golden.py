@@ -147,6 +147,53 @@ def shared_entry_points(eng, name):
         taps = np.ascontiguousarray(util.table_for("fir_vec", name), dtype=np.float32)
         for vec in (False, True):
             out["mimo_convolve/vectorized=%d" % vec] = eng.mimo_convolve(sig, taps, mics, vectorized=vec)
+    out.update(miso_and_helpers(eng, sig, d32.ravel(), off // c["M"], np.random.default_rng(19)))
+    return out
+
+
+def miso_and_helpers(eng, sig, d32, direction, rng):
+    """The MISO entry points the reference's Cython wrappers never call (miso_convolve_vectorized, miso_convolve_hybrid,
+    miso_pad2) at table offset `direction`, and the seven single-signal helpers on one row: key -> float32 [N].
+    `d32` is the flat float32 delay table [D * M] (D >= direction + 1); the FIR taps, the pad2 table, the microphone list
+    of miso_pad2 and the helpers' inputs are drawn from `rng`."""
+    M, N, T = sig.shape[0], eng.N, eng.T
+    D = d32.size // M
+    out = {}
+    taps = rng.uniform(-0.5, 0.5, D * M * T).astype(np.float32)
+    out["miso_convolve_vectorized"] = eng.miso_convolve_vectorized(sig, taps, np.arange(M, dtype=np.int32), direction * M * T)
+    out["miso_convolve_hybrid"] = eng.miso_hybrid(sig, d32, np.arange(M, dtype=np.int32), direction * M)
+    # pad2: delays by microphone id (one of them past the block), a permuted subset of the microphones with gaps
+    by_mic = np.floor(d32[direction * M:(direction + 1) * M]).astype(np.int32)
+    by_mic[rng.integers(M)] = N + 3
+    keep = rng.permutation(M)[:(3 * M) // 4].astype(np.int32)
+    out["miso_pad2"] = eng.miso_pad2(sig, by_mic, keep, direction * M)
+    x = sig[3]
+    base = rng.standard_normal(N).astype(np.float32)
+    h = rng.uniform(-0.5, 0.5, T).astype(np.float32)
+    hyb = rng.uniform(-0.5, 0.5, T).astype(np.float32)
+    out["pad_delay"] = eng.pad_delay(x, base, 17)
+    out["lerp_delay"] = eng.lerp_delay(x, base, 0.3125, 9)
+    out["convolve_delay_naive"] = eng.convolve_delay_naive(x, base, h)
+    out["convolve_delay_naive_add"] = eng.convolve_delay_naive_add(x, h, base)
+    out["convolve_delay_vectorized"] = eng.convolve_delay_vectorized(x, h, base)      # overwrites: `base` must not show
+    out["convolve_delay_vectorized_add"] = eng.convolve_delay_vectorized_add(x, h, base)
+    out["convolve_hybrid_delay_add"] = eng.convolve_hybrid_delay_add(x, hyb, 5, base)
+    return out
+
+
+def miso_small_table(eng, name):
+    """miso_and_helpers at one size on a small seeded table of five directions (at cfg5 the full 361 x 361 x 256 table takes
+    minutes to build): delays up to N + 40 -- some past the block -- and the middle direction.  Plus miso_pad / miso_lerp at
+    the last direction of that table.  oracle/gen_golden_refhash.py records the compiled reference's side."""
+    c = CONFIGS[name]
+    M, N, D = c["M"], c["N"], 5
+    rng = np.random.default_rng(23)
+    sig = (rng.standard_normal((M, N)) * 0.25).astype(np.float32)
+    d32 = rng.uniform(0, N + 40, D * M).astype(np.float32)
+    mics = np.arange(M, dtype=np.int32)
+    out = miso_and_helpers(eng, sig, d32, D // 2, rng)
+    out["miso_pad"] = eng.miso_pad(sig, np.floor(d32).astype(np.int32), mics, (D - 1) * M)
+    out["miso_lerp"] = eng.miso_lerp(sig, d32, mics, (D - 1) * M)
     return out
 
 
@@ -166,3 +213,22 @@ def test_oracle_equals_compiled_reference(oracle_lib, name):
         want = shared_entry_points(oracle_lib.RefLib(name), name)
         for key, a in got.items():
             assert a.dtype == want[key].dtype and a.tobytes() == want[key].tobytes(), (name, key)
+
+
+def test_miso_cfg5_equals_compiled_reference(oracle_lib):
+    """N = 1024 (BASELINE config 5): every MISO entry point and single-signal helper on a small seeded table, bit for bit
+    against the SHA-256 of the compiled reference's outputs (refc_hashes.json `miso_small_table`), and against the compiled
+    reference itself where oracle/_ref has been built."""
+    import json
+    name = "cfg5"
+    c = CONFIGS[name]
+    got = miso_small_table(oracle_lib.Oracle(c["N"], c["X"], c["Y"], c["T"]), name)
+    rec = json.load(open(os.path.join(util.GOLDEN, "refc_hashes.json")))["miso_small_table"][name]
+    assert sorted(got) == sorted(rec)
+    for key, a in got.items():
+        assert a.dtype == np.float32 and a.shape == (c["N"],), key
+        assert sha(a) == rec[key], (name, key)
+    if oracle_lib.RefLib.available(name):
+        want = miso_small_table(oracle_lib.RefLib(name), name)
+        for key, a in got.items():
+            assert a.tobytes() == want[key].tobytes(), (name, key)
