@@ -163,6 +163,38 @@ int bf_get_steer(int *n_out);
 int bf_das_device(int algo, const float *d_signals, int m_total, float *d_images, int image_stride, int frames,
                   const int *adaptive_array, int n, int dir_begin, int dir_end, void *stream);
 
+/* ---- device-resident, batched steered beams (the MISO counterpart of bf_das_device) ----
+ * algo      : BF_PAD -> miso_pad, BF_LERP -> miso_lerp, BF_HYBRID -> miso_convolve_hybrid, BF_FIR_VEC -> miso_convolve_vectorized;
+ *             BF_FIR_NAIVE is refused (the reference has no MISO form of it).  Uses the table the matching load_coefficients_*
+ *             loaded -- the one bf_das_device reads, so one load serves maps and beams.
+ * d_signals : HIP device pointer, float32 [frames][m_total][N_SAMPLES], mic-major, as bf_das_device (no dead-row masking)
+ * adaptive_array / n : HOST array of the active mic rows, handled as bf_das_device handles it
+ * d_offsets : HIP device pointer, int32 [frames][beams]: the `offset` argument of the matching miso_* call -- the flat table
+ *             offset d * n, for BF_FIR_VEC the float offset d * n * N_TAPS into the tap table
+ * mic_gain  : 0 -> raw beams, bit-identical to miso_* at that offset; any other finite value -> out[i] = (out[i] / (float)n) * mic_gain
+ *             (two float32 roundings, as the reference's playback loop, api.c:519-523, and bf_miso_listen_block); not finite -> error
+ * d_out     : HIP device pointer, float32 [frames][beams][out_stride], out_stride >= N_SAMPLES; floats [N_SAMPLES, out_stride) of
+ *             every row are left untouched
+ * d_status  : HIP device pointer, int32 [frames][beams], or NULL.  When given, every entry is written: 0 ok, 1 offset negative or
+ *             past the loaded table (offset + n > entries; BF_FIR_VEC: offset + n * N_TAPS > entries, counted in floats),
+ *             2 BF_FIR_VEC offset not a multiple of N_TAPS.  A rejected beam reads nothing from the table and its N_SAMPLES
+ *             floats are NaN; the other beams of the call are unaffected.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only, no allocation after the first call -- except a call with a new
+ *             adaptive array, which synchronises the device as bf_das_device does; graph-capturable after one warm-up call.
+ *             Does not change bf_last_das_variant.
+ * Returns 0, or -1 (see bf_last_error; nothing enqueued) for an unknown or refused algo, a null pointer (d_status excepted),
+ * frames < 1, beams < 1, n < 1, out_stride < N_SAMPLES, an adaptive_array row outside [0, m_total), a mic_gain that is not finite,
+ * no GPU, or a table that is not loaded.  The arguments are checked before device bring-up. */
+int bf_miso_device(int algo, const float *d_signals, int m_total, int frames, const int *adaptive_array, int n,
+                   const int *d_offsets, int beams, float mic_gain, float *d_out, int out_stride, int *d_status, void *stream);
+/* d_offsets[f] = argmax_{0 <= j < n_dirs} d_power[f * image_stride + j] * offset_per_dir (device pointers, enqueue only): the
+ * loudest direction of every map as a [frames][1] offset array for bf_miso_device (offset_per_dir = n, or n * N_TAPS for
+ * BF_FIR_VEC).  Ties and NaN as np.argmax: the first of equal maxima wins, a NaN counts as the maximum (the first NaN wins).
+ * Returns 0, or -1 for a null pointer, frames / n_dirs / offset_per_dir < 1, image_stride < n_dirs,
+ * (n_dirs - 1) * offset_per_dir > INT_MAX, or no GPU. */
+int bf_peak_offsets_device(const float *d_power, int frames, int image_stride, int n_dirs, int offset_per_dir,
+                           int *d_offsets, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

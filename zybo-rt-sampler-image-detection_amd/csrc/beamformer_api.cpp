@@ -986,6 +986,67 @@ int bf_das_device(int algo, const float* d_signals, int m_total, float* d_images
     return HIP_OK(bf::launch_das(L, plan, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
 }
 
+int bf_miso_device(int algo, const float* d_signals, int m_total, int frames, const int* adaptive_array, int n, const int* d_offsets, int beams,
+                   float mic_gain, float* d_out, int out_stride, int* d_status, void* stream)
+{
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    sizes_from_env_once();
+    const int N = s.sz.n_samples;
+    if (algo == bf::ALGO_FIR_NAIVE) { set_error("bf_miso_device: algo BF_FIR_NAIVE has no MISO form in the reference"); return -1; }
+    const int slot = slot_of(algo);
+    if (slot < 0) { set_error("bf_miso_device: unknown algo %d", algo); return -1; }
+    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"},
+                                                               {d_out, "d_out"}};
+    for (const auto& a : ptrs)
+        if (!a.p) { set_error("bf_miso_device: %s is null", a.name); return -1; }
+    if (frames < 1) { set_error("bf_miso_device: frames = %d < 1", frames); return -1; }
+    if (beams < 1) { set_error("bf_miso_device: beams = %d < 1", beams); return -1; }
+    if (n < 1) { set_error("bf_miso_device: n = %d < 1", n); return -1; }
+    if (out_stride < N) { set_error("bf_miso_device: out_stride = %d < N_SAMPLES = %d", out_stride, N); return -1; }
+    for (int i = 0; i < n; ++i)
+        if (adaptive_array[i] < 0 || adaptive_array[i] >= m_total) {
+            set_error("bf_miso_device: adaptive_array[%d] = %d is not a row of frames with m_total = %d rows", i, adaptive_array[i], m_total);
+            return -1;
+        }
+    if (!std::isfinite(mic_gain)) { set_error("bf_miso_device: mic_gain = %g is not finite", (double)mic_gain); return -1; }
+    if (!ensure_device()) return -1;
+    const TableSet& t = s.tab[slot];
+    if (!t.loaded) { set_error("bf_miso_device: %s has not been called", loader_name(slot)); return -1; }
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    // planned as run_miso_host plans one beam of one frame
+    bf::DasLaunch L{};
+    L.algo = algo;
+    L.tab.whole = t.whole.p; L.tab.frac = t.frac.p; L.tab.taps = t.taps.p; L.tab.max_whole = t.max_whole;
+    L.n_mics = n; L.m_total = m_total; L.n_samples = N; L.n_taps = s.sz.n_taps; L.n_dirs = 1;
+    L.dir_begin = 0; L.dir_end = 1; L.image_stride = 1; L.image_origin = 0; L.frames = 1;
+    L.signals = d_signals; L.images = nullptr; L.mics = s.d_mics.p;
+    bf::DasPlan plan{};
+    if (!plan_or_error(L, &plan)) return -1;
+    L.frames = frames;
+    return HIP_OK(bf::launch_miso_batch(L, plan, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status,
+                                        reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
+int bf_peak_offsets_device(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, void* stream)
+{
+    std::lock_guard<std::mutex> lock(S().mu);
+    sizes_from_env_once();
+    if (!d_power) { set_error("bf_peak_offsets_device: d_power is null"); return -1; }
+    if (!d_offsets) { set_error("bf_peak_offsets_device: d_offsets is null"); return -1; }
+    if (frames < 1) { set_error("bf_peak_offsets_device: frames = %d < 1", frames); return -1; }
+    if (n_dirs < 1) { set_error("bf_peak_offsets_device: n_dirs = %d < 1", n_dirs); return -1; }
+    if (offset_per_dir < 1) { set_error("bf_peak_offsets_device: offset_per_dir = %d < 1", offset_per_dir); return -1; }
+    if (image_stride < n_dirs) { set_error("bf_peak_offsets_device: image_stride = %d < n_dirs = %d", image_stride, n_dirs); return -1; }
+    if ((long long)(n_dirs - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
+        set_error("bf_peak_offsets_device: (n_dirs - 1) * offset_per_dir = %lld does not fit an int offset", (long long)(n_dirs - 1) * offset_per_dir);
+        return -1;
+    }
+    if (!ensure_device()) return -1;
+    return HIP_OK(bf::launch_peak_offsets(d_power, frames, image_stride, n_dirs, offset_per_dir, d_offsets, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

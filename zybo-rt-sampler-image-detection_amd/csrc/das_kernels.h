@@ -86,6 +86,14 @@ hipError_t launch_das(const DasLaunch& L, const DasPlan& plan, hipStream_t strea
 hipError_t launch_miso(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev,
                        hipStream_t stream);
 
+// Steered beams of a batch (bf_miso_device): the same kernel with one workgroup per (frame, group of up to kMisoWaves beams),
+// one wave per beam.  d_offsets int32 [L.frames][beams] (table offsets, checked in the kernel against `entries`), d_out float32
+// [L.frames][beams][out_stride], d_status int32 [L.frames][beams] or null; gain 0 = raw beams.  `plan` is the one-direction,
+// one-frame plan run_miso_host uses (LDS is per workgroup, so its chunk sizing holds for any wave count).
+constexpr int kMisoWaves = 16;
+hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int beams, long long entries, float gain,
+                             float* d_out, int out_stride, int* d_status, hipStream_t stream);
+
 // FPGA protocol-v2 datagrams (one per sample instant) -> float32 [n_mics_out][n_samples] mic-major frame (receiver.c:94-151).
 hipError_t launch_ingest(const void* d_packets, int packet_stride, int header_bytes, int n_samples, int n_mics_out, int stream_len,
                          int rows, int columns, float* d_frame, hipStream_t stream);
@@ -100,6 +108,8 @@ hipError_t launch_overlay(const unsigned char* d_small, int frames, int small_w,
 hipError_t launch_letterbox(const unsigned char* d_src, int sh, int sw, unsigned char* d_out, int oh, int ow, int new_h, int new_w, int top, int left, int value,
                             hipStream_t stream);
 hipError_t launch_power_center(const float* d_power, int frames, int rows, int cols, float* d_centers, float* d_workspace, hipStream_t stream);
+// d_offsets[f] = argmax_{j < n_dirs} d_power[f * image_stride + j] * offset_per_dir, np.argmax's rules (first maximum, first NaN)
+hipError_t launch_peak_offsets(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, hipStream_t stream);
 
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.

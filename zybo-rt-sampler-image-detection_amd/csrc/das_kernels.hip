@@ -416,18 +416,50 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
     if (filled > 0) flush_powers(scratch, filled, img, a, lane);
 }
 
-// One direction, raw out[N] (no division): miso_pad / miso_lerp / miso_convolve_* (pad_and_sum.c:54-70 ...).
+// Steered beams, raw out[N] (miso_pad / miso_lerp / miso_convolve_*, pad_and_sum.c:54-70 ...).  Workgroup id = frame * groups +
+// group: the workgroup's W = blockDim / 64 waves stage each microphone chunk of ITS frame together (the frame is read from HBM
+// once per workgroup, not once per beam) and wave w then accumulates beam group * W + w out of the shared rows, in the
+// reference's mic order, so every beam is the one-direction result bit for bit.
+//   host path (bf::launch_miso): offsets == nullptr, one frame, one beam, offset a.miso_row, `miso_init` optionally seeds the
+//                                 accumulators (the single-signal helpers), out = miso_out[0..N)
+//   device path (launch_miso_batch): offsets [frames][beams] are table offsets (FIR_VEC: in floats, d * n * T), checked here
+//                                 against `entries` (status 1: outside the table, 2: FIR_VEC offset not a multiple of T);
+//                                 a rejected beam reads no table entry and its N samples are NaN.  gain != 0 scales the
+//                                 beam as api.c:519-523 does, (out / n) * gain, two float32 roundings.
 template <int ALGO, int NC>
-__global__ void __launch_bounds__(64) das_miso_kernel(BF_TABLE_PARAMS, const float* __restrict__ miso_init, float* __restrict__ miso_out, KArgs a)
+__global__ void __launch_bounds__(1024) das_miso_kernel(BF_TABLE_PARAMS, const float* __restrict__ miso_init, float* __restrict__ miso_out, KArgs a,
+                                                        const int32_t* __restrict__ offsets, int beams, int* __restrict__ status,
+                                                        long long entries, float gain, int out_stride)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = (int)(blockDim.x >> 6);
+    const int groups = (beams + nwaves - 1) / nwaves;
+    const int frame = (int)(blockIdx.x / (unsigned)groups);
+    const int beam = (int)(blockIdx.x % (unsigned)groups) * nwaves + wave;   // wave-uniform
+    const bool live = beam < beams;                                           // the last group may be partial
+    const size_t slot = (size_t)frame * beams + beam;
+
+    // this wave's table row (wave-uniform) and its verdict
+    long long row = a.miso_row;
+    int verdict = 0;
+    if (offsets != nullptr && live) {
+        const long long off = __builtin_amdgcn_readfirstlane(offsets[slot]);
+        const long long per = ALGO == ALGO_FIR_VEC ? a.n_taps : 1;
+        if (off < 0 || off + (long long)a.n_mics * per > entries) verdict = 1;
+        else if (ALGO == ALGO_FIR_VEC && off % per != 0) verdict = 2;
+        row = off / per;
+    }
+    const bool run = live && verdict == 0;
+
     {
         const int total4 = (a.mic_chunk * a.row_stride) >> 2;
         float4* z = reinterpret_cast<float4*>(lds);
         for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
+    const float* __restrict__ frame_sig = signals + (size_t)frame * a.m_total * a.n_samples;
     float acc[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c)
@@ -436,13 +468,21 @@ __global__ void __launch_bounds__(64) das_miso_kernel(BF_TABLE_PARAMS, const flo
         const int m0 = ch * a.mic_chunk;
         const int mc = min(a.mic_chunk, a.n_mics - m0);
         if (ch > 0) __syncthreads();
-        stage_chunk(lds, a, mics, signals, m0, mc, 0, 1, lane);
+        stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
         __syncthreads();
-        accumulate<ALGO, NC>(acc, lds, a, whole, frac, taps, (size_t)a.miso_row, m0, mc, lane);
+        if (run) accumulate<ALGO, NC>(acc, lds, a, whole, frac, taps, (size_t)row, m0, mc, lane);
     }
+    if (!live) return;
+    if (status != nullptr && lane == 0) status[slot] = verdict;
+    float* __restrict__ out = miso_out + slot * (size_t)out_stride;
+    const float nan = __int_as_float(0x7fc00000);
+    const float fn = (float)a.n_mics;
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (lane + c * kWave < a.n_samples) miso_out[lane + c * kWave] = acc[c];
+    for (int c = 0; c < NC; ++c) {
+        float v = acc[c];
+        if (gain != 0.0f) v = (v / fn) * gain;   // true division: a reciprocal multiply differs unless n is a power of two
+        if (lane + c * kWave < a.n_samples) out[lane + c * kWave] = run ? v : nan;
+    }
 }
 
 // ==================================================================================================
@@ -2937,15 +2977,28 @@ hipError_t launch_algo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, 
     }
 }
 
+// The beams of one das_miso_kernel launch (MisoBatch{} = the host path: one frame, one beam at KArgs::miso_row, one wave).
+struct MisoBatch {
+    const int32_t* offsets = nullptr;
+    int frames = 1, beams = 1, waves = 1;
+    int* status = nullptr;
+    long long entries = 0;
+    float gain = 0.0f;
+    int out_stride = 0;
+};
+
 template <int ALGO>
-hipError_t launch_miso_algo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, const float* init_dev, float* out_dev, hipStream_t stream)
+hipError_t launch_miso_algo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, const float* init_dev, float* out_dev, const MisoBatch& B,
+                            hipStream_t stream)
 {
+    const unsigned groups = (unsigned)((B.beams + B.waves - 1) / B.waves);
+    const int out_stride = B.out_stride > 0 ? B.out_stride : L.n_samples;
     auto go = [&](auto kernel) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)plan.lds_bytes);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(kWave), plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps,
-                           init_dev, out_dev, a);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)B.frames * groups), dim3((unsigned)B.waves * kWave), plan.lds_bytes, stream, L.signals, L.images, L.mics,
+                           L.tab.whole, L.tab.frac, L.tab.taps, init_dev, out_dev, a, B.offsets, B.beams, B.status, B.entries, B.gain, out_stride);
         return hipGetLastError();
     };
     switch (plan.nc) {
@@ -3239,19 +3292,37 @@ hipError_t launch_das(const DasLaunch& L, const DasPlan& plan, hipStream_t strea
     }
 }
 
-hipError_t launch_miso(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev,
-                       hipStream_t stream)
+namespace {
+hipError_t launch_miso_any(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev, const MisoBatch& B,
+                           hipStream_t stream)
 {
     KArgs a = make_args(L, plan);
     a.miso_row = row_offset;
     switch (L.algo) {
-        case ALGO_PAD: return launch_miso_algo<ALGO_PAD>(L, a, plan, init_dev, out_dev, stream);
-        case ALGO_LERP: return launch_miso_algo<ALGO_LERP>(L, a, plan, init_dev, out_dev, stream);
-        case ALGO_HYBRID: return launch_miso_algo<ALGO_HYBRID>(L, a, plan, init_dev, out_dev, stream);
-        case ALGO_FIR_NAIVE: return launch_miso_algo<ALGO_FIR_NAIVE>(L, a, plan, init_dev, out_dev, stream);
-        case ALGO_FIR_VEC: return launch_miso_algo<ALGO_FIR_VEC>(L, a, plan, init_dev, out_dev, stream);
+        case ALGO_PAD: return launch_miso_algo<ALGO_PAD>(L, a, plan, init_dev, out_dev, B, stream);
+        case ALGO_LERP: return launch_miso_algo<ALGO_LERP>(L, a, plan, init_dev, out_dev, B, stream);
+        case ALGO_HYBRID: return launch_miso_algo<ALGO_HYBRID>(L, a, plan, init_dev, out_dev, B, stream);
+        case ALGO_FIR_NAIVE: return launch_miso_algo<ALGO_FIR_NAIVE>(L, a, plan, init_dev, out_dev, B, stream);
+        case ALGO_FIR_VEC: return launch_miso_algo<ALGO_FIR_VEC>(L, a, plan, init_dev, out_dev, B, stream);
         default: return hipErrorInvalidValue;
     }
+}
+}  // namespace
+
+hipError_t launch_miso(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev,
+                       hipStream_t stream)
+{
+    return launch_miso_any(L, plan, row_offset, init_dev, out_dev, MisoBatch{}, stream);
+}
+
+hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int beams, long long entries, float gain,
+                             float* d_out, int out_stride, int* d_status, hipStream_t stream)
+{
+    if (L.frames < 1 || beams < 1 || out_stride < L.n_samples) return hipErrorInvalidValue;
+    MisoBatch B;
+    B.offsets = d_offsets; B.frames = L.frames; B.beams = beams; B.waves = std::min(beams, kMisoWaves);
+    B.status = d_status; B.entries = entries; B.gain = gain; B.out_stride = out_stride;
+    return launch_miso_any(L, plan, 0, nullptr, d_out, B, stream);
 }
 
 }  // namespace bf

@@ -374,4 +374,46 @@ hipError_t launch_power_center(const float* d_power, int frames, int rows, int c
     return hipGetLastError();
 }
 
+namespace {
+
+// np.argmax order on (value, index) pairs: a NaN beats every number, a larger value beats a smaller one, and among equals (two
+// NaNs included) the lower index wins.  (-inf, INT_MAX) loses to every real entry.
+__device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi)
+{
+    const bool nan_v = v != v, nan_o = ov != ov;
+    const bool take = nan_o ? (!nan_v || oi < i) : (!nan_v && (ov > v || (ov == v && oi < i)));
+    if (take) { v = ov; i = oi; }
+}
+
+// One workgroup per frame: the loudest direction of the map -> its table offset (bf_peak_offsets_device).
+__global__ void __launch_bounds__(256) peak_offsets_kernel(const float* __restrict__ power, int image_stride, int n_dirs, int offset_per_dir,
+                                                           int* __restrict__ offsets)
+{
+    __shared__ float rv[4];
+    __shared__ int ri[4];
+    const float* img = power + (size_t)blockIdx.x * image_stride;
+    float v = -INFINITY;
+    int i = INT32_MAX;
+    for (int j = threadIdx.x; j < n_dirs; j += blockDim.x) argmax_merge(v, i, img[j], j);
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(v, off, 64);
+        const int oi = __shfl_xor(i, off, 64);
+        argmax_merge(v, i, ov, oi);
+    }
+    if ((threadIdx.x & 63) == 0) { rv[threadIdx.x >> 6] = v; ri[threadIdx.x >> 6] = i; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) argmax_merge(v, i, rv[w], ri[w]);
+        offsets[blockIdx.x] = i * offset_per_dir;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_peak_offsets(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, hipStream_t stream)
+{
+    hipLaunchKernelGGL(peak_offsets_kernel, dim3(frames), dim3(256), 0, stream, d_power, image_stride, n_dirs, offset_per_dir, d_offsets);
+    return hipGetLastError();
+}
+
 }  // namespace bf

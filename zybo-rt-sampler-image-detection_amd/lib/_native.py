@@ -95,6 +95,9 @@ _sig("bf_publish_frame", None, FP)
 _sig("bf_miso_listen_block", C.c_int, FP, C.c_float)
 _sig("bf_get_steer", C.c_int, IP)
 _sig("bf_das_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, IP, C.c_int, C.c_int, C.c_int, C.c_void_p)
+_sig("bf_miso_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, IP, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+     C.c_void_p)
+_sig("bf_peak_offsets_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
 _sig("bf_plan_das", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))
 _sig("bf_ingest", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, FP)
 _sig("bf_ingest_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
