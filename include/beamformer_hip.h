@@ -210,7 +210,8 @@ void bf_jet_lut(unsigned char *out768);
 /* ---- heat-map post-processing on the device (PC/src/visual.py; display side of the path) ----
  * bf_heatmap_colorize_device: visual.py:143-185 -- d_power float32 [frames][MAX_RES_X*MAX_RES_Y] -> d_small uint8
  *   [frames][MAX_RES_Y][MAX_RES_X][3] (reversed-jet colours, flipped as the reference indexes it) and should_overlay flags.
- *   Reference defaults: threshold 1e-7, amount 0.5, exponent 5.
+ *   Reference defaults: threshold 1e-7, amount 0.5, exponent 5.  should_overlay follows NumPy's `np.max(image) > threshold`: a frame that
+ *   contains a NaN has a NaN maximum, so it comes out blank with flag 0 (visual.py:156-162) and leaves its neighbours in the batch alone.
  * bf_heatmap_overlay_device: cv2.resize(INTER_LINEAR) to out_w x out_h (:186), res = w_prev*prev + w_new*new (:450, 0.5/0.5;
  *   d_prev uint8 [out_h][out_w][3] is the carried state, updated in place), then onto the camera frames
  *   w_cam*frame + w_heat*res (:452, 0.9/0.9) when d_camera is not NULL.  d_out uint8 [frames][out_h][out_w][3].

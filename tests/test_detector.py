@@ -41,10 +41,10 @@ def test_gpu_decode_and_nms_match_oracle(native, half, nhwc):
     for b in range(B):
         order = np.argsort(-scores[b], kind="stable")[:1024]
         keep = D.nms(boxes[b][order], scores[b][order], 0.45, 300)
-        want = np.concatenate([boxes[b][order][keep], scores[b][order][keep][:, None]], axis=1)
+        want = np.concatenate([boxes[b][order][keep], scores[b][order][keep][:, None], cls[b][order][keep][:, None]], axis=1)
         assert n[b] == len(keep) and n[b] > 3
         assert not out[b, n[b]:].any()                 # rows past the kept boxes are zeros
-        got = out[b, : n[b], :5]
+        got = out[b, : n[b]]
         gi, wi = np.lexsort((got[:, 0], -got[:, 4])), np.lexsort((want[:, 0], -want[:, 4]))
         assert np.allclose(got[gi], want[wi], rtol=2e-5, atol=2e-4)
 

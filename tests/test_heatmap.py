@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import util
+from test_postproc_f64 import COLOR_BAND, ambiguous_cap, center_tol
 
 
 def _map(name="cfg2", sig="s3"):
@@ -62,6 +63,9 @@ def test_gpu_heatmap_matches_oracle(native, name, sig):
         gi = np.flatnonzero((lut == got_small[y, x].astype(int)).all(axis=1))
         wi = np.flatnonzero((lut == want_small[y, x].astype(int)).all(axis=1))
         assert gi.size and wi.size and np.abs(gi[:, None] - wi[None, :]).min() <= 1
+    # tighter (tests/test_postproc_f64.py: band and cap): equal to the float64 colour except on the pixels float32 rounding can move
+    _, wrong, amb, _ = V.check_small(got_small, img, mult=COLOR_BAND)
+    assert not wrong.any() and amb.sum() <= ambiguous_cap(img.size), (int(wrong.sum()), int(amb.sum()))
     # upscale + temporal blend + camera overlay: exact, given the kernel's own small image
     cam = torch.from_numpy(np.random.default_rng(2).integers(0, 256, (2, 640, 640, 3), dtype=np.uint8)).cuda()
     two = small.expand(2, -1, -1, -1).contiguous()
@@ -88,19 +92,22 @@ def test_gpu_reference_named_functions(native):
     cx, cy = visual.find_power_center(np.clip(img, 1e-12, None))
     wx, wy = V.find_power_center(img)
     assert abs(cx - wx) < 1e-3 and abs(cy - wy) < 1e-3
+    fx, fy, gap, _ = V.find_power_center_f64(img)                                 # tighter: float64, the mask settled (tests/test_postproc_f64.py)
+    assert gap >= 1e-5 and abs(cx - fx) <= center_tol(57) and abs(cy - fy) <= center_tol(57), (cx, cy, fx, fy)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,with_cam,n_frames", [(640, 640, False, 3), (322, 200, True, 3), (322, 200, False, 3), (1280, 720, True, 3), (4, 3, True, 3),
-                                                   (256, 128, True, 60), (640, 640, True, 11)])
+                                                   (256, 128, True, 60), (640, 640, True, 11), (128, 64, True, 5), (644, 360, True, 4)])
 def test_gpu_overlay_both_kernels(native, w, h, with_cam, n_frames):
     """bf_heatmap_overlay_device picks the tiled kernel when the width allows it and the one-pixel kernel otherwise: both equal the
     oracle's resize + blend chain byte for byte, with and without a camera frame, over the frames of a batch with a carried `prev`
-    (60 frames at 256 x 128: the tile's source pixels of all frames do not fit LDS at once -- three chunks; 11 frames: a ragged group of eight)."""
+    (60 frames at 256 x 128: the tile's source pixels of all frames do not fit LDS at once -- three chunks; 11 frames: a ragged group of eight;
+    128 x 64: the tile kernel shrinking the 101 rows; 644 x 360: from the as-shipped 57 x 32 grid)."""
     import torch
     import visual
     import visual_np as V
-    c = util.configure("cfg2")
+    c = util.configure("shipped" if (w, h) == (644, 360) else "cfg2")
     rng = np.random.default_rng(w * 7 + h)
     small = rng.integers(0, 256, (n_frames, c["Y"], c["X"], 3), dtype=np.uint8)
     cam = rng.integers(0, 256, (n_frames, h, w, 3), dtype=np.uint8)

@@ -54,11 +54,13 @@ __global__ void __launch_bounds__(1024) colorize_kernel(const float* __restrict_
     for (int i = threadIdx.x; i < D; i += blockDim.x) {
         const float v = img[i];
         vmax = fmaxf(vmax, v);
-        smin = fminf(smin, fmaxf(v, 1e-12f));
+        // fmaxf / fminf drop a NaN where np.max keeps it: a NaN rides through the min reduction as -inf (the clipped values are >= 1e-12)
+        smin = v != v ? -INFINITY : fminf(smin, fmaxf(v, 1e-12f));
     }
     vmax = block_reduce(vmax, red, true);
     smin = block_reduce(smin, red, false);
-    const bool overlay = vmax > threshold;
+    // np.max of a map with a NaN is NaN and `NaN > threshold` is false: blank image, flag 0 (visual.py:156-162)
+    const bool overlay = smin != -INFINITY && vmax > threshold;
     const float lmin = log10f(smin);
     // max over the image of log10(clip(v)) - log10(min): log10 is monotonic, so it is log10(clip(max)) - lmin
     const float lmax = log10f(fmaxf(vmax, 1e-12f)) - lmin;
