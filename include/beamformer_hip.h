@@ -167,7 +167,8 @@ int bf_das_device(int algo, const float *d_signals, int m_total, float *d_images
  * algo      : BF_PAD -> miso_pad, BF_LERP -> miso_lerp, BF_HYBRID -> miso_convolve_hybrid, BF_FIR_VEC -> miso_convolve_vectorized;
  *             BF_FIR_NAIVE is refused (the reference has no MISO form of it).  Uses the table the matching load_coefficients_*
  *             loaded -- the one bf_das_device reads, so one load serves maps and beams.
- * d_signals : HIP device pointer, float32 [frames][m_total][N_SAMPLES], mic-major, as bf_das_device (no dead-row masking)
+ * d_signals : HIP device pointer, float32 [frames][m_total][N_SAMPLES], mic-major, as bf_das_device (no dead-row masking here:
+ *             bf_ingest_stream_device's row mask zeroes dead rows when it builds the frames)
  * adaptive_array / n : HOST array of the active mic rows, handled as bf_das_device handles it
  * d_offsets : HIP device pointer, int32 [frames][beams]: the `offset` argument of the matching miso_* call -- the flat table
  *             offset d * n, for BF_FIR_VEC the float offset d * n * N_TAPS into the tap table
@@ -203,6 +204,45 @@ int bf_peak_offsets_device(const float *d_power, int frames, int image_stride, i
  * The one element the reference reads past the end of the datagram (last array, last row, x = 0) is defined as 0. */
 int bf_ingest(const void *packets, int n_arrays, int rows, int columns, float *frame);
 int bf_ingest_device(const void *d_packets, int n_arrays, int rows, int columns, float *d_frame, void *stream);
+
+/* ---- batched stream ingest: a stream of datagrams -> a batch of frames in one enqueue (the front door of the device path) ----
+ * d_packets  : HIP device pointer, 4-byte aligned: n_datagrams datagrams back to back, each 8 + 4*N_MICROPHONES bytes laid out as
+ *              `msg` above (receiver.h:51-59).  Frame f is built from datagrams [f*hop, f*hop + N_SAMPLES); hop < N_SAMPLES gives
+ *              overlapping windows, hop > N_SAMPLES skips datagrams.
+ * n_arrays / rows / columns : as bf_ingest_device (rows x columns is the 8 x 8 tile of config.json:7-8)
+ * m_total    : rows of every output frame, >= n_arrays*rows*columns (what bf_das_device / bf_miso_device take as m_total)
+ * d_row_mask : HIP device pointer, m_total bytes, or NULL for no mask.  A non-zero byte zeroes that row of every frame, as get_data
+ *              zeroes its dead microphones (api.c:830-859; bf_default_disabled_mics below lists them).
+ * protocol_ver : the version byte every header is expected to carry (FPGA_PROTOCOL_VERSION, config.json)
+ * d_frames   : HIP device pointer, 4-byte aligned, float32 [frames][m_total][N_SAMPLES], mic-major.  EVERY element is written:
+ *              rows s < n_arrays*rows*columns hold the reference's conversion in its serpentine order (receiver.c:122-145), value
+ *              (float)v * 2^-24, bit-identical to bf_ingest_device on the frame's slice of the stream; masked rows and rows
+ *              [n_arrays*rows*columns, m_total) are zero.  The one element the reference reads past the end of the datagram (all
+ *              arrays present, last row, x = 0) is 0 here too: in a stream that address is the next datagram's header, and it is
+ *              never read as data.
+ * d_status   : HIP device pointer, int32 [frames][4], or NULL.  When given, every entry is written by every call (the caller clears
+ *              nothing) and no entry depends on the order workgroups run in.  For frame f, over its N_SAMPLES datagrams:
+ *                [0] datagrams whose protocol_ver byte differs from `protocol_ver`   (receive_header_data's check, receiver.c:224-239)
+ *                [1] datagrams whose n_arrays byte differs from `n_arrays`           (same; both bytes are compared as unsigned values)
+ *                [2] t in [1, N_SAMPLES) with counter[t] - counter[t-1] != 1 in wrapping int32 arithmetic -- counted inside the frame
+ *                    only: a jump between the last datagram of one frame and the first of the next is in neither frame's count
+ *                [3] the counter of the frame's first datagram
+ *              [2] and [3] are an extension: the reference stores `counter` and never interprets it.  A non-zero entry changes
+ *              nothing about d_frames; what to do with such a frame is the caller's decision.
+ * stream     : hipStream_t (0 = null stream).  Enqueue only: no allocation, no synchronisation, graph-capturable from the first call.
+ *              The fast form of the kernel (8-byte datagram reads, 16-byte stores) needs d_packets 8-byte aligned with N_MICROPHONES even
+ *              and 64 % columns == 0, and d_frames 16-byte aligned with N_SAMPLES a multiple of 4; other shapes give the same result
+ *              through narrower accesses.
+ * Returns 0, or -1 (see bf_last_error, which names the failing value; nothing enqueued) for a null d_packets or d_frames, frames < 1,
+ * hop < 1, n_arrays / rows / columns < 1, n_arrays*rows*columns > N_MICROPHONES or > m_total, (frames - 1)*hop + N_SAMPLES >
+ * n_datagrams, a d_packets or d_frames that is not 4-byte aligned, more workgroups than one launch holds, or no GPU.  The arguments
+ * are checked before device bring-up. */
+int bf_ingest_stream_device(const void *d_packets, long long n_datagrams, int n_arrays, int rows, int columns,
+                            int hop, int frames, int m_total, const unsigned char *d_row_mask, int protocol_ver,
+                            float *d_frames, int *d_status, void *stream);
+/* get_data's 122 dead rows (api.c:835-851), strictly increasing -- the list the get_data shim here applies: returns the count, fills
+ * out[0..count) when out is not NULL. */
+int bf_default_disabled_mics(int *out);
 
 /* bf_jet_lut: visual.py:26-49 generate_color_map("jet") -- the colour table the colourise kernel uses, uint8 [256][3]. */
 void bf_jet_lut(unsigned char *out768);

@@ -812,6 +812,13 @@ void bf_publish_frame(const float* signals)
     s.published.assign(signals, signals + n);
 }
 
+// PC/src/api.c:835-856 zeroes the rows of the 122 microphones that are dead on the authors' arrays (get_data; bf_default_disabled_mics).
+static const short kDeadMics[] = {0, 1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30,
+    31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 64,
+    83, 84, 85, 86, 87, 88, 89, 90, 91, 92, 93, 94, 95, 96, 98, 99, 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111,
+    112, 135, 137, 143, 145, 146, 147, 148, 149, 150, 151, 152, 153, 154, 159, 160, 162, 163, 164, 165, 166, 167, 169, 175,
+    184, 192, 193, 194, 195, 196, 197, 198, 199, 200, 201};
+
 static bool copy_published(float* out, bool mask_dead)
 {
     State& s = S();
@@ -821,13 +828,7 @@ static bool copy_published(float* out, bool mask_dead)
     std::memcpy(out, s.published.data(), n * sizeof(float));
     if (mask_dead) {
         if (s.disabled_default) {
-            // PC/src/api.c:835-856 zeroes the rows of the 122 microphones that are dead on the authors' arrays.
-            static const short dead[] = {0, 1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30,
-                31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 64,
-                83, 84, 85, 86, 87, 88, 89, 90, 91, 92, 93, 94, 95, 96, 98, 99, 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111,
-                112, 135, 137, 143, 145, 146, 147, 148, 149, 150, 151, 152, 153, 154, 159, 160, 162, 163, 164, 165, 166, 167, 169, 175,
-                184, 192, 193, 194, 195, 196, 197, 198, 199, 200, 201};
-            s.disabled_mics.assign(dead, dead + sizeof(dead) / sizeof(dead[0]));
+            s.disabled_mics.assign(kDeadMics, kDeadMics + sizeof(kDeadMics) / sizeof(kDeadMics[0]));
             s.disabled_default = false;
         }
         for (int mic : s.disabled_mics)
@@ -1087,6 +1088,46 @@ int bf_ingest(const void* packets, int n_arrays, int rows, int columns, float* f
     ok = ok && HIP_OK(sync_short(s.stream));
     if (!ok) poison(frame, out_n);
     return ok ? 0 : -1;
+}
+
+int bf_ingest_stream_device(const void* d_packets, long long n_datagrams, int n_arrays, int rows, int columns, int hop, int frames, int m_total,
+                            const unsigned char* d_row_mask, int protocol_ver, float* d_frames, int* d_status, void* stream)
+{
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    sizes_from_env_once();
+    const int M = s.sz.n_microphones, N = s.sz.n_samples;
+    if (!d_packets) { set_error("bf_ingest_stream_device: d_packets is null"); return -1; }
+    if (!d_frames) { set_error("bf_ingest_stream_device: d_frames is null"); return -1; }
+    if (frames < 1) { set_error("bf_ingest_stream_device: frames = %d < 1", frames); return -1; }
+    if (hop < 1) { set_error("bf_ingest_stream_device: hop = %d < 1", hop); return -1; }
+    if (n_arrays < 1) { set_error("bf_ingest_stream_device: n_arrays = %d < 1", n_arrays); return -1; }
+    if (rows < 1) { set_error("bf_ingest_stream_device: rows = %d < 1", rows); return -1; }
+    if (columns < 1) { set_error("bf_ingest_stream_device: columns = %d < 1", columns); return -1; }
+    const long long mics_out = (long long)n_arrays * rows * columns;
+    if (mics_out > M) { set_error("bf_ingest_stream_device: n_arrays*rows*columns = %lld > N_MICROPHONES = %d", mics_out, M); return -1; }
+    if (mics_out > m_total) { set_error("bf_ingest_stream_device: n_arrays*rows*columns = %lld > m_total = %d", mics_out, m_total); return -1; }
+    const long long needed = (long long)(frames - 1) * hop + N;
+    if (needed > n_datagrams) {
+        set_error("bf_ingest_stream_device: (frames - 1) * hop + N_SAMPLES = %lld > n_datagrams = %lld", needed, n_datagrams);
+        return -1;
+    }
+    if (reinterpret_cast<uintptr_t>(d_packets) & 3) { set_error("bf_ingest_stream_device: d_packets = %p is not 4-byte aligned", d_packets); return -1; }
+    if (reinterpret_cast<uintptr_t>(d_frames) & 3) { set_error("bf_ingest_stream_device: d_frames = %p is not 4-byte aligned", (const void*)d_frames); return -1; }
+    const long long tiles = (long long)frames * ((N + 63) / 64) * ((m_total + 63) / 64) + frames;
+    if (tiles > 0x7fffff00ll) { set_error("bf_ingest_stream_device: frames = %d needs %lld workgroups, more than one launch holds", frames, tiles); return -1; }
+    if (!ensure_device()) return -1;
+    const int stride = 8 + 4 * M;   // sizeof(msg), receiver.h:51-59
+    return HIP_OK(bf::launch_ingest_stream(d_packets, stride, N, M, (int)mics_out, rows, columns, hop, frames, m_total, d_row_mask, protocol_ver, n_arrays,
+                                           d_frames, d_status, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
+int bf_default_disabled_mics(int* out)
+{
+    const int n = (int)(sizeof(kDeadMics) / sizeof(kDeadMics[0]));
+    if (out)
+        for (int i = 0; i < n; ++i) out[i] = kDeadMics[i];
+    return n;
 }
 
 // ---------------------------------------------------------------- heat-map post-processing (visual.py)

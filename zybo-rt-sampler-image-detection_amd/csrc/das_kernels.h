@@ -97,6 +97,11 @@ hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int3
 // FPGA protocol-v2 datagrams (one per sample instant) -> float32 [n_mics_out][n_samples] mic-major frame (receiver.c:94-151).
 hipError_t launch_ingest(const void* d_packets, int packet_stride, int header_bytes, int n_samples, int n_mics_out, int stream_len,
                          int rows, int columns, float* d_frame, hipStream_t stream);
+// A stream of datagrams -> float32 [frames][m_total][n_samples], frame f from datagrams [f*hop, f*hop + n_samples) (bf_ingest_stream_device):
+// rows named by d_row_mask (m_total bytes, or null) and rows [n_mics_out, m_total) are zero; d_status int32 [frames][4] or null.
+hipError_t launch_ingest_stream(const void* d_packets, int packet_stride, int n_samples, int stream_len, int n_mics_out, int rows, int columns,
+                                int hop, int frames, int m_total, const unsigned char* d_row_mask, int protocol_ver, int n_arrays,
+                                float* d_frames, int* d_status, hipStream_t stream);
 
 // heat-map post-processing (PC/src/visual.py:143-188, 295-322, 450-452); see heatmap_kernels.hip
 hipError_t launch_colorize(const float* d_power, int frames, int res_x, int res_y, float threshold, float amount, float exponent,

@@ -1,6 +1,7 @@
 """Fused acoustic heat-map -> overlay -> detection on one MI355X (BASELINE.json config 4).
 
 Per batch of B (audio window, camera frame) pairs, everything stays in HBM:
+  0. (step_packets) datagram stream -> the B windows                 bf_ingest_stream_device (csrc/ingest_kernel.hip)
   1. delay-and-sum power maps of the B windows                      bf_das_device           (csrc/das_kernels.hip)
   2. colourise, upscale to the camera size, temporal blend, overlay  bf_heatmap_*_device     (csrc/heatmap_kernels.hip)
   3. YOLOv5s-shaped detector on the overlaid frames                  PyTorch-ROCm module graph, convolutions = csrc/conv_kernels.hip
@@ -51,3 +52,10 @@ class FusedPipeline:
         frames = self.stream_state.overlay(small, d_camera)
         boxes, counts = self.detector.detect(frames, conf_thres)
         return power, frames, boxes, counts
+
+    def step_packets(self, d_packets, d_camera, ingest, conf_thres=0.1):
+        """The same batch starting from the datagram stream: d_packets uint8 [T, 8 + 4 * N_MICROPHONES] -> ingest.frames (an
+        ingest.PacketIngest: windows, dead-row mask, header report; one launch) -> step.  Returns step's tuple plus the ingest status
+        int32 [B, 4]; d_camera holds one frame per window, B = ingest.n_frames(T)."""
+        d_windows, status = ingest.frames(d_packets)
+        return self.step(d_windows, d_camera, conf_thres) + (status,)
