@@ -131,7 +131,8 @@ int bf_gpu_available(void);
  * (direction-outer, chosen for tables without structure), 4 shifted copies (8-tap FIR), 5 shifted copies (sweep, two
  * frames per workgroup: batched launches of pad / lerp), 6 shifted copies for long blocks (256 < N_SAMPLES <= 1024: LDS image in
  * two halves, conflict-free lane mapping), 7 hybrid sweep with shared windows, two frames per workgroup (batched launches of the
- * 8-tap FIR flavours), 8 the two-frame sweep on frame-interleaved rows (batched lerp); -1 before the first launch. */
+ * 8-tap FIR flavours), 8 the two-frame sweep on frame-interleaved rows (batched lerp), 9 strided with the previous window's tail in
+ * front of every row (bf_das_stream_device); -1 before the first launch. */
 int bf_last_das_variant(void);
 /* Profiling builds only (hipcc -DBF_STAMPS, scripts/dev/phase_stamps.py): per-phase wave time of the batched pad / lerp kernel,
  * summed over all waves since the last clear: out16[0..7] = sweep, wait, staging, wait, wait, parking, wait, ordered power sum
@@ -195,6 +196,48 @@ int bf_miso_device(int algo, const float *d_signals, int m_total, int frames, co
  * (n_dirs - 1) * offset_per_dir > INT_MAX, or no GPU. */
 int bf_peak_offsets_device(const float *d_power, int frames, int image_stride, int n_dirs, int offset_per_dir,
                            int *d_offsets, void *stream);
+
+/* ---- continuous-stream mode of the device path (BF_PAD, BF_LERP): delays read the previous window ----
+ * Every other entry point treats a window as if the world began at its first sample: a microphone delayed by p samples gives
+ * nothing to the first p outputs (out[p + i] += s[i], zero prefix), as the reference does.  That is the first item of the reference
+ * authors' own low-level future work (PC/TODO.md, "Padding -> read previous samples": the zero prefix "introduces clipping", "a
+ * better solution is to read the last N samples of the previous signal", a ring buffer for it "has not been put in place").  Here
+ * the samples a delay reaches before the start of frame f are taken from frame f - 1 of the batch, for f = 0 from d_prev.
+ *
+ * Definition.  N = N_SAMPLES; frames float32 [frames][m_total][N], mic-major, as bf_das_device takes them; `hop` = distance in samples
+ * between the starts of consecutive frames (the hop of bf_ingest_stream_device).  For frame f, microphone row r:
+ *     x_r(t) = frame f's own sample [r][t]          for 0 <= t < N
+ *     x_r(t) = prev_f[r][hop + t]                   for t < 0
+ * prev_f = frame f - 1 of the call for f >= 1; prev_0 = d_prev, float32 [m_total][N] on the device: the frame that started `hop`
+ * samples before frame 0 (NULL: all zeros -- silence before the stream).  With p_m, h_m the loaded table's entries for (direction,
+ * mic m) and r_m = adaptive_array[m], summed in mic order m = 0 .. n-1 starting from 0.0f, for EVERY t in [0, N):
+ *     pad :  out[t] = sum_m x_{r_m}(t - p_m)
+ *     lerp:  out[t] = sum_m fma(h_m, x_{r_m}(t - p_m) - x_{r_m}(t - p_m - 1), x_{r_m}(t - p_m - 1))
+ * (the reference drops the i < 0 edge samples; this mode does not).  For t >= H both equal miso_pad / miso_lerp bit for bit.
+ * With d_prev == NULL and silence as history, lerp gives h * s[0] at t = p where the reference gives 0: that follows from the
+ * definition, the sample before the stream is 0, not absent.
+ * A map entry is image[d] = (sum_t (out_d[t] / n)^2) / N, summed in t order in float32 as bf_das_device sums it.
+ *
+ * History: H = max_whole (pad) or max_whole + 1 (lerp), max_whole the largest whole-sample delay of the loaded table.  The calls
+ * require H <= hop <= N_SAMPLES.  bf_stream_history returns H for BF_PAD / BF_LERP, -1 when that table is not loaded or for any
+ * other algo (it records no error).
+ *
+ * bf_miso_stream_device: bf_miso_device's contract -- d_offsets, mic_gain, d_status codes, NaN beams for rejected offsets,
+ * out_stride, adaptive_array -- with the two extra arguments.  bf_das_stream_device: bf_das_device's contract (direction shards,
+ * image_stride, adaptive_array); maps in this mode always take the strided kernel layout (bf_last_das_variant 9; the beam call
+ * leaves that value alone), no digest is built.  Both only enqueue and allocate nothing after the first call (a new adaptive
+ * array synchronises the device, as in bf_das_device); graph-capturable after one warm-up call.  d_prev is read by the launch: keep
+ * it alive and unchanged until the launch has run.
+ * Return 0, or -1 (bf_last_error names the value; nothing enqueued) for: BF_HYBRID, BF_FIR_NAIVE, BF_FIR_VEC (they read ahead of
+ * the window's end, which a causal stream cannot supply) or an unknown algo; hop < 1; hop > N_SAMPLES; H > hop; a table with
+ * entries beyond N_SAMPLES (the loader clamps them, a stream cannot reach them); and everything bf_miso_device / bf_das_device
+ * refuse.  All arguments are checked before device bring-up; the table checks need the device the table lives on. */
+int bf_stream_history(int algo);
+int bf_miso_stream_device(int algo, const float *d_signals, int m_total, int frames, int hop, const float *d_prev,
+                          const int *adaptive_array, int n, const int *d_offsets, int beams, float mic_gain,
+                          float *d_out, int out_stride, int *d_status, void *stream);
+int bf_das_stream_device(int algo, const float *d_signals, int m_total, float *d_images, int image_stride, int frames, int hop,
+                         const float *d_prev, const int *adaptive_array, int n, int dir_begin, int dir_end, void *stream);
 
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
@@ -387,6 +430,8 @@ int bf_plan_das(int algo, int n, int frames, int dir_begin, int dir_end, int max
 /* Copies of the tables as resident on the GPU after load_coefficients_lerp / _convolve_hybrid (the reference
  * keeps them in file-scope globals: lerp_and_sum.c:33-34, hybrid_convolve_and_sum.c:40-41). */
 int bf_get_lerp_tables(int *whole, float *h, int n);
+/* The whole-sample table as resident after load_coefficients_pad (entries beyond N_SAMPLES clamped to it), n = entries loaded. */
+int bf_get_pad_table(int *whole, int n);
 int bf_get_hybrid_tables(int *whole, float *taps, int n);
 
 /* ---- steering tables: PC/src/directions.pyx, bit-exact, host C++ (float64 with the float32-typed

@@ -80,6 +80,7 @@ struct TableSet {
     bool loaded = false;
     int entries = 0;      // n of the load call = D * M
     int max_whole = 0;
+    int clamped = 0;      // entries beyond N_SAMPLES that the loader clamped to it (the continuous-stream calls refuse such a table)
     DevBuf<int32_t> whole;
     DevBuf<float> frac;
     DevBuf<float> taps;
@@ -99,7 +100,7 @@ struct TableSet {
     void invalidate_digests() { for (auto& d : digests) d.key = DigestKey{}; }   // (buffers stay allocated; keys never match again)
     void drop()
     {
-        loaded = false; entries = 0; max_whole = 0;
+        loaded = false; entries = 0; max_whole = 0; clamped = 0;
         whole.release(); frac.release(); taps.release();
         for (auto& d : digests) { d.buf.release(); d.key = DigestKey{}; d.direct = false; d.used = 0; }
     }
@@ -512,15 +513,16 @@ void run_delay_host(int algo, const float* signal, float* out, bool accumulate, 
 
 // Integer table sanity shared by the loaders: no negative delays; values beyond N contribute nothing, so they
 // are clamped to N (keeps the LDS zero prefix bounded).
-bool sanitize_whole(std::vector<int32_t>& w, int n_samples, int* max_whole, const char* who)
+bool sanitize_whole(std::vector<int32_t>& w, int n_samples, int* max_whole, const char* who, int* clamped = nullptr)
 {
-    int mx = 0;
+    int mx = 0, cl = 0;
     for (size_t i = 0; i < w.size(); ++i) {
         if (w[i] < 0) { set_error("%s: negative delay %d at index %zu (the reference would write out of bounds)", who, w[i], i); return false; }
-        if (w[i] > n_samples) w[i] = n_samples;
+        if (w[i] > n_samples) { w[i] = n_samples; ++cl; }
         mx = std::max(mx, w[i]);
     }
     *max_whole = mx;
+    if (clamped) *clamped = cl;
     return true;
 }
 
@@ -532,10 +534,10 @@ bool load_whole_only(int slot, const int* whole, int n, const char* who)
     if (!ensure_device()) return false;
     std::vector<int32_t> w(whole, whole + n);
     TableSet& t = s.tab[slot];
-    int mx = 0;
-    if (!sanitize_whole(w, s.sz.n_samples, &mx, who)) return false;
+    int mx = 0, cl = 0;
+    if (!sanitize_whole(w, s.sz.n_samples, &mx, who, &cl)) return false;
     if (!upload(t.whole, w.data(), w.size())) return false;
-    t.loaded = true; t.entries = n; t.max_whole = mx;
+    t.loaded = true; t.entries = n; t.max_whole = mx; t.clamped = cl;
     t.invalidate_digests();   // new table values: any digest built from the old ones is stale
     return true;
 }
@@ -692,10 +694,10 @@ void load_coefficients_lerp(float* delays, int n)
         w[(size_t)i] = (int)ip;
     }
     TableSet& t = s.tab[SLOT_LERP];
-    int mx = 0;
-    if (!sanitize_whole(w, s.sz.n_samples, &mx, "load_coefficients_lerp")) return;
+    int mx = 0, cl = 0;
+    if (!sanitize_whole(w, s.sz.n_samples, &mx, "load_coefficients_lerp", &cl)) return;
     if (!upload(t.whole, w.data(), w.size()) || !upload(t.frac, h.data(), h.size())) return;
-    t.loaded = true; t.entries = n; t.max_whole = mx;
+    t.loaded = true; t.entries = n; t.max_whole = mx; t.clamped = cl;
     t.invalidate_digests();   // new table values: any digest built from the old ones is stale
 }
 void unload_coefficients_lerp(void) { std::lock_guard<std::mutex> lock(S().mu); S().tab[SLOT_LERP].drop(); }
@@ -717,6 +719,16 @@ int bf_get_lerp_tables(int* whole, float* h, int n)
     bool ok = HIP_OK(hipMemcpy(whole, t.whole.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     ok = ok && HIP_OK(hipMemcpy(h, t.frac.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return ok ? 0 : -1;
+}
+
+int bf_get_pad_table(int* whole, int n)
+{
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    const TableSet& t = s.tab[SLOT_PAD];
+    if (!whole) { set_error("bf_get_pad_table: whole is null"); return -1; }
+    if (!t.loaded || n != t.entries) { set_error("bf_get_pad_table: %d requested, %d loaded", n, t.loaded ? t.entries : 0); return -1; }
+    return HIP_OK(hipMemcpy(whole, t.whole.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost)) ? 0 : -1;
 }
 
 // ---------------------------------------------------------------- convolve (full FIR)
@@ -1028,6 +1040,123 @@ int bf_miso_device(int algo, const float* d_signals, int m_total, int frames, co
     L.frames = frames;
     return HIP_OK(bf::launch_miso_batch(L, plan, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status,
                                         reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
+// ---------------------------------------------------------------- continuous-stream mode (pad / lerp)
+
+// What both stream calls check before device bring-up.  `who` names the entry point in the message.
+static bool stream_args_ok(const char* who, int algo, int m_total, int frames, int hop, const int* adaptive_array, int n)
+{
+    const int N = S().sz.n_samples;
+    if (algo == bf::ALGO_HYBRID || algo == bf::ALGO_FIR_NAIVE || algo == bf::ALGO_FIR_VEC) {
+        static const char* name[] = {"", "", "BF_HYBRID", "BF_FIR_NAIVE", "BF_FIR_VEC"};
+        set_error("%s: algo %s reads ahead of the window's end, which a causal stream cannot supply (continuous mode: BF_PAD, BF_LERP)", who, name[algo]);
+        return false;
+    }
+    if (algo != bf::ALGO_PAD && algo != bf::ALGO_LERP) { set_error("%s: unknown algo %d", who, algo); return false; }
+    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return false; }
+    if (hop < 1) { set_error("%s: hop = %d < 1", who, hop); return false; }
+    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return false; }
+    if (n < 1) { set_error("%s: n = %d < 1", who, n); return false; }
+    for (int i = 0; i < n; ++i)
+        if (adaptive_array[i] < 0 || adaptive_array[i] >= m_total) {
+            set_error("%s: adaptive_array[%d] = %d is not a row of frames with m_total = %d rows", who, i, adaptive_array[i], m_total);
+            return false;
+        }
+    return true;
+}
+
+// The loaded table's side of the contract: H <= hop, and no entry that the loader had to clamp.
+static bool stream_table_ok(const char* who, int algo, const TableSet& t, int slot, int hop)
+{
+    if (!t.loaded) { set_error("%s: %s has not been called", who, loader_name(slot)); return false; }
+    const int H = bf::stream_history(algo, t.max_whole);
+    if (H > hop) {
+        set_error("%s: the loaded table needs H = %d samples of history but hop = %d (continuous mode wants H <= hop)", who, H, hop);
+        return false;
+    }
+    if (t.clamped > 0) {
+        set_error("%s: %d entries of the loaded table lie beyond N_SAMPLES = %d; a stream with hop <= N_SAMPLES cannot reach that far back", who, t.clamped,
+                  S().sz.n_samples);
+        return false;
+    }
+    return true;
+}
+
+int bf_stream_history(int algo)
+{
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (algo != bf::ALGO_PAD && algo != bf::ALGO_LERP) return -1;
+    const TableSet& t = s.tab[slot_of(algo)];
+    return t.loaded ? bf::stream_history(algo, t.max_whole) : -1;
+}
+
+int bf_miso_stream_device(int algo, const float* d_signals, int m_total, int frames, int hop, const float* d_prev, const int* adaptive_array, int n,
+                          const int* d_offsets, int beams, float mic_gain, float* d_out, int out_stride, int* d_status, void* stream)
+{
+    static const char* who = "bf_miso_stream_device";
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    sizes_from_env_once();
+    const int N = s.sz.n_samples;
+    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"},
+                                                               {d_out, "d_out"}};
+    for (const auto& a : ptrs)
+        if (!a.p) { set_error("%s: %s is null", who, a.name); return -1; }
+    if (!stream_args_ok(who, algo, m_total, frames, hop, adaptive_array, n)) return -1;
+    if (beams < 1) { set_error("%s: beams = %d < 1", who, beams); return -1; }
+    if (out_stride < N) { set_error("%s: out_stride = %d < N_SAMPLES = %d", who, out_stride, N); return -1; }
+    if (!std::isfinite(mic_gain)) { set_error("%s: mic_gain = %g is not finite", who, (double)mic_gain); return -1; }
+    if (!ensure_device()) return -1;
+    const int slot = slot_of(algo);
+    const TableSet& t = s.tab[slot];
+    if (!stream_table_ok(who, algo, t, slot, hop)) return -1;
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    // planned as bf_miso_device plans: one beam of one frame
+    bf::DasLaunch L{};
+    L.algo = algo;
+    L.tab.whole = t.whole.p; L.tab.frac = t.frac.p; L.tab.taps = t.taps.p; L.tab.max_whole = t.max_whole;
+    L.n_mics = n; L.m_total = m_total; L.n_samples = N; L.n_taps = s.sz.n_taps; L.n_dirs = 1;
+    L.dir_begin = 0; L.dir_end = 1; L.image_stride = 1; L.image_origin = 0; L.frames = 1;
+    L.signals = d_signals; L.images = nullptr; L.mics = s.d_mics.p;
+    bf::DasPlan plan{};
+    if (!plan_or_error(L, &plan)) return -1;
+    L.frames = frames;
+    return HIP_OK(bf::launch_stream_beams(L, plan, d_prev, hop, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status,
+                                          reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
+int bf_das_stream_device(int algo, const float* d_signals, int m_total, float* d_images, int image_stride, int frames, int hop, const float* d_prev,
+                         const int* adaptive_array, int n, int dir_begin, int dir_end, void* stream)
+{
+    static const char* who = "bf_das_stream_device";
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    sizes_from_env_once();
+    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {d_images, "d_images"}, {adaptive_array, "adaptive_array"}};
+    for (const auto& a : ptrs)
+        if (!a.p) { set_error("%s: %s is null", who, a.name); return -1; }
+    if (!stream_args_ok(who, algo, m_total, frames, hop, adaptive_array, n)) return -1;
+    const int D = s.sz.dirs();
+    if (dir_begin < 0 || dir_end > D || dir_begin >= dir_end) { set_error("%s: bad direction range [%d,%d) of %d", who, dir_begin, dir_end, D); return -1; }
+    if (image_stride < dir_end - dir_begin) { set_error("%s: image_stride %d < %d directions", who, image_stride, dir_end - dir_begin); return -1; }
+    if (!ensure_device()) return -1;
+    const int slot = slot_of(algo);
+    if (!stream_table_ok(who, algo, s.tab[slot], slot, hop)) return -1;
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    bf::DasLaunch L{};
+    if (!describe(algo, slot, n, &L)) return -1;
+    L.signals = d_signals; L.images = d_images; L.m_total = m_total; L.frames = frames;
+    L.dir_begin = dir_begin; L.dir_end = dir_end; L.image_stride = image_stride; L.image_origin = dir_begin;
+    bf::DasPlan plan{};
+    const char* why = "";
+    if (bf::plan_stream_maps(L, s.n_cus, &plan, &why) != 0) { set_error("%s: unsupported shape: %s", who, why); return -1; }
+    if (!HIP_OK(bf::launch_stream_maps(L, plan, d_prev, hop, reinterpret_cast<hipStream_t>(stream)))) return -1;
+    s.last_variant = 9;
+    return 0;
 }
 
 int bf_peak_offsets_device(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, void* stream)

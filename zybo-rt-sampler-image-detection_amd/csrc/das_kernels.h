@@ -94,6 +94,18 @@ constexpr int kMisoWaves = 16;
 hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int beams, long long entries, float gain,
                              float* d_out, int out_stride, int* d_status, hipStream_t stream);
 
+// Continuous-stream mode (bf_das_stream_device / bf_miso_stream_device; pad and lerp): the samples a delay reaches before the start
+// of frame f come from frame f - 1 of the launch, for frame 0 from d_prev (float32 [m_total][N], the frame that started `hop`
+// samples earlier; null = silence).  stream_history: samples of history a table needs (max_whole for pad, max_whole + 1 for lerp,
+// -1 for the other flavours); the launches want history <= hop <= N.
+int stream_history(int algo, int max_whole);
+// Maps: always the strided layout (stream_map_kernel); `plan` comes from plan_stream_maps, never from plan_das.
+int plan_stream_maps(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why);
+hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, hipStream_t stream);
+// Beams (stream_beam_kernel): `plan` is the one-direction, one-frame plan launch_miso_batch takes.
+hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
+                               long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream);
+
 // FPGA protocol-v2 datagrams (one per sample instant) -> float32 [n_mics_out][n_samples] mic-major frame (receiver.c:94-151).
 hipError_t launch_ingest(const void* d_packets, int packet_stride, int header_bytes, int n_samples, int n_mics_out, int stream_len,
                          int rows, int columns, float* d_frame, hipStream_t stream);

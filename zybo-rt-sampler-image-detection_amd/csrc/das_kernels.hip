@@ -127,8 +127,9 @@ __device__ __forceinline__ RowHead request_row_head(const int32_t* __restrict__ 
 }
 
 // Accumulate mics [m0, m0+mc) of the table row starting at flat entry `row_base` (= d*M for direction d)
-// into acc[NC] (lane l holds samples l + 64 c).
-template <int ALGO, int NC>
+// into acc[NC] (lane l holds samples l + 64 c).  HIST (the continuous-stream kernels): the columns in front of a staged row hold
+// the samples that precede the window instead of zeros, so lerp's i >= 0 guard is not applied (pad has none).
+template <int ALGO, int NC, bool HIST = false>
 __device__ __forceinline__ void accumulate(float (&acc)[NC], const float* lds, const KArgs& a, const int32_t* __restrict__ whole,
                                            const float* __restrict__ frac, const float* __restrict__ taps, size_t row_base, int m0,
                                            int mc, int lane, const RowHead head = RowHead())
@@ -177,7 +178,9 @@ __device__ __forceinline__ void accumulate(float (&acc)[NC], const float* lds, c
                     const float s0 = r[c * kWave];
                     const float s1 = r[c * kWave + 1];
                     float v = __fmaf_rn(h, s1 - s0, s0);      // gcc contracts s0 + h*(s1-s0) into one fma
-                    if (c * kWave <= p) v = (lane + c * kWave > p) ? v : 0.0f;   // i >= 0 only (wave-uniform guard)
+                    if constexpr (!HIST) {
+                        if (c * kWave <= p) v = (lane + c * kWave > p) ? v : 0.0f;   // i >= 0 only (wave-uniform guard)
+                    }
                     acc[c] += v;
                 }
             };
@@ -481,6 +484,166 @@ __global__ void __launch_bounds__(1024) das_miso_kernel(BF_TABLE_PARAMS, const f
     for (int c = 0; c < NC; ++c) {
         float v = acc[c];
         if (gain != 0.0f) v = (v / fn) * gain;   // true division: a reciprocal multiply differs unless n is a power of two
+        if (lane + c * kWave < a.n_samples) out[lane + c * kWave] = run ? v : nan;
+    }
+}
+
+// ---- continuous-stream mode (bf_das_stream_device / bf_miso_stream_device) ----------------------------------------------
+// das_mimo_kernel / das_miso_kernel with one change: the `hist` columns in front of every staged row, [lead - hist, lead), hold
+// the samples that precede the window -- row[hop - hist, hop) of the previous frame (frame f - 1 of the launch; `prev0` for
+// frame 0, zeros when that is null) -- instead of zeros, and accumulate<.., HIST = true> drops lerp's i >= 0 guard.  A delayed
+// read lead - p (- 1) + k then finds x(k - p) for every k in [0, N): the first p outputs of a window are no longer sums over a
+// growing subset of the microphones.  hist = max_whole (pad) or max_whole + 1 (lerp); the host checks hist <= hop <= N and
+// hist <= lead, so the slice lies inside the previous frame's row and inside the row's lead.  The slice starts at an arbitrary
+// sample (hop - hist), so it is copied with plain dword loads; it is hist / N of the row's bytes.
+__device__ __forceinline__ void stage_chunk_stream(float* lds, const KArgs& a, const int32_t* __restrict__ mics, const float* __restrict__ frame,
+                                                   const float* __restrict__ prev, int hop, int hist, int m0, int mc, int wave, int nwaves, int lane)
+{
+    stage_chunk(lds, a, mics, frame, m0, mc, wave, nwaves, lane);
+    for (int r = wave; r < mc; r += nwaves) {
+        float* dst = lds + r * a.row_stride + (a.lead - hist);
+        if (prev != nullptr) {   // (workgroup-uniform)
+            const float* src = prev + (size_t)mics[m0 + r] * a.n_samples + (hop - hist);
+            for (int i = lane; i < hist; i += kWave) dst[i] = src[i];
+        } else {
+            for (int i = lane; i < hist; i += kWave) dst[i] = 0.0f;
+        }
+    }
+}
+
+template <int ALGO, int NC, int DPW>
+__global__ void __launch_bounds__(1024) stream_map_kernel(BF_TABLE_PARAMS, KArgs a, const float* __restrict__ prev0, int hop, int hist)
+{
+    static_assert(ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = (int)(blockDim.x >> 6);
+    const int tile = (int)(blockIdx.x % (unsigned)a.n_tiles);
+    const int frame = (int)(blockIdx.x / (unsigned)a.n_tiles);
+    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
+    if (tile_begin >= a.dir_end) return;
+    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
+
+    // zero the whole LDS image once: the columns in front of the history and behind the samples stay zero
+    {
+        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
+        float4* z = reinterpret_cast<float4*>(lds);
+        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+
+    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
+    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
+    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
+    float* __restrict__ img = images + (size_t)frame * a.image_stride;
+    const int group = nwaves * DPW;
+    float* scratch = lds + a.scratch_off + wave * (a.pbw * a.srow);
+    int filled = 0;   // wave-uniform
+
+    // work items and the table-row head requested one item ahead: as das_mimo_kernel
+    auto item_dir = [&](int g0_, int j_) { return g0_ + j_ * nwaves + wave; };
+    RowHead head;
+    if (item_dir(tile_begin, 0) < tile_end)
+        head = request_row_head<ALGO>(whole, frac, (size_t)item_dir(tile_begin, 0) * a.n_mics, min(a.mic_chunk, a.n_mics), lane);
+
+    for (int g0 = tile_begin; g0 < tile_end; g0 += group) {
+        float acc[DPW][NC];
+#pragma unroll
+        for (int j = 0; j < DPW; ++j)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) acc[j][c] = 0.0f;
+
+        for (int ch = 0; ch < a.n_chunks; ++ch) {
+            const int m0 = ch * a.mic_chunk;
+            const int mc = min(a.mic_chunk, a.n_mics - m0);
+            if (a.n_chunks > 1 || g0 == tile_begin) {
+                if (a.n_chunks > 1 && (ch > 0 || g0 != tile_begin)) __syncthreads();  // previous readers done
+                stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);   // the history is refilled with every chunk
+                __syncthreads();
+            }
+#pragma unroll
+            for (int j = 0; j < DPW; ++j) {
+                const int d = g0 + j * nwaves + wave;  // wave-uniform
+                int ng0 = g0, nch = ch, nj = j + 1;
+                if (nj == DPW) { nj = 0; nch = ch + 1; if (nch == a.n_chunks) { nch = 0; ng0 = g0 + group; } }
+                const int nd = item_dir(ng0, nj);
+                const RowHead cur = head;
+                head = RowHead();
+                if (nd < tile_end) {
+                    const int nm0 = nch * a.mic_chunk;
+                    head = request_row_head<ALGO>(whole, frac, (size_t)nd * a.n_mics + nm0, min(a.mic_chunk, a.n_mics - nm0), lane);
+                }
+                if (d < tile_end) accumulate<ALGO, NC, true>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DPW; ++j) {
+            const int d = g0 + j * nwaves + wave;
+            if (d < tile_end) {
+                park_squares<NC>(acc[j], scratch + filled * a.srow, a, d, lane);
+                if (++filled == a.pbw) { flush_powers(scratch, filled, img, a, lane); filled = 0; }
+            }
+        }
+    }
+    if (filled > 0) flush_powers(scratch, filled, img, a, lane);
+}
+
+// Workgroup id = frame * groups + group, one wave per beam, offsets / status / gain / NaN beams as das_miso_kernel's device path.
+template <int ALGO, int NC>
+__global__ void __launch_bounds__(1024) stream_beam_kernel(BF_TABLE_PARAMS, float* __restrict__ beam_out, KArgs a, const int32_t* __restrict__ offsets,
+                                                           int beams, int* __restrict__ status, long long entries, float gain, int out_stride,
+                                                           const float* __restrict__ prev0, int hop, int hist)
+{
+    static_assert(ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = (int)(blockDim.x >> 6);
+    const int groups = (beams + nwaves - 1) / nwaves;
+    const int frame = (int)(blockIdx.x / (unsigned)groups);
+    const int beam = (int)(blockIdx.x % (unsigned)groups) * nwaves + wave;   // wave-uniform
+    const bool live = beam < beams;                                           // the last group may be partial
+    const size_t slot = (size_t)frame * beams + beam;
+
+    long long row = 0;
+    int verdict = 0;
+    if (live) {
+        const long long off = __builtin_amdgcn_readfirstlane(offsets[slot]);
+        if (off < 0 || off + (long long)a.n_mics > entries) verdict = 1;
+        row = off;
+    }
+    const bool run = live && verdict == 0;
+
+    {
+        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
+        float4* z = reinterpret_cast<float4*>(lds);
+        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
+    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
+    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
+    float acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.0f;
+    for (int ch = 0; ch < a.n_chunks; ++ch) {
+        const int m0 = ch * a.mic_chunk;
+        const int mc = min(a.mic_chunk, a.n_mics - m0);
+        if (ch > 0) __syncthreads();
+        stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);
+        __syncthreads();
+        if (run) accumulate<ALGO, NC, true>(acc, lds, a, whole, frac, taps, (size_t)row, m0, mc, lane);
+    }
+    if (!live) return;
+    if (status != nullptr && lane == 0) status[slot] = verdict;
+    float* __restrict__ out = beam_out + slot * (size_t)out_stride;
+    const float nan = __int_as_float(0x7fc00000);
+    const float fn = (float)a.n_mics;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        float v = acc[c];
+        if (gain != 0.0f) v = (v / fn) * gain;   // as das_miso_kernel: true division, two roundings
         if (lane + c * kWave < a.n_samples) out[lane + c * kWave] = run ? v : nan;
     }
 }
@@ -3323,6 +3486,118 @@ hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int3
     B.offsets = d_offsets; B.frames = L.frames; B.beams = beams; B.waves = std::min(beams, kMisoWaves);
     B.status = d_status; B.entries = entries; B.gain = gain; B.out_stride = out_stride;
     return launch_miso_any(L, plan, 0, nullptr, d_out, B, stream);
+}
+
+// ---- continuous-stream mode: planning and launches ------------------------------------------------------------------------
+
+int stream_history(int algo, int max_whole)
+{
+    return algo == ALGO_PAD ? max_whole : algo == ALGO_LERP ? max_whole + 1 : -1;
+}
+
+// Maps in stream mode always take the strided layout (lane l owns samples l, l + 64, ..), whatever N: the sizing is plan_das's
+// for that layout -- one 16-wave workgroup with the whole LDS, mic rows (or a chunk of them) beside the per-wave power scratch.
+int plan_stream_maps(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
+{
+    auto fail = [&](const char* msg) { if (why) *why = msg; return -1; };
+    if (L.algo != ALGO_PAD && L.algo != ALGO_LERP) return fail("continuous mode exists for pad and lerp only");
+    if (L.n_samples < 1 || L.n_samples > 1024) return fail("N_SAMPLES must be in [1, 1024]");
+    if (L.n_mics < 1 || L.frames < 1 || L.dir_end <= L.dir_begin) return fail("empty launch");
+    DasPlan p{};
+    p.nf = 1;
+    const int nc = (L.n_samples + kWave - 1) / kWave;
+    p.nc = nc <= 1 ? 1 : nc <= 2 ? 2 : nc <= 4 ? 4 : nc <= 8 ? 8 : 16;
+    p.lead = round_up(L.tab.max_whole + 1, 4);      // >= the history of either flavour
+    p.row_stride = p.lead + p.nc * kWave;
+    const size_t row_bytes = (size_t)p.row_stride * sizeof(float);
+    p.waves = 16;
+    p.srow = p.nc * kWave + 4;
+    p.pbw = p.nc <= 4 ? 4 : p.nc <= 8 ? 2 : 1;
+    const size_t scratch_bytes = (size_t)p.waves * p.pbw * p.srow * sizeof(float);
+    const size_t sig_budget = (size_t)160 * 1024 - scratch_bytes - 16;
+    if (row_bytes * (size_t)L.n_mics <= sig_budget) {
+        p.mic_chunk = L.n_mics; p.n_chunks = 1; p.dpw = 1;
+    } else {
+        int mc = (int)(sig_budget / row_bytes);
+        if (mc < 1) return fail("one microphone row does not fit in LDS");
+        if (mc >= 4) mc &= ~3;
+        p.mic_chunk = mc; p.n_chunks = (L.n_mics + mc - 1) / mc;
+        p.dpw = 4;
+    }
+    p.scratch_off = round_up(p.mic_chunk * p.row_stride, 4);
+    p.lds_bytes = (size_t)p.scratch_off * sizeof(float) + scratch_bytes;
+    // Tiles: whole wave groups, about four workgroups per CU; a launch too small for that gives every CU a tile.  With one chunk a
+    // tile stages its frame once, so more groups per tile save staging; with several chunks every group restages anyway.
+    const int group = p.waves * p.dpw;
+    const long long dirs = (long long)(L.dir_end - L.dir_begin), work = dirs * L.frames;
+    long long td;
+    if (work < (long long)n_cus * group) {
+        td = round_up((int)std::max<long long>(1, (work + n_cus - 1) / n_cus), p.dpw);
+    } else {
+        long long k = p.n_chunks > 1 ? 1 : work / ((long long)n_cus * 4 * group);
+        k = std::min<long long>(std::max<long long>(k, 1), 8);
+        td = k * group;
+    }
+    p.tile_dirs = (int)td;
+    p.n_tiles = (int)((dirs + td - 1) / td);
+    *plan = p;
+    if (why) *why = "";
+    return 0;
+}
+
+hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, hipStream_t stream)
+{
+    const int hist = stream_history(L.algo, L.tab.max_whole);
+    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist || plan.layout != 0) return hipErrorInvalidValue;
+    const KArgs a = make_args(L, plan);
+    auto go = [&](auto kernel) -> hipError_t {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)plan.n_tiles * (unsigned)L.frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream,
+                           L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a, d_prev, hop, hist);
+        return hipGetLastError();
+    };
+    auto by_dpw = [&](auto nc) -> hipError_t {
+        constexpr int NC = decltype(nc)::value;
+        if (plan.dpw == 1) return L.algo == ALGO_PAD ? go(stream_map_kernel<ALGO_PAD, NC, 1>) : go(stream_map_kernel<ALGO_LERP, NC, 1>);
+        if (plan.dpw == 4) return L.algo == ALGO_PAD ? go(stream_map_kernel<ALGO_PAD, NC, 4>) : go(stream_map_kernel<ALGO_LERP, NC, 4>);
+        return hipErrorInvalidValue;
+    };
+    switch (plan.nc) {
+        case 1: return by_dpw(std::integral_constant<int, 1>());
+        case 2: return by_dpw(std::integral_constant<int, 2>());
+        case 4: return by_dpw(std::integral_constant<int, 4>());
+        case 8: return by_dpw(std::integral_constant<int, 8>());
+        case 16: return by_dpw(std::integral_constant<int, 16>());
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
+                               long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream)
+{
+    const int hist = stream_history(L.algo, L.tab.max_whole);
+    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist) return hipErrorInvalidValue;
+    if (L.frames < 1 || beams < 1 || out_stride < L.n_samples || d_offsets == nullptr) return hipErrorInvalidValue;
+    const KArgs a = make_args(L, plan);
+    const int waves = std::min(beams, kMisoWaves);
+    const unsigned groups = (unsigned)((beams + waves - 1) / waves);
+    auto go = [&](auto kernel) -> hipError_t {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)L.frames * groups), dim3((unsigned)waves * kWave), plan.lds_bytes, stream, L.signals, L.images, L.mics,
+                           L.tab.whole, L.tab.frac, L.tab.taps, d_out, a, d_offsets, beams, d_status, entries, gain, out_stride, d_prev, hop, hist);
+        return hipGetLastError();
+    };
+    const bool pad = L.algo == ALGO_PAD;
+    switch (plan.nc) {
+        case 1: return pad ? go(stream_beam_kernel<ALGO_PAD, 1>) : go(stream_beam_kernel<ALGO_LERP, 1>);
+        case 2: return pad ? go(stream_beam_kernel<ALGO_PAD, 2>) : go(stream_beam_kernel<ALGO_LERP, 2>);
+        case 4: return pad ? go(stream_beam_kernel<ALGO_PAD, 4>) : go(stream_beam_kernel<ALGO_LERP, 4>);
+        case 8: return pad ? go(stream_beam_kernel<ALGO_PAD, 8>) : go(stream_beam_kernel<ALGO_LERP, 8>);
+        case 16: return pad ? go(stream_beam_kernel<ALGO_PAD, 16>) : go(stream_beam_kernel<ALGO_LERP, 16>);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace bf

@@ -97,6 +97,11 @@ _sig("bf_get_steer", C.c_int, IP)
 _sig("bf_das_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, IP, C.c_int, C.c_int, C.c_int, C.c_void_p)
 _sig("bf_miso_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, IP, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
      C.c_void_p)
+_sig("bf_stream_history", C.c_int, C.c_int)
+_sig("bf_miso_stream_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, IP, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_void_p)
+_sig("bf_das_stream_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, IP, C.c_int, C.c_int, C.c_int,
+     C.c_void_p)
 _sig("bf_peak_offsets_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
 _sig("bf_plan_das", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))
 _sig("bf_ingest", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, FP)
@@ -137,6 +142,7 @@ _sig("bf_topk_candidates_device", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C
 _sig("bf_nms_device", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("bf_jet_lut", None, C.POINTER(C.c_ubyte))
 _sig("bf_get_lerp_tables", C.c_int, IP, FP, C.c_int)
+_sig("bf_get_pad_table", C.c_int, IP, C.c_int)
 _sig("bf_get_hybrid_tables", C.c_int, IP, FP, C.c_int)
 _sig("bf_default_geometry", None, C.POINTER(Geometry))
 _sig("bf_active_microphones", C.c_int, C.POINTER(Geometry), IP, C.c_int, IP)
