@@ -197,6 +197,44 @@ int bf_miso_device(int algo, const float *d_signals, int m_total, int frames, co
 int bf_peak_offsets_device(const float *d_power, int frames, int image_stride, int n_dirs, int offset_per_dir,
                            int *d_offsets, void *stream);
 
+/* ---- the K loudest separated sources of every map: maps -> [frames][k] offsets for bf_miso_device, one enqueue ----
+ * bf_peak_offsets_device is a plain argmax: one source per frame.  The reference authors list the general case as open
+ * (PC/TODO.md, "Peak detection"): their 2D convolution for local maxima "failed when the resolution went up", because neighbouring
+ * pixels of one lobe each looked like a peak.  Here the neighbourhood scales with the grid: a direction is a source only if it is
+ * the maximum of its whole (2*radius+1) x (2*radius+1) window.  The reference has nothing to compare with; the definition below
+ * consists of comparisons and one float32 multiplication, so results are exact.
+ *
+ * d_power   : HIP device pointer, float32 [frames][image_stride]; the first rows*cols entries of a frame are the map in the library's
+ *             own order d = x*cols + y (rows = MAX_RES_X, cols = MAX_RES_Y, as mimo_* write image[d]); the rest is never read.
+ * Non-finite entries (NaN, +inf, -inf) are never sources and never suppress a neighbour: they compare as below everything.  They
+ *             are counted in d_counts[f][2].
+ * Order     : finite entries are totally ordered by (value descending, flat index d ascending); -0.0f equals 0.0f.  This is the tie
+ *             rule of bf_peak_offsets_device.
+ * Candidates: a finite entry (x, y) is a candidate iff no OTHER finite entry (x', y') of the grid with |x'-x| <= radius and
+ *             |y'-y| <= radius comes before it in that order.  So any two candidates are more than `radius` apart in Chebyshev
+ *             distance; a constant map has exactly one candidate, index 0; radius 0 makes every finite entry a candidate (a plain
+ *             top-k); radius >= max(rows, cols) - 1 leaves at most one.
+ * Threshold : top = the first entry of the order = the largest finite value of the frame (always a candidate);
+ *             thr = fmaxf(floor_abs, floor_rel * top), the product one float32 multiplication.  Candidates with value >= thr are kept.
+ * d_offsets : HIP device pointer, int32 [frames][k]: d * offset_per_dir of the kept candidates, in order; unfilled slots hold -1,
+ *             which bf_miso_device rejects with status 1 and a NaN beam.
+ * d_values  : HIP device pointer, float32 [frames][k], or NULL: the powers image[d] of those candidates; unfilled slots hold 0.0f.
+ * d_counts  : HIP device pointer, int32 [frames][3], or NULL: [0] slots filled = min(k, [1]); [1] kept candidates in total (shows when
+ *             k truncated the list); [2] non-finite entries of the frame.
+ * Every entry of every output is written by every call.  A frame with no finite entry, or with floor_abs above its top, has no source.
+ * The result does not depend on which of the two internal forms runs (one workgroup per frame where the map fits LDS -- up to 13632
+ * directions --, three launches over tiles and a library-owned buffer above that) nor on the order workgroups run in.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only; the buffer of the tiled form grows on the first call of a larger shape
+ *             and nothing is allocated after that: graph-capturable after one warm-up call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_power or d_offsets null; frames, rows, cols or
+ * offset_per_dir < 1; k < 1 or k > BF_PEAKS_MAX_K; radius < 0; rows*cols not fitting an int or exceeding image_stride;
+ * (rows*cols - 1) * offset_per_dir > INT_MAX; floor_rel not finite or outside [0, 1]; floor_abs not finite; no GPU.  All arguments are
+ * checked before device bring-up. */
+#define BF_PEAKS_MAX_K 64
+int bf_peaks_device(const float *d_power, int frames, int image_stride, int rows, int cols, int radius, int k,
+                    float floor_rel, float floor_abs, int offset_per_dir,
+                    int *d_offsets, float *d_values, int *d_counts, void *stream);
+
 /* ---- continuous-stream mode of the device path (BF_PAD, BF_LERP): delays read the previous window ----
  * Every other entry point treats a window as if the world began at its first sample: a microphone delayed by p samples gives
  * nothing to the first p outputs (out[p + i] += s[i], zero prefix), as the reference does.  That is the first item of the reference

@@ -126,6 +126,7 @@ struct State {
     DevBuf<float> fd_work;               // partial planes of the bin-reducing GEMMs (bf::fd_workspace_floats)
     DevBuf<float> fd_chol_work;          // blocks of the 129..256-mic Cholesky / inverse (bf::fd_cholesky_workspace_floats)
     DevBuf<float> fd_tw;                 // twiddles of the MFMA DFT for (N, bin_lo, n_bins) = fd_tw_key
+    DevBuf<unsigned long long> peaks_work;  // row-pass results and per-tile lists of bf_peaks_device's tiled form (bf::peaks_workspace_words)
     long long fd_tw_key = -1;
     std::vector<int> mics_host;          // what d_mics currently holds
     std::vector<float> published;        // bf_publish_frame / get_data
@@ -1175,6 +1176,38 @@ int bf_peak_offsets_device(const float* d_power, int frames, int image_stride, i
     }
     if (!ensure_device()) return -1;
     return HIP_OK(bf::launch_peak_offsets(d_power, frames, image_stride, n_dirs, offset_per_dir, d_offsets, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
+int bf_peaks_device(const float* d_power, int frames, int image_stride, int rows, int cols, int radius, int k, float floor_rel, float floor_abs,
+                    int offset_per_dir, int* d_offsets, float* d_values, int* d_counts, void* stream)
+{
+    static const char* who = "bf_peaks_device";
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    sizes_from_env_once();
+    if (!d_power) { set_error("%s: d_power is null", who); return -1; }
+    if (!d_offsets) { set_error("%s: d_offsets is null", who); return -1; }
+    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
+    if (rows < 1) { set_error("%s: rows = %d < 1", who, rows); return -1; }
+    if (cols < 1) { set_error("%s: cols = %d < 1", who, cols); return -1; }
+    if (offset_per_dir < 1) { set_error("%s: offset_per_dir = %d < 1", who, offset_per_dir); return -1; }
+    if (k < 1) { set_error("%s: k = %d < 1", who, k); return -1; }
+    if (k > BF_PEAKS_MAX_K) { set_error("%s: k = %d > %d", who, k, BF_PEAKS_MAX_K); return -1; }
+    if (radius < 0) { set_error("%s: radius = %d < 0", who, radius); return -1; }
+    const long long D = (long long)rows * cols;
+    if (D > (long long)std::numeric_limits<int>::max()) { set_error("%s: rows * cols = %lld does not fit an int", who, D); return -1; }
+    if (D > image_stride) { set_error("%s: image_stride = %d < rows * cols = %lld", who, image_stride, D); return -1; }
+    if ((D - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
+        set_error("%s: (rows * cols - 1) * offset_per_dir = %lld does not fit an int offset", who, (D - 1) * offset_per_dir);
+        return -1;
+    }
+    if (!std::isfinite(floor_rel) || floor_rel < 0.0f || floor_rel > 1.0f) { set_error("%s: floor_rel = %g is not in [0, 1]", who, (double)floor_rel); return -1; }
+    if (!std::isfinite(floor_abs)) { set_error("%s: floor_abs = %g is not finite", who, (double)floor_abs); return -1; }
+    if (!ensure_device()) return -1;
+    const size_t work = bf::peaks_workspace_words(frames, rows, cols, k);
+    if (work && !HIP_OK(s.peaks_work.reserve(work))) return -1;
+    return HIP_OK(bf::launch_peaks(d_power, frames, image_stride, rows, cols, radius, k, floor_rel, floor_abs, offset_per_dir, d_offsets, d_values, d_counts,
+                                   s.peaks_work.p, s.peaks_work.cap, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
 }
 
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)

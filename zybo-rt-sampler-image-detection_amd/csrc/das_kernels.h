@@ -127,6 +127,12 @@ hipError_t launch_letterbox(const unsigned char* d_src, int sh, int sw, unsigned
 hipError_t launch_power_center(const float* d_power, int frames, int rows, int cols, float* d_centers, float* d_workspace, hipStream_t stream);
 // d_offsets[f] = argmax_{j < n_dirs} d_power[f * image_stride + j] * offset_per_dir, np.argmax's rules (first maximum, first NaN)
 hipError_t launch_peak_offsets(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, hipStream_t stream);
+// bf_peaks_device: the k loudest sources of every map that are the maximum of their (2 radius + 1)^2 window.  Maps that fit LDS take one
+// workgroup per frame and no workspace; larger ones three launches over peaks_workspace_words(...) 8-byte words (0: none needed).
+size_t peaks_workspace_words(int frames, int rows, int cols, int k);
+hipError_t launch_peaks(const float* d_power, int frames, int image_stride, int rows, int cols, int radius, int k, float floor_rel, float floor_abs,
+                        int offset_per_dir, int* d_offsets, float* d_values, int* d_counts, unsigned long long* d_workspace, size_t workspace_words,
+                        hipStream_t stream);
 
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.

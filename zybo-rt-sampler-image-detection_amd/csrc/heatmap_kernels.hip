@@ -418,4 +418,313 @@ hipError_t launch_peak_offsets(const float* d_power, int frames, int image_strid
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- bf_peaks_device: the K loudest separated sources of every map
+//
+// The order of include/beamformer_hip.h -- value descending, flat index ascending, non-finite entries below everything -- as ONE
+// unsigned 64-bit key, so that "comes before" is `>` and the best of a window is an integer maximum (argmax_merge's ordering with the
+// NaN rule turned round: here a NaN never wins).  High word: the float's bits mapped monotonically to unsigned (both zeros share a
+// code; the smallest finite value maps to 0x00800000, so 0 is free for "non-finite"); low word: ~index.  Keys of different entries
+// differ, key 0 is "nothing".  The maximum of a total order over a square window is the maximum over the rows of the per-row maxima:
+// a row pass leaves each entry's best key over its horizontal window, a column pass over those gives the best over the square, and an
+// entry is a candidate iff that is its own key -- 2 (2r + 1) reads per entry instead of (2r + 1)^2.
+namespace {
+
+typedef unsigned long long PeakKey;
+
+__device__ __forceinline__ unsigned peak_code(float v)
+{
+    unsigned b = __float_as_uint(v);
+    if ((b & 0x7f800000u) == 0x7f800000u) return 0u;        // NaN, +inf, -inf
+    if (b == 0x80000000u) b = 0u;                           // -0.0f == 0.0f
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// the value of a non-zero code (a -0.0f comes back as 0.0f, which compares the same)
+__device__ __forceinline__ float peak_value(unsigned code) { return __uint_as_float((code & 0x80000000u) ? (code ^ 0x80000000u) : ~code); }
+__device__ __forceinline__ PeakKey peak_key(unsigned code, int index) { return code ? ((PeakKey)code << 32) | (PeakKey)(0xffffffffu - (unsigned)index) : 0ull; }
+__device__ __forceinline__ int peak_index(PeakKey key) { return (int)(0xffffffffu - (unsigned)key); }
+
+// thr = fmaxf(floor_abs, floor_rel * top): one float32 multiplication (the build has -ffp-contract=off; there is nothing to fuse with anyway)
+__device__ __forceinline__ float peak_threshold(PeakKey top, float floor_rel, float floor_abs)
+{
+    return top ? fmaxf(floor_abs, floor_rel * peak_value((unsigned)(top >> 32))) : floor_abs;
+}
+
+// Block-wide maximum / sum, the same value in every thread.  red: one slot per wave; safe to call back to back.
+__device__ __forceinline__ PeakKey block_max_key(PeakKey v, PeakKey* red)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const PeakKey o = __shfl_xor(v, off, 64);
+        v = o > v ? o : v;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    PeakKey r = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = red[w] > r ? red[w] : r;
+    return r;
+}
+
+__device__ __forceinline__ int block_sum_int(int v, int* red)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int r = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += red[w];
+    return r;
+}
+
+__device__ __forceinline__ void peak_write(PeakKey key, size_t slot, const float* __restrict__ img, int offset_per_dir, int* __restrict__ offsets,
+                                           float* __restrict__ values)
+{
+    const int d = peak_index(key);
+    offsets[slot] = key ? d * offset_per_dir : -1;
+    if (values) values[slot] = key ? img[d] : 0.0f;
+}
+
+// Maps that fit LDS: one workgroup per frame, the map is read from HBM once.  LDS: best[D] keys (row-pass results), code[D] (the
+// entries' codes; after the column pass: the kept candidates' codes, 0 everywhere else).  The ordered top k is then k rounds of
+// "largest key below the previous one" over code[] -- exact for any number of candidates (radius 0: every finite entry), no list,
+// no atomics.  radius has been clamped to max(rows, cols) by the launcher.
+__global__ void __launch_bounds__(1024) peaks_frame_kernel(const float* __restrict__ power, int image_stride, int rows, int cols, int radius, int k,
+                                                          float floor_rel, float floor_abs, int offset_per_dir, int* __restrict__ offsets,
+                                                          float* __restrict__ values, int* __restrict__ counts)
+{
+    extern __shared__ PeakKey pk_lds[];
+    __shared__ PeakKey red[16];
+    __shared__ int redi[16];
+    const int D = rows * cols, tid = threadIdx.x, nt = blockDim.x;
+    PeakKey* best = pk_lds;
+    unsigned* code = reinterpret_cast<unsigned*>(pk_lds + D);
+    const float* img = power + (size_t)blockIdx.x * image_stride;
+    PeakKey top = 0;
+    int bad = 0;
+    for (int i = tid; i < D; i += nt) {
+        const unsigned c = peak_code(img[i]);
+        code[i] = c;
+        bad += c == 0u;
+        const PeakKey key = peak_key(c, i);
+        top = key > top ? key : top;
+    }
+    top = block_max_key(top, red);          // (its barriers also publish code[])
+    bad = block_sum_int(bad, redi);
+    for (int i = tid; i < D; i += nt) {
+        const int x = i / cols, y = i - x * cols;
+        const int lo = y - min(radius, y), hi = y + min(radius, cols - 1 - y);
+        const unsigned* row = code + x * cols;
+        unsigned bc = 0u;
+        int by = 0;
+        for (int j = lo; j <= hi; ++j) {     // ascending index: only a larger code replaces the best so far
+            const unsigned c = row[j];
+            if (c > bc) { bc = c; by = j; }
+        }
+        best[i] = peak_key(bc, x * cols + by);
+    }
+    __syncthreads();
+    const float thr = peak_threshold(top, floor_rel, floor_abs);
+    int kept = 0;
+    for (int i = tid; i < D; i += nt) {
+        const unsigned c = code[i];
+        if (c == 0u) continue;
+        const int x = i / cols, y = i - x * cols;
+        const int lo = x - min(radius, x), hi = x + min(radius, rows - 1 - x);
+        PeakKey m = 0;
+        for (int j = lo; j <= hi; ++j) {
+            const PeakKey b = best[j * cols + y];
+            m = b > m ? b : m;
+        }
+        const bool keep = m == peak_key(c, i) && peak_value(c) >= thr;
+        if (!keep) code[i] = 0u;             // (only this thread reads code[i] in this pass)
+        kept += keep;
+    }
+    kept = block_sum_int(kept, redi);       // (publishes the edited code[])
+    PeakKey last = ~0ull;
+    for (int s = 0; s < k; ++s) {
+        PeakKey m = 0;
+        if (s < kept) {                      // uniform
+            for (int i = tid; i < D; i += nt) {
+                const PeakKey key = peak_key(code[i], i);
+                if (key < last && key > m) m = key;
+            }
+            m = block_max_key(m, red);
+        }
+        if (tid == 0) peak_write(m, (size_t)blockIdx.x * k + s, img, offset_per_dir, offsets, values);
+        last = m;
+    }
+    if (tid == 0 && counts) {
+        counts[(size_t)blockIdx.x * 3 + 0] = min(k, kept);
+        counts[(size_t)blockIdx.x * 3 + 1] = kept;
+        counts[(size_t)blockIdx.x * 3 + 2] = bad;
+    }
+}
+
+// Larger maps, any radius: the same three steps as three launches over tiles of kPeakTile consecutive entries, the row-pass results
+// in a library-owned buffer.  A tile's window reaches into its neighbours through that buffer (and through the map itself in the row
+// pass), so no halo is staged and a radius as large as the grid needs nothing special.
+//   1. peaks_row_kernel   : best[f][i] = best key of entry i's horizontal window; per tile: the best own key and the non-finite count
+//   2. peaks_col_kernel   : frame top (from the tiles' partials) -> threshold; candidates by the column pass; per tile: the number of
+//                           kept candidates and their ordered top k
+//   3. peaks_merge_kernel : per frame: counts summed, the ordered top k of the tiles' lists
+// Every partial is written by one workgroup and read by later launches: nothing depends on the order workgroups run in.
+constexpr int kPeakTile = 1024;
+
+__global__ void __launch_bounds__(kPeakTile) peaks_row_kernel(const float* __restrict__ power, int image_stride, int D, int cols, int radius, int tiles,
+                                                             PeakKey* __restrict__ best, PeakKey* __restrict__ tile_top, int* __restrict__ tile_bad)
+{
+    __shared__ PeakKey red[16];
+    __shared__ int redi[16];
+    const int f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
+    const int i = tile * kPeakTile + threadIdx.x;
+    const float* img = power + (size_t)f * image_stride;
+    PeakKey own = 0;
+    int bad = 0;
+    if (i < D) {
+        const int x = i / cols, y = i - x * cols;
+        const int lo = y - min(radius, y), hi = y + min(radius, cols - 1 - y);
+        const float* row = img + (size_t)x * cols;
+        unsigned bc = 0u;
+        int by = 0;
+        for (int j = lo; j <= hi; ++j) {
+            const unsigned c = peak_code(row[j]);
+            if (c > bc) { bc = c; by = j; }
+        }
+        best[(size_t)f * D + i] = peak_key(bc, x * cols + by);
+        own = peak_key(peak_code(img[i]), i);
+        bad = own == 0ull;
+    }
+    own = block_max_key(own, red);
+    bad = block_sum_int(bad, redi);
+    if (threadIdx.x == 0) { tile_top[blockIdx.x] = own; tile_bad[blockIdx.x] = bad; }
+}
+
+__global__ void __launch_bounds__(kPeakTile) peaks_col_kernel(const float* __restrict__ power, int image_stride, int D, int rows, int cols, int radius, int k,
+                                                             float floor_rel, float floor_abs, int tiles, const PeakKey* __restrict__ best,
+                                                             const PeakKey* __restrict__ tile_top, PeakKey* __restrict__ tile_keys,
+                                                             int* __restrict__ tile_kept)
+{
+    __shared__ PeakKey red[16];
+    __shared__ int redi[16];
+    const int f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
+    const int i = tile * kPeakTile + threadIdx.x;
+    const float* img = power + (size_t)f * image_stride;
+    PeakKey top = 0;
+    for (int t = threadIdx.x; t < tiles; t += kPeakTile) {
+        const PeakKey o = tile_top[(size_t)f * tiles + t];
+        top = o > top ? o : top;
+    }
+    top = block_max_key(top, red);
+    const float thr = peak_threshold(top, floor_rel, floor_abs);
+    PeakKey own = 0;
+    if (i < D) {
+        const unsigned c = peak_code(img[i]);
+        if (c) {
+            const int x = i / cols, y = i - x * cols;
+            const int lo = x - min(radius, x), hi = x + min(radius, rows - 1 - x);
+            const PeakKey* col = best + (size_t)f * D + y;
+            PeakKey m = 0;
+            for (int j = lo; j <= hi; ++j) {
+                const PeakKey b = col[(size_t)j * cols];
+                m = b > m ? b : m;
+            }
+            if (m == peak_key(c, i) && peak_value(c) >= thr) own = m;
+        }
+    }
+    const int kept = block_sum_int(own != 0ull, redi);
+    PeakKey last = ~0ull;
+    for (int s = 0; s < k; ++s) {
+        PeakKey m = 0;
+        if (s < kept) m = block_max_key(own < last ? own : 0ull, red);
+        if (threadIdx.x == 0) tile_keys[(size_t)blockIdx.x * k + s] = m;
+        last = m;
+    }
+    if (threadIdx.x == 0) tile_kept[blockIdx.x] = kept;
+}
+
+__global__ void __launch_bounds__(256) peaks_merge_kernel(const float* __restrict__ power, int image_stride, int k, int offset_per_dir, int tiles,
+                                                         const PeakKey* __restrict__ tile_keys, const int* __restrict__ tile_kept,
+                                                         const int* __restrict__ tile_bad, int* __restrict__ offsets, float* __restrict__ values,
+                                                         int* __restrict__ counts)
+{
+    __shared__ PeakKey red[4];
+    __shared__ int redi[4];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const float* img = power + (size_t)f * image_stride;
+    int kept = 0, bad = 0;
+    for (int t = tid; t < tiles; t += 256) { kept += tile_kept[(size_t)f * tiles + t]; bad += tile_bad[(size_t)f * tiles + t]; }
+    kept = block_sum_int(kept, redi);
+    bad = block_sum_int(bad, redi);
+    const PeakKey* keys = tile_keys + (size_t)f * tiles * k;
+    const long long n = (long long)tiles * k;
+    PeakKey last = ~0ull;
+    for (int s = 0; s < k; ++s) {
+        PeakKey m = 0;
+        if (s < kept) {
+            for (long long j = tid; j < n; j += 256) {
+                const PeakKey key = keys[j];
+                if (key < last && key > m) m = key;
+            }
+            m = block_max_key(m, red);
+        }
+        if (tid == 0) peak_write(m, (size_t)f * k + s, img, offset_per_dir, offsets, values);
+        last = m;
+    }
+    if (tid == 0 && counts) {
+        counts[(size_t)f * 3 + 0] = min(k, kept);
+        counts[(size_t)f * 3 + 1] = kept;
+        counts[(size_t)f * 3 + 2] = bad;
+    }
+}
+
+// LDS of the one-workgroup form: 12 bytes per entry, beside the 192 bytes of the reduction slots, within the CU's 160 KiB
+constexpr long long kPeakLdsBudget = 160 * 1024 - 256;
+
+inline bool peaks_fit_lds(long long D) { return D * 12 <= kPeakLdsBudget; }
+inline long long peaks_tiles(long long D) { return (D + kPeakTile - 1) / kPeakTile; }
+
+}  // namespace
+
+// Workspace of the tiled form in 8-byte words (0: the map fits LDS, no workspace): best[frames][D], tile_top[frames][tiles],
+// tile_keys[frames][tiles][k], then tile_kept and tile_bad as int [frames][tiles] each.
+size_t peaks_workspace_words(int frames, int rows, int cols, int k)
+{
+    const long long D = (long long)rows * cols;
+    if (peaks_fit_lds(D)) return 0;
+    const long long tiles = peaks_tiles(D);
+    return (size_t)frames * (size_t)(D + tiles + tiles * k + tiles);
+}
+
+hipError_t launch_peaks(const float* d_power, int frames, int image_stride, int rows, int cols, int radius, int k, float floor_rel, float floor_abs,
+                        int offset_per_dir, int* d_offsets, float* d_values, int* d_counts, unsigned long long* d_workspace, size_t workspace_words,
+                        hipStream_t stream)
+{
+    const long long D = (long long)rows * cols;
+    radius = std::min(radius, std::max(rows, cols));       // a window past the grid's edge is the window to the edge; keeps y + radius an int
+    if (peaks_fit_lds(D)) {
+        const size_t lds = (size_t)D * 12;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(peaks_frame_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        // a frame's workgroup is alone on the critical path of its map: sixteen waves as soon as each has more than one entry to look at
+        const int threads = D > 1024 ? 1024 : 256;
+        hipLaunchKernelGGL(peaks_frame_kernel, dim3(frames), dim3(threads), lds, stream, d_power, image_stride, rows, cols, radius, k, floor_rel, floor_abs,
+                           offset_per_dir, d_offsets, d_values, d_counts);
+        return hipGetLastError();
+    }
+    const long long tiles = peaks_tiles(D);
+    if (!d_workspace || workspace_words < peaks_workspace_words(frames, rows, cols, k) || frames * tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    PeakKey* best = d_workspace;
+    PeakKey* tile_top = best + (size_t)frames * D;
+    PeakKey* tile_keys = tile_top + (size_t)frames * tiles;
+    int* tile_kept = reinterpret_cast<int*>(tile_keys + (size_t)frames * tiles * k);
+    int* tile_bad = tile_kept + (size_t)frames * tiles;
+    const dim3 grid((unsigned)(frames * tiles));
+    hipLaunchKernelGGL(peaks_row_kernel, grid, dim3(kPeakTile), 0, stream, d_power, image_stride, (int)D, cols, radius, (int)tiles, best, tile_top, tile_bad);
+    hipLaunchKernelGGL(peaks_col_kernel, grid, dim3(kPeakTile), 0, stream, d_power, image_stride, (int)D, rows, cols, radius, k, floor_rel, floor_abs, (int)tiles,
+                       best, tile_top, tile_keys, tile_kept);
+    hipLaunchKernelGGL(peaks_merge_kernel, dim3(frames), dim3(256), 0, stream, d_power, image_stride, k, offset_per_dir, (int)tiles, tile_keys, tile_kept, tile_bad,
+                       d_offsets, d_values, d_counts);
+    return hipGetLastError();
+}
+
 }  // namespace bf

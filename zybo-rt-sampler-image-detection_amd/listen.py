@@ -5,8 +5,8 @@ In the reference a playback child runs `miso_pad` at the steered table offset on
 detection box (`focus_beam`, sensorfusion/decider.py:70-88).  `BeamListener` is the batched, device-resident form: windows
 already in HBM (bf_ingest_device output, FusedPipeline's batch) -> the beams of every frame at any number of offsets in one
 enqueue (bf_miso_device), and `loudest` aims one beam per frame at the frame's loudest direction of a power map without a
-host round trip (bf_peak_offsets_device).  Both only enqueue on the current torch stream, so maps, peak and beams can be
-captured as one graph.  Raw beams (mic_gain 0) are bit-identical to the reference's miso_* calls."""
+host round trip (bf_peak_offsets_device); `sources` gives up to k beams per frame, one per separated source of the map
+(bf_peaks_device).  All only enqueue on the current torch stream, so maps, peaks and beams can be captured as one graph.  Raw beams (mic_gain 0) are bit-identical to the reference's miso_* calls."""
 import numpy as np
 
 from interface import config
@@ -94,3 +94,29 @@ class BeamListener:
         if rc != 0:
             _fail("bf_peak_offsets_device")
         return offs
+
+    def sources(self, d_power, k, radius, floor_rel=0.5, floor_abs=0.0, shape=None):
+        """d_power float32 cuda [F, >= rows*cols] power maps, shape = (rows, cols) of a map (default (config.MAX_RES_X, config.MAX_RES_Y))
+        -> (offsets int32 [F, k], values float32 [F, k], counts int32 [F, 3]): the k loudest directions of every map that are the
+        maximum of their (2*radius+1)^2 window and reach max(floor_abs, floor_rel * the map's maximum), loudest first, as table
+        offsets ready for listen(); empty slots hold -1 (listen: status 1, a NaN beam) and value 0.  counts: slots filled, candidates
+        kept before k cut the list, non-finite entries of the map (never sources).  bf_peaks_device in include/beamformer_hip.h."""
+        torch = _torch()
+        if d_power.dim() != 2 or d_power.dtype != torch.float32 or not d_power.is_cuda:
+            raise ValueError("d_power must be a float32 cuda tensor [F, D], got %s %s" % (d_power.dtype, tuple(d_power.shape)))
+        rows, cols = (config.MAX_RES_X, config.MAX_RES_Y) if shape is None else (int(shape[0]), int(shape[1]))
+        if d_power.shape[1] < rows * cols:
+            raise ValueError("d_power rows hold %d entries, a %d x %d map needs %d" % (d_power.shape[1], rows, cols, rows * cols))
+        power = d_power if d_power.stride(1) == 1 else d_power.contiguous()
+        F = power.shape[0]
+        k = int(k)
+        offs = torch.empty((F, max(k, 0)), dtype=torch.int32, device=self.device)
+        vals = torch.empty((F, max(k, 0)), dtype=torch.float32, device=self.device)
+        counts = torch.empty((F, 3), dtype=torch.int32, device=self.device)
+        # a row narrower than rows*cols is refused by the library (image_stride < rows * cols); a wider one is never read past the map
+        stride = power.stride(0) if F > 1 else power.shape[1]
+        rc = _entry("bf_peaks_device")(power.data_ptr(), F, stride, rows, cols, int(radius), k, float(floor_rel), float(floor_abs),
+                                       self.offset_per_dir, offs.data_ptr(), vals.data_ptr(), counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _fail("bf_peaks_device")
+        return offs, vals, counts
