@@ -235,6 +235,55 @@ int bf_peaks_device(const float *d_power, int frames, int image_stride, int rows
                     float floor_rel, float floor_abs, int offset_per_dir,
                     int *d_offsets, float *d_values, int *d_counts, void *stream);
 
+/* ---- take beams back out of the frames: the subtraction step of a time-domain CLEAN loop (BF_PAD, BF_LERP) ----
+ * Every map is a plain delay-and-sum map, so a source 10 dB below another one sits under the stronger one's main-lobe skirt and
+ * sidelobes; the reference authors list this as open (PC/TODO.md, "Improved spatial filtering": "techniques for suppressing signals
+ * from undesired directions").  Subtractive deconvolution answers it with what the library already has: take the loudest direction
+ * of the map (bf_peaks_device), form its beam (bf_miso_device), project the beam back onto the microphones and subtract it from the
+ * frames (this call), map the residual (bf_das_device), repeat.  The projection is the ADJOINT (transpose) of the delay operator,
+ * not an inverse: the steering operator has no inverse (n microphones onto one beam), and with gain / n in front the adjoint is the
+ * least-squares step for a source that dominates its beam -- for whole-sample delays it returns every microphone's share exactly.
+ *
+ * algo      : BF_PAD or BF_LERP; reads the table the matching load_coefficients_* loaded, the one bf_miso_device reads.
+ * d_signals : HIP device pointer, float32 [frames][m_total][N_SAMPLES], mic-major, as bf_miso_device
+ * adaptive_array / n : HOST array of the active mic rows, as bf_miso_device; here no row may be listed twice
+ * d_offsets : HIP device pointer, int32 [frames][beams], table offsets as bf_miso_device takes them (d * n)
+ * d_beams   : HIP device pointer, float32 [frames][beams][beam_stride], beam_stride >= N_SAMPLES: the RAW beams, as bf_miso_device
+ *             writes them with mic_gain 0
+ * gain      : the CLEAN loop gain, any finite value; c = gain / (float)n, one float32 division on the host
+ * d_residual: HIP device pointer, float32 [frames][m_total][N_SAMPLES].  Every element is written; rows not named in adaptive_array
+ *             are copied unchanged.  May be d_signals itself (every element depends on its own input element and the beams only);
+ *             any other overlap of the two is not supported.
+ * d_status  : HIP device pointer, int32 [frames][beams], or NULL; bf_miso_device's codes: 0 ok, 1 offset negative or past the loaded
+ *             table (offset + n > entries).  A rejected beam subtracts nothing and its d_beams row is never read, so a -1 slot from
+ *             bf_peaks_device, or the NaN beam bf_miso_device wrote for it, is harmless.
+ *
+ * Definition, float32, every operation rounded once and none contracted.  N = N_SAMPLES; p, h = the loaded table's entries at
+ * offset_b + m (pad: p only); o_b = beam b of the frame; r_m = adaptive_array[m].  For every j in [0, N):
+ *     acc = x[f][r_m][j]
+ *     for b = 0 .. beams-1, accepted offsets only, in this order:
+ *         pad :  a = (j + p < N) ? o_b[j + p] : 0
+ *         lerp:  u = (j + p + 1 < N) ? o_b[j + p + 1] : 0
+ *                v = (j >= 1 && j + p < N) ? o_b[j + p] : 0
+ *                a = (1 - h) * u  +  h * v                   (sub, mul, mul, add)
+ *         acc = acc - c * a                                  (mul, sub)
+ *     residual[f][r_m][j] = acc
+ * `a` is the transpose of the library's delay operators, miso_pad: out[p + i] += s[i] (i < N - p), miso_lerp: out[p + i + 1] +=
+ * s[i] + h * (s[i + 1] - s[i]) (i < N - p - 1): sum_t beam(x)[t] * o[t] == sum_{m, j} x[m][j] * a_m[j] in exact arithmetic.  Table
+ * entries at or beyond N give a = 0; NaN and infinities propagate.  The result does not depend on which internal path runs (16-byte
+ * or 4-byte accesses, beams staged in LDS or read through L2).
+ * stream    : hipStream_t (0 = null stream).  Enqueue only, no allocation after the first call -- except a call with a new
+ *             adaptive array or m_total, which synchronises the device as bf_das_device does; graph-capturable after one warm-up
+ *             call.  Does not change bf_last_das_variant.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: any algo but BF_PAD / BF_LERP; a null pointer (d_status
+ * excepted); frames < 1; beams < 1 or > BF_REMOVE_MAX_BEAMS; n < 1; beam_stride < N_SAMPLES; an adaptive_array row outside
+ * [0, m_total) or listed twice; a gain that is not finite; no GPU; a table that is not loaded.  All arguments are checked before
+ * device bring-up; the table check needs the device the table lives on. */
+#define BF_REMOVE_MAX_BEAMS 64
+int bf_remove_sources_device(int algo, const float *d_signals, int m_total, int frames, const int *adaptive_array, int n,
+                             const int *d_offsets, int beams, const float *d_beams, int beam_stride, float gain,
+                             float *d_residual, int *d_status, void *stream);
+
 /* ---- continuous-stream mode of the device path (BF_PAD, BF_LERP): delays read the previous window ----
  * Every other entry point treats a window as if the world began at its first sample: a microphone delayed by p samples gives
  * nothing to the first p outputs (out[p + i] += s[i], zero prefix), as the reference does.  That is the first item of the reference

@@ -129,6 +129,8 @@ struct State {
     DevBuf<unsigned long long> peaks_work;  // row-pass results and per-tile lists of bf_peaks_device's tiled form (bf::peaks_workspace_words)
     long long fd_tw_key = -1;
     std::vector<int> mics_host;          // what d_mics currently holds
+    DevBuf<int32_t> d_row_slot;          // bf_remove_sources_device: frame row -> slot of the adaptive array, -1 = not listed
+    std::vector<int32_t> row_slot_host;  // what d_row_slot currently holds
     std::vector<float> published;        // bf_publish_frame / get_data
     std::vector<int> disabled_mics;      // get_data's dead-microphone rows
     bool disabled_default = true;
@@ -1041,6 +1043,66 @@ int bf_miso_device(int algo, const float* d_signals, int m_total, int frames, co
     L.frames = frames;
     return HIP_OK(bf::launch_miso_batch(L, plan, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status,
                                         reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
+int bf_remove_sources_device(int algo, const float* d_signals, int m_total, int frames, const int* adaptive_array, int n, const int* d_offsets,
+                             int beams, const float* d_beams, int beam_stride, float gain, float* d_residual, int* d_status, void* stream)
+{
+    static const char* who = "bf_remove_sources_device";
+    State& s = S();
+    std::lock_guard<std::mutex> lock(s.mu);
+    sizes_from_env_once();
+    const int N = s.sz.n_samples;
+    if (algo == bf::ALGO_HYBRID || algo == bf::ALGO_FIR_NAIVE || algo == bf::ALGO_FIR_VEC) {
+        static const char* name[] = {"", "", "BF_HYBRID", "BF_FIR_NAIVE", "BF_FIR_VEC"};
+        set_error("%s: algo %s (%d) has no adjoint here (the subtraction exists for BF_PAD and BF_LERP)", who, name[algo], algo);
+        return -1;
+    }
+    if (algo != bf::ALGO_PAD && algo != bf::ALGO_LERP) { set_error("%s: unknown algo %d", who, algo); return -1; }
+    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"},
+                                                               {d_beams, "d_beams"}, {d_residual, "d_residual"}};
+    for (const auto& a : ptrs)
+        if (!a.p) { set_error("%s: %s is null", who, a.name); return -1; }
+    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
+    if (beams < 1) { set_error("%s: beams = %d < 1", who, beams); return -1; }
+    if (beams > BF_REMOVE_MAX_BEAMS) { set_error("%s: beams = %d > %d", who, beams, BF_REMOVE_MAX_BEAMS); return -1; }
+    if (n < 1) { set_error("%s: n = %d < 1", who, n); return -1; }
+    if (beam_stride < N) { set_error("%s: beam_stride = %d < N_SAMPLES = %d", who, beam_stride, N); return -1; }
+    for (int i = 0; i < n; ++i)
+        if (adaptive_array[i] < 0 || adaptive_array[i] >= m_total) {
+            set_error("%s: adaptive_array[%d] = %d is not a row of frames with m_total = %d rows", who, i, adaptive_array[i], m_total);
+            return -1;
+        }
+    {
+        std::vector<int> sorted(adaptive_array, adaptive_array + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+        if (twice != sorted.end()) {
+            set_error("%s: row %d is listed twice in adaptive_array; which beam sample to subtract from it would be ambiguous", who, *twice);
+            return -1;
+        }
+    }
+    if (!std::isfinite(gain)) { set_error("%s: gain = %g is not finite", who, (double)gain); return -1; }
+    if (!ensure_device()) return -1;
+    const int slot = slot_of(algo);
+    const TableSet& t = s.tab[slot];
+    if (!t.loaded) { set_error("%s: %s has not been called", who, loader_name(slot)); return -1; }
+    // frame row -> slot of the adaptive array, kept on the device while the array and m_total stay the same
+    std::vector<int32_t> row_slot((size_t)m_total, -1);
+    for (int i = 0; i < n; ++i) row_slot[(size_t)adaptive_array[i]] = i;
+    if (row_slot != s.row_slot_host || !s.d_row_slot.p) {
+        // launches already enqueued on the caller's (non-blocking) streams may still read the old copy
+        if (s.d_row_slot.p && !HIP_OK(hipDeviceSynchronize())) return -1;
+        s.row_slot_host.clear();
+        if (!upload(s.d_row_slot, row_slot.data(), row_slot.size())) return -1;
+        s.row_slot_host = row_slot;
+    }
+    bf::DeviceTables tab;
+    tab.whole = t.whole.p; tab.frac = t.frac.p; tab.max_whole = t.max_whole;
+    const float c = gain / (float)n;
+    static_assert(BF_REMOVE_MAX_BEAMS == bf::kRemoveMaxBeams, "the header's limit is the kernel's");
+    return HIP_OK(bf::launch_remove_sources(algo, d_signals, d_residual, m_total, frames, N, n, s.d_row_slot.p, tab, t.entries, d_offsets, beams, d_beams,
+                                            beam_stride, c, d_status, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
 }
 
 // ---------------------------------------------------------------- continuous-stream mode (pad / lerp)

@@ -106,6 +106,14 @@ hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const flo
 hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
                                long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream);
 
+// bf_remove_sources_device (pad and lerp): d_residual = d_signals - c * (adjoint of the delay operator)(beams), rows of the frames
+// named by d_row_slot int32 [m_total] (slot m of the adaptive array, or -1: the row is copied).  d_offsets / d_status / entries as
+// launch_miso_batch; d_beams float32 [frames][beams][beam_stride], rows of rejected offsets never read.  d_residual may equal d_signals.
+constexpr int kRemoveMaxBeams = 64;
+hipError_t launch_remove_sources(int algo, const float* d_signals, float* d_residual, int m_total, int frames, int n_samples, int n_mics,
+                                 const int32_t* d_row_slot, const DeviceTables& tab, long long entries, const int32_t* d_offsets, int beams,
+                                 const float* d_beams, int beam_stride, float c, int* d_status, hipStream_t stream);
+
 // FPGA protocol-v2 datagrams (one per sample instant) -> float32 [n_mics_out][n_samples] mic-major frame (receiver.c:94-151).
 hipError_t launch_ingest(const void* d_packets, int packet_stride, int header_bytes, int n_samples, int n_mics_out, int stream_len,
                          int rows, int columns, float* d_frame, hipStream_t stream);

@@ -97,6 +97,8 @@ _sig("bf_get_steer", C.c_int, IP)
 _sig("bf_das_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, IP, C.c_int, C.c_int, C.c_int, C.c_void_p)
 _sig("bf_miso_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, IP, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
      C.c_void_p)
+_sig("bf_remove_sources_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, IP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
+     C.c_void_p, C.c_void_p)
 _sig("bf_stream_history", C.c_int, C.c_int)
 _sig("bf_miso_stream_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, IP, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
      C.c_int, C.c_void_p, C.c_void_p)

@@ -6,7 +6,10 @@ detection box (`focus_beam`, sensorfusion/decider.py:70-88).  `BeamListener` is 
 already in HBM (bf_ingest_device output, FusedPipeline's batch) -> the beams of every frame at any number of offsets in one
 enqueue (bf_miso_device), and `loudest` aims one beam per frame at the frame's loudest direction of a power map without a
 host round trip (bf_peak_offsets_device); `sources` gives up to k beams per frame, one per separated source of the map
-(bf_peaks_device).  All only enqueue on the current torch stream, so maps, peaks and beams can be captured as one graph.  Raw beams (mic_gain 0) are bit-identical to the reference's miso_* calls."""
+(bf_peaks_device).  `maps` makes the power maps themselves (bf_das_device), `remove` takes beams back out of the frames
+(bf_remove_sources_device) and `separate` runs the two in a loop -- map, loudest direction, beam, subtract -- so that a source
+under a stronger one's sidelobes is found and heard: time-domain CLEAN.  All only enqueue on the current torch stream, so maps,
+peaks, beams and residuals can be captured as one graph.  Raw beams (mic_gain 0) are bit-identical to the reference's miso_* calls."""
 import numpy as np
 
 from interface import config
@@ -120,3 +123,80 @@ class BeamListener:
         if rc != 0:
             _fail("bf_peaks_device")
         return offs, vals, counts
+
+    def _check_frames(self, d_frames):
+        torch = _torch()
+        if d_frames.dim() != 3 or d_frames.dtype != torch.float32 or not d_frames.is_cuda or d_frames.shape[2] != config.N_SAMPLES or d_frames.shape[0] < 1:
+            raise ValueError("d_frames must be a float32 cuda tensor [F, M_total, %d], got %s %s" % (config.N_SAMPLES, d_frames.dtype, tuple(d_frames.shape)))
+
+    def maps(self, d_frames, dir_begin=0, dir_end=None):
+        """d_frames float32 cuda [F, M_total, N_SAMPLES] -> power maps float32 [F, dir_end - dir_begin] of the flat direction range
+        (default: the whole grid) through bf_das_device."""
+        torch = _torch()
+        self._check_frames(d_frames)
+        frames = d_frames.contiguous()
+        F, m_total, N = frames.shape
+        D = config.MAX_RES_X * config.MAX_RES_Y
+        dir_end = D if dir_end is None else int(dir_end)
+        dir_begin = int(dir_begin)
+        if dir_begin < 0 or dir_end > D or dir_begin >= dir_end:
+            raise ValueError("bad direction range [%d, %d) of %d" % (dir_begin, dir_end, D))
+        img = torch.empty((F, dir_end - dir_begin), dtype=torch.float32, device=self.device)
+        rc = _entry("bf_das_device")(ALGOS[self.algo], frames.data_ptr(), m_total, img.data_ptr(), img.shape[1], F, nat.iptr(self.mics), self.n,
+                                     dir_begin, dir_end, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _fail("bf_das_device")
+        return img
+
+    def remove(self, d_frames, offsets, d_beams, gain=1.0, out=None):
+        """d_frames float32 cuda [F, M_total, N_SAMPLES]; offsets [B] or [F, B] as listen() takes them; d_beams float32 cuda [F, B, >= N_SAMPLES],
+        the raw beams listen() gave at those offsets -> (residual float32 [F, M_total, N_SAMPLES], status int32 [F, B]): the frames with
+        gain / n times every accepted beam, projected back onto the microphones by the adjoint of the delay, subtracted
+        (bf_remove_sources_device; pad and lerp).  Rejected offsets (status 1) subtract nothing.  out=d_frames runs in place."""
+        torch = _torch()
+        self._check_frames(d_frames)
+        if out is None:
+            frames = d_frames.contiguous()
+            out = torch.empty_like(frames)
+        else:
+            if out.shape != d_frames.shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or not d_frames.is_contiguous():
+                raise ValueError("out must be a contiguous float32 cuda tensor shaped like a contiguous d_frames, got %s %s" % (out.dtype, tuple(out.shape)))
+            frames = d_frames
+        F, m_total, N = frames.shape
+        offs = self._offsets(offsets, F)
+        B = offs.shape[1]
+        if d_beams.dim() != 3 or d_beams.dtype != torch.float32 or not d_beams.is_cuda or d_beams.shape[:2] != (F, B) or d_beams.shape[2] < N:
+            raise ValueError("d_beams must be a float32 cuda tensor [%d, %d, >= %d], got %s %s" % (F, B, N, d_beams.dtype, tuple(d_beams.shape)))
+        beams = d_beams.contiguous()
+        status = torch.empty((F, B), dtype=torch.int32, device=self.device)
+        rc = _entry("bf_remove_sources_device")(ALGOS[self.algo], frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, offs.data_ptr(), B,
+                                                beams.data_ptr(), beams.shape[2], float(gain), out.data_ptr(), status.data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _fail("bf_remove_sources_device")
+        return out, status
+
+    def separate(self, d_frames, k, gain=1.0, floor_rel=0.0, floor_abs=0.0):
+        """d_frames float32 cuda [F, M_total, N_SAMPLES] -> (offsets int32 [F, k], values float32 [F, k], beams float32 [F, k, N_SAMPLES],
+        residual float32 [F, M_total, N_SAMPLES]): k rounds of map -> loudest direction -> beam -> subtract on a copy of the frames.
+        beams[:, i] is source i heard with sources 0 .. i-1 already taken out of the microphones, values[:, i] its power in the map of
+        that residual.  A frame whose map falls below max(floor_abs, floor_rel * its maximum) -- or has no finite entry -- stops: its
+        slot holds offset -1, value 0 and a NaN beam, and nothing more is subtracted from it.  No host synchronisation."""
+        torch = _torch()
+        self._check_frames(d_frames)
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1, got %d" % k)
+        residual = d_frames.contiguous().clone()
+        F, m_total, N = residual.shape
+        offsets = torch.empty((F, k), dtype=torch.int32, device=self.device)
+        values = torch.empty((F, k), dtype=torch.float32, device=self.device)
+        beams = torch.empty((F, k, N), dtype=torch.float32, device=self.device)
+        rows, cols = config.MAX_RES_X, config.MAX_RES_Y
+        for i in range(k):
+            power = self.maps(residual)
+            offs, vals, _ = self.sources(power, 1, max(rows, cols), floor_rel, floor_abs)    # that radius leaves the one global maximum
+            beam, _ = self.listen(residual, offs)
+            self.remove(residual, offs, beam, gain, out=residual)
+            offsets[:, i:i + 1], values[:, i:i + 1], beams[:, i:i + 1] = offs, vals, beam
+        return offsets, values, beams, residual

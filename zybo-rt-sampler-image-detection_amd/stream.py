@@ -86,6 +86,14 @@ class StreamBeamformer(BeamListener):
             _fail("bf_miso_stream_device")
         return out, status
 
+    def remove(self, *args, **kwargs):
+        raise NotImplementedError("StreamBeamformer.remove: stream beams read the previous window, and the adjoint BeamListener.remove applies is "
+                                  "that of the zero-prefix delay: it does not match them")
+
+    def separate(self, *args, **kwargs):
+        raise NotImplementedError("StreamBeamformer.separate: stream beams read the previous window, and the adjoint BeamListener.remove applies is "
+                                  "that of the zero-prefix delay: it does not match them")
+
     def advance(self, d_frames):
         """Done with this batch: keep a copy of its last frame as the history of the next batch's first frame (which starts `hop`
         samples after that frame did)."""
