@@ -284,6 +284,70 @@ int bf_remove_sources_device(int algo, const float *d_signals, int m_total, int 
                              const int *d_offsets, int beams, const float *d_beams, int beam_stride, float gain,
                              float *d_residual, int *d_status, void *stream);
 
+/* ---- track map sources across frames: bf_peaks_device's [frames][k] offsets -> [frames][slots] offsets with identity over time ----
+ * bf_peaks_device orders a frame's sources loudest first, so two talkers of similar level swap slots from window to window, a source
+ * that drops out shifts everyone behind it up a slot, and a one-window false alarm takes a slot.  Joining slot b of every window
+ * into one signal needs slot b to be the same source in every window.  The reference authors list this as open (PC/TODO.md,
+ * "Tracking + Prediction") and wrote a constant-velocity Kalman filter for it (PC/src/kf.hpp) that nothing calls.  This call is that
+ * filter, one per slot, with a gated greedy nearest-neighbour association in front of it and track birth / coasting / death around
+ * it.  ONE deliberate difference from kf.hpp: a track starts at its first measurement (velocity 0, P = I), not at the origin.
+ *
+ * d_offsets : HIP device pointer, int32 [frames][k], as bf_peaks_device writes it: d * offset_per_dir or -1; k <= BF_PEAKS_MAX_K.  An
+ *             entry is a DETECTION iff it is >= 0, a multiple of offset_per_dir, and d < rows*cols; anything else (an empty -1 slot
+ *             included) is ignored and counted in d_counts[f][3].  A detection's position is zx = (float)(d / cols),
+ *             zy = (float)(d % cols), the library's own order d = x*cols + y.
+ * d_state   : HIP device pointer, bf_track_state_words(slots) = 4 + 12 * slots 32-bit words, read and written: the tracks carried from
+ *             one call to the next.  All zero is a fresh stream (hipMemset it once).  Integer fields int32, the rest float32:
+ *                 word 0                 next_id (ids start at 1 and are never reused)
+ *                 words 1..3             0
+ *                 words 4 + 12*s ..      slot s: id (0 = free), hits, misses, 0, x, vx, y, vy, p00, p01, p11, 0
+ *             A free slot is written as twelve zeros.
+ * d_track_offsets : HIP device pointer, int32 [frames][slots]: for a live slot with hits >= min_hits, (xi*cols + yi) * offset_per_dir
+ *             with xi = clamp((int)rintf(x), 0, rows-1), yi = clamp((int)rintf(y), 0, cols-1) -- ready for bf_miso_device; every other
+ *             slot holds -1, which bf_miso_device rejects with status 1 and a NaN beam.
+ * d_track_ids : int32 [frames][slots], or NULL: the slot's id, 0 for a free slot; unconfirmed tracks (hits < min_hits) show theirs.
+ * d_track_pos : float32 [frames][slots][4], or NULL: x, y, vx, vy; zeros for a free slot.
+ * d_match   : int32 [frames][slots], or NULL: the column of d_offsets the slot took in this frame (a newborn track: the column it was
+ *             born from); -1 when the slot is coasting or free.
+ * d_counts  : int32 [frames][4], or NULL: tracks born, tracks ended, detections dropped because no slot was free, entries ignored.
+ * Every entry of every given output is written by every call.
+ *
+ * Definition.  Frames in order f = 0 .. frames-1; float32, every operation rounded once and none contracted, plain division.
+ * gate2 = gate * gate (one float32 multiplication on the host).  A slot is live iff its id != 0.  Per frame:
+ *   1. Predict every live slot:   x = x + vx;  y = y + vy;
+ *                                 a = p00 + p01;  b = p01 + p11;  p00 = (a + b) + q;  p01 = b;  p11 = p11 + q
+ *      (A P A^T + Q of kf.hpp:88-89 for one axis: kf.hpp's A, Q, H, R never couple the axes and P starts as the identity, so all axes
+ *      share one 2x2 covariance and the 6x6 form reduces to this.)
+ *   2. Associate.  For live slot s and detection column j: dx = zx - x; dy = zy - y; cost = dx*dx + dy*dy (sub, sub, mul, mul, add);
+ *      the pair is eligible iff cost <= gate2.  Repeat: among the eligible pairs whose slot and detection are both unassigned take the
+ *      smallest by (cost, slot index, column) and assign it; stop when none is left.
+ *   3. Update each assigned slot from its predicted state and its detection z (kf.hpp:92-98):
+ *                                 S = p00 + r;  k0 = p00 / S;  k1 = p01 / S
+ *                     per axis:   e = z - x;  x = x + k0*e;  v = v + k1*e
+ *          from the old values:   p00 = p00 - k0*p00;  p01 = p01 - k0*p01;  p11 = p11 - k1*p01
+ *                                 hits += 1;  misses = 0
+ *   4. Coast each unassigned live slot: it keeps the prediction, misses += 1; if misses > max_miss the slot becomes free (counted as
+ *      ended) and is available to step 5 of this same frame.
+ *   5. Birth.  Each unassigned detection, in column order, takes the lowest free slot: next_id += 1; id = next_id; hits = 1;
+ *      misses = 0; x = zx; y = zy; vx = vy = 0; p00 = 1; p01 = 0; p11 = 1; d_match gets its column.  With no free slot the detection
+ *      is dropped and counted.
+ *   6. Write the frame's outputs from the state as it now stands.
+ * The clamp of step 6's rounding is done in float before the conversion, so a position outside the int range (or NaN -> 0) is defined.
+ * One call over F frames equals two calls over F1 + F2 frames on the same d_state, bit for bit.  next_id wraps like an int32.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: one launch of one 64-lane wave (lane s owns slot s), no allocation, no
+ *             synchronisation, no workspace; graph-capturable from the first call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_offsets, d_state or d_track_offsets null; frames < 1;
+ * k < 1 or k > BF_PEAKS_MAX_K; slots < 1 or slots > BF_TRACK_MAX_SLOTS; rows, cols or offset_per_dir < 1; rows*cols not fitting an
+ * int; (rows*cols - 1) * offset_per_dir > INT_MAX; gate not finite or < 0; max_miss < 0; min_hits < 1; q not finite or < 0; r not
+ * finite or <= 0; no GPU.  All arguments are checked before device bring-up.
+ * bf_track_state_words(slots) returns 4 + 12 * slots, or -1 for slots outside [1, BF_TRACK_MAX_SLOTS] (it records no error). */
+#define BF_TRACK_MAX_SLOTS 64
+int bf_track_state_words(int slots);
+int bf_track_sources_device(const int *d_offsets, int frames, int k, int rows, int cols, int offset_per_dir,
+                            int slots, float gate, int max_miss, int min_hits, float q, float r,
+                            void *d_state, int *d_track_offsets, int *d_track_ids, float *d_track_pos,
+                            int *d_match, int *d_counts, void *stream);
+
 /* ---- continuous-stream mode of the device path (BF_PAD, BF_LERP): delays read the previous window ----
  * Every other entry point treats a window as if the world began at its first sample: a microphone delayed by p samples gives
  * nothing to the first p outputs (out[p + i] += s[i], zero prefix), as the reference does.  That is the first item of the reference

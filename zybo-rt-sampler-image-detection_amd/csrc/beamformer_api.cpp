@@ -1272,6 +1272,47 @@ int bf_peaks_device(const float* d_power, int frames, int image_stride, int rows
                                    s.peaks_work.p, s.peaks_work.cap, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
 }
 
+int bf_track_state_words(int slots)
+{
+    return slots >= 1 && slots <= BF_TRACK_MAX_SLOTS ? 4 + 12 * slots : -1;
+}
+
+int bf_track_sources_device(const int* d_offsets, int frames, int k, int rows, int cols, int offset_per_dir, int slots, float gate, int max_miss, int min_hits,
+                            float q, float r, void* d_state, int* d_track_offsets, int* d_track_ids, float* d_track_pos, int* d_match, int* d_counts,
+                            void* stream)
+{
+    static const char* who = "bf_track_sources_device";
+    static_assert(BF_TRACK_MAX_SLOTS == bf::kTrackMaxSlots, "the header's limit is the kernel's");
+    std::lock_guard<std::mutex> lock(S().mu);
+    sizes_from_env_once();
+    if (!d_offsets) { set_error("%s: d_offsets is null", who); return -1; }
+    if (!d_state) { set_error("%s: d_state is null", who); return -1; }
+    if (!d_track_offsets) { set_error("%s: d_track_offsets is null", who); return -1; }
+    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
+    if (k < 1) { set_error("%s: k = %d < 1", who, k); return -1; }
+    if (k > BF_PEAKS_MAX_K) { set_error("%s: k = %d > %d", who, k, BF_PEAKS_MAX_K); return -1; }
+    if (slots < 1) { set_error("%s: slots = %d < 1", who, slots); return -1; }
+    if (slots > BF_TRACK_MAX_SLOTS) { set_error("%s: slots = %d > %d", who, slots, BF_TRACK_MAX_SLOTS); return -1; }
+    if (rows < 1) { set_error("%s: rows = %d < 1", who, rows); return -1; }
+    if (cols < 1) { set_error("%s: cols = %d < 1", who, cols); return -1; }
+    if (offset_per_dir < 1) { set_error("%s: offset_per_dir = %d < 1", who, offset_per_dir); return -1; }
+    const long long D = (long long)rows * cols;
+    if (D > (long long)std::numeric_limits<int>::max()) { set_error("%s: rows * cols = %lld does not fit an int", who, D); return -1; }
+    if ((D - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
+        set_error("%s: (rows * cols - 1) * offset_per_dir = %lld does not fit an int offset", who, (D - 1) * offset_per_dir);
+        return -1;
+    }
+    if (!std::isfinite(gate) || gate < 0.0f) { set_error("%s: gate = %g is not finite and >= 0", who, (double)gate); return -1; }
+    if (max_miss < 0) { set_error("%s: max_miss = %d < 0", who, max_miss); return -1; }
+    if (min_hits < 1) { set_error("%s: min_hits = %d < 1", who, min_hits); return -1; }
+    if (!std::isfinite(q) || q < 0.0f) { set_error("%s: q = %g is not finite and >= 0", who, (double)q); return -1; }
+    if (!std::isfinite(r) || !(r > 0.0f)) { set_error("%s: r = %g is not finite and > 0", who, (double)r); return -1; }
+    if (!ensure_device()) return -1;
+    const float gate2 = gate * gate;                 // one float32 multiplication, as the definition says
+    return HIP_OK(bf::launch_track_sources(d_offsets, frames, k, rows, cols, offset_per_dir, slots, gate2, max_miss, min_hits, q, r, static_cast<int*>(d_state),
+                                           d_track_offsets, d_track_ids, d_track_pos, d_match, d_counts, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

@@ -141,6 +141,13 @@ size_t peaks_workspace_words(int frames, int rows, int cols, int k);
 hipError_t launch_peaks(const float* d_power, int frames, int image_stride, int rows, int cols, int radius, int k, float floor_rel, float floor_abs,
                         int offset_per_dir, int* d_offsets, float* d_values, int* d_counts, unsigned long long* d_workspace, size_t workspace_words,
                         hipStream_t stream);
+// bf_track_sources_device: bf_peaks_device's [frames][k] offsets -> [frames][slots] offsets whose slot s is one source over time (greedy
+// gated nearest neighbour + a constant-velocity Kalman filter per slot).  One launch of one wave; d_state (4 + 12 * slots words)
+// carries the tracks from call to call.  k and slots at most kTrackMaxSlots; the four outputs after d_track_offsets may be null.
+constexpr int kTrackMaxSlots = 64;
+hipError_t launch_track_sources(const int* d_offsets, int frames, int k, int rows, int cols, int offset_per_dir, int slots, float gate2, int max_miss,
+                                int min_hits, float q, float r, int* d_state, int* d_track_offsets, int* d_track_ids, float* d_track_pos, int* d_match,
+                                int* d_counts, hipStream_t stream);
 
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.

@@ -727,4 +727,185 @@ hipError_t launch_peaks(const float* d_power, int frames, int image_stride, int 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- bf_track_sources_device: identity over time for bf_peaks_device's sources
+//
+// The frame loop is sequential by definition (a frame's association reads the state the previous frame left), so the launch is ONE
+// wave: lane s owns slot s and keeps its track in registers from the first frame to the last; the state buffer is read once and
+// written once.  Per frame: lanes j < k decode the detection row into LDS (512 bytes, read back by broadcast), the row of frame
+// f + 1 is already in flight; the greedy association runs as wave-wide rounds -- every unassigned lane holds its best unassigned
+// eligible detection, the 64-bit key (cost bits << 32) | (slot << 8) | column is reduced to its minimum across the wave (cost >= 0,
+// so the bits order as the floats do, and the low bytes are the definition's tie rule), the winner is assigned and only lanes whose
+// best detection was just taken look again; at most min(slots, k) rounds.  Births are serial over the few detections left, lowest
+// free slot by ballot.  No atomics, no workspace.  The kernel is bound by latency, not by throughput.
+namespace {
+
+constexpr unsigned kTrackNone = 0xffffffffu;       // no eligible detection (a cost's bits are at most +inf's, 0x7f800000)
+
+// lane's best (cost bits, column) among the detections of `avail`: ascending columns, only a smaller cost replaces the best so far
+__device__ __forceinline__ void track_best(unsigned long long avail, const float* zx, const float* zy, float x, float y, float gate2, unsigned& bc, int& bj)
+{
+    bc = kTrackNone;
+    bj = -1;
+    for (; avail; avail &= avail - 1) {
+        const int j = __ffsll((long long)avail) - 1;
+        const float dx = zx[j] - x, dy = zy[j] - y;
+        const float cost = dx * dx + dy * dy;
+        if (cost <= gate2) {
+            const unsigned cb = __float_as_uint(cost);
+            if (cb < bc) { bc = cb; bj = j; }
+        }
+    }
+}
+
+// clamp((int)rintf(v), 0, n - 1), the clamp to the int range done in float: no conversion overflows, a NaN gives 0
+__device__ __forceinline__ int track_pixel(float v, int n)
+{
+    const float r = rintf(v);
+    if (!(r >= 0.0f)) return 0;
+    return min((int)fminf(r, 2147483520.0f), n - 1);
+}
+
+__global__ void __launch_bounds__(64) track_sources_kernel(const int* __restrict__ offsets, int frames, int k, int rows, int cols, int offset_per_dir,
+                                                         int slots, float gate2, int max_miss, int min_hits, float q, float r, int* __restrict__ state,
+                                                         int* __restrict__ track_offsets, int* __restrict__ track_ids, float* __restrict__ track_pos,
+                                                         int* __restrict__ match, int* __restrict__ counts)
+{
+    __shared__ float zx[64], zy[64];
+    const int lane = threadIdx.x;
+    const bool mine = lane < slots;
+    const int D = rows * cols;
+    int* const sw = state + 4 + 12 * lane;
+    float* const sf = reinterpret_cast<float*>(sw);
+    int next_id = state[0];
+    int id = 0, hits = 0, misses = 0;
+    float x = 0.0f, vx = 0.0f, y = 0.0f, vy = 0.0f, p00 = 0.0f, p01 = 0.0f, p11 = 0.0f;
+    if (mine) {
+        id = sw[0]; hits = sw[1]; misses = sw[2];
+        x = sf[4]; vx = sf[5]; y = sf[6]; vy = sf[7]; p00 = sf[8]; p01 = sf[9]; p11 = sf[10];
+    }
+    int raw = lane < k ? offsets[lane] : -1;
+    for (int f = 0; f < frames; ++f) {
+        const int cur = raw;
+        if (f + 1 < frames && lane < k) raw = offsets[(size_t)(f + 1) * k + lane];      // in flight while this frame is worked on
+        bool det = false;
+        if (cur >= 0) {                                  // (lanes >= k hold -1)
+            const int d = cur / offset_per_dir;
+            det = d * offset_per_dir == cur && d < D;
+            if (det) {
+                const int dx = d / cols;
+                zx[lane] = (float)dx;
+                zy[lane] = (float)(d - dx * cols);
+            }
+        }
+        unsigned long long avail = __ballot(det);        // detections no slot has taken yet
+        const int invalid = k - __popcll(avail);
+        // 1. predict
+        if (id != 0) {
+            x = x + vx;
+            y = y + vy;
+            const float a = p00 + p01, b = p01 + p11;
+            p00 = (a + b) + q;
+            p01 = b;
+            p11 = p11 + q;
+        }
+        __syncthreads();                                 // zx, zy visible
+        // 2. associate
+        int took = -1;
+        bool want = id != 0;
+        unsigned bc = kTrackNone;
+        int bj = -1;
+        if (want) track_best(avail, zx, zy, x, y, gate2, bc, bj);
+        for (;;) {
+            unsigned long long key = bj >= 0 ? ((unsigned long long)bc << 32) | (unsigned)(lane << 8) | (unsigned)bj : ~0ull;
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long o = __shfl_xor(key, off, 64);
+                key = o < key ? o : key;
+            }
+            if (key == ~0ull) break;                     // uniform: every lane holds the minimum
+            const int win = __builtin_amdgcn_readfirstlane((int)(unsigned)key);
+            const int ws = (win >> 8) & 0xff, wj = win & 0xff;
+            avail &= ~(1ull << wj);
+            if (lane == ws) { took = wj; want = false; bj = -1; }
+            const bool redo = want && bj == wj;
+            if (__any(redo)) {
+                if (redo) track_best(avail, zx, zy, x, y, gate2, bc, bj);
+            }
+        }
+        // 3. update / 4. coast
+        bool ends = false;
+        if (took >= 0) {
+            const float S = p00 + r;
+            const float k0 = p00 / S, k1 = p01 / S;
+            const float ex = zx[took] - x;
+            x = x + k0 * ex;
+            vx = vx + k1 * ex;
+            const float ey = zy[took] - y;
+            y = y + k0 * ey;
+            vy = vy + k1 * ey;
+            const float o00 = p00, o01 = p01;
+            p00 = o00 - k0 * o00;
+            p01 = o01 - k0 * o01;
+            p11 = p11 - k1 * o01;
+            hits += 1;
+            misses = 0;
+        } else if (id != 0) {
+            misses += 1;
+            ends = misses > max_miss;
+            if (ends) id = 0;
+        }
+        const int ended = __popcll(__ballot(ends));
+        // 5. birth: the detections left, in column order, each into the lowest free slot
+        unsigned long long free_slots = __ballot(mine && id == 0);
+        int born = 0, dropped = 0;
+        for (; avail; avail &= avail - 1) {
+            if (!free_slots) { dropped = __popcll(avail); break; }
+            const int j = __ffsll((long long)avail) - 1;
+            const int s = __ffsll((long long)free_slots) - 1;
+            free_slots &= free_slots - 1;
+            next_id += 1;
+            born += 1;
+            if (lane == s) {
+                id = next_id; hits = 1; misses = 0; took = j;
+                x = zx[j]; y = zy[j]; vx = 0.0f; vy = 0.0f;
+                p00 = 1.0f; p01 = 0.0f; p11 = 1.0f;
+            }
+        }
+        // 6. write
+        if (mine) {
+            const size_t o = (size_t)f * slots + lane;
+            const bool live = id != 0;
+            track_offsets[o] = live && hits >= min_hits ? (track_pixel(x, rows) * cols + track_pixel(y, cols)) * offset_per_dir : -1;
+            if (track_ids) track_ids[o] = id;
+            if (track_pos) {
+                track_pos[o * 4 + 0] = live ? x : 0.0f;
+                track_pos[o * 4 + 1] = live ? y : 0.0f;
+                track_pos[o * 4 + 2] = live ? vx : 0.0f;
+                track_pos[o * 4 + 3] = live ? vy : 0.0f;
+            }
+            if (match) match[o] = live ? took : -1;
+        }
+        if (counts && lane < 4) counts[(size_t)f * 4 + lane] = lane == 0 ? born : lane == 1 ? ended : lane == 2 ? dropped : invalid;
+        __syncthreads();                                 // every read of zx, zy is done before the next row lands
+    }
+    if (lane == 0) { state[0] = next_id; state[1] = 0; state[2] = 0; state[3] = 0; }
+    if (mine) {
+        const bool live = id != 0;                       // a free slot is stored as zeros
+        sw[0] = id; sw[1] = live ? hits : 0; sw[2] = live ? misses : 0; sw[3] = 0;
+        sf[4] = live ? x : 0.0f; sf[5] = live ? vx : 0.0f; sf[6] = live ? y : 0.0f; sf[7] = live ? vy : 0.0f;
+        sf[8] = live ? p00 : 0.0f; sf[9] = live ? p01 : 0.0f; sf[10] = live ? p11 : 0.0f; sw[11] = 0;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_track_sources(const int* d_offsets, int frames, int k, int rows, int cols, int offset_per_dir, int slots, float gate2, int max_miss,
+                                int min_hits, float q, float r, int* d_state, int* d_track_offsets, int* d_track_ids, float* d_track_pos, int* d_match,
+                                int* d_counts, hipStream_t stream)
+{
+    if (k < 1 || k > 64 || slots < 1 || slots > 64) return hipErrorInvalidValue;   // one wave: a lane per slot and per column (das_kernels.h: kTrackMaxSlots)
+    hipLaunchKernelGGL(track_sources_kernel, dim3(1), dim3(64), 0, stream, d_offsets, frames, k, rows, cols, offset_per_dir, slots, gate2, max_miss, min_hits,
+                       q, r, d_state, d_track_offsets, d_track_ids, d_track_pos, d_match, d_counts);
+    return hipGetLastError();
+}
+
 }  // namespace bf
