@@ -348,6 +348,69 @@ int bf_track_sources_device(const int *d_offsets, int frames, int k, int rows, i
                             void *d_state, int *d_track_offsets, int *d_track_ids, float *d_track_pos,
                             int *d_match, int *d_counts, void *stream);
 
+/* ---- detector boxes meet the acoustic map: what does a detected object sound like, which box is the talker of a track slot ----
+ * The camera half of the device path ends in bf_nms_device's boxes, the acoustic half in bf_das_device's maps and the offsets of
+ * bf_peaks_device / bf_track_sources_device; the reference relates the two in PC/sensorfusion/decider.py (focus_beam, :70-88: a
+ * detection box steers the listening beam).  This call is that relation on the device: for every box the part of the map it covers
+ * (its FOOTPRINT) and the loudest direction in it as a table offset bf_miso_device takes, and for every source the box it lies in.
+ * focus_beam's own arithmetic is not reproduced: it maps the box centre linearly to an angle and indexes the grid as if it spanned
+ * +-90 degrees (main.pyx:498-515), while the grid spans VIEW_ANGLE and is linear in tan(angle), so it does not point where the box is
+ * drawn.  The footprint here is the nearest-cell inverse of the display path the library reproduces: direction (x, y) is painted at
+ * small-image pixel [MAX_RES_Y-1-y][MAX_RES_X-1-x] (bf_heatmap_colorize_device), and the overlay stretches that image over the frame
+ * with half-pixel centres (cv2.resize INTER_LINEAR, bf_heatmap_overlay_device).
+ *
+ * d_power   : HIP device pointer, float32 [frames][image_stride]; the first rows*cols entries of a frame are the map in the library's
+ *             order d = x*cols + y, as bf_peaks_device reads it.
+ * d_boxes   : HIP device pointer, float32 [frames][max_boxes][6] = x1, y1, x2, y2, score, cls, coordinates in pixels of the
+ *             img_w x img_h frame the heat-map was overlaid on: what bf_nms_device writes.
+ * d_box_counts : HIP device pointer, int32 [frames], or NULL.  When given, rows at or beyond clamp(count, 0, max_boxes) are not boxes;
+ *             NULL: all rows are candidates.
+ * conf      : a row is a BOX iff it is inside the count and score >= conf (a NaN score is not a box).  The decider uses 0.5.
+ * d_src_offsets : HIP device pointer, int32 [frames][n_src], or NULL with n_src == 0: offsets as bf_peaks_device or
+ *             bf_track_sources_device write them.  An entry is a SOURCE iff it is >= 0, a multiple of offset_per_dir, and
+ *             d < rows*cols (the tracker's rule); its cell is (d / cols, d % cols).
+ *
+ * Footprint of a box.  float32, every operation rounded once and none contracted, then integers.  Horizontally:
+ *     ua = ceilf(x1 - 0.5f);  ub = floorf(x2 - 0.5f)            the display columns whose centres lie inside the box
+ *     ua = fmaxf(ua, 0);      ub = fminf(ub, (float)(img_w - 1))
+ *     the axis is EMPTY if x1 or x2 is NaN or !(ua <= ub), decided in float before any conversion; the conversion to int then
+ *     clamps to img_w - 1 (which matters only where (float)(img_w - 1) rounds up, above 2^24 pixels)
+ *     c(u) = ((2u + 1) * rows) / (2 * img_w)                    64-bit integer division: the small-image column under display column u
+ *     xa = rows-1 - c(ub);    xb = rows-1 - c(ua)
+ * and the same with y1, y2, img_h, cols and r(v) = ((2v + 1) * cols) / (2 * img_h) for ya, yb.  The footprint is the cells
+ * [xa, xb] x [ya, yb]; a box with an empty axis has none.
+ *
+ * d_peak_offsets : int32 [frames][max_boxes]: of the FINITE cells of the footprint the first in bf_peaks_device's order (value
+ *             descending, flat index ascending, -0.0f == 0.0f), as d * offset_per_dir; -1 when the row is not a box, the box has no
+ *             footprint, or no cell of it is finite.  bf_miso_device turns -1 into status 1 and a NaN beam.
+ * d_peak_power : float32 [frames][max_boxes], or NULL: that cell's power; 0.0f wherever the offset is -1.
+ * d_center_offsets : int32 [frames][max_boxes], or NULL: the cell under the box's midpoint (focus_beam's analogue):
+ *             um = floorf((x1 + x2) * 0.5f), valid iff 0 <= um <= (float)(img_w - 1); vm likewise from y1, y2, img_h; the offset is
+ *             ((rows-1 - c(um)) * cols + (cols-1 - r(vm))) * offset_per_dir; -1 for a row that is not a box or an invalid midpoint.
+ * d_rects   : int32 [frames][max_boxes][4], or NULL: xa, xb, ya, yb; four -1 for a row that is not a box or an empty footprint.
+ * d_src_box : int32 [frames][n_src]; required when n_src > 0, ignored when n_src == 0: the lowest row index of a box whose footprint
+ *             contains the source's cell -- bf_nms_device's rows come in descending score order, so that is the best-scored box --,
+ *             -1 when there is none or the entry is not a source.  Two sources may share a box.
+ * d_counts  : int32 [frames][3], or NULL: boxes, boxes with a peak offset >= 0, sources with a box.
+ * Every entry of every given output is written by every call.
+ *
+ * The result does not depend on which internal form reads the map (staged into LDS once per workgroup up to BF_FUSE_STAGE_MAX =
+ * 15360 directions, 60 KiB, through L2 above that), on how a frame's rows are split over workgroups (32 rows each) or on the order
+ * workgroups run in.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: one launch for the boxes, and one more of one wave per frame when
+ *             n_src > 0 or d_counts is given; no allocation, no synchronisation, no workspace; graph-capturable from the first call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_power, d_boxes or d_peak_offsets null; frames, rows,
+ * cols, offset_per_dir, max_boxes, img_w or img_h < 1; rows*cols not fitting an int or exceeding image_stride;
+ * (rows*cols - 1) * offset_per_dir > INT_MAX; conf not finite; n_src < 0 or > BF_FUSE_MAX_SOURCES; n_src > 0 with d_src_offsets or
+ * d_src_box null; no GPU.  All arguments are checked before device bring-up. */
+#define BF_FUSE_MAX_SOURCES 64
+#define BF_FUSE_STAGE_MAX 15360
+int bf_fuse_boxes_device(const float *d_power, int frames, int image_stride, int rows, int cols, int offset_per_dir,
+                         const float *d_boxes, const int *d_box_counts, int max_boxes, int img_w, int img_h, float conf,
+                         const int *d_src_offsets, int n_src,
+                         int *d_peak_offsets, float *d_peak_power, int *d_center_offsets, int *d_rects,
+                         int *d_src_box, int *d_counts, void *stream);
+
 /* ---- continuous-stream mode of the device path (BF_PAD, BF_LERP): delays read the previous window ----
  * Every other entry point treats a window as if the world began at its first sample: a microphone delayed by p samples gives
  * nothing to the first p outputs (out[p + i] += s[i], zero prefix), as the reference does.  That is the first item of the reference

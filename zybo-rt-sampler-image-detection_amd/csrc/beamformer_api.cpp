@@ -1313,6 +1313,43 @@ int bf_track_sources_device(const int* d_offsets, int frames, int k, int rows, i
                                            d_track_offsets, d_track_ids, d_track_pos, d_match, d_counts, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
 }
 
+int bf_fuse_boxes_device(const float* d_power, int frames, int image_stride, int rows, int cols, int offset_per_dir, const float* d_boxes,
+                         const int* d_box_counts, int max_boxes, int img_w, int img_h, float conf, const int* d_src_offsets, int n_src, int* d_peak_offsets,
+                         float* d_peak_power, int* d_center_offsets, int* d_rects, int* d_src_box, int* d_counts, void* stream)
+{
+    static const char* who = "bf_fuse_boxes_device";
+    static_assert(BF_FUSE_MAX_SOURCES == bf::kFuseMaxSources, "the header's limit is the kernel's");
+    static_assert(BF_FUSE_STAGE_MAX == bf::kFuseStageMax, "the header's bound is the kernel's");
+    std::lock_guard<std::mutex> lock(S().mu);
+    sizes_from_env_once();
+    if (!d_power) { set_error("%s: d_power is null", who); return -1; }
+    if (!d_boxes) { set_error("%s: d_boxes is null", who); return -1; }
+    if (!d_peak_offsets) { set_error("%s: d_peak_offsets is null", who); return -1; }
+    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
+    if (rows < 1) { set_error("%s: rows = %d < 1", who, rows); return -1; }
+    if (cols < 1) { set_error("%s: cols = %d < 1", who, cols); return -1; }
+    if (offset_per_dir < 1) { set_error("%s: offset_per_dir = %d < 1", who, offset_per_dir); return -1; }
+    if (max_boxes < 1) { set_error("%s: max_boxes = %d < 1", who, max_boxes); return -1; }
+    if (img_w < 1) { set_error("%s: img_w = %d < 1", who, img_w); return -1; }
+    if (img_h < 1) { set_error("%s: img_h = %d < 1", who, img_h); return -1; }
+    const long long D = (long long)rows * cols;
+    if (D > (long long)std::numeric_limits<int>::max()) { set_error("%s: rows * cols = %lld does not fit an int", who, D); return -1; }
+    if (D > image_stride) { set_error("%s: image_stride = %d < rows * cols = %lld", who, image_stride, D); return -1; }
+    if ((D - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
+        set_error("%s: (rows * cols - 1) * offset_per_dir = %lld does not fit an int offset", who, (D - 1) * offset_per_dir);
+        return -1;
+    }
+    if (!std::isfinite(conf)) { set_error("%s: conf = %g is not finite", who, (double)conf); return -1; }
+    if (n_src < 0) { set_error("%s: n_src = %d < 0", who, n_src); return -1; }
+    if (n_src > BF_FUSE_MAX_SOURCES) { set_error("%s: n_src = %d > %d", who, n_src, BF_FUSE_MAX_SOURCES); return -1; }
+    if (n_src > 0 && !d_src_offsets) { set_error("%s: d_src_offsets is null with n_src = %d", who, n_src); return -1; }
+    if (n_src > 0 && !d_src_box) { set_error("%s: d_src_box is null with n_src = %d", who, n_src); return -1; }
+    if (!ensure_device()) return -1;
+    return HIP_OK(bf::launch_fuse_boxes(d_power, frames, image_stride, rows, cols, offset_per_dir, d_boxes, d_box_counts, max_boxes, img_w, img_h, conf,
+                                        d_src_offsets, n_src, d_peak_offsets, d_peak_power, d_center_offsets, d_rects, d_src_box, d_counts,
+                                        reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

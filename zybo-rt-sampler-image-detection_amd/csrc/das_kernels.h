@@ -148,6 +148,15 @@ constexpr int kTrackMaxSlots = 64;
 hipError_t launch_track_sources(const int* d_offsets, int frames, int k, int rows, int cols, int offset_per_dir, int slots, float gate2, int max_miss,
                                 int min_hits, float q, float r, int* d_state, int* d_track_offsets, int* d_track_ids, float* d_track_pos, int* d_match,
                                 int* d_counts, hipStream_t stream);
+// bf_fuse_boxes_device: every detector box's footprint on the map -> its loudest cell, its centre cell and its rect; every source's
+// best-scored box.  Maps of at most kFuseStageMax directions (60 KiB of LDS, two workgroups to a CU) are staged, larger ones read
+// through L2.  One launch for the boxes, a second of one wave per frame when n_src > 0 or d_counts is given; n_src at most
+// kFuseMaxSources; no workspace.
+constexpr int kFuseMaxSources = 64;
+constexpr int kFuseStageMax = 15360;
+hipError_t launch_fuse_boxes(const float* d_power, int frames, int image_stride, int rows, int cols, int offset_per_dir, const float* d_boxes,
+                             const int* d_box_counts, int max_boxes, int img_w, int img_h, float conf, const int* d_src_offsets, int n_src,
+                             int* d_peak_offsets, float* d_peak_power, int* d_center_offsets, int* d_rects, int* d_src_box, int* d_counts, hipStream_t stream);
 
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdint>
 #include <stdint.h>
+#include "das_kernels.h"
 
 namespace bf {
 
@@ -905,6 +906,197 @@ hipError_t launch_track_sources(const int* d_offsets, int frames, int k, int row
     if (k < 1 || k > 64 || slots < 1 || slots > 64) return hipErrorInvalidValue;   // one wave: a lane per slot and per column (das_kernels.h: kTrackMaxSlots)
     hipLaunchKernelGGL(track_sources_kernel, dim3(1), dim3(64), 0, stream, d_offsets, frames, k, rows, cols, offset_per_dir, slots, gate2, max_miss, min_hits,
                        q, r, d_state, d_track_offsets, d_track_ids, d_track_pos, d_match, d_counts);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- bf_fuse_boxes_device: detector boxes meet the acoustic map
+//
+// A box's footprint is the nearest-cell inverse of the display path (colourise's flip, then the half-pixel upscale of the overlay):
+// integer arithmetic after four float32 roundings, see include/beamformer_hip.h.  Two kernels on the stream:
+//   fuse_boxes_kernel   : one workgroup of four waves per (frame, kFuseBoxesPerGroup rows).  A wave takes rows in a strided loop, its
+//                         lanes stride over the footprint's cells, and the first cell in bf_peaks_device's order is the maximum of
+//                         peak_key over the wave.  Maps of at most kFuseStageMax directions are staged into LDS once per workgroup
+//                         (a group without a box skips that), larger ones are read through L2: the same bits either way.
+//   fuse_sources_kernel : one wave per frame, only when sources or counts are asked for.  Lane l of a 64-row chunk holds row l's
+//                         rect, lane s holds source s; a ballot per source over the chunk gives the lowest row that contains it, and
+//                         chunks go in ascending order.  counts[1] reads the peak offsets the first kernel wrote (stream order).
+// Every output entry has one writer and every reduction is a maximum or a sum of integers: nothing depends on the split of rows
+// over workgroups or on the order they run in.  No atomics, no workspace.
+namespace {
+
+constexpr int kFuseBoxesPerGroup = 32;
+
+struct FuseGrid { int rows, cols, img_w, img_h; };
+
+// (int)u for a float u in [0, (float)(n - 1)], clamped to n - 1: (float)(n - 1) rounds up above 2^24
+__device__ __forceinline__ int fuse_pixel(float u, int n) { return min((int)fminf(u, 2147483520.0f), n - 1); }
+
+// small-image index of display pixel u: ((2u + 1) * cells) / (2 * img), in [0, cells - 1] for u in [0, img - 1]
+__device__ __forceinline__ int fuse_cell(int u, int cells, int img) { return (int)(((2ll * u + 1) * cells) / (2ll * img)); }
+
+// the grid range [lo, hi] of the display pixels whose centres lie in [a, b]; false: none
+__device__ __forceinline__ bool fuse_axis(float a, float b, int img, int cells, int& lo, int& hi)
+{
+    if (a != a || b != b) return false;
+    float ua = ceilf(a - 0.5f), ub = floorf(b - 0.5f);
+    ua = fmaxf(ua, 0.0f);
+    ub = fminf(ub, (float)(img - 1));
+    if (!(ua <= ub)) return false;
+    lo = cells - 1 - fuse_cell(fuse_pixel(ub, img), cells, img);
+    hi = cells - 1 - fuse_cell(fuse_pixel(ua, img), cells, img);
+    return true;
+}
+
+// the grid index of the display pixel under the midpoint of [a, b]; -1: the midpoint is outside the frame (or NaN)
+__device__ __forceinline__ int fuse_mid(float a, float b, int img, int cells)
+{
+    const float um = floorf((a + b) * 0.5f);
+    if (!(um >= 0.0f && um <= (float)(img - 1))) return -1;
+    return cells - 1 - fuse_cell(fuse_pixel(um, img), cells, img);
+}
+
+__device__ __forceinline__ bool fuse_is_box(const float* __restrict__ row, int b, int nb, float conf) { return b < nb && row[4] >= conf; }
+
+__device__ __forceinline__ int fuse_box_count(const int* __restrict__ box_counts, int f, int max_boxes)
+{
+    return box_counts ? min(max(box_counts[f], 0), max_boxes) : max_boxes;
+}
+
+template <bool kStaged>
+__global__ void __launch_bounds__(256) fuse_boxes_kernel(const float* __restrict__ power, int image_stride, FuseGrid g, int offset_per_dir,
+                                                         const float* __restrict__ boxes, const int* __restrict__ box_counts, int max_boxes, int groups,
+                                                         float conf, int* __restrict__ peak_offsets, float* __restrict__ peak_power,
+                                                         int* __restrict__ center_offsets, int* __restrict__ rects)
+{
+    extern __shared__ float fuse_lds[];
+    __shared__ int any_box;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f = blockIdx.x / groups, b0 = (blockIdx.x - f * groups) * kFuseBoxesPerGroup;
+    const int b1 = min(b0 + kFuseBoxesPerGroup, max_boxes);
+    const int nb = fuse_box_count(box_counts, f, max_boxes);
+    const float* img = power + (size_t)f * image_stride;
+    const float* frame_boxes = boxes + (size_t)f * max_boxes * 6;
+    const float* cells = img;
+    if (kStaged) {
+        if (tid == 0) any_box = 0;
+        __syncthreads();
+        if (b0 + tid < b1 && fuse_is_box(frame_boxes + (size_t)(b0 + tid) * 6, b0 + tid, nb, conf)) any_box = 1;
+        __syncthreads();
+        if (any_box) {                           // uniform
+            const int D = g.rows * g.cols;
+            for (int i = tid; i < D; i += 256) fuse_lds[i] = img[i];
+        }
+        __syncthreads();
+        cells = fuse_lds;
+    }
+    for (int b = b0 + wave; b < b1; b += 4) {    // everything but the cell loop is uniform over the wave
+        const float* row = frame_boxes + (size_t)b * 6;
+        const bool is_box = fuse_is_box(row, b, nb, conf);
+        int xa = -1, xb = -1, ya = -1, yb = -1, center = -1;
+        PeakKey key = 0;
+        if (is_box) {
+            const float x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
+            const int cx = fuse_mid(x1, x2, g.img_w, g.rows), cy = fuse_mid(y1, y2, g.img_h, g.cols);
+            if (cx >= 0 && cy >= 0) center = (cx * g.cols + cy) * offset_per_dir;
+            const bool hx = fuse_axis(x1, x2, g.img_w, g.rows, xa, xb), hy = fuse_axis(y1, y2, g.img_h, g.cols, ya, yb);
+            if (hx && hy) {
+                // cell i of the footprint, row-major: (xa + i / w, ya + i % w); a lane steps by 64 cells without dividing again
+                const int w = yb - ya + 1, n = (xb - xa + 1) * w;
+                const int sx = 64 / w, sy = 64 - sx * w;
+                int x = lane / w, y = lane - x * w;
+                for (int i = lane; i < n; i += 64) {
+                    const int d = (xa + x) * g.cols + ya + y;
+                    const PeakKey k = peak_key(peak_code(cells[d]), d);
+                    key = k > key ? k : key;
+                    x += sx;
+                    y += sy;
+                    if (y >= w) { y -= w; x += 1; }
+                }
+                for (int off = 32; off > 0; off >>= 1) {
+                    const PeakKey o = __shfl_xor(key, off, 64);
+                    key = o > key ? o : key;
+                }
+            } else {
+                xa = xb = ya = yb = -1;
+            }
+        }
+        if (lane == 0) {
+            const size_t slot = (size_t)f * max_boxes + b;
+            peak_write(key, slot, img, offset_per_dir, peak_offsets, peak_power);
+            if (center_offsets) center_offsets[slot] = center;
+            if (rects) { rects[slot * 4 + 0] = xa; rects[slot * 4 + 1] = xb; rects[slot * 4 + 2] = ya; rects[slot * 4 + 3] = yb; }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64) fuse_sources_kernel(FuseGrid g, int offset_per_dir, const float* __restrict__ boxes, const int* __restrict__ box_counts,
+                                                        int max_boxes, float conf, const int* __restrict__ src_offsets, int n_src,
+                                                        const int* __restrict__ peak_offsets, int* __restrict__ src_box, int* __restrict__ counts)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int nb = fuse_box_count(box_counts, f, max_boxes);
+    const float* frame_boxes = boxes + (size_t)f * max_boxes * 6;
+    int sx = -1, sy = -1;                        // a lane without a source is inside no rect
+    if (lane < n_src) {
+        const int o = src_offsets[(size_t)f * n_src + lane];
+        if (o >= 0) {
+            const int d = o / offset_per_dir;
+            if (d * offset_per_dir == o && d < g.rows * g.cols) { sx = d / g.cols; sy = d - sx * g.cols; }
+        }
+    }
+    int best = -1, n_boxes = 0, n_peaks = 0;
+    for (int base = 0; base < nb; base += 64) {
+        const int b = base + lane;
+        const float* row = frame_boxes + (size_t)b * 6;
+        const bool is_box = b < nb && fuse_is_box(row, b, nb, conf);
+        int xa = 0, xb = -1, ya = 0, yb = -1;
+        bool has = false;
+        if (is_box) {
+            n_boxes += 1;
+            n_peaks += peak_offsets[(size_t)f * max_boxes + b] >= 0;
+            const bool hx = fuse_axis(row[0], row[2], g.img_w, g.rows, xa, xb), hy = fuse_axis(row[1], row[3], g.img_h, g.cols, ya, yb);
+            has = hx && hy;
+        }
+        if (!__any(has)) continue;
+        for (int s = 0; s < n_src; ++s) {
+            const int X = __shfl(sx, s, 64), Y = __shfl(sy, s, 64);
+            const unsigned long long in = __ballot(has && xa <= X && X <= xb && ya <= Y && Y <= yb);
+            if (in && lane == s && best < 0) best = base + __ffsll((long long)in) - 1;
+        }
+    }
+    if (lane < n_src) src_box[(size_t)f * n_src + lane] = best;
+    if (counts) {
+        for (int off = 32; off > 0; off >>= 1) {
+            n_boxes += __shfl_xor(n_boxes, off, 64);
+            n_peaks += __shfl_xor(n_peaks, off, 64);
+        }
+        const int with_box = __popcll(__ballot(best >= 0));
+        if (lane < 3) counts[(size_t)f * 3 + lane] = lane == 0 ? n_boxes : lane == 1 ? n_peaks : with_box;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_fuse_boxes(const float* d_power, int frames, int image_stride, int rows, int cols, int offset_per_dir, const float* d_boxes,
+                             const int* d_box_counts, int max_boxes, int img_w, int img_h, float conf, const int* d_src_offsets, int n_src,
+                             int* d_peak_offsets, float* d_peak_power, int* d_center_offsets, int* d_rects, int* d_src_box, int* d_counts, hipStream_t stream)
+{
+    if (n_src < 0 || n_src > kFuseMaxSources) return hipErrorInvalidValue;     // one wave: a lane per source
+    const long long D = (long long)rows * cols;
+    const long long groups = ((long long)max_boxes + kFuseBoxesPerGroup - 1) / kFuseBoxesPerGroup;
+    if (frames * groups > 0x7fffffffLL) return hipErrorInvalidValue;
+    const FuseGrid g{rows, cols, img_w, img_h};
+    const dim3 grid((unsigned)(frames * groups));
+    if (D <= kFuseStageMax)
+        hipLaunchKernelGGL(fuse_boxes_kernel<true>, grid, dim3(256), (size_t)D * sizeof(float), stream, d_power, image_stride, g, offset_per_dir, d_boxes,
+                           d_box_counts, max_boxes, (int)groups, conf, d_peak_offsets, d_peak_power, d_center_offsets, d_rects);
+    else
+        hipLaunchKernelGGL(fuse_boxes_kernel<false>, grid, dim3(256), 0, stream, d_power, image_stride, g, offset_per_dir, d_boxes, d_box_counts, max_boxes,
+                           (int)groups, conf, d_peak_offsets, d_peak_power, d_center_offsets, d_rects);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || (n_src == 0 && !d_counts)) return e;
+    hipLaunchKernelGGL(fuse_sources_kernel, dim3(frames), dim3(64), 0, stream, g, offset_per_dir, d_boxes, d_box_counts, max_boxes, conf, d_src_offsets, n_src,
+                       d_peak_offsets, d_src_box, d_counts);
     return hipGetLastError();
 }
 

@@ -59,3 +59,8 @@ class FusedPipeline:
         int32 [B, 4]; d_camera holds one frame per window, B = ingest.n_frames(T)."""
         d_windows, status = ingest.frames(d_packets)
         return self.step(d_windows, d_camera, conf_thres) + (status,)
+
+    def focus(self, power, boxes, counts, fusion, sources=None):
+        """step's power maps, boxes and counts -> fusion.focus (a fuse.SensorFusion) at this pipeline's frame size: per box the
+        loudest direction under it as a table offset for listen(), per source of `sources` the box it lies in."""
+        return fusion.focus(power, boxes, counts, sources=sources, image_size=(self.size, self.size))
