@@ -5,14 +5,15 @@
 // file only validates, copies and enqueues.  There is no CPU compute path: when no GPU is usable every entry
 // point reports an error and poisons its output with NaN.
 #include <hip/hip_runtime.h>
-#include <chrono>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <mutex>
 #include <string>
@@ -98,6 +99,18 @@ struct TableSet {
     DigestSlot digests[kDigestSlots];
     unsigned long long digest_clock = 0;
     void invalidate_digests() { for (auto& d : digests) d.key = DigestKey{}; }   // (buffers stay allocated; keys never match again)
+    // What every loader ends with, once its uploads have succeeded: new table values, so any digest built from the old ones is stale.
+    void commit(int n, int mx, int cl = 0)
+    {
+        loaded = true; entries = n; max_whole = mx; clamped = cl;
+        invalidate_digests();
+    }
+    bf::DeviceTables device() const
+    {
+        bf::DeviceTables d;
+        d.whole = whole.p; d.frac = frac.p; d.taps = taps.p; d.max_whole = max_whole;
+        return d;
+    }
     void drop()
     {
         loaded = false; entries = 0; max_whole = 0; clamped = 0;
@@ -118,9 +131,12 @@ struct State {
     hipStream_t stream = nullptr;
     TableSet tab[SLOT_COUNT];
     std::vector<int> pad2_host;          // load_coefficients_pad2: per-mic delays (pad_and_sum.c:153-157)
+    TableSet pad2_row;                   // miso_pad2: those delays for the call's microphones, a private one-row table in slot order
+    TableSet delay_tab;                  // the single-signal helpers: a one-entry table (run_delay_host)
     // scratch for the host-pointer entry points
-    DevBuf<float> d_frame, d_image, d_out, d_init, d_one_taps, d_one_frac;
-    DevBuf<int32_t> d_mics, d_one_whole;
+    DevBuf<float> d_frame, d_image, d_out, d_init;
+    DevBuf<int32_t> d_mics;
+    DevBuf<unsigned char> d_packets;     // bf_ingest: the caller's datagrams, staged
     DevBuf<unsigned long long> d_counter;  // digest build: direction steps that change the delay
     PinnedBuf h_frame, h_image;          // host-pointer mimo_*: pinned staging of the frame in / the image out
     DevBuf<float> fd_work;               // partial planes of the bin-reducing GEMMs (bf::fd_workspace_floats)
@@ -169,6 +185,103 @@ void poison(float* out, size_t n)
         if (e__ != hipSuccess) { set_error("%s -> %s", #expr, hipGetErrorString(e__)); return false; } \
         return true;                                                                          \
     }())
+// ... as an entry point's return value.  The call stays spelled at the call site: the message names what failed.
+#define HIP_RC(expr) (HIP_OK(expr) ? 0 : -1)
+
+hipStream_t as_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+
+// ---- the checks the entry points share.  Each names the entry point (`who`) in its message, sets the error and returns false.
+struct NamedPtr { const void* p; const char* name; };
+bool need_ptrs(const char* who, std::initializer_list<NamedPtr> ptrs)   // refuses the first null one, in the order given
+{
+    for (const NamedPtr& a : ptrs)
+        if (!a.p) { set_error("%s: %s is null", who, a.name); return false; }
+    return true;
+}
+
+bool need_min(const char* who, const char* name, int v, int lo)
+{
+    if (v < lo) { set_error("%s: %s = %d < %d", who, name, v, lo); return false; }
+    return true;
+}
+
+bool need_max(const char* who, const char* name, int v, int hi)
+{
+    if (v > hi) { set_error("%s: %s = %d > %d", who, name, v, hi); return false; }
+    return true;
+}
+
+// (a bound that has a name of its own: a stride under N_SAMPLES, say)
+bool need_min(const char* who, const char* name, int v, const char* bound, int lo)
+{
+    if (v < lo) { set_error("%s: %s = %d < %s = %d", who, name, v, bound, lo); return false; }
+    return true;
+}
+
+enum Finite { FINITE, FINITE_GE0, FINITE_GT0 };
+bool need_finite(const char* who, const char* name, float v, Finite range = FINITE)
+{
+    static const char* wording[] = {"is not finite", "is not finite and >= 0", "is not finite and > 0"};
+    if (!std::isfinite(v) || (range == FINITE_GE0 && v < 0.0f) || (range == FINITE_GT0 && !(v > 0.0f))) {
+        set_error("%s: %s = %g %s", who, name, (double)v, wording[range]);
+        return false;
+    }
+    return true;
+}
+
+// Every entry of the adaptive array names a row of the caller's frames.
+bool need_rows(const char* who, const int* adaptive_array, int n, int m_total)
+{
+    for (int i = 0; i < n; ++i)
+        if (adaptive_array[i] < 0 || adaptive_array[i] >= m_total) {
+            set_error("%s: adaptive_array[%d] = %d is not a row of frames with m_total = %d rows", who, i, adaptive_array[i], m_total);
+            return false;
+        }
+    return true;
+}
+
+// The geometry of a rows x cols map, in two parts because the entry points check other arguments in between: the three sizes ...
+bool need_map_dims(const char* who, int rows, int cols, int offset_per_dir)
+{
+    return need_min(who, "rows", rows, 1) && need_min(who, "cols", cols, 1) && need_min(who, "offset_per_dir", offset_per_dir, 1);
+}
+
+// ... and a map of `count` directions (named `what` in the messages: "rows * cols", "n_dirs") whose flat table offsets d * offset_per_dir are
+// ints, and which fits the image stride where the call has one (null: no such clause).
+bool need_map(const char* who, const char* what, long long count, int offset_per_dir, const int* image_stride)
+{
+    const long long int_max = std::numeric_limits<int>::max();
+    if (count > int_max) { set_error("%s: %s = %lld does not fit an int", who, what, count); return false; }
+    if (image_stride && count > *image_stride) { set_error("%s: image_stride = %d < %s = %lld", who, *image_stride, what, count); return false; }
+    if ((count - 1) * offset_per_dir > int_max) {
+        set_error("%s: (%s - 1) * offset_per_dir = %lld does not fit an int offset", who, what, (count - 1) * offset_per_dir);
+        return false;
+    }
+    return true;
+}
+
+// The shard [dir_begin, dir_end) of n_dirs directions, and room for it in every image.
+bool need_dir_range(const char* who, int dir_begin, int dir_end, int n_dirs, int image_stride)
+{
+    if (dir_begin < 0 || dir_end > n_dirs || dir_begin >= dir_end) { set_error("%s: bad direction range [%d,%d) of %d", who, dir_begin, dir_end, n_dirs); return false; }
+    if (image_stride < dir_end - dir_begin) { set_error("%s: image_stride %d < %d directions", who, image_stride, dir_end - dir_begin); return false; }
+    return true;
+}
+
+// Calls that exist for BF_PAD and BF_LERP only; `reason` says why the other algorithms are refused (`with_number` adds the algo's value).
+bool need_pad_or_lerp(const char* who, int algo, bool with_number, const char* reason)
+{
+    if (algo == bf::ALGO_PAD || algo == bf::ALGO_LERP) return true;
+    if (algo == bf::ALGO_HYBRID || algo == bf::ALGO_FIR_NAIVE || algo == bf::ALGO_FIR_VEC) {
+        static const char* name[] = {"BF_PAD", "BF_LERP", "BF_HYBRID", "BF_FIR_NAIVE", "BF_FIR_VEC"};
+        char number[16] = "";
+        if (with_number) snprintf(number, sizeof(number), " (%d)", algo);
+        set_error("%s: algo %s%s %s", who, name[algo], number, reason);
+    } else {
+        set_error("%s: unknown algo %d", who, algo);
+    }
+    return false;
+}
 
 // The host-pointer calls (one 64 KB frame in, one 40 KB map out) end in a wait for the stream.  hipStreamSynchronize may block or yield, depending on the
 // scheduling policy the runtime picks for the box (CPU count, other devices): the same call measured 58 us on one box and 206 us on another.  A call this
@@ -242,6 +355,13 @@ void sizes_from_env_once()
     s.sizes_from_env_done = true;
     if (const char* p = getenv("BF_CONFIG")) (void)configure_from_json(p);
 }
+
+// How an entry point that reads the sizes begins: the process lock for the length of the call, then $BF_CONFIG on the first one.
+struct Entered {
+    State& s = S();
+    std::lock_guard<std::mutex> lock{s.mu};
+    Entered() { sizes_from_env_once(); }
+};
 
 // Lazy, per-process HIP bring-up (never at library load: callers fork first).
 bool ensure_device()
@@ -330,7 +450,7 @@ bool describe(int algo, int slot, int n, bf::DasLaunch* L)
         return false;
     }
     L->algo = algo;
-    L->tab.whole = t.whole.p; L->tab.frac = t.frac.p; L->tab.taps = t.taps.p; L->tab.max_whole = t.max_whole;
+    L->tab = t.device();
     L->n_mics = n; L->n_samples = s.sz.n_samples; L->n_taps = s.sz.n_taps; L->n_dirs = D;
     L->dir_begin = 0; L->dir_end = D; L->image_stride = D; L->image_origin = 0; L->frames = 1;
     L->mics = s.d_mics.p;
@@ -342,6 +462,20 @@ bool plan_or_error(const bf::DasLaunch& L, bf::DasPlan* plan)
     const char* why = "";
     if (bf::plan_das(L, S().n_cus, plan, &why) != 0) { set_error("unsupported shape: %s", why); return false; }
     return true;
+}
+
+// One beam of one frame: the launch every MISO path plans with (the batched and the stream calls raise L->frames afterwards), so
+// that all of them reach the kernel instantiation the host-pointer miso_* call reaches.  The adaptive array is already uploaded.
+bool plan_one_beam(int algo, const TableSet& t, int n, int m_total, const float* d_signals, bf::DasLaunch* L, bf::DasPlan* plan)
+{
+    State& s = S();
+    *L = bf::DasLaunch{};
+    L->algo = algo;
+    L->tab = t.device();
+    L->n_mics = n; L->m_total = m_total; L->n_samples = s.sz.n_samples; L->n_taps = s.sz.n_taps; L->n_dirs = 1;
+    L->dir_begin = 0; L->dir_end = 1; L->image_stride = 1; L->image_origin = 0; L->frames = 1;
+    L->signals = d_signals; L->images = nullptr; L->mics = s.d_mics.p;
+    return plan_or_error(*L, plan);
 }
 
 // Shifted-copies layout with scalar tables: make sure the table set carries a digest built for this plan.
@@ -402,9 +536,8 @@ bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t
 // mimo_* with host pointers: one frame in, one image out (PC/src/algorithms/pad_and_sum.c:100-143 and twins).
 void run_mimo_host(int algo, int slot, const float* signals, float* image, const int* adaptive, int n)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
+    State& s = in.s;
     const size_t D = (size_t)s.sz.dirs();
     if (!signals || !image || !adaptive) { set_error("null argument"); poison(image, image ? D : 0); return; }
     bool ok = ensure_device();
@@ -451,23 +584,15 @@ void run_miso_host(int algo, const TableSet& t, const char* loader, bool fir, co
             set_error("offset %lld + n %d exceeds the %d loaded coefficients", row_offset, n, t.entries);
             ok = false;
         }
-        if (ok) {
-            L.algo = algo;
-            L.tab.whole = t.whole.p; L.tab.frac = t.frac.p; L.tab.taps = t.taps.p; L.tab.max_whole = t.max_whole;
-            L.n_mics = n; L.n_samples = s.sz.n_samples; L.n_taps = s.sz.n_taps; L.n_dirs = 1;
-            L.dir_begin = 0; L.dir_end = 1; L.image_stride = 1; L.image_origin = 0; L.frames = 1;
-        }
     }
     if (ok) {
         const size_t rows = (size_t)max_row + 1;
-        L.m_total = (int)rows;
         ok = HIP_OK(s.d_frame.reserve(rows * N)) && HIP_OK(s.d_out.reserve(N));
         ok = ok && HIP_OK(hipMemcpyAsync(s.d_frame.p, signals, rows * N * sizeof(float), hipMemcpyHostToDevice, s.stream));
         if (ok && init) {
             ok = HIP_OK(s.d_init.reserve(N)) && HIP_OK(hipMemcpyAsync(s.d_init.p, init, N * sizeof(float), hipMemcpyHostToDevice, s.stream));
         }
-        L.signals = s.d_frame.p; L.images = nullptr; L.mics = s.d_mics.p;
-        ok = ok && plan_or_error(L, &plan);
+        ok = ok && plan_one_beam(algo, t, n, (int)rows, s.d_frame.p, &L, &plan);
         ok = ok && HIP_OK(bf::launch_miso(L, plan, row_offset, init ? s.d_init.p : nullptr, s.d_out.p, s.stream));
         ok = ok && HIP_OK(hipMemcpyAsync(out, s.d_out.p, N * sizeof(float), hipMemcpyDeviceToHost, s.stream));
         ok = ok && HIP_OK(sync_short(s.stream));
@@ -479,9 +604,8 @@ void run_miso_host(int algo, const TableSet& t, const char* loader, bool fir, co
 // one-mic, one-entry-table MISO launch with `out` as the initial accumulator.
 void run_delay_host(int algo, const float* signal, float* out, bool accumulate, int whole, float h, const float* taps)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
+    State& s = in.s;
     const size_t N = (size_t)s.sz.n_samples;
     if (!signal || !out) { set_error("null argument"); poison(out, out ? N : 0); return; }
     bool ok = ensure_device();
@@ -491,22 +615,18 @@ void run_delay_host(int algo, const float* signal, float* out, bool accumulate, 
     const int zero = 0;
     int max_row = 0;
     ok = ok && upload_mics(&zero, 1, &max_row);
+    TableSet& t = s.delay_tab;
     if (ok) {
-        const int T = s.sz.n_taps;
         const int w = std::min(whole, s.sz.n_samples);
-        ok = upload(s.d_one_whole, &w, 1) && upload(s.d_one_frac, &h, 1);
-        if (ok && taps) ok = upload(s.d_one_taps, taps, (size_t)T);
-        L.algo = algo;
-        L.tab.whole = s.d_one_whole.p; L.tab.frac = s.d_one_frac.p; L.tab.taps = s.d_one_taps.p; L.tab.max_whole = w;
-        L.n_mics = 1; L.m_total = 1; L.n_samples = s.sz.n_samples; L.n_taps = T; L.n_dirs = 1;
-        L.dir_begin = 0; L.dir_end = 1; L.image_stride = 1; L.image_origin = 0; L.frames = 1;
+        ok = upload(t.whole, &w, 1) && upload(t.frac, &h, 1);
+        if (ok && taps) ok = upload(t.taps, taps, (size_t)s.sz.n_taps);
+        t.max_whole = w;
     }
     if (ok) {
         ok = HIP_OK(s.d_frame.reserve(N)) && HIP_OK(s.d_out.reserve(N)) && HIP_OK(s.d_init.reserve(N));
         ok = ok && HIP_OK(hipMemcpyAsync(s.d_frame.p, signal, N * sizeof(float), hipMemcpyHostToDevice, s.stream));
         if (ok && accumulate) ok = HIP_OK(hipMemcpyAsync(s.d_init.p, out, N * sizeof(float), hipMemcpyHostToDevice, s.stream));
-        L.signals = s.d_frame.p; L.mics = s.d_mics.p;
-        ok = ok && plan_or_error(L, &plan);
+        ok = ok && plan_one_beam(algo, t, 1, 1, s.d_frame.p, &L, &plan);
         ok = ok && HIP_OK(bf::launch_miso(L, plan, 0, accumulate ? s.d_init.p : nullptr, s.d_out.p, s.stream));
         ok = ok && HIP_OK(hipMemcpyAsync(out, s.d_out.p, N * sizeof(float), hipMemcpyDeviceToHost, s.stream));
         ok = ok && HIP_OK(sync_short(s.stream));
@@ -540,8 +660,7 @@ bool load_whole_only(int slot, const int* whole, int n, const char* who)
     int mx = 0, cl = 0;
     if (!sanitize_whole(w, s.sz.n_samples, &mx, who, &cl)) return false;
     if (!upload(t.whole, w.data(), w.size())) return false;
-    t.loaded = true; t.entries = n; t.max_whole = mx; t.clamped = cl;
-    t.invalidate_digests();   // new table values: any digest built from the old ones is stale
+    t.commit(n, mx, cl);
     return true;
 }
 
@@ -601,17 +720,16 @@ int bf_configure_from_json(const char* path)
 
 void bf_get_config(int out[5])
 {
-    std::lock_guard<std::mutex> lock(S().mu);
-    sizes_from_env_once();
-    const Sizes& z = S().sz;
+    Entered in;
+    const Sizes& z = in.s.sz;
     out[0] = z.n_microphones; out[1] = z.n_samples; out[2] = z.res_x; out[3] = z.res_y; out[4] = z.n_taps;
 }
 
 const char* bf_last_error(void) { return S().err.c_str(); }
 void bf_clear_error(void) { S().err.clear(); }
 
-// Which kernel family the last delay-and-sum launch used: 0 strided, (1 retired), 2 shifted copies / sweep, 3 shifted copies /
-// direction-outer (table without structure), 4 shifted copies / 8-tap FIR; -1 before the first launch.  For tests and tuning.
+// Which kernel family the last delay-and-sum launch used, -1 before the first one (the values are listed at its declaration in
+// include/beamformer_hip.h).  For tests and tuning.
 int bf_last_das_variant(void) { return S().last_variant; }
 int bf_read_phase_stamps(unsigned long long* out16, int clear)
 {
@@ -670,11 +788,10 @@ void miso_pad2(float* signals, float* out, int* adaptive_array, int n, int offse
         row[(size_t)m] = s.pad2_host[(size_t)mic];
     }
     if (!ensure_device()) { poison(out, N); return; }
-    static TableSet one;  // a private one-row table in slot order
     int mx = 0;
-    if (!sanitize_whole(row, s.sz.n_samples, &mx, "miso_pad2") || !upload(one.whole, row.data(), row.size())) { poison(out, N); return; }
-    one.loaded = true; one.entries = n; one.max_whole = mx;
-    run_miso_host(bf::ALGO_PAD, one, "load_coefficients_pad2", false, signals, out, adaptive_array, n, 0, nullptr);
+    if (!sanitize_whole(row, s.sz.n_samples, &mx, "miso_pad2") || !upload(s.pad2_row.whole, row.data(), row.size())) { poison(out, N); return; }
+    s.pad2_row.commit(n, mx);
+    run_miso_host(bf::ALGO_PAD, s.pad2_row, "load_coefficients_pad2", false, signals, out, adaptive_array, n, 0, nullptr);
 }
 
 void pad_delay(float* signal, float* out, int pos_pad) { run_delay_host(bf::ALGO_PAD, signal, out, true, pos_pad, 0.f, nullptr); }
@@ -700,8 +817,7 @@ void load_coefficients_lerp(float* delays, int n)
     int mx = 0, cl = 0;
     if (!sanitize_whole(w, s.sz.n_samples, &mx, "load_coefficients_lerp", &cl)) return;
     if (!upload(t.whole, w.data(), w.size()) || !upload(t.frac, h.data(), h.size())) return;
-    t.loaded = true; t.entries = n; t.max_whole = mx; t.clamped = cl;
-    t.invalidate_digests();   // new table values: any digest built from the old ones is stale
+    t.commit(n, mx, cl);
 }
 void unload_coefficients_lerp(void) { std::lock_guard<std::mutex> lock(S().mu); S().tab[SLOT_LERP].drop(); }
 
@@ -731,7 +847,7 @@ int bf_get_pad_table(int* whole, int n)
     const TableSet& t = s.tab[SLOT_PAD];
     if (!whole) { set_error("bf_get_pad_table: whole is null"); return -1; }
     if (!t.loaded || n != t.entries) { set_error("bf_get_pad_table: %d requested, %d loaded", n, t.loaded ? t.entries : 0); return -1; }
-    return HIP_OK(hipMemcpy(whole, t.whole.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost)) ? 0 : -1;
+    return HIP_RC(hipMemcpy(whole, t.whole.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
 }
 
 // ---------------------------------------------------------------- convolve (full FIR)
@@ -744,8 +860,7 @@ void load_coefficients_convolve(float* h, int n)
     if (!ensure_device()) return;
     TableSet& t = s.tab[SLOT_FIR];
     if (!upload(t.taps, h, (size_t)n)) return;
-    t.loaded = true; t.entries = n; t.max_whole = 0;
-    t.invalidate_digests();   // new table values: any digest built from the old ones is stale
+    t.commit(n, 0);
 }
 void unload_coefficients_convolve(void) { std::lock_guard<std::mutex> lock(S().mu); S().tab[SLOT_FIR].drop(); }
 
@@ -791,8 +906,7 @@ void load_coefficients_convolve_hybrid(float* delays, int n)
     int mx = 0;
     if (!sanitize_whole(w, s.sz.n_samples, &mx, "load_coefficients_convolve_hybrid")) return;
     if (!upload(t.whole, w.data(), w.size()) || !upload(t.taps, taps.data(), taps.size())) return;
-    t.loaded = true; t.entries = n; t.max_whole = mx;
-    t.invalidate_digests();   // new table values: any digest built from the old ones is stale
+    t.commit(n, mx);
 }
 void unload_coefficients_convolve_hybrid(void) { std::lock_guard<std::mutex> lock(S().mu); S().tab[SLOT_HYBRID].drop(); }
 
@@ -819,12 +933,10 @@ int bf_get_hybrid_tables(int* whole, float* taps, int n)
 
 void bf_publish_frame(const float* signals)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
-    const size_t n = (size_t)s.sz.n_microphones * s.sz.n_samples;
+    Entered in;
+    const size_t n = (size_t)in.s.sz.n_microphones * in.s.sz.n_samples;
     if (!signals) { set_error("bf_publish_frame: null frame"); return; }
-    s.published.assign(signals, signals + n);
+    in.s.published.assign(signals, signals + n);
 }
 
 // PC/src/api.c:835-856 zeroes the rows of the 122 microphones that are dead on the authors' arrays (get_data; bf_default_disabled_mics).
@@ -858,15 +970,22 @@ void get_data(float* signals)
     if (signals) (void)copy_published(signals, true);
 }
 
+// The published frame as the api.h calls take it: get_data's copy, with the dead-microphone mask or (mimo_truncated) without.
+// Empty after a refusal.
+static std::vector<float> published_frame(bool mask_dead)
+{
+    std::vector<float> frame((size_t)S().sz.n_microphones * S().sz.n_samples);
+    if (!copy_published(frame.data(), mask_dead)) frame.clear();
+    return frame;
+}
+
 static void shim(int algo, int slot, float* image, int* adaptive_array, int n, bool mask_dead)
 {
     std::vector<float> frame;
     {
-        State& s = S();
-        std::lock_guard<std::mutex> lock(s.mu);
-        sizes_from_env_once();
-        frame.resize((size_t)s.sz.n_microphones * s.sz.n_samples);
-        if (!copy_published(frame.data(), mask_dead)) { poison(image, (size_t)s.sz.dirs()); return; }
+        Entered in;
+        frame = published_frame(mask_dead);
+        if (frame.empty()) { poison(image, (size_t)in.s.sz.dirs()); return; }
     }
     run_mimo_host(algo, slot, frame.data(), image, adaptive_array, n);
 }
@@ -882,12 +1001,10 @@ void mimo_truncated(float* image, int* adaptive_array, int n) { shim(bf::ALGO_PA
 
 void miso_steer_listen(float* out, int* adaptive_array, int n, int steer_offset)
 {
-    std::vector<float> frame;
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
-    frame.resize((size_t)s.sz.n_microphones * s.sz.n_samples);
-    if (!copy_published(frame.data(), true)) { poison(out, (size_t)s.sz.n_samples); return; }
+    Entered in;
+    State& s = in.s;
+    std::vector<float> frame = published_frame(true);
+    if (frame.empty()) { poison(out, (size_t)s.sz.n_samples); return; }
     run_miso_host(bf::ALGO_PAD, s.tab[SLOT_PAD], loader_name(SLOT_PAD), false, frame.data(), out, adaptive_array, n, steer_offset, nullptr);
 }
 
@@ -952,15 +1069,13 @@ int bf_get_steer(int* n_out)
 int bf_miso_listen_block(float* out, float mic_gain)
 {
     // miso_loop's body (api.c:505-531): get_data; miso_pad(signals, out, adaptive_array, n, steer_offset); out[i] /= n; out[i] *= MIC_GAIN
-    std::vector<float> frame;
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
+    State& s = in.s;
     const size_t N = (size_t)s.sz.n_samples;
     if (!out) { set_error("bf_miso_listen_block: null output"); return -1; }
     if (s.listen_mics.empty()) { set_error("bf_miso_listen_block: load_miso / load_pa has not been called"); poison(out, N); return -1; }
-    frame.resize((size_t)s.sz.n_microphones * N);
-    if (!copy_published(frame.data(), true)) { poison(out, N); return -1; }
+    std::vector<float> frame = published_frame(true);
+    if (frame.empty()) { poison(out, N); return -1; }
     const std::string before = s.err;
     s.err.clear();
     std::vector<int> mics = s.listen_mics;     // run_miso_host uploads from a stable copy
@@ -980,9 +1095,7 @@ int bf_miso_listen_block(float* out, float mic_gain)
 int bf_das_device(int algo, const float* d_signals, int m_total, float* d_images, int image_stride, int frames,
                   const int* adaptive_array, int n, int dir_begin, int dir_end, void* stream)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
     const int slot = slot_of(algo);
     if (slot < 0) { set_error("bf_das_device: unknown algo %d", algo); return -1; }
     if (!d_signals || !d_images || !adaptive_array || frames < 1) { set_error("bf_das_device: null argument or frames < 1"); return -1; }
@@ -992,87 +1105,51 @@ int bf_das_device(int algo, const float* d_signals, int m_total, float* d_images
     if (max_row >= m_total) { set_error("bf_das_device: adaptive_array names row %d but frames have %d rows", max_row, m_total); return -1; }
     bf::DasLaunch L{};
     if (!describe(algo, slot, n, &L)) return -1;
-    if (dir_begin < 0 || dir_end > L.n_dirs || dir_begin >= dir_end) { set_error("bf_das_device: bad direction range [%d,%d) of %d", dir_begin, dir_end, L.n_dirs); return -1; }
-    if (image_stride < dir_end - dir_begin) { set_error("bf_das_device: image_stride %d < %d directions", image_stride, dir_end - dir_begin); return -1; }
+    if (!need_dir_range("bf_das_device", dir_begin, dir_end, L.n_dirs, image_stride)) return -1;
     L.signals = d_signals; L.images = d_images; L.m_total = m_total; L.frames = frames;
     L.dir_begin = dir_begin; L.dir_end = dir_end; L.image_stride = image_stride; L.image_origin = dir_begin;
     bf::DasPlan plan{};
     if (!plan_or_error(L, &plan)) return -1;
-    if (!ensure_digest(s.tab[slot], L, plan, reinterpret_cast<hipStream_t>(stream))) return -1;
-    return HIP_OK(bf::launch_das(L, plan, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    if (!ensure_digest(in.s.tab[slot], L, plan, as_stream(stream))) return -1;
+    return HIP_RC(bf::launch_das(L, plan, as_stream(stream)));
 }
 
 int bf_miso_device(int algo, const float* d_signals, int m_total, int frames, const int* adaptive_array, int n, const int* d_offsets, int beams,
                    float mic_gain, float* d_out, int out_stride, int* d_status, void* stream)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
-    const int N = s.sz.n_samples;
+    static const char* who = "bf_miso_device";
+    Entered in;
     if (algo == bf::ALGO_FIR_NAIVE) { set_error("bf_miso_device: algo BF_FIR_NAIVE has no MISO form in the reference"); return -1; }
     const int slot = slot_of(algo);
     if (slot < 0) { set_error("bf_miso_device: unknown algo %d", algo); return -1; }
-    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"},
-                                                               {d_out, "d_out"}};
-    for (const auto& a : ptrs)
-        if (!a.p) { set_error("bf_miso_device: %s is null", a.name); return -1; }
-    if (frames < 1) { set_error("bf_miso_device: frames = %d < 1", frames); return -1; }
-    if (beams < 1) { set_error("bf_miso_device: beams = %d < 1", beams); return -1; }
-    if (n < 1) { set_error("bf_miso_device: n = %d < 1", n); return -1; }
-    if (out_stride < N) { set_error("bf_miso_device: out_stride = %d < N_SAMPLES = %d", out_stride, N); return -1; }
-    for (int i = 0; i < n; ++i)
-        if (adaptive_array[i] < 0 || adaptive_array[i] >= m_total) {
-            set_error("bf_miso_device: adaptive_array[%d] = %d is not a row of frames with m_total = %d rows", i, adaptive_array[i], m_total);
-            return -1;
-        }
-    if (!std::isfinite(mic_gain)) { set_error("bf_miso_device: mic_gain = %g is not finite", (double)mic_gain); return -1; }
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"}, {d_out, "d_out"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "beams", beams, 1) || !need_min(who, "n", n, 1)) return -1;
+    if (!need_min(who, "out_stride", out_stride, "N_SAMPLES", in.s.sz.n_samples)) return -1;
+    if (!need_rows(who, adaptive_array, n, m_total) || !need_finite(who, "mic_gain", mic_gain)) return -1;
     if (!ensure_device()) return -1;
-    const TableSet& t = s.tab[slot];
+    const TableSet& t = in.s.tab[slot];
     if (!t.loaded) { set_error("bf_miso_device: %s has not been called", loader_name(slot)); return -1; }
     int max_row = 0;
     if (!upload_mics(adaptive_array, n, &max_row)) return -1;
-    // planned as run_miso_host plans one beam of one frame
     bf::DasLaunch L{};
-    L.algo = algo;
-    L.tab.whole = t.whole.p; L.tab.frac = t.frac.p; L.tab.taps = t.taps.p; L.tab.max_whole = t.max_whole;
-    L.n_mics = n; L.m_total = m_total; L.n_samples = N; L.n_taps = s.sz.n_taps; L.n_dirs = 1;
-    L.dir_begin = 0; L.dir_end = 1; L.image_stride = 1; L.image_origin = 0; L.frames = 1;
-    L.signals = d_signals; L.images = nullptr; L.mics = s.d_mics.p;
     bf::DasPlan plan{};
-    if (!plan_or_error(L, &plan)) return -1;
+    if (!plan_one_beam(algo, t, n, m_total, d_signals, &L, &plan)) return -1;
     L.frames = frames;
-    return HIP_OK(bf::launch_miso_batch(L, plan, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status,
-                                        reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_miso_batch(L, plan, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status, as_stream(stream)));
 }
 
 int bf_remove_sources_device(int algo, const float* d_signals, int m_total, int frames, const int* adaptive_array, int n, const int* d_offsets,
                              int beams, const float* d_beams, int beam_stride, float gain, float* d_residual, int* d_status, void* stream)
 {
     static const char* who = "bf_remove_sources_device";
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
+    State& s = in.s;
     const int N = s.sz.n_samples;
-    if (algo == bf::ALGO_HYBRID || algo == bf::ALGO_FIR_NAIVE || algo == bf::ALGO_FIR_VEC) {
-        static const char* name[] = {"", "", "BF_HYBRID", "BF_FIR_NAIVE", "BF_FIR_VEC"};
-        set_error("%s: algo %s (%d) has no adjoint here (the subtraction exists for BF_PAD and BF_LERP)", who, name[algo], algo);
+    if (!need_pad_or_lerp(who, algo, true, "has no adjoint here (the subtraction exists for BF_PAD and BF_LERP)")) return -1;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"}, {d_beams, "d_beams"}, {d_residual, "d_residual"}}))
         return -1;
-    }
-    if (algo != bf::ALGO_PAD && algo != bf::ALGO_LERP) { set_error("%s: unknown algo %d", who, algo); return -1; }
-    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"},
-                                                               {d_beams, "d_beams"}, {d_residual, "d_residual"}};
-    for (const auto& a : ptrs)
-        if (!a.p) { set_error("%s: %s is null", who, a.name); return -1; }
-    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
-    if (beams < 1) { set_error("%s: beams = %d < 1", who, beams); return -1; }
-    if (beams > BF_REMOVE_MAX_BEAMS) { set_error("%s: beams = %d > %d", who, beams, BF_REMOVE_MAX_BEAMS); return -1; }
-    if (n < 1) { set_error("%s: n = %d < 1", who, n); return -1; }
-    if (beam_stride < N) { set_error("%s: beam_stride = %d < N_SAMPLES = %d", who, beam_stride, N); return -1; }
-    for (int i = 0; i < n; ++i)
-        if (adaptive_array[i] < 0 || adaptive_array[i] >= m_total) {
-            set_error("%s: adaptive_array[%d] = %d is not a row of frames with m_total = %d rows", who, i, adaptive_array[i], m_total);
-            return -1;
-        }
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "beams", beams, 1) || !need_max(who, "beams", beams, BF_REMOVE_MAX_BEAMS)) return -1;
+    if (!need_min(who, "n", n, 1) || !need_min(who, "beam_stride", beam_stride, "N_SAMPLES", N) || !need_rows(who, adaptive_array, n, m_total)) return -1;
     {
         std::vector<int> sorted(adaptive_array, adaptive_array + n);
         std::sort(sorted.begin(), sorted.end());
@@ -1082,7 +1159,7 @@ int bf_remove_sources_device(int algo, const float* d_signals, int m_total, int 
             return -1;
         }
     }
-    if (!std::isfinite(gain)) { set_error("%s: gain = %g is not finite", who, (double)gain); return -1; }
+    if (!need_finite(who, "gain", gain)) return -1;
     if (!ensure_device()) return -1;
     const int slot = slot_of(algo);
     const TableSet& t = s.tab[slot];
@@ -1097,12 +1174,10 @@ int bf_remove_sources_device(int algo, const float* d_signals, int m_total, int 
         if (!upload(s.d_row_slot, row_slot.data(), row_slot.size())) return -1;
         s.row_slot_host = row_slot;
     }
-    bf::DeviceTables tab;
-    tab.whole = t.whole.p; tab.frac = t.frac.p; tab.max_whole = t.max_whole;
     const float c = gain / (float)n;
     static_assert(BF_REMOVE_MAX_BEAMS == bf::kRemoveMaxBeams, "the header's limit is the kernel's");
-    return HIP_OK(bf::launch_remove_sources(algo, d_signals, d_residual, m_total, frames, N, n, s.d_row_slot.p, tab, t.entries, d_offsets, beams, d_beams,
-                                            beam_stride, c, d_status, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_remove_sources(algo, d_signals, d_residual, m_total, frames, N, n, s.d_row_slot.p, t.device(), t.entries, d_offsets, beams, d_beams,
+                                            beam_stride, c, d_status, as_stream(stream)));
 }
 
 // ---------------------------------------------------------------- continuous-stream mode (pad / lerp)
@@ -1111,22 +1186,10 @@ int bf_remove_sources_device(int algo, const float* d_signals, int m_total, int 
 static bool stream_args_ok(const char* who, int algo, int m_total, int frames, int hop, const int* adaptive_array, int n)
 {
     const int N = S().sz.n_samples;
-    if (algo == bf::ALGO_HYBRID || algo == bf::ALGO_FIR_NAIVE || algo == bf::ALGO_FIR_VEC) {
-        static const char* name[] = {"", "", "BF_HYBRID", "BF_FIR_NAIVE", "BF_FIR_VEC"};
-        set_error("%s: algo %s reads ahead of the window's end, which a causal stream cannot supply (continuous mode: BF_PAD, BF_LERP)", who, name[algo]);
-        return false;
-    }
-    if (algo != bf::ALGO_PAD && algo != bf::ALGO_LERP) { set_error("%s: unknown algo %d", who, algo); return false; }
-    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return false; }
-    if (hop < 1) { set_error("%s: hop = %d < 1", who, hop); return false; }
+    if (!need_pad_or_lerp(who, algo, false, "reads ahead of the window's end, which a causal stream cannot supply (continuous mode: BF_PAD, BF_LERP)")) return false;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "hop", hop, 1)) return false;
     if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return false; }
-    if (n < 1) { set_error("%s: n = %d < 1", who, n); return false; }
-    for (int i = 0; i < n; ++i)
-        if (adaptive_array[i] < 0 || adaptive_array[i] >= m_total) {
-            set_error("%s: adaptive_array[%d] = %d is not a row of frames with m_total = %d rows", who, i, adaptive_array[i], m_total);
-            return false;
-        }
-    return true;
+    return need_min(who, "n", n, 1) && need_rows(who, adaptive_array, n, m_total);
 }
 
 // The loaded table's side of the contract: H <= hop, and no entry that the loader had to clamp.
@@ -1159,52 +1222,33 @@ int bf_miso_stream_device(int algo, const float* d_signals, int m_total, int fra
                           const int* d_offsets, int beams, float mic_gain, float* d_out, int out_stride, int* d_status, void* stream)
 {
     static const char* who = "bf_miso_stream_device";
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
-    const int N = s.sz.n_samples;
-    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"},
-                                                               {d_out, "d_out"}};
-    for (const auto& a : ptrs)
-        if (!a.p) { set_error("%s: %s is null", who, a.name); return -1; }
+    Entered in;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"}, {d_out, "d_out"}})) return -1;
     if (!stream_args_ok(who, algo, m_total, frames, hop, adaptive_array, n)) return -1;
-    if (beams < 1) { set_error("%s: beams = %d < 1", who, beams); return -1; }
-    if (out_stride < N) { set_error("%s: out_stride = %d < N_SAMPLES = %d", who, out_stride, N); return -1; }
-    if (!std::isfinite(mic_gain)) { set_error("%s: mic_gain = %g is not finite", who, (double)mic_gain); return -1; }
+    if (!need_min(who, "beams", beams, 1) || !need_min(who, "out_stride", out_stride, "N_SAMPLES", in.s.sz.n_samples)) return -1;
+    if (!need_finite(who, "mic_gain", mic_gain)) return -1;
     if (!ensure_device()) return -1;
     const int slot = slot_of(algo);
-    const TableSet& t = s.tab[slot];
+    const TableSet& t = in.s.tab[slot];
     if (!stream_table_ok(who, algo, t, slot, hop)) return -1;
     int max_row = 0;
     if (!upload_mics(adaptive_array, n, &max_row)) return -1;
-    // planned as bf_miso_device plans: one beam of one frame
     bf::DasLaunch L{};
-    L.algo = algo;
-    L.tab.whole = t.whole.p; L.tab.frac = t.frac.p; L.tab.taps = t.taps.p; L.tab.max_whole = t.max_whole;
-    L.n_mics = n; L.m_total = m_total; L.n_samples = N; L.n_taps = s.sz.n_taps; L.n_dirs = 1;
-    L.dir_begin = 0; L.dir_end = 1; L.image_stride = 1; L.image_origin = 0; L.frames = 1;
-    L.signals = d_signals; L.images = nullptr; L.mics = s.d_mics.p;
     bf::DasPlan plan{};
-    if (!plan_or_error(L, &plan)) return -1;
+    if (!plan_one_beam(algo, t, n, m_total, d_signals, &L, &plan)) return -1;
     L.frames = frames;
-    return HIP_OK(bf::launch_stream_beams(L, plan, d_prev, hop, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status,
-                                          reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_stream_beams(L, plan, d_prev, hop, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status, as_stream(stream)));
 }
 
 int bf_das_stream_device(int algo, const float* d_signals, int m_total, float* d_images, int image_stride, int frames, int hop, const float* d_prev,
                          const int* adaptive_array, int n, int dir_begin, int dir_end, void* stream)
 {
     static const char* who = "bf_das_stream_device";
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
-    const struct { const void* p; const char* name; } ptrs[] = {{d_signals, "d_signals"}, {d_images, "d_images"}, {adaptive_array, "adaptive_array"}};
-    for (const auto& a : ptrs)
-        if (!a.p) { set_error("%s: %s is null", who, a.name); return -1; }
+    Entered in;
+    State& s = in.s;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {d_images, "d_images"}, {adaptive_array, "adaptive_array"}})) return -1;
     if (!stream_args_ok(who, algo, m_total, frames, hop, adaptive_array, n)) return -1;
-    const int D = s.sz.dirs();
-    if (dir_begin < 0 || dir_end > D || dir_begin >= dir_end) { set_error("%s: bad direction range [%d,%d) of %d", who, dir_begin, dir_end, D); return -1; }
-    if (image_stride < dir_end - dir_begin) { set_error("%s: image_stride %d < %d directions", who, image_stride, dir_end - dir_begin); return -1; }
+    if (!need_dir_range(who, dir_begin, dir_end, s.sz.dirs(), image_stride)) return -1;
     if (!ensure_device()) return -1;
     const int slot = slot_of(algo);
     if (!stream_table_ok(who, algo, s.tab[slot], slot, hop)) return -1;
@@ -1217,59 +1261,39 @@ int bf_das_stream_device(int algo, const float* d_signals, int m_total, float* d
     bf::DasPlan plan{};
     const char* why = "";
     if (bf::plan_stream_maps(L, s.n_cus, &plan, &why) != 0) { set_error("%s: unsupported shape: %s", who, why); return -1; }
-    if (!HIP_OK(bf::launch_stream_maps(L, plan, d_prev, hop, reinterpret_cast<hipStream_t>(stream)))) return -1;
+    if (!HIP_OK(bf::launch_stream_maps(L, plan, d_prev, hop, as_stream(stream)))) return -1;
     s.last_variant = 9;
     return 0;
 }
 
 int bf_peak_offsets_device(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, void* stream)
 {
-    std::lock_guard<std::mutex> lock(S().mu);
-    sizes_from_env_once();
-    if (!d_power) { set_error("bf_peak_offsets_device: d_power is null"); return -1; }
-    if (!d_offsets) { set_error("bf_peak_offsets_device: d_offsets is null"); return -1; }
-    if (frames < 1) { set_error("bf_peak_offsets_device: frames = %d < 1", frames); return -1; }
-    if (n_dirs < 1) { set_error("bf_peak_offsets_device: n_dirs = %d < 1", n_dirs); return -1; }
-    if (offset_per_dir < 1) { set_error("bf_peak_offsets_device: offset_per_dir = %d < 1", offset_per_dir); return -1; }
-    if (image_stride < n_dirs) { set_error("bf_peak_offsets_device: image_stride = %d < n_dirs = %d", image_stride, n_dirs); return -1; }
-    if ((long long)(n_dirs - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
-        set_error("bf_peak_offsets_device: (n_dirs - 1) * offset_per_dir = %lld does not fit an int offset", (long long)(n_dirs - 1) * offset_per_dir);
-        return -1;
-    }
+    static const char* who = "bf_peak_offsets_device";
+    Entered in;
+    if (!need_ptrs(who, {{d_power, "d_power"}, {d_offsets, "d_offsets"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "n_dirs", n_dirs, 1) || !need_min(who, "offset_per_dir", offset_per_dir, 1)) return -1;
+    if (!need_map(who, "n_dirs", n_dirs, offset_per_dir, &image_stride)) return -1;
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_peak_offsets(d_power, frames, image_stride, n_dirs, offset_per_dir, d_offsets, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_peak_offsets(d_power, frames, image_stride, n_dirs, offset_per_dir, d_offsets, as_stream(stream)));
 }
 
 int bf_peaks_device(const float* d_power, int frames, int image_stride, int rows, int cols, int radius, int k, float floor_rel, float floor_abs,
                     int offset_per_dir, int* d_offsets, float* d_values, int* d_counts, void* stream)
 {
     static const char* who = "bf_peaks_device";
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
-    if (!d_power) { set_error("%s: d_power is null", who); return -1; }
-    if (!d_offsets) { set_error("%s: d_offsets is null", who); return -1; }
-    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
-    if (rows < 1) { set_error("%s: rows = %d < 1", who, rows); return -1; }
-    if (cols < 1) { set_error("%s: cols = %d < 1", who, cols); return -1; }
-    if (offset_per_dir < 1) { set_error("%s: offset_per_dir = %d < 1", who, offset_per_dir); return -1; }
-    if (k < 1) { set_error("%s: k = %d < 1", who, k); return -1; }
-    if (k > BF_PEAKS_MAX_K) { set_error("%s: k = %d > %d", who, k, BF_PEAKS_MAX_K); return -1; }
-    if (radius < 0) { set_error("%s: radius = %d < 0", who, radius); return -1; }
-    const long long D = (long long)rows * cols;
-    if (D > (long long)std::numeric_limits<int>::max()) { set_error("%s: rows * cols = %lld does not fit an int", who, D); return -1; }
-    if (D > image_stride) { set_error("%s: image_stride = %d < rows * cols = %lld", who, image_stride, D); return -1; }
-    if ((D - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
-        set_error("%s: (rows * cols - 1) * offset_per_dir = %lld does not fit an int offset", who, (D - 1) * offset_per_dir);
-        return -1;
-    }
+    Entered in;
+    State& s = in.s;
+    if (!need_ptrs(who, {{d_power, "d_power"}, {d_offsets, "d_offsets"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_map_dims(who, rows, cols, offset_per_dir)) return -1;
+    if (!need_min(who, "k", k, 1) || !need_max(who, "k", k, BF_PEAKS_MAX_K) || !need_min(who, "radius", radius, 0)) return -1;
+    if (!need_map(who, "rows * cols", (long long)rows * cols, offset_per_dir, &image_stride)) return -1;
     if (!std::isfinite(floor_rel) || floor_rel < 0.0f || floor_rel > 1.0f) { set_error("%s: floor_rel = %g is not in [0, 1]", who, (double)floor_rel); return -1; }
-    if (!std::isfinite(floor_abs)) { set_error("%s: floor_abs = %g is not finite", who, (double)floor_abs); return -1; }
+    if (!need_finite(who, "floor_abs", floor_abs)) return -1;
     if (!ensure_device()) return -1;
     const size_t work = bf::peaks_workspace_words(frames, rows, cols, k);
     if (work && !HIP_OK(s.peaks_work.reserve(work))) return -1;
-    return HIP_OK(bf::launch_peaks(d_power, frames, image_stride, rows, cols, radius, k, floor_rel, floor_abs, offset_per_dir, d_offsets, d_values, d_counts,
-                                   s.peaks_work.p, s.peaks_work.cap, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_peaks(d_power, frames, image_stride, rows, cols, radius, k, floor_rel, floor_abs, offset_per_dir, d_offsets, d_values, d_counts,
+                                   s.peaks_work.p, s.peaks_work.cap, as_stream(stream)));
 }
 
 int bf_track_state_words(int slots)
@@ -1283,34 +1307,17 @@ int bf_track_sources_device(const int* d_offsets, int frames, int k, int rows, i
 {
     static const char* who = "bf_track_sources_device";
     static_assert(BF_TRACK_MAX_SLOTS == bf::kTrackMaxSlots, "the header's limit is the kernel's");
-    std::lock_guard<std::mutex> lock(S().mu);
-    sizes_from_env_once();
-    if (!d_offsets) { set_error("%s: d_offsets is null", who); return -1; }
-    if (!d_state) { set_error("%s: d_state is null", who); return -1; }
-    if (!d_track_offsets) { set_error("%s: d_track_offsets is null", who); return -1; }
-    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
-    if (k < 1) { set_error("%s: k = %d < 1", who, k); return -1; }
-    if (k > BF_PEAKS_MAX_K) { set_error("%s: k = %d > %d", who, k, BF_PEAKS_MAX_K); return -1; }
-    if (slots < 1) { set_error("%s: slots = %d < 1", who, slots); return -1; }
-    if (slots > BF_TRACK_MAX_SLOTS) { set_error("%s: slots = %d > %d", who, slots, BF_TRACK_MAX_SLOTS); return -1; }
-    if (rows < 1) { set_error("%s: rows = %d < 1", who, rows); return -1; }
-    if (cols < 1) { set_error("%s: cols = %d < 1", who, cols); return -1; }
-    if (offset_per_dir < 1) { set_error("%s: offset_per_dir = %d < 1", who, offset_per_dir); return -1; }
-    const long long D = (long long)rows * cols;
-    if (D > (long long)std::numeric_limits<int>::max()) { set_error("%s: rows * cols = %lld does not fit an int", who, D); return -1; }
-    if ((D - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
-        set_error("%s: (rows * cols - 1) * offset_per_dir = %lld does not fit an int offset", who, (D - 1) * offset_per_dir);
-        return -1;
-    }
-    if (!std::isfinite(gate) || gate < 0.0f) { set_error("%s: gate = %g is not finite and >= 0", who, (double)gate); return -1; }
-    if (max_miss < 0) { set_error("%s: max_miss = %d < 0", who, max_miss); return -1; }
-    if (min_hits < 1) { set_error("%s: min_hits = %d < 1", who, min_hits); return -1; }
-    if (!std::isfinite(q) || q < 0.0f) { set_error("%s: q = %g is not finite and >= 0", who, (double)q); return -1; }
-    if (!std::isfinite(r) || !(r > 0.0f)) { set_error("%s: r = %g is not finite and > 0", who, (double)r); return -1; }
+    Entered in;
+    if (!need_ptrs(who, {{d_offsets, "d_offsets"}, {d_state, "d_state"}, {d_track_offsets, "d_track_offsets"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "k", k, 1) || !need_max(who, "k", k, BF_PEAKS_MAX_K)) return -1;
+    if (!need_min(who, "slots", slots, 1) || !need_max(who, "slots", slots, BF_TRACK_MAX_SLOTS)) return -1;
+    if (!need_map_dims(who, rows, cols, offset_per_dir) || !need_map(who, "rows * cols", (long long)rows * cols, offset_per_dir, nullptr)) return -1;
+    if (!need_finite(who, "gate", gate, FINITE_GE0) || !need_min(who, "max_miss", max_miss, 0) || !need_min(who, "min_hits", min_hits, 1)) return -1;
+    if (!need_finite(who, "q", q, FINITE_GE0) || !need_finite(who, "r", r, FINITE_GT0)) return -1;
     if (!ensure_device()) return -1;
     const float gate2 = gate * gate;                 // one float32 multiplication, as the definition says
-    return HIP_OK(bf::launch_track_sources(d_offsets, frames, k, rows, cols, offset_per_dir, slots, gate2, max_miss, min_hits, q, r, static_cast<int*>(d_state),
-                                           d_track_offsets, d_track_ids, d_track_pos, d_match, d_counts, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_track_sources(d_offsets, frames, k, rows, cols, offset_per_dir, slots, gate2, max_miss, min_hits, q, r, static_cast<int*>(d_state),
+                                           d_track_offsets, d_track_ids, d_track_pos, d_match, d_counts, as_stream(stream)));
 }
 
 int bf_fuse_boxes_device(const float* d_power, int frames, int image_stride, int rows, int cols, int offset_per_dir, const float* d_boxes,
@@ -1320,34 +1327,17 @@ int bf_fuse_boxes_device(const float* d_power, int frames, int image_stride, int
     static const char* who = "bf_fuse_boxes_device";
     static_assert(BF_FUSE_MAX_SOURCES == bf::kFuseMaxSources, "the header's limit is the kernel's");
     static_assert(BF_FUSE_STAGE_MAX == bf::kFuseStageMax, "the header's bound is the kernel's");
-    std::lock_guard<std::mutex> lock(S().mu);
-    sizes_from_env_once();
-    if (!d_power) { set_error("%s: d_power is null", who); return -1; }
-    if (!d_boxes) { set_error("%s: d_boxes is null", who); return -1; }
-    if (!d_peak_offsets) { set_error("%s: d_peak_offsets is null", who); return -1; }
-    if (frames < 1) { set_error("%s: frames = %d < 1", who, frames); return -1; }
-    if (rows < 1) { set_error("%s: rows = %d < 1", who, rows); return -1; }
-    if (cols < 1) { set_error("%s: cols = %d < 1", who, cols); return -1; }
-    if (offset_per_dir < 1) { set_error("%s: offset_per_dir = %d < 1", who, offset_per_dir); return -1; }
-    if (max_boxes < 1) { set_error("%s: max_boxes = %d < 1", who, max_boxes); return -1; }
-    if (img_w < 1) { set_error("%s: img_w = %d < 1", who, img_w); return -1; }
-    if (img_h < 1) { set_error("%s: img_h = %d < 1", who, img_h); return -1; }
-    const long long D = (long long)rows * cols;
-    if (D > (long long)std::numeric_limits<int>::max()) { set_error("%s: rows * cols = %lld does not fit an int", who, D); return -1; }
-    if (D > image_stride) { set_error("%s: image_stride = %d < rows * cols = %lld", who, image_stride, D); return -1; }
-    if ((D - 1) * offset_per_dir > (long long)std::numeric_limits<int>::max()) {
-        set_error("%s: (rows * cols - 1) * offset_per_dir = %lld does not fit an int offset", who, (D - 1) * offset_per_dir);
-        return -1;
-    }
-    if (!std::isfinite(conf)) { set_error("%s: conf = %g is not finite", who, (double)conf); return -1; }
-    if (n_src < 0) { set_error("%s: n_src = %d < 0", who, n_src); return -1; }
-    if (n_src > BF_FUSE_MAX_SOURCES) { set_error("%s: n_src = %d > %d", who, n_src, BF_FUSE_MAX_SOURCES); return -1; }
+    Entered in;
+    if (!need_ptrs(who, {{d_power, "d_power"}, {d_boxes, "d_boxes"}, {d_peak_offsets, "d_peak_offsets"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_map_dims(who, rows, cols, offset_per_dir)) return -1;
+    if (!need_min(who, "max_boxes", max_boxes, 1) || !need_min(who, "img_w", img_w, 1) || !need_min(who, "img_h", img_h, 1)) return -1;
+    if (!need_map(who, "rows * cols", (long long)rows * cols, offset_per_dir, &image_stride)) return -1;
+    if (!need_finite(who, "conf", conf) || !need_min(who, "n_src", n_src, 0) || !need_max(who, "n_src", n_src, BF_FUSE_MAX_SOURCES)) return -1;
     if (n_src > 0 && !d_src_offsets) { set_error("%s: d_src_offsets is null with n_src = %d", who, n_src); return -1; }
     if (n_src > 0 && !d_src_box) { set_error("%s: d_src_box is null with n_src = %d", who, n_src); return -1; }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_fuse_boxes(d_power, frames, image_stride, rows, cols, offset_per_dir, d_boxes, d_box_counts, max_boxes, img_w, img_h, conf,
-                                        d_src_offsets, n_src, d_peak_offsets, d_peak_power, d_center_offsets, d_rects, d_src_box, d_counts,
-                                        reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_fuse_boxes(d_power, frames, image_stride, rows, cols, offset_per_dir, d_boxes, d_box_counts, max_boxes, img_w, img_h, conf,
+                                        d_src_offsets, n_src, d_peak_offsets, d_peak_power, d_center_offsets, d_rects, d_src_box, d_counts, as_stream(stream)));
 }
 
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
@@ -1361,31 +1351,28 @@ static int ingest_common(const void* d_packets, int n_arrays, int rows, int colu
         return -1;
     }
     const int stride = 8 + 4 * s.sz.n_microphones;   // sizeof(msg), receiver.h:51-59
-    return HIP_OK(bf::launch_ingest(d_packets, stride, 8, s.sz.n_samples, mics_out, s.sz.n_microphones, rows, columns, d_frame, stream)) ? 0 : -1;
+    return HIP_RC(bf::launch_ingest(d_packets, stride, 8, s.sz.n_samples, mics_out, s.sz.n_microphones, rows, columns, d_frame, stream));
 }
 
 int bf_ingest_device(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, void* stream)
 {
-    std::lock_guard<std::mutex> lock(S().mu);
-    sizes_from_env_once();
+    Entered in;
     if (!d_packets || !d_frame) { set_error("bf_ingest_device: null argument"); return -1; }
     if (!ensure_device()) return -1;
-    return ingest_common(d_packets, n_arrays, rows, columns, d_frame, reinterpret_cast<hipStream_t>(stream));
+    return ingest_common(d_packets, n_arrays, rows, columns, d_frame, as_stream(stream));
 }
 
 int bf_ingest(const void* packets, int n_arrays, int rows, int columns, float* frame)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
+    State& s = in.s;
     if (!packets || !frame) { set_error("bf_ingest: null argument"); return -1; }
     const size_t out_n = (size_t)std::max(0, n_arrays * rows * columns) * s.sz.n_samples;
     if (!ensure_device()) { poison(frame, out_n); return -1; }
     const size_t in_bytes = (size_t)(8 + 4 * s.sz.n_microphones) * s.sz.n_samples;
-    static DevBuf<unsigned char> d_in;
-    bool ok = HIP_OK(d_in.reserve(in_bytes)) && HIP_OK(s.d_frame.reserve(out_n ? out_n : 1));
-    ok = ok && HIP_OK(hipMemcpyAsync(d_in.p, packets, in_bytes, hipMemcpyHostToDevice, s.stream));
-    ok = ok && ingest_common(d_in.p, n_arrays, rows, columns, s.d_frame.p, s.stream) == 0;
+    bool ok = HIP_OK(s.d_packets.reserve(in_bytes)) && HIP_OK(s.d_frame.reserve(out_n ? out_n : 1));
+    ok = ok && HIP_OK(hipMemcpyAsync(s.d_packets.p, packets, in_bytes, hipMemcpyHostToDevice, s.stream));
+    ok = ok && ingest_common(s.d_packets.p, n_arrays, rows, columns, s.d_frame.p, s.stream) == 0;
     ok = ok && HIP_OK(hipMemcpyAsync(frame, s.d_frame.p, out_n * sizeof(float), hipMemcpyDeviceToHost, s.stream));
     ok = ok && HIP_OK(sync_short(s.stream));
     if (!ok) poison(frame, out_n);
@@ -1395,17 +1382,12 @@ int bf_ingest(const void* packets, int n_arrays, int rows, int columns, float* f
 int bf_ingest_stream_device(const void* d_packets, long long n_datagrams, int n_arrays, int rows, int columns, int hop, int frames, int m_total,
                             const unsigned char* d_row_mask, int protocol_ver, float* d_frames, int* d_status, void* stream)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
-    const int M = s.sz.n_microphones, N = s.sz.n_samples;
-    if (!d_packets) { set_error("bf_ingest_stream_device: d_packets is null"); return -1; }
-    if (!d_frames) { set_error("bf_ingest_stream_device: d_frames is null"); return -1; }
-    if (frames < 1) { set_error("bf_ingest_stream_device: frames = %d < 1", frames); return -1; }
-    if (hop < 1) { set_error("bf_ingest_stream_device: hop = %d < 1", hop); return -1; }
-    if (n_arrays < 1) { set_error("bf_ingest_stream_device: n_arrays = %d < 1", n_arrays); return -1; }
-    if (rows < 1) { set_error("bf_ingest_stream_device: rows = %d < 1", rows); return -1; }
-    if (columns < 1) { set_error("bf_ingest_stream_device: columns = %d < 1", columns); return -1; }
+    static const char* who = "bf_ingest_stream_device";
+    Entered in;
+    const int M = in.s.sz.n_microphones, N = in.s.sz.n_samples;
+    if (!need_ptrs(who, {{d_packets, "d_packets"}, {d_frames, "d_frames"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "hop", hop, 1)) return -1;
+    if (!need_min(who, "n_arrays", n_arrays, 1) || !need_min(who, "rows", rows, 1) || !need_min(who, "columns", columns, 1)) return -1;
     const long long mics_out = (long long)n_arrays * rows * columns;
     if (mics_out > M) { set_error("bf_ingest_stream_device: n_arrays*rows*columns = %lld > N_MICROPHONES = %d", mics_out, M); return -1; }
     if (mics_out > m_total) { set_error("bf_ingest_stream_device: n_arrays*rows*columns = %lld > m_total = %d", mics_out, m_total); return -1; }
@@ -1420,8 +1402,8 @@ int bf_ingest_stream_device(const void* d_packets, long long n_datagrams, int n_
     if (tiles > 0x7fffff00ll) { set_error("bf_ingest_stream_device: frames = %d needs %lld workgroups, more than one launch holds", frames, tiles); return -1; }
     if (!ensure_device()) return -1;
     const int stride = 8 + 4 * M;   // sizeof(msg), receiver.h:51-59
-    return HIP_OK(bf::launch_ingest_stream(d_packets, stride, N, M, (int)mics_out, rows, columns, hop, frames, m_total, d_row_mask, protocol_ver, n_arrays,
-                                           d_frames, d_status, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_ingest_stream(d_packets, stride, N, M, (int)mics_out, rows, columns, hop, frames, m_total, d_row_mask, protocol_ver, n_arrays,
+                                           d_frames, d_status, as_stream(stream)));
 }
 
 int bf_default_disabled_mics(int* out)
@@ -1437,35 +1419,28 @@ int bf_default_disabled_mics(int* out)
 int bf_heatmap_colorize_device(const float* d_power, int frames, float threshold, float amount, float exponent, unsigned char* d_small,
                                int* d_should_overlay, void* stream)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
     if (!d_power || !d_small || !d_should_overlay || frames < 1) { set_error("bf_heatmap_colorize_device: null argument or frames < 1"); return -1; }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_colorize(d_power, frames, s.sz.res_x, s.sz.res_y, threshold, amount, exponent, d_small, d_should_overlay,
-                                      reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_colorize(d_power, frames, in.s.sz.res_x, in.s.sz.res_y, threshold, amount, exponent, d_small, d_should_overlay, as_stream(stream)));
 }
 
 int bf_heatmap_overlay_device(const unsigned char* d_small, int frames, int out_w, int out_h, unsigned char* d_prev, const unsigned char* d_camera,
                               unsigned char* d_out, float w_prev, float w_new, float w_cam, float w_heat, void* stream)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
     if (!d_small || !d_prev || !d_out || frames < 1 || out_w < 1 || out_h < 1) { set_error("bf_heatmap_overlay_device: bad argument"); return -1; }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_overlay(d_small, frames, s.sz.res_x, s.sz.res_y, out_w, out_h, d_prev, d_camera, d_out, w_prev, w_new, w_cam, w_heat,
-                                     reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_overlay(d_small, frames, in.s.sz.res_x, in.s.sz.res_y, out_w, out_h, d_prev, d_camera, d_out, w_prev, w_new, w_cam, w_heat,
+                                     as_stream(stream)));
 }
 
 int bf_power_center_device(const float* d_power, int frames, float* d_centers, float* d_workspace, void* stream)
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
     if (!d_power || !d_centers || !d_workspace || frames < 1) { set_error("bf_power_center_device: bad argument"); return -1; }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_power_center(d_power, frames, s.sz.res_x, s.sz.res_y, d_centers, d_workspace, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_power_center(d_power, frames, in.s.sz.res_x, in.s.sz.res_y, d_centers, d_workspace, as_stream(stream)));
 }
 
 int bf_letterbox_bgr8_device(const unsigned char* d_frame, int h, int w, unsigned char* d_out, int out_h, int out_w, int new_h, int new_w, int top, int left, int value,
@@ -1478,30 +1453,32 @@ int bf_letterbox_bgr8_device(const unsigned char* d_frame, int h, int w, unsigne
         return -1;
     }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_letterbox(d_frame, h, w, d_out, out_h, out_w, new_h, new_w, top, left, value, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_letterbox(d_frame, h, w, d_out, out_h, out_w, new_h, new_w, top, left, value, as_stream(stream)));
 }
 
 // ---------------------------------------------------------------- frequency-domain beamformers
 
-#define FD_ENTER(cond, name)                                                     \
-    State& s = S();                                                              \
-    std::lock_guard<std::mutex> lock(s.mu);                                      \
-    sizes_from_env_once();                                                       \
-    if (!(cond)) { set_error(name ": null pointer or non-positive size"); return -1; } \
-    if (!ensure_device()) return -1;                                             \
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+// These calls (and the detector's decode and NMS below) check pointers and sizes in one expression, `args_ok`, under one refusal
+// text; then the device comes up.
+static bool sized_args_ready(const char* who, bool args_ok)
+{
+    if (!args_ok) { set_error("%s: null pointer or non-positive size", who); return false; }
+    return ensure_device();
+}
 
 int bf_fd_steering_device(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, void* stream)
 {
-    FD_ENTER(d_tau && d_freq && d_are && d_aim && n_dirs > 0 && n_mics > 0 && n_bins > 0, "bf_fd_steering_device")
-    return HIP_OK(bf::launch_fd_steering(d_tau, d_freq, n_dirs, n_mics, n_bins, d_are, d_aim, st)) ? 0 : -1;
+    Entered in;
+    if (!sized_args_ready("bf_fd_steering_device", d_tau && d_freq && d_are && d_aim && n_dirs > 0 && n_mics > 0 && n_bins > 0)) return -1;
+    return HIP_RC(bf::launch_fd_steering(d_tau, d_freq, n_dirs, n_mics, n_bins, d_are, d_aim, as_stream(stream)));
 }
 
 int bf_fd_dft_device(const float* d_frames, int m_total, int frames, const int* adaptive_array, int n, int bin_lo, int n_bins, float* d_xre_mf,
                      float* d_xim_mf, float* d_xre_fm, float* d_xim_fm, void* stream)
 {
-    FD_ENTER(d_frames && adaptive_array && d_xre_mf && d_xim_mf && d_xre_fm && d_xim_fm && frames > 0 && n > 0 && n_bins > 0 && bin_lo >= 0,
-             "bf_fd_dft_device")
+    Entered in;
+    State& s = in.s;
+    if (!sized_args_ready("bf_fd_dft_device", d_frames && adaptive_array && d_xre_mf && d_xim_mf && d_xre_fm && d_xim_fm && frames > 0 && n > 0 && n_bins > 0 && bin_lo >= 0)) return -1;
     if (bin_lo + n_bins > s.sz.n_samples / 2 + 1) { set_error("bf_fd_dft_device: bins [%d,%d) exceed N_SAMPLES/2+1 = %d", bin_lo, bin_lo + n_bins, s.sz.n_samples / 2 + 1); return -1; }
     int max_row = 0;
     if (!upload_mics(adaptive_array, n, &max_row)) return -1;
@@ -1509,48 +1486,48 @@ int bf_fd_dft_device(const float* d_frames, int m_total, int frames, const int* 
     const long long key = ((long long)s.sz.n_samples << 40) ^ ((long long)bin_lo << 20) ^ n_bins;
     if (s.fd_tw_key != key || !s.fd_tw.p) {
         if (!HIP_OK(s.fd_tw.reserve(bf::fd_twiddle_floats(s.sz.n_samples, n_bins)))) return -1;
-        if (!HIP_OK(bf::launch_fd_twiddles(s.sz.n_samples, bin_lo, n_bins, s.fd_tw.p, st))) return -1;
-        if (!HIP_OK(hipStreamSynchronize(st))) return -1;     // once per (N, bin range): see ensure_digest
+        if (!HIP_OK(bf::launch_fd_twiddles(s.sz.n_samples, bin_lo, n_bins, s.fd_tw.p, as_stream(stream)))) return -1;
+        if (!HIP_OK(hipStreamSynchronize(as_stream(stream)))) return -1;     // once per (N, bin range): see ensure_digest
         s.fd_tw_key = key;
     }
-    return HIP_OK(bf::launch_fd_dft(d_frames, s.d_mics.p, m_total, s.sz.n_samples, frames, n, bin_lo, n_bins, s.fd_tw.p, d_xre_mf, d_xim_mf, d_xre_fm, d_xim_fm,
-                                    st)) ? 0 : -1;
+    return HIP_RC(bf::launch_fd_dft(d_frames, s.d_mics.p, m_total, s.sz.n_samples, frames, n, bin_lo, n_bins, s.fd_tw.p, d_xre_mf, d_xim_mf, d_xre_fm, d_xim_fm, as_stream(stream)));
 }
 
 int bf_fd_das_power_device(const float* d_xre_mf, const float* d_xim_mf, const float* d_are, const float* d_aim, int frames, int n_mics, int n_dirs,
                            int n_bins, float* d_power, void* stream)
 {
-    FD_ENTER(d_xre_mf && d_xim_mf && d_are && d_aim && d_power && frames > 0 && n_mics > 0 && n_dirs > 0 && n_bins > 0, "bf_fd_das_power_device")
-    const size_t work = bf::fd_workspace_floats(frames, n_dirs, n_bins);
-    if (!HIP_OK(s.fd_work.reserve(work))) return -1;
-    return HIP_OK(bf::launch_fd_das_power(d_xre_mf, d_xim_mf, d_are, d_aim, frames, n_mics, n_dirs, n_bins, d_power, s.fd_work.p, s.fd_work.cap, st)) ? 0 : -1;
+    Entered in;
+    if (!sized_args_ready("bf_fd_das_power_device", d_xre_mf && d_xim_mf && d_are && d_aim && d_power && frames > 0 && n_mics > 0 && n_dirs > 0 && n_bins > 0)) return -1;
+    if (!HIP_OK(in.s.fd_work.reserve(bf::fd_workspace_floats(frames, n_dirs, n_bins)))) return -1;
+    return HIP_RC(bf::launch_fd_das_power(d_xre_mf, d_xim_mf, d_are, d_aim, frames, n_mics, n_dirs, n_bins, d_power, in.s.fd_work.p, in.s.fd_work.cap, as_stream(stream)));
 }
 
 int bf_fd_covariance_device(const float* d_xre_fm, const float* d_xim_fm, int frames, int n_mics, int n_bins, float* d_rre, float* d_rim, void* stream)
 {
-    FD_ENTER(d_xre_fm && d_xim_fm && d_rre && d_rim && frames > 0 && n_mics > 0 && n_bins > 0, "bf_fd_covariance_device")
-    return HIP_OK(bf::launch_fd_covariance(d_xre_fm, d_xim_fm, frames, n_mics, n_bins, d_rre, d_rim, st)) ? 0 : -1;
+    Entered in;
+    if (!sized_args_ready("bf_fd_covariance_device", d_xre_fm && d_xim_fm && d_rre && d_rim && frames > 0 && n_mics > 0 && n_bins > 0)) return -1;
+    return HIP_RC(bf::launch_fd_covariance(d_xre_fm, d_xim_fm, frames, n_mics, n_bins, d_rre, d_rim, as_stream(stream)));
 }
 
 int bf_fd_cholesky_inverse_device(const float* d_rre, const float* d_rim, int n_mics, int n_bins, float loading, float* d_lire_t, float* d_liim_t,
                                   int* d_status, void* stream)
 {
-    FD_ENTER(d_rre && d_rim && d_lire_t && d_liim_t && d_status && n_mics > 0 && n_bins > 0, "bf_fd_cholesky_inverse_device")
+    Entered in;
+    DevBuf<float>& work = in.s.fd_chol_work;
+    if (!sized_args_ready("bf_fd_cholesky_inverse_device", d_rre && d_rim && d_lire_t && d_liim_t && d_status && n_mics > 0 && n_bins > 0)) return -1;
     if (n_mics > 256) { set_error("bf_fd_cholesky_inverse_device: %d mics; the blocked factorisation handles at most 256", n_mics); return -1; }
-    const size_t work = bf::fd_cholesky_workspace_floats(n_mics, n_bins);
-    if (work && !HIP_OK(s.fd_chol_work.reserve(work))) return -1;
-    return HIP_OK(bf::launch_fd_cholesky_inverse(d_rre, d_rim, n_mics, n_bins, loading, d_lire_t, d_liim_t, d_status, s.fd_chol_work.p, s.fd_chol_work.cap, st))
-               ? 0 : -1;
+    if (!HIP_OK(work.reserve(bf::fd_cholesky_workspace_floats(n_mics, n_bins)))) return -1;     // (no blocks, nothing reserved: up to 128 mics)
+    return HIP_RC(bf::launch_fd_cholesky_inverse(d_rre, d_rim, n_mics, n_bins, loading, d_lire_t, d_liim_t, d_status, work.p, work.cap, as_stream(stream)));
 }
 
 int bf_fd_mvdr_power_device(const float* d_lire_t, const float* d_liim_t, const float* d_are, const float* d_aim, int n_mics, int n_dirs, int n_bins,
                             float* d_power, void* stream)
 {
-    FD_ENTER(d_lire_t && d_liim_t && d_are && d_aim && d_power && n_mics > 0 && n_dirs > 0 && n_bins > 0, "bf_fd_mvdr_power_device")
+    Entered in;
+    if (!sized_args_ready("bf_fd_mvdr_power_device", d_lire_t && d_liim_t && d_are && d_aim && d_power && n_mics > 0 && n_dirs > 0 && n_bins > 0)) return -1;
     if (n_mics > 256) { set_error("bf_fd_mvdr_power_device: %d mics; at most 256", n_mics); return -1; }
-    const size_t work = bf::fd_workspace_floats(1, n_dirs, n_bins);
-    if (!HIP_OK(s.fd_work.reserve(work))) return -1;
-    return HIP_OK(bf::launch_fd_mvdr_power(d_lire_t, d_liim_t, d_are, d_aim, n_mics, n_dirs, n_bins, d_power, s.fd_work.p, s.fd_work.cap, st)) ? 0 : -1;
+    if (!HIP_OK(in.s.fd_work.reserve(bf::fd_workspace_floats(1, n_dirs, n_bins)))) return -1;
+    return HIP_RC(bf::launch_fd_mvdr_power(d_lire_t, d_liim_t, d_are, d_aim, n_mics, n_dirs, n_bins, d_power, in.s.fd_work.p, in.s.fd_work.cap, as_stream(stream)));
 }
 
 // The 256-entry colour table of the colourise kernel (visual.py:26-49 generate_color_map("jet")), uint8 [256][3].
@@ -1569,8 +1546,10 @@ void bf_jet_lut(unsigned char* out768)
 int bf_yolo_decode_device(const void* const raw[3], const int h[3], const int w[3], const int strides[3], const float* anchors, int batch, int nc,
                           int format, float conf_thres, float* d_boxes, float* d_scores, int* d_cls, void* stream)
 {
-    FD_ENTER(raw && raw[0] && raw[1] && raw[2] && h && w && strides && anchors && d_boxes && d_scores && d_cls && batch > 0 && nc > 0, "bf_yolo_decode_device")
-    return HIP_OK(bf::launch_yolo_decode(raw, h, w, strides, anchors, batch, nc, format, conf_thres, d_boxes, d_scores, d_cls, st)) ? 0 : -1;
+    Entered in;
+    const bool args_ok = raw && raw[0] && raw[1] && raw[2] && h && w && strides && anchors && d_boxes && d_scores && d_cls && batch > 0 && nc > 0;
+    if (!sized_args_ready("bf_yolo_decode_device", args_ok)) return -1;
+    return HIP_RC(bf::launch_yolo_decode(raw, h, w, strides, anchors, batch, nc, format, conf_thres, d_boxes, d_scores, d_cls, as_stream(stream)));
 }
 
 int bf_topk_candidates_device(const float* d_scores, const float* d_boxes, const int* d_cls, int batch, int total, int k, float* d_top_scores,
@@ -1580,8 +1559,7 @@ int bf_topk_candidates_device(const float* d_scores, const float* d_boxes, const
     if (!d_scores || !d_boxes || !d_cls || !d_top_scores || !d_top_boxes || !d_top_cls || !d_counts) { set_error("bf_topk_candidates_device: null pointer"); return -1; }
     if (k < 1 || k > 1024 || batch < 1 || total < 1) { set_error("bf_topk_candidates_device: batch %d, %d boxes, k = %d (1..1024)", batch, total, k); return -1; }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_topk_candidates(d_scores, d_boxes, d_cls, batch, total, k, d_top_scores, d_top_boxes, d_top_cls, d_counts,
-                                             reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_topk_candidates(d_scores, d_boxes, d_cls, batch, total, k, d_top_scores, d_top_boxes, d_top_cls, d_counts, as_stream(stream)));
 }
 
 static int upsample_concat_checked(const char* who, int eb, const void* d_a, const void* d_b, void* d_out, int batch, int h, int w, int ca, int cb, void* stream)
@@ -1593,7 +1571,7 @@ static int upsample_concat_checked(const char* who, int eb, const void* d_a, con
         return -1;
     }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_upsample_concat(d_a, d_b, d_out, batch, h, w, ca, cb, eb, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_upsample_concat(d_a, d_b, d_out, batch, h, w, ca, cb, eb, as_stream(stream)));
 }
 int bf_upsample_concat_device(const void* d_a, const void* d_b, void* d_out, int batch, int h, int w, int ca, int cb, void* stream)
 {
@@ -1613,7 +1591,7 @@ static int sppf_pool_checked(const char* who, int eb, void* d_buf, int batch, in
         return -1;
     }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_sppf_pool(d_buf, batch, h, w, c, eb, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_sppf_pool(d_buf, batch, h, w, c, eb, as_stream(stream)));
 }
 int bf_sppf_pool_device(void* d_buf, int batch, int h, int w, int c, void* stream) { return sppf_pool_checked("bf_sppf_pool_device", 2, d_buf, batch, h, w, c, stream); }
 int bf_sppf_pool_f32_device(void* d_buf, int batch, int h, int w, int c, void* stream) { return sppf_pool_checked("bf_sppf_pool_f32_device", 4, d_buf, batch, h, w, c, stream); }
@@ -1623,7 +1601,7 @@ static int preprocess_checked(const char* who, int eb, const void* d_frames, voi
     std::lock_guard<std::mutex> lock(S().mu);
     if (!d_frames || !d_out || batch < 1 || h < 1 || w < 1 || cpad < 3) { set_error("%s: batch %d, %d x %d, %d channels", who, batch, h, w, cpad); return -1; }
     if (!ensure_device()) return -1;
-    return HIP_OK(bf::launch_preprocess_bgr8(d_frames, d_out, (long long)batch * h * w, cpad, eb, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_preprocess_bgr8(d_frames, d_out, (long long)batch * h * w, cpad, eb, as_stream(stream)));
 }
 int bf_preprocess_bgr8_device(const void* d_frames, void* d_out, int batch, int h, int w, int cpad, void* stream)
 {
@@ -1670,8 +1648,8 @@ static int conv2d_checked(const char* who, int eb, const void* d_x, const void* 
     }
     if (!ensure_device()) return -1;
     // (a plain dense source through the cat entry still takes the 1x1 path: ld1 = c selects it only when something differs -- force it with up1 / x2 / ld1)
-    return HIP_OK(bf::launch_conv2d_nhwc(eb, d_x, d_w, d_bias, d_y, batch, h, w, c, n, kh, kw, stride, pad, silu, ldy, d_res, ldr, cat ? d_x2 : nullptr,
-                                         cat ? c1 : c, cat ? ld1 : c, cat ? ld2 : 0, cat ? up1 : 0, reinterpret_cast<hipStream_t>(stream))) ? 0 : -1;
+    return HIP_RC(bf::launch_conv2d_nhwc(eb, d_x, d_w, d_bias, d_y, batch, h, w, c, n, kh, kw, stride, pad, silu, ldy, d_res, ldr, cat ? d_x2 : nullptr,
+                                         cat ? c1 : c, cat ? ld1 : c, cat ? ld2 : 0, cat ? up1 : 0, as_stream(stream)));
 }
 
 int bf_conv2d_nhwc_f16_device(const void* d_x, const void* d_w, const float* d_bias, void* d_y, int batch, int h, int w, int c, int n, int kh, int kw, int stride,
@@ -1715,18 +1693,17 @@ int bf_conv1x1_cat_nhwc_f32_device(const void* d_x1, int ld1, int c1, int up1, c
 int bf_nms_device(const float* d_boxes, const float* d_scores, const int* d_cls, const int* d_counts, int batch, int k, float iou_thres, int max_det,
                   unsigned long long* d_mask, float* d_out, int* d_out_count, void* stream)
 {
-    FD_ENTER(d_boxes && d_scores && d_cls && d_counts && d_mask && d_out && d_out_count && batch > 0 && k > 0 && max_det > 0, "bf_nms_device")
+    Entered in;
+    if (!sized_args_ready("bf_nms_device", d_boxes && d_scores && d_cls && d_counts && d_mask && d_out && d_out_count && batch > 0 && k > 0 && max_det > 0)) return -1;
     if (k > 4096) { set_error("bf_nms_device: k = %d candidates; at most 4096", k); return -1; }
-    return HIP_OK(bf::launch_nms(d_boxes, d_scores, d_cls, d_counts, batch, k, iou_thres, max_det, d_mask, d_out, d_out_count, st)) ? 0 : -1;
+    return HIP_RC(bf::launch_nms(d_boxes, d_scores, d_cls, d_counts, batch, k, iou_thres, max_det, d_mask, d_out, d_out_count, as_stream(stream)));
 }
 
 int bf_plan_das(int algo, int n, int frames, int dir_begin, int dir_end, int max_whole, int n_cus, long long out[10])
 {
-    State& s = S();
-    std::lock_guard<std::mutex> lock(s.mu);
-    sizes_from_env_once();
+    Entered in;
     bf::DasLaunch L{};
-    L.algo = algo; L.n_mics = n; L.m_total = n; L.n_samples = s.sz.n_samples; L.n_taps = s.sz.n_taps; L.n_dirs = s.sz.dirs();
+    L.algo = algo; L.n_mics = n; L.m_total = n; L.n_samples = in.s.sz.n_samples; L.n_taps = in.s.sz.n_taps; L.n_dirs = in.s.sz.dirs();
     L.dir_begin = dir_begin; L.dir_end = dir_end; L.frames = frames; L.tab.max_whole = max_whole;
     bf::DasPlan p{};
     const char* why = "";
