@@ -134,6 +134,24 @@ int bf_gpu_available(void);
  * 8-tap FIR flavours), 8 the two-frame sweep on frame-interleaved rows (batched lerp), 9 strided with the previous window's tail in
  * front of every row (bf_das_stream_device); -1 before the first launch. */
 int bf_last_das_variant(void);
+/* The digest the last delay-and-sum launch used (families 2, 3, 5, 8 of bf_last_das_variant: pad / lerp with 16 waves): *steps =
+ * direction steps inside a wave's run over which the sweep could share its reads (7 of every 8 positions, times the microphones),
+ * *changes = those of them at which the whole-sample delay changes, i.e. the sweep re-reads -- counted in the order the launch
+ * sweeps (bf_sweep_order).  Returns 0, or -1 with both set to -1 / 0 when the last launch counted nothing. */
+int bf_last_das_reloads(long long *changes, long long *steps);
+/* The order in which a batched pad / lerp launch (families 5 and 8) over directions [dir_begin, dir_end) sweeps them: order_out[s]
+ * = flat direction at position s, s in [0, dir_end - dir_begin).  A wave carries dpw (8) consecutive positions and re-reads a
+ * microphone's samples wherever its whole-sample delay changes between two of them; the images do not depend on the order.
+ * Host only: needs no GPU.  whole: int32 [n_dirs][n_mics] whole-sample delays (the pad table; floor of the lerp table).  The rule,
+ * with p[s] = row dir_begin + s, M = n_mics:
+ *   1. c[s] = number of mics with p[s+1][m] != p[s][m]
+ *   2. a new segment starts at s + 1 wherever 2 * c[s] > M
+ *   3. the first segment runs forward
+ *   4. a later segment [a, b) is reversed if fewer mics differ between the row placed last and p[b-1] than between it and p[a]
+ *   5. unless this order has strictly fewer changes inside runs of dpw positions (counted from position 0) than the identity,
+ *      the identity is returned.
+ * Returns 0, or -1 (bf_last_error) for a null pointer, a size below 1 or a range outside [0, n_dirs). */
+int bf_sweep_order(const int *whole, int n_dirs, int n_mics, int dir_begin, int dir_end, int dpw, int *order_out);
 /* Profiling builds only (hipcc -DBF_STAMPS, scripts/dev/phase_stamps.py): per-phase wave time of the batched pad / lerp kernel,
  * summed over all waves since the last clear: out16[0..7] = sweep, wait, staging, wait, wait, parking, wait, ordered power sum
  * (s_memtime ticks), out16[8] = waves counted.  All zero in the production build.  Returns 0 or -1. */

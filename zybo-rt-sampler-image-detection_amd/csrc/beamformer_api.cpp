@@ -22,6 +22,7 @@
 
 #include "../../include/beamformer_hip.h"
 #include "das_kernels.h"
+#include "sweep_order.h"
 
 namespace {
 
@@ -53,10 +54,11 @@ struct DevBuf {
 struct DigestKey {
     bool valid = false;
     int mic_chunk = 0, row_stride = 0, lead = 0, algo = 0, dpw = 0, dir_begin = 0, dir_end = 0, n_mics = 0, nf = 0;
+    bool ordered = false;   // built for a kernel that sweeps in the table's own order (bf::sweep_order) rather than in flat order
     bool operator==(const DigestKey& o) const
     {
         return valid && o.valid && mic_chunk == o.mic_chunk && row_stride == o.row_stride && lead == o.lead && algo == o.algo && dpw == o.dpw &&
-               dir_begin == o.dir_begin && dir_end == o.dir_end && n_mics == o.n_mics && nf == o.nf;
+               dir_begin == o.dir_begin && dir_end == o.dir_end && n_mics == o.n_mics && nf == o.nf && ordered == o.ordered;
     }
 };
 
@@ -93,6 +95,8 @@ struct TableSet {
         DevBuf<int32_t> buf;
         DigestKey key;            // what the digest was built for
         bool direct = false;      // ... in the [D][M] layout of the direction-outer kernel variant (table without structure)
+        long long order_off = 0;  // where the digest keeps its sweep order (0: none -- the rule gave the identity, or the kernel takes no order)
+        long long changes = -1, steps = 0;   // grouped build: direction steps that change a delay, of the steps that could share (-1: not counted)
         unsigned long long used = 0;
     };
     static constexpr int kDigestSlots = 4;
@@ -115,7 +119,7 @@ struct TableSet {
     {
         loaded = false; entries = 0; max_whole = 0; clamped = 0;
         whole.release(); frac.release(); taps.release();
-        for (auto& d : digests) { d.buf.release(); d.key = DigestKey{}; d.direct = false; d.used = 0; }
+        for (auto& d : digests) { d.buf.release(); d.key = DigestKey{}; d.direct = false; d.order_off = 0; d.changes = -1; d.steps = 0; d.used = 0; }
     }
 };
 
@@ -153,6 +157,7 @@ struct State {
     int steer_offset = 0;                // steer(): flat table offset of the listening beam (api.c:576-581)
     std::vector<int> listen_mics;        // load_pa(): microphones of the listening beam (api.c:553-567); empty before load_miso / load_pa
     int last_variant = -1;               // bf_last_das_variant
+    long long last_changes = -1, last_steps = 0;   // bf_last_das_reloads
     std::string err;
 };
 
@@ -478,14 +483,35 @@ bool plan_one_beam(int algo, const TableSet& t, int n, int m_total, const float*
     return plan_or_error(*L, plan);
 }
 
+// The sweep order of a launch (bf::sweep_order on the whole-sample rows of its direction range, fetched once), stored at d_order
+// padded to whole groups by repeating the last entry.  *stored = false when the rule gave the identity: nothing is written then.
+bool store_sweep_order(const bf::DasLaunch& L, const bf::DasPlan& plan, int32_t* d_order, bool* stored)
+{
+    const int n_pos = L.dir_end - L.dir_begin;
+    const size_t padded = ((size_t)n_pos + plan.dpw - 1) / plan.dpw * plan.dpw;
+    std::vector<int32_t> rows((size_t)n_pos * L.n_mics), order(padded);
+    if (!HIP_OK(hipMemcpy(rows.data(), L.tab.whole + (size_t)L.dir_begin * L.n_mics, rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost))) return false;
+    bf::SweepOrderStats st;
+    if (bf::sweep_order(rows.data(), L.n_mics, n_pos, L.n_mics, L.dir_begin, plan.dpw, order.data(), &st) != 0) {
+        set_error("sweep order: bad launch geometry");
+        return false;
+    }
+    *stored = !st.identity;
+    if (st.identity) return true;
+    for (size_t i = (size_t)n_pos; i < padded; ++i) order[i] = order[(size_t)n_pos - 1];
+    return HIP_OK(hipMemcpy(d_order, order.data(), padded * sizeof(int32_t), hipMemcpyHostToDevice));
+}
+
 // Shifted-copies layout with scalar tables: make sure the table set carries a digest built for this plan.
 bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t stream)
 {
     S().last_variant = plan.layout == 2 ? (plan.nf == 2 ? 7 : 4) : plan.layout;   // refined below for the digest-driven kernels
+    S().last_changes = -1; S().last_steps = 0;
     const bool plain_fir = L.algo == bf::ALGO_FIR_NAIVE || L.algo == bf::ALGO_FIR_VEC;
     if (plan.layout != 2 || (plain_fir && plan.nf != 2)) return true;   // the plain FIRs have no whole-sample table (their pair kernel wants the taps regrouped)
     // everything the digest depends on: the plan's geometry, the algorithm and (grouped layouts) the direction range
-    const DigestKey key{true, plan.mic_chunk, plan.row_stride, plan.lead, L.algo, plan.dpw, L.dir_begin, L.dir_end, L.n_mics, plan.nf};
+    const long long want_order = bf::digest_order_offset(L, plan);   // (non-zero: the plan's kernel stores by an order table)
+    const DigestKey key{true, plan.mic_chunk, plan.row_stride, plan.lead, L.algo, plan.dpw, L.dir_begin, L.dir_end, L.n_mics, plan.nf, want_order != 0};
     TableSet::DigestSlot* slot = nullptr;
     for (auto& d : t.digests)
         if (d.buf.p && d.key == key) slot = &d;
@@ -501,23 +527,31 @@ bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t
         victim->key = DigestKey{};
         if (!HIP_OK(victim->buf.reserve(bf::digest_elements(L, plan))) || !HIP_OK(s.d_counter.reserve(1))) return false;
         victim->direct = false;
+        victim->order_off = 0; victim->changes = -1; victim->steps = 0;
+        if (want_order != 0) {
+            bool stored = false;
+            if (!store_sweep_order(L, plan, victim->buf.p + want_order, &stored)) return false;
+            if (stored) victim->order_off = want_order;
+        }
         const bool plain = L.algo == bf::ALGO_PAD || L.algo == bf::ALGO_LERP;
         const bool grouped = plain || ((L.algo == bf::ALGO_HYBRID || plain_fir) && plan.nf == 2);
         if (grouped && !HIP_OK(hipMemsetAsync(s.d_counter.p, 0, sizeof(unsigned long long), stream))) return false;
-        if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, grouped ? s.d_counter.p : nullptr, false, stream))) return false;
+        if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, grouped ? s.d_counter.p : nullptr, false, victim->order_off, stream))) return false;
         // once per (table, geometry): wait, so that a later launch on ANOTHER stream cannot overtake the digest's construction
         if (!HIP_OK(hipStreamSynchronize(stream))) return false;
         if (plain && plan.waves == 16) {
-            // A table without structure (more than half of the direction steps change the delay) defeats the sweep: use the
-            // direction-outer kernel variant and its [D][M] digest instead.
+            // A table without structure (more than half of the direction steps change the delay, counted in sweep order) defeats the
+            // sweep: use the direction-outer kernel variant and its [D][M] digest instead.
             unsigned long long reloads = 0;
             if (!HIP_OK(hipMemcpy(&reloads, s.d_counter.p, sizeof(reloads), hipMemcpyDeviceToHost))) return false;
             const long long steps = bf::digest_shareable_steps(L, plan);
+            victim->changes = (long long)reloads; victim->steps = steps;
             if (steps > 0 && 2 * (long long)reloads > steps) {
                 L.tab.digest_direct = true;
                 if (!plan_or_error(L, &plan)) return false;     // that variant reads at every step: four shifted copies, its own chunk size
-                if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, nullptr, true, stream)) || !HIP_OK(hipStreamSynchronize(stream))) return false;
+                if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, nullptr, true, 0, stream)) || !HIP_OK(hipStreamSynchronize(stream))) return false;
                 victim->direct = true;
+                victim->order_off = 0;                          // (that variant walks [D][M] in flat order)
             }
         }
         victim->key = key;                                      // (the key is the sweep plan's: what the caller's planning yields next time)
@@ -529,6 +563,8 @@ bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t
     slot->used = ++t.digest_clock;
     L.tab.digest_direct = slot->direct;
     L.tab.digest = slot->buf.p;
+    L.tab.digest_order_off = slot->order_off;
+    S().last_changes = slot->changes; S().last_steps = slot->steps;
     S().last_variant = (L.algo == bf::ALGO_PAD || L.algo == bf::ALGO_LERP) ? (slot->direct ? 3 : plan.nf == 2 ? (plan.interleaved ? 8 : 5) : plan.long_rows ? 6 : 2) : plan.nf == 2 ? 7 : 4;
     return true;
 }
@@ -731,6 +767,27 @@ void bf_clear_error(void) { S().err.clear(); }
 // Which kernel family the last delay-and-sum launch used, -1 before the first one (the values are listed at its declaration in
 // include/beamformer_hip.h).  For tests and tuning.
 int bf_last_das_variant(void) { return S().last_variant; }
+
+int bf_last_das_reloads(long long* changes, long long* steps)
+{
+    if (!need_ptrs("bf_last_das_reloads", {{changes, "changes"}, {steps, "steps"}})) return -1;
+    *changes = S().last_changes; *steps = S().last_steps;
+    if (S().last_changes < 0) { set_error("bf_last_das_reloads: the last launch used no digest whose re-reads were counted"); return -1; }
+    return 0;
+}
+
+int bf_sweep_order(const int* whole, int n_dirs, int n_mics, int dir_begin, int dir_end, int dpw, int* order_out)
+{
+    if (!need_ptrs("bf_sweep_order", {{whole, "whole"}, {order_out, "order_out"}})) return -1;
+    if (n_dirs < 1 || n_mics < 1 || dpw < 1 || dir_begin < 0 || dir_end > n_dirs || dir_begin >= dir_end) {
+        set_error("bf_sweep_order: want n_dirs, n_mics, dpw >= 1 and 0 <= dir_begin < dir_end <= n_dirs (got %d, %d, %d, [%d, %d))", n_dirs, n_mics, dpw,
+                  dir_begin, dir_end);
+        return -1;
+    }
+    static_assert(sizeof(int) == sizeof(int32_t), "the C-ABI's int tables are int32");
+    return bf::sweep_order(reinterpret_cast<const int32_t*>(whole) + (size_t)dir_begin * n_mics, n_mics, dir_end - dir_begin, n_mics, dir_begin, dpw,
+                           reinterpret_cast<int32_t*>(order_out), nullptr);
+}
 int bf_read_phase_stamps(unsigned long long* out16, int clear)
 {
     std::lock_guard<std::mutex> lock(S().mu);

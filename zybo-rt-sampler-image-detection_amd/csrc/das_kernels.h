@@ -25,6 +25,7 @@ struct DeviceTables {
     bool digest_direct = false;      // digest is in the [D][M] layout: run the direction-outer (DIRECT) kernel variant (plan_das sizes the chunk for its four copies)
     const int32_t* digest = nullptr; // LDS byte offsets for the shifted-copies layout (launch_digest): grouped by the wave's directions for pad / lerp
                                      // (+ the lerp weights in the same order), [D][M] for hybrid; null when not built
+    long long digest_order_off = 0;  // grouped digest of the pad / lerp pair kernels: where its sweep order starts (4-byte elements); 0: position = direction
 };
 
 // Geometry of one launch.  Directions [dir_begin, dir_end) of every frame in [0, frames).
@@ -74,7 +75,12 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why);
 size_t digest_elements(const DasLaunch& L, const DasPlan& plan);   // 4-byte elements the digest of this launch needs (0: none)
 // `direct`: the [D][M] layout of the direction-outer kernel variant (tables without structure) instead of the grouped one;
 // d_reload_count (grouped build, optional) receives the number of direction steps whose delay differs from the previous one's.
-hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, bool direct, hipStream_t stream);
+// order_off (grouped build; 0: none): the sweep order already stored at d_digest + order_off -- int32, one entry per position of the
+// launch padded to whole groups of plan.dpw by repeating the last (digest_order_offset says where; sweep_order.h what) -- in which
+// the digest is then grouped and its re-reads counted.
+long long digest_order_offset(const DasLaunch& L, const DasPlan& plan);    // 0: the plan's kernel takes no order (all but the pad / lerp pair kernels)
+hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, bool direct, long long order_off,
+                         hipStream_t stream);
 long long digest_shareable_steps(const DasLaunch& L, const DasPlan& plan);
 
 // Enqueue on `stream`; no host synchronisation, no allocation (graph-capturable).

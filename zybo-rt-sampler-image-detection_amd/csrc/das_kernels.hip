@@ -50,6 +50,7 @@ struct KArgs {
     int wg_frames, frame_inner;   // workgroup id -> (tile, frame [pair]): see tile_and_frame()
     long long digest_h_off;   // shifted-copies pad / lerp: where the grouped lerp weights start in the digest buffer (floats)
     long long digest_t_off;   // the 8-tap FIR pair kernel: where the taps regrouped per 8 directions start in the digest buffer (floats)
+    long long digest_o_off;   // pad / lerp pair kernels: where the sweep order (flat direction of every position) starts in the digest buffer; 0 = positions are directions
 };
 
 // Workgroup id -> (direction tile, frame or frame pair).  Ids go round-robin over the 8 XCDs.
@@ -681,12 +682,13 @@ __global__ void __launch_bounds__(256) digest_kernel(const int32_t* __restrict__
 // from dir_begin, and the group's entries of one mic sit together: entry ((g * M + m) * gdirs + j) = direction
 // dir_begin + g * gdirs + j, mic m, so one s_load_dwordx8 brings the 8 directions' offsets of a mic.  The lerp weights
 // follow in the same buffer (float, same order) at `h_off`.  Directions past dir_end repeat the last one (their results
-// are never stored).
+// are never stored).  With an `order` table (sweep_order.h; one entry per position, the padded ones repeating the last) position
+// g * gdirs + j holds direction order[g * gdirs + j] instead, and the re-reads are counted in that order.
 __global__ void __launch_bounds__(256) digest_grouped_kernel(const int32_t* __restrict__ whole, const float* __restrict__ frac, int32_t* __restrict__ digest,
                                                              long long entries, long long h_off, int n_mics, int gdirs, int dir_begin, int dir_end,
                                                              int mic_chunk, int arrays, int row_stride, int lead, int bias, int ncopies,
                                                              unsigned long long* __restrict__ reload_count, int pack_guards, int scale,
-                                                             const float* __restrict__ taps, long long t_off)
+                                                             const float* __restrict__ taps, long long t_off, const int32_t* __restrict__ order)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < entries; i += (long long)gridDim.x * blockDim.x) {
         const int j = (int)(i % gdirs);
@@ -695,6 +697,7 @@ __global__ void __launch_bounds__(256) digest_grouped_kernel(const int32_t* __re
         const long long g = gm / n_mics;
         long long d = dir_begin + g * gdirs + j;
         if (d > dir_end - 1) d = dir_end - 1;
+        if (order != nullptr) d = order[g * gdirs + j];
         if (taps != nullptr) {
             // the 8 taps of (direction, mic), regrouped like the entries: [group][mic][direction of the group][8] -- the FIR sweep
             // then walks ONE pointer per wave (eight row pointers cost it 14 scalar registers it does not have)
@@ -719,7 +722,8 @@ __global__ void __launch_bounds__(256) digest_grouped_kernel(const int32_t* __re
             // how often the sweep will have to re-read: this direction's delay differs from the previous direction's
             // (directions past the end repeat the last one: never a change)
             const long long dn = dir_begin + g * gdirs + j;
-            if (dn <= dir_end - 1 && whole[(d - 1) * n_mics + mic] != whole[d * n_mics + mic]) atomicAdd(reload_count, 1ull);
+            const long long dp = order != nullptr ? (long long)order[g * gdirs + j - 1] : d - 1;
+            if (dn <= dir_end - 1 && whole[dp * n_mics + mic] != whole[d * n_mics + mic]) atomicAdd(reload_count, 1ull);
         }
     }
 }
@@ -1815,6 +1819,8 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
             const int g = wave * kWave + lane;            // parked row of this lane
             const int d = g0 + g;
             if (g < kGroup && d < tile_end && (f == 0 || two)) {
+                // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
+                const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
                 const float* row = lds + g * kPark;
                 const float4* row4 = reinterpret_cast<const float4*>(row);
                 float sum = 0.0f;
@@ -1827,7 +1833,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
                     for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
                 }
                 for (; k < N; ++k) sum += row[k];
-                (f == 0 ? img0 : img1)[d - a.image_origin] = sum / (float)N;
+                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
             }
         }
     }
@@ -2107,6 +2113,8 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
             const int g = wave * kWave + lane_o;          // parked row of this lane
             const int d = g0 + g;
             if (g < kGroup && d < tile_end && (f == 0 || two)) {
+                // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
+                const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
                 const float* row = lds + g * kPark;
                 const float4* row4 = reinterpret_cast<const float4*>(row);
                 float sum = 0.0f;
@@ -2119,7 +2127,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
                     for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
                 }
                 for (; k < N; ++k) sum += row[k];
-                (f == 0 ? img0 : img1)[d - a.image_origin] = sum / (float)N;
+                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
             }
         }
     }
@@ -3196,6 +3204,7 @@ KArgs make_args(const DasLaunch& L, const DasPlan& plan)
     a.frame_inner = plan.frame_inner;
     a.digest_h_off = (plan.layout == 2 && (L.algo == ALGO_LERP || (L.algo == ALGO_HYBRID && plan.nf == 2))) ? grouped_entries_for_args(L, plan) : 0;
     a.digest_t_off = (plan.layout == 2 && L.algo == ALGO_HYBRID && plan.nf == 2) ? 2 * grouped_entries_for_args(L, plan) : 0;
+    a.digest_o_off = L.tab.digest_order_off;
     return a;
 }
 
@@ -3383,19 +3392,29 @@ namespace {
 long long grouped_entries(const DasLaunch& L, const DasPlan& plan) { return grouped_entries_for_args(L, plan); }
 }  // namespace
 
+// Where the sweep order of a launch sits in its digest (behind the grouped entries and lerp's weights), 0 where the plan's kernel
+// takes none: only the pad / lerp pair kernels do.
+long long digest_order_offset(const DasLaunch& L, const DasPlan& plan)
+{
+    if (plan.layout != 2 || plan.nf != 2 || (L.algo != ALGO_PAD && L.algo != ALGO_LERP)) return 0;
+    return (L.algo == ALGO_LERP ? 2 : 1) * grouped_entries(L, plan);
+}
+
 size_t digest_elements(const DasLaunch& L, const DasPlan& plan)
 {
     if (plan.layout != 2) return 0;
     const size_t direct = (size_t)L.n_dirs * (size_t)L.n_mics;                 // the [D][M] layout of the DIRECT variant
-    if (L.algo == ALGO_PAD) return std::max((size_t)grouped_entries(L, plan), direct);
-    if (L.algo == ALGO_LERP) return std::max((size_t)(2 * grouped_entries(L, plan)), direct);    // offsets, then the lerp weights in the same order
+    const size_t order = digest_order_offset(L, plan) != 0 ? (size_t)(grouped_entries(L, plan) / L.n_mics) : 0;   // one entry per (padded) position
+    if (L.algo == ALGO_PAD) return std::max((size_t)grouped_entries(L, plan) + order, direct);
+    if (L.algo == ALGO_LERP) return std::max((size_t)(2 * grouped_entries(L, plan)) + order, direct);    // offsets, then the lerp weights in the same order
     // the FIR pair kernel: offsets and packed guards (hybrid), then the taps regrouped per 8 directions
     if (L.algo == ALGO_HYBRID) return std::max((size_t)L.n_dirs * (size_t)L.n_mics, plan.nf == 2 ? (size_t)(10 * grouped_entries(L, plan)) : (size_t)0);
     if ((L.algo == ALGO_FIR_NAIVE || L.algo == ALGO_FIR_VEC) && plan.nf == 2) return (size_t)(8 * grouped_entries(L, plan));
     return 0;
 }
 
-hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, bool direct, hipStream_t stream)
+hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, bool direct, long long order_off,
+                         hipStream_t stream)
 {
     // what the kernel looks back by beyond the whole-sample delay: lerp reads s[k - p - 1], hybrid starts its window at
     // s[k - p - 1 - T/2] (T = 8)
@@ -3413,7 +3432,7 @@ hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_dig
                            L.algo == ALGO_LERP ? L.tab.frac : nullptr, d_digest,
                            entries, entries, L.n_mics, plan.dpw, L.dir_begin, L.dir_end, plan.mic_chunk, arrays, plan.row_stride, plan.lead, bias,
                            plan.copies, d_reload_count, L.algo == ALGO_HYBRID ? 1 : 0, plan.interleaved ? 2 : 1, fir_pair ? L.tab.taps : nullptr,
-                           fir_pair ? (L.algo == ALGO_HYBRID ? 2 * entries : 0) : 0);
+                           fir_pair ? (L.algo == ALGO_HYBRID ? 2 * entries : 0) : 0, order_off != 0 ? d_digest + order_off : nullptr);
     }
     return hipGetLastError();
 }
