@@ -1,0 +1,202 @@
+"""Cases for test_batched_plan_branches.py (GPU) and test_batched_cases_host.py (CPU): frame batches that reach every kernel family
+plan_das (csrc/das_kernels.hip) routes a bf_das_device call to, with more frame rows than active microphones, and a NumPy
+restatement of the routing rule so that a case's expected family is checked on the CPU before a GPU sees it.
+TEST INFRASTRUCTURE ONLY.
+
+Two table kinds:
+  random   independent uniform delays per (direction, microphone), as test_gpu_parity._random_case draws them: the whole-sample
+           delay changes at nearly every direction step, so pad / lerp with 16 waves replan to the direction-outer variant (3)
+  smooth   delays[d, m] = c_m + s_m * d / D over the flat direction index d, c_m uniform in [0, pmax - span], s_m uniform in
+           [-span, span], clipped at 0, with span = min(D / 8, pmax / 2).  A microphone's whole-sample delay then changes at most
+           span + 1 times over the D - 1 steps (under 1/4 of them at every D used here, span / 2D on average), so the sweep
+           kernels (2, 5, 6, 8) are what runs."""
+import collections
+import functools
+import zlib
+
+import numpy as np
+
+import sweep_order_np as SO
+from util import ALGOS
+
+PLAIN = ("pad", "lerp")
+FIRS = ("hybrid", "fir_naive", "fir_vec")
+ALL = PLAIN + FIRS
+
+Case = collections.namedtuple("Case", "name family algos M_total n N X Y T pmax kind rows F")
+
+
+def _c(name, family, algos, M_total, n, N, X, Y, T, pmax, kind, rows="sorted", F=3):
+    return Case(name, family, algos, M_total, n, N, X, Y, T, pmax, kind, rows, F)
+
+
+# `family`: bf_last_das_variant() of the batched call (include/beamformer_hip.h), one number or one per algorithm.
+CASES = [
+    # ---- 0: the strided kernel das_mimo_kernel
+    _c("strided_nc1_odd_n", 0, ALL, 8, 5, 64, 3, 3, 8, 63.9, "random", rows="reversed"),   # nc = 1, odd n, delays up to the block
+    _c("strided_masked_tail", 0, ALL, 16, 13, 100, 5, 3, 8, 20.0, "random"),               # N not a multiple of 64
+    _c("strided_chunked_dpw4", 0, PLAIN, 300, 280, 128, 4, 3, 8, 47.0, "random"),          # mics chunked, 4 accumulators carried across chunks
+    _c("strided_fir_16_taps", 0, FIRS, 40, 32, 256, 4, 4, 16, 9.0, "random"),              # T = 16: no shifted-copies layout
+    _c("strided_fir_512", 0, FIRS, 24, 20, 512, 5, 4, 8, 60.0, "random"),                  # FIR beyond 256 samples, nc = 8
+    # ---- 2: the one-frame sweep das_copies_kernel walking the frames
+    _c("sweep_8_waves", 2, PLAIN, 64, 37, 256, 7, 5, 8, 30.0, "random"),                   # fewer than 256 directions, n % 16 != 0 (8 waves count no re-reads: random stays in the sweep)
+    _c("sweep_16_waves_odd_n", 2, PLAIN, 64, 37, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),   # 272 directions, n % 16 != 0
+    _c("sweep_scalar_staging", 2, PLAIN, 20, 16, 202, 17, 16, 8, 30.0, "smooth"),          # N % 4 != 0
+    _c("sweep_runtime_stride", 2, PLAIN, 20, 16, 256, 17, 16, 8, 200.0, "smooth"),         # lead > 56; n and N otherwise pair-eligible
+    # ---- 3: the direction-outer variant of das_copies_kernel
+    _c("direct_m_total", 3, PLAIN, 20, 16, 256, 17, 16, 8, 40.0, "random", rows="reversed"),
+    _c("direct_four_segments", 3, PLAIN, 40, 24, 1024, 9, 8, 8, 40.0, "random"),
+    # ---- 4: the FIR one-frame kernel walking the frames
+    _c("fir_one_frame_odd_n", 4, FIRS, 64, 37, 256, 7, 5, 8, 30.0, "random", rows="reversed"),
+    # ---- 6: das_long_kernel
+    _c("long_two_segments", 6, PLAIN, 40, 32, 512, 17, 16, 8, 40.0, "smooth", rows="reversed"),   # fixed row stride
+    _c("long_partial_third", 6, PLAIN, 64, 48, 700, 17, 16, 8, 20.0, "smooth"),            # third segment partial, fourth empty
+    # four segments, run-time row stride.  lerp: rows of (sample, difference) pairs behind a 304-float prefix are 2 * 1328 floats; two
+    # copies of 8 microphones are 169984 bytes, more than the 160 KiB of LDS, so plan_das keeps das_copies_kernel (2) for it
+    _c("long_runtime_stride", {"pad": 6, "lerp": 2}, PLAIN, 20, 16, 1000, 9, 8, 8, 300.0, "smooth"),
+    _c("sweep_two_segments_odd_n", 2, PLAIN, 12, 9, 450, 9, 8, 8, 30.0, "smooth"),         # n % half != 0: das_copies_kernel at two segments
+    # ---- 5 / 8 and 7: the pair kernels with out-of-order rows
+    _c("pair_reversed_rows", {"pad": 5, "lerp": 8}, PLAIN, 20, 16, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),
+    _c("fir_pair_reversed_rows", 7, FIRS, 40, 32, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),
+    # ---- two frames: the smallest batch the pair kernels take, no workgroup row with a single frame
+    _c("pair_two_frames", {"pad": 5, "lerp": 8}, PLAIN, 20, 16, 256, 17, 16, 8, 30.0, "smooth", F=2),
+]
+BY_NAME = {c.name: c for c in CASES}
+PARAMS = [(c.name, a) for c in CASES for a in c.algos]
+
+# the cases of the digest-cache eviction tests
+EVICT_PLAIN, EVICT_FIR = "pair_reversed_rows", "fir_pair_reversed_rows"
+
+
+def family_of(case, algo):
+    return case.family[algo] if isinstance(case.family, dict) else case.family
+
+
+def shard(case):
+    """The direction range [lo, hi) of the batched call."""
+    return 3, case.X * case.Y - 2
+
+
+def span_of(case):
+    return min(case.X * case.Y / 8.0, case.pmax / 2.0)
+
+
+Data = collections.namedtuple("Data", "frames mics delays taps")
+
+
+@functools.lru_cache(maxsize=None)
+def data(name):
+    """frames float32 [F, M_total, N], mics int32 [n] (rows of a frame; column i of a table pairs with mics[i]), delays float64
+    [D, n], taps float32 [D, n, T].  Seeded by the case's name; read-only, shared by every test that asks."""
+    c = BY_NAME[name]
+    D = c.X * c.Y
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    frames = (rng.standard_normal((c.F, c.M_total, c.N)) * 0.25).astype(np.float32)
+    mics = np.sort(rng.choice(c.M_total, c.n, replace=False)).astype(np.int32)
+    if c.rows == "reversed":
+        mics = np.ascontiguousarray(mics[::-1])
+    if c.kind == "random":
+        delays = rng.uniform(0, c.pmax, size=(D, c.n))
+    else:
+        span = span_of(c)
+        c_m = rng.uniform(0, c.pmax - span, size=c.n)
+        s_m = rng.uniform(-span, span, size=c.n)
+        delays = np.maximum(c_m[None, :] + s_m[None, :] * (np.arange(D)[:, None] / D), 0.0)
+    taps = rng.uniform(-0.5, 0.5, size=(D, c.n, c.T)).astype(np.float32)
+    for a in (frames, mics, delays, taps):
+        a.setflags(write=False)
+    return Data(frames, mics, delays, taps)
+
+
+def table(name, algo):
+    """What load_coefficients_* takes for `algo`, shaped [X, Y, n(, T)]."""
+    c, d = BY_NAME[name], data(name)
+    if algo == "pad":
+        t = d.delays.astype(int).astype(np.int32)
+    elif algo in ("lerp", "hybrid"):
+        t = np.float32(d.delays)
+    else:
+        return np.ascontiguousarray(d.taps.reshape(c.X, c.Y, c.n, c.T))
+    return np.ascontiguousarray(t.reshape(c.X, c.Y, c.n))
+
+
+def whole(name, algo):
+    """The whole-sample rows int32 [D, n] the library keeps for `algo` (values beyond N clamp to N); None for the plain FIRs."""
+    c, d = BY_NAME[name], data(name)
+    if algo in ("fir_naive", "fir_vec"):
+        return None
+    w = d.delays.astype(int).astype(np.int32) if algo == "pad" else SO.whole_of(d.delays)
+    return np.minimum(w, c.N)
+
+
+# ---- the routing rule, restated ---------------------------------------------------------------------------------------------
+
+def reload_share(w, lo, hi, dpw, order=None):
+    """(changes, steps) as bf_last_das_reloads defines them for directions [lo, hi) swept in `order` (default: flat): steps =
+    the positions of every run of dpw but its first (a partial last run padded to dpw), times the microphones; changes = those
+    at which the whole-sample delay differs from the position before."""
+    order = np.arange(lo, hi) if order is None else order
+    steps = -(-(hi - lo) // dpw) * (dpw - 1) * w.shape[1]
+    return SO.run_changes(w, order, dpw), steps
+
+
+def _round_up(v, m):
+    return (v + m - 1) // m * m
+
+
+def plan(algo, n, N, T, dirs, frames, max_whole):
+    """What plan_das decides before any digest is counted: dict(nc, layout, lead, waves, dpw, pair, long_rows)."""
+    nc = -(-N // 64)
+    nc = 1 if nc <= 1 else 2 if nc <= 2 else 4 if nc <= 4 else 8 if nc <= 8 else 16
+    plain = algo in PLAIN
+    if not (nc >= 4 if plain else (nc == 4 and T == 8)):
+        return dict(nc=nc, layout=0)
+    nseg = nc // 4
+    fixed_lead = 56 if nseg == 1 else 64
+    back = max_whole + 1 + T // 2 if algo == "hybrid" else T // 2 if not plain else max_whole + 1
+    lead = max(_round_up(back + 1, 4), fixed_lead)
+    waves = 8 if plain and nseg == 1 and dirs < 256 else 16
+    dpw = 4 if nseg == 4 else 8
+    pair = nseg == 1 and waves == 16 and lead == fixed_lead and n % 16 == 0 and N % 4 == 0 and frames >= 2
+    long_rows = False
+    if plain and nseg > 1:
+        half = 16 // nseg
+        slot_bytes = (2 if algo == "lerp" else 1) * 2 * (lead + nseg * 256) * 4      # two shifted copies of a microphone's row(s)
+        long_rows = n % half == 0 and N % 4 == 0 and slot_bytes * 2 * half <= 160 * 1024
+    return dict(nc=nc, layout=2, lead=lead, waves=waves, dpw=dpw, pair=pair, long_rows=long_rows)
+
+
+def predict_family(algo, n, N, T, w, lo, hi, frames):
+    """bf_last_das_variant() of a launch over directions [lo, hi) of a table whose whole-sample rows are `w` (None: the plain
+    FIRs), following plan_das and ensure_digest (csrc/beamformer_api.cpp)."""
+    max_whole = 0 if w is None else int(w.max())
+    p = plan(algo, n, N, T, hi - lo, frames, max_whole)
+    if p["layout"] == 0:
+        return 0
+    if algo not in PLAIN:
+        return 7 if p["pair"] else 4
+    if p["waves"] == 16:
+        # the digest build counts the re-reads in the order the launch sweeps (the pair kernels: bf_sweep_order) and hands a table
+        # that re-reads at more than half of the shareable steps to the direction-outer variant
+        order = SO.sweep_order(w, lo, hi, p["dpw"])[0] if p["pair"] else None
+        changes, steps = reload_share(w, lo, hi, p["dpw"], order)
+        if steps > 0 and 2 * changes > steps:
+            return 3
+    if p["pair"]:
+        return 8 if algo == "lerp" else 5
+    return 6 if p["long_rows"] else 2
+
+
+_WANT = {}
+
+
+def want(oracle_lib, name, algo):
+    """Oracle maps float32 [F, D] of every frame over the full direction range: computed once per (case, algo), read-only."""
+    if (name, algo) not in _WANT:
+        c, d = BY_NAME[name], data(name)
+        orc = oracle_lib.Oracle(c.N, c.X, c.Y, c.T)
+        orc.load(ALGOS[algo], table(name, algo))
+        w = np.stack([orc.mimo_range(ALGOS[algo], d.frames[f], d.mics, 0, c.X * c.Y) for f in range(c.F)])
+        w.setflags(write=False)
+        _WANT[(name, algo)] = w
+    return _WANT[(name, algo)]
