@@ -1,4 +1,4 @@
-"""ISA check for the asm-managed LDS reads of das_kernels.hip.
+"""ISA check for the asm-managed LDS reads of the shifted-copies kernels (das_kernels.hip, das_pair.hip).
 
 issue_quads / steps4 / pair_steps request LDS reads into registers that later asm statements consume after an s_waitcnt of
 their own; the compiler does not know those registers have a read in flight.  That is sound only while NOTHING touches such
@@ -15,7 +15,7 @@ bytes.  This script checks that on the gfx950 assembly of every das_copies_kerne
   * from the code-object metadata: no instantiation that keeps reads in flight may spill (`.vgpr_spill_count`,
     `.private_segment_fixed_size` must be 0).
 
-usage: python scripts/dev/check_inflight_copies.py [file.s]     (without a file: compiles das_kernels.hip to assembly first)"""
+usage: python scripts/dev/check_inflight_copies.py [file.s]     (without a file: compiles the delay-and-sum units to assembly first)"""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,11 +23,28 @@ KERNEL_RE = re.compile(r"^(_ZN2bf\S*(das_copies_kernel|das_pair_kernel|das_pair2
 MAX_QUEUE = 24          # lgkmcnt is a 4-bit counter; older entries than this cannot be told apart by any wait
 
 
-def compile_asm(out):
-    src = os.path.join(ROOT, "zybo-rt-sampler-image-detection_amd", "csrc", "das_kernels.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-jump-tables",
-           "--cuda-device-only", "-S", src, "-o", out]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
+UNITS = ["das_kernels.hip", "das_strided.hip", "das_pair.hip"]
+
+
+def compile_asm(out, units=None):
+    """Compile the named delay-and-sum units (default: all) to gfx950 assembly, at most six at a time, and concatenate it into `out`.
+    Local label numbers repeat from unit to unit; every reader below resolves them inside one kernel."""
+    units = list(units or UNITS)
+    csrc = os.path.join(ROOT, "zybo-rt-sampler-image-detection_amd", "csrc")
+    with tempfile.TemporaryDirectory() as tmp:
+        parts = [os.path.join(tmp, u + ".s") for u in units]
+        for i in range(0, len(units), 6):
+            jobs = []
+            for u, part in zip(units[i:i + 6], parts[i:i + 6]):
+                cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-jump-tables",
+                       "--cuda-device-only", "-S", os.path.join(csrc, u), "-o", part]
+                jobs.append((cmd, subprocess.Popen(cmd, stderr=subprocess.DEVNULL)))
+            for cmd, job in jobs:
+                if job.wait() != 0:
+                    raise subprocess.CalledProcessError(job.returncode, cmd)
+        with open(out, "w") as f:
+            for part in parts:
+                f.write(open(part).read())
 
 
 def demangle(names):
@@ -224,7 +241,7 @@ if __name__ == "__main__":
     if len(sys.argv) > 1:
         path = sys.argv[1]
     else:
-        path = os.path.join(tempfile.mkdtemp(), "das_kernels.s")
+        path = os.path.join(tempfile.mkdtemp(), "das_units.s")
         compile_asm(path)
     kernels, bad = scan(path)
     for b in bad[:20]:

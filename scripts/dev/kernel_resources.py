@@ -1,9 +1,11 @@
 """Compact per-kernel register / scratch / LDS / occupancy table for a .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python scripts/dev/kernel_resources.py [file.hip] [name filter]"""
+usage: python scripts/dev/kernel_resources.py file.hip [name filter]     (file.hip: a path, or the name of a unit in csrc/, e.g. das_pair.hip)"""
 import os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-src = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] else os.path.join(ROOT, "zybo-rt-sampler-image-detection_amd", "csrc", "das_kernels.hip")
+if len(sys.argv) < 2:
+    sys.exit(__doc__)
+src = sys.argv[1] if os.path.exists(sys.argv[1]) else os.path.join(ROOT, "zybo-rt-sampler-image-detection_amd", "csrc", sys.argv[1])
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-jump-tables", "--cuda-device-only",
        "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]

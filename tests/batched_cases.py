@@ -1,5 +1,5 @@
 """Cases for test_batched_plan_branches.py (GPU) and test_batched_cases_host.py (CPU): frame batches that reach every kernel family
-plan_das (csrc/das_kernels.hip) routes a bf_das_device call to, with more frame rows than active microphones, and a NumPy
+plan_das (csrc/das_plan.cpp) routes a bf_das_device call to, with more frame rows than active microphones, and a NumPy
 restatement of the routing rule so that a case's expected family is checked on the CPU before a GPU sees it.
 TEST INFRASTRUCTURE ONLY.
 

@@ -1,4 +1,4 @@
-"""The hand-scheduled LDS reads of das_kernels.hip stay sound only while nothing touches a register that has a read in
+"""The hand-scheduled LDS reads of the shifted-copies kernels (csrc/das_kernels.hip, das_pair.hip) stay sound only while nothing touches a register that has a read in
 flight (scripts/dev/check_inflight_copies.py explains).  CPU-only: compiles the kernels to gfx950 assembly, builds the control-
 flow graph of every das_copies_kernel / das_pair_kernel instantiation (out-of-line `.subsection 1` stubs and loop back-edges
 included), runs the in-flight data-flow over every path, and reads spill / scratch sizes from the code-object metadata."""
@@ -21,7 +21,7 @@ def chk():
 
 @pytest.fixture(scope="module")
 def asm(chk, tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("isa") / "das_kernels.s")
+    path = str(tmp_path_factory.mktemp("isa") / "das_units.s")
     chk.compile_asm(path)
     return path
 
@@ -59,6 +59,68 @@ def test_scanner_finds_what_it_should(chk, tmp_path, body, n_bad):
     assert kernels == 1 and len(bad) == n_bad, bad
 
 
+@pytest.fixture(scope="module")
+def iseq():
+    spec = importlib.util.spec_from_file_location("isa_equal", os.path.join(util.ROOT, "scripts", "dev", "isa_equal.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+FAKE_UNIT = """
+_Z5alphaPf:
+	s_load_dwordx2 s[0:1], s[4:5], 0x0 ; a comment
+.LBB%(n)d_1:
+
+	v_add_f32_e32 v1, %(operand)s, v1
+	s_cbranch_scc1 .LBB%(n)d_1
+	s_cbranch_scc0 .Lr1_%(stmt)d
+.Lb1_%(stmt)d:
+	s_endpgm
+	.subsection 1
+.Lr1_%(stmt)d:
+	s_branch .Lb1_%(stmt)d
+	.subsection 0
+.Lfunc_end%(n)d:
+%(second)s
+	.amdgpu_metadata
+---
+amdhsa.kernels:
+  - .agpr_count:     0
+    .group_segment_fixed_size: 0
+    .name:           _Z5alphaPf
+    .private_segment_fixed_size: 0
+    .sgpr_count:     12
+    .vgpr_count:     %(vgprs)d
+    .vgpr_spill_count: 0
+%(second_md)s...
+	.end_amdgpu_metadata
+"""
+FAKE_SECOND = "_Z4betaPf:\n\ts_endpgm\n.Lfunc_end7:\n"
+FAKE_SECOND_MD = """  - .agpr_count:     0
+    .group_segment_fixed_size: 1024
+    .name:           _Z4betaPf
+    .private_segment_fixed_size: 0
+    .sgpr_count:     8
+    .vgpr_count:     2
+    .vgpr_spill_count: 0
+"""
+
+
+@pytest.mark.parametrize("change,n_diff,needle", [
+    (dict(n=3, stmt=212), 0, None),                                     # equal but for the label numbers of another unit
+    (dict(operand="v3"), 1, "v_add_f32_e32 v1, v3, v1"),                # one changed instruction
+    (dict(vgprs=25), 1, ".vgpr_count 24 -> 25"),                        # one changed metadata field
+    (dict(second="", second_md=""), 1, "only in OLD: _Z4betaPf"),       # one kernel missing
+])
+def test_comparator_finds_what_it_should(iseq, change, n_diff, needle):
+    base = dict(n=0, stmt=17, operand="v2", vgprs=24, second=FAKE_SECOND, second_md=FAKE_SECOND_MD)
+    diffs, common = iseq.compare(FAKE_UNIT % base, FAKE_UNIT % dict(base, **change))
+    assert common == (1 if "second" in change else 2)
+    assert len(diffs) == n_diff, diffs
+    assert needle is None or needle in diffs[0], diffs
+
+
 def test_no_register_with_a_read_in_flight_is_touched(chk, asm):
     kernels, bad = chk.scan(asm)
     assert kernels >= 43
@@ -66,7 +128,7 @@ def test_no_register_with_a_read_in_flight_is_touched(chk, asm):
 
 
 def test_every_default_plan_instantiation_is_scanned_and_none_that_pipelines_reads_spills(chk, asm):
-    """launch_copies (das_kernels.hip) can pick: the pair kernel (pad) and its frame-interleaved successor (lerp); the one-frame sweep for 1 / 2 / 4 segments with the fixed or
+    """launch_das (das_plan.cpp) can pick for the shifted-copies layout: the pair kernel (pad) and its frame-interleaved successor (lerp); the one-frame sweep for 1 / 2 / 4 segments with the fixed or
     the run-time row stride, 16 waves -- one segment also with 8 waves -- and its direction-outer (DIRECT) twin; the three 8-tap FIR
     flavours.  The instantiations that keep LDS reads in flight across asm statements (pair kernel; one-segment sweep; the long-row
     kernel, whose lerp sweep issues a mic's reads behind its predecessor's last step) must not use scratch: a spilled register with a read in flight is reloaded before the data lands."""
@@ -87,7 +149,7 @@ def test_every_default_plan_instantiation_is_scanned_and_none_that_pipelines_rea
     pipelined = [w for w in want if "bf::copies::das_pair_kernel" in w or "bf::copies::das_long_kernel" in w or "bf::copies::das_pair2_kernel" in w or
                  "bf::copies::das_hybrid_pair_kernel" in w or
                  (w.startswith("bf::copies::das_copies_kernel<0, 1,") or w.startswith("bf::copies::das_copies_kernel<1, 1,")) and w.endswith("false>")]
-    assert len(pipelined) == 1 + 8 + 2 * 4 + 1 + 3     # (das_kernels.hip refuses to launch any of these from a build that uses scratch)
+    assert len(pipelined) == 1 + 8 + 2 * 4 + 1 + 3     # (their launchers refuse to launch any of these from a build that uses scratch)
     for w in pipelined:
         m = md[short[w]]
         assert m["spill"] == 0 and m["scratch"] == 0, (w, m)

@@ -128,8 +128,8 @@ def asm(tmp_path_factory):
     spec = importlib.util.spec_from_file_location("check_inflight_copies", os.path.join(util.ROOT, "scripts", "dev", "check_inflight_copies.py"))
     chk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(chk)
-    path = str(tmp_path_factory.mktemp("miso_isa") / "das_kernels.s")
-    chk.compile_asm(path)
+    path = str(tmp_path_factory.mktemp("miso_isa") / "das_strided.s")
+    chk.compile_asm(path, units=["das_strided.hip"])
     return chk, path
 
 

@@ -1,7 +1,7 @@
 """GPU (-m gpu): the one-direction path, bit for bit against the oracle.
 
 Every miso_* entry point and every single-signal helper (pad_delay, lerp_delay, convolve_*_delay*) runs
-das_miso_kernel<ALGO, NC> (csrc/das_kernels.hip), NC in {1, 2, 4, 8, 16} by N, with the microphones staged through LDS in
+das_miso_kernel<ALGO, NC> (csrc/das_strided.hip), NC in {1, 2, 4, 8, 16} by N, with the microphones staged through LDS in
 one or several chunks.  The oracle (oracle/das_oracle.c) is pinned to the compiled reference by test_oracle_golden.py, and
 the kernels keep the reference's microphone order and operation order, so the raw blocks must be BIT-IDENTICAL.
 

@@ -1,7 +1,7 @@
 // beamformer_api.cpp -- the C-ABI of include/beamformer_hip.h: process-global state, table upload, launch glue.
 //
 // Mirrors the reference's process model: one table set per process, loaded once before the frame loop
-// (PC/src/main.pyx:172-181), single-threaded callers.  Everything numerical runs in das_kernels.hip; this
+// (PC/src/main.pyx:172-181), single-threaded callers.  Everything numerical runs in das_kernels.hip, das_strided.hip and das_pair.hip; this
 // file only validates, copies and enqueues.  There is no CPU compute path: when no GPU is usable every entry
 // point reports an error and poisons its output with NaN.
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI layer (beamformer_api.cpp) and the gfx950 kernels (das_kernels.hip).
+// Internal interface between the C-ABI layer (beamformer_api.cpp) and the gfx950 kernels (das_kernels.hip, das_strided.hip, das_pair.hip, planned by das_plan.cpp).
 // Not installed; the public boundary is include/beamformer_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -187,7 +187,7 @@ hipError_t launch_fd_cholesky_inverse(const float* rre, const float* rim, int n_
 hipError_t launch_fd_mvdr_power(const float* lire_t, const float* liim_t, const float* are, const float* aim, int n_mics, int n_dirs, int n_bins,
                                 float* d_power, float* d_work, size_t work_floats, hipStream_t stream);
 
-// Profiling build only (-DBF_STAMPS): phase totals of das_pair_kernel, see das_kernels.hip (zeros in a production build).
+// Profiling build only (-DBF_STAMPS): phase totals of das_pair_kernel, see das_pair.hip (zeros in a production build).
 hipError_t read_phase_stamps(unsigned long long* out16, bool clear);
 
 // detector post-processing (nms_kernels.hip): YOLOv5 head decode + confidence filter, greedy NMS over score-sorted candidates

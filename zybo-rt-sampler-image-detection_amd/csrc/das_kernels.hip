@@ -11,22 +11,25 @@
 //   * mic order and operation order are the reference's, and the final sum over k is sequential in k (rows parked in
 //     LDS, one lane per direction), so the images are bit-identical to the CPU result.
 // Two families of kernels (DESIGN.md section 4.1 has the measurements behind each choice):
-//   * das_mimo_kernel / das_miso_kernel ("strided": lane l owns samples l, l+64, ...): any N <= 1024, any tap count,
+//   * das_strided.hip: das_mimo_kernel / das_miso_kernel ("strided": lane l owns samples l, l+64, ...): any N <= 1024, any tap count,
 //     single beams; table entries by vector load + v_readlane.  The first implementation; now the general fallback.
 //   * copies::das_copies_kernel ("shifted copies": every staged row kept in copies shifted by one sample each, lane l owns
 //     the quad 4l..4l+3): pad / lerp for 128 < N <= 1024 and the 8-tap FIR flavours for N <= 256.  pad / lerp sweep a mic
 //     over the wave's 8 directions and re-read its quad from LDS only when the delay changes from one direction to the
 //     next (two copies, 8-byte reads); the FIR flavours and the direction-outer variant for tables without structure read
 //     at every step (four copies, 16-byte reads).
-//   * copies::das_pair_kernel (pad) / das_pair2_kernel (lerp): the same sweep with TWO frames per workgroup -- batched launches
+//   * das_pair.hip: copies::das_pair_kernel (pad) / das_pair2_kernel (lerp): the same sweep with TWO frames per workgroup -- batched launches
 //     at N <= 256, what the bench and every multi-frame caller run: the per-step scalar work is shared by both frames.
+// This unit holds the shifted-copies kernels that are not the pad / lerp pair: das_copies_kernel, the 8-tap FIR pair kernel
+// (das_hybrid_pair_kernel), the long-row kernel (das_long_kernel) and the digests all of them read.  das_plan.cpp (host only) sizes a
+// launch and picks its family; bf_remove_sources_device's kernel sits at the end of this file; das_device.h / das_geometry.h hold what the units share.
 // Workgroup id -> (tile, frame): with large tables the tile count is padded to a multiple of 8 so that tile % 8 == id % 8,
 // i.e. all frames' workgroups of one direction tile land on one XCD and re-read that tile's table slice from the XCD's
 // own L2; tables that fit every L2 spread their tiles over all XCDs (plan_das sizes the tiles by the rounds either costs).
 //
 // Roofline: gather-accumulate, no MFMA, not HBM-bound (tables and samples are reused out of L2 / LDS); the binding
 // resource is VALU issue.  See DESIGN.md section 5 for the byte / instruction accounting.
-#include "das_kernels.h"
+#include "das_device.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -34,620 +37,6 @@
 namespace bf {
 
 namespace {
-
-constexpr int kWave = 64;
-
-// Scalars of one launch (kernel argument, lives in SGPRs).
-struct KArgs {
-    long long miso_row;                   // launch_miso only: flat table offset (the reference's `offset`)
-    int n_mics, m_total, n_samples, n_taps;
-    int dir_begin, dir_end, image_stride, image_origin;
-    int lead, row_stride, mic_chunk, n_chunks, tile_dirs, n_tiles;
-    int scratch_off, srow, pbw;           // per-wave power scratch: float offset in LDS, row stride, rows per wave
-    int n_is_pow2;
-    float inv_n;
-    int n_frames;   // frames of the launch (das_pair_kernel: whether a workgroup's second frame exists)
-    int wg_frames, frame_inner;   // workgroup id -> (tile, frame [pair]): see tile_and_frame()
-    long long digest_h_off;   // shifted-copies pad / lerp: where the grouped lerp weights start in the digest buffer (floats)
-    long long digest_t_off;   // the 8-tap FIR pair kernel: where the taps regrouped per 8 directions start in the digest buffer (floats)
-    long long digest_o_off;   // pad / lerp pair kernels: where the sweep order (flat direction of every position) starts in the digest buffer; 0 = positions are directions
-};
-
-// Workgroup id -> (direction tile, frame or frame pair).  Ids go round-robin over the 8 XCDs.
-//   frame_inner == 0:  tile = id % n_tiles, frame = id / n_tiles.  With n_tiles a multiple of 8 a tile's workgroups stay on
-//                      one XCD (tile % 8 == id % 8); an XCD walks its tiles frame by frame, so a tile's table slice is
-//                      re-used out of L2 only if the XCD's share of the whole table stays resident (cfg2: 650 KB).
-//   frame_inner == 1:  tables beyond that (cfg5: 33 MB per XCD): XCD x = id % 8 walks tile x, x + 8, .. and runs ALL frames of
-//                      a tile back to back (its 32 CUs hold 32 frames of the same tile at a time), so the slice comes from
-//                      HBM once instead of once per frame.
-__device__ __forceinline__ void tile_and_frame(const KArgs& a, int* tile, int* frame)
-{
-    const unsigned id = blockIdx.x;
-    if (a.frame_inner) {
-        const unsigned x = id & 7u, j = id >> 3;
-        *tile = (int)(x + 8u * (j / (unsigned)a.wg_frames));
-        *frame = (int)(j % (unsigned)a.wg_frames);
-    } else {
-        *tile = (int)(id % (unsigned)a.n_tiles);
-        *frame = (int)(id / (unsigned)a.n_tiles);
-    }
-}
-
-// The read-only tables are separate `const __restrict__` kernel parameters on purpose: only then can the
-// compiler prove that no store in the kernel clobbers them and fetch the wave-uniform table entries with
-// scalar loads (s_load_*) instead of 64-lane vector loads.
-#define BF_TABLE_PARAMS                                                                                   \
-    const float* __restrict__ signals, float* __restrict__ images, const int32_t* __restrict__ mics,     \
-        const int32_t* __restrict__ whole, const float* __restrict__ frac, const float* __restrict__ taps
-#define BF_TABLE_ARGS signals, images, mics, whole, frac, taps
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-
-// Copy mic rows [m0, m0+mc) of one frame into LDS rows 0..mc-1 at column `lead`.  One wave per row, lanes
-// stride the row in 16-byte pieces (coalesced global_load_dwordx4 -> ds_write_b128).
-__device__ __forceinline__ void stage_chunk(float* lds, const KArgs& a, const int32_t* __restrict__ mics,
-                                            const float* __restrict__ frame, int m0, int mc, int wave, int nwaves, int lane)
-{
-    const int n = a.n_samples;
-    for (int r = wave; r < mc; r += nwaves) {
-        const int mic = mics[m0 + r];
-        const float* src = frame + (size_t)mic * n;
-        float* dst = lds + r * a.row_stride + a.lead;
-        if ((n & 3) == 0) {
-            const float4* s4 = reinterpret_cast<const float4*>(src);
-            float4* d4 = reinterpret_cast<float4*>(dst);
-            for (int i = lane; i < (n >> 2); i += kWave) d4[i] = s4[i];
-        } else {
-            for (int i = lane; i < n; i += kWave) dst[i] = src[i];
-        }
-    }
-}
-
-// First 64-entry block of a table row, requested one work item ahead (pad / lerp): lane m holds entry m.
-struct RowHead {
-    int p = 0;
-    float h = 0.0f;
-    bool valid = false;   // wave-uniform
-};
-
-template <int ALGO>
-__device__ __forceinline__ RowHead request_row_head(const int32_t* __restrict__ whole, const float* __restrict__ frac, size_t row, int mc, int lane)
-{
-    RowHead r;
-    if constexpr (ALGO == ALGO_PAD || ALGO == ALGO_LERP) {
-        r.p = (lane < mc) ? whole[row + lane] : 0;
-        if constexpr (ALGO == ALGO_LERP) r.h = (lane < mc) ? frac[row + lane] : 0.0f;
-        r.valid = true;
-    }
-    return r;
-}
-
-// Accumulate mics [m0, m0+mc) of the table row starting at flat entry `row_base` (= d*M for direction d)
-// into acc[NC] (lane l holds samples l + 64 c).  HIST (the continuous-stream kernels): the columns in front of a staged row hold
-// the samples that precede the window instead of zeros, so lerp's i >= 0 guard is not applied (pad has none).
-template <int ALGO, int NC, bool HIST = false>
-__device__ __forceinline__ void accumulate(float (&acc)[NC], const float* lds, const KArgs& a, const int32_t* __restrict__ whole,
-                                           const float* __restrict__ frac, const float* __restrict__ taps, size_t row_base, int m0,
-                                           int mc, int lane, const RowHead head = RowHead())
-{
-    const size_t row = row_base + m0;
-    const int rs = a.row_stride;
-
-    // pad / lerp: the table row of a direction is fetched 64 mics at a time with ONE coalesced vector load (lane m
-    // holds entry m; the next block is requested before the current one is consumed) and the wave-uniform entry of
-    // each mic is then read out of that register with v_readlane.  Scalar loads would need no VALU slot, but
-    // every new row misses the scalar cache and s_load shares the LDS wait counter, so their latency sat fully
-    // exposed in front of every group of LDS reads (measured: 14 instead of 9 cycles per (direction, mic) per CU).
-    if constexpr (ALGO == ALGO_PAD || ALGO == ALGO_LERP) {
-        const int32_t* __restrict__ wrow = whole + row;
-        const float* __restrict__ hrow = frac + row;
-        int vp = head.p;
-        float vh = head.h;
-        if (!head.valid) {
-            vp = (lane < mc) ? wrow[lane] : 0;
-            if constexpr (ALGO == ALGO_LERP) vh = (lane < mc) ? hrow[lane] : 0.0f;
-        }
-        for (int b0 = 0; b0 < mc; b0 += kWave) {
-            const int bn = min(kWave, mc - b0);
-            int vp_next = 0;
-            float vh_next = 0.0f;
-            if (b0 + kWave < mc) {   // wave-uniform
-                vp_next = (b0 + kWave + lane < mc) ? wrow[b0 + kWave + lane] : 0;
-                if constexpr (ALGO == ALGO_LERP) vh_next = (b0 + kWave + lane < mc) ? hrow[b0 + kWave + lane] : 0.0f;
-            }
-            // (v_readlane is a convergent operation: the compiler will not unroll a runtime-trip loop around it, so the
-            //  blocks of 8 / 4 mics are spelled out and a scalar remainder loop follows)
-            auto pad_one = [&](int u) {
-                // pad_and_sum.c:41-47,54-70   out[p + i] += s[i]
-                const int p = __builtin_amdgcn_readlane(vp, u);
-                const float* r = lds + (b0 + u) * rs + (a.lead - p) + lane;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) acc[c] += r[c * kWave];
-            };
-            auto lerp_one = [&](int u) {
-                // lerp_and_sum.c:50-56,67-92  out[p + i + 1] += s[i] + h * (s[i+1] - s[i]),  0 <= i < N - p - 1
-                const int p = __builtin_amdgcn_readlane(vp, u);
-                const float h = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vh), u));
-                const float* r = lds + (b0 + u) * rs + (a.lead - p - 1) + lane;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const float s0 = r[c * kWave];
-                    const float s1 = r[c * kWave + 1];
-                    float v = __fmaf_rn(h, s1 - s0, s0);      // gcc contracts s0 + h*(s1-s0) into one fma
-                    if constexpr (!HIST) {
-                        if (c * kWave <= p) v = (lane + c * kWave > p) ? v : 0.0f;   // i >= 0 only (wave-uniform guard)
-                    }
-                    acc[c] += v;
-                }
-            };
-            int u = 0;
-            if constexpr (ALGO == ALGO_PAD) {
-                constexpr int kU = NC <= 4 ? 8 : 4;
-                for (; u + kU <= bn; u += kU) {
-#pragma unroll
-                    for (int i = 0; i < kU; ++i) pad_one(u + i);
-                }
-                for (; u < bn; ++u) pad_one(u);
-            } else {
-                constexpr int kU = NC <= 4 ? 4 : 2;
-                for (; u + kU <= bn; u += kU) {
-#pragma unroll
-                    for (int i = 0; i < kU; ++i) lerp_one(u + i);
-                }
-                for (; u < bn; ++u) lerp_one(u);
-            }
-            vp = vp_next;
-            vh = vh_next;
-        }
-    } else if constexpr (ALGO == ALGO_HYBRID) {
-        // hybrid_convolve_and_sum.c:51-64  out[p + i + 1] += h[t] * padded[i + t], t = 0..T-1 in order
-        const int T = a.n_taps;
-        const int32_t* __restrict__ wrow = whole + row;
-        const float* __restrict__ trow = taps + row * T;
-        for (int ms = 0; ms < mc; ++ms) {
-            const int p = wrow[ms];
-            const float* __restrict__ h = trow + ms * T;
-            const float* r = lds + ms * rs + (a.lead - p - 1 - T / 2) + lane;
-            if (T == 8) {   // the reference's N_TAPS: taps in scalar registers, tap loop unrolled
-                const float h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4], h5 = h[5], h6 = h[6], h7 = h[7];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const float* x = r + c * kWave;
-                    float o = acc[c];
-                    o = __fmaf_rn(h0, x[0], o); o = __fmaf_rn(h1, x[1], o); o = __fmaf_rn(h2, x[2], o); o = __fmaf_rn(h3, x[3], o);
-                    o = __fmaf_rn(h4, x[4], o); o = __fmaf_rn(h5, x[5], o); o = __fmaf_rn(h6, x[6], o); o = __fmaf_rn(h7, x[7], o);
-                    acc[c] = (c * kWave <= p && !(lane + c * kWave > p)) ? acc[c] : o;   // samples with i < 0 receive nothing
-                }
-                continue;
-            }
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                float o = acc[c];
-                if (c * kWave <= p) {
-                    // this segment contains samples with i < 0: they must not receive anything
-                    const bool live = lane + c * kWave > p;
-                    for (int t = 0; t < T; ++t) o = live ? __fmaf_rn(h[t], r[c * kWave + t], o) : o;
-                } else {
-                    for (int t = 0; t < T; ++t) o = __fmaf_rn(h[t], r[c * kWave + t], o);
-                }
-                acc[c] = o;
-            }
-        }
-    } else if constexpr (ALGO == ALGO_FIR_NAIVE) {
-        // convolve_and_sum.c:197-211  out[i] += h[t] * padded[i + t], t in order (fma chain into out)
-        const int T = a.n_taps;
-        const float* __restrict__ trow = taps + row * T;
-        for (int ms = 0; ms < mc; ++ms) {
-            const float* __restrict__ h = trow + ms * T;
-            const float* r = lds + ms * rs + (a.lead - T / 2) + lane;
-            if (T == 8) {
-                const float h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4], h5 = h[5], h6 = h[6], h7 = h[7];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const float* x = r + c * kWave;
-                    float o = acc[c];
-                    o = __fmaf_rn(h0, x[0], o); o = __fmaf_rn(h1, x[1], o); o = __fmaf_rn(h2, x[2], o); o = __fmaf_rn(h3, x[3], o);
-                    o = __fmaf_rn(h4, x[4], o); o = __fmaf_rn(h5, x[5], o); o = __fmaf_rn(h6, x[6], o); o = __fmaf_rn(h7, x[7], o);
-                    acc[c] = o;
-                }
-                continue;
-            }
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                float o = acc[c];
-                for (int t = 0; t < T; ++t) o = __fmaf_rn(h[t], r[c * kWave + t], o);
-                acc[c] = o;
-            }
-        }
-    } else {  // ALGO_FIR_VEC
-        // convolve_and_sum.c:158-192 + sum8 :132-153: 8 independent fma lanes over tap blocks, fixed tree, out +=
-        const int T = a.n_taps;
-        const float* __restrict__ trow = taps + row * T;
-        for (int ms = 0; ms < mc; ++ms) {
-            const float* __restrict__ h = trow + ms * T;
-            const float* r = lds + ms * rs + (a.lead - T / 2) + lane;
-            if (T == 8) {   // one AVX block: the eight fma lanes start from 0, i.e. they are plain products
-                const float h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4], h5 = h[5], h6 = h[6], h7 = h[7];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const float* x = r + c * kWave;
-                    const float q0 = x[0] * h0 + x[4] * h4, q1 = x[1] * h1 + x[5] * h5, q2 = x[2] * h2 + x[6] * h6, q3 = x[3] * h3 + x[7] * h7;
-                    acc[c] += (q0 + q2) + (q1 + q3);
-                }
-                continue;
-            }
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                float l0 = 0.f, l1 = 0.f, l2 = 0.f, l3 = 0.f, l4 = 0.f, l5 = 0.f, l6 = 0.f, l7 = 0.f;
-                for (int t = 0; t < T; t += 8) {
-                    const float* x = r + c * kWave + t;
-                    l0 = __fmaf_rn(x[0], h[t + 0], l0); l1 = __fmaf_rn(x[1], h[t + 1], l1);
-                    l2 = __fmaf_rn(x[2], h[t + 2], l2); l3 = __fmaf_rn(x[3], h[t + 3], l3);
-                    l4 = __fmaf_rn(x[4], h[t + 4], l4); l5 = __fmaf_rn(x[5], h[t + 5], l5);
-                    l6 = __fmaf_rn(x[6], h[t + 6], l6); l7 = __fmaf_rn(x[7], h[t + 7], l7);
-                }
-                const float q0 = l0 + l4, q1 = l1 + l5, q2 = l2 + l6, q3 = l3 + l7;
-                const float d0 = q0 + q2, d1 = q1 + q3;
-                acc[c] += d0 + d1;
-            }
-        }
-    }
-}
-
-// ---- mean power, in the reference's summation order ------------------------------------------------------
-// The reference finishes a direction with (pad_and_sum.c:122-131)
-//     for k: out[k] /= n; sum += out[k]^2          (gcc: vdivps, vmulps, then one vaddss per k, in k order)
-//     image = sum / N
-// A float32 sum of N squares taken in another order differs from that by up to ~N*2^-24 relative (2e-5 observed
-// at N = 1024), which is more than the 1e-5 parity bar.  So the squares are summed in k order here too:
-// every wave parks the squares of `pbw` finished directions as rows of a private LDS scratch, then lanes
-// 0..pbw-1 each walk one row front to back (ds_read_b128, four ordered adds per read).
-template <int NC>
-__device__ __forceinline__ void park_squares(const float (&acc)[NC], float* scratch_row, const KArgs& a, int d, int lane)
-{
-    float sq[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        // out[k] /= (float)n: for a power-of-two n the reciprocal multiply is exact; otherwise a true division
-        const float o = a.n_is_pow2 ? acc[c] * a.inv_n : acc[c] / (float)a.n_mics;
-        sq[c] = o * o;
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) scratch_row[lane + c * kWave] = sq[c];
-    if (lane == 0) scratch_row[a.srow - 4] = __int_as_float(d);   // the pad column carries the direction id
-}
-
-// Rows are 16-byte aligned and 4 (mod 64) dwords apart, so up to 16 lanes can each stream their own row with
-// ds_read_b128 without sharing a bank; the additions stay strictly in k order.
-__device__ __forceinline__ void flush_powers(const float* scratch, int filled, float* __restrict__ img, const KArgs& a, int lane)
-{
-    if (lane < filled) {
-        const float* row = scratch + lane * a.srow;
-        const float4* row4 = reinterpret_cast<const float4*>(row);
-        const int n = a.n_samples;
-        float sum = 0.0f;
-        int k = 0;
-#pragma unroll 4
-        for (; k + 4 <= n; k += 4) {
-            const float4 v = row4[k >> 2];
-            sum += v.x; sum += v.y; sum += v.z; sum += v.w;
-        }
-        for (; k < n; ++k) sum += row[k];
-        const int d = __float_as_int(row[a.srow - 4]);
-        img[d - a.image_origin] = sum / (float)n;
-    }
-}
-
-template <int ALGO, int NC, int DPW>
-__global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nwaves = (int)(blockDim.x >> 6);
-    const int tile = (int)(blockIdx.x % (unsigned)a.n_tiles);
-    const int frame = (int)(blockIdx.x / (unsigned)a.n_tiles);
-    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
-    if (tile_begin >= a.dir_end) return;  // padding tile (n_tiles is rounded up to a multiple of 8)
-    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
-
-    // zero the whole LDS image once: the lead/tail columns and unused rows stay zero for the kernel's lifetime
-    {
-        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
-        float4* z = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-
-    const float* __restrict__ frame_sig = signals + (size_t)frame * a.m_total * a.n_samples;
-    float* __restrict__ img = images + (size_t)frame * a.image_stride;
-    const int group = nwaves * DPW;
-    float* scratch = lds + a.scratch_off + wave * (a.pbw * a.srow);
-    int filled = 0;   // wave-uniform
-
-    // Work items of this wave, in order: for g0 / for chunk / for j.  The table-row head of item i+1 is requested
-    // (vector load, its own wait counter) before item i is computed, so its HBM/L2 latency hides behind ~64 mics of work.
-    auto item_dir = [&](int g0_, int j_) { return g0_ + j_ * nwaves + wave; };
-    RowHead head;
-    if (item_dir(tile_begin, 0) < tile_end)
-        head = request_row_head<ALGO>(whole, frac, (size_t)item_dir(tile_begin, 0) * a.n_mics, min(a.mic_chunk, a.n_mics), lane);
-
-    for (int g0 = tile_begin; g0 < tile_end; g0 += group) {
-        float acc[DPW][NC];
-#pragma unroll
-        for (int j = 0; j < DPW; ++j)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[j][c] = 0.0f;
-
-        for (int ch = 0; ch < a.n_chunks; ++ch) {
-            const int m0 = ch * a.mic_chunk;
-            const int mc = min(a.mic_chunk, a.n_mics - m0);
-            if (a.n_chunks > 1 || g0 == tile_begin) {
-                if (a.n_chunks > 1 && (ch > 0 || g0 != tile_begin)) __syncthreads();  // previous readers done
-                stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
-                __syncthreads();
-            }
-#pragma unroll
-            for (int j = 0; j < DPW; ++j) {
-                const int d = g0 + j * nwaves + wave;  // wave-uniform
-                // successor of (g0, ch, j)
-                int ng0 = g0, nch = ch, nj = j + 1;
-                if (nj == DPW) { nj = 0; nch = ch + 1; if (nch == a.n_chunks) { nch = 0; ng0 = g0 + group; } }
-                const int nd = item_dir(ng0, nj);
-                const RowHead cur = head;
-                head = RowHead();
-                if (nd < tile_end) {
-                    const int nm0 = nch * a.mic_chunk;
-                    head = request_row_head<ALGO>(whole, frac, (size_t)nd * a.n_mics + nm0, min(a.mic_chunk, a.n_mics - nm0), lane);
-                }
-                if (d < tile_end) accumulate<ALGO, NC>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < DPW; ++j) {
-            const int d = g0 + j * nwaves + wave;
-            if (d < tile_end) {
-                park_squares<NC>(acc[j], scratch + filled * a.srow, a, d, lane);
-                if (++filled == a.pbw) { flush_powers(scratch, filled, img, a, lane); filled = 0; }
-            }
-        }
-    }
-    if (filled > 0) flush_powers(scratch, filled, img, a, lane);
-}
-
-// Steered beams, raw out[N] (miso_pad / miso_lerp / miso_convolve_*, pad_and_sum.c:54-70 ...).  Workgroup id = frame * groups +
-// group: the workgroup's W = blockDim / 64 waves stage each microphone chunk of ITS frame together (the frame is read from HBM
-// once per workgroup, not once per beam) and wave w then accumulates beam group * W + w out of the shared rows, in the
-// reference's mic order, so every beam is the one-direction result bit for bit.
-//   host path (bf::launch_miso): offsets == nullptr, one frame, one beam, offset a.miso_row, `miso_init` optionally seeds the
-//                                 accumulators (the single-signal helpers), out = miso_out[0..N)
-//   device path (launch_miso_batch): offsets [frames][beams] are table offsets (FIR_VEC: in floats, d * n * T), checked here
-//                                 against `entries` (status 1: outside the table, 2: FIR_VEC offset not a multiple of T);
-//                                 a rejected beam reads no table entry and its N samples are NaN.  gain != 0 scales the
-//                                 beam as api.c:519-523 does, (out / n) * gain, two float32 roundings.
-template <int ALGO, int NC>
-__global__ void __launch_bounds__(1024) das_miso_kernel(BF_TABLE_PARAMS, const float* __restrict__ miso_init, float* __restrict__ miso_out, KArgs a,
-                                                        const int32_t* __restrict__ offsets, int beams, int* __restrict__ status,
-                                                        long long entries, float gain, int out_stride)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nwaves = (int)(blockDim.x >> 6);
-    const int groups = (beams + nwaves - 1) / nwaves;
-    const int frame = (int)(blockIdx.x / (unsigned)groups);
-    const int beam = (int)(blockIdx.x % (unsigned)groups) * nwaves + wave;   // wave-uniform
-    const bool live = beam < beams;                                           // the last group may be partial
-    const size_t slot = (size_t)frame * beams + beam;
-
-    // this wave's table row (wave-uniform) and its verdict
-    long long row = a.miso_row;
-    int verdict = 0;
-    if (offsets != nullptr && live) {
-        const long long off = __builtin_amdgcn_readfirstlane(offsets[slot]);
-        const long long per = ALGO == ALGO_FIR_VEC ? a.n_taps : 1;
-        if (off < 0 || off + (long long)a.n_mics * per > entries) verdict = 1;
-        else if (ALGO == ALGO_FIR_VEC && off % per != 0) verdict = 2;
-        row = off / per;
-    }
-    const bool run = live && verdict == 0;
-
-    {
-        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
-        float4* z = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-    const float* __restrict__ frame_sig = signals + (size_t)frame * a.m_total * a.n_samples;
-    float acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        acc[c] = (miso_init != nullptr && lane + c * kWave < a.n_samples) ? miso_init[lane + c * kWave] : 0.0f;
-    for (int ch = 0; ch < a.n_chunks; ++ch) {
-        const int m0 = ch * a.mic_chunk;
-        const int mc = min(a.mic_chunk, a.n_mics - m0);
-        if (ch > 0) __syncthreads();
-        stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
-        __syncthreads();
-        if (run) accumulate<ALGO, NC>(acc, lds, a, whole, frac, taps, (size_t)row, m0, mc, lane);
-    }
-    if (!live) return;
-    if (status != nullptr && lane == 0) status[slot] = verdict;
-    float* __restrict__ out = miso_out + slot * (size_t)out_stride;
-    const float nan = __int_as_float(0x7fc00000);
-    const float fn = (float)a.n_mics;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        float v = acc[c];
-        if (gain != 0.0f) v = (v / fn) * gain;   // true division: a reciprocal multiply differs unless n is a power of two
-        if (lane + c * kWave < a.n_samples) out[lane + c * kWave] = run ? v : nan;
-    }
-}
-
-// ---- continuous-stream mode (bf_das_stream_device / bf_miso_stream_device) ----------------------------------------------
-// das_mimo_kernel / das_miso_kernel with one change: the `hist` columns in front of every staged row, [lead - hist, lead), hold
-// the samples that precede the window -- row[hop - hist, hop) of the previous frame (frame f - 1 of the launch; `prev0` for
-// frame 0, zeros when that is null) -- instead of zeros, and accumulate<.., HIST = true> drops lerp's i >= 0 guard.  A delayed
-// read lead - p (- 1) + k then finds x(k - p) for every k in [0, N): the first p outputs of a window are no longer sums over a
-// growing subset of the microphones.  hist = max_whole (pad) or max_whole + 1 (lerp); the host checks hist <= hop <= N and
-// hist <= lead, so the slice lies inside the previous frame's row and inside the row's lead.  The slice starts at an arbitrary
-// sample (hop - hist), so it is copied with plain dword loads; it is hist / N of the row's bytes.
-__device__ __forceinline__ void stage_chunk_stream(float* lds, const KArgs& a, const int32_t* __restrict__ mics, const float* __restrict__ frame,
-                                                   const float* __restrict__ prev, int hop, int hist, int m0, int mc, int wave, int nwaves, int lane)
-{
-    stage_chunk(lds, a, mics, frame, m0, mc, wave, nwaves, lane);
-    for (int r = wave; r < mc; r += nwaves) {
-        float* dst = lds + r * a.row_stride + (a.lead - hist);
-        if (prev != nullptr) {   // (workgroup-uniform)
-            const float* src = prev + (size_t)mics[m0 + r] * a.n_samples + (hop - hist);
-            for (int i = lane; i < hist; i += kWave) dst[i] = src[i];
-        } else {
-            for (int i = lane; i < hist; i += kWave) dst[i] = 0.0f;
-        }
-    }
-}
-
-template <int ALGO, int NC, int DPW>
-__global__ void __launch_bounds__(1024) stream_map_kernel(BF_TABLE_PARAMS, KArgs a, const float* __restrict__ prev0, int hop, int hist)
-{
-    static_assert(ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nwaves = (int)(blockDim.x >> 6);
-    const int tile = (int)(blockIdx.x % (unsigned)a.n_tiles);
-    const int frame = (int)(blockIdx.x / (unsigned)a.n_tiles);
-    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
-    if (tile_begin >= a.dir_end) return;
-    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
-
-    // zero the whole LDS image once: the columns in front of the history and behind the samples stay zero
-    {
-        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
-        float4* z = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-
-    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
-    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
-    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
-    float* __restrict__ img = images + (size_t)frame * a.image_stride;
-    const int group = nwaves * DPW;
-    float* scratch = lds + a.scratch_off + wave * (a.pbw * a.srow);
-    int filled = 0;   // wave-uniform
-
-    // work items and the table-row head requested one item ahead: as das_mimo_kernel
-    auto item_dir = [&](int g0_, int j_) { return g0_ + j_ * nwaves + wave; };
-    RowHead head;
-    if (item_dir(tile_begin, 0) < tile_end)
-        head = request_row_head<ALGO>(whole, frac, (size_t)item_dir(tile_begin, 0) * a.n_mics, min(a.mic_chunk, a.n_mics), lane);
-
-    for (int g0 = tile_begin; g0 < tile_end; g0 += group) {
-        float acc[DPW][NC];
-#pragma unroll
-        for (int j = 0; j < DPW; ++j)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[j][c] = 0.0f;
-
-        for (int ch = 0; ch < a.n_chunks; ++ch) {
-            const int m0 = ch * a.mic_chunk;
-            const int mc = min(a.mic_chunk, a.n_mics - m0);
-            if (a.n_chunks > 1 || g0 == tile_begin) {
-                if (a.n_chunks > 1 && (ch > 0 || g0 != tile_begin)) __syncthreads();  // previous readers done
-                stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);   // the history is refilled with every chunk
-                __syncthreads();
-            }
-#pragma unroll
-            for (int j = 0; j < DPW; ++j) {
-                const int d = g0 + j * nwaves + wave;  // wave-uniform
-                int ng0 = g0, nch = ch, nj = j + 1;
-                if (nj == DPW) { nj = 0; nch = ch + 1; if (nch == a.n_chunks) { nch = 0; ng0 = g0 + group; } }
-                const int nd = item_dir(ng0, nj);
-                const RowHead cur = head;
-                head = RowHead();
-                if (nd < tile_end) {
-                    const int nm0 = nch * a.mic_chunk;
-                    head = request_row_head<ALGO>(whole, frac, (size_t)nd * a.n_mics + nm0, min(a.mic_chunk, a.n_mics - nm0), lane);
-                }
-                if (d < tile_end) accumulate<ALGO, NC, true>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < DPW; ++j) {
-            const int d = g0 + j * nwaves + wave;
-            if (d < tile_end) {
-                park_squares<NC>(acc[j], scratch + filled * a.srow, a, d, lane);
-                if (++filled == a.pbw) { flush_powers(scratch, filled, img, a, lane); filled = 0; }
-            }
-        }
-    }
-    if (filled > 0) flush_powers(scratch, filled, img, a, lane);
-}
-
-// Workgroup id = frame * groups + group, one wave per beam, offsets / status / gain / NaN beams as das_miso_kernel's device path.
-template <int ALGO, int NC>
-__global__ void __launch_bounds__(1024) stream_beam_kernel(BF_TABLE_PARAMS, float* __restrict__ beam_out, KArgs a, const int32_t* __restrict__ offsets,
-                                                           int beams, int* __restrict__ status, long long entries, float gain, int out_stride,
-                                                           const float* __restrict__ prev0, int hop, int hist)
-{
-    static_assert(ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nwaves = (int)(blockDim.x >> 6);
-    const int groups = (beams + nwaves - 1) / nwaves;
-    const int frame = (int)(blockIdx.x / (unsigned)groups);
-    const int beam = (int)(blockIdx.x % (unsigned)groups) * nwaves + wave;   // wave-uniform
-    const bool live = beam < beams;                                           // the last group may be partial
-    const size_t slot = (size_t)frame * beams + beam;
-
-    long long row = 0;
-    int verdict = 0;
-    if (live) {
-        const long long off = __builtin_amdgcn_readfirstlane(offsets[slot]);
-        if (off < 0 || off + (long long)a.n_mics > entries) verdict = 1;
-        row = off;
-    }
-    const bool run = live && verdict == 0;
-
-    {
-        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
-        float4* z = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
-    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
-    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
-    float acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.0f;
-    for (int ch = 0; ch < a.n_chunks; ++ch) {
-        const int m0 = ch * a.mic_chunk;
-        const int mc = min(a.mic_chunk, a.n_mics - m0);
-        if (ch > 0) __syncthreads();
-        stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);
-        __syncthreads();
-        if (run) accumulate<ALGO, NC, true>(acc, lds, a, whole, frac, taps, (size_t)row, m0, mc, lane);
-    }
-    if (!live) return;
-    if (status != nullptr && lane == 0) status[slot] = verdict;
-    float* __restrict__ out = beam_out + slot * (size_t)out_stride;
-    const float nan = __int_as_float(0x7fc00000);
-    const float fn = (float)a.n_mics;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        float v = acc[c];
-        if (gain != 0.0f) v = (v / fn) * gain;   // as das_miso_kernel: true division, two roundings
-        if (lane + c * kWave < a.n_samples) out[lane + c * kWave] = run ? v : nan;
-    }
-}
 
 // ==================================================================================================
 // "Shifted-copies" layout (copies::das_copies_kernel below).
@@ -730,37 +119,6 @@ __global__ void __launch_bounds__(256) digest_grouped_kernel(const int32_t* __re
 
 namespace copies {
 
-constexpr int kWaves = 16;       // waves per workgroup (8 for pad / lerp at N <= 256: two workgroups per CU cover each other's barriers)
-
-__device__ __forceinline__ float dpp_prev(float x)   // lane-1's value, 0 in lane 0
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float dpp_next(float x)   // lane+1's value, 0 in lane 63
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float lane_value(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
-
-// Shifted copies kept per staged array.  The sweep of pad / lerp re-reads rarely and reads 8-byte halves: one copy per
-// delay mod 2 is enough (half the staging writes and half the LDS per mic).  The kernels that read at every step -- the
-// 8-tap FIR flavours and the direction-outer (DIRECT) variant of pad / lerp -- need ds_read_b128: one copy per delay mod 4.
-__host__ __device__ constexpr int copies_of(int algo, bool direct) { return ((algo == ALGO_PAD || algo == ALGO_LERP) && !direct) ? 2 : 4; }
-
-// Geometry of the shifted-copies layout for a block of NSEG x 256 samples (N <= 256: 1, <= 512: 2, <= 1024: 4).
-//   * a wave owns DW directions x NSEG segments of 256 samples (one aligned quad per lane per segment);
-//   * compile-time row stride (RS > 0) when the largest delay fits kLead: the D / segment reads become immediate offsets.
-template <int NSEG>
-struct Geo {
-    static constexpr int kDw = NSEG == 1 ? 8 : NSEG == 2 ? 8 : 4;   // directions per wave
-    static constexpr int kBatch = 4 / NSEG;                          // mics whose reads are in flight together
-    static constexpr int kLead = NSEG == 1 ? 56 : 64;                // zero prefix of the fixed-stride variant (56: the as-shipped array's delays, up to 47 samples, still fit; 32 lerp mics x 4 rows x 312 floats = 156 KiB)
-    static constexpr int kRs = NSEG * 256 + kLead;                   // its row stride
-    static constexpr int kPark = NSEG * 256 + 4;                     // floats per parked row of squares
-    static constexpr int kFirTail = 8;                               // 8-tap FIR rows: the reference's zero padding after the block
-    static constexpr int kRsFir = kRs + kFirTail;
-};
-
 // One 8-tap FIR step of the hybrid beamformer on a quad (hybrid_convolve_and_sum.c:51-64): output j of the lane (sample
 // k = 4 lane + j) takes  o_j = fma(h_t, W[j + t], o_j), t = 0..7 in order, but only where k > p (the reference starts at
 // i = 0, i.e. k = p + 1).  The live lanes of output j are a wave-uniform suffix of the wave, so the four guards are four
@@ -797,30 +155,6 @@ struct Staged {
     float edge;   // NSEG > 1: lanes 0..2 hold s[4q-3 .. 4q-1] of the segment's first quad, lane 63 holds s[4q+4] of its last
 };
 
-// Write the NC shifted copies of a segment: copy c holds the row shifted right by c samples, i.e. its aligned
-// quad i is (x[4i-c], ..., x[4i-c+3]); (py, pz, pw) are x[4q-3 .. 4q-1] (previous lane, or the segment edge).
-// NC = 4 serves 16-byte reads at any delay (the FIR flavours' ds_read_b128), NC = 2 the 8-byte reads of pad / lerp.
-template <int NC>
-__device__ __forceinline__ void write_copies(float* row0, int rs, int col, int lane, float4 v, float py, float pz, float pw)
-{
-    float4* q0 = reinterpret_cast<float4*>(row0 + 0 * rs + col) + lane;
-    float4* q1 = reinterpret_cast<float4*>(row0 + 1 * rs + col) + lane;
-    *q0 = v;
-    *q1 = make_float4(pw, v.x, v.y, v.z);
-    if constexpr (NC == 4) {
-        float4* q2 = reinterpret_cast<float4*>(row0 + 2 * rs + col) + lane;
-        float4* q3 = reinterpret_cast<float4*>(row0 + 3 * rs + col) + lane;
-        *q2 = make_float4(pz, pw, v.x, v.y);
-        *q3 = make_float4(py, pz, pw, v.x);
-    }
-}
-
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// The quad (two register pairs) of one 256-sample segment of a staged mic row, and of its difference row for lerp.
-struct Quad { f32x2 lo, hi; };
 
 // (Re)load the NSEG quads of a mic for LDS byte offset `e` -- unless `e` equals the offset they were loaded for (`ep`):
 // a scalar compare and branch, no vector work and no wait when the quads are still valid; a reload waits for its reads,
@@ -1579,561 +913,7 @@ __global__ void __launch_bounds__(W * 64, 4) das_copies_kernel(BF_TABLE_PARAMS, 
 }
 
 
-// ==================================================================================================
-// Two frames per workgroup (pad, N <= 256, fixed row stride, mic count a multiple of 16, two or more frames; lerp runs
-// das_pair2_kernel below).
-//
-// The sweep above is bound by the number of instructions a SIMD issues, and per (direction, mic) step only 2 of them (pad) are
-// arithmetic: the rest -- table loads, the address, the offset tests, waits -- depends on the tables alone.  A wave that
-// carries its eight directions through TWO frames pays that part once per 4 packed operations.
-// Same layout as das_copies_kernel<pad, NSEG = 1, RS = kRs, W = 16> (two shifted copies), with the two frames' rows of a mic
-// next to each other: frame 1's quads sit kFoff bytes after frame 0's, an immediate offset off the same address.  16 mics x 2
-// frames per chunk; the 64 accumulator registers leave no room for quads in flight across a mic, so a mic's first quads are
-// read (and waited for) in place -- the other three waves of the SIMD cover that.
-// Mic order and operation order per frame are those of the one-frame kernel: bit-identical maps.
-struct PairGeo {
-    static constexpr int kC = 2, kRs = Geo<1>::kRs, kLead = Geo<1>::kLead;
-    static constexpr int kSlot = kC * kRs;               // floats per staged (mic, frame)
-    static constexpr int kFoff = kSlot * 4;              // bytes from a frame-0 quad to the same quad of frame 1
-    static constexpr int kMc = 16;                       // mics per LDS image (the digest's slot count) ...
-    static constexpr int kHalf = 8;                      // ... swept and re-staged in halves of 8
-};
-
-#define BF_P_ACC(n, j, f) [a##n##0] "+v"(acc[j][f][0]), [a##n##1] "+v"(acc[j][f][1])
-// two direction steps x two frames; a0/a1 = step A frame 0/1, a2/a3 = step B frame 0/1
-#define BF_P_PAD_STEP(n0, n1)                                                                             \
-    "v_pk_add_f32 %[a" #n0 "0], %[a" #n0 "0], %[s0l]\n\tv_pk_add_f32 %[a" #n0 "1], %[a" #n0 "1], %[s0h]\n\t" \
-    "v_pk_add_f32 %[a" #n1 "0], %[a" #n1 "0], %[s1l]\n\tv_pk_add_f32 %[a" #n1 "1], %[a" #n1 "1], %[s1h]\n\t"
-#define BF_P_PAD_READ                                                                                     \
-    "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"                         \
-    "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\t"                 \
-    "s_waitcnt lgkmcnt(0)\n\t"
-#define BF_P_ADDR(e) "v_add_u32 %[ad], %[" #e "], %[lb]\n\t"
-#define BF_P_CHECK(n, ep, ec) "s_cmp_lg_u32 %[" #ec "], %[" #ep "]\n\ts_cbranch_scc1 .Lr" #n "_%=\n.Lb" #n "_%=:\n\t"
-#define BF_P_STUB(n, ec, READ) ".Lr" #n "_%=:\n\t" BF_P_ADDR(ec) READ "s_branch .Lb" #n "_%=\n"
-
-// Direction steps 0 and 1 of a mic for both frames: the mic's first quads are read in place (offset eb) before step 0, step 1
-// tests eb -> ec first.
-__device__ __forceinline__ void pair_pad_first(f32x2 (&acc)[8][2][2], Quad& S0, Quad& S1, int eb, int ec, int lbase)
-{
-    using G = PairGeo;
-    int ad;
-    // pad_and_sum.c:41-47   out[k] += s[k - p]
-    // (step 0: each frame's adds wait only for that frame's two reads -- LDS returns in order)
-    asm volatile(BF_P_ADDR(eb)
-                 "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"
-                 "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\ts_waitcnt lgkmcnt(2)\n\t"
-                 "v_pk_add_f32 %[a00], %[a00], %[s0l]\n\tv_pk_add_f32 %[a01], %[a01], %[s0h]\n\ts_waitcnt lgkmcnt(0)\n\t"
-                 "v_pk_add_f32 %[a10], %[a10], %[s1l]\n\tv_pk_add_f32 %[a11], %[a11], %[s1h]\n\t"
-                 BF_P_CHECK(1, eb, ec) BF_P_PAD_STEP(2, 3)
-                 ".subsection 1\n" BF_P_STUB(1, ec, BF_P_PAD_READ) "\t.subsection 0"
-                 // (the quads are pure outputs here: as in-out operands they are carried around the mic loop -- and copied at its back-edge)
-                 : BF_P_ACC(0, 0, 0), BF_P_ACC(1, 0, 1), BF_P_ACC(2, 1, 0), BF_P_ACC(3, 1, 1), [s0l] "=&v"(S0.lo), [s0h] "=&v"(S0.hi),
-                   [s1l] "=&v"(S1.lo), [s1h] "=&v"(S1.hi), [ad] "=&v"(ad)
-                 : [eb] "s"(eb), [ec] "s"(ec), [lb] "v"(lbase), [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8) : "scc");
-}
-
-// pad, direction steps 2..7 of a mic for both frames as ONE statement (between two statements the hazard recogniser puts an s_nop:
-// three issue slots per mic with one statement per pair of steps).
-__device__ __forceinline__ void pair_pad_rest(f32x2 (&acc)[8][2][2], Quad& S0, Quad& S1, const int (&e)[8], int lbase)
-{
-    using G = PairGeo;
-    int ad;
-#define BF_P_ACC2(n, j) [a##n##0] "+v"(acc[j][0][0]), [a##n##1] "+v"(acc[j][0][1]), [b##n##0] "+v"(acc[j][1][0]), [b##n##1] "+v"(acc[j][1][1])
-#define BF_P_PAD1(n) "v_pk_add_f32 %[a" #n "0], %[a" #n "0], %[s0l]\n\tv_pk_add_f32 %[a" #n "1], %[a" #n "1], %[s0h]\n\t" \
-                     "v_pk_add_f32 %[b" #n "0], %[b" #n "0], %[s1l]\n\tv_pk_add_f32 %[b" #n "1], %[b" #n "1], %[s1h]\n\t"
-    asm volatile(BF_P_CHECK(2, e1, e2) BF_P_PAD1(2) BF_P_CHECK(3, e2, e3) BF_P_PAD1(3) BF_P_CHECK(4, e3, e4) BF_P_PAD1(4)
-                 BF_P_CHECK(5, e4, e5) BF_P_PAD1(5) BF_P_CHECK(6, e5, e6) BF_P_PAD1(6) BF_P_CHECK(7, e6, e7) BF_P_PAD1(7)
-                 ".subsection 1\n" BF_P_STUB(2, e2, BF_P_PAD_READ) BF_P_STUB(3, e3, BF_P_PAD_READ) BF_P_STUB(4, e4, BF_P_PAD_READ)
-                 BF_P_STUB(5, e5, BF_P_PAD_READ) BF_P_STUB(6, e6, BF_P_PAD_READ) BF_P_STUB(7, e7, BF_P_PAD_READ) "\t.subsection 0"
-                 : BF_P_ACC2(2, 2), BF_P_ACC2(3, 3), BF_P_ACC2(4, 4), BF_P_ACC2(5, 5), BF_P_ACC2(6, 6), BF_P_ACC2(7, 7),
-                   [s0l] "+v"(S0.lo), [s0h] "+v"(S0.hi), [s1l] "+v"(S1.lo), [s1h] "+v"(S1.hi), [ad] "=&v"(ad)
-                 : [e1] "s"(e[1]), [e2] "s"(e[2]), [e3] "s"(e[3]), [e4] "s"(e[4]), [e5] "s"(e[5]), [e6] "s"(e[6]), [e7] "s"(e[7]), [lb] "v"(lbase),
-                   [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8)
-                 : "scc");
-#undef BF_P_ACC2
-#undef BF_P_PAD1
-}
-
-// Profiling build only (-DBF_STAMPS, scripts/dev/phase_stamps.py): every wave sums the time it spends in each phase of
-// das_pair_kernel / das_pair2_kernel (s_memtime at the phase boundaries, which are barrier neighbours anyway) and adds the totals to
-// g_stamps[phase] when its workgroup ends.  BF_STAMP(k) closes the phase that was running and charges it to slot k:
-//   0 sweep  1 wait (chunk free)  2 staging  3 wait (chunk staged)  4 wait (power: rows free)  5 parking  6 wait (rows parked)  7 ordered sum
-#ifdef BF_STAMPS
-__device__ unsigned long long g_stamps[64 * 16];         // (sums over all waves, in 64 replicas picked by workgroup id: nine atomics per wave on one
-                                                         //  line would make the flush longer than the kernel)
-#define BF_STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_prev = __builtin_amdgcn_s_memtime();
-#define BF_STAMP(k) do { const unsigned long long st_now = __builtin_amdgcn_s_memtime(); st_acc[k] += st_now - st_prev; st_prev = st_now; } while (0)
-#define BF_STAMP_FLUSH do { if (lane == 0) { unsigned long long* gs = g_stamps + 16 * (blockIdx.x & 63); for (int i = 0; i < 8; ++i) atomicAdd(&gs[i], st_acc[i]); atomicAdd(&gs[8], 1ull); } } while (0)
-#else
-#define BF_STAMP_DECL
-#define BF_STAMP(k)
-#define BF_STAMP_FLUSH
-#endif
-
-template <int ALGO>   // (pad only: the parameter keeps the kernel's symbol, which the profiles and ISA checks name)
-__global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArgs a)
-{
-    static_assert(ALGO == ALGO_PAD, "das_pair_kernel: pad (lerp runs das_pair2_kernel)");
-    using G = PairGeo;
-    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    int tile, fpair;
-    tile_and_frame(a, &tile, &fpair);
-    const int f0 = 2 * fpair;
-    const bool two = f0 + 1 < a.n_frames;                      // an odd frame count: the last workgroup row computes its frame twice
-    const int f1 = two ? f0 + 1 : f0;
-    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
-    if (tile_begin >= a.dir_end) return;
-    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
-    const int M = a.n_mics, N = a.n_samples;                   // M % 16 == 0, N % 4 == 0, N <= 256 (plan_das)
-    const int n_half = M / HC;                                  // half chunks of 8 mics
-    const float* __restrict__ sig0 = signals + (size_t)f0 * a.m_total * N;
-    const float* __restrict__ sig1 = signals + (size_t)f1 * a.m_total * N;
-    float* __restrict__ img0 = images + (size_t)f0 * a.image_stride;
-    float* __restrict__ img1 = images + (size_t)f1 * a.image_stride;
-    const int32_t* __restrict__ dig = reinterpret_cast<const int32_t*>(taps);   // the digest rides in the unused `taps` slot
-
-    // The LDS image is the 16-mic chunk the digest was built for (mic m -> slot m % 16), used as TWO halves of 8 mics: while
-    // the waves sweep half h, each of them also writes its row of half h + 1 into the other half -- ONE barrier per 8 mics,
-    // and the staging stores (slow: 13 cycles per ds_write_b128 and wave on the LDS store path) run under other waves' adds
-    // instead of between two barriers with every SIMD idle.
-    // This wave stages row `wave` of every half: mic (wave >> 1) of the half, frame (wave & 1).
-    // Lane c holds half c's mic id (first 64 halves): the per-half prefetch is then one independent load.
-    const int vmic = (lane < n_half) ? mics[lane * HC + (wave >> 1)] : 0;
-    auto fetch = [&](int h) -> float4 {
-        const int mic = (h < kWave) ? __builtin_amdgcn_readlane(vmic, h) : mics[h * HC + (wave >> 1)];
-        const float* src = ((wave & 1) ? sig1 : sig0) + (size_t)mic * N;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (4 * lane < N) v = *reinterpret_cast<const float4*>(src + 4 * lane);
-        return v;
-    };
-    auto stage = [&](int h, const float4 v, bool wipe) {
-        float* row0 = lds + (((h & 1) * W) + wave) * G::kSlot;  // slot (h & 1) * 8 + (wave >> 1), frame wave & 1
-        const float py = dpp_prev(v.y), pz = dpp_prev(v.z), pw = dpp_prev(v.w);
-        write_copies<C>(row0, RS, LEAD, lane, v, py, pz, pw);
-        if (wipe) {
-            // the zero prefix: nothing but the parked rows of the power pass ever overwrites it, so only a group's first
-            // visit of a half restores it -- one store: lane -> (copy row lane / 14, quad lane % 14) of the C rows
-            static_assert((LEAD >> 2) * C <= kWave, "one lane per prefix quad");
-            constexpr int PQ = LEAD >> 2;
-            if (lane < PQ * C) reinterpret_cast<float4*>(row0 + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-
-    float4 st = fetch(0);
-    const int lb = 16 * lane + (int)(unsigned)(size_t)((__attribute__((address_space(3))) char*)lds);
-    BF_STAMP_DECL
-
-    for (int g0 = tile_begin; g0 < tile_end; g0 += kGroup) {
-        f32x2 acc[DW][2][2];
-#pragma unroll
-        for (int j = 0; j < DW; ++j)
-#pragma unroll
-            for (int f = 0; f < 2; ++f) { acc[j][f][0] = f32x2{0.0f, 0.0f}; acc[j][f][1] = f32x2{0.0f, 0.0f}; }
-
-        BF_STAMP(7);
-        __syncthreads();   // the previous group's parked rows have been summed
-        BF_STAMP(1);
-        stage(0, st, true);
-        st = fetch(1);
-        BF_STAMP(2);
-        __syncthreads();
-        BF_STAMP(3);
-
-        for (int h = 0; h < n_half; ++h) {
-            if (h + 1 < n_half) {
-                stage(h + 1, st, h == 0);                       // into the half whose sweeps ended before the last barrier
-                // request what is staged an iteration from now: half h + 2, or the next group's first half (the same rows)
-                if (h + 2 < n_half) st = fetch(h + 2);
-                else if (g0 + kGroup < tile_end) st = fetch(0);
-                BF_STAMP(2);
-            }
-            const int dw0 = g0 + wave * DW;                     // wave-uniform
-            if (dw0 < tile_end) {
-                const size_t grp = (size_t)(dw0 - a.dir_begin) / DW;
-                const int32_t* __restrict__ et = dig + (grp * M + (size_t)h * HC) * DW;
-                struct Entries { int e[DW]; };
-                auto request = [&](Entries& t, int m) {
-                    // (reads past the half's last mic stay inside the slack-padded table and are dropped)
-#pragma unroll
-                    for (int j = 0; j < DW; ++j) t.e[j] = et[m * DW + j];
-                };
-                Entries E[3];
-                Quad S0, S1;
-                S0.lo = S0.hi = S1.lo = S1.hi = f32x2{0.0f, 0.0f};
-                request(E[0], 0);
-                request(E[1], 1);
-                auto mic = [&](int m, auto kc) {
-                    constexpr int K = decltype(kc)::value, K2 = (K + 2) % 3;
-                    const Entries& cur = E[K];
-                    pair_pad_first(acc, S0, S1, cur.e[0], cur.e[1], lb);
-                    request(E[K2], m + 2);      // after the first statement's wait, so that it does not sit on these loads
-                    pair_pad_rest(acc, S0, S1, cur.e, lb);
-                };
-                using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-                static_assert(HC == 8, "eight mics: two trips of three and two more");
-#pragma unroll 1
-                for (int t = 0; t < 2; ++t) {
-                    mic(0, I0{}); mic(1, I1{}); mic(2, I2{});
-                    et += 3 * DW;
-                }
-                mic(0, I0{});
-                mic(1, I1{});
-            }
-            BF_STAMP(0);       // sweep -> waiting for the others
-            __syncthreads();   // half h is free, half h + 1 is staged
-            BF_STAMP(h + 1 < n_half ? 3 : 4);
-        }
-
-        // ---- k-ordered mean power (pad_and_sum.c:120-128), one frame at a time: the 16 waves park the squared means of their
-        // directions (row = direction; the rows alias the chunk buffer), then one direction per lane runs the sequential sum.
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            if (f == 1) {
-                __syncthreads();        // frame 0's rows have been summed
-                BF_STAMP(4);
-            }
-            auto park = [&](auto mul_c) {
-#pragma unroll
-                for (int j = 0; j < DW; ++j) {
-                    float* row = lds + (wave * DW + j) * kPark;
-                    const f32x2 a0 = acc[j][f][0], a1 = acc[j][f][1];
-                    float o0, o1, o2, o3;
-                    if constexpr (decltype(mul_c)::value) {
-                        o0 = a0.x * a.inv_n; o1 = a0.y * a.inv_n; o2 = a1.x * a.inv_n; o3 = a1.y * a.inv_n;
-                    } else {
-                        float fm = (float)M;
-                        asm volatile("" : "+v"(fm));   // not speculatable: keeps this path behind its branch
-                        o0 = a0.x / fm; o1 = a0.y / fm; o2 = a1.x / fm; o3 = a1.y / fm;
-                    }
-                    reinterpret_cast<float4*>(row)[lane] = make_float4(o0 * o0, o1 * o1, o2 * o2, o3 * o3);
-                }
-            };
-            if (__builtin_expect(a.n_is_pow2, 1)) park(std::true_type{}); else park(std::false_type{});
-            BF_STAMP(5);                // -> waiting
-            __syncthreads();
-            BF_STAMP(6);                // -> ordered sum (two waves; the others go on to the next barrier)
-            const int g = wave * kWave + lane;            // parked row of this lane
-            const int d = g0 + g;
-            if (g < kGroup && d < tile_end && (f == 0 || two)) {
-                // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
-                const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
-                const float* row = lds + g * kPark;
-                const float4* row4 = reinterpret_cast<const float4*>(row);
-                float sum = 0.0f;
-                int k = 0;
-                for (; k + 32 <= N; k += 32) {
-                    float4 v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = row4[(k >> 2) + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
-                }
-                for (; k < N; ++k) sum += row[k];
-                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
-            }
-        }
-    }
-    BF_STAMP(7);
-    BF_STAMP_FLUSH;
-}
-#undef BF_P_ACC
-#undef BF_P_PAD_STEP
-#undef BF_P_PAD_READ
-#undef BF_P_ADDR
-#undef BF_P_CHECK
-#undef BF_P_STUB
-
-// ==================================================================================================
-// Two frames per workgroup, frames INTERLEAVED sample by sample in the LDS rows (lerp, N <= 256; das_pair_kernel's successor).
-//
-// Every instruction costs a SIMD a quad-cycle, so what is left to gain on the sweep is instruction count.  With the
-// row of a mic holding (f0 s0, f1 s0, f0 s1, f1 s1, ..):
-//   * one ds_read_b128 brings two samples of BOTH frames: a (re)load is 4 LDS instructions instead of 8, and with lane l owning
-//     the sample pairs (2l, 2l+1) and (128+2l, 128+2l+1) every read covers 1 KiB of contiguous LDS (no bank conflicts; the
-//     16-byte lane stride of ds_read_b64 pairs was a two-way conflict on every read);
-//   * a register pair is (frame 0, frame 1) of one sample, so the packed operations are the same 8 per direction step, the
-//     lerp weight still one scalar operand for both lanes;
-//   * the quads live in HARD-WIRED registers v[96:111] (+ products v[112:119], address v120), named as clobbers: 16-byte reads
-//     need 4-register tuples whose halves the packed operations address, which inline-asm operands cannot express.  A mic is
-//     two statements -- S1: address, reads, wait, step 0;  S2: steps 1..7 with their tests and out-of-line re-reads -- and the
-//     quads must survive from S1 to S2 across the table requests the compiler places between them (scalar instructions only;
-//     tests/test_isa_hazards.py checks that nothing between the two markers touches a vector register).
-// Halves of 8 mics staged under the sweep, power pass, digest: as das_pair_kernel (digest offsets scaled for the 2-float samples).
-// (pad, which reads half as much to begin with, measured 2 % slower on interleaved rows: it runs das_pair_kernel)
-struct Pair2Geo {
-    static constexpr int kC = 2, kLead = Geo<1>::kLead, kRs = 2 * Geo<1>::kRs, kMc = 16, kHalf = 8;
-    static constexpr int kSlot = 2 * kC * kRs;           // floats per staged mic (both frames): samples and differences
-    static constexpr int kDoff = kC * kRs * 4;           // bytes from a sample quad to its difference quad
-};
-
-#define BF_I_ACC(n, j) [a##n##0] "+v"(acc[j][0]), [a##n##1] "+v"(acc[j][1]), [a##n##2] "+v"(acc[j][2]), [a##n##3] "+v"(acc[j][3])
-#define BF_I_READ                                                                                   \
-    "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[100:103], v120 offset:1024\n\t"                   \
-    "ds_read_b128 v[104:107], v120 offset:%[g0]\n\tds_read_b128 v[108:111], v120 offset:%[g1]\n\ts_waitcnt lgkmcnt(0)\n\t"
-#define BF_I_STEP(n, h, mods)                                                                       \
-    "v_pk_fma_f32 v[112:113], %[" #h "], v[104:105], v[96:97] " mods "\n\tv_pk_fma_f32 v[114:115], %[" #h "], v[106:107], v[98:99] " mods "\n\t" \
-    "v_pk_fma_f32 v[116:117], %[" #h "], v[108:109], v[100:101] " mods "\n\tv_pk_fma_f32 v[118:119], %[" #h "], v[110:111], v[102:103] " mods "\n\t" \
-    "v_pk_add_f32 %[a" #n "0], %[a" #n "0], v[112:113]\n\tv_pk_add_f32 %[a" #n "1], %[a" #n "1], v[114:115]\n\t" \
-    "v_pk_add_f32 %[a" #n "2], %[a" #n "2], v[116:117]\n\tv_pk_add_f32 %[a" #n "3], %[a" #n "3], v[118:119]\n\t"
-// A mic's first reads with direction step 0 behind them, each half of the step waiting only for its own reads (LDS returns in order;
-// a counted wait bounds the outstanding operations of any kind, hence the outstanding reads).
-#define BF_I_FIRST(h, mods)                                                                         \
-    "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[104:107], v120 offset:%[g0]\n\t"                \
-    "ds_read_b128 v[100:103], v120 offset:1024\n\tds_read_b128 v[108:111], v120 offset:%[g1]\n\ts_waitcnt lgkmcnt(2)\n\t" \
-    "v_pk_fma_f32 v[112:113], %[" #h "], v[104:105], v[96:97] " mods "\n\tv_pk_fma_f32 v[114:115], %[" #h "], v[106:107], v[98:99] " mods "\n\t" \
-    "v_pk_add_f32 %[a00], %[a00], v[112:113]\n\tv_pk_add_f32 %[a01], %[a01], v[114:115]\n\ts_waitcnt lgkmcnt(0)\n\t" \
-    "v_pk_fma_f32 v[116:117], %[" #h "], v[108:109], v[100:101] " mods "\n\tv_pk_fma_f32 v[118:119], %[" #h "], v[110:111], v[102:103] " mods "\n\t" \
-    "v_pk_add_f32 %[a02], %[a02], v[116:117]\n\tv_pk_add_f32 %[a03], %[a03], v[118:119]\n\t"
-#define BF_I_EVEN "op_sel_hi:[0,1,1]"
-#define BF_I_ODD "op_sel:[1,0,0] op_sel_hi:[1,1,1]"
-#define BF_I_CHECK(n, ep, ec) "s_cmp_lg_u32 %[" #ec "], %[" #ep "]\n\ts_cbranch_scc1 .Lr" #n "_%=\n.Lb" #n "_%=:\n\t"
-#define BF_I_STUB(n, ec) ".Lr" #n "_%=:\n\tv_add_u32 v120, %[" #ec "], %[lb]\n\t" BF_I_READ "s_branch .Lb" #n "_%=\n"
-#define BF_I_CLOB "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", \
-                  "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120"
-
-// S1: a mic's first quads, read in place, and direction step 0
-// lerp_and_sum.c:50-56  out[k] += s[i] + h * (s[i+1] - s[i]),  i = k - p - 1   (gcc contracts it into one fma)
-__device__ __forceinline__ void pair2_first(f32x2 (&acc)[8][4], int e0, unsigned long long h01, int lbase)
-{
-    using G = Pair2Geo;
-    asm volatile("v_add_u32 v120, %[e0], %[lb]\n\t" BF_I_FIRST(h01, BF_I_EVEN) ";BF_S1_END"
-                 : BF_I_ACC(0, 0) : [e0] "s"(e0), [h01] "s"(h01), [lb] "v"(lbase), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024) : BF_I_CLOB);
-}
-// S2: direction steps 1..7, each behind the test of its LDS offset against the previous step's
-__device__ __forceinline__ void pair2_rest(f32x2 (&acc)[8][4], const int (&e)[8], const unsigned long long (&hp)[4], int lbase)
-{
-    using G = Pair2Geo;
-    asm volatile(";BF_S2_BEGIN\n\t"
-                 BF_I_CHECK(1, e0, e1) BF_I_STEP(1, h01, BF_I_ODD) BF_I_CHECK(2, e1, e2) BF_I_STEP(2, h23, BF_I_EVEN)
-                 BF_I_CHECK(3, e2, e3) BF_I_STEP(3, h23, BF_I_ODD) BF_I_CHECK(4, e3, e4) BF_I_STEP(4, h45, BF_I_EVEN)
-                 BF_I_CHECK(5, e4, e5) BF_I_STEP(5, h45, BF_I_ODD) BF_I_CHECK(6, e5, e6) BF_I_STEP(6, h67, BF_I_EVEN)
-                 BF_I_CHECK(7, e6, e7) BF_I_STEP(7, h67, BF_I_ODD)
-                 ".subsection 1\n" BF_I_STUB(1, e1) BF_I_STUB(2, e2) BF_I_STUB(3, e3) BF_I_STUB(4, e4) BF_I_STUB(5, e5) BF_I_STUB(6, e6) BF_I_STUB(7, e7)
-                 "\t.subsection 0"
-                 : BF_I_ACC(1, 1), BF_I_ACC(2, 2), BF_I_ACC(3, 3), BF_I_ACC(4, 4), BF_I_ACC(5, 5), BF_I_ACC(6, 6), BF_I_ACC(7, 7)
-                 : [e0] "s"(e[0]), [e1] "s"(e[1]), [e2] "s"(e[2]), [e3] "s"(e[3]), [e4] "s"(e[4]), [e5] "s"(e[5]), [e6] "s"(e[6]), [e7] "s"(e[7]), [lb] "v"(lbase),
-                   [h01] "s"(hp[0]), [h23] "s"(hp[1]), [h45] "s"(hp[2]), [h67] "s"(hp[3]), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024)
-                 : "scc", BF_I_CLOB);
-}
-#undef BF_I_ACC
-#undef BF_I_READ
-#undef BF_I_FIRST
-#undef BF_I_STEP
-#undef BF_I_EVEN
-#undef BF_I_ODD
-#undef BF_I_CHECK
-#undef BF_I_STUB
-#undef BF_I_CLOB
-
-template <int ALGO>   // (lerp only: the parameter keeps the kernel's symbol, which the profiles and ISA checks name)
-__global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KArgs a)
-{
-    static_assert(ALGO == ALGO_LERP, "das_pair2_kernel: lerp (pad runs das_pair_kernel)");
-    using G = Pair2Geo;
-    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane_ = threadIdx.x & (kWave - 1), lane = lane_;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    int tile, fpair;
-    tile_and_frame(a, &tile, &fpair);
-    const int f0 = 2 * fpair;
-    const bool two = f0 + 1 < a.n_frames;                      // an odd frame count: the last workgroup row computes its frame twice
-    const int f1 = two ? f0 + 1 : f0;
-    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
-    if (tile_begin >= a.dir_end) return;
-    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
-    const int M = a.n_mics, N = a.n_samples;                   // M % 16 == 0, N % 4 == 0, N <= 256 (plan_das)
-    const int n_half = M / HC;
-    const float* __restrict__ sig0 = signals + (size_t)f0 * a.m_total * N;
-    const float* __restrict__ sig1 = signals + (size_t)f1 * a.m_total * N;
-    float* __restrict__ img0 = images + (size_t)f0 * a.image_stride;
-    float* __restrict__ img1 = images + (size_t)f1 * a.image_stride;
-    const int32_t* __restrict__ dig = reinterpret_cast<const int32_t*>(taps);   // the digest rides in the unused `taps` slot
-
-    // Staging: waves w and w + 8 share mic (w & 7) of every half (both fetch its two frames): part 0 writes the sample rows, part 1
-    // the difference rows.  Lane c holds half c's mic id (first 64 halves).
-    const int my_mic = wave & 7, part = wave >> 3;
-    const int vmic = (lane < n_half) ? mics[lane * HC + my_mic] : 0;
-    struct Staged2 { float4 v0, v1; };
-    auto fetch = [&](int h) -> Staged2 {
-        const int mic = (h < kWave) ? __builtin_amdgcn_readlane(vmic, h) : mics[h * HC + my_mic];
-        Staged2 st;
-        st.v0 = make_float4(0.f, 0.f, 0.f, 0.f);
-        st.v1 = st.v0;
-        if (4 * lane < N) {
-            // scalar row base + one 32-bit lane offset (global_load saddr form): the per-lane 64-bit pointers of the two frames, hoisted out
-            // of the group loop, used to be spilled around the sweep (16 bytes of scratch per lane, stored once per workgroup and
-            // reloaded per group: WRITE_SIZE 5x the image bytes)
-            unsigned voff = 16u * (unsigned)lane;
-            asm volatile("" : "+v"(voff));                      // (opaque: or hipcc folds it back into two hoisted 64-bit lane pointers)
-            const char* r0 = reinterpret_cast<const char*>(sig0 + (size_t)mic * N);
-            const char* r1 = reinterpret_cast<const char*>(sig1 + (size_t)mic * N);
-            st.v0 = *reinterpret_cast<const float4*>(r0 + voff);
-            st.v1 = *reinterpret_cast<const float4*>(r1 + voff);
-        }
-        return st;
-    };
-    // rows of a mic: [s copy 0][s copy 1][d copy 0][d copy 1]; copy c holds sample i - c at position i; position i = floats 2 i, 2 i + 1
-    auto write_row = [&](float* row, const float4 x0, const float4 x1, float p0, float p1, bool shifted, int lane) {
-        float4* q = reinterpret_cast<float4*>(row + 2 * LEAD) + 2 * lane;
-        if (!shifted) {
-            q[0] = make_float4(x0.x, x1.x, x0.y, x1.y);
-            q[1] = make_float4(x0.z, x1.z, x0.w, x1.w);
-        } else {
-            q[0] = make_float4(p0, p1, x0.x, x1.x);
-            q[1] = make_float4(x0.y, x1.y, x0.z, x1.z);
-        }
-    };
-    auto stage = [&](int h, const Staged2& st, bool wipe) {
-        int lane = lane_;                                       // (opaque copy: the per-lane addresses are recomputed here, not hoisted)
-        asm volatile("" : "+v"(lane));
-        float* slot = lds + ((h & 1) * HC + my_mic) * G::kSlot;
-        float4 x0 = st.v0, x1 = st.v1;
-        float* rows = slot + part * C * RS;                     // the two rows this wave writes
-        if (part == 1) {
-            // D[i] = s[i+1] - s[i], the reference's own subtraction (lerp_and_sum.c:54); D[-1] stays 0 (prefix)
-            const float n0 = dpp_next(x0.x), n1 = dpp_next(x1.x);
-            x0 = make_float4(x0.y - x0.x, x0.z - x0.y, x0.w - x0.z, n0 - x0.w);
-            x1 = make_float4(x1.y - x1.x, x1.z - x1.y, x1.w - x1.z, n1 - x1.w);
-        }
-        const float p0 = dpp_prev(x0.w), p1 = dpp_prev(x1.w);   // the previous lane's last sample (0 in lane 0: the prefix)
-        write_row(rows, x0, x1, p0, p1, false, lane);
-        write_row(rows + RS, x0, x1, p0, p1, true, lane);
-        if (wipe) {
-            // the zero prefix (56 samples x 2 frames = 28 quads per row): only the parked rows of the power pass overwrite it
-            constexpr int PQ = LEAD >> 1;
-            static_assert(2 * PQ <= kWave, "one lane per prefix quad of two rows");
-            if (lane < 2 * PQ) reinterpret_cast<float4*>(rows + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-
-    BF_STAMP_DECL
-    Staged2 st = fetch(0);
-    const int lb = 16 * lane + (int)(unsigned)(size_t)((__attribute__((address_space(3))) char*)lds);
-
-    for (int g0 = tile_begin; g0 < tile_end; g0 += kGroup) {
-        f32x2 acc[DW][4];                                       // (frame 0, frame 1) of samples 2l, 2l+1, 128+2l, 128+2l+1
-#pragma unroll
-        for (int j = 0; j < DW; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[j][q] = f32x2{0.0f, 0.0f};
-
-        BF_STAMP(7);
-        __syncthreads();   // the previous group's parked rows have been summed
-        BF_STAMP(1);
-        stage(0, st, true);
-        st = fetch(1 % n_half);
-        BF_STAMP(2);
-        __syncthreads();
-        BF_STAMP(3);
-
-        const int dw0 = g0 + wave * DW;                         // wave-uniform
-        const bool busy = dw0 < tile_end;
-        const size_t grp = busy ? (size_t)(dw0 - a.dir_begin) / DW : 0;
-        for (int h = 0; h < n_half; ++h) {
-            if (h + 1 < n_half) {
-                stage(h + 1, st, h == 0);                       // into the half whose sweeps ended before the last barrier
-                if (h + 2 < n_half) st = fetch(h + 2);
-                else if (g0 + kGroup < tile_end) st = fetch(0);
-                BF_STAMP(2);
-            }
-            if (busy) {
-                const int32_t* __restrict__ et = dig + (grp * M + (size_t)h * HC) * DW;
-                const float* __restrict__ ht = reinterpret_cast<const float*>(dig) + a.digest_h_off + (grp * M + (size_t)h * HC) * DW;
-                struct Entries { int e[DW]; unsigned long long hp[DW / 2]; };
-                auto request = [&](Entries& t, int m) {
-                    // (reads past the half's last mic stay inside the slack-padded table and are dropped)
-#pragma unroll
-                    for (int j = 0; j < DW; ++j) t.e[j] = et[m * DW + j];
-#pragma unroll
-                    for (int j = 0; j < DW / 2; ++j) t.hp[j] = *reinterpret_cast<const unsigned long long*>(ht + m * DW + 2 * j);
-                };
-                Entries E[3];
-                request(E[0], 0);
-                request(E[1], 1);
-                auto mic = [&](int m, auto kc) {
-                    constexpr int K = decltype(kc)::value, K2 = (K + 2) % 3;
-                    const Entries& cur = E[K];
-                    pair2_first(acc, cur.e[0], cur.hp[0], lb);
-                    request(E[K2], m + 2);      // after the first statement's wait, so that it does not sit on these loads
-                    pair2_rest(acc, cur.e, cur.hp, lb);
-                };
-                using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-                static_assert(HC == 8, "eight mics: two trips of three and two more");
-#pragma unroll 1
-                for (int t = 0; t < 2; ++t) {
-                    mic(0, I0{}); mic(1, I1{}); mic(2, I2{});
-                    et += 3 * DW; ht += 3 * DW;
-                }
-                mic(0, I0{});
-                mic(1, I1{});
-                __builtin_amdgcn_s_waitcnt(0xC07F);             // the entries requested past the half's end have landed (and are dropped)
-            }
-            BF_STAMP(0);       // sweep -> waiting for the others
-            __syncthreads();   // half h is free, half h + 1 is staged
-            BF_STAMP(h + 1 < n_half ? 3 : 4);
-        }
-
-        // ---- k-ordered mean power (pad_and_sum.c:120-128), one frame at a time: the 16 waves park the squared means of their
-        // directions (row = direction, k in order; the rows alias the LDS image), then one direction per lane runs the sequential sum.
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            if (f == 1) {
-                __syncthreads();        // frame 0's rows have been summed
-                BF_STAMP(4);
-            }
-            auto park = [&](auto mul_c) __attribute__((always_inline)) {
-#pragma unroll
-                for (int j = 0; j < DW; ++j) {
-                    float* row = lds + (wave * DW + j) * kPark;
-                    const float x0 = f == 0 ? acc[j][0].x : acc[j][0].y, x1 = f == 0 ? acc[j][1].x : acc[j][1].y;
-                    const float x2 = f == 0 ? acc[j][2].x : acc[j][2].y, x3 = f == 0 ? acc[j][3].x : acc[j][3].y;
-                    float o0, o1, o2, o3;
-                    if constexpr (decltype(mul_c)::value) {
-                        o0 = x0 * a.inv_n; o1 = x1 * a.inv_n; o2 = x2 * a.inv_n; o3 = x3 * a.inv_n;
-                    } else {
-                        float fm = (float)M;
-                        asm volatile("" : "+v"(fm));   // not speculatable: keeps this path behind its branch
-                        o0 = x0 / fm; o1 = x1 / fm; o2 = x2 / fm; o3 = x3 / fm;
-                    }
-                    reinterpret_cast<float2*>(row)[lane] = make_float2(o0 * o0, o1 * o1);             // samples 2l, 2l+1
-                    reinterpret_cast<float2*>(row + 128)[lane] = make_float2(o2 * o2, o3 * o3);       // samples 128+2l, 128+2l+1
-                }
-            };
-            if (__builtin_expect(a.n_is_pow2, 1)) park(std::true_type{}); else park(std::false_type{});
-            BF_STAMP(5);                // -> waiting
-            __syncthreads();
-            BF_STAMP(6);                // -> ordered sum (two waves; the others go on to the next barrier)
-            int lane_o = lane;                            // (opaque: keeps the per-lane row address out of the registers the sweep needs)
-            asm volatile("" : "+v"(lane_o));
-            const int g = wave * kWave + lane_o;          // parked row of this lane
-            const int d = g0 + g;
-            if (g < kGroup && d < tile_end && (f == 0 || two)) {
-                // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
-                const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
-                const float* row = lds + g * kPark;
-                const float4* row4 = reinterpret_cast<const float4*>(row);
-                float sum = 0.0f;
-                int k = 0;
-                for (; k + 32 <= N; k += 32) {
-                    float4 v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = row4[(k >> 2) + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
-                }
-                for (; k < N; ++k) sum += row[k];
-                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
-            }
-        }
-    }
-    BF_STAMP(7);
-    BF_STAMP_FLUSH;
-}
+// (two frames per workgroup, pad / lerp at N <= 256: das_pair_kernel / das_pair2_kernel, das_pair.hip)
 
 // ==================================================================================================
 // Hybrid beamformer (integer delay + 8-tap fractional FIR, hybrid_convolve_and_sum.c:51-121), two frames per workgroup.
@@ -2152,11 +932,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
 //   * interleaved rows need only TWO shifted copies for 16-byte-aligned window reads (the window start must fall on an even
 //     sample), so the LDS image holds 32 mics: two halves of 16, staged under the sweep as in das_pair_kernel.
 // Operation order per output is the reference's (taps 0..7 in order, mics in order): bit-identical maps.
-struct HybridGeo {
-    static constexpr int kC = 2, kLead = Geo<1>::kLead, kRs = 2 * Geo<1>::kRsFir;   // floats per row: two frames interleaved
-    static constexpr int kHalf = 16, kMc = 2 * kHalf;
-    static constexpr int kSlot = kC * kRs;               // floats per staged mic (both frames)
-};
+// (HybridGeo: das_geometry.h)
 
 // The guard of a (direction, mic): output j of a lane (sample 4 lane + j) is live on the lanes n_j .. 63 (four bytes of `ng`,
 // digest_grouped_kernel; n < 64 under the fixed row stride).  It depends on the whole-sample delay only -- like the window.
@@ -2726,12 +1502,7 @@ __device__ __forceinline__ void long_pad_rest(f32x2 (&acc)[Geo<NSEG>::kDw][NSEG]
 #undef BF_L_STUB
 #undef BF_L_CLOB
 
-template <int ALGO, int NSEG>
-struct LongGeo {
-    static constexpr bool kLerp = ALGO == ALGO_LERP;
-    static constexpr int kA = kLerp ? 2 : 1, kC = 2, kDw = Geo<NSEG>::kDw, kHalf = 16 / NSEG, kMc = 2 * kHalf;
-    static constexpr int kPark = Geo<NSEG>::kPark;
-};
+// (LongGeo: das_geometry.h)
 
 template <int ALGO, int NSEG, int RS>
 __global__ void __launch_bounds__(1024, 4) das_long_kernel(BF_TABLE_PARAMS, KArgs a)
@@ -2989,86 +1760,14 @@ __global__ void __launch_bounds__(1024, 4) das_long_kernel(BF_TABLE_PARAMS, KArg
 
 }  // namespace copies
 
-// The sweeps keep LDS reads in flight in hard-wired registers across asm statements: sound only in a build that does not spill
-// (tests/test_isa_hazards.py checks the build the tests run on; this checks the one that is about to launch).
-template <typename K>
-static hipError_t refuse_scratch(K kernel, int* cached)
-{
-    if (*cached < 0) {
-        hipFuncAttributes fa{};
-        hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
-        if (e != hipSuccess) return e;
-        *cached = (int)fa.localSizeBytes;
-    }
-#ifdef BF_STAMPS
-    return hipSuccess;              // (the profiling build's stamp registers may spill: its phase shares are read, never its images)
-#else
-    return *cached != 0 ? hipErrorInvalidDeviceFunction : hipSuccess;
-#endif
-}
-
-// Shifted-copies layout (plan.layout == 2): pad / lerp at NSEG = 1, 2, 4 segments of 256 samples, the 8-tap FIR flavours at NSEG = 1.
+// pad / lerp at NSEG = 1, 2, 4 segments of 256 samples, the 8-tap FIR flavours at NSEG = 1.
 template <int ALGO, int NSEG>
-hipError_t launch_copies(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
+hipError_t launch_copies_seg(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
 {
+    constexpr bool kFir = is_fir(ALGO);
+    const KArgs a = make_args(L, plan);
     const dim3 grid((unsigned)plan.n_tiles * (unsigned)frames);
     const dim3 block((unsigned)plan.waves * kWave);
-    constexpr bool kFir = ALGO == ALGO_HYBRID || ALGO == ALGO_FIR_NAIVE || ALGO == ALGO_FIR_VEC;
-    constexpr bool kNeedsDigest = ALGO != ALGO_FIR_NAIVE && ALGO != ALGO_FIR_VEC;
-    if (kNeedsDigest && L.tab.digest == nullptr) return hipErrorInvalidValue;   // launch_digest first
-    if (kFir && L.n_taps != 8) return hipErrorInvalidValue;
-    if constexpr (!kFir && NSEG == 1) {
-        if (plan.nf == 2) {                             // das_pair_kernel (pad) / das_pair2_kernel (lerp: frames interleaved in the rows)
-            constexpr bool kLerp = ALGO == ALGO_LERP;
-            using PG = std::conditional_t<kLerp, copies::Pair2Geo, copies::PairGeo>;
-            if (L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != PG::kMc || plan.row_stride != PG::kRs ||
-                plan.lead != PG::kLead || plan.interleaved != (kLerp ? 1 : 0) || (L.n_mics % 16) != 0)
-                return hipErrorInvalidValue;
-            auto kernel = [] { if constexpr (kLerp) return copies::das_pair2_kernel<ALGO>; else return copies::das_pair_kernel<ALGO>; }();
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-            if (e != hipSuccess) return e;
-            static int pair_scratch = -1;
-            if ((e = refuse_scratch(kernel, &pair_scratch)) != hipSuccess) return e;
-            const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
-            hipLaunchKernelGGL(kernel, pair_grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
-                               reinterpret_cast<const float*>(L.tab.digest), a);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (kFir) {
-        if (plan.nf == 2) {                             // das_hybrid_pair_kernel<hybrid | fir_naive | fir_vec>
-            using HG = copies::HybridGeo;
-            if (L.tab.digest == nullptr || plan.waves != copies::kWaves || plan.mic_chunk != HG::kMc || plan.row_stride != HG::kRs ||
-                plan.lead != HG::kLead || (L.n_mics % 16) != 0 || L.n_taps != 8)
-                return hipErrorInvalidValue;
-            auto kernel = copies::das_hybrid_pair_kernel<ALGO>;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-            if (e != hipSuccess) return e;
-            static int hybrid_scratch = -1;
-            if ((e = refuse_scratch(kernel, &hybrid_scratch)) != hipSuccess) return e;
-            const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
-            hipLaunchKernelGGL(kernel, pair_grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole,
-                               reinterpret_cast<const float*>(L.tab.digest), L.tab.taps, a);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (!kFir && (NSEG == 2 || NSEG == 4)) {
-        if (plan.long_rows) {                           // das_long_kernel
-            using LG = copies::LongGeo<ALGO, NSEG>;
-            if (L.tab.digest == nullptr || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != LG::kMc ||
-                (L.n_mics % LG::kHalf) != 0 || plan.dpw != LG::kDw)
-                return hipErrorInvalidValue;
-            const bool fixed_rs = plan.row_stride == (LG::kLerp ? 2 : 1) * copies::Geo<NSEG>::kRs && plan.lead == copies::Geo<NSEG>::kLead;
-            auto kernel = fixed_rs ? copies::das_long_kernel<ALGO, NSEG, copies::Geo<NSEG>::kRs> : copies::das_long_kernel<ALGO, NSEG, 0>;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-            if (e != hipSuccess) return e;
-            static int long_scratch[2] = {-1, -1};
-            if ((e = refuse_scratch(kernel, &long_scratch[fixed_rs ? 1 : 0])) != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
-                               reinterpret_cast<const float*>(L.tab.digest), a);
-            return hipGetLastError();
-        }
-    }
     using G = copies::Geo<NSEG>;
     constexpr int kRs = kFir ? G::kRsFir : G::kRs;
     const bool fixed = plan.row_stride == kRs && plan.lead == G::kLead;
@@ -3085,332 +1784,94 @@ hipError_t launch_copies(const DasLaunch& L, const KArgs& a, const DasPlan& plan
         }
     }
     if (plan.waves != copies::kWaves && !(plan.waves == 8 && !kFir && NSEG == 1)) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-    if (e != hipSuccess) return e;
-    if constexpr (!kFir && NSEG == 1) if (!direct) {
-        // This variant keeps LDS reads in flight across asm statements (issue_quads / await_quads): sound only while
-        // the compiler neither spills nor copies those registers.  Spilling is checkable: refuse to run a build that
-        // uses scratch (copies would show in the bit-exact parity tests).
-        static int scratch_bytes[4] = {-1, -1, -1, -1};
-        int& sb = scratch_bytes[(fixed ? 1 : 0) + (plan.waves == 8 ? 2 : 0)];
-        if (sb < 0) {
-            hipFuncAttributes fa{};
-            e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
-            if (e != hipSuccess) return e;
-            sb = (int)fa.localSizeBytes;
-        }
-        if (sb != 0) return hipErrorInvalidDeviceFunction;
-    }
+    // The pad / lerp sweep keeps LDS reads in flight across asm statements (issue_quads / await_quads): sound only while the
+    // compiler neither spills nor copies those registers.  Spilling is checkable: refuse to run a build that uses scratch
+    // (copies would show in the bit-exact parity tests).
+    static int scratch_bytes[4] = {-1, -1, -1, -1};
+    int* scratch = (!kFir && NSEG == 1 && !direct) ? &scratch_bytes[(fixed ? 1 : 0) + (plan.waves == 8 ? 2 : 0)] : nullptr;
     // the digest rides in a pointer slot the algorithm does not use: taps (pad, lerp) or frac (hybrid)
     const float* dig = reinterpret_cast<const float*>(L.tab.digest);
-    hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, stream, L.signals, L.images, L.mics, L.tab.whole, kFir ? dig : L.tab.frac,
-                       kFir ? L.tab.taps : dig, a);
-    return hipGetLastError();
+    return launch_with_lds(kernel, grid, block, plan.lds_bytes, stream, scratch, L.signals, L.images, L.mics, L.tab.whole, kFir ? dig : L.tab.frac,
+                           kFir ? L.tab.taps : dig, a);
 }
 
-template <int ALGO, int NC>
-hipError_t launch_nc(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
+template <int ALGO>
+hipError_t launch_hybrid_pair_algo(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
 {
-    constexpr bool kFir = ALGO == ALGO_HYBRID || ALGO == ALGO_FIR_NAIVE || ALGO == ALGO_FIR_VEC;
-    if constexpr (!kFir && NC >= 4) {
-        // pad / lerp beyond 128 samples: shifted copies only (plan_das gives them no other layout)
-        return plan.layout == 2 ? launch_copies<ALGO, NC / 4>(L, a, plan, frames, stream) : hipErrorInvalidValue;
-    } else {
-        if constexpr (NC == 4) {                        // the 8-tap FIR flavours; other tap counts take the strided kernel
-            if (plan.layout == 2) return launch_copies<ALGO, 1>(L, a, plan, frames, stream);
-        }
-        auto go = [&](auto kernel) -> hipError_t {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)plan.lds_bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)plan.n_tiles * (unsigned)frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream,
-                               L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a);
-            return hipGetLastError();
-        };
-        switch (plan.dpw) {
-            case 1: return go(das_mimo_kernel<ALGO, NC, 1>);
-            case 4: return go(das_mimo_kernel<ALGO, NC, 4>);
+    using HG = copies::HybridGeo;
+    if (L.tab.digest == nullptr || plan.waves != copies::kWaves || plan.mic_chunk != HG::kMc || plan.row_stride != HG::kRs ||
+        plan.lead != HG::kLead || (L.n_mics % 16) != 0 || L.n_taps != 8)
+        return hipErrorInvalidValue;
+    static int hybrid_scratch = -1;
+    const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
+    return launch_with_lds(copies::das_hybrid_pair_kernel<ALGO>, pair_grid, dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream, &hybrid_scratch,
+                           L.signals, L.images, L.mics, L.tab.whole, reinterpret_cast<const float*>(L.tab.digest), L.tab.taps, make_args(L, plan));
+}
+
+template <int ALGO, int NSEG>
+hipError_t launch_long_seg(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
+{
+    using LG = copies::LongGeo<ALGO, NSEG>;
+    if (L.tab.digest == nullptr || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != LG::kMc ||
+        (L.n_mics % LG::kHalf) != 0 || plan.dpw != LG::kDw)
+        return hipErrorInvalidValue;
+    const bool fixed_rs = plan.row_stride == (LG::kLerp ? 2 : 1) * copies::Geo<NSEG>::kRs && plan.lead == copies::Geo<NSEG>::kLead;
+    auto kernel = fixed_rs ? copies::das_long_kernel<ALGO, NSEG, copies::Geo<NSEG>::kRs> : copies::das_long_kernel<ALGO, NSEG, 0>;
+    static int long_scratch[2] = {-1, -1};
+    return launch_with_lds(kernel, dim3((unsigned)plan.n_tiles * (unsigned)frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream,
+                           &long_scratch[fixed_rs ? 1 : 0], L.signals, L.images, L.mics, L.tab.whole, L.tab.frac,
+                           reinterpret_cast<const float*>(L.tab.digest), make_args(L, plan));
+}
+
+}  // namespace
+
+hipError_t launch_hybrid_pair(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
+{
+    switch (L.algo) {
+        case ALGO_HYBRID: return launch_hybrid_pair_algo<ALGO_HYBRID>(L, plan, frames, stream);
+        case ALGO_FIR_NAIVE: return launch_hybrid_pair_algo<ALGO_FIR_NAIVE>(L, plan, frames, stream);
+        case ALGO_FIR_VEC: return launch_hybrid_pair_algo<ALGO_FIR_VEC>(L, plan, frames, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_long(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
+{
+    auto by_seg = [&](auto al) -> hipError_t {
+        constexpr int A = decltype(al)::value;
+        switch (plan.nc) {
+            case 8: return launch_long_seg<A, 2>(L, plan, frames, stream);
+            case 16: return launch_long_seg<A, 4>(L, plan, frames, stream);
             default: return hipErrorInvalidValue;
         }
-    }
-}
-
-template <int ALGO>
-hipError_t launch_algo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
-{
-    switch (plan.nc) {
-        case 1: return launch_nc<ALGO, 1>(L, a, plan, frames, stream);
-        case 2: return launch_nc<ALGO, 2>(L, a, plan, frames, stream);
-        case 4: return launch_nc<ALGO, 4>(L, a, plan, frames, stream);
-        case 8: return launch_nc<ALGO, 8>(L, a, plan, frames, stream);
-        case 16: return launch_nc<ALGO, 16>(L, a, plan, frames, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-// The beams of one das_miso_kernel launch (MisoBatch{} = the host path: one frame, one beam at KArgs::miso_row, one wave).
-struct MisoBatch {
-    const int32_t* offsets = nullptr;
-    int frames = 1, beams = 1, waves = 1;
-    int* status = nullptr;
-    long long entries = 0;
-    float gain = 0.0f;
-    int out_stride = 0;
-};
-
-template <int ALGO>
-hipError_t launch_miso_algo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, const float* init_dev, float* out_dev, const MisoBatch& B,
-                            hipStream_t stream)
-{
-    const unsigned groups = (unsigned)((B.beams + B.waves - 1) / B.waves);
-    const int out_stride = B.out_stride > 0 ? B.out_stride : L.n_samples;
-    auto go = [&](auto kernel) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)plan.lds_bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)B.frames * groups), dim3((unsigned)B.waves * kWave), plan.lds_bytes, stream, L.signals, L.images, L.mics,
-                           L.tab.whole, L.tab.frac, L.tab.taps, init_dev, out_dev, a, B.offsets, B.beams, B.status, B.entries, B.gain, out_stride);
-        return hipGetLastError();
     };
-    switch (plan.nc) {
-        case 1: return go(das_miso_kernel<ALGO, 1>);
-        case 2: return go(das_miso_kernel<ALGO, 2>);
-        case 4: return go(das_miso_kernel<ALGO, 4>);
-        case 8: return go(das_miso_kernel<ALGO, 8>);
-        case 16: return go(das_miso_kernel<ALGO, 16>);
+    switch (L.algo) {
+        case ALGO_PAD: return by_seg(std::integral_constant<int, ALGO_PAD>());
+        case ALGO_LERP: return by_seg(std::integral_constant<int, ALGO_LERP>());
         default: return hipErrorInvalidValue;
     }
 }
 
-long long grouped_entries_for_args(const DasLaunch& L, const DasPlan& plan)
+hipError_t launch_copies(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
 {
-    const long long groups = ((long long)(L.dir_end - L.dir_begin) + plan.dpw - 1) / plan.dpw;
-    return groups * L.n_mics * plan.dpw;
-}
-
-KArgs make_args(const DasLaunch& L, const DasPlan& plan)
-{
-    KArgs a{};
-    a.miso_row = 0;
-    a.n_mics = L.n_mics; a.m_total = L.m_total; a.n_samples = L.n_samples; a.n_taps = L.n_taps;
-    a.dir_begin = L.dir_begin; a.dir_end = L.dir_end; a.image_stride = L.image_stride; a.image_origin = L.image_origin;
-    a.lead = plan.lead; a.row_stride = plan.row_stride; a.mic_chunk = plan.mic_chunk; a.n_chunks = plan.n_chunks;
-    a.tile_dirs = plan.tile_dirs; a.n_tiles = plan.n_tiles;
-    a.scratch_off = plan.scratch_off; a.srow = plan.srow; a.pbw = plan.pbw;
-    a.n_is_pow2 = (L.n_mics & (L.n_mics - 1)) == 0;
-    a.inv_n = 1.0f / (float)L.n_mics;
-    a.n_frames = L.frames;
-    a.wg_frames = plan.nf == 2 ? (L.frames + 1) / 2 : L.frames;
-    a.frame_inner = plan.frame_inner;
-    a.digest_h_off = (plan.layout == 2 && (L.algo == ALGO_LERP || (L.algo == ALGO_HYBRID && plan.nf == 2))) ? grouped_entries_for_args(L, plan) : 0;
-    a.digest_t_off = (plan.layout == 2 && L.algo == ALGO_HYBRID && plan.nf == 2) ? 2 * grouped_entries_for_args(L, plan) : 0;
-    a.digest_o_off = L.tab.digest_order_off;
-    return a;
-}
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-}  // namespace
-
-int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
-{
-    static const char* kWhy[] = {"", "N_SAMPLES must be in [1, 1024]", "N_TAPS must be in [1, 64] (multiple of 8 for the vectorized FIR)",
-                                 "one microphone row does not fit in LDS", "empty launch"};
-    auto fail = [&](int i) { if (why) *why = kWhy[i]; return -i; };
-    if (L.n_samples < 1 || L.n_samples > 1024) return fail(1);
-    const bool fir = L.algo == ALGO_HYBRID || L.algo == ALGO_FIR_NAIVE || L.algo == ALGO_FIR_VEC;
-    if (fir && (L.n_taps < 1 || L.n_taps > 64 || (L.algo == ALGO_FIR_VEC && (L.n_taps % 8) != 0))) return fail(2);
-    if (L.n_mics < 1 || L.frames < 1 || L.dir_end <= L.dir_begin) return fail(4);
-
-    DasPlan p{};
-    p.nf = 1;
-    p.frame_inner = 0;
-    int nc = (L.n_samples + kWave - 1) / kWave;
-    p.nc = nc <= 1 ? 1 : nc <= 2 ? 2 : nc <= 4 ? 4 : nc <= 8 ? 8 : 16;
-    const int T = fir ? L.n_taps : 0;
-    const int shift = (L.algo == ALGO_FIR_NAIVE || L.algo == ALGO_FIR_VEC) ? 0 : L.tab.max_whole;
-    p.lead = round_up(shift + 1 + T / 2, 4);
-    const int tail = round_up(T, 4);
-    p.row_stride = p.lead + p.nc * kWave + tail;
-    const size_t row_bytes = (size_t)p.row_stride * sizeof(float);
-
-    // One 1024-thread workgroup (16 waves) per CU owns the whole 160 KiB LDS:
-    //   [ mic rows of one frame (or one chunk of them) | per-wave power scratch: waves x pbw rows of 64*nc+4 floats ]
-    // When the frame's mic block does not fit beside the scratch, the mics are staged in chunks and every wave
-    // carries DPW directions' accumulators across the chunks.
-    const size_t lds_budget = 160 * 1024;
-    p.waves = 16;
-    p.srow = p.nc * kWave + 4;   // +4: keeps rows 16-byte aligned and 4 banks apart; column nc*64 holds the direction id
-    p.pbw = p.nc <= 4 ? 4 : p.nc <= 8 ? 2 : 1;
-    const size_t scratch_bytes = (size_t)p.waves * p.pbw * p.srow * sizeof(float);
-    const size_t sig_budget = lds_budget - scratch_bytes - 16;
-    if (row_bytes * (size_t)L.n_mics <= sig_budget) {
-        p.mic_chunk = L.n_mics; p.n_chunks = 1; p.dpw = 1;
-    } else {
-        int mc = (int)(sig_budget / row_bytes);
-        if (mc < 1) return fail(3);
-        if (mc >= 4) mc &= ~3;
-        if (mc > L.n_mics) mc = L.n_mics;
-        p.mic_chunk = mc; p.n_chunks = (L.n_mics + mc - 1) / mc;
-        p.dpw = p.n_chunks > 1 ? 4 : 1;
-    }
-    // Layout: 2 = shifted copies for pad / lerp at 128 < N <= 1024 and for the 8-tap FIR flavours at 128 < N <= 256, 0 = strided
-    // everywhere else.
-    const bool plain = L.algo == ALGO_PAD || L.algo == ALGO_LERP;
-    const bool copies_ok = plain ? p.nc >= 4 : (p.nc == 4 && L.n_taps == 8);
-    p.layout = copies_ok ? 2 : 0;
-    if (p.layout == 2) {
-        const int nseg = p.nc / 4, arrays = (L.algo == ALGO_LERP) ? 2 : 1;
-        const int fixed_lead = nseg == 1 ? copies::Geo<1>::kLead : copies::Geo<4>::kLead;   // Geo<2> == Geo<4> here
-        const int dw = nseg == 4 ? copies::Geo<4>::kDw : copies::Geo<1>::kDw;               // Geo<2> == Geo<1> here
-        // zero prefix: the furthest look-back is the delay (+1 for lerp, +1 + T/2 for hybrid, T/2 for the plain FIRs)
-        const int back = L.algo == ALGO_HYBRID ? L.tab.max_whole + 1 + L.n_taps / 2 : fir ? L.n_taps / 2 : L.tab.max_whole + 1;
-        p.lead = round_up(back + 1, 4);
-        if (p.lead <= fixed_lead) p.lead = fixed_lead;   // compile-time row stride
-        p.row_stride = p.lead + nseg * 256 + (fir ? copies::Geo<1>::kFirTail : 0);
-        p.copies = copies::copies_of(L.algo, L.tab.digest_direct);
-        const size_t slot_bytes = (size_t)arrays * p.copies * p.row_stride * sizeof(float);
-        // a chunk: as many mics as fit beside nothing else in 156 KiB, at most 16 (one s_load of table entries) and at
-        // most what the 16 waves stage in one go (one (mic, segment) pair each; two for pad with several segments)
-        int stage_pairs = 16 * ((nseg > 1 && L.algo == ALGO_PAD) ? 2 : 1);
-        // One 16-wave workgroup per CU with (nearly) the whole LDS.  pad / lerp at N <= 256 also come as 8-wave workgroups
-        // (two per CU, 78 KiB each): twice the staging per direction, so only for grids too coarse to fill 16 waves' 128
-        // directions (cfg1: 121 directions, 637K -> 961K frames/s).  (cfg2, 190 frames: 16 waves 80.0K, 8 waves 72.0K.)
-        const int waves = (plain && nseg == 1 && (L.dir_end - L.dir_begin) < 256) ? 8 : copies::kWaves;
-        const size_t budget = waves == 8 ? (size_t)78 * 1024 : (size_t)156 * 1024;
-        if (plain && nseg == 1 && waves == copies::kWaves && !L.tab.digest_direct) stage_pairs = 32;
-        int mc = (int)(budget / slot_bytes);
-        if (mc > stage_pairs / nseg) mc = stage_pairs / nseg;
-        mc = mc >= 32 ? 32 : mc >= 16 ? 16 : mc >= 8 ? 8 : mc >= 4 ? 4 : mc >= 2 ? 2 : mc;
-        if (mc < 1) return fail(3);
-        if (mc > L.n_mics) mc = L.n_mics;
-        // Two frames per workgroup (das_pair_kernel) where its fixed geometry applies: the per-step scalar work is then shared
-        // by both frames.
-        p.nf = 1;
-        if (plain && nseg == 1 && waves == copies::kWaves && !L.tab.digest_direct && p.lead == fixed_lead && (L.n_mics % 16) == 0 &&
-            (L.n_samples % 4) == 0 && L.frames >= 2) {
-            p.nf = 2;
-            mc = 16;
-            // frames interleaved in the rows (das_pair2_kernel) for lerp: 4 instead of 8 LDS reads per (re)load, +1.5 %; pad reads
-            // half as much to begin with and measured 2 % slower that way
-            if (L.algo == ALGO_LERP) {
-                p.interleaved = 1;
-                p.row_stride = 2 * copies::Geo<1>::kRs;         // the two frames of a mic share a row, sample by sample
-            }
+    auto plain = [&](auto al) -> hipError_t {
+        constexpr int A = decltype(al)::value;
+        switch (plan.nc) {
+            case 4: return launch_copies_seg<A, 1>(L, plan, frames, stream);
+            case 8: return launch_copies_seg<A, 2>(L, plan, frames, stream);
+            case 16: return launch_copies_seg<A, 4>(L, plan, frames, stream);
+            default: return hipErrorInvalidValue;
         }
-        // The hybrid beamformer's two-frame sweep (das_hybrid_pair_kernel) under the same conditions.
-        if (fir && nseg == 1 && L.n_taps == 8 && waves == copies::kWaves && p.lead == fixed_lead && (L.n_mics % 16) == 0 &&
-            (L.n_samples % 4) == 0 && L.frames >= 2) {
-            p.nf = 2;
-            mc = copies::HybridGeo::kMc;                        // 32 mic slots: two frames interleaved per row, two shifted copies
-            p.copies = copies::HybridGeo::kC;
-            p.row_stride = copies::HybridGeo::kRs;
-            p.interleaved = 1;
-        }
-        const bool hybrid_pair = fir && p.nf == 2;
-        // Long rows (2 / 4 segments): das_long_kernel where its LDS image -- two halves of 16 / nseg mics -- fits and the mic count is
-        // a whole number of halves.
-        p.long_rows = 0;
-        if (plain && nseg > 1 && !L.tab.digest_direct) {
-            const int half = 16 / nseg;
-            if ((L.n_mics % half) == 0 && (L.n_samples % 4) == 0 && slot_bytes * (size_t)(2 * half) <= (size_t)160 * 1024) {
-                p.long_rows = 1;
-                mc = 2 * half;
-                if (L.algo == ALGO_LERP) {                      // rows of (sample pair, difference pair) quads: two floats per sample, no separate difference rows
-                    p.interleaved = 1;
-                    p.row_stride *= 2;
-                }
-            }
-        }
-        p.mic_chunk = mc; p.n_chunks = (L.n_mics + mc - 1) / mc;
-        p.waves = waves; p.dpw = dw; p.srow = nseg * 256 + 4;
-        p.scratch_off = 0;
-        const size_t buf = hybrid_pair ? (size_t)mc * copies::HybridGeo::kSlot * sizeof(float) : slot_bytes * (size_t)mc * (size_t)p.nf;
-        const size_t wave_rows = (size_t)dw * p.srow * sizeof(float);          // the parked rows of one wave
-        p.lds_bytes = buf > 2 * wave_rows ? buf : 2 * wave_rows;
-        if (p.long_rows && p.lds_bytes < 8 * wave_rows) p.lds_bytes = 8 * wave_rows;             // eight waves park together (two rounds)
-        if (nseg == 1 && p.lds_bytes < p.waves * wave_rows) p.lds_bytes = p.waves * wave_rows;   // N <= 256: the whole group parks at once
-        int pw = (int)(p.lds_bytes / wave_rows);                                 // waves that park together (power of two)
-        p.pbw = pw >= 16 ? 16 : pw >= 8 ? 8 : pw >= 4 ? 4 : 2;
-        if (p.pbw > p.waves) p.pbw = p.waves;
+    };
+    if (is_fir(L.algo) && plan.nc != 4) return hipErrorInvalidValue;
+    switch (L.algo) {
+        case ALGO_PAD: return plain(std::integral_constant<int, ALGO_PAD>());
+        case ALGO_LERP: return plain(std::integral_constant<int, ALGO_LERP>());
+        case ALGO_HYBRID: return launch_copies_seg<ALGO_HYBRID, 1>(L, plan, frames, stream);
+        case ALGO_FIR_NAIVE: return launch_copies_seg<ALGO_FIR_NAIVE, 1>(L, plan, frames, stream);
+        case ALGO_FIR_VEC: return launch_copies_seg<ALGO_FIR_VEC, 1>(L, plan, frames, stream);
+        default: return hipErrorInvalidValue;
     }
-    if (p.layout != 2) {
-        p.scratch_off = round_up(p.mic_chunk * p.row_stride, 4);
-        p.lds_bytes = (size_t)p.scratch_off * sizeof(float) + scratch_bytes;
-    }
-
-    // Tile size: enough workgroups to fill the chip a few times over, but as many directions per staged block
-    // as possible.  A tile is a whole number of wave groups -- except for small launches (a single frame through the
-    // host-pointer API), where latency matters: then every CU gets a tile, even if that leaves waves of a group idle.
-    const int group = p.waves * p.dpw;
-    const long long dirs = (long long)(L.dir_end - L.dir_begin);
-    bool spread = false;   // no XCD affinity of the tiles (see below)
-    const long long target_wgs = (long long)n_cus * 4;
-    const long long wg_frames = p.nf == 2 ? (L.frames + 1) / 2 : L.frames;   // frames (frame pairs) a column of the grid walks
-    long long td = (dirs * wg_frames + target_wgs - 1) / target_wgs;
-    if (dirs * wg_frames < (long long)n_cus * group) {
-        td = (dirs * wg_frames + n_cus - 1) / n_cus;
-        td = round_up((int)(td < 1 ? 1 : td), p.dpw);
-    } else {
-        // A whole number of wave groups per tile, chosen by what the grid costs.  Workgroup ids go round-robin over the 8 XCDs.
-        //   * Large tables: workgroup id -> (tile, frame) with the tile count padded to a multiple of 8 keeps
-        //     tile % 8 == id % 8, so every XCD's L2 serves only its own tiles' table rows for all frames; XCD x then runs
-        //     the tiles with tile % 8 == x on its 32 CUs and the launch takes  max_x ceil(tiles_x * frames / 32)  rounds of
-        //     k groups.  (cfg2, 95 frame pairs, lerp: k = 2 or 5 -> 30 units, 122K frames/s; k = 4 -> 36, 106K; k = 8 -> 48,
-        //     80K: measured.)
-        //   * Tables that fit every XCD's L2 whole (a rank's direction shard of bench.py --gpus 4 / 8): no padding, every
-        //     tile's workgroups spread over the XCDs, ceil(tiles * frames / CUs) rounds -- pinning 10 tiles to 8 XCDs left
-        //     a rank of the 8-GPU shape at 63 % of the one-GPU rate.
-        // Ties go to the first of 2, 3, .., 8, 1.
-        const size_t table_bytes = (size_t)dirs * (size_t)L.n_mics * 4u * ((L.algo == ALGO_LERP ? 2u : 1u) + (fir ? (size_t)L.n_taps : 0u));
-        spread = table_bytes <= ((size_t)3 << 20);
-        // an XCD's share of the table beyond its L2: all frames of a tile back to back (tile_and_frame)
-        p.frame_inner = (!spread && p.layout == 2 && table_bytes > ((size_t)16 << 20) && wg_frames > 1) ? 1 : 0;
-        const int wg_per_cu = 1;
-        const int xcds = 8, cus_per_xcd = (n_cus >= xcds ? n_cus / xcds : 1) * wg_per_cu;
-        long long best_cost = -1;
-        int best_k = 4;
-        for (int i = 0; i < 8; ++i) {
-            const int k = i < 7 ? i + 2 : 1;
-            const long long tiles = (dirs + (long long)k * group - 1) / ((long long)k * group);
-            const long long tiles_x = tiles / xcds + (tiles % xcds ? 1 : 0);        // the busiest XCD's share
-            const long long slots = (long long)n_cus * wg_per_cu;
-            const long long rounds = spread ? (tiles * wg_frames + slots - 1) / slots : (tiles_x * wg_frames + cus_per_xcd - 1) / cus_per_xcd;
-            const long long cost = rounds * k;
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_k = k; }
-        }
-        td = (long long)best_k * group;
-    }
-    p.tile_dirs = (int)td;
-    p.n_tiles = spread ? (int)((dirs + td - 1) / td) : round_up((int)((dirs + td - 1) / td), 8);
-    *plan = p;
-    if (why) *why = kWhy[0];
-    return 0;
-}
-
-namespace {
-long long grouped_entries(const DasLaunch& L, const DasPlan& plan) { return grouped_entries_for_args(L, plan); }
-}  // namespace
-
-// Where the sweep order of a launch sits in its digest (behind the grouped entries and lerp's weights), 0 where the plan's kernel
-// takes none: only the pad / lerp pair kernels do.
-long long digest_order_offset(const DasLaunch& L, const DasPlan& plan)
-{
-    if (plan.layout != 2 || plan.nf != 2 || (L.algo != ALGO_PAD && L.algo != ALGO_LERP)) return 0;
-    return (L.algo == ALGO_LERP ? 2 : 1) * grouped_entries(L, plan);
-}
-
-size_t digest_elements(const DasLaunch& L, const DasPlan& plan)
-{
-    if (plan.layout != 2) return 0;
-    const size_t direct = (size_t)L.n_dirs * (size_t)L.n_mics;                 // the [D][M] layout of the DIRECT variant
-    const size_t order = digest_order_offset(L, plan) != 0 ? (size_t)(grouped_entries(L, plan) / L.n_mics) : 0;   // one entry per (padded) position
-    if (L.algo == ALGO_PAD) return std::max((size_t)grouped_entries(L, plan) + order, direct);
-    if (L.algo == ALGO_LERP) return std::max((size_t)(2 * grouped_entries(L, plan)) + order, direct);    // offsets, then the lerp weights in the same order
-    // the FIR pair kernel: offsets and packed guards (hybrid), then the taps regrouped per 8 directions
-    if (L.algo == ALGO_HYBRID) return std::max((size_t)L.n_dirs * (size_t)L.n_mics, plan.nf == 2 ? (size_t)(10 * grouped_entries(L, plan)) : (size_t)0);
-    if ((L.algo == ALGO_FIR_NAIVE || L.algo == ALGO_FIR_VEC) && plan.nf == 2) return (size_t)(8 * grouped_entries(L, plan));
-    return 0;
 }
 
 hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, bool direct, long long order_off,
@@ -3422,12 +1883,12 @@ hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_dig
     // (the hybrid pair kernel interleaves its two frames inside a row: one array per mic)
     // (das_long_kernel's lerp rows carry their differences inside: one array)
     const int arrays = ((L.algo == ALGO_LERP && !(plan.long_rows && plan.interleaved)) ? 2 : 1) * ((plan.nf == 2 && !plan.interleaved) ? 2 : 1), bias = (L.algo == ALGO_LERP) ? 1 : (L.algo == ALGO_HYBRID) ? 5 : 0;
-    const bool fir_pair = plan.nf == 2 && (L.algo == ALGO_HYBRID || L.algo == ALGO_FIR_NAIVE || L.algo == ALGO_FIR_VEC);
+    const bool fir_pair = plan.nf == 2 && is_fir(L.algo);
     if ((L.algo == ALGO_HYBRID && plan.nf != 2) || direct) {
         hipLaunchKernelGGL(digest_kernel, dim3(1024), dim3(256), 0, stream, L.tab.whole, d_digest, (long long)L.n_dirs * L.n_mics, L.n_mics, plan.mic_chunk,
                            arrays, plan.row_stride, plan.lead, bias, plan.copies);
     } else {
-        const long long entries = grouped_entries(L, plan);
+        const long long entries = grouped_entries_for_args(L, plan);
         hipLaunchKernelGGL(digest_grouped_kernel, dim3(1024), dim3(256), 0, stream, L.algo == ALGO_HYBRID || !fir_pair ? L.tab.whole : nullptr,
                            L.algo == ALGO_LERP ? L.tab.frac : nullptr, d_digest,
                            entries, entries, L.n_mics, plan.dpw, L.dir_begin, L.dir_end, plan.mic_chunk, arrays, plan.row_stride, plan.lead, bias,
@@ -3435,188 +1896,6 @@ hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_dig
                            fir_pair ? (L.algo == ALGO_HYBRID ? 2 * entries : 0) : 0, order_off != 0 ? d_digest + order_off : nullptr);
     }
     return hipGetLastError();
-}
-
-// Steps of a launch over which the sweep can share reads at all (all but the first direction of every group).
-long long digest_shareable_steps(const DasLaunch& L, const DasPlan& plan)
-{
-    return plan.dpw > 1 ? grouped_entries(L, plan) / plan.dpw * (plan.dpw - 1) : 0;
-}
-
-// Profiling build only: read and clear the phase totals of das_pair_kernel (16 counters; zeros in a production build).
-hipError_t read_phase_stamps(unsigned long long* out16, bool clear)
-{
-#ifdef BF_STAMPS
-    static unsigned long long all[64 * 16];
-    hipError_t e = hipMemcpyFromSymbol(all, HIP_SYMBOL(copies::g_stamps), sizeof(all));
-    if (e != hipSuccess) return e;
-    for (int i = 0; i < 16; ++i) { out16[i] = 0; for (int r = 0; r < 64; ++r) out16[i] += all[16 * r + i]; }
-    if (!clear) return e;
-    for (int i = 0; i < 64 * 16; ++i) all[i] = 0;
-    return hipMemcpyToSymbol(HIP_SYMBOL(copies::g_stamps), all, sizeof(all));
-#else
-    for (int i = 0; i < 16; ++i) out16[i] = 0;
-    (void)clear;
-    return hipSuccess;
-#endif
-}
-
-hipError_t launch_das(const DasLaunch& L, const DasPlan& plan, hipStream_t stream)
-{
-    const KArgs a = make_args(L, plan);
-    switch (L.algo) {
-        case ALGO_PAD: return launch_algo<ALGO_PAD>(L, a, plan, L.frames, stream);
-        case ALGO_LERP: return launch_algo<ALGO_LERP>(L, a, plan, L.frames, stream);
-        case ALGO_HYBRID: return launch_algo<ALGO_HYBRID>(L, a, plan, L.frames, stream);
-        case ALGO_FIR_NAIVE: return launch_algo<ALGO_FIR_NAIVE>(L, a, plan, L.frames, stream);
-        case ALGO_FIR_VEC: return launch_algo<ALGO_FIR_VEC>(L, a, plan, L.frames, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-namespace {
-hipError_t launch_miso_any(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev, const MisoBatch& B,
-                           hipStream_t stream)
-{
-    KArgs a = make_args(L, plan);
-    a.miso_row = row_offset;
-    switch (L.algo) {
-        case ALGO_PAD: return launch_miso_algo<ALGO_PAD>(L, a, plan, init_dev, out_dev, B, stream);
-        case ALGO_LERP: return launch_miso_algo<ALGO_LERP>(L, a, plan, init_dev, out_dev, B, stream);
-        case ALGO_HYBRID: return launch_miso_algo<ALGO_HYBRID>(L, a, plan, init_dev, out_dev, B, stream);
-        case ALGO_FIR_NAIVE: return launch_miso_algo<ALGO_FIR_NAIVE>(L, a, plan, init_dev, out_dev, B, stream);
-        case ALGO_FIR_VEC: return launch_miso_algo<ALGO_FIR_VEC>(L, a, plan, init_dev, out_dev, B, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-}  // namespace
-
-hipError_t launch_miso(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev,
-                       hipStream_t stream)
-{
-    return launch_miso_any(L, plan, row_offset, init_dev, out_dev, MisoBatch{}, stream);
-}
-
-hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int beams, long long entries, float gain,
-                             float* d_out, int out_stride, int* d_status, hipStream_t stream)
-{
-    if (L.frames < 1 || beams < 1 || out_stride < L.n_samples) return hipErrorInvalidValue;
-    MisoBatch B;
-    B.offsets = d_offsets; B.frames = L.frames; B.beams = beams; B.waves = std::min(beams, kMisoWaves);
-    B.status = d_status; B.entries = entries; B.gain = gain; B.out_stride = out_stride;
-    return launch_miso_any(L, plan, 0, nullptr, d_out, B, stream);
-}
-
-// ---- continuous-stream mode: planning and launches ------------------------------------------------------------------------
-
-int stream_history(int algo, int max_whole)
-{
-    return algo == ALGO_PAD ? max_whole : algo == ALGO_LERP ? max_whole + 1 : -1;
-}
-
-// Maps in stream mode always take the strided layout (lane l owns samples l, l + 64, ..), whatever N: the sizing is plan_das's
-// for that layout -- one 16-wave workgroup with the whole LDS, mic rows (or a chunk of them) beside the per-wave power scratch.
-int plan_stream_maps(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
-{
-    auto fail = [&](const char* msg) { if (why) *why = msg; return -1; };
-    if (L.algo != ALGO_PAD && L.algo != ALGO_LERP) return fail("continuous mode exists for pad and lerp only");
-    if (L.n_samples < 1 || L.n_samples > 1024) return fail("N_SAMPLES must be in [1, 1024]");
-    if (L.n_mics < 1 || L.frames < 1 || L.dir_end <= L.dir_begin) return fail("empty launch");
-    DasPlan p{};
-    p.nf = 1;
-    const int nc = (L.n_samples + kWave - 1) / kWave;
-    p.nc = nc <= 1 ? 1 : nc <= 2 ? 2 : nc <= 4 ? 4 : nc <= 8 ? 8 : 16;
-    p.lead = round_up(L.tab.max_whole + 1, 4);      // >= the history of either flavour
-    p.row_stride = p.lead + p.nc * kWave;
-    const size_t row_bytes = (size_t)p.row_stride * sizeof(float);
-    p.waves = 16;
-    p.srow = p.nc * kWave + 4;
-    p.pbw = p.nc <= 4 ? 4 : p.nc <= 8 ? 2 : 1;
-    const size_t scratch_bytes = (size_t)p.waves * p.pbw * p.srow * sizeof(float);
-    const size_t sig_budget = (size_t)160 * 1024 - scratch_bytes - 16;
-    if (row_bytes * (size_t)L.n_mics <= sig_budget) {
-        p.mic_chunk = L.n_mics; p.n_chunks = 1; p.dpw = 1;
-    } else {
-        int mc = (int)(sig_budget / row_bytes);
-        if (mc < 1) return fail("one microphone row does not fit in LDS");
-        if (mc >= 4) mc &= ~3;
-        p.mic_chunk = mc; p.n_chunks = (L.n_mics + mc - 1) / mc;
-        p.dpw = 4;
-    }
-    p.scratch_off = round_up(p.mic_chunk * p.row_stride, 4);
-    p.lds_bytes = (size_t)p.scratch_off * sizeof(float) + scratch_bytes;
-    // Tiles: whole wave groups, about four workgroups per CU; a launch too small for that gives every CU a tile.  With one chunk a
-    // tile stages its frame once, so more groups per tile save staging; with several chunks every group restages anyway.
-    const int group = p.waves * p.dpw;
-    const long long dirs = (long long)(L.dir_end - L.dir_begin), work = dirs * L.frames;
-    long long td;
-    if (work < (long long)n_cus * group) {
-        td = round_up((int)std::max<long long>(1, (work + n_cus - 1) / n_cus), p.dpw);
-    } else {
-        long long k = p.n_chunks > 1 ? 1 : work / ((long long)n_cus * 4 * group);
-        k = std::min<long long>(std::max<long long>(k, 1), 8);
-        td = k * group;
-    }
-    p.tile_dirs = (int)td;
-    p.n_tiles = (int)((dirs + td - 1) / td);
-    *plan = p;
-    if (why) *why = "";
-    return 0;
-}
-
-hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, hipStream_t stream)
-{
-    const int hist = stream_history(L.algo, L.tab.max_whole);
-    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist || plan.layout != 0) return hipErrorInvalidValue;
-    const KArgs a = make_args(L, plan);
-    auto go = [&](auto kernel) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)plan.n_tiles * (unsigned)L.frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream,
-                           L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a, d_prev, hop, hist);
-        return hipGetLastError();
-    };
-    auto by_dpw = [&](auto nc) -> hipError_t {
-        constexpr int NC = decltype(nc)::value;
-        if (plan.dpw == 1) return L.algo == ALGO_PAD ? go(stream_map_kernel<ALGO_PAD, NC, 1>) : go(stream_map_kernel<ALGO_LERP, NC, 1>);
-        if (plan.dpw == 4) return L.algo == ALGO_PAD ? go(stream_map_kernel<ALGO_PAD, NC, 4>) : go(stream_map_kernel<ALGO_LERP, NC, 4>);
-        return hipErrorInvalidValue;
-    };
-    switch (plan.nc) {
-        case 1: return by_dpw(std::integral_constant<int, 1>());
-        case 2: return by_dpw(std::integral_constant<int, 2>());
-        case 4: return by_dpw(std::integral_constant<int, 4>());
-        case 8: return by_dpw(std::integral_constant<int, 8>());
-        case 16: return by_dpw(std::integral_constant<int, 16>());
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
-                               long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream)
-{
-    const int hist = stream_history(L.algo, L.tab.max_whole);
-    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist) return hipErrorInvalidValue;
-    if (L.frames < 1 || beams < 1 || out_stride < L.n_samples || d_offsets == nullptr) return hipErrorInvalidValue;
-    const KArgs a = make_args(L, plan);
-    const int waves = std::min(beams, kMisoWaves);
-    const unsigned groups = (unsigned)((beams + waves - 1) / waves);
-    auto go = [&](auto kernel) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)L.frames * groups), dim3((unsigned)waves * kWave), plan.lds_bytes, stream, L.signals, L.images, L.mics,
-                           L.tab.whole, L.tab.frac, L.tab.taps, d_out, a, d_offsets, beams, d_status, entries, gain, out_stride, d_prev, hop, hist);
-        return hipGetLastError();
-    };
-    const bool pad = L.algo == ALGO_PAD;
-    switch (plan.nc) {
-        case 1: return pad ? go(stream_beam_kernel<ALGO_PAD, 1>) : go(stream_beam_kernel<ALGO_LERP, 1>);
-        case 2: return pad ? go(stream_beam_kernel<ALGO_PAD, 2>) : go(stream_beam_kernel<ALGO_LERP, 2>);
-        case 4: return pad ? go(stream_beam_kernel<ALGO_PAD, 4>) : go(stream_beam_kernel<ALGO_LERP, 4>);
-        case 8: return pad ? go(stream_beam_kernel<ALGO_PAD, 8>) : go(stream_beam_kernel<ALGO_LERP, 8>);
-        case 16: return pad ? go(stream_beam_kernel<ALGO_PAD, 16>) : go(stream_beam_kernel<ALGO_LERP, 16>);
-        default: return hipErrorInvalidValue;
-    }
 }
 
 // ---- bf_remove_sources_device: subtract beams, projected back onto the microphones, from the frames -------------------------

@@ -1,0 +1,604 @@
+// das_pair.hip -- the pad / lerp sweep with two frames per workgroup: copies::das_pair_kernel (pad) and das_pair2_kernel (lerp),
+// what the bench and every multi-frame caller at N <= 256 run.  das_kernels.hip has the overview and the one-frame sweep
+// (das_copies_kernel) these kernels grew out of.
+#include "das_device.h"
+
+namespace bf {
+
+namespace {
+
+namespace copies {
+
+// ==================================================================================================
+// Two frames per workgroup (pad, N <= 256, fixed row stride, mic count a multiple of 16, two or more frames; lerp runs
+// das_pair2_kernel below).
+//
+// The sweep above is bound by the number of instructions a SIMD issues, and per (direction, mic) step only 2 of them (pad) are
+// arithmetic: the rest -- table loads, the address, the offset tests, waits -- depends on the tables alone.  A wave that
+// carries its eight directions through TWO frames pays that part once per 4 packed operations.
+// Same layout as das_copies_kernel<pad, NSEG = 1, RS = kRs, W = 16> (two shifted copies), with the two frames' rows of a mic
+// next to each other: frame 1's quads sit kFoff bytes after frame 0's, an immediate offset off the same address.  16 mics x 2
+// frames per chunk; the 64 accumulator registers leave no room for quads in flight across a mic, so a mic's first quads are
+// read (and waited for) in place -- the other three waves of the SIMD cover that.
+// Mic order and operation order per frame are those of the one-frame kernel: bit-identical maps.
+// (PairGeo: das_geometry.h)
+
+#define BF_P_ACC(n, j, f) [a##n##0] "+v"(acc[j][f][0]), [a##n##1] "+v"(acc[j][f][1])
+// two direction steps x two frames; a0/a1 = step A frame 0/1, a2/a3 = step B frame 0/1
+#define BF_P_PAD_STEP(n0, n1)                                                                             \
+    "v_pk_add_f32 %[a" #n0 "0], %[a" #n0 "0], %[s0l]\n\tv_pk_add_f32 %[a" #n0 "1], %[a" #n0 "1], %[s0h]\n\t" \
+    "v_pk_add_f32 %[a" #n1 "0], %[a" #n1 "0], %[s1l]\n\tv_pk_add_f32 %[a" #n1 "1], %[a" #n1 "1], %[s1h]\n\t"
+#define BF_P_PAD_READ                                                                                     \
+    "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"                         \
+    "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\t"                 \
+    "s_waitcnt lgkmcnt(0)\n\t"
+#define BF_P_ADDR(e) "v_add_u32 %[ad], %[" #e "], %[lb]\n\t"
+#define BF_P_CHECK(n, ep, ec) "s_cmp_lg_u32 %[" #ec "], %[" #ep "]\n\ts_cbranch_scc1 .Lr" #n "_%=\n.Lb" #n "_%=:\n\t"
+#define BF_P_STUB(n, ec, READ) ".Lr" #n "_%=:\n\t" BF_P_ADDR(ec) READ "s_branch .Lb" #n "_%=\n"
+
+// Direction steps 0 and 1 of a mic for both frames: the mic's first quads are read in place (offset eb) before step 0, step 1
+// tests eb -> ec first.
+__device__ __forceinline__ void pair_pad_first(f32x2 (&acc)[8][2][2], Quad& S0, Quad& S1, int eb, int ec, int lbase)
+{
+    using G = PairGeo;
+    int ad;
+    // pad_and_sum.c:41-47   out[k] += s[k - p]
+    // (step 0: each frame's adds wait only for that frame's two reads -- LDS returns in order)
+    asm volatile(BF_P_ADDR(eb)
+                 "ds_read_b64 %[s0l], %[ad] offset:0\n\tds_read_b64 %[s0h], %[ad] offset:8\n\t"
+                 "ds_read_b64 %[s1l], %[ad] offset:%[f0]\n\tds_read_b64 %[s1h], %[ad] offset:%[f8]\n\ts_waitcnt lgkmcnt(2)\n\t"
+                 "v_pk_add_f32 %[a00], %[a00], %[s0l]\n\tv_pk_add_f32 %[a01], %[a01], %[s0h]\n\ts_waitcnt lgkmcnt(0)\n\t"
+                 "v_pk_add_f32 %[a10], %[a10], %[s1l]\n\tv_pk_add_f32 %[a11], %[a11], %[s1h]\n\t"
+                 BF_P_CHECK(1, eb, ec) BF_P_PAD_STEP(2, 3)
+                 ".subsection 1\n" BF_P_STUB(1, ec, BF_P_PAD_READ) "\t.subsection 0"
+                 // (the quads are pure outputs here: as in-out operands they are carried around the mic loop -- and copied at its back-edge)
+                 : BF_P_ACC(0, 0, 0), BF_P_ACC(1, 0, 1), BF_P_ACC(2, 1, 0), BF_P_ACC(3, 1, 1), [s0l] "=&v"(S0.lo), [s0h] "=&v"(S0.hi),
+                   [s1l] "=&v"(S1.lo), [s1h] "=&v"(S1.hi), [ad] "=&v"(ad)
+                 : [eb] "s"(eb), [ec] "s"(ec), [lb] "v"(lbase), [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8) : "scc");
+}
+
+// pad, direction steps 2..7 of a mic for both frames as ONE statement (between two statements the hazard recogniser puts an s_nop:
+// three issue slots per mic with one statement per pair of steps).
+__device__ __forceinline__ void pair_pad_rest(f32x2 (&acc)[8][2][2], Quad& S0, Quad& S1, const int (&e)[8], int lbase)
+{
+    using G = PairGeo;
+    int ad;
+#define BF_P_ACC2(n, j) [a##n##0] "+v"(acc[j][0][0]), [a##n##1] "+v"(acc[j][0][1]), [b##n##0] "+v"(acc[j][1][0]), [b##n##1] "+v"(acc[j][1][1])
+#define BF_P_PAD1(n) "v_pk_add_f32 %[a" #n "0], %[a" #n "0], %[s0l]\n\tv_pk_add_f32 %[a" #n "1], %[a" #n "1], %[s0h]\n\t" \
+                     "v_pk_add_f32 %[b" #n "0], %[b" #n "0], %[s1l]\n\tv_pk_add_f32 %[b" #n "1], %[b" #n "1], %[s1h]\n\t"
+    asm volatile(BF_P_CHECK(2, e1, e2) BF_P_PAD1(2) BF_P_CHECK(3, e2, e3) BF_P_PAD1(3) BF_P_CHECK(4, e3, e4) BF_P_PAD1(4)
+                 BF_P_CHECK(5, e4, e5) BF_P_PAD1(5) BF_P_CHECK(6, e5, e6) BF_P_PAD1(6) BF_P_CHECK(7, e6, e7) BF_P_PAD1(7)
+                 ".subsection 1\n" BF_P_STUB(2, e2, BF_P_PAD_READ) BF_P_STUB(3, e3, BF_P_PAD_READ) BF_P_STUB(4, e4, BF_P_PAD_READ)
+                 BF_P_STUB(5, e5, BF_P_PAD_READ) BF_P_STUB(6, e6, BF_P_PAD_READ) BF_P_STUB(7, e7, BF_P_PAD_READ) "\t.subsection 0"
+                 : BF_P_ACC2(2, 2), BF_P_ACC2(3, 3), BF_P_ACC2(4, 4), BF_P_ACC2(5, 5), BF_P_ACC2(6, 6), BF_P_ACC2(7, 7),
+                   [s0l] "+v"(S0.lo), [s0h] "+v"(S0.hi), [s1l] "+v"(S1.lo), [s1h] "+v"(S1.hi), [ad] "=&v"(ad)
+                 : [e1] "s"(e[1]), [e2] "s"(e[2]), [e3] "s"(e[3]), [e4] "s"(e[4]), [e5] "s"(e[5]), [e6] "s"(e[6]), [e7] "s"(e[7]), [lb] "v"(lbase),
+                   [f0] "n"(G::kFoff), [f8] "n"(G::kFoff + 8)
+                 : "scc");
+#undef BF_P_ACC2
+#undef BF_P_PAD1
+}
+
+// Profiling build only (-DBF_STAMPS, scripts/dev/phase_stamps.py): every wave sums the time it spends in each phase of
+// das_pair_kernel / das_pair2_kernel (s_memtime at the phase boundaries, which are barrier neighbours anyway) and adds the totals to
+// g_stamps[phase] when its workgroup ends.  BF_STAMP(k) closes the phase that was running and charges it to slot k:
+//   0 sweep  1 wait (chunk free)  2 staging  3 wait (chunk staged)  4 wait (power: rows free)  5 parking  6 wait (rows parked)  7 ordered sum
+#ifdef BF_STAMPS
+__device__ unsigned long long g_stamps[64 * 16];         // (sums over all waves, in 64 replicas picked by workgroup id: nine atomics per wave on one
+                                                         //  line would make the flush longer than the kernel)
+#define BF_STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_prev = __builtin_amdgcn_s_memtime();
+#define BF_STAMP(k) do { const unsigned long long st_now = __builtin_amdgcn_s_memtime(); st_acc[k] += st_now - st_prev; st_prev = st_now; } while (0)
+#define BF_STAMP_FLUSH do { if (lane == 0) { unsigned long long* gs = g_stamps + 16 * (blockIdx.x & 63); for (int i = 0; i < 8; ++i) atomicAdd(&gs[i], st_acc[i]); atomicAdd(&gs[8], 1ull); } } while (0)
+#else
+#define BF_STAMP_DECL
+#define BF_STAMP(k)
+#define BF_STAMP_FLUSH
+#endif
+
+template <int ALGO>   // (pad only: the parameter keeps the kernel's symbol, which the profiles and ISA checks name)
+__global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArgs a)
+{
+    static_assert(ALGO == ALGO_PAD, "das_pair_kernel: pad (lerp runs das_pair2_kernel)");
+    using G = PairGeo;
+    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int tile, fpair;
+    tile_and_frame(a, &tile, &fpair);
+    const int f0 = 2 * fpair;
+    const bool two = f0 + 1 < a.n_frames;                      // an odd frame count: the last workgroup row computes its frame twice
+    const int f1 = two ? f0 + 1 : f0;
+    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
+    if (tile_begin >= a.dir_end) return;
+    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
+    const int M = a.n_mics, N = a.n_samples;                   // M % 16 == 0, N % 4 == 0, N <= 256 (plan_das)
+    const int n_half = M / HC;                                  // half chunks of 8 mics
+    const float* __restrict__ sig0 = signals + (size_t)f0 * a.m_total * N;
+    const float* __restrict__ sig1 = signals + (size_t)f1 * a.m_total * N;
+    float* __restrict__ img0 = images + (size_t)f0 * a.image_stride;
+    float* __restrict__ img1 = images + (size_t)f1 * a.image_stride;
+    const int32_t* __restrict__ dig = reinterpret_cast<const int32_t*>(taps);   // the digest rides in the unused `taps` slot
+
+    // The LDS image is the 16-mic chunk the digest was built for (mic m -> slot m % 16), used as TWO halves of 8 mics: while
+    // the waves sweep half h, each of them also writes its row of half h + 1 into the other half -- ONE barrier per 8 mics,
+    // and the staging stores (slow: 13 cycles per ds_write_b128 and wave on the LDS store path) run under other waves' adds
+    // instead of between two barriers with every SIMD idle.
+    // This wave stages row `wave` of every half: mic (wave >> 1) of the half, frame (wave & 1).
+    // Lane c holds half c's mic id (first 64 halves): the per-half prefetch is then one independent load.
+    const int vmic = (lane < n_half) ? mics[lane * HC + (wave >> 1)] : 0;
+    auto fetch = [&](int h) -> float4 {
+        const int mic = (h < kWave) ? __builtin_amdgcn_readlane(vmic, h) : mics[h * HC + (wave >> 1)];
+        const float* src = ((wave & 1) ? sig1 : sig0) + (size_t)mic * N;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (4 * lane < N) v = *reinterpret_cast<const float4*>(src + 4 * lane);
+        return v;
+    };
+    auto stage = [&](int h, const float4 v, bool wipe) {
+        float* row0 = lds + (((h & 1) * W) + wave) * G::kSlot;  // slot (h & 1) * 8 + (wave >> 1), frame wave & 1
+        const float py = dpp_prev(v.y), pz = dpp_prev(v.z), pw = dpp_prev(v.w);
+        write_copies<C>(row0, RS, LEAD, lane, v, py, pz, pw);
+        if (wipe) {
+            // the zero prefix: nothing but the parked rows of the power pass ever overwrites it, so only a group's first
+            // visit of a half restores it -- one store: lane -> (copy row lane / 14, quad lane % 14) of the C rows
+            static_assert((LEAD >> 2) * C <= kWave, "one lane per prefix quad");
+            constexpr int PQ = LEAD >> 2;
+            if (lane < PQ * C) reinterpret_cast<float4*>(row0 + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+
+    float4 st = fetch(0);
+    const int lb = 16 * lane + (int)(unsigned)(size_t)((__attribute__((address_space(3))) char*)lds);
+    BF_STAMP_DECL
+
+    for (int g0 = tile_begin; g0 < tile_end; g0 += kGroup) {
+        f32x2 acc[DW][2][2];
+#pragma unroll
+        for (int j = 0; j < DW; ++j)
+#pragma unroll
+            for (int f = 0; f < 2; ++f) { acc[j][f][0] = f32x2{0.0f, 0.0f}; acc[j][f][1] = f32x2{0.0f, 0.0f}; }
+
+        BF_STAMP(7);
+        __syncthreads();   // the previous group's parked rows have been summed
+        BF_STAMP(1);
+        stage(0, st, true);
+        st = fetch(1);
+        BF_STAMP(2);
+        __syncthreads();
+        BF_STAMP(3);
+
+        for (int h = 0; h < n_half; ++h) {
+            if (h + 1 < n_half) {
+                stage(h + 1, st, h == 0);                       // into the half whose sweeps ended before the last barrier
+                // request what is staged an iteration from now: half h + 2, or the next group's first half (the same rows)
+                if (h + 2 < n_half) st = fetch(h + 2);
+                else if (g0 + kGroup < tile_end) st = fetch(0);
+                BF_STAMP(2);
+            }
+            const int dw0 = g0 + wave * DW;                     // wave-uniform
+            if (dw0 < tile_end) {
+                const size_t grp = (size_t)(dw0 - a.dir_begin) / DW;
+                const int32_t* __restrict__ et = dig + (grp * M + (size_t)h * HC) * DW;
+                struct Entries { int e[DW]; };
+                auto request = [&](Entries& t, int m) {
+                    // (reads past the half's last mic stay inside the slack-padded table and are dropped)
+#pragma unroll
+                    for (int j = 0; j < DW; ++j) t.e[j] = et[m * DW + j];
+                };
+                Entries E[3];
+                Quad S0, S1;
+                S0.lo = S0.hi = S1.lo = S1.hi = f32x2{0.0f, 0.0f};
+                request(E[0], 0);
+                request(E[1], 1);
+                auto mic = [&](int m, auto kc) {
+                    constexpr int K = decltype(kc)::value, K2 = (K + 2) % 3;
+                    const Entries& cur = E[K];
+                    pair_pad_first(acc, S0, S1, cur.e[0], cur.e[1], lb);
+                    request(E[K2], m + 2);      // after the first statement's wait, so that it does not sit on these loads
+                    pair_pad_rest(acc, S0, S1, cur.e, lb);
+                };
+                using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+                static_assert(HC == 8, "eight mics: two trips of three and two more");
+#pragma unroll 1
+                for (int t = 0; t < 2; ++t) {
+                    mic(0, I0{}); mic(1, I1{}); mic(2, I2{});
+                    et += 3 * DW;
+                }
+                mic(0, I0{});
+                mic(1, I1{});
+            }
+            BF_STAMP(0);       // sweep -> waiting for the others
+            __syncthreads();   // half h is free, half h + 1 is staged
+            BF_STAMP(h + 1 < n_half ? 3 : 4);
+        }
+
+        // ---- k-ordered mean power (pad_and_sum.c:120-128), one frame at a time: the 16 waves park the squared means of their
+        // directions (row = direction; the rows alias the chunk buffer), then one direction per lane runs the sequential sum.
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            if (f == 1) {
+                __syncthreads();        // frame 0's rows have been summed
+                BF_STAMP(4);
+            }
+            auto park = [&](auto mul_c) {
+#pragma unroll
+                for (int j = 0; j < DW; ++j) {
+                    float* row = lds + (wave * DW + j) * kPark;
+                    const f32x2 a0 = acc[j][f][0], a1 = acc[j][f][1];
+                    float o0, o1, o2, o3;
+                    if constexpr (decltype(mul_c)::value) {
+                        o0 = a0.x * a.inv_n; o1 = a0.y * a.inv_n; o2 = a1.x * a.inv_n; o3 = a1.y * a.inv_n;
+                    } else {
+                        float fm = (float)M;
+                        asm volatile("" : "+v"(fm));   // not speculatable: keeps this path behind its branch
+                        o0 = a0.x / fm; o1 = a0.y / fm; o2 = a1.x / fm; o3 = a1.y / fm;
+                    }
+                    reinterpret_cast<float4*>(row)[lane] = make_float4(o0 * o0, o1 * o1, o2 * o2, o3 * o3);
+                }
+            };
+            if (__builtin_expect(a.n_is_pow2, 1)) park(std::true_type{}); else park(std::false_type{});
+            BF_STAMP(5);                // -> waiting
+            __syncthreads();
+            BF_STAMP(6);                // -> ordered sum (two waves; the others go on to the next barrier)
+            const int g = wave * kWave + lane;            // parked row of this lane
+            const int d = g0 + g;
+            if (g < kGroup && d < tile_end && (f == 0 || two)) {
+                // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
+                const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
+                const float* row = lds + g * kPark;
+                const float4* row4 = reinterpret_cast<const float4*>(row);
+                float sum = 0.0f;
+                int k = 0;
+                for (; k + 32 <= N; k += 32) {
+                    float4 v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = row4[(k >> 2) + u];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
+                }
+                for (; k < N; ++k) sum += row[k];
+                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
+            }
+        }
+    }
+    BF_STAMP(7);
+    BF_STAMP_FLUSH;
+}
+#undef BF_P_ACC
+#undef BF_P_PAD_STEP
+#undef BF_P_PAD_READ
+#undef BF_P_ADDR
+#undef BF_P_CHECK
+#undef BF_P_STUB
+
+// ==================================================================================================
+// Two frames per workgroup, frames INTERLEAVED sample by sample in the LDS rows (lerp, N <= 256; das_pair_kernel's successor).
+//
+// Every instruction costs a SIMD a quad-cycle, so what is left to gain on the sweep is instruction count.  With the
+// row of a mic holding (f0 s0, f1 s0, f0 s1, f1 s1, ..):
+//   * one ds_read_b128 brings two samples of BOTH frames: a (re)load is 4 LDS instructions instead of 8, and with lane l owning
+//     the sample pairs (2l, 2l+1) and (128+2l, 128+2l+1) every read covers 1 KiB of contiguous LDS (no bank conflicts; the
+//     16-byte lane stride of ds_read_b64 pairs was a two-way conflict on every read);
+//   * a register pair is (frame 0, frame 1) of one sample, so the packed operations are the same 8 per direction step, the
+//     lerp weight still one scalar operand for both lanes;
+//   * the quads live in HARD-WIRED registers v[96:111] (+ products v[112:119], address v120), named as clobbers: 16-byte reads
+//     need 4-register tuples whose halves the packed operations address, which inline-asm operands cannot express.  A mic is
+//     two statements -- S1: address, reads, wait, step 0;  S2: steps 1..7 with their tests and out-of-line re-reads -- and the
+//     quads must survive from S1 to S2 across the table requests the compiler places between them (scalar instructions only;
+//     tests/test_isa_hazards.py checks that nothing between the two markers touches a vector register).
+// Halves of 8 mics staged under the sweep, power pass, digest: as das_pair_kernel (digest offsets scaled for the 2-float samples).
+// (pad, which reads half as much to begin with, measured 2 % slower on interleaved rows: it runs das_pair_kernel)
+// (Pair2Geo: das_geometry.h)
+
+#define BF_I_ACC(n, j) [a##n##0] "+v"(acc[j][0]), [a##n##1] "+v"(acc[j][1]), [a##n##2] "+v"(acc[j][2]), [a##n##3] "+v"(acc[j][3])
+#define BF_I_READ                                                                                   \
+    "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[100:103], v120 offset:1024\n\t"                   \
+    "ds_read_b128 v[104:107], v120 offset:%[g0]\n\tds_read_b128 v[108:111], v120 offset:%[g1]\n\ts_waitcnt lgkmcnt(0)\n\t"
+#define BF_I_STEP(n, h, mods)                                                                       \
+    "v_pk_fma_f32 v[112:113], %[" #h "], v[104:105], v[96:97] " mods "\n\tv_pk_fma_f32 v[114:115], %[" #h "], v[106:107], v[98:99] " mods "\n\t" \
+    "v_pk_fma_f32 v[116:117], %[" #h "], v[108:109], v[100:101] " mods "\n\tv_pk_fma_f32 v[118:119], %[" #h "], v[110:111], v[102:103] " mods "\n\t" \
+    "v_pk_add_f32 %[a" #n "0], %[a" #n "0], v[112:113]\n\tv_pk_add_f32 %[a" #n "1], %[a" #n "1], v[114:115]\n\t" \
+    "v_pk_add_f32 %[a" #n "2], %[a" #n "2], v[116:117]\n\tv_pk_add_f32 %[a" #n "3], %[a" #n "3], v[118:119]\n\t"
+// A mic's first reads with direction step 0 behind them, each half of the step waiting only for its own reads (LDS returns in order;
+// a counted wait bounds the outstanding operations of any kind, hence the outstanding reads).
+#define BF_I_FIRST(h, mods)                                                                         \
+    "ds_read_b128 v[96:99], v120\n\tds_read_b128 v[104:107], v120 offset:%[g0]\n\t"                \
+    "ds_read_b128 v[100:103], v120 offset:1024\n\tds_read_b128 v[108:111], v120 offset:%[g1]\n\ts_waitcnt lgkmcnt(2)\n\t" \
+    "v_pk_fma_f32 v[112:113], %[" #h "], v[104:105], v[96:97] " mods "\n\tv_pk_fma_f32 v[114:115], %[" #h "], v[106:107], v[98:99] " mods "\n\t" \
+    "v_pk_add_f32 %[a00], %[a00], v[112:113]\n\tv_pk_add_f32 %[a01], %[a01], v[114:115]\n\ts_waitcnt lgkmcnt(0)\n\t" \
+    "v_pk_fma_f32 v[116:117], %[" #h "], v[108:109], v[100:101] " mods "\n\tv_pk_fma_f32 v[118:119], %[" #h "], v[110:111], v[102:103] " mods "\n\t" \
+    "v_pk_add_f32 %[a02], %[a02], v[116:117]\n\tv_pk_add_f32 %[a03], %[a03], v[118:119]\n\t"
+#define BF_I_EVEN "op_sel_hi:[0,1,1]"
+#define BF_I_ODD "op_sel:[1,0,0] op_sel_hi:[1,1,1]"
+#define BF_I_CHECK(n, ep, ec) "s_cmp_lg_u32 %[" #ec "], %[" #ep "]\n\ts_cbranch_scc1 .Lr" #n "_%=\n.Lb" #n "_%=:\n\t"
+#define BF_I_STUB(n, ec) ".Lr" #n "_%=:\n\tv_add_u32 v120, %[" #ec "], %[lb]\n\t" BF_I_READ "s_branch .Lb" #n "_%=\n"
+#define BF_I_CLOB "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", \
+                  "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120"
+
+// S1: a mic's first quads, read in place, and direction step 0
+// lerp_and_sum.c:50-56  out[k] += s[i] + h * (s[i+1] - s[i]),  i = k - p - 1   (gcc contracts it into one fma)
+__device__ __forceinline__ void pair2_first(f32x2 (&acc)[8][4], int e0, unsigned long long h01, int lbase)
+{
+    using G = Pair2Geo;
+    asm volatile("v_add_u32 v120, %[e0], %[lb]\n\t" BF_I_FIRST(h01, BF_I_EVEN) ";BF_S1_END"
+                 : BF_I_ACC(0, 0) : [e0] "s"(e0), [h01] "s"(h01), [lb] "v"(lbase), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024) : BF_I_CLOB);
+}
+// S2: direction steps 1..7, each behind the test of its LDS offset against the previous step's
+__device__ __forceinline__ void pair2_rest(f32x2 (&acc)[8][4], const int (&e)[8], const unsigned long long (&hp)[4], int lbase)
+{
+    using G = Pair2Geo;
+    asm volatile(";BF_S2_BEGIN\n\t"
+                 BF_I_CHECK(1, e0, e1) BF_I_STEP(1, h01, BF_I_ODD) BF_I_CHECK(2, e1, e2) BF_I_STEP(2, h23, BF_I_EVEN)
+                 BF_I_CHECK(3, e2, e3) BF_I_STEP(3, h23, BF_I_ODD) BF_I_CHECK(4, e3, e4) BF_I_STEP(4, h45, BF_I_EVEN)
+                 BF_I_CHECK(5, e4, e5) BF_I_STEP(5, h45, BF_I_ODD) BF_I_CHECK(6, e5, e6) BF_I_STEP(6, h67, BF_I_EVEN)
+                 BF_I_CHECK(7, e6, e7) BF_I_STEP(7, h67, BF_I_ODD)
+                 ".subsection 1\n" BF_I_STUB(1, e1) BF_I_STUB(2, e2) BF_I_STUB(3, e3) BF_I_STUB(4, e4) BF_I_STUB(5, e5) BF_I_STUB(6, e6) BF_I_STUB(7, e7)
+                 "\t.subsection 0"
+                 : BF_I_ACC(1, 1), BF_I_ACC(2, 2), BF_I_ACC(3, 3), BF_I_ACC(4, 4), BF_I_ACC(5, 5), BF_I_ACC(6, 6), BF_I_ACC(7, 7)
+                 : [e0] "s"(e[0]), [e1] "s"(e[1]), [e2] "s"(e[2]), [e3] "s"(e[3]), [e4] "s"(e[4]), [e5] "s"(e[5]), [e6] "s"(e[6]), [e7] "s"(e[7]), [lb] "v"(lbase),
+                   [h01] "s"(hp[0]), [h23] "s"(hp[1]), [h45] "s"(hp[2]), [h67] "s"(hp[3]), [g0] "n"(G::kDoff), [g1] "n"(G::kDoff + 1024)
+                 : "scc", BF_I_CLOB);
+}
+#undef BF_I_ACC
+#undef BF_I_READ
+#undef BF_I_FIRST
+#undef BF_I_STEP
+#undef BF_I_EVEN
+#undef BF_I_ODD
+#undef BF_I_CHECK
+#undef BF_I_STUB
+#undef BF_I_CLOB
+
+template <int ALGO>   // (lerp only: the parameter keeps the kernel's symbol, which the profiles and ISA checks name)
+__global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KArgs a)
+{
+    static_assert(ALGO == ALGO_LERP, "das_pair2_kernel: lerp (pad runs das_pair_kernel)");
+    using G = Pair2Geo;
+    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane_ = threadIdx.x & (kWave - 1), lane = lane_;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int tile, fpair;
+    tile_and_frame(a, &tile, &fpair);
+    const int f0 = 2 * fpair;
+    const bool two = f0 + 1 < a.n_frames;                      // an odd frame count: the last workgroup row computes its frame twice
+    const int f1 = two ? f0 + 1 : f0;
+    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
+    if (tile_begin >= a.dir_end) return;
+    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
+    const int M = a.n_mics, N = a.n_samples;                   // M % 16 == 0, N % 4 == 0, N <= 256 (plan_das)
+    const int n_half = M / HC;
+    const float* __restrict__ sig0 = signals + (size_t)f0 * a.m_total * N;
+    const float* __restrict__ sig1 = signals + (size_t)f1 * a.m_total * N;
+    float* __restrict__ img0 = images + (size_t)f0 * a.image_stride;
+    float* __restrict__ img1 = images + (size_t)f1 * a.image_stride;
+    const int32_t* __restrict__ dig = reinterpret_cast<const int32_t*>(taps);   // the digest rides in the unused `taps` slot
+
+    // Staging: waves w and w + 8 share mic (w & 7) of every half (both fetch its two frames): part 0 writes the sample rows, part 1
+    // the difference rows.  Lane c holds half c's mic id (first 64 halves).
+    const int my_mic = wave & 7, part = wave >> 3;
+    const int vmic = (lane < n_half) ? mics[lane * HC + my_mic] : 0;
+    struct Staged2 { float4 v0, v1; };
+    auto fetch = [&](int h) -> Staged2 {
+        const int mic = (h < kWave) ? __builtin_amdgcn_readlane(vmic, h) : mics[h * HC + my_mic];
+        Staged2 st;
+        st.v0 = make_float4(0.f, 0.f, 0.f, 0.f);
+        st.v1 = st.v0;
+        if (4 * lane < N) {
+            // scalar row base + one 32-bit lane offset (global_load saddr form): the per-lane 64-bit pointers of the two frames, hoisted out
+            // of the group loop, used to be spilled around the sweep (16 bytes of scratch per lane, stored once per workgroup and
+            // reloaded per group: WRITE_SIZE 5x the image bytes)
+            unsigned voff = 16u * (unsigned)lane;
+            asm volatile("" : "+v"(voff));                      // (opaque: or hipcc folds it back into two hoisted 64-bit lane pointers)
+            const char* r0 = reinterpret_cast<const char*>(sig0 + (size_t)mic * N);
+            const char* r1 = reinterpret_cast<const char*>(sig1 + (size_t)mic * N);
+            st.v0 = *reinterpret_cast<const float4*>(r0 + voff);
+            st.v1 = *reinterpret_cast<const float4*>(r1 + voff);
+        }
+        return st;
+    };
+    // rows of a mic: [s copy 0][s copy 1][d copy 0][d copy 1]; copy c holds sample i - c at position i; position i = floats 2 i, 2 i + 1
+    auto write_row = [&](float* row, const float4 x0, const float4 x1, float p0, float p1, bool shifted, int lane) {
+        float4* q = reinterpret_cast<float4*>(row + 2 * LEAD) + 2 * lane;
+        if (!shifted) {
+            q[0] = make_float4(x0.x, x1.x, x0.y, x1.y);
+            q[1] = make_float4(x0.z, x1.z, x0.w, x1.w);
+        } else {
+            q[0] = make_float4(p0, p1, x0.x, x1.x);
+            q[1] = make_float4(x0.y, x1.y, x0.z, x1.z);
+        }
+    };
+    auto stage = [&](int h, const Staged2& st, bool wipe) {
+        int lane = lane_;                                       // (opaque copy: the per-lane addresses are recomputed here, not hoisted)
+        asm volatile("" : "+v"(lane));
+        float* slot = lds + ((h & 1) * HC + my_mic) * G::kSlot;
+        float4 x0 = st.v0, x1 = st.v1;
+        float* rows = slot + part * C * RS;                     // the two rows this wave writes
+        if (part == 1) {
+            // D[i] = s[i+1] - s[i], the reference's own subtraction (lerp_and_sum.c:54); D[-1] stays 0 (prefix)
+            const float n0 = dpp_next(x0.x), n1 = dpp_next(x1.x);
+            x0 = make_float4(x0.y - x0.x, x0.z - x0.y, x0.w - x0.z, n0 - x0.w);
+            x1 = make_float4(x1.y - x1.x, x1.z - x1.y, x1.w - x1.z, n1 - x1.w);
+        }
+        const float p0 = dpp_prev(x0.w), p1 = dpp_prev(x1.w);   // the previous lane's last sample (0 in lane 0: the prefix)
+        write_row(rows, x0, x1, p0, p1, false, lane);
+        write_row(rows + RS, x0, x1, p0, p1, true, lane);
+        if (wipe) {
+            // the zero prefix (56 samples x 2 frames = 28 quads per row): only the parked rows of the power pass overwrite it
+            constexpr int PQ = LEAD >> 1;
+            static_assert(2 * PQ <= kWave, "one lane per prefix quad of two rows");
+            if (lane < 2 * PQ) reinterpret_cast<float4*>(rows + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+
+    BF_STAMP_DECL
+    Staged2 st = fetch(0);
+    const int lb = 16 * lane + (int)(unsigned)(size_t)((__attribute__((address_space(3))) char*)lds);
+
+    for (int g0 = tile_begin; g0 < tile_end; g0 += kGroup) {
+        f32x2 acc[DW][4];                                       // (frame 0, frame 1) of samples 2l, 2l+1, 128+2l, 128+2l+1
+#pragma unroll
+        for (int j = 0; j < DW; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[j][q] = f32x2{0.0f, 0.0f};
+
+        BF_STAMP(7);
+        __syncthreads();   // the previous group's parked rows have been summed
+        BF_STAMP(1);
+        stage(0, st, true);
+        st = fetch(1 % n_half);
+        BF_STAMP(2);
+        __syncthreads();
+        BF_STAMP(3);
+
+        const int dw0 = g0 + wave * DW;                         // wave-uniform
+        const bool busy = dw0 < tile_end;
+        const size_t grp = busy ? (size_t)(dw0 - a.dir_begin) / DW : 0;
+        for (int h = 0; h < n_half; ++h) {
+            if (h + 1 < n_half) {
+                stage(h + 1, st, h == 0);                       // into the half whose sweeps ended before the last barrier
+                if (h + 2 < n_half) st = fetch(h + 2);
+                else if (g0 + kGroup < tile_end) st = fetch(0);
+                BF_STAMP(2);
+            }
+            if (busy) {
+                const int32_t* __restrict__ et = dig + (grp * M + (size_t)h * HC) * DW;
+                const float* __restrict__ ht = reinterpret_cast<const float*>(dig) + a.digest_h_off + (grp * M + (size_t)h * HC) * DW;
+                struct Entries { int e[DW]; unsigned long long hp[DW / 2]; };
+                auto request = [&](Entries& t, int m) {
+                    // (reads past the half's last mic stay inside the slack-padded table and are dropped)
+#pragma unroll
+                    for (int j = 0; j < DW; ++j) t.e[j] = et[m * DW + j];
+#pragma unroll
+                    for (int j = 0; j < DW / 2; ++j) t.hp[j] = *reinterpret_cast<const unsigned long long*>(ht + m * DW + 2 * j);
+                };
+                Entries E[3];
+                request(E[0], 0);
+                request(E[1], 1);
+                auto mic = [&](int m, auto kc) {
+                    constexpr int K = decltype(kc)::value, K2 = (K + 2) % 3;
+                    const Entries& cur = E[K];
+                    pair2_first(acc, cur.e[0], cur.hp[0], lb);
+                    request(E[K2], m + 2);      // after the first statement's wait, so that it does not sit on these loads
+                    pair2_rest(acc, cur.e, cur.hp, lb);
+                };
+                using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+                static_assert(HC == 8, "eight mics: two trips of three and two more");
+#pragma unroll 1
+                for (int t = 0; t < 2; ++t) {
+                    mic(0, I0{}); mic(1, I1{}); mic(2, I2{});
+                    et += 3 * DW; ht += 3 * DW;
+                }
+                mic(0, I0{});
+                mic(1, I1{});
+                __builtin_amdgcn_s_waitcnt(0xC07F);             // the entries requested past the half's end have landed (and are dropped)
+            }
+            BF_STAMP(0);       // sweep -> waiting for the others
+            __syncthreads();   // half h is free, half h + 1 is staged
+            BF_STAMP(h + 1 < n_half ? 3 : 4);
+        }
+
+        // ---- k-ordered mean power (pad_and_sum.c:120-128), one frame at a time: the 16 waves park the squared means of their
+        // directions (row = direction, k in order; the rows alias the LDS image), then one direction per lane runs the sequential sum.
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            if (f == 1) {
+                __syncthreads();        // frame 0's rows have been summed
+                BF_STAMP(4);
+            }
+            auto park = [&](auto mul_c) __attribute__((always_inline)) {
+#pragma unroll
+                for (int j = 0; j < DW; ++j) {
+                    float* row = lds + (wave * DW + j) * kPark;
+                    const float x0 = f == 0 ? acc[j][0].x : acc[j][0].y, x1 = f == 0 ? acc[j][1].x : acc[j][1].y;
+                    const float x2 = f == 0 ? acc[j][2].x : acc[j][2].y, x3 = f == 0 ? acc[j][3].x : acc[j][3].y;
+                    float o0, o1, o2, o3;
+                    if constexpr (decltype(mul_c)::value) {
+                        o0 = x0 * a.inv_n; o1 = x1 * a.inv_n; o2 = x2 * a.inv_n; o3 = x3 * a.inv_n;
+                    } else {
+                        float fm = (float)M;
+                        asm volatile("" : "+v"(fm));   // not speculatable: keeps this path behind its branch
+                        o0 = x0 / fm; o1 = x1 / fm; o2 = x2 / fm; o3 = x3 / fm;
+                    }
+                    reinterpret_cast<float2*>(row)[lane] = make_float2(o0 * o0, o1 * o1);             // samples 2l, 2l+1
+                    reinterpret_cast<float2*>(row + 128)[lane] = make_float2(o2 * o2, o3 * o3);       // samples 128+2l, 128+2l+1
+                }
+            };
+            if (__builtin_expect(a.n_is_pow2, 1)) park(std::true_type{}); else park(std::false_type{});
+            BF_STAMP(5);                // -> waiting
+            __syncthreads();
+            BF_STAMP(6);                // -> ordered sum (two waves; the others go on to the next barrier)
+            int lane_o = lane;                            // (opaque: keeps the per-lane row address out of the registers the sweep needs)
+            asm volatile("" : "+v"(lane_o));
+            const int g = wave * kWave + lane_o;          // parked row of this lane
+            const int d = g0 + g;
+            if (g < kGroup && d < tile_end && (f == 0 || two)) {
+                // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
+                const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
+                const float* row = lds + g * kPark;
+                const float4* row4 = reinterpret_cast<const float4*>(row);
+                float sum = 0.0f;
+                int k = 0;
+                for (; k + 32 <= N; k += 32) {
+                    float4 v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = row4[(k >> 2) + u];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
+                }
+                for (; k < N; ++k) sum += row[k];
+                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
+            }
+        }
+    }
+    BF_STAMP(7);
+    BF_STAMP_FLUSH;
+}
+
+}  // namespace copies
+
+template <int ALGO>
+hipError_t launch_pair_algo(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
+{
+    constexpr bool kLerp = ALGO == ALGO_LERP;           // das_pair_kernel (pad) / das_pair2_kernel (lerp: frames interleaved in the rows)
+    using PG = std::conditional_t<kLerp, copies::Pair2Geo, copies::PairGeo>;
+    if (L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != PG::kMc || plan.row_stride != PG::kRs ||
+        plan.lead != PG::kLead || plan.interleaved != (kLerp ? 1 : 0) || (L.n_mics % 16) != 0)
+        return hipErrorInvalidValue;
+    auto kernel = [] { if constexpr (kLerp) return copies::das_pair2_kernel<ALGO>; else return copies::das_pair_kernel<ALGO>; }();
+    static int pair_scratch = -1;
+    const dim3 pair_grid((unsigned)plan.n_tiles * (unsigned)((frames + 1) / 2));
+    return launch_with_lds(kernel, pair_grid, dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream, &pair_scratch, L.signals, L.images, L.mics,
+                           L.tab.whole, L.tab.frac, reinterpret_cast<const float*>(L.tab.digest), make_args(L, plan));
+}
+
+}  // namespace
+
+hipError_t launch_pair(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
+{
+    switch (L.algo) {
+        case ALGO_PAD: return launch_pair_algo<ALGO_PAD>(L, plan, frames, stream);
+        case ALGO_LERP: return launch_pair_algo<ALGO_LERP>(L, plan, frames, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// Profiling build only: read and clear the phase totals of das_pair_kernel (16 counters; zeros in a production build).
+hipError_t read_phase_stamps(unsigned long long* out16, bool clear)
+{
+#ifdef BF_STAMPS
+    static unsigned long long all[64 * 16];
+    hipError_t e = hipMemcpyFromSymbol(all, HIP_SYMBOL(copies::g_stamps), sizeof(all));
+    if (e != hipSuccess) return e;
+    for (int i = 0; i < 16; ++i) { out16[i] = 0; for (int r = 0; r < 64; ++r) out16[i] += all[16 * r + i]; }
+    if (!clear) return e;
+    for (int i = 0; i < 64 * 16; ++i) all[i] = 0;
+    return hipMemcpyToSymbol(HIP_SYMBOL(copies::g_stamps), all, sizeof(all));
+#else
+    for (int i = 0; i < 16; ++i) out16[i] = 0;
+    (void)clear;
+    return hipSuccess;
+#endif
+}
+
+}  // namespace bf

@@ -2,7 +2,7 @@
 
 Per batch of B (audio window, camera frame) pairs, everything stays in HBM:
   0. (step_packets) datagram stream -> the B windows                 bf_ingest_stream_device (csrc/ingest_kernel.hip)
-  1. delay-and-sum power maps of the B windows                      bf_das_device           (csrc/das_kernels.hip)
+  1. delay-and-sum power maps of the B windows                      bf_das_device           (csrc/das_pair.hip, das_kernels.hip)
   2. colourise, upscale to the camera size, temporal blend, overlay  bf_heatmap_*_device     (csrc/heatmap_kernels.hip)
   3. YOLOv5s-shaped detector on the overlaid frames                  PyTorch-ROCm module graph, convolutions = csrc/conv_kernels.hip
                                                                      (float32 like the reference's predict call; half=True: float16)
