@@ -471,6 +471,39 @@ int bf_miso_stream_device(int algo, const float *d_signals, int m_total, int fra
 int bf_das_stream_device(int algo, const float *d_signals, int m_total, float *d_images, int image_stride, int frames, int hop,
                          const float *d_prev, const int *adaptive_array, int n, int dir_begin, int dir_end, void *stream);
 
+/* ---- band selection on the time-domain path: one FIR per band on every row of a frame batch, continuous across windows ----
+ * The time-domain maps and beams are broadband; delay-and-sum is linear, so ONE filter applied to every microphone row leaves all
+ * inter-microphone delays intact: a band-limited map is bf_das_device on filtered frames, band-limited audio is the same filter on
+ * the [frames][beams][N] output of bf_miso_device (far fewer rows than the microphones).
+ * d_signals : HIP device pointer, float32 [frames][rows][N_SAMPLES] (N = N_SAMPLES); `rows` is whatever the caller has --
+ *             the microphone rows of a frame batch, or frames x beams rows of beams (then frames = 1, or hop = 0).
+ * d_taps    : HIP DEVICE pointer, float32 [bands][n_taps]: h[b][t].
+ * d_out     : HIP device pointer, float32 [bands][frames][rows][N_SAMPLES].  Every element is written.
+ * Definition (builder-defined; there is no band selection on the reference's time-domain path):
+ *     out[b][f][r][j] = acc_T,   acc_0 = 0.0f,   acc_{t+1} = fmaf(h[b][t], x~_f[r][j - t], acc_t)   for t = 0 .. n_taps-1
+ * in that order, one float32 rounding per step (a single-rounding fused multiply-add, libm's fmaf), where
+ *     x~_f[r][i] = d_signals[f][r][i]                                 for 0 <= i < N
+ *     x~_f[r][i] = d_signals[f-1][r][hop + i]                         for i < 0, hop > 0, f >= 1  (frame f - 1 of the call)
+ *     x~_0[r][i] = d_prev[r][hop + i], or 0.0f when d_prev is NULL    for i < 0, hop > 0
+ *     x~_f[r][i] = 0.0f                                               for i < 0, hop == 0         (independent windows)
+ * `hop` is the distance in samples between the starts of consecutive frames and d_prev float32 [rows][N_SAMPLES] the unfiltered
+ * window that began `hop` samples before frame 0: bf_miso_stream_device's convention.  With n_taps - 1 <= hop the outputs of
+ * overlapping windows agree bit for bit where both exist (out[f][j] == out[f-1][j + hop]), so the filtered frames are again the
+ * windows of one stream -- of the filtered stream -- and may be handed to bf_das_stream_device / bf_miso_stream_device with
+ * the filtered previous window as their d_prev.
+ * The result does not depend on the internal blocking (a lane owns four consecutive outputs, all bands share the LDS reads),
+ * on the alignment of the pointers or on N % 4: every output's chain runs t = 0 .. n_taps-1 in order, taps past the last are
+ * skipped, not multiplied by zero.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: one launch; no allocation, no workspace, no atomics, no
+ *             synchronisation; graph-capturable from the first call.  d_prev and d_taps are read by the launch.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_signals, d_taps or d_out null; rows, frames, bands or
+ * n_taps < 1; bands > BF_BAND_MAX_BANDS; n_taps > N_SAMPLES; hop < 0; hop > N_SAMPLES; hop > 0 with n_taps - 1 > hop; d_out's byte
+ * range overlapping that of d_signals or d_prev (frame f - 1 is read while frame f is written); no GPU.  All arguments are
+ * checked before device bring-up. */
+#define BF_BAND_MAX_BANDS 16
+int bf_band_filter_device(const float *d_signals, int rows, int frames, int hop, const float *d_prev,
+                          const float *d_taps, int n_taps, int bands, float *d_out, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

@@ -1397,6 +1397,49 @@ int bf_fuse_boxes_device(const float* d_power, int frames, int image_stride, int
                                         d_src_offsets, n_src, d_peak_offsets, d_peak_power, d_center_offsets, d_rects, d_src_box, d_counts, as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- band selection on the time-domain path
+
+// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (Sizes saturate: four ints and N_SAMPLES can pass 2^64.)
+static bool ranges_overlap(const void* a, unsigned long long a_bytes, const void* b, unsigned long long b_bytes)
+{
+    const unsigned long long top = std::numeric_limits<unsigned long long>::max();
+    const unsigned long long a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    const unsigned long long a1 = a_bytes > top - a0 ? top : a0 + a_bytes, b1 = b_bytes > top - b0 ? top : b0 + b_bytes;
+    return a0 < b1 && b0 < a1;
+}
+
+int bf_band_filter_device(const float* d_signals, int rows, int frames, int hop, const float* d_prev, const float* d_taps, int n_taps, int bands, float* d_out,
+                          void* stream)
+{
+    static const char* who = "bf_band_filter_device";
+    static_assert(BF_BAND_MAX_BANDS == bf::kBandMaxBands, "the header's limit is the kernel's");
+    Entered in;
+    const int N = in.s.sz.n_samples;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {d_taps, "d_taps"}, {d_out, "d_out"}})) return -1;
+    if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "bands", bands, 1) || !need_min(who, "n_taps", n_taps, 1)) return -1;
+    if (!need_max(who, "bands", bands, BF_BAND_MAX_BANDS)) return -1;
+    if (n_taps > N) { set_error("%s: n_taps = %d > N_SAMPLES = %d", who, n_taps, N); return -1; }
+    if (!need_min(who, "hop", hop, 0)) return -1;
+    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return -1; }
+    if (hop > 0 && n_taps - 1 > hop) {
+        set_error("%s: the filter needs n_taps - 1 = %d samples of history but hop = %d (continuous mode wants n_taps - 1 <= hop)", who, n_taps - 1, hop);
+        return -1;
+    }
+    {
+        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
+        auto mul = [top](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
+        const unsigned long long frame_bytes = mul((unsigned long long)rows * N, sizeof(float));
+        const unsigned long long in_bytes = mul(frame_bytes, (unsigned long long)frames), out_bytes = mul(in_bytes, (unsigned long long)bands);
+        if (ranges_overlap(d_out, out_bytes, d_signals, in_bytes)) {
+            set_error("%s: d_out overlaps d_signals (frame f - 1 is read while frame f is written)", who);
+            return -1;
+        }
+        if (d_prev && ranges_overlap(d_out, out_bytes, d_prev, frame_bytes)) { set_error("%s: d_out overlaps d_prev", who); return -1; }
+    }
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_band_filter(d_signals, rows, frames, N, hop, d_prev, d_taps, n_taps, bands, d_out, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

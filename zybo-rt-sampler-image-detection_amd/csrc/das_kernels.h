@@ -164,6 +164,14 @@ hipError_t launch_fuse_boxes(const float* d_power, int frames, int image_stride,
                              const int* d_box_counts, int max_boxes, int img_w, int img_h, float conf, const int* d_src_offsets, int n_src,
                              int* d_peak_offsets, float* d_peak_power, int* d_center_offsets, int* d_rects, int* d_src_box, int* d_counts, hipStream_t stream);
 
+// bf_band_filter_device (band_filter.hip): `bands` FIRs of n_taps taps (d_taps float32 [bands][n_taps]) on every row of d_signals float32
+// [frames][rows][n_samples] -> d_out float32 [bands][frames][rows][n_samples].  The n_taps - 1 samples before a row come from the
+// frame before it (`hop` samples earlier; d_prev float32 [rows][n_samples] for frame 0, null = silence), hop 0 = zeros for every frame.
+// One launch; no workspace.  d_out must not overlap the inputs (frame f - 1 is read while frame f is written).
+constexpr int kBandMaxBands = 16;
+hipError_t launch_band_filter(const float* d_signals, int rows, int frames, int n_samples, int hop, const float* d_prev, const float* d_taps, int n_taps,
+                              int bands, float* d_out, hipStream_t stream);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);
