@@ -504,6 +504,50 @@ int bf_das_stream_device(int algo, const float *d_signals, int m_total, float *d
 int bf_band_filter_device(const float *d_signals, int rows, int frames, int hop, const float *d_prev,
                           const float *d_taps, int n_taps, int bands, float *d_out, void *stream);
 
+/* ---- filter-and-sum beams: one FIR per (beam, microphone), then a sum over the microphones ----
+ * Every beam of bf_miso_device / bf_miso_stream_device is delay-and-sum: one whole-sample or lerp delay per microphone from the loaded
+ * table, which has no gain control over any direction but its own.  Any FIXED beamformer -- null steering (LCMV), superdirective, MVDR
+ * weights frozen over a batch -- is a filter-and-sum: this call takes the filters as taps and leaves their design to the caller
+ * (filtersum.design_lcmv is one).  The loaded tables play no part.
+ * d_signals : HIP device pointer, float32 [frames][m_total][N_SAMPLES] (N = N_SAMPLES), as bf_miso_device takes it.
+ * adaptive_array / n : HOST array of the active rows, as in bf_miso_device: cached on the device, a new array synchronises the
+ *             device once.
+ * d_taps    : HIP DEVICE pointer, float32 [beams][n][n_taps]: g[b][m][t] is tap t of active microphone m (row r_m = adaptive_array[m])
+ *             for beam b.
+ * d_out     : HIP device pointer, float32 [frames][beams][out_stride], out_stride >= N_SAMPLES.  Floats past N_SAMPLES in a row are
+ *             left untouched, every other element is written.
+ * hop, d_prev : bf_band_filter_device's convention.  d_prev is float32 [m_total][N_SAMPLES] or NULL, and
+ *     x~_f[r][i] = d_signals[f][r][i]                                 for 0 <= i < N
+ *     x~_f[r][i] = d_signals[f-1][r][hop + i]                         for i < 0, hop > 0, f >= 1  (frame f - 1 of the call)
+ *     x~_0[r][i] = d_prev[r][hop + i], or 0.0f when d_prev is NULL    for i < 0, hop > 0
+ *     x~_f[r][i] = 0.0f                                               for i < 0, hop == 0         (independent windows)
+ * Definition, in float32, nothing contracted except the written fmaf (single rounding, libm's fmaf):
+ *     c_m[j]       = acc_T,  acc_0 = 0.0f,  acc_{t+1} = fmaf(g[b][m][t], x~_f[r_m][j - t], acc_t)   t = 0 .. n_taps-1, in that order
+ *     out[f][b][j] = s_n,    s_0 = 0.0f,    s_{m+1} = s_m + c_m[j]                                   m = 0 .. n-1, in that order
+ * A tap past the last is skipped, never multiplied by zero.  Two consequences:
+ *   - with g[b][m][t] = (t == p_m) and finite samples, hop == 0 gives miso_pad / bf_miso_device(BF_PAD, mic_gain 0) at the delay
+ *     row p bit for bit (a delta chain hands the sample through unchanged, and both sums start at +0.0f in microphone order);
+ *   - with hop > 0 and max p_m + 1 <= n_taps <= hop + 1 the same taps give bf_miso_stream_device(BF_PAD) bit for bit.
+ * With n_taps - 1 <= hop the outputs of overlapping windows agree bit for bit where both exist (out[f][b][j] == out[f-1][b][j + hop]).
+ * The result does not depend on the internal blocking (a workgroup takes 256 outputs of one beam and deals the microphones round
+ * its waves; a lane owns four consecutive outputs), on which wave computes which microphone (the c_m are parked and added by one
+ * owner in microphone order, never accumulated where they are computed), on the alignment of the pointers, on N % 4 or on the
+ * number of beams launched together.  bf_filter_sum_waves(1 | 2 | 4 | 8 | 16) pins the waves of a workgroup for measurements (0: the
+ * launch decides, the default; returns the previous value, -1 for another argument): the result is the same for each.  It is a
+ * process-global measurement switch, not a tuning interface: it changes the launch shape of every later call, captures included.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: one launch; no allocation after the first call, no workspace, no atomics;
+ *             a new adaptive array synchronises the device; graph-capturable after one warm-up call, as bf_miso_device.  d_prev and
+ *             d_taps are read by the launch.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_signals, adaptive_array, d_taps or d_out null; frames, n,
+ * beams or n_taps < 1; beams > BF_FILTER_SUM_MAX_BEAMS; n_taps > N_SAMPLES; hop < 0; hop > N_SAMPLES; hop > 0 with n_taps - 1 > hop;
+ * out_stride < N_SAMPLES; an adaptive_array row outside [0, m_total); d_out's byte range (its first float to the last one written)
+ * overlapping that of d_signals, d_prev or d_taps; no GPU.  All arguments are checked before device bring-up. */
+#define BF_FILTER_SUM_MAX_BEAMS 16
+int bf_filter_sum_device(const float *d_signals, int m_total, int frames, int hop, const float *d_prev,
+                         const int *adaptive_array, int n, const float *d_taps, int n_taps, int beams,
+                         float *d_out, int out_stride, void *stream);
+int bf_filter_sum_waves(int waves);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

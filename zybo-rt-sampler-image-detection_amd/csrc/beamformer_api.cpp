@@ -1440,6 +1440,49 @@ int bf_band_filter_device(const float* d_signals, int rows, int frames, int hop,
     return HIP_RC(bf::launch_band_filter(d_signals, rows, frames, N, hop, d_prev, d_taps, n_taps, bands, d_out, as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- filter-and-sum beams: one FIR per (beam, microphone)
+
+int bf_filter_sum_device(const float* d_signals, int m_total, int frames, int hop, const float* d_prev, const int* adaptive_array, int n, const float* d_taps,
+                         int n_taps, int beams, float* d_out, int out_stride, void* stream)
+{
+    static const char* who = "bf_filter_sum_device";
+    static_assert(BF_FILTER_SUM_MAX_BEAMS == bf::kFilterSumMaxBeams, "the header's limit is the kernel's");
+    Entered in;
+    const int N = in.s.sz.n_samples;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_taps, "d_taps"}, {d_out, "d_out"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "n", n, 1) || !need_min(who, "beams", beams, 1) || !need_min(who, "n_taps", n_taps, 1)) return -1;
+    if (!need_max(who, "beams", beams, BF_FILTER_SUM_MAX_BEAMS)) return -1;
+    if (n_taps > N) { set_error("%s: n_taps = %d > N_SAMPLES = %d", who, n_taps, N); return -1; }
+    if (!need_min(who, "hop", hop, 0)) return -1;
+    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return -1; }
+    if (hop > 0 && n_taps - 1 > hop) {
+        set_error("%s: the filters need n_taps - 1 = %d samples of history but hop = %d (continuous mode wants n_taps - 1 <= hop)", who, n_taps - 1, hop);
+        return -1;
+    }
+    if (!need_min(who, "out_stride", out_stride, "N_SAMPLES", N) || !need_rows(who, adaptive_array, n, m_total)) return -1;
+    {
+        // d_out's range runs from its first float to the last one written: the floats behind the last row's N_SAMPLES are not part of it
+        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
+        auto mul = [](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
+        const unsigned long long frame_bytes = mul((unsigned long long)m_total * N, sizeof(float));
+        const unsigned long long in_bytes = mul(frame_bytes, (unsigned long long)frames);
+        const unsigned long long tap_bytes = mul(mul((unsigned long long)beams * n, (unsigned long long)n_taps), sizeof(float));
+        const unsigned long long out_rows = (unsigned long long)frames * beams;
+        const unsigned long long gaps = mul(mul(out_rows - 1, (unsigned long long)out_stride), sizeof(float));
+        const unsigned long long out_bytes = gaps > top - N * sizeof(float) ? top : gaps + N * sizeof(float);
+        if (ranges_overlap(d_out, out_bytes, d_signals, in_bytes)) { set_error("%s: d_out overlaps d_signals", who); return -1; }
+        if (d_prev && ranges_overlap(d_out, out_bytes, d_prev, frame_bytes)) { set_error("%s: d_out overlaps d_prev", who); return -1; }
+        if (ranges_overlap(d_out, out_bytes, d_taps, tap_bytes)) { set_error("%s: d_out overlaps d_taps", who); return -1; }
+    }
+    if (!ensure_device()) return -1;
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    return HIP_RC(bf::launch_filter_sum(d_signals, m_total, frames, N, hop, d_prev, in.s.d_mics.p, n, d_taps, n_taps, beams, d_out, out_stride, in.s.n_cus,
+                                        as_stream(stream)));
+}
+
+int bf_filter_sum_waves(int waves) { return bf::filter_sum_waves(waves); }
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

@@ -172,6 +172,18 @@ constexpr int kBandMaxBands = 16;
 hipError_t launch_band_filter(const float* d_signals, int rows, int frames, int n_samples, int hop, const float* d_prev, const float* d_taps, int n_taps,
                               int bands, float* d_out, hipStream_t stream);
 
+// bf_filter_sum_device (filter_sum.hip): `beams` filter-and-sum beams of the n microphone rows d_mics (int32, device) of d_signals float32
+// [frames][m_total][n_samples]: d_taps float32 [beams][n][n_taps], one FIR per (beam, microphone), the filtered rows summed in
+// microphone order -> d_out float32 [frames][beams][out_stride] (floats past n_samples of a row untouched).  hop / d_prev as
+// launch_band_filter.  One launch; no workspace, no atomics.  d_out must not overlap the inputs.  n_cus: compute units of the device
+// (a batch that leaves most of them idle splits its microphones over more waves).
+constexpr int kFilterSumMaxBeams = 16;
+hipError_t launch_filter_sum(const float* d_signals, int m_total, int frames, int n_samples, int hop, const float* d_prev, const int32_t* d_mics, int n,
+                             const float* d_taps, int n_taps, int beams, float* d_out, int out_stride, int n_cus, hipStream_t stream);
+// Waves of a filter-and-sum workgroup: 1, 2, 4, 8 or 16 pins them (the launch still halves what the LDS cannot hold), 0 gives the
+// choice back to the launch.  Returns the previous value, -1 for any other argument.  The result does not depend on it.
+int filter_sum_waves(int waves);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);

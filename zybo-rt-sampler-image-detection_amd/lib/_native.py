@@ -115,6 +115,9 @@ _sig("bf_track_sources_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, 
 _sig("bf_fuse_boxes_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("bf_band_filter_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
+_sig("bf_filter_sum_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, IP, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+     C.c_void_p)
+_sig("bf_filter_sum_waves", C.c_int, C.c_int)
 _sig("bf_plan_das", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))
 _sig("bf_ingest", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, FP)
 _sig("bf_ingest_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
