@@ -548,6 +548,52 @@ int bf_filter_sum_device(const float *d_signals, int m_total, int frames, int ho
                          float *d_out, int out_stride, void *stream);
 int bf_filter_sum_waves(int waves);
 
+/* ---- null-steering taps designed on the device: one row of slot offsets -> the [beams][n][n_taps] taps bf_filter_sum_device reads ----
+ * bf_peaks_device / bf_track_sources_device leave their offsets on the device and bf_filter_sum_device reads its taps there; this
+ * call is the link between them, so tracker -> designer -> filter-and-sum beams is one stream of launches (and one captured graph)
+ * with no host round trip when a source moves.  The design is filtersum.design_lcmv's, in float64 throughout (LCMV for spatially
+ * white noise, by frequency sampling); filtersum.design_slots is its host statement with the slot semantics below.  The loaded
+ * tables and the configured sizes play no part.
+ * d_tau     : HIP device pointer, float64 [dirs][n]: calculate_delays() reshaped, uploaded once by the caller.  Microphone m LEADS
+ *             by tau[d][m] samples (design_lcmv's convention).
+ * d_offsets : HIP device pointer, int32 [sources]: one row of what bf_peaks_device or bf_track_sources_device writes.  Slot i is a
+ *             SOURCE iff its entry is >= 0, a multiple of offset_per_dir and entry / offset_per_dir < dirs (the tracker's rule, as in
+ *             bf_fuse_boxes_device); its direction is entry / offset_per_dir.
+ * Beam i belongs to slot i; slots are NOT compacted, a tracker slot keeps its beam.  The look direction of beam i is slot i's, its
+ * nulls are every OTHER slot that is a source, tried in slot order.  A slot that is not a source gets all-zero taps (a silent beam),
+ * d_status[i] = 1, zero gains and zero kept entries; a designed slot gets d_status[i] = 0.
+ * bin_lo .. bin_hi (inclusive) are the in-band bins k of the n_taps-point grid (T = n_taps), K = bin_hi - bin_lo + 1 of them; the host
+ * computes them (filtersum.band_bins), no frequency is compared on the device.  For every beam i and in-band bin k:
+ *     w = 2 pi k / T,   c_d[m] = e^{+jw tau[d][m]}
+ *     a null is DROPPED at the bin iff |c^H c'| / n > rho against the look vector or against a null already kept at that bin
+ *     C = [c_look, kept nulls],  f = (e^{-jw(T-1)/2}, 0, ..),  u = C (C^H C)^{-1} conj(f),  G_k[m] = conj(u[m])
+ * the minimum-norm gains with H(w, look) = e^{-jw(T-1)/2} and H(w, kept null) = 0, and
+ *     g[i][m][t] = (1/T) sum_k s_k Re(G_k[m] e^{+j 2 pi k t / T})   over the in-band bins, in ascending k,
+ *     s_k = 1 for k = 0 and for k = T/2 with T even, 2 otherwise    (NumPy's irfft: the real part of a DC or Nyquist gain is kept)
+ * rounded once to float32.  Everything before that rounding is float64; sines and cosines are the device library's, the p x p
+ * system (p <= sources) is solved by a Cholesky factorisation, so gains agree with a host design to roundoff times the condition
+ * of C^H C, not bit for bit.  rho = 1 with two slots on one direction keeps a null the look vector cannot be told from: C^H C is
+ * singular and that beam's gains and taps are not finite; nothing else is affected.
+ * d_gains   : float64 [sources][K][n][2], (re, im) of G_k[m].  Required: it is the call's intermediate (the second launch reads
+ *             it) and an output a caller can inspect; because of it the call needs no workspace and allocates nothing.
+ * d_taps    : float32 [sources][n][n_taps], bf_filter_sum_device's layout for beams = sources.
+ * d_kept    : int32 [sources][K][sources]: 1 iff slot j is a kept null of beam i at that bin; the diagonal, slots that are no source
+ *             and dropped nulls are 0.
+ * d_status  : int32 [sources].
+ * Every entry of every output is written by every call.  The result does not depend on the number of slots designed together
+ * (slots behind the last source change nothing) and is the same bits from call to call.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: two launches (gains, then taps); no allocation, no synchronisation, no
+ *             atomics; graph-capturable from the first call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: any pointer null; dirs, n, sources, offset_per_dir or
+ * n_taps < 1; sources > BF_LCMV_MAX_SOURCES; sources > n (more constraints than microphones make C^H C singular); n_taps >
+ * BF_LCMV_MAX_TAPS; a bin range outside 0 <= bin_lo <= bin_hi <= n_taps / 2; rho not in (0, 1] (NaN included); the byte range of an
+ * output overlapping that of an input or of another output; no GPU.  All arguments are checked before device bring-up. */
+#define BF_LCMV_MAX_SOURCES 8
+#define BF_LCMV_MAX_TAPS 1024
+int bf_lcmv_design_device(const double *d_tau, int dirs, int n, const int *d_offsets, int sources, int offset_per_dir,
+                          int n_taps, int bin_lo, int bin_hi, double rho,
+                          double *d_gains, float *d_taps, int *d_kept, int *d_status, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

@@ -1483,6 +1483,49 @@ int bf_filter_sum_device(const float* d_signals, int m_total, int frames, int ho
 
 int bf_filter_sum_waves(int waves) { return bf::filter_sum_waves(waves); }
 
+// ---------------------------------------------------------------- null-steering taps designed on the device
+
+int bf_lcmv_design_device(const double* d_tau, int dirs, int n, const int* d_offsets, int sources, int offset_per_dir, int n_taps, int bin_lo, int bin_hi, double rho,
+                          double* d_gains, float* d_taps, int* d_kept, int* d_status, void* stream)
+{
+    static const char* who = "bf_lcmv_design_device";
+    static_assert(BF_LCMV_MAX_SOURCES == bf::kLcmvMaxSources && BF_LCMV_MAX_TAPS == bf::kLcmvMaxTaps, "the header's limits are the kernels'");
+    Entered in;
+    if (!need_ptrs(who, {{d_tau, "d_tau"}, {d_offsets, "d_offsets"}, {d_gains, "d_gains"}, {d_taps, "d_taps"}, {d_kept, "d_kept"}, {d_status, "d_status"}})) return -1;
+    if (!need_min(who, "dirs", dirs, 1) || !need_min(who, "n", n, 1) || !need_min(who, "sources", sources, 1) ||
+        !need_min(who, "offset_per_dir", offset_per_dir, 1) || !need_min(who, "n_taps", n_taps, 1))
+        return -1;
+    if (!need_max(who, "sources", sources, BF_LCMV_MAX_SOURCES)) return -1;
+    if (sources > n) {
+        set_error("%s: sources = %d > n = %d (more constraints than microphones make the system singular)", who, sources, n);
+        return -1;
+    }
+    if (!need_max(who, "n_taps", n_taps, BF_LCMV_MAX_TAPS)) return -1;
+    if (bin_lo < 0 || bin_hi < bin_lo || bin_hi > n_taps / 2) {
+        set_error("%s: bins [%d, %d] are not within 0 <= bin_lo <= bin_hi <= n_taps / 2 = %d", who, bin_lo, bin_hi, n_taps / 2);
+        return -1;
+    }
+    if (!(rho > 0.0 && rho <= 1.0)) { set_error("%s: rho = %.17g is not in (0, 1]", who, rho); return -1; }
+    {
+        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
+        auto mul = [](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
+        const unsigned long long S = (unsigned long long)sources, K = (unsigned long long)(bin_hi - bin_lo + 1);
+        struct Range { const void* p; unsigned long long bytes; const char* name; };
+        const Range r[] = {{d_gains, mul(mul(S * K, (unsigned long long)n), 2 * sizeof(double)), "d_gains"},
+                           {d_taps, mul(mul(S * (unsigned long long)n_taps, (unsigned long long)n), sizeof(float)), "d_taps"},
+                           {d_kept, S * K * S * sizeof(int), "d_kept"},
+                           {d_status, S * sizeof(int), "d_status"},
+                           {d_tau, mul(mul((unsigned long long)dirs, (unsigned long long)n), sizeof(double)), "d_tau"},
+                           {d_offsets, S * sizeof(int), "d_offsets"}};
+        for (int a = 0; a < 4; ++a)              // every output against the outputs behind it and both inputs
+            for (int b = a + 1; b < 6; ++b)
+                if (ranges_overlap(r[a].p, r[a].bytes, r[b].p, r[b].bytes)) { set_error("%s: %s overlaps %s", who, r[a].name, r[b].name); return -1; }
+    }
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_lcmv_design(d_tau, dirs, n, d_offsets, sources, offset_per_dir, n_taps, bin_lo, bin_hi, rho, d_gains, d_taps, d_kept, d_status,
+                                         as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

@@ -184,6 +184,15 @@ hipError_t launch_filter_sum(const float* d_signals, int m_total, int frames, in
 // choice back to the launch.  Returns the previous value, -1 for any other argument.  The result does not depend on it.
 int filter_sum_waves(int waves);
 
+// bf_lcmv_design_device (lcmv_design.hip): null-steering taps for launch_filter_sum, designed in float64 from one row of slot offsets.
+// d_tau float64 [dirs][n], d_offsets int32 [sources]; bins [bin_lo, bin_hi] of the n_taps-point grid, K of them -> d_gains float64
+// [sources][K][n][2] (the intermediate, and an output), d_taps float32 [sources][n][n_taps], d_kept int32 [sources][K][sources], d_status
+// int32 [sources].  Two launches (gains, then taps); no workspace, no atomics.  The outputs must not overlap the inputs or each other.
+constexpr int kLcmvMaxSources = 8;
+constexpr int kLcmvMaxTaps = 1024;
+hipError_t launch_lcmv_design(const double* d_tau, int dirs, int n, const int32_t* d_offsets, int sources, int offset_per_dir, int n_taps, int bin_lo, int bin_hi,
+                              double rho, double* d_gains, float* d_taps, int32_t* d_kept, int32_t* d_status, hipStream_t stream);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);

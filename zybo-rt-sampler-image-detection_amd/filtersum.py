@@ -12,9 +12,16 @@ Recipe, two talkers:
     fs_ = FilterSumListener.cross_null(tau, offs[0].cpu().numpy(), bl.offset_per_dir, hop=hop)    # beam i: source i heard, the others nulled
     out = fs_.listen(d_frames);  fs_.advance(d_frames);  audio = fs_.audio(out)                    # delayed by fs_.delay samples
 
-Limits of this step.  The design runs on the HOST: re-designing when a tracker moves a source is a host round trip.  Data-dependent
-(MVDR) weights are not designed here; a caller who has them passes `taps=` to FilterSumListener.  A device-side designer and an
-MVDR designer would reuse the kernel unchanged."""
+Beams that follow a tracker without a host round trip: `cross_null` needs the offsets on the host and designs there.  A listener
+built by `for_slots` keeps one beam per tracker slot and re-designs on the device (bf_lcmv_design_device: the same design, float64,
+written into the taps the beams read), so tracker -> designer -> beams is one stream of launches and captures into one graph:
+    fs_ = FilterSumListener.for_slots(tau, slots, bl.offset_per_dir, hop=hop)
+    offsets, ids, pos = tracker.update(offs)
+    status, kept = fs_.retarget(offsets[-1]);  out = fs_.listen(d_frames)                           # beam s: slot s heard, the other sources nulled
+`design_slots` is the host statement of that call: the fallback without a device, and what the tests hold the device to.
+
+Limits of this step.  Data-dependent (MVDR) weights are not designed here; a caller who has them passes `taps=` to
+FilterSumListener, and an MVDR designer would reuse the kernel unchanged."""
 import numpy as np
 
 from interface import config
@@ -22,6 +29,8 @@ from lib import _native as nat
 from listen import _entry, _fail, _torch
 
 MAX_BEAMS = 16
+MAX_SLOTS = 8           # BF_LCMV_MAX_SOURCES
+MAX_DESIGN_TAPS = 1024  # BF_LCMV_MAX_TAPS
 
 
 def band_bins(n_taps, band, fs=None):
@@ -96,6 +105,54 @@ def design_lcmv(tau, look, nulls=None, n_taps=65, band=(3000.0, 8000.0), rho=0.9
     return np.ascontiguousarray(taps, dtype=np.float32), kept
 
 
+def slot_directions(offsets, offset_per_dir, n_dirs):
+    """The direction of every slot of a row of offsets, -1 where the slot is no source: an entry is a source iff it is >= 0, a
+    multiple of offset_per_dir and names one of the n_dirs directions (the tracker's rule)."""
+    step = int(offset_per_dir)
+    if step < 1:
+        raise ValueError("offset_per_dir must be >= 1, got %d" % step)
+    return [int(o) // step if int(o) >= 0 and int(o) % step == 0 and int(o) // step < int(n_dirs) else -1 for o in np.asarray(offsets).ravel()]
+
+
+def design_slots(tau, offsets, offset_per_dir, n_taps=65, band=(3000.0, 8000.0), rho=0.95, fs=None):
+    """One beam per SLOT of a row of offsets (what BeamListener.sources / SourceTracker wrote), designed on the host in float64: the
+    statement of bf_lcmv_design_device (include/beamformer_hip.h), on top of design_lcmv.
+
+    Beam i belongs to slot i -- slots are not compacted as cross_null compacts them, a tracker slot keeps its beam.  Its look
+    direction is slot i's, its nulls are every other slot that is a source, tried in slot order.  A slot that is no source
+    (`slot_directions`) gets all-zero taps, status 1 and no kept entry; a designed slot gets status 0.
+    ->    (taps float32 [S, M, T], kept int32 [S, K, S], status int32 [S]);  kept[i][k][j] = 1 iff slot j is a kept null of beam i at
+          in-band bin k (the diagonal, slots that are no source and dropped nulls are 0)."""
+    tau = np.asarray(tau, dtype=np.float64)
+    if tau.ndim != 2:
+        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    dirs = slot_directions(offsets, offset_per_dir, tau.shape[0])
+    S, T = len(dirs), int(n_taps)
+    if S < 1:
+        raise ValueError("offsets is empty")
+    if S > tau.shape[1]:
+        raise ValueError("%d slots but %d microphones: more constraints than microphones make the system singular" % (S, tau.shape[1]))
+    if T < 1:
+        raise ValueError("n_taps must be >= 1, got %d" % T)
+    K = band_bins(T, band, fs).size
+    if K == 0:
+        raise ValueError("no bin of the %d-point grid lies in the band (%g, %g)" % (T, band[0], band[1]))
+    if not 0.0 < float(rho) <= 1.0:
+        raise ValueError("rho must be in (0, 1], got %g" % rho)
+    taps = np.zeros((S, tau.shape[1], T), dtype=np.float32)
+    kept = np.zeros((S, K, S), dtype=np.int32)
+    status = np.array([0 if d >= 0 else 1 for d in dirs], dtype=np.int32)
+    live = [i for i in range(S) if dirs[i] >= 0]
+    if live:
+        others = [[j for j in live if j != i] for i in live]
+        g, k = design_lcmv(tau, [dirs[i] for i in live], [[dirs[j] for j in row] for row in others], n_taps=T, band=band, rho=rho, fs=fs)
+        for b, i in enumerate(live):
+            taps[i] = g[b]
+            for col, j in enumerate(others[b]):
+                kept[i, :, j] = k[b, :, col]
+    return taps, kept, status
+
+
 def response(taps, tau_row, w):
     """H(w, d) of one beam in float64: taps [M, T], tau_row float64 [M] = tau[d], w rad/sample (a scalar or an array) -> complex, w's shape."""
     g = np.asarray(taps, dtype=np.float64)
@@ -146,6 +203,7 @@ class FilterSumListener:
         self.d_taps = _torch().from_numpy(g).to(device)
         self._prev = None
         self.dirs = self.kept = None                    # set by cross_null
+        self.d_tau = None                               # set by for_slots: the device-side designer's state
 
     @classmethod
     def cross_null(cls, tau, offsets, offset_per_dir, mics=None, hop=None, device="cuda", **design):
@@ -165,6 +223,61 @@ class FilterSumListener:
         self = cls(taps, mics=mics, hop=hop, device=device)
         self.dirs, self.kept = dirs, kept
         return self
+
+    @classmethod
+    def for_slots(cls, tau, slots, offset_per_dir, hop=None, n_taps=65, band=(3000.0, 8000.0), rho=0.95, fs=None, mics=None, device="cuda"):
+        """A listener with B = `slots` beams whose taps are designed ON THE DEVICE: beam s belongs to slot s of the offsets given to
+        `retarget` (design_slots' semantics).  The taps start at zero (silent beams); tau is uploaded once, the designer's outputs
+        (d_gains float64 [slots, K, M, 2], d_kept int32 [slots, K, slots], d_status int32 [slots]) are allocated once.  `.taps`, the
+        host copy, is None until `taps_host()` fetches it."""
+        torch = _torch()
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        if tau.ndim != 2:
+            raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+        S, T, step = int(slots), int(n_taps), int(offset_per_dir)
+        if S < 1 or S > MAX_SLOTS:
+            raise ValueError("1 .. %d slots, got %d" % (MAX_SLOTS, S))
+        if S > tau.shape[1]:
+            raise ValueError("%d slots but %d microphones: more constraints than microphones" % (S, tau.shape[1]))
+        if T < 1 or T > MAX_DESIGN_TAPS:
+            raise ValueError("1 .. %d taps, got %d" % (MAX_DESIGN_TAPS, T))
+        if step < 1:
+            raise ValueError("offset_per_dir must be >= 1, got %d" % step)
+        if not 0.0 < float(rho) <= 1.0:
+            raise ValueError("rho must be in (0, 1], got %g" % rho)
+        bins = band_bins(T, band, fs)
+        if bins.size == 0:
+            raise ValueError("no bin of the %d-point grid lies in the band (%g, %g)" % (T, band[0], band[1]))
+        self = cls(np.zeros((S, tau.shape[1], T), dtype=np.float32), mics=mics, hop=hop, device=device)
+        self.taps = None
+        self.bins, self.rho, self.offset_per_dir, self.n_dirs = bins, float(rho), step, int(tau.shape[0])
+        self.d_tau = torch.from_numpy(tau).to(device)
+        self.d_gains = torch.zeros((S, bins.size, self.n, 2), dtype=torch.float64, device=device)
+        self.d_kept = torch.zeros((S, bins.size, S), dtype=torch.int32, device=device)
+        self.d_status = torch.ones((S,), dtype=torch.int32, device=device)
+        return self
+
+    def retarget(self, d_offsets):
+        """Re-design every beam for the slots of d_offsets, an int32 cuda tensor [slots] -- offsets[-1] of SourceTracker.update, a row
+        of BeamListener.sources: enqueues bf_lcmv_design_device on the current stream, which writes self.d_taps IN PLACE (the address
+        a captured graph reads stays valid).  -> (d_status int32 [slots], d_kept int32 [slots, K, slots]), the listener's own tensors."""
+        torch = _torch()
+        if self.d_tau is None:
+            raise ValueError("retarget() needs a listener built by for_slots")
+        if d_offsets.dtype != torch.int32 or not d_offsets.is_cuda or tuple(d_offsets.shape) != (self.B,) or not d_offsets.is_contiguous():
+            raise ValueError("d_offsets must be a contiguous int32 cuda tensor [%d], got %s %s" % (self.B, d_offsets.dtype, tuple(d_offsets.shape)))
+        rc = _entry("bf_lcmv_design_device")(self.d_tau.data_ptr(), self.n_dirs, self.n, d_offsets.data_ptr(), self.B, self.offset_per_dir, self.T,
+                                             int(self.bins[0]), int(self.bins[-1]), self.rho, self.d_gains.data_ptr(), self.d_taps.data_ptr(),
+                                             self.d_kept.data_ptr(), self.d_status.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _fail("bf_lcmv_design_device")
+        self.taps = None
+        return self.d_status, self.d_kept
+
+    def taps_host(self):
+        """The taps the beams read now, fetched from the device (synchronises): float32 [B, M, T], also kept as `.taps`."""
+        self.taps = self.d_taps.cpu().numpy()
+        return self.taps
 
     def _frames(self, d_frames):
         torch = _torch()
