@@ -672,7 +672,7 @@ int bf_power_center_device(const float *d_power, int frames, float *d_centers, f
  *   bf_fd_das_power_device  P[f][d] = sum_k | sum_m X[k][m][f] a[k][m][d] |^2                                    -> float32 [F][D]
  *   bf_fd_covariance_device R[k] = (1/F) sum_f x x^H                                                              -> [K][M][M]
  *   bf_fd_cholesky_inverse_device  R += loading*tr(R)/M*I = L L^H;  writes inverse(L) transposed [K][col][row];  M <= 256 (two blocks of 128 above 128);
- *                           d_status int32 [K] (zeroed by the caller) receives j+1 where a pivot was not positive
+ *                           d_status int32 [K] (zeroed by the caller) receives the first column j (as j+1) whose pivot was not positive
  *   bf_fd_mvdr_power_device P[d] = sum_k 1 / || inverse(L_k) a[k][:, d] ||^2                                     -> float32 [D]
  *                           d_lire_t / d_liim_t are the planes bf_fd_cholesky_inverse_device writes, [K][col][row] of a LOWER-TRIANGULAR inverse: entries with
  *                           col > row are taken to be zero and whole 32 x 32 blocks of them are not multiplied at all

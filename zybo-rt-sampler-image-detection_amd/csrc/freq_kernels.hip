@@ -513,7 +513,7 @@ __global__ void __launch_bounds__(256) steering_kernel(const double* __restrict_
 // Generalised for the blocked factorisation of larger matrices: the M x M input block sits in a matrix of leading
 // dimension ld_in (one matrix of in_stride floats per bin), the transposed inverse goes to a block of leading dimension
 // ld_out, and the diagonal loading is either relative to this block's trace (load_abs == nullptr) or an absolute per-bin
-// value computed from the whole matrix.  `status_base` offsets the column index reported for a non-positive pivot.
+// value computed from the whole matrix.  `status_base` offsets the column index reported for the first non-positive pivot (status[b] is left alone once non-zero).
 __global__ void __launch_bounds__(256) cholesky_inverse_kernel(const float* __restrict__ rre, const float* __restrict__ rim, size_t in_stride, int ld_in, int M,
                                                                float loading, const float* __restrict__ load_abs, float* __restrict__ lire_t,
                                                                float* __restrict__ liim_t, size_t out_stride, int ld_out, int* __restrict__ status,
@@ -546,7 +546,7 @@ __global__ void __launch_bounds__(256) cholesky_inverse_kernel(const float* __re
     for (int j = 0; j < M; ++j) {
         __syncthreads();                       // column j and d_j are final
         const float d = Lr[j * LD + j];
-        if (t == 0 && !(d > 0.0f)) status[b] = status_base + j + 1;
+        if (t == 0 && !(d > 0.0f) && status[b] == 0) status[b] = status_base + j + 1;      // the first such column only (an earlier block's report stays too)
         const float invd = 1.0f / fmaxf(d, 1e-30f);
         // trailing update: A[i][c] -= a_ij conj(a_cj) / d_j,  j < c <= i
         for (int i = j + 1 + ti; i < M; i += 16) {
@@ -652,7 +652,7 @@ __global__ void __launch_bounds__(256) cholesky_inverse_reg_kernel(const float* 
             const int j = 16 * blk + jj, cur = j & 1;
             if (j >= M) return;                             // (uniform)
             const float d = colr[cur][j];
-            if (t == 0) { if (!(d > 0.0f)) status[b] = status_base + j + 1; rdiag[j] = 1.0f / sqrtf(fmaxf(d, 1e-30f)); }
+            if (t == 0) { if (!(d > 0.0f) && status[b] == 0) status[b] = status_base + j + 1; rdiag[j] = 1.0f / sqrtf(fmaxf(d, 1e-30f)); }   // the first such column only
             const float invd = 1.0f / fmaxf(d, 1e-30f);
             float sr[4], si[4], cr[4], ci[4];
 #pragma unroll
