@@ -594,6 +594,53 @@ int bf_lcmv_design_device(const double *d_tau, int dirs, int n, const int *d_off
                           int n_taps, int bin_lo, int bin_hi, double rho,
                           double *d_gains, float *d_taps, int *d_kept, int *d_status, void *stream);
 
+/* ---- adaptive (MVDR) taps designed on the device: the frames' own covariance -> the [beams][n][n_taps] taps bf_filter_sum_device reads ----
+ * bf_lcmv_design_device is geometry-only: a beam nulls a direction some slot names.  A talker under another one's main-lobe skirt, a
+ * reflection, a fan never get a slot.  This call designs the taps from the data: frames already on the device go in, the sample
+ * covariance of short segments of them is formed per bin, and every source slot gets the minimum-variance gains with unit response
+ * in its own direction (MVDR, one constraint per beam; the other slots are NOT hard nulls here).  filtersum.design_mvdr_slots is the
+ * host statement.  Everything before the taps' rounding to float32 is float64.  The loaded tables play no part.
+ * d_signals, m_total, adaptive_array, n : as bf_filter_sum_device (float32 [frames][m_total][N_SAMPLES]; HOST array of the n active rows
+ *             r_m, cached on the device, a new array synchronises the device once).  n <= BF_MVDR_MAX_MICS.
+ * d_tau, dirs, d_offsets, sources, offset_per_dir, the slot rule, bin_lo .. bin_hi and T = n_taps : as bf_lcmv_design_device.
+ *             K = bin_hi - bin_lo + 1, P = frames * segs.
+ * Snapshots.  p = f * segs + q; segment q starts at sample s = seg_first + q * seg_hop of window f; for k = bin_lo + kk
+ *     X_p[kk][m] = sum_t win[t] * (double)x_f[r_m][s + t] * e^{-j 2 pi ((k t) mod T) / T},   t = 0 .. T-1 in ascending order
+ *   with cos / sin(2 pi r / T) from a sincospi table indexed by the integer (k t) mod T.  win = d_window, float64 [T], NULL = all ones.
+ * Covariance.  R_k[a][b] = (1/P) sum_p X_p[a] conj(X_p[b]), one sequential chain per entry in ascending p, divided by P once;
+ *   computed for a >= b and mirrored: d_cov is EXACTLY Hermitian, its diagonal's imaginary part is exactly zero.
+ * Loading.  tr_k = sum_a R_k[a][a] in ascending a.  Finite and > 0: R'_k = R_k + (loading * tr_k / n) I, d_fallback[kk] = 0.  Otherwise
+ *   (silence, NaN or Inf samples): R'_k = I, d_fallback[kk] = 1, and the gains below are the no-null design's, c conj(f0) / n.
+ * Factor and solve.  R'_k = L L^H (Cholesky; an entry's subtractions run in ascending column order).  With w = 2 pi k / T, for every
+ *   source slot i and its look vector c[m] = e^{+jw tau[d_i][m]}:
+ *     y = L^{-1} c,  z = L^{-H} y,  den = sum_m |y_m|^2 (ascending m),  u = z conj(f0) / den,  f0 = e^{-jw(T-1)/2},  G_k[m] = conj(u[m])
+ *   which is u = R'^{-1} c conj(f0) / (c^H R'^{-1} c): H(w, look) = f0.  All slots share one factorisation per bin.  A loading so small
+ *   that R'_k is not numerically positive definite leaves that bin's gains (and the taps) not finite; nothing else is affected.
+ * Taps.  bf_lcmv_design_device's second stage on these gains (the same launch).  A slot that is no source gets zero taps, zero gains
+ *   and d_status 1; a designed slot d_status 0.
+ * Known limit: with the look talker in the frames at the interferer's level and any steering mismatch, sample-covariance MVDR cancels
+ * part of the look signal too (self-cancellation); the T-sample snapshot is a narrowband model and delays here reach 15 samples.
+ * Learn the covariance from frames in which the look talker is weak, or raise the loading.
+ * d_snap    : float64 [P][K][n][2].   d_cov, d_chol : float64 [K][n][n][2]; d_chol's lower triangle is L, its strict upper is 0.
+ * d_gains   : float64 [sources][K][n][2].   d_taps : float32 [sources][n][n_taps].   d_status : int32 [sources].   d_fallback : int32 [K].
+ * All seven are outputs a caller can inspect and the call's only workspace.  Every entry of every one is written by every call; the
+ * bits are the same from call to call and do not depend on the number of slots designed together.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: four launches (snapshots, covariance, factor and solve, taps); no
+ *             allocation after the first call, no atomics; a new adaptive array synchronises the device; graph-capturable after one
+ *             warm-up call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: any pointer except d_window null; frames, n, segs, seg_hop,
+ * dirs, sources, offset_per_dir or n_taps < 1; seg_first < 0; seg_first + (segs - 1) * seg_hop + n_taps > N_SAMPLES; n >
+ * BF_MVDR_MAX_MICS; sources > BF_LCMV_MAX_SOURCES; n_taps > BF_LCMV_MAX_TAPS; a bin range outside 0 <= bin_lo <= bin_hi <= n_taps / 2;
+ * loading not finite or <= 0; an adaptive_array row outside [0, m_total); the byte range of an output overlapping that of an input
+ * or of another output; no GPU.  All arguments are checked before device bring-up. */
+#define BF_MVDR_MAX_MICS 256
+int bf_mvdr_design_device(const float *d_signals, int m_total, int frames, const int *adaptive_array, int n,
+                          int seg_first, int seg_hop, int segs, const double *d_window,
+                          const double *d_tau, int dirs, const int *d_offsets, int sources, int offset_per_dir,
+                          int n_taps, int bin_lo, int bin_hi, double loading,
+                          double *d_snap, double *d_cov, double *d_chol, double *d_gains,
+                          float *d_taps, int *d_status, int *d_fallback, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

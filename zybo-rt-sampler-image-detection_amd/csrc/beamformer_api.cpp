@@ -1526,6 +1526,68 @@ int bf_lcmv_design_device(const double* d_tau, int dirs, int n, const int* d_off
                                          as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- adaptive (MVDR) taps designed on the device from the frames' covariance
+
+int bf_mvdr_design_device(const float* d_signals, int m_total, int frames, const int* adaptive_array, int n, int seg_first, int seg_hop, int segs,
+                          const double* d_window, const double* d_tau, int dirs, const int* d_offsets, int sources, int offset_per_dir, int n_taps, int bin_lo,
+                          int bin_hi, double loading, double* d_snap, double* d_cov, double* d_chol, double* d_gains, float* d_taps, int* d_status,
+                          int* d_fallback, void* stream)
+{
+    static const char* who = "bf_mvdr_design_device";
+    static_assert(BF_MVDR_MAX_MICS == bf::kMvdrMaxMics, "the header's limit is the kernels'");
+    Entered in;
+    const int N = in.s.sz.n_samples;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_tau, "d_tau"}, {d_offsets, "d_offsets"}, {d_snap, "d_snap"},
+                         {d_cov, "d_cov"}, {d_chol, "d_chol"}, {d_gains, "d_gains"}, {d_taps, "d_taps"}, {d_status, "d_status"}, {d_fallback, "d_fallback"}}))
+        return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "n", n, 1) || !need_min(who, "segs", segs, 1) || !need_min(who, "seg_hop", seg_hop, 1) ||
+        !need_min(who, "dirs", dirs, 1) || !need_min(who, "sources", sources, 1) || !need_min(who, "offset_per_dir", offset_per_dir, 1) ||
+        !need_min(who, "n_taps", n_taps, 1) || !need_min(who, "seg_first", seg_first, 0))
+        return -1;
+    if (!need_max(who, "n", n, BF_MVDR_MAX_MICS) || !need_max(who, "sources", sources, BF_LCMV_MAX_SOURCES) || !need_max(who, "n_taps", n_taps, BF_LCMV_MAX_TAPS))
+        return -1;
+    {
+        const long long last = (long long)seg_first + (long long)(segs - 1) * seg_hop + n_taps;
+        if (last > N) {
+            set_error("%s: seg_first + (segs - 1) * seg_hop + n_taps = %lld > N_SAMPLES = %d (a segment would leave its window)", who, last, N);
+            return -1;
+        }
+    }
+    if (bin_lo < 0 || bin_hi < bin_lo || bin_hi > n_taps / 2) {
+        set_error("%s: bins [%d, %d] are not within 0 <= bin_lo <= bin_hi <= n_taps / 2 = %d", who, bin_lo, bin_hi, n_taps / 2);
+        return -1;
+    }
+    if (!std::isfinite(loading) || !(loading > 0.0)) { set_error("%s: loading = %.17g is not finite and > 0", who, loading); return -1; }
+    if (!need_rows(who, adaptive_array, n, m_total)) return -1;
+    {
+        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
+        auto mul = [](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
+        const unsigned long long S = (unsigned long long)sources, K = (unsigned long long)(bin_hi - bin_lo + 1), M = (unsigned long long)n;
+        const unsigned long long P = (unsigned long long)frames * (unsigned long long)segs, cplx = 2 * sizeof(double);
+        struct Range { const void* p; unsigned long long bytes; const char* name; };
+        const Range r[] = {{d_snap, mul(mul(mul(P, K), M), cplx), "d_snap"},
+                           {d_cov, mul(K * M * M, cplx), "d_cov"},
+                           {d_chol, mul(K * M * M, cplx), "d_chol"},
+                           {d_gains, mul(S * K * M, cplx), "d_gains"},
+                           {d_taps, mul(S * (unsigned long long)n_taps * M, sizeof(float)), "d_taps"},
+                           {d_status, S * sizeof(int), "d_status"},
+                           {d_fallback, K * sizeof(int), "d_fallback"},
+                           {d_signals, mul(mul(mul((unsigned long long)frames, (unsigned long long)m_total), (unsigned long long)N), sizeof(float)), "d_signals"},
+                           {d_tau, mul(mul((unsigned long long)dirs, M), sizeof(double)), "d_tau"},
+                           {d_offsets, S * sizeof(int), "d_offsets"},
+                           {d_window, (unsigned long long)n_taps * sizeof(double), "d_window"}};
+        for (int a = 0; a < 7; ++a)              // every output against the outputs behind it and the inputs (d_window only where given)
+            for (int b = a + 1; b < 11; ++b)
+                if (r[b].p && ranges_overlap(r[a].p, r[a].bytes, r[b].p, r[b].bytes)) { set_error("%s: %s overlaps %s", who, r[a].name, r[b].name); return -1; }
+    }
+    if (!ensure_device()) return -1;
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    return HIP_RC(bf::launch_mvdr_design(d_signals, m_total, frames, N, in.s.d_mics.p, n, seg_first, seg_hop, segs, d_window, d_tau, dirs, d_offsets, sources,
+                                         offset_per_dir, n_taps, bin_lo, bin_hi, loading, d_snap, d_cov, d_chol, d_gains, d_taps, d_status, d_fallback,
+                                         as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

@@ -192,6 +192,21 @@ constexpr int kLcmvMaxSources = 8;
 constexpr int kLcmvMaxTaps = 1024;
 hipError_t launch_lcmv_design(const double* d_tau, int dirs, int n, const int32_t* d_offsets, int sources, int offset_per_dir, int n_taps, int bin_lo, int bin_hi,
                               double rho, double* d_gains, float* d_taps, int32_t* d_kept, int32_t* d_status, hipStream_t stream);
+// Its second launch on its own: gains float64 [sources][K][n][2] and the status the gains stage wrote -> d_taps (a beam whose status is
+// not 0 gets zeros).  bf_mvdr_design_device ends with it.
+hipError_t launch_lcmv_taps(const double* d_gains, const int32_t* d_status, int sources, int n, int n_taps, int bin_lo, int K, float* d_taps, hipStream_t stream);
+
+// bf_mvdr_design_device (mvdr_design.hip): adaptive taps for launch_filter_sum from the covariance of the frames themselves, float64.
+// Snapshots of n_taps samples (segment q of frame f starts at seg_first + q seg_hop; d_window float64 [n_taps] or null) -> d_snap float64
+// [frames * segs][K][n][2]; their covariance per bin -> d_cov float64 [K][n][n][2] (Hermitian bit for bit); the loaded matrix's Cholesky
+// factor -> d_chol float64 [K][n][n][2]; one MVDR solve per source slot -> d_gains float64 [sources][K][n][2]; launch_lcmv_taps -> d_taps.
+// d_fallback int32 [K]: 1 where the trace was not finite and > 0 and the identity stood in.  Four launches; no atomics, no workspace
+// beyond these buffers, which must not overlap the inputs or each other.  d_mics: the n rows (int32, device).
+constexpr int kMvdrMaxMics = 256;
+hipError_t launch_mvdr_design(const float* d_signals, int m_total, int frames, int n_samples, const int32_t* d_mics, int n, int seg_first, int seg_hop, int segs,
+                              const double* d_window, const double* d_tau, int dirs, const int32_t* d_offsets, int sources, int offset_per_dir, int n_taps,
+                              int bin_lo, int bin_hi, double loading, double* d_snap, double* d_cov, double* d_chol, double* d_gains, float* d_taps,
+                              int32_t* d_status, int32_t* d_fallback, hipStream_t stream);
 
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.

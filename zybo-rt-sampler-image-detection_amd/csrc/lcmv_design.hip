@@ -220,12 +220,18 @@ hipError_t launch_lcmv_design(const double* d_tau, int dirs, int n, const int32_
         bin_hi < bin_lo || bin_hi > n_taps / 2 || !(rho > 0.0 && rho <= 1.0))
         return hipErrorInvalidValue;
     const int K = bin_hi - bin_lo + 1;
-    const int mic_blocks = (n + kMicBlock - 1) / kMicBlock;
-    if ((long long)sources * mic_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lcmv_gains_kernel, dim3((unsigned)(sources * K)), dim3(kLanes), 0, stream, d_tau, d_offsets, dirs, n, sources, offset_per_dir, n_taps,
                        bin_lo, K, rho, d_gains, d_kept, d_status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_lcmv_taps(d_gains, d_status, sources, n, n_taps, bin_lo, K, d_taps, stream);
+}
+
+hipError_t launch_lcmv_taps(const double* d_gains, const int32_t* d_status, int sources, int n, int n_taps, int bin_lo, int K, float* d_taps, hipStream_t stream)
+{
+    if (sources < 1 || n < 1 || n_taps < 1 || n_taps > kLcmvMaxTaps || bin_lo < 0 || K < 1 || bin_lo + K - 1 > n_taps / 2) return hipErrorInvalidValue;
+    const int mic_blocks = (n + kMicBlock - 1) / kMicBlock;
+    if ((long long)sources * mic_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lcmv_taps_kernel, dim3((unsigned)(sources * mic_blocks)), dim3(kTapThreads), (size_t)n_taps * 2 * sizeof(double), stream, d_gains, d_status,
                        n, n_taps, bin_lo, K, mic_blocks, d_taps);
     return hipGetLastError();

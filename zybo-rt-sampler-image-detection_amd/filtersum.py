@@ -20,8 +20,12 @@ written into the taps the beams read), so tracker -> designer -> beams is one st
     status, kept = fs_.retarget(offsets[-1]);  out = fs_.listen(d_frames)                           # beam s: slot s heard, the other sources nulled
 `design_slots` is the host statement of that call: the fallback without a device, and what the tests hold the device to.
 
-Limits of this step.  Data-dependent (MVDR) weights are not designed here; a caller who has them passes `taps=` to
-FilterSumListener, and an MVDR designer would reuse the kernel unchanged."""
+Interference no slot names (a talker under another's main-lobe skirt, a reflection, a fan): `adapt` designs the same listener's taps
+from the covariance of the frames themselves (bf_mvdr_design_device: MVDR, unit response towards each slot, minimum output power):
+    status, fallback = fs_.adapt(d_frames, offsets[-1]);  out = fs_.listen(d_frames)
+`design_mvdr` / `design_mvdr_slots` are its host statements.  Limit: frames in which the look talker is as loud as the interference
+make sample-covariance MVDR cancel part of the look signal as well (self-cancellation); adapt on frames where it is weak.
+A caller with weights of their own passes `taps=` to FilterSumListener."""
 import numpy as np
 
 from interface import config
@@ -153,6 +157,122 @@ def design_slots(tau, offsets, offset_per_dir, n_taps=65, band=(3000.0, 8000.0),
     return taps, kept, status
 
 
+def _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_hop, segs, window, fs):
+    """The float64 statement of bf_mvdr_design_device up to the gains, for the directions `dirs` (-1: no source, zero gains).
+    -> (gains complex128 [B, K, M], fallback int32 [K], bins)."""
+    x = np.asarray(frames)
+    if x.ndim != 3 or x.dtype != np.float32:
+        raise ValueError("frames must be float32 [F, M_total, N], got %s %s" % (x.dtype, x.shape))
+    tau = np.asarray(tau, dtype=np.float64)
+    if tau.ndim != 2:
+        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    mics = np.asarray(mics).astype(np.int64).ravel()
+    F, m_total, N = x.shape
+    M, T = int(mics.size), int(n_taps)
+    if M < 1 or M != tau.shape[1]:
+        raise ValueError("mics lists %d rows, tau is for %d microphones" % (M, tau.shape[1]))
+    if mics.min() < 0 or mics.max() >= m_total:
+        raise ValueError("mics names a row outside the frames' %d rows" % m_total)
+    if T < 1 or T > N:
+        raise ValueError("n_taps must be in [1, N = %d], got %d" % (N, T))
+    seg_first, seg_hop = int(seg_first), int(seg_hop)
+    if seg_first < 0 or seg_hop < 1:
+        raise ValueError("seg_first must be >= 0 and seg_hop >= 1, got %d and %d" % (seg_first, seg_hop))
+    segs = (N - seg_first - T) // seg_hop + 1 if segs is None else int(segs)
+    if F < 1 or segs < 1 or seg_first + (segs - 1) * seg_hop + T > N:
+        raise ValueError("segments [%d + q * %d, + %d), q < %d, do not fit windows of %d samples" % (seg_first, seg_hop, T, segs, N))
+    loading = float(loading)
+    if not (np.isfinite(loading) and loading > 0.0):
+        raise ValueError("loading must be finite and > 0, got %g" % loading)
+    win = np.ones(T) if window is None else np.asarray(window, dtype=np.float64)
+    if win.shape != (T,):
+        raise ValueError("window must be [n_taps = %d], got shape %s" % (T, win.shape))
+    bins = band_bins(T, band, fs)
+    if bins.size == 0:
+        raise ValueError("no bin of the %d-point grid lies in the band (%g, %g)" % (T, band[0], band[1]))
+    for d in dirs:
+        if d >= tau.shape[0]:
+            raise ValueError("direction %d is outside tau's %d directions" % (d, tau.shape[0]))
+    K, P = bins.size, F * segs
+    r = np.arange(T)
+    table = np.cos(2.0 * np.pi * r / T) - 1j * np.sin(2.0 * np.pi * r / T)            # e^{-j 2 pi r / T}
+    E = table[(np.arange(T)[:, None] * bins[None, :]) % T]                           # [T, K]: the integer (k t) mod T picks the entry
+    snap = np.empty((P, K, M), dtype=np.complex128)
+    with np.errstate(all="ignore"):                                                  # NaN and Inf samples are an input like any other
+        for f in range(F):
+            for q in range(segs):
+                s0 = seg_first + q * seg_hop
+                seg = x[f][mics, s0:s0 + T].astype(np.float64) * win[None, :]
+                snap[f * segs + q] = (seg @ E).T
+        cov = np.einsum("pka,pkb->kab", snap, snap.conj()) / P
+        fallback = np.zeros(K, dtype=np.int32)
+        G = np.zeros((len(dirs), K, M), dtype=np.complex128)
+        for i, k in enumerate(bins):
+            tr = float(np.sum(cov[i].diagonal().real))
+            if np.isfinite(tr) and tr > 0.0:
+                loaded = cov[i] + (loading * tr / M) * np.eye(M)
+            else:
+                loaded = np.eye(M, dtype=np.complex128)
+                fallback[i] = 1
+            L = np.linalg.cholesky(loaded)
+            w = 2.0 * np.pi * k / T
+            for b, d in enumerate(dirs):
+                if d < 0:
+                    continue
+                c = np.exp(1j * w * tau[d])
+                y = np.linalg.solve(L, c)
+                z = np.linalg.solve(L.conj().T, y)
+                u = z * np.exp(1j * w * (T - 1) / 2.0) / np.sum(np.abs(y) ** 2)
+                G[b, i] = u.conj()
+    return G, fallback, bins
+
+
+def _taps_of_gains(G, bins, T):
+    """design_lcmv's last two lines: gains [B, K, M] on the whole grid, irfft, one rounding to float32 -> [B, M, T]."""
+    B, K, M = G.shape
+    full = np.zeros((B, M, T // 2 + 1), dtype=np.complex128)
+    full[:, :, bins] = G.transpose(0, 2, 1)
+    return np.ascontiguousarray(np.fft.irfft(full, n=T, axis=2), dtype=np.float32)
+
+
+def design_mvdr(frames, mics, tau, look, n_taps=65, band=(3000.0, 8000.0), loading=0.1, seg_first=0, seg_hop=16, segs=None, window=None, fs=None):
+    """Adaptive (MVDR) filter-and-sum taps from the covariance of the frames themselves, in float64: the host statement of
+    bf_mvdr_design_device (include/beamformer_hip.h has the definition) for the look directions `look`, one beam each.
+
+    frames float32 [F, M_total, N]; mics the M rows of a frame the beams use (tau's microphones, in its order); tau as design_lcmv.
+    Snapshots: the T = n_taps point DFT, at the in-band bins, of `window` (float64 [T], None: rectangular) times the T samples from
+    seg_first + q * seg_hop of every window, q < segs (None: as many as fit).  Per bin: R = mean of X X^H over the snapshots,
+    R' = R + (loading tr R / M) I, gains u = R'^{-1} c conj(f0) / (c^H R'^{-1} c) with c = e^{+jw tau[look]}, f0 = e^{-jw(T-1)/2}: unit
+    response towards `look`, minimum output power for THESE frames -- whatever interferes in them is suppressed without being named.
+    A bin whose trace is not finite and > 0 (silence, NaN, Inf) uses R' = I, design_lcmv's beam without nulls, and reports fallback 1.
+    ->    (taps float32 [B, M, T], fallback int32 [K]).
+
+    Limit: if the look talker is in the frames about as loud as the interference, any mismatch between c and its true wavefront
+    (the T-sample snapshot is a narrowband model; delays reach 15 samples) makes the design cancel part of it too."""
+    look = [int(d) for d in np.asarray(look).ravel()]
+    if not look:
+        raise ValueError("look is empty")
+    if min(look) < 0:
+        raise ValueError("direction %d is outside tau's directions" % min(look))
+    G, fallback, bins = _mvdr_gains(frames, mics, tau, look, n_taps, band, loading, seg_first, seg_hop, segs, window, fs)
+    return _taps_of_gains(G, bins, int(n_taps)), fallback
+
+
+def design_mvdr_slots(frames, mics, tau, offsets, offset_per_dir, n_taps=65, band=(3000.0, 8000.0), loading=0.1, seg_first=0, seg_hop=16, segs=None,
+                      window=None, fs=None):
+    """design_mvdr with design_slots' slot semantics: beam i looks at slot i of a row of offsets; a slot that is no source
+    (`slot_directions`) gets all-zero taps and status 1.  The other slots are not nulls of a beam -- only the data decides.
+    ->    (taps float32 [S, M, T], fallback int32 [K], status int32 [S])."""
+    tau = np.asarray(tau, dtype=np.float64)
+    if tau.ndim != 2:
+        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    dirs = slot_directions(offsets, offset_per_dir, tau.shape[0])
+    if not dirs:
+        raise ValueError("offsets is empty")
+    G, fallback, bins = _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_hop, segs, window, fs)
+    return _taps_of_gains(G, bins, int(n_taps)), fallback, np.array([0 if d >= 0 else 1 for d in dirs], dtype=np.int32)
+
+
 def response(taps, tau_row, w):
     """H(w, d) of one beam in float64: taps [M, T], tau_row float64 [M] = tau[d], w rad/sample (a scalar or an array) -> complex, w's shape."""
     g = np.asarray(taps, dtype=np.float64)
@@ -204,6 +324,7 @@ class FilterSumListener:
         self._prev = None
         self.dirs = self.kept = None                    # set by cross_null
         self.d_tau = None                               # set by for_slots: the device-side designer's state
+        self.d_snap = self.d_cov = self.d_chol = self.d_fallback = self._window = self._mvdr_key = None      # adapt's workspaces
 
     @classmethod
     def cross_null(cls, tau, offsets, offset_per_dir, mics=None, hop=None, device="cuda", **design):
@@ -273,6 +394,56 @@ class FilterSumListener:
             _fail("bf_lcmv_design_device")
         self.taps = None
         return self.d_status, self.d_kept
+
+    def adapt(self, d_frames, d_offsets, loading=0.1, seg_hop=16, window=None):
+        """Re-design every beam from the covariance of d_frames (float32 cuda [F, M_total, N_SAMPLES], what `listen` takes) with unit
+        response towards the slots of d_offsets (int32 cuda [slots], as `retarget`): enqueues bf_mvdr_design_device on the current
+        stream -- design_mvdr_slots' design -- which writes self.d_taps IN PLACE, where retarget writes and listen reads.
+        Segments of n_taps samples every seg_hop samples: of the whole window without a hop; with one, from max(0, N - hop - T + 1) on,
+        so consecutive overlapping windows never count one segment twice.  window: float64 [n_taps] or None (rectangular).  The
+        workspaces (d_snap, d_cov, d_chol) are allocated on the first call for a frame count and kept.
+        -> (d_status int32 [slots], d_fallback int32 [K]: 1 where a bin fell back to the beam without nulls), the listener's own tensors."""
+        torch = _torch()
+        if self.d_tau is None:
+            raise ValueError("adapt() needs a listener built by for_slots")
+        if d_offsets.dtype != torch.int32 or not d_offsets.is_cuda or tuple(d_offsets.shape) != (self.B,) or not d_offsets.is_contiguous():
+            raise ValueError("d_offsets must be a contiguous int32 cuda tensor [%d], got %s %s" % (self.B, d_offsets.dtype, tuple(d_offsets.shape)))
+        frames = self._frames(d_frames)
+        F, m_total, N = frames.shape
+        loading, seg_hop = float(loading), int(seg_hop)
+        if not (np.isfinite(loading) and loading > 0.0):
+            raise ValueError("loading must be finite and > 0, got %g" % loading)
+        if seg_hop < 1:
+            raise ValueError("seg_hop must be >= 1, got %d" % seg_hop)
+        seg_first = max(0, N - self.hop - self.T + 1) if self.hop > 0 else 0
+        segs = (N - seg_first - self.T) // seg_hop + 1
+        K = int(self.bins.size)
+        if window is None:
+            d_window = None
+        else:
+            win = np.ascontiguousarray(window, dtype=np.float64)
+            if win.shape != (self.T,):
+                raise ValueError("window must be [n_taps = %d], got shape %s" % (self.T, win.shape))
+            if self._window is None or not np.array_equal(self._window[0], win):
+                self._window = (win.copy(), torch.from_numpy(win).to(self.device))
+            d_window = self._window[1]
+        key = (F, segs)
+        if self._mvdr_key != key:
+            self.d_snap = torch.empty((F * segs, K, self.n, 2), dtype=torch.float64, device=self.device)
+            if self.d_cov is None:
+                self.d_cov = torch.empty((K, self.n, self.n, 2), dtype=torch.float64, device=self.device)
+                self.d_chol = torch.empty((K, self.n, self.n, 2), dtype=torch.float64, device=self.device)
+                self.d_fallback = torch.zeros((K,), dtype=torch.int32, device=self.device)
+            self._mvdr_key = key
+        rc = _entry("bf_mvdr_design_device")(frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, seg_first, seg_hop, segs,
+                                             None if d_window is None else d_window.data_ptr(), self.d_tau.data_ptr(), self.n_dirs, d_offsets.data_ptr(),
+                                             self.B, self.offset_per_dir, self.T, int(self.bins[0]), int(self.bins[-1]), loading, self.d_snap.data_ptr(),
+                                             self.d_cov.data_ptr(), self.d_chol.data_ptr(), self.d_gains.data_ptr(), self.d_taps.data_ptr(),
+                                             self.d_status.data_ptr(), self.d_fallback.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _fail("bf_mvdr_design_device")
+        self.taps = None
+        return self.d_status, self.d_fallback
 
     def taps_host(self):
         """The taps the beams read now, fetched from the device (synchronises): float32 [B, M, T], also kept as `.taps`."""
