@@ -21,9 +21,9 @@ Recipes.
 """
 import numpy as np
 
+from carried import CarriedFrame, check_frames
 from interface import config
-from lib import _native as nat
-from listen import _entry, _fail, _torch
+from lib._native import _torch, call
 
 MAX_BANDS = 16
 _WINDOWS = {"hamming": np.hamming, "hann": np.hanning, "blackman": np.blackman, "rect": np.ones}
@@ -60,12 +60,13 @@ def design(bands, n_taps=65, window="hamming", fs=None):
     return out.astype(np.float32)
 
 
-class BandFilter:
+class BandFilter(CarriedFrame):
     """K FIR band filters of n_taps taps on the rows of device frame batches.  `bands`: list of (f_lo, f_hi) in Hz (see `design`), or
     `taps=` a ready float32 [K, T] array instead of a design.  `hop`: samples between the starts of consecutive frames, as given to
     the ingest and to StreamBeamformer (None: independent windows, every window starts from silence -- BeamListener's convention).
     With a hop the carried state is one unfiltered frame, the last one of the batch before: `advance` sets it, `reset` clears it,
     the filtering calls only read it."""
+    _ROWS = ("R", 1)
 
     def __init__(self, bands=None, n_taps=65, hop=None, window="hamming", fs=None, device="cuda", taps=None):
         if (bands is None) == (taps is None):
@@ -91,42 +92,18 @@ class BandFilter:
             raise ValueError("n_taps - 1 = %d samples of history do not fit hop = %d" % (T - 1, hop))
         self.taps, self.K, self.T, self.hop, self.device = h, K, T, hop, device
         self.d_taps = _torch().from_numpy(h).to(device)
-        self._prev = None
 
-    def _rows(self, d_x, what):
-        torch = _torch()
-        if d_x.dim() != 3 or d_x.dtype != torch.float32 or not d_x.is_cuda or d_x.shape[2] != config.N_SAMPLES or d_x.shape[0] < 1 or d_x.shape[1] < 1:
-            raise ValueError("%s must be a float32 cuda tensor [F, R, %d], got %s %s" % (what, config.N_SAMPLES, d_x.dtype, tuple(d_x.shape)))
-        return d_x.contiguous()
-
-    def _run(self, x, frames, rows, hop, prev):
+    def _run(self, x, frames, rows, hop, prev_ptr):
         torch = _torch()
         out = torch.empty((self.K, frames, rows, config.N_SAMPLES), dtype=torch.float32, device=self.device)
-        rc = _entry("bf_band_filter_device")(x.data_ptr(), rows, frames, hop, None if prev is None else prev.data_ptr(), self.d_taps.data_ptr(), self.T,
-                                             self.K, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_band_filter_device")
+        call("bf_band_filter_device", x.data_ptr(), rows, frames, hop, prev_ptr, self.d_taps.data_ptr(), self.T, self.K, out.data_ptr())
         return out
 
     def frames(self, d_frames):
         """d_frames float32 cuda [F, R, N_SAMPLES] -> [K, F, R, N_SAMPLES]: every row filtered by every band; with a hop, frame f's
         history is frame f - 1, frame 0's the carried frame.  Does not change the carried state."""
-        x = self._rows(d_frames, "d_frames")
-        if self._prev is not None and self._prev.shape[0] != x.shape[1]:
-            raise ValueError("the carried frame has %d rows, d_frames %d: reset() before changing the frame layout" % (self._prev.shape[0], x.shape[1]))
-        return self._run(x, x.shape[0], x.shape[1], self.hop, self._prev if self.hop > 0 else None)
-
-    def advance(self, d_frames):
-        """Done with this batch: keep a copy of its last (unfiltered) frame as the history of the next batch's first frame."""
-        x = self._rows(d_frames, "d_frames")
-        if self._prev is None:
-            self._prev = x[-1].clone()
-        else:
-            self._prev.copy_(x[-1])           # in place: the address a captured graph reads stays valid
-
-    def reset(self):
-        """Forget the carried frame: the next batch starts a new stream (silence before it)."""
-        self._prev = None
+        x = self._frames(d_frames)
+        return self._run(x, x.shape[0], x.shape[1], self.hop, self._prev_ptr())
 
     def maps(self, bl, d_frames, dir_begin=0, dir_end=None):
         """Band-limited power maps [K, F, dir_end - dir_begin] of a BeamListener `bl`: filter, then ONE bl.maps call on the
@@ -138,6 +115,6 @@ class BandFilter:
     def beams(self, out):
         """out float32 cuda [F, B, N_SAMPLES] from listen() -> [K, F, B, N_SAMPLES]: every beam filtered as one row, each window on
         its own (from silence): beams of independent windows have no common stream to continue."""
-        x = self._rows(out, "out")
+        x = check_frames(out, "out", *self._ROWS)
         F, B, N = x.shape
         return self._run(x, 1, F * B, 0, None).view(self.K, F, B, N)

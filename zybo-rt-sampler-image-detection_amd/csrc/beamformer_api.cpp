@@ -273,6 +273,62 @@ bool need_dir_range(const char* who, int dir_begin, int dir_end, int n_dirs, int
     return true;
 }
 
+// A window may continue the one before it by `hop` samples, and no further than its own length.
+bool need_hop_max(const char* who, int hop, int N)
+{
+    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return false; }
+    return true;
+}
+
+// A FIR of n_taps over such windows: it fits one, hop = 0 means unrelated windows, and a continued window has the n_taps - 1 samples of history
+// in the one before it.  `subject` opens the last sentence ("the filter needs", "the filters need").
+bool need_fir_window(const char* who, int n_taps, int hop, int N, const char* subject)
+{
+    if (n_taps > N) { set_error("%s: n_taps = %d > N_SAMPLES = %d", who, n_taps, N); return false; }
+    if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, N)) return false;
+    if (hop > 0 && n_taps - 1 > hop) {
+        set_error("%s: %s n_taps - 1 = %d samples of history but hop = %d (continuous mode wants n_taps - 1 <= hop)", who, subject, n_taps - 1, hop);
+        return false;
+    }
+    return true;
+}
+
+// The band [bin_lo, bin_hi] of an n_taps-point grid.
+bool need_bins(const char* who, int bin_lo, int bin_hi, int n_taps)
+{
+    if (bin_lo < 0 || bin_hi < bin_lo || bin_hi > n_taps / 2) {
+        set_error("%s: bins [%d, %d] are not within 0 <= bin_lo <= bin_hi <= n_taps / 2 = %d", who, bin_lo, bin_hi, n_taps / 2);
+        return false;
+    }
+    return true;
+}
+
+// The bytes an argument covers.  Sizes saturate: four ints and N_SAMPLES can pass 2^64.
+using u64 = unsigned long long;
+constexpr u64 kTop = std::numeric_limits<u64>::max();
+u64 sat_mul(u64 a, u64 b) { return b && a > kTop / b ? kTop : a * b; }
+u64 sat_add(u64 a, u64 b) { return b > kTop - a ? kTop : a + b; }
+
+struct Span { const void* p; u64 bytes; const char* name; const char* note = ""; };   // (note: why this one must not be written, behind its name)
+
+// The first `n_outputs` spans are written.  Refuses the first pair (a, b), a an output and a < b, that shares a byte; an optional argument that
+// was not given (null) is skipped.
+bool need_disjoint(const char* who, std::initializer_list<Span> spans, int n_outputs)
+{
+    const Span* s = spans.begin();
+    const int count = (int)spans.size();
+    for (int a = 0; a < n_outputs; ++a)
+        for (int b = a + 1; b < count; ++b) {
+            if (!s[a].p || !s[b].p) continue;
+            const u64 a0 = reinterpret_cast<uintptr_t>(s[a].p), b0 = reinterpret_cast<uintptr_t>(s[b].p);
+            if (a0 < sat_add(b0, s[b].bytes) && b0 < sat_add(a0, s[a].bytes)) {
+                set_error("%s: %s overlaps %s%s", who, s[a].name, s[b].name, s[b].note);
+                return false;
+            }
+        }
+    return true;
+}
+
 // Calls that exist for BF_PAD and BF_LERP only; `reason` says why the other algorithms are refused (`with_number` adds the algo's value).
 bool need_pad_or_lerp(const char* who, int algo, bool with_number, const char* reason)
 {
@@ -1242,10 +1298,8 @@ int bf_remove_sources_device(int algo, const float* d_signals, int m_total, int 
 // What both stream calls check before device bring-up.  `who` names the entry point in the message.
 static bool stream_args_ok(const char* who, int algo, int m_total, int frames, int hop, const int* adaptive_array, int n)
 {
-    const int N = S().sz.n_samples;
     if (!need_pad_or_lerp(who, algo, false, "reads ahead of the window's end, which a causal stream cannot supply (continuous mode: BF_PAD, BF_LERP)")) return false;
-    if (!need_min(who, "frames", frames, 1) || !need_min(who, "hop", hop, 1)) return false;
-    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return false; }
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "hop", hop, 1) || !need_hop_max(who, hop, S().sz.n_samples)) return false;
     return need_min(who, "n", n, 1) && need_rows(who, adaptive_array, n, m_total);
 }
 
@@ -1399,15 +1453,6 @@ int bf_fuse_boxes_device(const float* d_power, int frames, int image_stride, int
 
 // ---------------------------------------------------------------- band selection on the time-domain path
 
-// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  (Sizes saturate: four ints and N_SAMPLES can pass 2^64.)
-static bool ranges_overlap(const void* a, unsigned long long a_bytes, const void* b, unsigned long long b_bytes)
-{
-    const unsigned long long top = std::numeric_limits<unsigned long long>::max();
-    const unsigned long long a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    const unsigned long long a1 = a_bytes > top - a0 ? top : a0 + a_bytes, b1 = b_bytes > top - b0 ? top : b0 + b_bytes;
-    return a0 < b1 && b0 < a1;
-}
-
 int bf_band_filter_device(const float* d_signals, int rows, int frames, int hop, const float* d_prev, const float* d_taps, int n_taps, int bands, float* d_out,
                           void* stream)
 {
@@ -1418,24 +1463,12 @@ int bf_band_filter_device(const float* d_signals, int rows, int frames, int hop,
     if (!need_ptrs(who, {{d_signals, "d_signals"}, {d_taps, "d_taps"}, {d_out, "d_out"}})) return -1;
     if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "bands", bands, 1) || !need_min(who, "n_taps", n_taps, 1)) return -1;
     if (!need_max(who, "bands", bands, BF_BAND_MAX_BANDS)) return -1;
-    if (n_taps > N) { set_error("%s: n_taps = %d > N_SAMPLES = %d", who, n_taps, N); return -1; }
-    if (!need_min(who, "hop", hop, 0)) return -1;
-    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return -1; }
-    if (hop > 0 && n_taps - 1 > hop) {
-        set_error("%s: the filter needs n_taps - 1 = %d samples of history but hop = %d (continuous mode wants n_taps - 1 <= hop)", who, n_taps - 1, hop);
+    if (!need_fir_window(who, n_taps, hop, N, "the filter needs")) return -1;
+    const u64 frame_bytes = sat_mul((u64)rows * N, sizeof(float)), in_bytes = sat_mul(frame_bytes, (u64)frames);
+    if (!need_disjoint(who, {{d_out, sat_mul(in_bytes, (u64)bands), "d_out"},
+                             {d_signals, in_bytes, "d_signals", " (frame f - 1 is read while frame f is written)"},
+                             {d_prev, frame_bytes, "d_prev"}}, 1))
         return -1;
-    }
-    {
-        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
-        auto mul = [top](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
-        const unsigned long long frame_bytes = mul((unsigned long long)rows * N, sizeof(float));
-        const unsigned long long in_bytes = mul(frame_bytes, (unsigned long long)frames), out_bytes = mul(in_bytes, (unsigned long long)bands);
-        if (ranges_overlap(d_out, out_bytes, d_signals, in_bytes)) {
-            set_error("%s: d_out overlaps d_signals (frame f - 1 is read while frame f is written)", who);
-            return -1;
-        }
-        if (d_prev && ranges_overlap(d_out, out_bytes, d_prev, frame_bytes)) { set_error("%s: d_out overlaps d_prev", who); return -1; }
-    }
     if (!ensure_device()) return -1;
     return HIP_RC(bf::launch_band_filter(d_signals, rows, frames, N, hop, d_prev, d_taps, n_taps, bands, d_out, as_stream(stream)));
 }
@@ -1452,28 +1485,15 @@ int bf_filter_sum_device(const float* d_signals, int m_total, int frames, int ho
     if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_taps, "d_taps"}, {d_out, "d_out"}})) return -1;
     if (!need_min(who, "frames", frames, 1) || !need_min(who, "n", n, 1) || !need_min(who, "beams", beams, 1) || !need_min(who, "n_taps", n_taps, 1)) return -1;
     if (!need_max(who, "beams", beams, BF_FILTER_SUM_MAX_BEAMS)) return -1;
-    if (n_taps > N) { set_error("%s: n_taps = %d > N_SAMPLES = %d", who, n_taps, N); return -1; }
-    if (!need_min(who, "hop", hop, 0)) return -1;
-    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return -1; }
-    if (hop > 0 && n_taps - 1 > hop) {
-        set_error("%s: the filters need n_taps - 1 = %d samples of history but hop = %d (continuous mode wants n_taps - 1 <= hop)", who, n_taps - 1, hop);
-        return -1;
-    }
+    if (!need_fir_window(who, n_taps, hop, N, "the filters need")) return -1;
     if (!need_min(who, "out_stride", out_stride, "N_SAMPLES", N) || !need_rows(who, adaptive_array, n, m_total)) return -1;
-    {
-        // d_out's range runs from its first float to the last one written: the floats behind the last row's N_SAMPLES are not part of it
-        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
-        auto mul = [](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
-        const unsigned long long frame_bytes = mul((unsigned long long)m_total * N, sizeof(float));
-        const unsigned long long in_bytes = mul(frame_bytes, (unsigned long long)frames);
-        const unsigned long long tap_bytes = mul(mul((unsigned long long)beams * n, (unsigned long long)n_taps), sizeof(float));
-        const unsigned long long out_rows = (unsigned long long)frames * beams;
-        const unsigned long long gaps = mul(mul(out_rows - 1, (unsigned long long)out_stride), sizeof(float));
-        const unsigned long long out_bytes = gaps > top - N * sizeof(float) ? top : gaps + N * sizeof(float);
-        if (ranges_overlap(d_out, out_bytes, d_signals, in_bytes)) { set_error("%s: d_out overlaps d_signals", who); return -1; }
-        if (d_prev && ranges_overlap(d_out, out_bytes, d_prev, frame_bytes)) { set_error("%s: d_out overlaps d_prev", who); return -1; }
-        if (ranges_overlap(d_out, out_bytes, d_taps, tap_bytes)) { set_error("%s: d_out overlaps d_taps", who); return -1; }
-    }
+    // d_out's span runs from its first float to the last one written: the floats behind the last row's N_SAMPLES are not part of it
+    const u64 frame_bytes = sat_mul((u64)m_total * N, sizeof(float)), out_rows = (u64)frames * beams;
+    if (!need_disjoint(who, {{d_out, sat_add(sat_mul(sat_mul(out_rows - 1, (u64)out_stride), sizeof(float)), N * sizeof(float)), "d_out"},
+                             {d_signals, sat_mul(frame_bytes, (u64)frames), "d_signals"},
+                             {d_prev, frame_bytes, "d_prev"},
+                             {d_taps, sat_mul(sat_mul((u64)beams * n, (u64)n_taps), sizeof(float)), "d_taps"}}, 1))
+        return -1;
     if (!ensure_device()) return -1;
     int max_row = 0;
     if (!upload_mics(adaptive_array, n, &max_row)) return -1;
@@ -1501,26 +1521,16 @@ int bf_lcmv_design_device(const double* d_tau, int dirs, int n, const int* d_off
         return -1;
     }
     if (!need_max(who, "n_taps", n_taps, BF_LCMV_MAX_TAPS)) return -1;
-    if (bin_lo < 0 || bin_hi < bin_lo || bin_hi > n_taps / 2) {
-        set_error("%s: bins [%d, %d] are not within 0 <= bin_lo <= bin_hi <= n_taps / 2 = %d", who, bin_lo, bin_hi, n_taps / 2);
-        return -1;
-    }
+    if (!need_bins(who, bin_lo, bin_hi, n_taps)) return -1;
     if (!(rho > 0.0 && rho <= 1.0)) { set_error("%s: rho = %.17g is not in (0, 1]", who, rho); return -1; }
-    {
-        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
-        auto mul = [](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
-        const unsigned long long S = (unsigned long long)sources, K = (unsigned long long)(bin_hi - bin_lo + 1);
-        struct Range { const void* p; unsigned long long bytes; const char* name; };
-        const Range r[] = {{d_gains, mul(mul(S * K, (unsigned long long)n), 2 * sizeof(double)), "d_gains"},
-                           {d_taps, mul(mul(S * (unsigned long long)n_taps, (unsigned long long)n), sizeof(float)), "d_taps"},
-                           {d_kept, S * K * S * sizeof(int), "d_kept"},
-                           {d_status, S * sizeof(int), "d_status"},
-                           {d_tau, mul(mul((unsigned long long)dirs, (unsigned long long)n), sizeof(double)), "d_tau"},
-                           {d_offsets, S * sizeof(int), "d_offsets"}};
-        for (int a = 0; a < 4; ++a)              // every output against the outputs behind it and both inputs
-            for (int b = a + 1; b < 6; ++b)
-                if (ranges_overlap(r[a].p, r[a].bytes, r[b].p, r[b].bytes)) { set_error("%s: %s overlaps %s", who, r[a].name, r[b].name); return -1; }
-    }
+    const u64 S = (u64)sources, K = (u64)(bin_hi - bin_lo + 1);
+    if (!need_disjoint(who, {{d_gains, sat_mul(sat_mul(S * K, (u64)n), 2 * sizeof(double)), "d_gains"},
+                             {d_taps, sat_mul(sat_mul(S * (u64)n_taps, (u64)n), sizeof(float)), "d_taps"},
+                             {d_kept, S * K * S * sizeof(int), "d_kept"},
+                             {d_status, S * sizeof(int), "d_status"},
+                             {d_tau, sat_mul(sat_mul((u64)dirs, (u64)n), sizeof(double)), "d_tau"},
+                             {d_offsets, S * sizeof(int), "d_offsets"}}, 4))   // four outputs, two inputs
+        return -1;
     if (!ensure_device()) return -1;
     return HIP_RC(bf::launch_lcmv_design(d_tau, dirs, n, d_offsets, sources, offset_per_dir, n_taps, bin_lo, bin_hi, rho, d_gains, d_taps, d_kept, d_status,
                                          as_stream(stream)));
@@ -1553,33 +1563,22 @@ int bf_mvdr_design_device(const float* d_signals, int m_total, int frames, const
             return -1;
         }
     }
-    if (bin_lo < 0 || bin_hi < bin_lo || bin_hi > n_taps / 2) {
-        set_error("%s: bins [%d, %d] are not within 0 <= bin_lo <= bin_hi <= n_taps / 2 = %d", who, bin_lo, bin_hi, n_taps / 2);
-        return -1;
-    }
+    if (!need_bins(who, bin_lo, bin_hi, n_taps)) return -1;
     if (!std::isfinite(loading) || !(loading > 0.0)) { set_error("%s: loading = %.17g is not finite and > 0", who, loading); return -1; }
     if (!need_rows(who, adaptive_array, n, m_total)) return -1;
-    {
-        const unsigned long long top = std::numeric_limits<unsigned long long>::max();
-        auto mul = [](unsigned long long a, unsigned long long b) { return a > top / b ? top : a * b; };
-        const unsigned long long S = (unsigned long long)sources, K = (unsigned long long)(bin_hi - bin_lo + 1), M = (unsigned long long)n;
-        const unsigned long long P = (unsigned long long)frames * (unsigned long long)segs, cplx = 2 * sizeof(double);
-        struct Range { const void* p; unsigned long long bytes; const char* name; };
-        const Range r[] = {{d_snap, mul(mul(mul(P, K), M), cplx), "d_snap"},
-                           {d_cov, mul(K * M * M, cplx), "d_cov"},
-                           {d_chol, mul(K * M * M, cplx), "d_chol"},
-                           {d_gains, mul(S * K * M, cplx), "d_gains"},
-                           {d_taps, mul(S * (unsigned long long)n_taps * M, sizeof(float)), "d_taps"},
-                           {d_status, S * sizeof(int), "d_status"},
-                           {d_fallback, K * sizeof(int), "d_fallback"},
-                           {d_signals, mul(mul(mul((unsigned long long)frames, (unsigned long long)m_total), (unsigned long long)N), sizeof(float)), "d_signals"},
-                           {d_tau, mul(mul((unsigned long long)dirs, M), sizeof(double)), "d_tau"},
-                           {d_offsets, S * sizeof(int), "d_offsets"},
-                           {d_window, (unsigned long long)n_taps * sizeof(double), "d_window"}};
-        for (int a = 0; a < 7; ++a)              // every output against the outputs behind it and the inputs (d_window only where given)
-            for (int b = a + 1; b < 11; ++b)
-                if (r[b].p && ranges_overlap(r[a].p, r[a].bytes, r[b].p, r[b].bytes)) { set_error("%s: %s overlaps %s", who, r[a].name, r[b].name); return -1; }
-    }
+    const u64 S = (u64)sources, K = (u64)(bin_hi - bin_lo + 1), M = (u64)n, P = (u64)frames * (u64)segs, cplx = 2 * sizeof(double);
+    if (!need_disjoint(who, {{d_snap, sat_mul(sat_mul(sat_mul(P, K), M), cplx), "d_snap"},
+                             {d_cov, sat_mul(K * M * M, cplx), "d_cov"},
+                             {d_chol, sat_mul(K * M * M, cplx), "d_chol"},
+                             {d_gains, sat_mul(S * K * M, cplx), "d_gains"},
+                             {d_taps, sat_mul(S * (u64)n_taps * M, sizeof(float)), "d_taps"},
+                             {d_status, S * sizeof(int), "d_status"},
+                             {d_fallback, K * sizeof(int), "d_fallback"},
+                             {d_signals, sat_mul(sat_mul(sat_mul((u64)frames, (u64)m_total), (u64)N), sizeof(float)), "d_signals"},
+                             {d_tau, sat_mul(sat_mul((u64)dirs, M), sizeof(double)), "d_tau"},
+                             {d_offsets, S * sizeof(int), "d_offsets"},
+                             {d_window, (u64)n_taps * sizeof(double), "d_window"}}, 7))   // seven outputs, four inputs (d_window only where given)
+        return -1;
     if (!ensure_device()) return -1;
     int max_row = 0;
     if (!upload_mics(adaptive_array, n, &max_row)) return -1;

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "das_kernels.h"
+#include "design_device.h"
 
 namespace bf {
 namespace {
@@ -30,15 +31,6 @@ constexpr int kS = kLcmvMaxSources;
 constexpr int kPairs = kS * (kS + 1) / 2;      // entries (a <= b) of the Hermitian Gram matrix
 constexpr int kTapThreads = 256;
 constexpr int kMicBlock = 8;                   // microphones of a taps workgroup: they share one table
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-
-// The tracker's rule (bf_fuse_boxes_device words it): a source iff >= 0, a multiple of offset_per_dir, and a direction of the table.
-__device__ __forceinline__ int slot_direction(int off, int offset_per_dir, int dirs)
-{
-    if (off < 0 || off % offset_per_dir != 0) return -1;
-    const int d = off / offset_per_dir;
-    return d < dirs ? d : -1;
-}
 
 __global__ void __launch_bounds__(kLanes)
 lcmv_gains_kernel(const double* __restrict__ tau, const int32_t* __restrict__ offsets, int dirs, int n, int S, int offset_per_dir, int T, int bin_lo, int K,

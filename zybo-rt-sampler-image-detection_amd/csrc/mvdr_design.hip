@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "das_kernels.h"
+#include "design_device.h"
 
 namespace bf {
 namespace {
@@ -40,15 +41,6 @@ constexpr int kCovThreads = kTile * kTile;
 constexpr int kCovP = 16;                      // ... and stages this many snapshots at a time
 constexpr int kSolveThreads = 1024;
 constexpr int kSolveWaves = kSolveThreads / 64;
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-
-// The tracker's rule (bf_fuse_boxes_device words it): a source iff >= 0, a multiple of offset_per_dir, and a direction of the table.
-__device__ __forceinline__ int slot_direction(int off, int offset_per_dir, int dirs)
-{
-    if (off < 0 || off % offset_per_dir != 0) return -1;
-    const int d = off / offset_per_dir;
-    return d < dirs ? d : -1;
-}
 
 __global__ void __launch_bounds__(kSnapThreads)
 mvdr_snapshot_kernel(const float* __restrict__ signals, const int32_t* __restrict__ mics, int m_total, int n_samples, int n, int seg_first, int seg_hop, int segs,

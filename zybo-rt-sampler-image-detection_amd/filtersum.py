@@ -28,9 +28,10 @@ make sample-covariance MVDR cancel part of the look signal as well (self-cancell
 A caller with weights of their own passes `taps=` to FilterSumListener."""
 import numpy as np
 
+from carried import CarriedBeams
 from interface import config
 from lib import _native as nat
-from listen import _entry, _fail, _torch
+from lib._native import _torch, call
 
 MAX_BEAMS = 16
 MAX_SLOTS = 8           # BF_LCMV_MAX_SOURCES
@@ -44,6 +45,24 @@ def band_bins(n_taps, band, fs=None):
     k = np.arange(T // 2 + 1)
     f = k * fs / T
     return k[(f >= float(band[0])) & (f <= float(band[1]))]
+
+
+def _design_args(tau, n_taps, band, fs, rho=None):
+    """What every designer checks of its design: tau [D, M], n_taps >= 1, rho in (0, 1] where the design has one, a band that holds a
+    bin -> (tau float64, T = n_taps, the in-band bins)."""
+    tau = np.asarray(tau, dtype=np.float64)
+    if tau.ndim != 2:
+        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    T = int(n_taps)
+    if T < 1:
+        raise ValueError("n_taps must be >= 1, got %d" % T)
+    if rho is not None and not 0.0 < float(rho) <= 1.0:
+        raise ValueError("rho must be in (0, 1], got %g" % rho)
+    fs = float(config.SAMPLE_RATE if fs is None else fs)
+    bins = band_bins(T, band, fs)
+    if bins.size == 0:
+        raise ValueError("no bin of the %d-point grid lies in the band (%g, %g) at fs = %g" % (T, band[0], band[1], fs))
+    return tau, T, bins
 
 
 def design_lcmv(tau, look, nulls=None, n_taps=65, band=(3000.0, 8000.0), rho=0.95, fs=None):
@@ -65,14 +84,8 @@ def design_lcmv(tau, look, nulls=None, n_taps=65, band=(3000.0, 8000.0), rho=0.9
 
     A beam's output is the look direction's signal delayed by (T - 1) / 2 samples and band-limited.  With no nulls the design is
     band-limited delay-and-sum with exact fractional delays."""
-    fs = float(config.SAMPLE_RATE if fs is None else fs)
-    tau = np.asarray(tau, dtype=np.float64)
-    if tau.ndim != 2:
-        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    tau, T, bins = _design_args(tau, n_taps, band, fs, rho)
     D, M = tau.shape
-    T = int(n_taps)
-    if T < 1:
-        raise ValueError("n_taps must be >= 1, got %d" % T)
     look = [int(d) for d in np.asarray(look).ravel()]
     B = len(look)
     if B < 1:
@@ -83,11 +96,6 @@ def design_lcmv(tau, look, nulls=None, n_taps=65, band=(3000.0, 8000.0), rho=0.9
     for d in look + [d for row in nulls for d in row]:
         if d < 0 or d >= D:
             raise ValueError("direction %d is outside tau's %d directions" % (d, D))
-    if not 0.0 < float(rho) <= 1.0:
-        raise ValueError("rho must be in (0, 1], got %g" % rho)
-    bins = band_bins(T, band, fs)
-    if bins.size == 0:
-        raise ValueError("no bin of the %d-point grid lies in the band (%g, %g) at fs = %g" % (T, band[0], band[1], fs))
     J = max([len(row) for row in nulls] + [0])
     kept = np.zeros((B, bins.size, J), dtype=bool)
     G = np.zeros((B, M, T // 2 + 1), dtype=np.complex128)
@@ -127,22 +135,13 @@ def design_slots(tau, offsets, offset_per_dir, n_taps=65, band=(3000.0, 8000.0),
     (`slot_directions`) gets all-zero taps, status 1 and no kept entry; a designed slot gets status 0.
     ->    (taps float32 [S, M, T], kept int32 [S, K, S], status int32 [S]);  kept[i][k][j] = 1 iff slot j is a kept null of beam i at
           in-band bin k (the diagonal, slots that are no source and dropped nulls are 0)."""
-    tau = np.asarray(tau, dtype=np.float64)
-    if tau.ndim != 2:
-        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    tau, T, bins = _design_args(tau, n_taps, band, fs, rho)
     dirs = slot_directions(offsets, offset_per_dir, tau.shape[0])
-    S, T = len(dirs), int(n_taps)
+    S, K = len(dirs), bins.size
     if S < 1:
         raise ValueError("offsets is empty")
     if S > tau.shape[1]:
         raise ValueError("%d slots but %d microphones: more constraints than microphones make the system singular" % (S, tau.shape[1]))
-    if T < 1:
-        raise ValueError("n_taps must be >= 1, got %d" % T)
-    K = band_bins(T, band, fs).size
-    if K == 0:
-        raise ValueError("no bin of the %d-point grid lies in the band (%g, %g)" % (T, band[0], band[1]))
-    if not 0.0 < float(rho) <= 1.0:
-        raise ValueError("rho must be in (0, 1], got %g" % rho)
     taps = np.zeros((S, tau.shape[1], T), dtype=np.float32)
     kept = np.zeros((S, K, S), dtype=np.int32)
     status = np.array([0 if d >= 0 else 1 for d in dirs], dtype=np.int32)
@@ -163,17 +162,15 @@ def _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_h
     x = np.asarray(frames)
     if x.ndim != 3 or x.dtype != np.float32:
         raise ValueError("frames must be float32 [F, M_total, N], got %s %s" % (x.dtype, x.shape))
-    tau = np.asarray(tau, dtype=np.float64)
-    if tau.ndim != 2:
-        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    tau, T, bins = _design_args(tau, n_taps, band, fs)
     mics = np.asarray(mics).astype(np.int64).ravel()
     F, m_total, N = x.shape
-    M, T = int(mics.size), int(n_taps)
+    M = int(mics.size)
     if M < 1 or M != tau.shape[1]:
         raise ValueError("mics lists %d rows, tau is for %d microphones" % (M, tau.shape[1]))
     if mics.min() < 0 or mics.max() >= m_total:
         raise ValueError("mics names a row outside the frames' %d rows" % m_total)
-    if T < 1 or T > N:
+    if T > N:
         raise ValueError("n_taps must be in [1, N = %d], got %d" % (N, T))
     seg_first, seg_hop = int(seg_first), int(seg_hop)
     if seg_first < 0 or seg_hop < 1:
@@ -187,9 +184,6 @@ def _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_h
     win = np.ones(T) if window is None else np.asarray(window, dtype=np.float64)
     if win.shape != (T,):
         raise ValueError("window must be [n_taps = %d], got shape %s" % (T, win.shape))
-    bins = band_bins(T, band, fs)
-    if bins.size == 0:
-        raise ValueError("no bin of the %d-point grid lies in the band (%g, %g)" % (T, band[0], band[1]))
     for d in dirs:
         if d >= tau.shape[0]:
             raise ValueError("direction %d is outside tau's %d directions" % (d, tau.shape[0]))
@@ -263,14 +257,12 @@ def design_mvdr_slots(frames, mics, tau, offsets, offset_per_dir, n_taps=65, ban
     """design_mvdr with design_slots' slot semantics: beam i looks at slot i of a row of offsets; a slot that is no source
     (`slot_directions`) gets all-zero taps and status 1.  The other slots are not nulls of a beam -- only the data decides.
     ->    (taps float32 [S, M, T], fallback int32 [K], status int32 [S])."""
-    tau = np.asarray(tau, dtype=np.float64)
-    if tau.ndim != 2:
-        raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
+    tau, T, _ = _design_args(tau, n_taps, band, fs)
     dirs = slot_directions(offsets, offset_per_dir, tau.shape[0])
     if not dirs:
         raise ValueError("offsets is empty")
-    G, fallback, bins = _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_hop, segs, window, fs)
-    return _taps_of_gains(G, bins, int(n_taps)), fallback, np.array([0 if d >= 0 else 1 for d in dirs], dtype=np.int32)
+    G, fallback, bins = _mvdr_gains(frames, mics, tau, dirs, T, band, loading, seg_first, seg_hop, segs, window, fs)
+    return _taps_of_gains(G, bins, T), fallback, np.array([0 if d >= 0 else 1 for d in dirs], dtype=np.int32)
 
 
 def response(taps, tau_row, w):
@@ -287,7 +279,7 @@ def response(taps, tau_row, w):
     return h.reshape(w.shape) if w.ndim else complex(h[0])
 
 
-class FilterSumListener:
+class FilterSumListener(CarriedBeams):
     """B filter-and-sum beams over the microphone rows `mics` (default: lib.directions.active_microphones(), as BeamListener).
     `taps`: float32 [B, M, T], g[b][m][t] for microphone row mics[m] -- from `design_lcmv`, `cross_null`, or a caller's own design.
     `hop`: samples between the starts of consecutive frames, as given to the ingest (None: independent windows, every window starts
@@ -321,7 +313,6 @@ class FilterSumListener:
         self.taps, self.B, self.T, self.hop, self.device = g, B, T, hop, device
         self.delay = (T - 1) / 2.0
         self.d_taps = _torch().from_numpy(g).to(device)
-        self._prev = None
         self.dirs = self.kept = None                    # set by cross_null
         self.d_tau = None                               # set by for_slots: the device-side designer's state
         self.d_snap = self.d_cov = self.d_chol = self.d_fallback = self._window = self._mvdr_key = None      # adapt's workspaces
@@ -333,10 +324,7 @@ class FilterSumListener:
         (the tracker's rule).  **design goes to design_lcmv (n_taps, band, rho, fs).  The listener's `.dirs` lists the beams'
         directions in the order of the valid offsets, `.kept` is design_lcmv's."""
         tau = np.asarray(tau, dtype=np.float64)
-        step = int(offset_per_dir)
-        if step < 1:
-            raise ValueError("offset_per_dir must be >= 1, got %d" % step)
-        dirs = [int(o) // step for o in np.asarray(offsets).ravel() if int(o) >= 0 and int(o) % step == 0 and int(o) // step < tau.shape[0]]
+        dirs = [d for d in slot_directions(offsets, offset_per_dir, tau.shape[0]) if d >= 0]
         if not dirs:
             raise ValueError("offsets holds no valid source")
         nulls = [[d for j, d in enumerate(dirs) if j != i] for i in range(len(dirs))]
@@ -352,46 +340,42 @@ class FilterSumListener:
         (d_gains float64 [slots, K, M, 2], d_kept int32 [slots, K, slots], d_status int32 [slots]) are allocated once.  `.taps`, the
         host copy, is None until `taps_host()` fetches it."""
         torch = _torch()
-        tau = np.ascontiguousarray(tau, dtype=np.float64)
-        if tau.ndim != 2:
-            raise ValueError("tau must be [D, M], got shape %s" % (tau.shape,))
-        S, T, step = int(slots), int(n_taps), int(offset_per_dir)
+        tau, T, bins = _design_args(tau, n_taps, band, fs, rho)
+        S, step = int(slots), int(offset_per_dir)
         if S < 1 or S > MAX_SLOTS:
             raise ValueError("1 .. %d slots, got %d" % (MAX_SLOTS, S))
         if S > tau.shape[1]:
             raise ValueError("%d slots but %d microphones: more constraints than microphones" % (S, tau.shape[1]))
-        if T < 1 or T > MAX_DESIGN_TAPS:
+        if T > MAX_DESIGN_TAPS:
             raise ValueError("1 .. %d taps, got %d" % (MAX_DESIGN_TAPS, T))
         if step < 1:
             raise ValueError("offset_per_dir must be >= 1, got %d" % step)
-        if not 0.0 < float(rho) <= 1.0:
-            raise ValueError("rho must be in (0, 1], got %g" % rho)
-        bins = band_bins(T, band, fs)
-        if bins.size == 0:
-            raise ValueError("no bin of the %d-point grid lies in the band (%g, %g)" % (T, band[0], band[1]))
         self = cls(np.zeros((S, tau.shape[1], T), dtype=np.float32), mics=mics, hop=hop, device=device)
         self.taps = None
         self.bins, self.rho, self.offset_per_dir, self.n_dirs = bins, float(rho), step, int(tau.shape[0])
-        self.d_tau = torch.from_numpy(tau).to(device)
+        self.d_tau = torch.from_numpy(np.ascontiguousarray(tau)).to(device)
         self.d_gains = torch.zeros((S, bins.size, self.n, 2), dtype=torch.float64, device=device)
         self.d_kept = torch.zeros((S, bins.size, S), dtype=torch.int32, device=device)
         self.d_status = torch.ones((S,), dtype=torch.int32, device=device)
         return self
 
+    def _check_slots(self, who, d_offsets):
+        """What retarget and adapt ask of the listener and of d_offsets -> torch."""
+        torch = _torch()
+        if self.d_tau is None:
+            raise ValueError("%s() needs a listener built by for_slots" % who)
+        if d_offsets.dtype != torch.int32 or not d_offsets.is_cuda or tuple(d_offsets.shape) != (self.B,) or not d_offsets.is_contiguous():
+            raise ValueError("d_offsets must be a contiguous int32 cuda tensor [%d], got %s %s" % (self.B, d_offsets.dtype, tuple(d_offsets.shape)))
+        return torch
+
     def retarget(self, d_offsets):
         """Re-design every beam for the slots of d_offsets, an int32 cuda tensor [slots] -- offsets[-1] of SourceTracker.update, a row
         of BeamListener.sources: enqueues bf_lcmv_design_device on the current stream, which writes self.d_taps IN PLACE (the address
         a captured graph reads stays valid).  -> (d_status int32 [slots], d_kept int32 [slots, K, slots]), the listener's own tensors."""
-        torch = _torch()
-        if self.d_tau is None:
-            raise ValueError("retarget() needs a listener built by for_slots")
-        if d_offsets.dtype != torch.int32 or not d_offsets.is_cuda or tuple(d_offsets.shape) != (self.B,) or not d_offsets.is_contiguous():
-            raise ValueError("d_offsets must be a contiguous int32 cuda tensor [%d], got %s %s" % (self.B, d_offsets.dtype, tuple(d_offsets.shape)))
-        rc = _entry("bf_lcmv_design_device")(self.d_tau.data_ptr(), self.n_dirs, self.n, d_offsets.data_ptr(), self.B, self.offset_per_dir, self.T,
-                                             int(self.bins[0]), int(self.bins[-1]), self.rho, self.d_gains.data_ptr(), self.d_taps.data_ptr(),
-                                             self.d_kept.data_ptr(), self.d_status.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_lcmv_design_device")
+        self._check_slots("retarget", d_offsets)
+        call("bf_lcmv_design_device", self.d_tau.data_ptr(), self.n_dirs, self.n, d_offsets.data_ptr(), self.B, self.offset_per_dir, self.T,
+             int(self.bins[0]), int(self.bins[-1]), self.rho, self.d_gains.data_ptr(), self.d_taps.data_ptr(), self.d_kept.data_ptr(),
+             self.d_status.data_ptr())
         self.taps = None
         return self.d_status, self.d_kept
 
@@ -403,11 +387,7 @@ class FilterSumListener:
         so consecutive overlapping windows never count one segment twice.  window: float64 [n_taps] or None (rectangular).  The
         workspaces (d_snap, d_cov, d_chol) are allocated on the first call for a frame count and kept.
         -> (d_status int32 [slots], d_fallback int32 [K]: 1 where a bin fell back to the beam without nulls), the listener's own tensors."""
-        torch = _torch()
-        if self.d_tau is None:
-            raise ValueError("adapt() needs a listener built by for_slots")
-        if d_offsets.dtype != torch.int32 or not d_offsets.is_cuda or tuple(d_offsets.shape) != (self.B,) or not d_offsets.is_contiguous():
-            raise ValueError("d_offsets must be a contiguous int32 cuda tensor [%d], got %s %s" % (self.B, d_offsets.dtype, tuple(d_offsets.shape)))
+        torch = self._check_slots("adapt", d_offsets)
         frames = self._frames(d_frames)
         F, m_total, N = frames.shape
         loading, seg_hop = float(loading), int(seg_hop)
@@ -435,13 +415,10 @@ class FilterSumListener:
                 self.d_chol = torch.empty((K, self.n, self.n, 2), dtype=torch.float64, device=self.device)
                 self.d_fallback = torch.zeros((K,), dtype=torch.int32, device=self.device)
             self._mvdr_key = key
-        rc = _entry("bf_mvdr_design_device")(frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, seg_first, seg_hop, segs,
-                                             None if d_window is None else d_window.data_ptr(), self.d_tau.data_ptr(), self.n_dirs, d_offsets.data_ptr(),
-                                             self.B, self.offset_per_dir, self.T, int(self.bins[0]), int(self.bins[-1]), loading, self.d_snap.data_ptr(),
-                                             self.d_cov.data_ptr(), self.d_chol.data_ptr(), self.d_gains.data_ptr(), self.d_taps.data_ptr(),
-                                             self.d_status.data_ptr(), self.d_fallback.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_mvdr_design_device")
+        call("bf_mvdr_design_device", frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, seg_first, seg_hop, segs,
+             None if d_window is None else d_window.data_ptr(), self.d_tau.data_ptr(), self.n_dirs, d_offsets.data_ptr(), self.B, self.offset_per_dir,
+             self.T, int(self.bins[0]), int(self.bins[-1]), loading, self.d_snap.data_ptr(), self.d_cov.data_ptr(), self.d_chol.data_ptr(),
+             self.d_gains.data_ptr(), self.d_taps.data_ptr(), self.d_status.data_ptr(), self.d_fallback.data_ptr())
         self.taps = None
         return self.d_status, self.d_fallback
 
@@ -450,15 +427,6 @@ class FilterSumListener:
         self.taps = self.d_taps.cpu().numpy()
         return self.taps
 
-    def _frames(self, d_frames):
-        torch = _torch()
-        if d_frames.dim() != 3 or d_frames.dtype != torch.float32 or not d_frames.is_cuda or d_frames.shape[2] != config.N_SAMPLES or d_frames.shape[0] < 1:
-            raise ValueError("d_frames must be a float32 cuda tensor [F, M_total, %d], got %s %s" % (config.N_SAMPLES, d_frames.dtype, tuple(d_frames.shape)))
-        frames = d_frames.contiguous()
-        if self._prev is not None and self._prev.shape[0] != frames.shape[1]:
-            raise ValueError("the carried frame has %d rows, d_frames %d: reset() before changing the frame layout" % (self._prev.shape[0], frames.shape[1]))
-        return frames
-
     def listen(self, d_frames):
         """d_frames float32 cuda [F, M_total, N_SAMPLES] -> float32 [F, B, N_SAMPLES]; with a hop, frame f's history is frame f - 1,
         frame 0's the carried frame (silence without one).  Does not change the carried state."""
@@ -466,31 +434,6 @@ class FilterSumListener:
         frames = self._frames(d_frames)
         F, m_total, N = frames.shape
         out = torch.empty((F, self.B, N), dtype=torch.float32, device=self.device)
-        prev = self._prev if self.hop > 0 else None
-        rc = _entry("bf_filter_sum_device")(frames.data_ptr(), m_total, F, self.hop, None if prev is None else prev.data_ptr(), nat.iptr(self.mics), self.n,
-                                            self.d_taps.data_ptr(), self.T, self.B, out.data_ptr(), N, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_filter_sum_device")
+        call("bf_filter_sum_device", frames.data_ptr(), m_total, F, self.hop, self._prev_ptr(), nat.iptr(self.mics), self.n, self.d_taps.data_ptr(),
+             self.T, self.B, out.data_ptr(), N)
         return out
-
-    def advance(self, d_frames):
-        """Done with this batch: keep a copy of its last frame as the history of the next batch's first frame."""
-        frames = self._frames(d_frames)
-        if self._prev is None:
-            self._prev = frames[-1].clone()
-        else:
-            self._prev.copy_(frames[-1])      # in place: the address a captured graph reads stays valid
-
-    def reset(self):
-        """Forget the carried frame: the next batch starts a new stream (silence before it)."""
-        self._prev = None
-
-    def audio(self, out):
-        """out [F, B, N_SAMPLES] from listen() -> [B, F * hop]: the last `hop` samples of every window joined, the gapless beams of the
-        stream from sample N_SAMPLES - hop of the batch's first window on (StreamBeamformer.audio's convention)."""
-        if self.hop < 1:
-            raise ValueError("audio() joins the windows of a stream: this listener has no hop (independent windows)")
-        if out.dim() != 3 or out.shape[2] != config.N_SAMPLES:
-            raise ValueError("out must be [F, B, %d], got %s" % (config.N_SAMPLES, tuple(out.shape)))
-        F, B, N = out.shape
-        return out[:, :, N - self.hop:].permute(1, 0, 2).reshape(B, F * self.hop)

@@ -12,7 +12,7 @@ captured as one graph:
     peak, power, center, rects, src_box, counts = sf.focus(d_maps, boxes, n_boxes, sources=track_offsets)
     out, status = sb.listen(d_frames, peak[:, :4])          # what the four best-scored detections sound like"""
 from interface import config
-from listen import _entry, _fail, _torch
+from lib._native import _torch, call
 
 
 class SensorFusion:
@@ -62,11 +62,7 @@ class SensorFusion:
         rects = torch.empty((F, B, 4), dtype=torch.int32, device=self.device)
         src_box = None if src is None else torch.empty((F, n_src), dtype=torch.int32, device=self.device)
         counts = torch.empty((F, 3), dtype=torch.int32, device=self.device)
-        rc = _entry("bf_fuse_boxes_device")(power.data_ptr(), F, stride, self.rows, self.cols, self.offset_per_dir, boxes.data_ptr(),
-                                            None if n_boxes is None else n_boxes.data_ptr(), B, w, h, self.conf,
-                                            None if src is None else src.data_ptr(), n_src, peak.data_ptr(), value.data_ptr(), center.data_ptr(),
-                                            rects.data_ptr(), None if src_box is None else src_box.data_ptr(), counts.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_fuse_boxes_device")
+        call("bf_fuse_boxes_device", power.data_ptr(), F, stride, self.rows, self.cols, self.offset_per_dir, boxes.data_ptr(),
+             None if n_boxes is None else n_boxes.data_ptr(), B, w, h, self.conf, None if src is None else src.data_ptr(), n_src, peak.data_ptr(),
+             value.data_ptr(), center.data_ptr(), rects.data_ptr(), None if src_box is None else src_box.data_ptr(), counts.data_ptr())
         return peak, value, center, rects, src_box, counts

@@ -11,26 +11,7 @@ import numpy as np
 
 from interface import config
 from lib import _native as nat
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        raise nat.BeamformerError("no usable HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
-    return torch
-
-
-def _entry(name):
-    fn = getattr(nat.lib, name, None)
-    if fn is None:
-        raise nat.BeamformerError("%s is missing from %s (a build older than the batched stream ingest)" % (name, nat.LIB_PATH))
-    return fn
-
-
-def _fail(what):
-    """A -1 return: raise with the library's message."""
-    nat.check()
-    raise nat.BeamformerError("%s failed" % what)
+from lib._native import _entry, _torch, call
 
 
 def default_disabled_mics():
@@ -113,9 +94,6 @@ class PacketIngest:
             self._d_mask = torch.from_numpy(self.mask).to(self.device)
         out = torch.empty((F, self.m_total, self.n_samples), dtype=torch.float32, device=self.device)
         status = torch.empty((F, 4), dtype=torch.int32, device=self.device)
-        rc = _entry("bf_ingest_stream_device")(packets.data_ptr(), T, self.n_arrays, self.rows, self.columns, self.hop, F, self.m_total,
-                                               None if self._d_mask is None else self._d_mask.data_ptr(), self.protocol_ver, out.data_ptr(),
-                                               status.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_ingest_stream_device")
+        call("bf_ingest_stream_device", packets.data_ptr(), T, self.n_arrays, self.rows, self.columns, self.hop, F, self.m_total,
+             None if self._d_mask is None else self._d_mask.data_ptr(), self.protocol_ver, out.data_ptr(), status.data_ptr())
         return out, status

@@ -196,6 +196,33 @@ def check():
         raise BeamformerError(text)
 
 
+def _torch():
+    import torch
+    if not torch.cuda.is_available():
+        raise BeamformerError("no usable HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
+    return torch
+
+
+def _entry(name):
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise BeamformerError("%s is missing from %s (a build older than the batched beam path)" % (name, LIB_PATH))
+    return fn
+
+
+def _fail(what):
+    """A -1 return: raise with the library's message."""
+    check()
+    raise BeamformerError("%s failed" % what)
+
+
+def call(name, *args):
+    """Enqueue the entry point `name` (one whose last argument is the stream) on the current torch stream; a non-zero return raises
+    with the library's message."""
+    if _entry(name)(*args, _torch().cuda.current_stream().cuda_stream) != 0:
+        _fail(name)
+
+
 def apply_config():
     """Push interface.config's sizes into the native library (bf_configure)."""
     from interface import config as cfg

@@ -12,30 +12,12 @@ under a stronger one's sidelobes is found and heard: time-domain CLEAN.  All onl
 peaks, beams and residuals can be captured as one graph.  Raw beams (mic_gain 0) are bit-identical to the reference's miso_* calls."""
 import numpy as np
 
+from carried import check_frames
 from interface import config
 from lib import _native as nat
+from lib._native import _torch, call
 
 ALGOS = {"pad": nat.PAD, "lerp": nat.LERP, "hybrid": nat.HYBRID, "fir_naive": nat.FIR_NAIVE, "fir_vec": nat.FIR_VEC}
-
-
-def _torch():
-    import torch
-    if not torch.cuda.is_available():
-        raise nat.BeamformerError("no usable HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
-    return torch
-
-
-def _entry(name):
-    fn = getattr(nat.lib, name, None)
-    if fn is None:
-        raise nat.BeamformerError("%s is missing from %s (a build older than the batched beam path)" % (name, nat.LIB_PATH))
-    return fn
-
-
-def _fail(what):
-    """A -1 return: raise with the library's message."""
-    nat.check()
-    raise nat.BeamformerError("%s failed" % what)
 
 
 class BeamListener:
@@ -69,18 +51,14 @@ class BeamListener:
         (out float32 [F, B, N_SAMPLES], status int32 [F, B]: 0 ok, 1 offset outside the table, 2 fir_vec offset not a multiple
         of N_TAPS -- rejected beams are NaN).  mic_gain 0: raw beams; otherwise (beam / n) * mic_gain."""
         torch = _torch()
-        if d_frames.dim() != 3 or d_frames.dtype != torch.float32 or not d_frames.is_cuda or d_frames.shape[2] != config.N_SAMPLES:
-            raise ValueError("d_frames must be a float32 cuda tensor [F, M_total, %d], got %s %s" % (config.N_SAMPLES, d_frames.dtype, tuple(d_frames.shape)))
-        frames = d_frames.contiguous()
+        frames = check_frames(d_frames, min_frames=0)
         F, m_total, N = frames.shape
         offs = self._offsets(offsets, F)
         B = offs.shape[1]
         out = torch.empty((F, B, N), dtype=torch.float32, device=self.device)
         status = torch.empty((F, B), dtype=torch.int32, device=self.device)
-        rc = _entry("bf_miso_device")(ALGOS[self.algo], frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, offs.data_ptr(), B,
-                                      float(mic_gain), out.data_ptr(), N, status.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_miso_device")
+        call("bf_miso_device", ALGOS[self.algo], frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, offs.data_ptr(), B, float(mic_gain),
+             out.data_ptr(), N, status.data_ptr())
         return out, status
 
     def loudest(self, d_power):
@@ -92,10 +70,7 @@ class BeamListener:
         power = d_power if d_power.stride(1) == 1 else d_power.contiguous()
         F, D = power.shape
         offs = torch.empty((F, 1), dtype=torch.int32, device=self.device)
-        rc = _entry("bf_peak_offsets_device")(power.data_ptr(), F, power.stride(0), D, self.offset_per_dir, offs.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_peak_offsets_device")
+        call("bf_peak_offsets_device", power.data_ptr(), F, power.stride(0), D, self.offset_per_dir, offs.data_ptr())
         return offs
 
     def sources(self, d_power, k, radius, floor_rel=0.5, floor_abs=0.0, shape=None):
@@ -118,23 +93,15 @@ class BeamListener:
         counts = torch.empty((F, 3), dtype=torch.int32, device=self.device)
         # a row narrower than rows*cols is refused by the library (image_stride < rows * cols); a wider one is never read past the map
         stride = power.stride(0) if F > 1 else power.shape[1]
-        rc = _entry("bf_peaks_device")(power.data_ptr(), F, stride, rows, cols, int(radius), k, float(floor_rel), float(floor_abs),
-                                       self.offset_per_dir, offs.data_ptr(), vals.data_ptr(), counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_peaks_device")
+        call("bf_peaks_device", power.data_ptr(), F, stride, rows, cols, int(radius), k, float(floor_rel), float(floor_abs), self.offset_per_dir,
+             offs.data_ptr(), vals.data_ptr(), counts.data_ptr())
         return offs, vals, counts
-
-    def _check_frames(self, d_frames):
-        torch = _torch()
-        if d_frames.dim() != 3 or d_frames.dtype != torch.float32 or not d_frames.is_cuda or d_frames.shape[2] != config.N_SAMPLES or d_frames.shape[0] < 1:
-            raise ValueError("d_frames must be a float32 cuda tensor [F, M_total, %d], got %s %s" % (config.N_SAMPLES, d_frames.dtype, tuple(d_frames.shape)))
 
     def maps(self, d_frames, dir_begin=0, dir_end=None):
         """d_frames float32 cuda [F, M_total, N_SAMPLES] -> power maps float32 [F, dir_end - dir_begin] of the flat direction range
         (default: the whole grid) through bf_das_device."""
         torch = _torch()
-        self._check_frames(d_frames)
-        frames = d_frames.contiguous()
+        frames = check_frames(d_frames)
         F, m_total, N = frames.shape
         D = config.MAX_RES_X * config.MAX_RES_Y
         dir_end = D if dir_end is None else int(dir_end)
@@ -142,10 +109,7 @@ class BeamListener:
         if dir_begin < 0 or dir_end > D or dir_begin >= dir_end:
             raise ValueError("bad direction range [%d, %d) of %d" % (dir_begin, dir_end, D))
         img = torch.empty((F, dir_end - dir_begin), dtype=torch.float32, device=self.device)
-        rc = _entry("bf_das_device")(ALGOS[self.algo], frames.data_ptr(), m_total, img.data_ptr(), img.shape[1], F, nat.iptr(self.mics), self.n,
-                                     dir_begin, dir_end, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_das_device")
+        call("bf_das_device", ALGOS[self.algo], frames.data_ptr(), m_total, img.data_ptr(), img.shape[1], F, nat.iptr(self.mics), self.n, dir_begin, dir_end)
         return img
 
     def remove(self, d_frames, offsets, d_beams, gain=1.0, out=None):
@@ -154,9 +118,8 @@ class BeamListener:
         gain / n times every accepted beam, projected back onto the microphones by the adjoint of the delay, subtracted
         (bf_remove_sources_device; pad and lerp).  Rejected offsets (status 1) subtract nothing.  out=d_frames runs in place."""
         torch = _torch()
-        self._check_frames(d_frames)
+        frames = check_frames(d_frames)
         if out is None:
-            frames = d_frames.contiguous()
             out = torch.empty_like(frames)
         else:
             if out.shape != d_frames.shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or not d_frames.is_contiguous():
@@ -169,11 +132,8 @@ class BeamListener:
             raise ValueError("d_beams must be a float32 cuda tensor [%d, %d, >= %d], got %s %s" % (F, B, N, d_beams.dtype, tuple(d_beams.shape)))
         beams = d_beams.contiguous()
         status = torch.empty((F, B), dtype=torch.int32, device=self.device)
-        rc = _entry("bf_remove_sources_device")(ALGOS[self.algo], frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, offs.data_ptr(), B,
-                                                beams.data_ptr(), beams.shape[2], float(gain), out.data_ptr(), status.data_ptr(),
-                                                torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_remove_sources_device")
+        call("bf_remove_sources_device", ALGOS[self.algo], frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, offs.data_ptr(), B, beams.data_ptr(),
+             beams.shape[2], float(gain), out.data_ptr(), status.data_ptr())
         return out, status
 
     def separate(self, d_frames, k, gain=1.0, floor_rel=0.0, floor_abs=0.0):
@@ -183,11 +143,11 @@ class BeamListener:
         that residual.  A frame whose map falls below max(floor_abs, floor_rel * its maximum) -- or has no finite entry -- stops: its
         slot holds offset -1, value 0 and a NaN beam, and nothing more is subtracted from it.  No host synchronisation."""
         torch = _torch()
-        self._check_frames(d_frames)
+        frames = check_frames(d_frames)
         k = int(k)
         if k < 1:
             raise ValueError("k must be >= 1, got %d" % k)
-        residual = d_frames.contiguous().clone()
+        residual = frames.clone()
         F, m_total, N = residual.shape
         offsets = torch.empty((F, k), dtype=torch.int32, device=self.device)
         values = torch.empty((F, k), dtype=torch.float32, device=self.device)

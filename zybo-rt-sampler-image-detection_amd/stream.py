@@ -9,12 +9,14 @@ other in HBM (`PacketIngest.frames`, bf_ingest_stream_device) -> beams and maps 
 the start of frame f come from frame f - 1, and for the first frame of a batch from the last frame of the batch before it
 (`advance`).  include/beamformer_hip.h has the definition; for samples at or past `history` the beams equal BeamListener's
 bit for bit."""
+from carried import CarriedBeams
 from interface import config
 from lib import _native as nat
-from listen import ALGOS, BeamListener, _entry, _fail, _torch
+from lib._native import _entry, _torch, call
+from listen import ALGOS, BeamListener
 
 
-class StreamBeamformer(BeamListener):
+class StreamBeamformer(CarriedBeams, BeamListener):
     """Beams and maps of one continuous stream, for the table loaded for `algo` ("pad" or "lerp") over the microphone rows `mics`
     (default as BeamListener).  `hop`: samples between the starts of consecutive frames, as given to the ingest (None: back to
     back, N_SAMPLES).  The carried state is one frame, the last one of the batch before: `advance` sets it, `reset` clears it
@@ -29,7 +31,6 @@ class StreamBeamformer(BeamListener):
         if hop < 1 or hop > N:
             raise ValueError("hop must be in [1, N_SAMPLES = %d], got %d" % (N, hop))
         self.hop = hop
-        self._prev = None
 
     @property
     def history(self):
@@ -38,18 +39,6 @@ class StreamBeamformer(BeamListener):
         if h < 0:
             raise nat.BeamformerError("bf_stream_history: the %s table is not loaded" % self.algo)
         return h
-
-    def _frames(self, d_frames):
-        torch = _torch()
-        if d_frames.dim() != 3 or d_frames.dtype != torch.float32 or not d_frames.is_cuda or d_frames.shape[2] != config.N_SAMPLES or d_frames.shape[0] < 1:
-            raise ValueError("d_frames must be a float32 cuda tensor [F, M_total, %d], got %s %s" % (config.N_SAMPLES, d_frames.dtype, tuple(d_frames.shape)))
-        frames = d_frames.contiguous()
-        if self._prev is not None and self._prev.shape[0] != frames.shape[1]:
-            raise ValueError("the carried frame has %d rows, d_frames %d: reset() before changing the frame layout" % (self._prev.shape[0], frames.shape[1]))
-        return frames
-
-    def _prev_ptr(self):
-        return None if self._prev is None else self._prev.data_ptr()
 
     def maps(self, d_frames, dir_begin=0, dir_end=None):
         """d_frames float32 cuda [F, M_total, N_SAMPLES] -> power maps float32 [F, dir_end - dir_begin] of the flat direction range
@@ -63,10 +52,8 @@ class StreamBeamformer(BeamListener):
         if dir_begin < 0 or dir_end > D or dir_begin >= dir_end:
             raise ValueError("bad direction range [%d, %d) of %d" % (dir_begin, dir_end, D))
         img = torch.empty((F, dir_end - dir_begin), dtype=torch.float32, device=self.device)
-        rc = _entry("bf_das_stream_device")(ALGOS[self.algo], frames.data_ptr(), m_total, img.data_ptr(), img.shape[1], F, self.hop, self._prev_ptr(),
-                                            nat.iptr(self.mics), self.n, dir_begin, dir_end, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_das_stream_device")
+        call("bf_das_stream_device", ALGOS[self.algo], frames.data_ptr(), m_total, img.data_ptr(), img.shape[1], F, self.hop, self._prev_ptr(),
+             nat.iptr(self.mics), self.n, dir_begin, dir_end)
         return img
 
     def listen(self, d_frames, offsets, mic_gain=0.0):
@@ -79,11 +66,8 @@ class StreamBeamformer(BeamListener):
         B = offs.shape[1]
         out = torch.empty((F, B, N), dtype=torch.float32, device=self.device)
         status = torch.empty((F, B), dtype=torch.int32, device=self.device)
-        rc = _entry("bf_miso_stream_device")(ALGOS[self.algo], frames.data_ptr(), m_total, F, self.hop, self._prev_ptr(), nat.iptr(self.mics), self.n,
-                                             offs.data_ptr(), B, float(mic_gain), out.data_ptr(), N, status.data_ptr(),
-                                             torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_miso_stream_device")
+        call("bf_miso_stream_device", ALGOS[self.algo], frames.data_ptr(), m_total, F, self.hop, self._prev_ptr(), nat.iptr(self.mics), self.n,
+             offs.data_ptr(), B, float(mic_gain), out.data_ptr(), N, status.data_ptr())
         return out, status
 
     def remove(self, *args, **kwargs):
@@ -93,24 +77,3 @@ class StreamBeamformer(BeamListener):
     def separate(self, *args, **kwargs):
         raise NotImplementedError("StreamBeamformer.separate: stream beams read the previous window, and the adjoint BeamListener.remove applies is "
                                   "that of the zero-prefix delay: it does not match them")
-
-    def advance(self, d_frames):
-        """Done with this batch: keep a copy of its last frame as the history of the next batch's first frame (which starts `hop`
-        samples after that frame did)."""
-        frames = self._frames(d_frames)
-        if self._prev is None:
-            self._prev = frames[-1].clone()
-        else:
-            self._prev.copy_(frames[-1])      # in place: the address a captured graph reads stays valid
-
-    def reset(self):
-        """Forget the carried frame: the next batch starts a new stream (silence before it)."""
-        self._prev = None
-
-    def audio(self, out):
-        """out [F, B, N_SAMPLES] from listen() -> [B, F * hop]: the last `hop` samples of every window joined, the gapless beam of
-        the stream from sample N_SAMPLES - hop of the batch's first window on."""
-        if out.dim() != 3 or out.shape[2] != config.N_SAMPLES:
-            raise ValueError("out must be [F, B, %d], got %s" % (config.N_SAMPLES, tuple(out.shape)))
-        F, B, N = out.shape
-        return out[:, :, N - self.hop:].permute(1, 0, 2).reshape(B, F * self.hop)

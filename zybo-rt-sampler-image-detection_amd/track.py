@@ -14,7 +14,7 @@ the device and can be captured as one graph:
     out, status = sb.listen(d_frames, offsets); audio = sb.audio(out)   # audio[b] now follows ONE source"""
 from interface import config
 from lib import _native as nat
-from listen import _entry, _fail, _torch
+from lib._native import _entry, _torch, call
 
 
 class SourceTracker:
@@ -55,9 +55,6 @@ class SourceTracker:
         pos = torch.empty((F, S, 4), dtype=torch.float32, device=self.device)
         match = torch.empty((F, S), dtype=torch.int32, device=self.device)
         counts = torch.empty((F, 4), dtype=torch.int32, device=self.device)
-        rc = _entry("bf_track_sources_device")(src.data_ptr(), F, k, self.rows, self.cols, self.offset_per_dir, S, self.gate, self.max_miss, self.min_hits,
-                                               self.q, self.r, self.state.data_ptr(), offsets.data_ptr(), ids.data_ptr(), pos.data_ptr(), match.data_ptr(),
-                                               counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _fail("bf_track_sources_device")
+        call("bf_track_sources_device", src.data_ptr(), F, k, self.rows, self.cols, self.offset_per_dir, S, self.gate, self.max_miss, self.min_hits, self.q,
+             self.r, self.state.data_ptr(), offsets.data_ptr(), ids.data_ptr(), pos.data_ptr(), match.data_ptr(), counts.data_ptr())
         return offsets, ids, pos, match, counts
