@@ -1,0 +1,213 @@
+"""Static instruction budget of das_pair2_kernel (csrc/das_pair.hip): what a wave issues around the packed arithmetic.
+
+Compiles the unit to gfx950 assembly with the build's flags (HIPCC_FLAGS of __graft_entry__.py) and reports, for das_pair2_kernel:
+  (a) the instructions on the staging path of one steady-state half (1 <= h, h + 2 < n_half, part == 1, N == 256): the longest path
+      through the control-flow graph from the source's `;BF_STAGE_BEGIN` marker to `;BF_STAGE_END` that passes none of the markers the
+      source puts on the other alternatives (`;BF_STAGE_MASKED`, `;BF_STAGE_PART0`, `;BF_STAGE_WIPE`, `;BF_STAGE_OTHER`);
+  (b) the instructions of every kind between one mic's `;BF_S2_BEGIN` and the next one's in the text, the out-of-line `.subsection 1`
+      re-read stubs excluded: a mic's steps 1..7, the next mic's address, reads, waits and step 0, and the table loads between;
+  (c) VGPRs, SGPRs, spilled SGPRs and scratch bytes from the code-object metadata, and the v_readlane / v_writelane (SGPR spill
+      traffic) between the barriers of the half loop.
+
+usage: python scripts/dev/pair2_instruction_budget.py [das_pair.hip]      (default: the unit in csrc/; another path: a variant of it
+       with the same markers, e.g. an older revision)"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+CSRC = os.path.join(ROOT, "zybo-rt-sampler-image-detection_amd", "csrc")
+KERNEL = "das_pair2_kernel"
+OFF_PATH = ("BF_STAGE_MASKED", "BF_STAGE_PART0", "BF_STAGE_WIPE", "BF_STAGE_OTHER")
+KINDS = ("packed", "test/branch", "lds", "wait", "table load", "scalar", "vector")
+
+
+def compile_asm(src=None):
+    """gfx950 assembly text of the unit (device side only), built with the flags the library is built with."""
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    src = src or os.path.join(CSRC, "das_pair.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "das_pair.s")
+        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + [f for f in ge.HIPCC_FLAGS if f != "-fPIC"] + [
+            "-I", CSRC, "--cuda-device-only", "-S", src, "-o", out]
+        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+        return open(out).read()
+
+
+def kernel_lines(txt):
+    """The text lines of das_pair2_kernel, from its symbol to its .Lfunc_end."""
+    lines = txt.split("\n")
+    start = next(i for i, l in enumerate(lines) if re.match(r"_ZN\S*%s\S*:" % KERNEL, l))
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    return lines[start + 1:end]
+
+
+def kind_of(text):
+    op = text.split()[0]
+    if op.startswith(("v_pk_fma_f32", "v_pk_add_f32")):
+        return "packed"
+    if op.startswith(("s_cmp", "s_cbranch", "s_branch", "s_bitcmp")):
+        return "test/branch"
+    if op.startswith("ds_"):
+        return "lds"
+    if op in ("s_waitcnt", "s_nop"):
+        return "wait"
+    if op.startswith(("s_load_", "s_buffer_load_")):
+        return "table load"
+    return "scalar" if op.startswith("s_") else "vector"
+
+
+def parse(lines):
+    """-> (items, labels): items are instructions {text, sub, next, targets} and markers {marker, sub, next}, subsection 0 first;
+    labels: name -> index of the item behind it."""
+    subs, cur = {0: [], 1: []}, 0
+    for line in lines:
+        l = line.strip()
+        m = re.match(r";\s*(BF_\w+)", l)
+        if m:
+            subs[cur].append({"marker": m.group(1)})
+            continue
+        l = l.split(";")[0].strip()
+        if not l:
+            continue
+        m = re.match(r"\.subsection\s+(\d+)", l)
+        if m:
+            cur = int(m.group(1))
+            subs.setdefault(cur, [])
+            continue
+        if l.startswith("."):
+            m = re.match(r"(\.[\w$.]+):", l)
+            if m:
+                subs[cur].append({"label": m.group(1)})
+            continue
+        subs[cur].append({"text": l})
+    items, labels = [], {}
+    for sub in sorted(subs):
+        pending = []
+        for it in subs[sub]:
+            if "label" in it:
+                pending.append(it["label"])
+                continue
+            for lab in pending:
+                labels[lab] = len(items)
+            pending = []
+            items.append(dict(it, sub=sub))
+    for i, it in enumerate(items):
+        nxt = i + 1 if i + 1 < len(items) and items[i + 1]["sub"] == it["sub"] else None
+        targets = []
+        if "text" in it:
+            op = it["text"].split()[0]
+            if op == "s_branch":
+                targets, nxt = [it["text"].split()[1]], None
+            elif op.startswith("s_cbranch"):
+                targets = [it["text"].split()[1]]
+            elif op in ("s_endpgm", "s_setpc_b64"):
+                nxt = None
+        it["next"], it["targets"] = nxt, targets
+    return items, labels
+
+
+def staging_path(items, labels):
+    """(a): the instructions of the longest BF_STAGE_BEGIN -> BF_STAGE_END path that passes no OFF_PATH marker, in order; None
+    where the source has no such markers."""
+    begins = [i for i, it in enumerate(items) if it.get("marker") == "BF_STAGE_BEGIN"]
+    if not begins:
+        return None
+    memo = {}
+
+    def longest(i, on_path):
+        if i is None or i in on_path:
+            return None
+        it = items[i]
+        if it.get("marker") == "BF_STAGE_END":
+            return []
+        if it.get("marker") in OFF_PATH:
+            return None
+        if i in memo:
+            return memo[i]
+        succ = [it["next"]] + [labels.get(t) for t in it["targets"]]
+        best = None
+        for s in succ:
+            p = longest(s, on_path | {i})
+            if p is not None and (best is None or len(p) > len(best)):
+                best = p
+        if best is not None and "text" in it:
+            best = [it["text"]] + best
+        memo[i] = best
+        return best
+
+    sys.setrecursionlimit(20000)
+    paths = [p for p in (longest(b, frozenset()) for b in begins) if p is not None]
+    return max(paths, key=len) if paths else None
+
+
+def mic_gaps(lines):
+    """(b): one {kind: count} per pair of consecutive BF_S2_BEGIN markers of the text, `.subsection 1` blocks excluded."""
+    gaps, cur, stub = [], None, False
+    for line in lines:
+        l = line.strip()
+        if "BF_S2_BEGIN" in l:
+            if cur is not None:
+                gaps.append(cur)
+            cur = dict.fromkeys(KINDS, 0)
+            continue
+        l = l.split(";")[0].strip()
+        if re.match(r"\.subsection\s+1", l):
+            stub = True
+        elif re.match(r"\.subsection\s+0", l):
+            stub = False
+        elif cur is not None and not stub and l and not l.startswith(".") and not l.endswith(":"):
+            cur[kind_of(l)] += 1
+    return gaps
+
+
+def resources(txt):
+    """(c): the metadata entry of the kernel."""
+    blk = next(b for b in re.split(r"\n\s+- (?=\.agpr_count:)", txt)[1:] if KERNEL in re.search(r"\.name:\s+(\S+)", b).group(1))
+    g = lambda key: int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
+    return dict(vgprs=g("vgpr_count"), sgprs=g("sgpr_count"), sgpr_spills=g("sgpr_spill_count"), scratch=g("private_segment_fixed_size"))
+
+
+def lane_spills_in_half_loop(lines):
+    """v_readlane / v_writelane from the barrier before the first mic of the half loop's text to the barrier behind its last mic
+    (the loop's own barrier); None where the text has no mic."""
+    s2 = [i for i, l in enumerate(lines) if "BF_S2_BEGIN" in l]
+    bars = [i for i, l in enumerate(lines) if l.split(";")[0].strip() == "s_barrier"]
+    if not s2 or not [b for b in bars if b < s2[0]] or not [b for b in bars if b > s2[-1]]:
+        return None
+    lo, hi = max(b for b in bars if b < s2[0]), min(b for b in bars if b > s2[-1])
+    return sum(1 for l in lines[lo:hi] if re.match(r"v_(readlane|writelane)_b32", l.split(";")[0].strip()))
+
+
+def budget(src=None):
+    txt = compile_asm(src)
+    lines = kernel_lines(txt)
+    items, labels = parse(lines)
+    return dict(staging=staging_path(items, labels), gaps=mic_gaps(lines), resources=resources(txt), lane_spills=lane_spills_in_half_loop(lines))
+
+
+def report(b):
+    out = []
+    st = b["staging"]
+    if st is None:
+        out.append("(a) staging path of a steady-state half: no BF_STAGE_BEGIN / BF_STAGE_END markers in this source")
+    else:
+        kinds = dict.fromkeys(KINDS, 0)
+        for t in st:
+            kinds[kind_of(t)] += 1
+        out.append("(a) staging path of a steady-state half: %d instructions  (%s)" % (len(st), ", ".join("%s %d" % (k, kinds[k]) for k in KINDS if kinds[k])))
+        out += ["      " + t for t in st]
+    out.append("(b) from one mic's S2 to the next one's, stubs excluded: %d gaps" % len(b["gaps"]))
+    for i, g in enumerate(b["gaps"]):
+        out.append("      gap %d: %3d instructions  (%s)" % (i, sum(g.values()), ", ".join("%s %d" % (k, g[k]) for k in KINDS if g[k])))
+    r = b["resources"]
+    out.append("(c) VGPRs %d, SGPRs %d, spilled SGPRs %d, scratch %d bytes; v_readlane / v_writelane inside the half loop: %s" %
+               (r["vgprs"], r["sgprs"], r["sgpr_spills"], r["scratch"], b["lane_spills"]))
+    return "\n".join(out)
+
+
+if __name__ == "__main__":
+    print(report(budget(sys.argv[1] if len(sys.argv) > 1 else None)))

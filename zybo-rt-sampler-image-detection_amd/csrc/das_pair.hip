@@ -356,7 +356,12 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
     using G = Pair2Geo;
     constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane_ = threadIdx.x & (kWave - 1), lane = lane_;
+    const int lane = threadIdx.x & (kWave - 1);               // (set-up only: inside the group loop lane_id() recomputes it, a register less to carry through the sweep)
+    auto lane_id = []() -> int {
+        int l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return l;
+    };
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     int tile, fpair;
     tile_and_frame(a, &tile, &fpair);
@@ -375,65 +380,87 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
     const int32_t* __restrict__ dig = reinterpret_cast<const int32_t*>(taps);   // the digest rides in the unused `taps` slot
 
     // Staging: waves w and w + 8 share mic (w & 7) of every half (both fetch its two frames): part 0 writes the sample rows, part 1
-    // the difference rows.  Lane c holds half c's mic id (first 64 halves).
+    // the difference rows.  A wave's share of a half is straight-line code: the row base from the mic id (a scalar, loaded a half
+    // ahead), two loads, the interleaved quads built in v96.. (free between two sweeps) where the four stores read them.
     const int my_mic = wave & 7, part = wave >> 3;
-    const int vmic = (lane < n_half) ? mics[lane * HC + my_mic] : 0;
+    constexpr unsigned kHalfBytes = HC * G::kSlot * 4;          // from a row of half 0 to the same row of half 1
+    const bool full = N == 256;                                 // every lane has a quad of the row (wave-uniform, once per workgroup)
+    // scalar row base + one 32-bit lane offset (global_load saddr form): the per-lane 64-bit pointers of the two frames, hoisted out
+    // of the group loop, used to be spilled around the sweep (16 bytes of scratch per lane, stored once per workgroup and
+    // reloaded per group: WRITE_SIZE 5x the image bytes).  The load is unconditional: a lane beyond a short row reads the row's last
+    // quad instead, and `stage` zeroes what it brought (a load under a lane mask is merged with zeros -- eight moves -- on the spot).
+    const unsigned row_bytes = 4u * (unsigned)N, hoff_end = (unsigned)n_half * (HC * 4u);
+    unsigned voff = min(16u * (unsigned)lane, row_bytes - 16u);
+    const bool in_row = 16u * (unsigned)lane < row_bytes;
+    const char* mic_ids = reinterpret_cast<const char*>(mics + my_mic);
+    unsigned hoff = 0;                                          // the half the next fetch reads (byte offset into mic_ids) ...
+    int mic_a = *reinterpret_cast<const int32_t*>(mic_ids);     // ... and its mic id: a scalar load, consumed half a sweep later
     struct Staged2 { float4 v0, v1; };
-    auto fetch = [&](int h) -> Staged2 {
-        const int mic = (h < kWave) ? __builtin_amdgcn_readlane(vmic, h) : mics[h * HC + my_mic];
+    auto fetch_next = [&]() -> Staged2 {
+        const size_t row = (size_t)(unsigned)mic_a * row_bytes;
+        const char* r0 = reinterpret_cast<const char*>(sig0) + row;
+        const char* r1 = reinterpret_cast<const char*>(sig1) + row;
+        asm volatile("" : "+v"(voff));                          // (opaque: or hipcc folds it back into two hoisted 64-bit lane pointers)
         Staged2 st;
-        st.v0 = make_float4(0.f, 0.f, 0.f, 0.f);
-        st.v1 = st.v0;
-        if (4 * lane < N) {
-            // scalar row base + one 32-bit lane offset (global_load saddr form): the per-lane 64-bit pointers of the two frames, hoisted out
-            // of the group loop, used to be spilled around the sweep (16 bytes of scratch per lane, stored once per workgroup and
-            // reloaded per group: WRITE_SIZE 5x the image bytes)
-            unsigned voff = 16u * (unsigned)lane;
-            asm volatile("" : "+v"(voff));                      // (opaque: or hipcc folds it back into two hoisted 64-bit lane pointers)
-            const char* r0 = reinterpret_cast<const char*>(sig0 + (size_t)mic * N);
-            const char* r1 = reinterpret_cast<const char*>(sig1 + (size_t)mic * N);
-            st.v0 = *reinterpret_cast<const float4*>(r0 + voff);
-            st.v1 = *reinterpret_cast<const float4*>(r1 + voff);
-        }
+        st.v0 = *reinterpret_cast<const float4*>(r0 + voff);
+        st.v1 = *reinterpret_cast<const float4*>(r1 + voff);
+        hoff = hoff + HC * 4u < hoff_end ? hoff + HC * 4u : 0u;  // (after the last half: half 0 again, the next group's first -- or for nothing)
+        mic_a = *reinterpret_cast<const int32_t*>(mic_ids + hoff);
         return st;
     };
-    // rows of a mic: [s copy 0][s copy 1][d copy 0][d copy 1]; copy c holds sample i - c at position i; position i = floats 2 i, 2 i + 1
-    auto write_row = [&](float* row, const float4 x0, const float4 x1, float p0, float p1, bool shifted, int lane) {
-        float4* q = reinterpret_cast<float4*>(row + 2 * LEAD) + 2 * lane;
-        if (!shifted) {
-            q[0] = make_float4(x0.x, x1.x, x0.y, x1.y);
-            q[1] = make_float4(x0.z, x1.z, x0.w, x1.w);
-        } else {
-            q[0] = make_float4(p0, p1, x0.x, x1.x);
-            q[1] = make_float4(x0.y, x1.y, x0.z, x1.z);
+    // rows of a mic: [s copy 0][s copy 1][d copy 0][d copy 1]; copy c holds sample i - c at position i; position i = floats 2 i, 2 i + 1.
+    // With x = frame 0's quad and y = frame 1's (part 1: their differences), v[98:105] = (x.x, y.x, x.y, y.y, x.z, y.z, x.w, y.w) is the
+    // lane's piece of copy 0; with v[96:97] = the previous lane's (x.w, y.w) (0 in lane 0: the prefix), v[96:103] is its piece of copy 1.
+    // One statement for both parts (part 0's moves out of line): a C++ branch costs five scalar instructions here.
+    // (each DPP operand is written two or more instructions before it is read)
+#define BF_I_DPP " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+    const int lb = 16 * lane + (int)(unsigned)(size_t)((__attribute__((address_space(3))) char*)lds);   // the sweep's lane base
+    // a lane's 32 bytes of this wave's first row: 2 lb + row0 in half 0, 2 lb + row1 in half 1
+    const int row0 = (my_mic * G::kSlot + part * C * RS) * 4 - (int)(unsigned)(size_t)((__attribute__((address_space(3))) char*)lds), row1 = row0 + (int)kHalfBytes;
+    auto stage = [&](int row, const Staged2& st) {
+        const int ad = 2 * lb + row;
+        float4 x = st.v0, y = st.v1;
+        if (!full) {
+            asm volatile(";BF_STAGE_MASKED");
+            x = make_float4(in_row ? x.x : 0.f, in_row ? x.y : 0.f, in_row ? x.z : 0.f, in_row ? x.w : 0.f);
+            y = make_float4(in_row ? y.x : 0.f, in_row ? y.y : 0.f, in_row ? y.z : 0.f, in_row ? y.w : 0.f);
         }
+        asm volatile("s_cmp_eq_u32 %[part], 0\n\ts_cbranch_scc1 .Lp0_%=\n\t"
+                     // D[i] = s[i+1] - s[i], the reference's own subtraction (lerp_and_sum.c:54); D[-1] stays 0 (prefix)
+                     "v_sub_f32 v98, %[xy], %[xx]\n\tv_sub_f32 v99, %[yy], %[yx]\n\t"
+                     "v_sub_f32_dpp v104, %[xx], %[xw] wave_shl:1" BF_I_DPP "v_sub_f32_dpp v105, %[yx], %[yw] wave_shl:1" BF_I_DPP
+                     "v_sub_f32 v100, %[xz], %[xy]\n\tv_sub_f32 v101, %[yz], %[yy]\n\t"
+                     "v_sub_f32 v102, %[xw], %[xz]\n\tv_sub_f32 v103, %[yw], %[yz]\n"
+                     ".Lst_%=:\n\t"
+                     "v_mov_b32_dpp v96, v104 wave_shr:1" BF_I_DPP "v_mov_b32_dpp v97, v105 wave_shr:1" BF_I_DPP
+                     "ds_write_b128 %[ad], v[98:101] offset:%[c0]\n\tds_write_b128 %[ad], v[102:105] offset:%[c0] + 16\n\t"
+                     "ds_write_b128 %[ad], v[96:99] offset:%[c1]\n\tds_write_b128 %[ad], v[100:103] offset:%[c1] + 16\n\t"
+                     ".subsection 1\n"
+                     ".Lp0_%=:\n\t;BF_STAGE_PART0\n\t"
+                     "v_mov_b32 v104, %[xw]\n\tv_mov_b32 v105, %[yw]\n\tv_mov_b32 v98, %[xx]\n\tv_mov_b32 v99, %[yx]\n\t"
+                     "v_mov_b32 v100, %[xy]\n\tv_mov_b32 v101, %[yy]\n\tv_mov_b32 v102, %[xz]\n\tv_mov_b32 v103, %[yz]\n\t"
+                     "s_branch .Lst_%=\n\t.subsection 0"
+                     : : [xx] "v"(x.x), [xy] "v"(x.y), [xz] "v"(x.z), [xw] "v"(x.w), [yx] "v"(y.x), [yy] "v"(y.y), [yz] "v"(y.z), [yw] "v"(y.w),
+                         [ad] "v"(ad), [part] "s"(part), [c0] "n"(2 * LEAD * 4), [c1] "n"((RS + 2 * LEAD) * 4)
+                     : "memory", "scc", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105");
     };
-    auto stage = [&](int h, const Staged2& st, bool wipe) {
-        int lane = lane_;                                       // (opaque copy: the per-lane addresses are recomputed here, not hoisted)
-        asm volatile("" : "+v"(lane));
-        float* slot = lds + ((h & 1) * HC + my_mic) * G::kSlot;
-        float4 x0 = st.v0, x1 = st.v1;
-        float* rows = slot + part * C * RS;                     // the two rows this wave writes
-        if (part == 1) {
-            // D[i] = s[i+1] - s[i], the reference's own subtraction (lerp_and_sum.c:54); D[-1] stays 0 (prefix)
-            const float n0 = dpp_next(x0.x), n1 = dpp_next(x1.x);
-            x0 = make_float4(x0.y - x0.x, x0.z - x0.y, x0.w - x0.z, n0 - x0.w);
-            x1 = make_float4(x1.y - x1.x, x1.z - x1.y, x1.w - x1.z, n1 - x1.w);
-        }
-        const float p0 = dpp_prev(x0.w), p1 = dpp_prev(x1.w);   // the previous lane's last sample (0 in lane 0: the prefix)
-        write_row(rows, x0, x1, p0, p1, false, lane);
-        write_row(rows + RS, x0, x1, p0, p1, true, lane);
-        if (wipe) {
-            // the zero prefix (56 samples x 2 frames = 28 quads per row): only the parked rows of the power pass overwrite it
-            constexpr int PQ = LEAD >> 1;
-            static_assert(2 * PQ <= kWave, "one lane per prefix quad of two rows");
-            if (lane < 2 * PQ) reinterpret_cast<float4*>(rows + (lane / PQ) * RS)[lane % PQ] = make_float4(0.f, 0.f, 0.f, 0.f);
+#undef BF_I_DPP
+    // the zero prefix (56 samples x 2 frames = 28 quads per row) of this wave's two rows, in both halves: only the parked rows of the
+    // power pass overwrite it, so a group restores it once, before its first half is staged
+    auto wipe_prefix = [&]() {
+        constexpr int PQ = LEAD >> 1;
+        static_assert(2 * PQ <= kWave, "one lane per prefix quad of two rows");
+        const int l = lane_id();
+        if (l < 2 * PQ) {
+            float* rows = lds + my_mic * G::kSlot + part * C * RS;
+            float4* q = reinterpret_cast<float4*>(rows + (l < PQ ? 0 : RS)) + (l < PQ ? l : l - PQ);
+            q[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(reinterpret_cast<char*>(q) + kHalfBytes) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
 
     BF_STAMP_DECL
-    Staged2 st = fetch(0);
-    const int lb = 16 * lane + (int)(unsigned)(size_t)((__attribute__((address_space(3))) char*)lds);
+    Staged2 st = fetch_next();
 
     for (int g0 = tile_begin; g0 < tile_end; g0 += kGroup) {
         f32x2 acc[DW][4];                                       // (frame 0, frame 1) of samples 2l, 2l+1, 128+2l, 128+2l+1
@@ -445,8 +472,9 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
         BF_STAMP(7);
         __syncthreads();   // the previous group's parked rows have been summed
         BF_STAMP(1);
-        stage(0, st, true);
-        st = fetch(1 % n_half);
+        wipe_prefix();
+        stage(row0, st);
+        st = fetch_next();                                      // half 1
         BF_STAMP(2);
         __syncthreads();
         BF_STAMP(3);
@@ -454,16 +482,22 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
         const int dw0 = g0 + wave * DW;                         // wave-uniform
         const bool busy = dw0 < tile_end;
         const size_t grp = busy ? (size_t)(dw0 - a.dir_begin) / DW : 0;
+        const int32_t* __restrict__ etg = dig + grp * M * DW;
+        const float* __restrict__ htg = reinterpret_cast<const float*>(dig) + a.digest_h_off + grp * M * DW;
+        int row_next = row1;                                    // where the next half is staged: halves alternate
         for (int h = 0; h < n_half; ++h) {
+            asm volatile(";BF_STAGE_BEGIN");                    // (;BF_STAGE_*: path markers for scripts/dev/pair2_instruction_budget.py, comments in the assembly)
             if (h + 1 < n_half) {
-                stage(h + 1, st, h == 0);                       // into the half whose sweeps ended before the last barrier
-                if (h + 2 < n_half) st = fetch(h + 2);
-                else if (g0 + kGroup < tile_end) st = fetch(0);
+                stage(row_next, st);                            // into the half whose sweeps ended before the last barrier
+                row_next = row0 + row1 - row_next;
+                st = fetch_next();                              // staged an iteration from now: half h + 2, or the next group's first half
                 BF_STAMP(2);
             }
+            asm volatile(";BF_STAGE_END");
             if (busy) {
-                const int32_t* __restrict__ et = dig + (grp * M + (size_t)h * HC) * DW;
-                const float* __restrict__ ht = reinterpret_cast<const float*>(dig) + a.digest_h_off + (grp * M + (size_t)h * HC) * DW;
+                // one table base per half: the eight mics' entries and weights are immediate offsets off it
+                const int32_t* __restrict__ et = etg + (size_t)h * (HC * DW);
+                const float* __restrict__ ht = htg + (size_t)h * (HC * DW);
                 struct Entries { int e[DW]; unsigned long long hp[DW / 2]; };
                 auto request = [&](Entries& t, int m) {
                     // (reads past the half's last mic stay inside the slack-padded table and are dropped)
@@ -483,14 +517,8 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
                     pair2_rest(acc, cur.e, cur.hp, lb);
                 };
                 using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-                static_assert(HC == 8, "eight mics: two trips of three and two more");
-#pragma unroll 1
-                for (int t = 0; t < 2; ++t) {
-                    mic(0, I0{}); mic(1, I1{}); mic(2, I2{});
-                    et += 3 * DW; ht += 3 * DW;
-                }
-                mic(0, I0{});
-                mic(1, I1{});
+                static_assert(HC == 8, "eight mics, the three entry sets in rotation");
+                mic(0, I0{}); mic(1, I1{}); mic(2, I2{}); mic(3, I0{}); mic(4, I1{}); mic(5, I2{}); mic(6, I0{}); mic(7, I1{});
                 __builtin_amdgcn_s_waitcnt(0xC07F);             // the entries requested past the half's end have landed (and are dropped)
             }
             BF_STAMP(0);       // sweep -> waiting for the others
@@ -507,6 +535,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
                 BF_STAMP(4);
             }
             auto park = [&](auto mul_c) __attribute__((always_inline)) {
+                const int lane = lane_id();
 #pragma unroll
                 for (int j = 0; j < DW; ++j) {
                     float* row = lds + (wave * DW + j) * kPark;
@@ -528,8 +557,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
             BF_STAMP(5);                // -> waiting
             __syncthreads();
             BF_STAMP(6);                // -> ordered sum (two waves; the others go on to the next barrier)
-            int lane_o = lane;                            // (opaque: keeps the per-lane row address out of the registers the sweep needs)
-            asm volatile("" : "+v"(lane_o));
+            const int lane_o = lane_id();                 // (recomputed: keeps the per-lane row address out of the registers the sweep needs)
             const int g = wave * kWave + lane_o;          // parked row of this lane
             const int d = g0 + g;
             if (g < kGroup && d < tile_end && (f == 0 || two)) {
@@ -539,6 +567,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
                 const float4* row4 = reinterpret_cast<const float4*>(row);
                 float sum = 0.0f;
                 int k = 0;
+#pragma unroll 1                                           // (eight reads in flight, as ever: two trips' worth spill the staged quads)
                 for (; k + 32 <= N; k += 32) {
                     float4 v[8];
 #pragma unroll
