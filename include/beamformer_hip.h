@@ -641,6 +641,47 @@ int bf_mvdr_design_device(const float *d_signals, int m_total, int frames, const
                           double *d_snap, double *d_cov, double *d_chol, double *d_gains,
                           float *d_taps, int *d_status, int *d_fallback, void *stream);
 
+/* ---- the same taps from a covariance that is CARRIED, WEIGHTED and FORGOTTEN: bf_mvdr_design_device with its covariance as device state ----
+ * bf_mvdr_design_device learns from every frame of one batch and drops what it learned.  Here the weighted sum of X X^H is state on the
+ * device that carries from call to call, every frame has a weight read on the device (0 for a frame in which the look talker speaks:
+ * no self-cancellation from it), and a forgetting factor sets how long old frames count.  filtersum.mvdr_learn followed by
+ * filtersum.design_mvdr_learned is the host statement.  Every argument not named here means what it means in bf_mvdr_design_device.
+ * State, read and written in place:  d_acc float64 [K][n][n][2], the weighted sum per bin;  d_mass float64 [1], the weights' sum times
+ *   segs.  All-zero bytes are the empty state: the caller zeroes both to start a stream.  One state belongs to one (adaptive array,
+ *   n_taps, bin range, window, segment layout); nothing records them.
+ * d_weights : float64 [frames] on the device, NULL = all 1.0.  Frame f is LEARNED iff w_f is finite and > 0.  +-0.0 is skipped
+ *   silently; a NaN, an Inf or a negative weight is skipped and counted.  d_used int32 [2] = (frames learned, weights refused); every
+ *   call writes it.
+ * forget : lambda in (0, 1], applied once per LEARNED frame; a skipped frame leaves the state untouched bit for bit.  Forgetting counts
+ *   what was learned, not the time that passed: a long stretch of look-talker speech does not decay the state to 0 / 0.
+ * The chains.  One per entry a >= b, starting at the stored d_acc[kk][a][b]; frames in ascending f; for a learned frame
+ *     acc = forget * acc (both parts),   then for q = 0 .. segs-1:  acc = acc + w_f * t,   t = (ar*br + ai*bi, ai*br - ar*bi)
+ *   with X_p[a] = (ar, ai), X_p[b] = (br, bi), p = f * segs + q: bf_mvdr_design_device's term; nothing is contracted.  And
+ *     mass = forget * mass + w_f * (double)segs   over the same frames in the same order.
+ *   After the last frame acc goes back to d_acc, its conjugate to the mirror, +0.0 to the diagonal's imaginary part (a call that learns
+ *   no frame does not write d_acc at all), and d_cov = acc / mass where mass > 0, otherwise d_cov = 0: every bin then falls back
+ *   (d_fallback 1, the beam without nulls).  With d_acc and d_mass zero, weights NULL or all 1.0 and forget 1 the chains are
+ *   bf_mvdr_design_device's operations and all seven of its outputs come out byte for byte.
+ * Loading, factor, solve, taps: bf_mvdr_design_device's launches on this d_cov.  d_snap is written for every frame, learned or not.
+ * frames == 0 is the RE-AIM: new taps for the offsets given now from the state as it stands.  d_signals, d_weights, d_window and d_snap
+ *   may be NULL (they are not touched), adaptive_array is still checked, the state is untouched, d_used = (0, 0).
+ * stream : enqueue only: four launches (snapshots and the mass, accumulation, factor and solve, taps), three for the re-aim; no
+ *   allocation after the first call, no atomics, the same bits from call to call on the same state and inputs; graph-capturable after one
+ *   warm-up call.  A REPLAY ADVANCES THE STATE like any other call: a graph that learns, replayed twice on the same frames, has learned
+ *   them twice.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued, the state untouched) for bf_mvdr_design_device's refusals with
+ * frames < 0 in place of frames < 1, and: forget outside (0, 1] or NaN; d_acc, d_mass or d_used null; with frames > 0, d_signals or
+ * d_snap null; the byte range of d_acc, d_mass, d_used or another output overlapping that of an input (d_weights among them) or of
+ * another output.  All arguments are checked before device bring-up. */
+int bf_mvdr_learn_device(const float *d_signals, int m_total, int frames, const int *adaptive_array, int n,
+                         int seg_first, int seg_hop, int segs, const double *d_window,
+                         const double *d_weights, double forget,
+                         const double *d_tau, int dirs, const int *d_offsets, int sources, int offset_per_dir,
+                         int n_taps, int bin_lo, int bin_hi, double loading,
+                         double *d_acc, double *d_mass, int *d_used,
+                         double *d_snap, double *d_cov, double *d_chol, double *d_gains,
+                         float *d_taps, int *d_status, int *d_fallback, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

@@ -1587,6 +1587,64 @@ int bf_mvdr_design_device(const float* d_signals, int m_total, int frames, const
                                          as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- the same taps from a covariance that is carried, weighted and forgotten
+
+int bf_mvdr_learn_device(const float* d_signals, int m_total, int frames, const int* adaptive_array, int n, int seg_first, int seg_hop, int segs,
+                         const double* d_window, const double* d_weights, double forget, const double* d_tau, int dirs, const int* d_offsets, int sources,
+                         int offset_per_dir, int n_taps, int bin_lo, int bin_hi, double loading, double* d_acc, double* d_mass, int* d_used, double* d_snap,
+                         double* d_cov, double* d_chol, double* d_gains, float* d_taps, int* d_status, int* d_fallback, void* stream)
+{
+    static const char* who = "bf_mvdr_learn_device";
+    Entered in;
+    const int N = in.s.sz.n_samples;
+    if (!need_ptrs(who, {{adaptive_array, "adaptive_array"}, {d_tau, "d_tau"}, {d_offsets, "d_offsets"}, {d_acc, "d_acc"}, {d_mass, "d_mass"}, {d_used, "d_used"},
+                         {d_cov, "d_cov"}, {d_chol, "d_chol"}, {d_gains, "d_gains"}, {d_taps, "d_taps"}, {d_status, "d_status"}, {d_fallback, "d_fallback"}}))
+        return -1;
+    if (!need_min(who, "frames", frames, 0)) return -1;
+    if (frames > 0 && !need_ptrs(who, {{d_signals, "d_signals"}, {d_snap, "d_snap"}})) return -1;   // (frames == 0, the re-aim, reads no frame and writes no snapshot)
+    if (!need_min(who, "n", n, 1) || !need_min(who, "segs", segs, 1) || !need_min(who, "seg_hop", seg_hop, 1) || !need_min(who, "dirs", dirs, 1) ||
+        !need_min(who, "sources", sources, 1) || !need_min(who, "offset_per_dir", offset_per_dir, 1) || !need_min(who, "n_taps", n_taps, 1) ||
+        !need_min(who, "seg_first", seg_first, 0))
+        return -1;
+    if (!need_max(who, "n", n, BF_MVDR_MAX_MICS) || !need_max(who, "sources", sources, BF_LCMV_MAX_SOURCES) || !need_max(who, "n_taps", n_taps, BF_LCMV_MAX_TAPS))
+        return -1;
+    {
+        const long long last = (long long)seg_first + (long long)(segs - 1) * seg_hop + n_taps;
+        if (last > N) {
+            set_error("%s: seg_first + (segs - 1) * seg_hop + n_taps = %lld > N_SAMPLES = %d (a segment would leave its window)", who, last, N);
+            return -1;
+        }
+    }
+    if (!need_bins(who, bin_lo, bin_hi, n_taps)) return -1;
+    if (!std::isfinite(loading) || !(loading > 0.0)) { set_error("%s: loading = %.17g is not finite and > 0", who, loading); return -1; }
+    if (!(forget > 0.0 && forget <= 1.0)) { set_error("%s: forget = %.17g is not in (0, 1]", who, forget); return -1; }
+    if (!need_rows(who, adaptive_array, n, m_total)) return -1;
+    const bool learns = frames > 0;
+    const u64 S = (u64)sources, K = (u64)(bin_hi - bin_lo + 1), M = (u64)n, P = (u64)frames * (u64)segs, cplx = 2 * sizeof(double);
+    if (!need_disjoint(who, {{d_acc, sat_mul(K * M * M, cplx), "d_acc"},
+                             {d_mass, sizeof(double), "d_mass"},
+                             {d_used, 2 * sizeof(int), "d_used"},
+                             {learns ? d_snap : nullptr, sat_mul(sat_mul(sat_mul(P, K), M), cplx), "d_snap"},
+                             {d_cov, sat_mul(K * M * M, cplx), "d_cov"},
+                             {d_chol, sat_mul(K * M * M, cplx), "d_chol"},
+                             {d_gains, sat_mul(S * K * M, cplx), "d_gains"},
+                             {d_taps, sat_mul(S * (u64)n_taps * M, sizeof(float)), "d_taps"},
+                             {d_status, S * sizeof(int), "d_status"},
+                             {d_fallback, K * sizeof(int), "d_fallback"},
+                             {learns ? d_signals : nullptr, sat_mul(sat_mul(sat_mul((u64)frames, (u64)m_total), (u64)N), sizeof(float)), "d_signals"},
+                             {d_tau, sat_mul(sat_mul((u64)dirs, M), sizeof(double)), "d_tau"},
+                             {d_offsets, S * sizeof(int), "d_offsets"},
+                             {learns ? d_window : nullptr, (u64)n_taps * sizeof(double), "d_window"},
+                             {learns ? d_weights : nullptr, (u64)frames * sizeof(double), "d_weights"}}, 10))   // ten outputs (the state among them), five inputs
+        return -1;
+    if (!ensure_device()) return -1;
+    int max_row = 0;
+    if (learns && !upload_mics(adaptive_array, n, &max_row)) return -1;
+    return HIP_RC(bf::launch_mvdr_learn(d_signals, m_total, frames, N, in.s.d_mics.p, n, seg_first, seg_hop, segs, d_window, d_weights, forget, d_tau, dirs, d_offsets,
+                                        sources, offset_per_dir, n_taps, bin_lo, bin_hi, loading, d_acc, d_mass, d_used, d_snap, d_cov, d_chol, d_gains, d_taps,
+                                        d_status, d_fallback, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

@@ -207,6 +207,17 @@ hipError_t launch_mvdr_design(const float* d_signals, int m_total, int frames, i
                               const double* d_window, const double* d_tau, int dirs, const int32_t* d_offsets, int sources, int offset_per_dir, int n_taps,
                               int bin_lo, int bin_hi, double loading, double* d_snap, double* d_cov, double* d_chol, double* d_gains, float* d_taps,
                               int32_t* d_status, int32_t* d_fallback, hipStream_t stream);
+// bf_mvdr_learn_device (mvdr_design.hip): the same design from a covariance that is device STATE.  d_acc float64 [K][n][n][2] (the weighted
+// sum of X X^H, Hermitian bit for bit once written) and d_mass float64 [1] are read and written in place, all-zero bytes being the empty
+// state; d_weights float64 [frames] or null (all 1): a frame is learned iff its weight is finite and > 0, and a learned frame multiplies
+// the state by forget, in (0, 1], before it is added.  d_used int32 [2] = (frames learned, weights refused).  d_cov = d_acc / d_mass (0
+// where the mass is not > 0); factor, solve and taps are launch_mvdr_design's launches.  frames == 0 re-aims: no snapshots (d_signals,
+// d_window, d_weights, d_snap are not read), the state is untouched, three launches instead of four.
+hipError_t launch_mvdr_learn(const float* d_signals, int m_total, int frames, int n_samples, const int32_t* d_mics, int n, int seg_first, int seg_hop, int segs,
+                             const double* d_window, const double* d_weights, double forget, const double* d_tau, int dirs, const int32_t* d_offsets, int sources,
+                             int offset_per_dir, int n_taps, int bin_lo, int bin_hi, double loading, double* d_acc, double* d_mass, int32_t* d_used,
+                             double* d_snap, double* d_cov, double* d_chol, double* d_gains, float* d_taps, int32_t* d_status, int32_t* d_fallback,
+                             hipStream_t stream);
 
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.

@@ -24,6 +24,17 @@
 //       (a dynamically indexed register array would go to scratch).
 //
 // Four launches (the fourth is lcmv_taps_kernel), no atomics, no workspace beyond the named buffers: the same bits from call to call.
+//
+// bf_mvdr_learn_device keeps the covariance as device state (d_acc, d_mass) that carries from call to call: every frame has a weight,
+// every learned frame (weight finite and > 0) multiplies the state by `forget` first.  Its stages are the ones above with
+//   mvdr_learn_snapshot_kernel : mvdr_snapshot_kernel's snapshots (the same body); thread 0 of workgroup 0 also advances d_mass over the
+//       learned frames and counts d_used -- no other thread of that launch reads either, the next launch reads the final mass.
+//   mvdr_accumulate_kernel     : in mvdr_cov_kernel's place and shape.  A thread's chain starts from the entry of d_acc it owns, runs
+//       over the learned frames in ascending f (acc = forget acc at q = 0, then acc = acc + w_f t over q upwards, t being
+//       mvdr_cov_kernel's term), goes back to d_acc with its mirror where a frame was learned, and d_cov = acc / mass (0 where the
+//       mass is not > 0: every bin then falls back).  A thread reads only the entry it owns and writes it and its mirror: in place
+//       without a race.  A staged chunk whose frames are all skipped is not loaded; a call that learns nothing does not write d_acc.
+// With frames == 0 (the re-aim) there are no snapshots: the accumulate launch turns the stored state into d_cov and writes d_used.
 #include <hip/hip_runtime.h>
 
 #include "das_kernels.h"
@@ -42,9 +53,10 @@ constexpr int kCovP = 16;                      // ... and stages this many snaps
 constexpr int kSolveThreads = 1024;
 constexpr int kSolveWaves = kSolveThreads / 64;
 
-__global__ void __launch_bounds__(kSnapThreads)
-mvdr_snapshot_kernel(const float* __restrict__ signals, const int32_t* __restrict__ mics, int m_total, int n_samples, int n, int seg_first, int seg_hop, int segs,
-                     const double* __restrict__ window, int T, int bin_lo, int K, int mic_blocks, double* __restrict__ snap)
+// The body of the two snapshot kernels: one workgroup's (snapshot, block of microphones).
+__device__ __forceinline__ void snapshot_block(const float* __restrict__ signals, const int32_t* __restrict__ mics, int m_total, int n_samples, int n, int seg_first,
+                                               int seg_hop, int segs, const double* __restrict__ window, int T, int bin_lo, int K, int mic_blocks,
+                                               double* __restrict__ snap)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];     // [T][2]: cos, sin of 2 pi r / T; then [T]: the window
     double* __restrict__ tw = lds;
@@ -80,6 +92,47 @@ mvdr_snapshot_kernel(const float* __restrict__ signals, const int32_t* __restric
         out[0] = acc_r;
         out[1] = acc_i;
     }
+}
+
+__global__ void __launch_bounds__(kSnapThreads)
+mvdr_snapshot_kernel(const float* __restrict__ signals, const int32_t* __restrict__ mics, int m_total, int n_samples, int n, int seg_first, int seg_hop, int segs,
+                     const double* __restrict__ window, int T, int bin_lo, int K, int mic_blocks, double* __restrict__ snap)
+{
+    snapshot_block(signals, mics, m_total, n_samples, n, seg_first, seg_hop, segs, window, T, bin_lo, K, mic_blocks, snap);
+}
+
+// A frame is learned iff its weight is finite and > 0 (a NaN fails both comparisons); the weight of a frame that is not is 0 here.
+__device__ __forceinline__ double learned_weight(const double* __restrict__ weights, int f)
+{
+    const double w = weights ? weights[f] : 1.0;
+    return w > 0.0 && w <= 1.79769313486231570815e308 ? w : 0.0;
+}
+
+// mvdr_snapshot_kernel, and the mass chain: mass = forget mass + w_f segs over the learned frames in ascending f.  used = (frames
+// learned, weights refused: NaN, Inf, negative; a weight of +-0 is skipped without being counted).
+__global__ void __launch_bounds__(kSnapThreads)
+mvdr_learn_snapshot_kernel(const float* __restrict__ signals, const int32_t* __restrict__ mics, int m_total, int n_samples, int n, int seg_first, int seg_hop, int segs,
+                           const double* __restrict__ window, int T, int bin_lo, int K, int mic_blocks, double* __restrict__ snap,
+                           const double* __restrict__ weights, int frames, double forget, double* __restrict__ mass, int32_t* __restrict__ used)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double m = mass[0];
+        int learned = 0, refused = 0;
+        for (int f = 0; f < frames; ++f) {
+            const double w = learned_weight(weights, f);
+            if (w > 0.0) {
+                m = forget * m;
+                m = m + w * (double)segs;
+                ++learned;
+            } else if (weights && !(weights[f] == 0.0)) {
+                ++refused;
+            }
+        }
+        mass[0] = m;
+        used[0] = learned;
+        used[1] = refused;
+    }
+    snapshot_block(signals, mics, m_total, n_samples, n, seg_first, seg_hop, segs, window, T, bin_lo, K, mic_blocks, snap);
 }
 
 __global__ void __launch_bounds__(kCovThreads)
@@ -124,6 +177,85 @@ mvdr_cov_kernel(const double* __restrict__ snap, int P, int K, int n, int tiles,
         if (a != b) {
             base[((size_t)b * n + a) * 2] = re;
             base[((size_t)b * n + a) * 2 + 1] = -im;
+        }
+    }
+}
+
+// `used` is given only where no snapshot launch ran (frames == 0): this launch then writes (0, 0), and nothing reads it.
+__global__ void __launch_bounds__(kCovThreads)
+mvdr_accumulate_kernel(const double* __restrict__ snap, const double* __restrict__ weights, int frames, int segs, double forget, int K, int n, int tiles,
+                       const double* __restrict__ mass, double* acc, double* __restrict__ cov, int32_t* __restrict__ used)
+{
+    __shared__ __attribute__((aligned(16))) double xa[kCovP][kTile][2];   // X_p[a0 + .]
+    __shared__ __attribute__((aligned(16))) double xb[kCovP][kTile][2];   // X_p[b0 + .]
+    const int tid = (int)threadIdx.x;
+    const int kk = (int)blockIdx.x / tiles;
+    int ta = 0, tb = (int)blockIdx.x % tiles;    // tile (ta >= tb) of the lower triangle, counted row by row
+    while (tb > ta) { tb -= ta + 1; ++ta; }
+    const int a0 = ta * kTile, b0 = tb * kTile;
+    const int ia = tid / kTile, ib = tid % kTile;
+    const int a = a0 + ia, b = b0 + ib;
+    const bool mine = a < n && b <= a;
+    double* base = acc + (size_t)kk * n * n * 2;  // (no __restrict__: the entry is read, then it and its mirror are written)
+    double acc_r = 0.0, acc_i = 0.0;
+    if (mine) { acc_r = base[((size_t)a * n + b) * 2]; acc_i = base[((size_t)a * n + b) * 2 + 1]; }
+    if (used && blockIdx.x == 0 && tid == 0) { used[0] = 0; used[1] = 0; }
+    const int P = frames * segs;
+    bool learned_any = false;
+    for (int p0 = 0; p0 < P; p0 += kCovP) {
+        const int live = min(kCovP, P - p0);
+        int f = p0 / segs, q = p0 - f * segs;    // of snapshot p0; a frame boundary may fall anywhere in the chunk
+        bool any = false;
+        for (int ff = f; ff <= (p0 + live - 1) / segs; ++ff) any = any || learned_weight(weights, ff) > 0.0;
+        if (!any) continue;                      // (the same for every thread of the workgroup)
+        learned_any = true;
+        {
+            const int pp = tid / kTile, j = tid % kTile, p = p0 + pp;      // consecutive threads: consecutive microphones of one snapshot
+            double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
+            if (p < P) {
+                const double* __restrict__ row = snap + ((size_t)p * K + kk) * (size_t)n * 2;
+                if (a0 + j < n) { ar = row[2 * (size_t)(a0 + j)]; ai = row[2 * (size_t)(a0 + j) + 1]; }
+                if (b0 + j < n) { br = row[2 * (size_t)(b0 + j)]; bi = row[2 * (size_t)(b0 + j) + 1]; }
+            }
+            xa[pp][j][0] = ar; xa[pp][j][1] = ai;
+            xb[pp][j][0] = br; xb[pp][j][1] = bi;
+        }
+        __syncthreads();
+        double w = learned_weight(weights, f);
+        for (int pp = 0; pp < live; ++pp) {      // ascending p
+            if (w > 0.0) {
+                if (q == 0) { acc_r = forget * acc_r; acc_i = forget * acc_i; }
+                const double ar = xa[pp][ia][0], ai = xa[pp][ia][1], br = xb[pp][ib][0], bi = xb[pp][ib][1];
+                acc_r = acc_r + w * (ar * br + ai * bi);          // w a conj(b)
+                acc_i = acc_i + w * (ai * br - ar * bi);
+            }
+            if (++q == segs) {
+                q = 0;
+                ++f;
+                w = f < frames ? learned_weight(weights, f) : 0.0;
+            }
+        }
+        __syncthreads();
+    }
+    if (mine) {
+        if (a == b) acc_i = 0.0;
+        if (learned_any) {                       // a call that learns nothing leaves the state's bytes alone
+            base[((size_t)a * n + b) * 2] = acc_r;
+            base[((size_t)a * n + b) * 2 + 1] = acc_i;
+            if (a != b) {
+                base[((size_t)b * n + a) * 2] = acc_r;
+                base[((size_t)b * n + a) * 2 + 1] = -acc_i;
+            }
+        }
+        const double m = mass[0];
+        const bool some = m > 0.0;               // (a NaN mass is none)
+        const double re = some ? acc_r / m : 0.0, im = some && a != b ? acc_i / m : 0.0;
+        double* __restrict__ out = cov + (size_t)kk * n * n * 2;
+        out[((size_t)a * n + b) * 2] = re;
+        out[((size_t)a * n + b) * 2 + 1] = im;
+        if (a != b) {
+            out[((size_t)b * n + a) * 2] = re;
+            out[((size_t)b * n + a) * 2 + 1] = -im;
         }
     }
 }
@@ -290,6 +422,40 @@ hipError_t launch_mvdr_design(const float* d_signals, int m_total, int frames, i
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mvdr_cov_kernel, dim3((unsigned)(K * tiles)), dim3(kCovThreads), 0, stream, d_snap, (int)P, K, n, tiles, d_cov);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mvdr_solve_kernel, dim3((unsigned)K), dim3(kSolveThreads), 0, stream, d_cov, d_tau, d_offsets, dirs, n, sources, offset_per_dir, n_taps,
+                       bin_lo, K, loading, d_chol, d_gains, d_status, d_fallback);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_lcmv_taps(d_gains, d_status, sources, n, n_taps, bin_lo, K, d_taps, stream);
+}
+
+hipError_t launch_mvdr_learn(const float* d_signals, int m_total, int frames, int n_samples, const int32_t* d_mics, int n, int seg_first, int seg_hop, int segs,
+                             const double* d_window, const double* d_weights, double forget, const double* d_tau, int dirs, const int32_t* d_offsets, int sources,
+                             int offset_per_dir, int n_taps, int bin_lo, int bin_hi, double loading, double* d_acc, double* d_mass, int32_t* d_used,
+                             double* d_snap, double* d_cov, double* d_chol, double* d_gains, float* d_taps, int32_t* d_status, int32_t* d_fallback,
+                             hipStream_t stream)
+{
+    if (m_total < 1 || frames < 0 || n < 1 || n > kMvdrMaxMics || seg_first < 0 || seg_hop < 1 || segs < 1 || dirs < 1 || sources < 1 || sources > kLcmvMaxSources ||
+        offset_per_dir < 1 || n_taps < 1 || n_taps > kLcmvMaxTaps || bin_lo < 0 || bin_hi < bin_lo || bin_hi > n_taps / 2 || !(loading > 0.0) ||
+        !(forget > 0.0 && forget <= 1.0) || (long long)seg_first + (long long)(segs - 1) * seg_hop + n_taps > n_samples)
+        return hipErrorInvalidValue;
+    const int K = bin_hi - bin_lo + 1;
+    const long long P = (long long)frames * segs;
+    const int snap_blocks = (n + kSnapMics - 1) / kSnapMics;
+    const int tiles_1d = (n + kTile - 1) / kTile, tiles = tiles_1d * (tiles_1d + 1) / 2;
+    if (P * snap_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipError_t e = hipSuccess;
+    if (frames > 0) {
+        hipLaunchKernelGGL(mvdr_learn_snapshot_kernel, dim3((unsigned)(P * snap_blocks)), dim3(kSnapThreads), (size_t)n_taps * 3 * sizeof(double), stream, d_signals,
+                           d_mics, m_total, n_samples, n, seg_first, seg_hop, segs, d_window, n_taps, bin_lo, K, snap_blocks, d_snap, d_weights, frames, forget,
+                           d_mass, d_used);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(mvdr_accumulate_kernel, dim3((unsigned)(K * tiles)), dim3(kCovThreads), 0, stream, d_snap, d_weights, frames, segs, forget, K, n, tiles, d_mass,
+                       d_acc, d_cov, frames > 0 ? nullptr : d_used);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mvdr_solve_kernel, dim3((unsigned)K), dim3(kSolveThreads), 0, stream, d_cov, d_tau, d_offsets, dirs, n, sources, offset_per_dir, n_taps,

@@ -25,6 +25,13 @@ from the covariance of the frames themselves (bf_mvdr_design_device: MVDR, unit 
     status, fallback = fs_.adapt(d_frames, offsets[-1]);  out = fs_.listen(d_frames)
 `design_mvdr` / `design_mvdr_slots` are its host statements.  Limit: frames in which the look talker is as loud as the interference
 make sample-covariance MVDR cancel part of the look signal as well (self-cancellation); adapt on frames where it is weak.
+The cure is `learn`: the covariance is state on the device that carries from call to call (bf_mvdr_learn_device), every frame has a
+weight read on the device -- 0 where the look talker speaks -- and `forget` sets how long old frames count; `reaim` designs new taps
+from the state as it stands when the tracker moves a slot, `forget_all` empties it:
+    offsets, ids, pos, match, counts = tracker.update(offs)
+    status, fallback, used = fs_.learn(d_frames, offsets[-1], weights=(match[:, s] < 0).double(), forget=0.9)
+    status, fallback = fs_.reaim(offsets[-1]);  out = fs_.listen(d_frames)
+`mvdr_learn` / `design_mvdr_learned` are its host statements.
 A caller with weights of their own passes `taps=` to FilterSumListener."""
 import numpy as np
 
@@ -156,19 +163,15 @@ def design_slots(tau, offsets, offset_per_dir, n_taps=65, band=(3000.0, 8000.0),
     return taps, kept, status
 
 
-def _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_hop, segs, window, fs):
-    """The float64 statement of bf_mvdr_design_device up to the gains, for the directions `dirs` (-1: no source, zero gains).
-    -> (gains complex128 [B, K, M], fallback int32 [K], bins)."""
+def _mvdr_snapshots(frames, mics, T, bins, seg_first, seg_hop, segs, window, min_frames=1):
+    """The snapshots of bf_mvdr_design_device in float64 -> (snap complex128 [F * segs, K, M], segs as chosen)."""
     x = np.asarray(frames)
     if x.ndim != 3 or x.dtype != np.float32:
         raise ValueError("frames must be float32 [F, M_total, N], got %s %s" % (x.dtype, x.shape))
-    tau, T, bins = _design_args(tau, n_taps, band, fs)
     mics = np.asarray(mics).astype(np.int64).ravel()
     F, m_total, N = x.shape
     M = int(mics.size)
-    if M < 1 or M != tau.shape[1]:
-        raise ValueError("mics lists %d rows, tau is for %d microphones" % (M, tau.shape[1]))
-    if mics.min() < 0 or mics.max() >= m_total:
+    if M < 1 or mics.min() < 0 or mics.max() >= m_total:
         raise ValueError("mics names a row outside the frames' %d rows" % m_total)
     if T > N:
         raise ValueError("n_taps must be in [1, N = %d], got %d" % (N, T))
@@ -176,29 +179,35 @@ def _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_h
     if seg_first < 0 or seg_hop < 1:
         raise ValueError("seg_first must be >= 0 and seg_hop >= 1, got %d and %d" % (seg_first, seg_hop))
     segs = (N - seg_first - T) // seg_hop + 1 if segs is None else int(segs)
-    if F < 1 or segs < 1 or seg_first + (segs - 1) * seg_hop + T > N:
+    if F < min_frames or segs < 1 or seg_first + (segs - 1) * seg_hop + T > N:
         raise ValueError("segments [%d + q * %d, + %d), q < %d, do not fit windows of %d samples" % (seg_first, seg_hop, T, segs, N))
-    loading = float(loading)
-    if not (np.isfinite(loading) and loading > 0.0):
-        raise ValueError("loading must be finite and > 0, got %g" % loading)
     win = np.ones(T) if window is None else np.asarray(window, dtype=np.float64)
     if win.shape != (T,):
         raise ValueError("window must be [n_taps = %d], got shape %s" % (T, win.shape))
-    for d in dirs:
-        if d >= tau.shape[0]:
-            raise ValueError("direction %d is outside tau's %d directions" % (d, tau.shape[0]))
-    K, P = bins.size, F * segs
     r = np.arange(T)
     table = np.cos(2.0 * np.pi * r / T) - 1j * np.sin(2.0 * np.pi * r / T)            # e^{-j 2 pi r / T}
     E = table[(np.arange(T)[:, None] * bins[None, :]) % T]                           # [T, K]: the integer (k t) mod T picks the entry
-    snap = np.empty((P, K, M), dtype=np.complex128)
+    snap = np.empty((F * segs, bins.size, M), dtype=np.complex128)
     with np.errstate(all="ignore"):                                                  # NaN and Inf samples are an input like any other
         for f in range(F):
             for q in range(segs):
                 s0 = seg_first + q * seg_hop
                 seg = x[f][mics, s0:s0 + T].astype(np.float64) * win[None, :]
                 snap[f * segs + q] = (seg @ E).T
-        cov = np.einsum("pka,pkb->kab", snap, snap.conj()) / P
+    return snap, segs
+
+
+def _mvdr_gains_of(cov, tau, dirs, bins, T, loading):
+    """Loading, factor and solve of bf_mvdr_design_device on a covariance complex128 [K, M, M], for the directions `dirs` (-1: no
+    source, zero gains) -> (gains complex128 [B, K, M], fallback int32 [K])."""
+    loading = float(loading)
+    if not (np.isfinite(loading) and loading > 0.0):
+        raise ValueError("loading must be finite and > 0, got %g" % loading)
+    for d in dirs:
+        if d >= tau.shape[0]:
+            raise ValueError("direction %d is outside tau's %d directions" % (d, tau.shape[0]))
+    K, M = bins.size, tau.shape[1]
+    with np.errstate(all="ignore"):
         fallback = np.zeros(K, dtype=np.int32)
         G = np.zeros((len(dirs), K, M), dtype=np.complex128)
         for i, k in enumerate(bins):
@@ -218,6 +227,19 @@ def _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_h
                 z = np.linalg.solve(L.conj().T, y)
                 u = z * np.exp(1j * w * (T - 1) / 2.0) / np.sum(np.abs(y) ** 2)
                 G[b, i] = u.conj()
+    return G, fallback
+
+
+def _mvdr_gains(frames, mics, tau, dirs, n_taps, band, loading, seg_first, seg_hop, segs, window, fs):
+    """The float64 statement of bf_mvdr_design_device up to the gains, for the directions `dirs` (-1: no source, zero gains).
+    -> (gains complex128 [B, K, M], fallback int32 [K], bins)."""
+    tau, T, bins = _design_args(tau, n_taps, band, fs)
+    if np.asarray(mics).size != tau.shape[1]:
+        raise ValueError("mics lists %d rows, tau is for %d microphones" % (np.asarray(mics).size, tau.shape[1]))
+    snap, _ = _mvdr_snapshots(frames, mics, T, bins, seg_first, seg_hop, segs, window)
+    with np.errstate(all="ignore"):
+        cov = np.einsum("pka,pkb->kab", snap, snap.conj()) / snap.shape[0]
+    G, fallback = _mvdr_gains_of(cov, tau, dirs, bins, T, loading)
     return G, fallback, bins
 
 
@@ -262,6 +284,73 @@ def design_mvdr_slots(frames, mics, tau, offsets, offset_per_dir, n_taps=65, ban
     if not dirs:
         raise ValueError("offsets is empty")
     G, fallback, bins = _mvdr_gains(frames, mics, tau, dirs, T, band, loading, seg_first, seg_hop, segs, window, fs)
+    return _taps_of_gains(G, bins, T), fallback, np.array([0 if d >= 0 else 1 for d in dirs], dtype=np.int32)
+
+
+def mvdr_learn(acc, mass, frames, mics, weights=None, forget=1.0, n_taps=65, band=(3000.0, 8000.0), seg_first=0, seg_hop=16, segs=None, window=None, fs=None):
+    """The state of bf_mvdr_learn_device advanced by one call, in float64 on the host: its chains one for one.
+
+    acc complex128 [K, M, M], the weighted sum of X X^H per in-band bin, and mass, the weights' sum times segs; zeros are the empty
+    state (acc None: empty).  frames float32 [F, M_total, N] (F = 0: nothing happens), mics, the segments and the window as
+    design_mvdr.  weights [F] or None (all 1): frame f is learned iff its weight is finite and > 0; +-0 is skipped silently, a NaN, an
+    Inf or a negative weight is skipped and counted.  Per learned frame, in ascending f:
+        acc = forget * acc;  acc = acc + w_f * X_p X_p^H for every segment q in ascending order;  mass = forget * mass + w_f * segs
+    with forget in (0, 1].  A skipped frame changes nothing: forgetting counts learned frames, not time.
+    ->    (acc complex128 [K, M, M] (a new array, exactly Hermitian), mass float, used int32 [2] = (learned, refused))."""
+    T = int(n_taps)
+    if T < 1:
+        raise ValueError("n_taps must be >= 1, got %d" % T)
+    bins = band_bins(T, band, fs)
+    if bins.size == 0:
+        raise ValueError("no bin of the %d-point grid lies in the band (%g, %g)" % (T, band[0], band[1]))
+    forget = float(forget)
+    if not 0.0 < forget <= 1.0:
+        raise ValueError("forget must be in (0, 1], got %g" % forget)
+    snap, segs = _mvdr_snapshots(frames, mics, T, bins, seg_first, seg_hop, segs, window, min_frames=0)
+    F, K, M = snap.shape[0] // segs, bins.size, snap.shape[2]
+    acc = np.zeros((K, M, M), dtype=np.complex128) if acc is None else np.asarray(acc, dtype=np.complex128)
+    if acc.shape != (K, M, M):
+        raise ValueError("acc must be [K = %d, M = %d, M], got shape %s" % (K, M, acc.shape))
+    w_all = np.ones(F) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
+    if w_all.shape != (F,):
+        raise ValueError("weights must be [F = %d], got shape %s" % (F, w_all.shape))
+    re, im, mass = acc.real.copy(), acc.imag.copy(), float(mass)
+    learned = refused = 0
+    with np.errstate(all="ignore"):
+        for f in range(F):
+            w = float(w_all[f])
+            if not (np.isfinite(w) and w > 0.0):
+                refused += 0 if w == 0.0 else 1
+                continue
+            learned += 1
+            re, im = forget * re, forget * im
+            for q in range(segs):
+                xr, xi = snap[f * segs + q].real, snap[f * segs + q].imag                        # [K, M]
+                re = re + w * (xr[:, :, None] * xr[:, None, :] + xi[:, :, None] * xi[:, None, :])     # X[a] conj(X[b])
+                im = im + w * (xi[:, :, None] * xr[:, None, :] - xr[:, :, None] * xi[:, None, :])
+            mass = forget * mass + w * float(segs)
+    out = np.empty((K, M, M), dtype=np.complex128)
+    out.real, out.imag = re, im
+    return out, mass, np.array([learned, refused], dtype=np.int32)
+
+
+def design_mvdr_learned(acc, mass, tau, offsets, offset_per_dir, n_taps=65, band=(3000.0, 8000.0), loading=0.1, fs=None):
+    """design_mvdr_slots' taps from a learned state (`mvdr_learn`) instead of frames: the covariance is acc / mass, all zeros where the
+    mass is not > 0 -- every bin then falls back to the beam without nulls.  Loading, factor, solve and taps are design_mvdr's.
+    ->    (taps float32 [S, M, T], fallback int32 [K], status int32 [S])."""
+    tau, T, bins = _design_args(tau, n_taps, band, fs)
+    dirs = slot_directions(offsets, offset_per_dir, tau.shape[0])
+    if not dirs:
+        raise ValueError("offsets is empty")
+    acc = np.asarray(acc, dtype=np.complex128)
+    if acc.shape != (bins.size, tau.shape[1], tau.shape[1]):
+        raise ValueError("acc must be [K = %d, M = %d, M], got shape %s" % (bins.size, tau.shape[1], acc.shape))
+    mass = float(mass)
+    cov = np.zeros_like(acc)
+    if mass > 0.0:
+        with np.errstate(all="ignore"):
+            cov.real, cov.imag = acc.real / mass, acc.imag / mass
+    G, fallback = _mvdr_gains_of(cov, tau, dirs, bins, T, loading)
     return _taps_of_gains(G, bins, T), fallback, np.array([0 if d >= 0 else 1 for d in dirs], dtype=np.int32)
 
 
@@ -315,7 +404,8 @@ class FilterSumListener(CarriedBeams):
         self.d_taps = _torch().from_numpy(g).to(device)
         self.dirs = self.kept = None                    # set by cross_null
         self.d_tau = None                               # set by for_slots: the device-side designer's state
-        self.d_snap = self.d_cov = self.d_chol = self.d_fallback = self._window = self._mvdr_key = None      # adapt's workspaces
+        self.d_snap = self.d_cov = self.d_chol = self.d_fallback = self._window = self._mvdr_key = None      # adapt's and learn's workspaces
+        self.d_acc = self.d_mass = self.d_used = None   # learn's state: the carried covariance
 
     @classmethod
     def cross_null(cls, tau, offsets, offset_per_dir, mics=None, hop=None, device="cuda", **design):
@@ -379,6 +469,38 @@ class FilterSumListener(CarriedBeams):
         self.taps = None
         return self.d_status, self.d_kept
 
+    def _mvdr_args(self, loading, seg_hop, window):
+        """What adapt and learn check and choose alike -> (loading, seg_hop, seg_first, segs, d_window or None)."""
+        torch = _torch()
+        N = config.N_SAMPLES
+        loading, seg_hop = float(loading), int(seg_hop)
+        if not (np.isfinite(loading) and loading > 0.0):
+            raise ValueError("loading must be finite and > 0, got %g" % loading)
+        if seg_hop < 1:
+            raise ValueError("seg_hop must be >= 1, got %d" % seg_hop)
+        seg_first = max(0, N - self.hop - self.T + 1) if self.hop > 0 else 0
+        segs = (N - seg_first - self.T) // seg_hop + 1
+        if window is None:
+            return loading, seg_hop, seg_first, segs, None
+        win = np.ascontiguousarray(window, dtype=np.float64)
+        if win.shape != (self.T,):
+            raise ValueError("window must be [n_taps = %d], got shape %s" % (self.T, win.shape))
+        if self._window is None or not np.array_equal(self._window[0], win):
+            self._window = (win.copy(), torch.from_numpy(win).to(self.device))
+        return loading, seg_hop, seg_first, segs, self._window[1]
+
+    def _mvdr_workspaces(self, P):
+        """d_snap for P snapshots (kept until another count is asked for; P = 0: none needed), d_cov, d_chol and d_fallback once."""
+        torch = _torch()
+        K = int(self.bins.size)
+        if self.d_cov is None:
+            self.d_cov = torch.empty((K, self.n, self.n, 2), dtype=torch.float64, device=self.device)
+            self.d_chol = torch.empty((K, self.n, self.n, 2), dtype=torch.float64, device=self.device)
+            self.d_fallback = torch.zeros((K,), dtype=torch.int32, device=self.device)
+        if P > 0 and self._mvdr_key != P:
+            self.d_snap = torch.empty((P, K, self.n, 2), dtype=torch.float64, device=self.device)
+            self._mvdr_key = P
+
     def adapt(self, d_frames, d_offsets, loading=0.1, seg_hop=16, window=None):
         """Re-design every beam from the covariance of d_frames (float32 cuda [F, M_total, N_SAMPLES], what `listen` takes) with unit
         response towards the slots of d_offsets (int32 cuda [slots], as `retarget`): enqueues bf_mvdr_design_device on the current
@@ -387,40 +509,72 @@ class FilterSumListener(CarriedBeams):
         so consecutive overlapping windows never count one segment twice.  window: float64 [n_taps] or None (rectangular).  The
         workspaces (d_snap, d_cov, d_chol) are allocated on the first call for a frame count and kept.
         -> (d_status int32 [slots], d_fallback int32 [K]: 1 where a bin fell back to the beam without nulls), the listener's own tensors."""
-        torch = self._check_slots("adapt", d_offsets)
+        self._check_slots("adapt", d_offsets)
         frames = self._frames(d_frames)
         F, m_total, N = frames.shape
-        loading, seg_hop = float(loading), int(seg_hop)
-        if not (np.isfinite(loading) and loading > 0.0):
-            raise ValueError("loading must be finite and > 0, got %g" % loading)
-        if seg_hop < 1:
-            raise ValueError("seg_hop must be >= 1, got %d" % seg_hop)
-        seg_first = max(0, N - self.hop - self.T + 1) if self.hop > 0 else 0
-        segs = (N - seg_first - self.T) // seg_hop + 1
-        K = int(self.bins.size)
-        if window is None:
-            d_window = None
-        else:
-            win = np.ascontiguousarray(window, dtype=np.float64)
-            if win.shape != (self.T,):
-                raise ValueError("window must be [n_taps = %d], got shape %s" % (self.T, win.shape))
-            if self._window is None or not np.array_equal(self._window[0], win):
-                self._window = (win.copy(), torch.from_numpy(win).to(self.device))
-            d_window = self._window[1]
-        key = (F, segs)
-        if self._mvdr_key != key:
-            self.d_snap = torch.empty((F * segs, K, self.n, 2), dtype=torch.float64, device=self.device)
-            if self.d_cov is None:
-                self.d_cov = torch.empty((K, self.n, self.n, 2), dtype=torch.float64, device=self.device)
-                self.d_chol = torch.empty((K, self.n, self.n, 2), dtype=torch.float64, device=self.device)
-                self.d_fallback = torch.zeros((K,), dtype=torch.int32, device=self.device)
-            self._mvdr_key = key
+        loading, seg_hop, seg_first, segs, d_window = self._mvdr_args(loading, seg_hop, window)
+        self._mvdr_workspaces(F * segs)
         call("bf_mvdr_design_device", frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, seg_first, seg_hop, segs,
              None if d_window is None else d_window.data_ptr(), self.d_tau.data_ptr(), self.n_dirs, d_offsets.data_ptr(), self.B, self.offset_per_dir,
              self.T, int(self.bins[0]), int(self.bins[-1]), loading, self.d_snap.data_ptr(), self.d_cov.data_ptr(), self.d_chol.data_ptr(),
              self.d_gains.data_ptr(), self.d_taps.data_ptr(), self.d_status.data_ptr(), self.d_fallback.data_ptr())
         self.taps = None
         return self.d_status, self.d_fallback
+
+    def _mvdr_state(self):
+        """d_acc, d_mass and d_used, allocated once (empty) and kept: the addresses a captured graph reads stay valid."""
+        torch = _torch()
+        if self.d_acc is None:
+            self.d_acc = torch.zeros((int(self.bins.size), self.n, self.n, 2), dtype=torch.float64, device=self.device)
+            self.d_mass = torch.zeros((1,), dtype=torch.float64, device=self.device)
+            self.d_used = torch.zeros((2,), dtype=torch.int32, device=self.device)
+
+    def _learn_call(self, frames_ptr, m_total, F, seg_first, seg_hop, segs, window_ptr, weights_ptr, forget, d_offsets, loading, snap_ptr):
+        call("bf_mvdr_learn_device", frames_ptr, m_total, F, nat.iptr(self.mics), self.n, seg_first, seg_hop, segs, window_ptr, weights_ptr, forget,
+             self.d_tau.data_ptr(), self.n_dirs, d_offsets.data_ptr(), self.B, self.offset_per_dir, self.T, int(self.bins[0]), int(self.bins[-1]), loading,
+             self.d_acc.data_ptr(), self.d_mass.data_ptr(), self.d_used.data_ptr(), snap_ptr, self.d_cov.data_ptr(), self.d_chol.data_ptr(),
+             self.d_gains.data_ptr(), self.d_taps.data_ptr(), self.d_status.data_ptr(), self.d_fallback.data_ptr())
+        self.taps = None
+
+    def learn(self, d_frames, d_offsets, weights=None, forget=1.0, loading=0.1, seg_hop=16, window=None):
+        """`adapt` with a memory: the covariance is the listener's STATE (d_acc float64 [K, M, M, 2], d_mass float64 [1]), advanced by
+        d_frames and kept for the next call; enqueues bf_mvdr_learn_device -- mvdr_learn then design_mvdr_learned on the host -- which
+        writes self.d_taps in place.  weights: a float64 cuda tensor [F] or None (all 1); a frame is learned iff its weight is finite
+        and > 0, so (match[:, s] < 0).double() of SourceTracker.update learns from the frames in which slot s was not heard, with no
+        host round trip.  forget in (0, 1] multiplies the state once per LEARNED frame.  Segments, window and loading as `adapt`.
+        A captured graph that holds this call advances the state with every replay.
+        -> (d_status int32 [slots], d_fallback int32 [K], d_used int32 [2] = (frames learned, weights refused)), the listener's own tensors."""
+        torch = self._check_slots("learn", d_offsets)
+        frames = self._frames(d_frames)
+        F, m_total, N = frames.shape
+        loading, seg_hop, seg_first, segs, d_window = self._mvdr_args(loading, seg_hop, window)
+        forget = float(forget)
+        if not 0.0 < forget <= 1.0:
+            raise ValueError("forget must be in (0, 1], got %g" % forget)
+        if weights is not None and (weights.dtype != torch.float64 or not weights.is_cuda or tuple(weights.shape) != (F,) or not weights.is_contiguous()):
+            raise ValueError("weights must be a contiguous float64 cuda tensor [%d], got %s %s" % (F, weights.dtype, tuple(weights.shape)))
+        self._mvdr_workspaces(F * segs)
+        self._mvdr_state()
+        self._learn_call(frames.data_ptr(), m_total, F, seg_first, seg_hop, segs, None if d_window is None else d_window.data_ptr(),
+                         None if weights is None else weights.data_ptr(), forget, d_offsets, loading, self.d_snap.data_ptr())
+        return self.d_status, self.d_fallback, self.d_used
+
+    def reaim(self, d_offsets, loading=0.1):
+        """New taps for the slots of d_offsets from the state as it stands (bf_mvdr_learn_device with no frames): what to call when the
+        tracker moves a slot.  The state is not changed; an empty state gives the beams without nulls and fallback 1 at every bin.
+        -> (d_status int32 [slots], d_fallback int32 [K])."""
+        self._check_slots("reaim", d_offsets)
+        loading = self._mvdr_args(loading, 1, None)[0]
+        self._mvdr_workspaces(0)
+        self._mvdr_state()
+        self._learn_call(None, int(self.mics.max()) + 1, 0, 0, 1, 1, None, None, 1.0, d_offsets, loading, None)
+        return self.d_status, self.d_fallback
+
+    def forget_all(self):
+        """Empty the state: d_acc and d_mass are zeroed IN PLACE on the current stream."""
+        self._mvdr_state()
+        self.d_acc.zero_()
+        self.d_mass.zero_()
 
     def taps_host(self):
         """The taps the beams read now, fetched from the device (synchronises): float32 [B, M, T], also kept as `.taps`."""
