@@ -448,7 +448,9 @@ int bf_fuse_boxes_device(const float *d_power, int frames, int image_stride, int
  * (the reference drops the i < 0 edge samples; this mode does not).  For t >= H both equal miso_pad / miso_lerp bit for bit.
  * With d_prev == NULL and silence as history, lerp gives h * s[0] at t = p where the reference gives 0: that follows from the
  * definition, the sample before the stream is 0, not absent.
- * A map entry is image[d] = (sum_t (out_d[t] / n)^2) / N, summed in t order in float32 as bf_das_device sums it.
+ * A map entry is image[d] = (sum_t (out_d[t] / n)^2) / N, summed in t order in float32 with every square rounded before it is
+ * added.  (bf_das_device sums in the same order, and where N_SAMPLES % 4 != 0 fuses square and add for the last N_SAMPLES % 4
+ * samples, as the compiled reference does; this mode has no such reference and does not.)
  *
  * History: H = max_whole (pad) or max_whole + 1 (lerp), max_whole the largest whole-sample delay of the loaded table.  The calls
  * require H <= hop <= N_SAMPLES.  bf_stream_history returns H for BF_PAD / BF_LERP, -1 when that table is not loaded or for any

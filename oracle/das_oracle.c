@@ -32,13 +32,24 @@ void oracle_configure(int n_samples, int max_res_x, int max_res_y, int n_taps)
     g_nsamp = n_samples; g_resx = max_res_x; g_resy = max_res_y; g_taps = n_taps;
 }
 
-/* mean power of one steered block: pad_and_sum.c:122-131 (identical tail in all four variants) */
+/* mean power of one steered block: pad_and_sum.c:122-131 (identical tail in all four variants).
+ * Where the roundings fall under the reference's flags: gcc vectorises division and square by 8, then by 4, and adds the rounded
+ * squares in k order; the last N % 4 samples go through a scalar epilogue in which -ffp-contract=fast fuses square and add,
+ * sum = fma(out[k], out[k], sum).  The reference compiled at N = 202 and N = 450 does the same (measured image by image), so the
+ * HIP kernels fuse exactly those samples too.  Written out with contraction off and an explicit fmaf, so that the place of
+ * every rounding is stated here and not left to the vectoriser of the gcc at hand. */
+__attribute__((optimize("fp-contract=off")))
 static float block_power(float *out, int n_mics)
 {
     float sum = 0.0;
-    for (int k = 0; k < g_nsamp; k++) {
+    const int fused_from = g_nsamp - g_nsamp % 4;
+    for (int k = 0; k < fused_from; k++) {
         out[k] /= (float)n_mics;
-        sum += powf(out[k], 2);
+        sum += out[k] * out[k];
+    }
+    for (int k = fused_from; k < g_nsamp; k++) {
+        out[k] /= (float)n_mics;
+        sum = fmaf(out[k], out[k], sum);
     }
     sum /= (float)g_nsamp;
     return sum;

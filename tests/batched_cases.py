@@ -1,6 +1,7 @@
 """Cases for test_batched_plan_branches.py (GPU) and test_batched_cases_host.py (CPU): frame batches that reach every kernel family
 plan_das (csrc/das_plan.cpp) routes a bf_das_device call to, with more frame rows than active microphones, and a NumPy
-restatement of the routing rule so that a case's expected family is checked on the CPU before a GPU sees it.
+restatement of the routing rule so that a case's expected family is checked on the CPU before a GPU sees it.  hostile(name, algo)
+gives every case a second batch, of samples that N(0, 0.25) never draws.
 TEST INFRASTRUCTURE ONLY.
 
 Two table kinds:
@@ -106,6 +107,101 @@ def data(name):
     for a in (frames, mics, delays, taps):
         a.setflags(write=False)
     return Data(frames, mics, delays, taps)
+
+
+def _oracle_maps(name, algo, frames):
+    """Oracle maps float32 [len(frames), D] over the full direction range (oracle/libdas_oracle.so has to be built: the tests
+    that come here ask for the oracle_lib fixture first)."""
+    import das_oracle
+    c, d = BY_NAME[name], data(name)
+    orc = das_oracle.Oracle(c.N, c.X, c.Y, c.T)
+    orc.load(ALGOS[algo], table(name, algo))
+    return np.stack([orc.mimo_range(ALGOS[algo], f, d.mics, 0, c.X * c.Y) for f in frames])
+
+
+# ---- hostile samples -----------------------------------------------------------------------------------------------------
+
+KINDS = ("quiet", "one bad sample", "plain", "loud", "saturated", "sparse", "poison in the unread tail")
+QUIET, BAD, PLAIN_F, LOUD, SATURATED, SPARSE, POISON = range(7)
+HOSTILE_FRAMES = len(KINDS)
+QUIET_LOG2 = -138       # where the median of the quiet frame's map is put: 12 binades below the smallest normal float32, 11 above the smallest subnormal
+
+# frame BAD: (case, algo) whose tables let the one NaN reach every direction although the algorithm delays by whole samples --
+# hybrid at T = 16 reads T / 2 = 8 samples past the whole-sample split, and that table's whole-sample delays span 0 .. 8
+BAD_REACHES_ALL = {("strided_fir_16_taps", "hybrid")}
+# frame POISON: (case, algo) whose tables leave no sample unread -- every microphone has whole-sample delay 0 in some direction
+# (hybrid: a delay of at most T / 2).  The plain FIRs read everything in every case and are not listed.
+POISON_NOTHING = {("direct_m_total", "pad"), ("direct_m_total", "lerp"),
+                  ("strided_masked_tail", "hybrid"), ("strided_fir_16_taps", "hybrid"), ("fir_one_frame_odd_n", "hybrid")}
+
+Hostile = collections.namedtuple("Hostile", "frames clean want info")
+
+
+def _seven_plain(name):
+    c, d = BY_NAME[name], data(name)
+    rng = np.random.default_rng(zlib.crc32((name + "/hostile").encode()))
+    f = (rng.standard_normal((HOSTILE_FRAMES, c.M_total, c.N)) * 0.25).astype(np.float32)
+    f[QUIET] = d.frames[0]                                      # "the case's plain frame"
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def hostile(name, algo):
+    """Seven frames on the tables, microphone list and shapes of data(name) -- so the family of a batched call is the case's --
+    that a kernel can get wrong while every N(0, 0.25) frame passes.  The pair kernels make partners of (0, 1), (2, 3), (4, 5);
+    frame 6 runs alone.  In every frame the rows the microphone list does not name are NaN throughout.
+
+      0 quiet      frames[0] of data(name) * 2^e, e such that the median of the oracle map is 2^QUIET_LOG2: a subnormal map
+      1 one bad    a plain frame with one NaN, at row mics[m*], index N - 1 - q: m* the microphone whose whole-sample delay
+                   varies most over the directions, q the median of its delays -- about half of the directions read it.  The
+                   plain FIRs have no whole-sample rows (m* = 0, q = N / 2): every direction reads every sample
+      2 plain      N(0, 0.25)
+      3 loud       a plain frame * 2^e, e the largest at which the largest sum of squares the oracle forms (N times the map) stays
+                   below 2^128: all finite, in [2^126, 2^128), less than a factor 4 from overflow.  (The map itself cannot come
+                   nearer than 1/N to the largest float32: it is that sum divided by N.)
+      4 saturated  frame 3 * 4: the sums are 16 times as large, and a map's smallest is within 2.6 of its largest, so all overflow
+      5 sparse     a plain frame whose active rows i = 0, 3, 6 ... of the microphone list are +0.0 and i = 1, 4, 7 ... are -0.0
+      6 poison     a plain frame, active row mics[m] NaN from index N - min_d whole[d][m] (hybrid: + T / 2) on: what no direction
+                   reads.  The plain FIRs read everything: untouched
+
+    -> Hostile(frames float32 [7, M_total, N], clean = the frames before NaNs went in (inactive rows 0: NaN), want = the oracle maps
+    float32 [7, D] of `frames`, info = dict(e_quiet, e_loud, bad = (row, index), poisoned = number of samples)).  Read-only."""
+    c, d = BY_NAME[name], data(name)
+    D = c.X * c.Y
+    w = whole(name, algo)
+    f = _seven_plain(name)
+    inactive = np.setdiff1d(np.arange(c.M_total), d.mics)
+    f[:, inactive] = 0.0
+    base = _oracle_maps(name, algo, f[[QUIET, LOUD]])           # of the plain frames, before scaling
+    e_quiet = int(np.round((QUIET_LOG2 - np.log2(np.median(base[0].astype(np.float64)))) / 2))
+    e_loud = int(np.floor((128 - np.log2(base[1].astype(np.float64).max() * c.N)) / 2 - 1e-9))
+    f[QUIET] = np.ldexp(f[QUIET], e_quiet)
+    f[LOUD] = np.ldexp(f[LOUD], e_loud)
+    f[SATURATED] = f[LOUD] * np.float32(4)
+    active = d.mics
+    f[SPARSE, active[0::3]] = 0.0
+    f[SPARSE, active[1::3]] = -0.0
+    clean = f.copy()
+    clean[:, inactive] = np.nan
+    if w is None:
+        m_star, q = 0, c.N // 2
+    else:
+        m_star = int(np.argmax(w.max(axis=0) - w.min(axis=0)))
+        q = int(np.sort(w[:, m_star])[D // 2])
+    bad = (int(active[m_star]), c.N - 1 - q)
+    f[BAD, bad[0], bad[1]] = np.nan
+    poisoned = 0
+    if w is not None:
+        first = c.N - w.min(axis=0) + (c.T // 2 if algo == "hybrid" else 0)
+        for m in range(c.n):
+            if first[m] < c.N:
+                f[POISON, active[m], first[m]:] = np.nan
+                poisoned += c.N - int(first[m])
+    f[:, inactive] = np.nan
+    want = _oracle_maps(name, algo, f)
+    for a in (f, clean, want):
+        a.setflags(write=False)
+    return Hostile(f, clean, want, dict(e_quiet=e_quiet, e_loud=e_loud, bad=bad, poisoned=poisoned))
 
 
 def table(name, algo):

@@ -157,6 +157,11 @@ EDGE = [
     (16,   16, 1000,  3,  3,  8, 300.0),   # long rows with delays past the fixed prefix: run-time row stride (direction-outer for pad and lerp alike)
     (64,   64,  700, 17, 16,  8,  20.0),   # direction-outer with N not a multiple of 256 (third segment partial), 272 directions = five wave groups of 64
     (32,   32,  516, 10,  8,  8,  30.0),   # direction-outer with four segments of which two lie wholly beyond the block (k0 = 768 > N): every staging load stays inside the mic's row
+    # N % 4 != 0 at 272 directions: the compiled reference fuses square and add for the last N % 4 samples of the power sum, which moves
+    # about one map entry in a hundred by a float32 step -- a 2x2 grid cannot show whether a kernel does the same
+    (16,   13,  101, 17, 16,  8,  20.0),   # N % 4 = 1 in the strided kernel (two chunks of 64 samples)
+    (8,     5,  127, 17, 16,  8,  30.0),   # N % 4 = 3 in the strided kernel
+    (20,   16,  253, 17, 16,  8,  30.0),   # N % 4 = 1 in the shifted-copies kernel: direction-outer for pad / lerp, the FIR one-frame kernel
 ]
 # Which kernel pad / lerp take on these one-frame calls (bf_last_das_variant): independent random delays change the whole-sample
 # delay at nearly every direction step, so wherever the digest build counts re-reads (16 waves: 256 directions or more, or N > 256)
@@ -164,6 +169,11 @@ EDGE = [
 # for das_long_kernel (6) therefore run family 3; that kernel meets the oracle on smooth tables in test_batched_plan_branches.py.
 # Two grids of a few directions (2x2 at N = 258, 3x3 at N = 450) pad their runs of 8 with steps that never change, which keeps the
 # re-reads at or under half: they stay in the sweep (2).
+
+# (algo, case) of EDGE whose map is not the oracle's bit for bit, each with its cause, the number of differing entries and the largest
+# distance in float32 steps as measured.  Empty: all 110 are held to bits.  An entry has to bring its own bound with it: the kernel's
+# distance from a float64 evaluation of the same sum at most twice the oracle's own, both measured and written beside the entry.
+NOT_BIT_IDENTICAL = {}
 
 
 @pytest.mark.parametrize("case", EDGE, ids=lambda c: "M%d_n%d_N%d_%dx%d_T%d" % c[:6])
@@ -190,6 +200,11 @@ def test_edge_shapes_match_oracle(nat, oracle_lib, algo, case):
         print("EDGE %s %s: family %d, rule %d" % (algo, case, family, rule))
         assert family == rule
         assert family in (0, 2, 3)              # one frame of random delays: never the pair kernels, never das_long_kernel
+    # the oracle is the definition: same microphone order, same operation order, same k-ordered power sum -- the same bits.  (REL_TOL
+    # cannot see an order: tests/test_batched_cases_host.py::test_a_wrong_order_hides_under_the_tolerance)
+    assert (algo, case) not in NOT_BIT_IDENTICAL, "no exception is implemented: see the comment at NOT_BIT_IDENTICAL"
+    why = util.bits_differ(got, want)
+    assert not why, "%s %s, family %d: %s" % (algo, case, family, why)
 
 
 @pytest.mark.parametrize("algo", ["pad", "lerp", "hybrid"])

@@ -65,6 +65,25 @@ def max_rel(got, want):
     return float(np.max(np.abs(got - want) / denom))
 
 
+def bits_differ(got, want, nan_is_nan=False):
+    """An empty string where float32 `got` equals `want` bit for bit; otherwise what to say: the first differing flat direction, both values
+    as hex bits, the number of differing entries and the largest distance in float32 steps.  nan_is_nan: an entry that is NaN on
+    both sides counts as equal whatever its payload (a NaN on one side only never does)."""
+    got, want = np.ascontiguousarray(got, dtype=np.float32).ravel(), np.ascontiguousarray(want, dtype=np.float32).ravel()
+    assert got.shape == want.shape, (got.shape, want.shape)
+    g, w = got.view(np.uint32), want.view(np.uint32)
+    bad = g != w
+    if nan_is_nan:
+        bad &= ~(np.isnan(got) & np.isnan(want))
+    if not bad.any():
+        return ""
+    # distance in steps: the bit patterns mapped to a line on which neighbouring floats are neighbouring integers
+    line = lambda u: np.where(u >> 31 != 0, -(u & 0x7FFFFFFF).astype(np.int64), (u & 0x7FFFFFFF).astype(np.int64))
+    d = int(np.flatnonzero(bad)[0])
+    return "first differing flat direction %d: got 0x%08x (%r), want 0x%08x (%r); %d of %d entries differ, by at most %d float32 steps" % (
+        d, g[d], float(got[d]), w[d], float(want[d]), int(bad.sum()), bad.size, int(np.abs(line(g[bad]) - line(w[bad])).max()))
+
+
 def configure(name, **extra):
     """Switch the product package (interface.config + native library) to a size of oracle/configs.py."""
     from interface import config

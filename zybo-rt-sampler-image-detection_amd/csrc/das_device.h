@@ -90,7 +90,13 @@ __device__ __forceinline__ void stage_chunk(float* lds, const KArgs& a, const in
 // at N = 1024), which is more than the 1e-5 parity bar.  So the squares are summed in k order here too:
 // every wave parks the squares of `pbw` finished directions as rows of a private LDS scratch, then lanes
 // 0..pbw-1 each walk one row front to back (ds_read_b128, four ordered adds per read).
-template <int NC>
+//
+// REF_TAIL: the last N % 4 samples as the compiled reference sums them.  gcc vectorises the loop above by 8, then by 4, and runs
+// the rest through a scalar epilogue in which its contraction default fuses square and add: sum = fma(out[k], out[k], sum) for
+// k >= N - N % 4 (measured on the reference compiled at N = 202 and N = 450; oracle/das_oracle.c states the same rule).  Those
+// samples are parked unsquared and the summing lane fuses them.  The reference's own sizes are multiples of 8: nothing is fused there.
+// The stream maps are defined with every square rounded (include/beamformer_hip.h): REF_TAIL = false.
+template <int NC, bool REF_TAIL = false>
 __device__ __forceinline__ void park_squares(const float (&acc)[NC], float* scratch_row, const KArgs& a, int d, int lane)
 {
     float sq[NC];
@@ -98,7 +104,7 @@ __device__ __forceinline__ void park_squares(const float (&acc)[NC], float* scra
     for (int c = 0; c < NC; ++c) {
         // out[k] /= (float)n: for a power-of-two n the reciprocal multiply is exact; otherwise a true division
         const float o = a.n_is_pow2 ? acc[c] * a.inv_n : acc[c] / (float)a.n_mics;
-        sq[c] = o * o;
+        sq[c] = (REF_TAIL && lane + c * kWave >= (a.n_samples & ~3)) ? o : o * o;
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) scratch_row[lane + c * kWave] = sq[c];
@@ -107,6 +113,7 @@ __device__ __forceinline__ void park_squares(const float (&acc)[NC], float* scra
 
 // Rows are 16-byte aligned and 4 (mod 64) dwords apart, so up to 16 lanes can each stream their own row with
 // ds_read_b128 without sharing a bank; the additions stay strictly in k order.
+template <bool REF_TAIL = false>
 __device__ __forceinline__ void flush_powers(const float* scratch, int filled, float* __restrict__ img, const KArgs& a, int lane)
 {
     if (lane < filled) {
@@ -120,7 +127,7 @@ __device__ __forceinline__ void flush_powers(const float* scratch, int filled, f
             const float4 v = row4[k >> 2];
             sum += v.x; sum += v.y; sum += v.z; sum += v.w;
         }
-        for (; k < n; ++k) sum += row[k];
+        for (; k < n; ++k) sum = REF_TAIL ? __fmaf_rn(row[k], row[k], sum) : sum + row[k];   // k >= n - n % 4 (REF_TAIL: parked unsquared)
         const int d = __float_as_int(row[a.srow - 4]);
         img[d - a.image_origin] = sum / (float)n;
     }

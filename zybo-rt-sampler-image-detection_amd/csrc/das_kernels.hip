@@ -869,7 +869,9 @@ __global__ void __launch_bounds__(W * 64, 4) das_copies_kernel(BF_TABLE_PARAMS, 
             if (wave >= w0 && wave < w0 + pw_waves) {
                 // mean over the mics: a power-of-two count multiplies (exact), anything else divides like the reference;
                 // two separate code paths so that the division sequence is never executed speculatively
-                auto park = [&](auto mul_c) {
+                // N % 4 != 0 (tail_c): the quad that holds the last N % 4 samples is parked unsquared, the summing lane below fuses
+                // square and add for them as the compiled reference's scalar epilogue does (REF_TAIL, das_device.h)
+                auto park = [&](auto mul_c, auto tail_c) {
 #pragma unroll
                     for (int j = 0; j < DW; ++j) {
                         float* row = lds + ((wave - w0) * DW + j) * kPark;
@@ -884,11 +886,19 @@ __global__ void __launch_bounds__(W * 64, 4) das_copies_kernel(BF_TABLE_PARAMS, 
                                 asm volatile("" : "+v"(fm));   // not speculatable: keeps this path behind its branch
                                 o0 = a0.x / fm; o1 = a0.y / fm; o2 = a1.x / fm; o3 = a1.y / fm;
                             }
-                            reinterpret_cast<float4*>(row + 256 * sg)[lane] = make_float4(o0 * o0, o1 * o1, o2 * o2, o3 * o3);
+                            float4 q = make_float4(o0 * o0, o1 * o1, o2 * o2, o3 * o3);
+                            if constexpr (decltype(tail_c)::value) {
+                                if (256 * sg + 4 * lane == (N & ~3)) q = make_float4(o0, o1, o2, o3);
+                            }
+                            reinterpret_cast<float4*>(row + 256 * sg)[lane] = q;
                         }
                     }
                 };
-                if (__builtin_expect(a.n_is_pow2, 1)) park(std::true_type{}); else park(std::false_type{});
+                if (__builtin_expect((N & 3) == 0, 1)) {
+                    if (__builtin_expect(a.n_is_pow2, 1)) park(std::true_type{}, std::false_type{}); else park(std::false_type{}, std::false_type{});
+                } else {
+                    if (a.n_is_pow2) park(std::true_type{}, std::true_type{}); else park(std::false_type{}, std::true_type{});
+                }
             }
             __syncthreads();
             const int g = wave * kWave + lane;            // parked row of this lane
@@ -905,7 +915,8 @@ __global__ void __launch_bounds__(W * 64, 4) das_copies_kernel(BF_TABLE_PARAMS, 
 #pragma unroll
                     for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
                 }
-                for (; k < N; ++k) sum += row[k];
+                for (; k < (N & ~3); ++k) sum += row[k];
+                for (; k < N; ++k) sum = __fmaf_rn(row[k], row[k], sum);   // the last N % 4 samples: parked unsquared
                 img[d - a.image_origin] = sum / (float)N;
             }
         }

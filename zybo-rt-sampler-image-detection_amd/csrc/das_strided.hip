@@ -266,12 +266,12 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
         for (int j = 0; j < DPW; ++j) {
             const int d = g0 + j * nwaves + wave;
             if (d < tile_end) {
-                park_squares<NC>(acc[j], scratch + filled * a.srow, a, d, lane);
-                if (++filled == a.pbw) { flush_powers(scratch, filled, img, a, lane); filled = 0; }
+                park_squares<NC, true>(acc[j], scratch + filled * a.srow, a, d, lane);
+                if (++filled == a.pbw) { flush_powers<true>(scratch, filled, img, a, lane); filled = 0; }
             }
         }
     }
-    if (filled > 0) flush_powers(scratch, filled, img, a, lane);
+    if (filled > 0) flush_powers<true>(scratch, filled, img, a, lane);
 }
 
 // Steered beams, raw out[N] (miso_pad / miso_lerp / miso_convolve_*, pad_and_sum.c:54-70 ...).  Workgroup id = frame * groups +
