@@ -59,6 +59,9 @@ CASES = [
     # ---- 5 / 8 and 7: the pair kernels with out-of-order rows
     _c("pair_reversed_rows", {"pad": 5, "lerp": 8}, PLAIN, 20, 16, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),
     _c("fir_pair_reversed_rows", 7, FIRS, 40, 32, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),
+    # the same two with a microphone count that is no power of two: the mean over the microphones divides (csrc/das_device.h, mic_mean)
+    _c("pair_divided_mean", {"pad": 5, "lerp": 8}, PLAIN, 56, 48, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),
+    _c("fir_pair_divided_mean", 7, FIRS, 56, 48, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),
     # ---- two frames: the smallest batch the pair kernels take, no workgroup row with a single frame
     _c("pair_two_frames", {"pad": 5, "lerp": 8}, PLAIN, 20, 16, 256, 17, 16, 8, 30.0, "smooth", F=2),
 ]

@@ -59,7 +59,7 @@ def _das(nat, c, algo, d_sig, mics, lo, hi, stride=None, spare_rows=0):
 
 
 # (case, algo) of BC.PARAMS whose maps are not the oracle's bit for bit, each with its cause, the number of differing entries and the
-# largest distance in float32 steps as measured.  Empty: all 48 are held to bits, on plain frames and on the hostile ones.  An entry
+# largest distance in float32 steps as measured.  Empty: all 53 are held to bits, on plain frames and on the hostile ones.  An entry
 # has to bring its own bound with it: the kernel's distance from a float64 evaluation of the same sum at most twice the oracle's own,
 # both measured and written beside the entry.
 NOT_BIT_IDENTICAL = {}

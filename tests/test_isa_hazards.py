@@ -121,6 +121,19 @@ def test_comparator_finds_what_it_should(iseq, change, n_diff, needle):
     assert needle is None or needle in diffs[0], diffs
 
 
+def test_renumbered_comparison_forgives_register_numbers_and_nothing_else(iseq):
+    base = dict(n=0, stmt=17, operand="v2", vgprs=24, second=FAKE_SECOND, second_md=FAKE_SECOND_MD)
+    old = FAKE_UNIT % base
+    assert iseq.compare(old, FAKE_UNIT % dict(base, operand="v3"))[0]                          # literal: a difference
+    assert not iseq.compare(old, FAKE_UNIT % dict(base, operand="v3"), renumbered=True)[0]     # another number of the same file
+    for change, needle in ((dict(operand="s3"), "'v_add_f32_e32 v, v, v' -> 'v_add_f32_e32 v, s, v'"),      # another register file
+                           (dict(operand="v[2:3]"), "-> 'v_add_f32_e32 v, v2, v'"),                        # a tuple: another width
+                           (dict(operand="1.0"), "-> 'v_add_f32_e32 v, 1.0, v'"),                          # an immediate
+                           (dict(vgprs=25), ".vgpr_count 24 -> 25")):                                      # the metadata, as ever
+        diffs, _ = iseq.compare(old, FAKE_UNIT % dict(base, **change), renumbered=True)
+        assert len(diffs) == 1 and needle in diffs[0], diffs
+
+
 def test_no_register_with_a_read_in_flight_is_touched(chk, asm):
     kernels, bad = chk.scan(asm)
     assert kernels >= 43

@@ -83,6 +83,8 @@ __device__ __forceinline__ void stage_chunk(float* lds, const KArgs& a, const in
 }
 
 // ---- mean power, in the reference's summation order ------------------------------------------------------
+// (the one statement of the rule, for both layouts: park_squares / flush_powers are the strided kernels' form of it, mic_mean /
+// row_mean_power below them the shifted-copies kernels')
 // The reference finishes a direction with (pad_and_sum.c:122-131)
 //     for k: out[k] /= n; sum += out[k]^2          (gcc: vdivps, vmulps, then one vaddss per k, in k order)
 //     image = sum / N
@@ -131,6 +133,53 @@ __device__ __forceinline__ void flush_powers(const float* scratch, int filled, f
         const int d = __float_as_int(row[a.srow - 4]);
         img[d - a.image_origin] = sum / (float)n;
     }
+}
+
+// The same rule for the shifted-copies kernels (das_kernels.hip, das_pair.hip), whose lanes hold four samples of a direction each and
+// whose rows alias the staging buffer: a kernel keeps its row layout, its barriers and its rounds, and takes the arithmetic here.
+//
+// out[k] /= (float)n for a lane's four sums.  MUL (the count is a power of two): the reciprocal multiply, exact.  Otherwise a true
+// division like the reference's, by a divisor passed through an empty asm: that is not speculatable, so the division sequence stays
+// behind the caller's branch on a.n_is_pow2.
+template <bool MUL>
+__device__ __forceinline__ void mic_mean(float x0, float x1, float x2, float x3, int n_mics, float inv_n, float& o0, float& o1, float& o2, float& o3)
+{
+    if constexpr (MUL) {
+        o0 = x0 * inv_n; o1 = x1 * inv_n; o2 = x2 * inv_n; o3 = x3 * inv_n;
+    } else {
+        float fm = (float)n_mics;
+        asm volatile("" : "+v"(fm));
+        o0 = x0 / fm; o1 = x1 / fm; o2 = x2 / fm; o3 = x3 / fm;
+    }
+}
+
+__device__ __forceinline__ float add_in_order(const float4* row4, float sum)   // 32 squares: eight reads in flight, then 32 ordered adds
+{
+    float4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = row4[u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
+    return sum;
+}
+
+// image = sum / N of one parked row (squares in k order, 16-byte aligned), walked by one lane.  ONE_TRIP: the 32-sample trip is not
+// unrolled further, for the kernels that have no registers for two trips' reads (each says why where it asks for it).  No REF_TAIL
+// form: the kernels that come here take N % 4 == 0 only (plan_das); das_copies_kernel, which takes any N, writes its sum out.
+template <bool ONE_TRIP>
+__device__ __forceinline__ float row_mean_power(const float* row, int n)
+{
+    const float4* row4 = reinterpret_cast<const float4*>(row);
+    float sum = 0.0f;
+    int k = 0;
+    if constexpr (ONE_TRIP) {
+#pragma unroll 1
+        for (; k + 32 <= n; k += 32) sum = add_in_order(row4 + (k >> 2), sum);
+    } else {
+        for (; k + 32 <= n; k += 32) sum = add_in_order(row4 + (k >> 2), sum);
+    }
+    for (; k < n; ++k) sum += row[k];
+    return sum / (float)n;
 }
 
 namespace copies {

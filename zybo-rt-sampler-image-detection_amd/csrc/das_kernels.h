@@ -112,7 +112,7 @@ hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const flo
 hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
                                long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream);
 
-// bf_remove_sources_device (pad and lerp): d_residual = d_signals - c * (adjoint of the delay operator)(beams), rows of the frames
+// bf_remove_sources_device (remove_sources.hip; pad and lerp): d_residual = d_signals - c * (adjoint of the delay operator)(beams), rows of the frames
 // named by d_row_slot int32 [m_total] (slot m of the adaptive array, or -1: the row is copied).  d_offsets / d_status / entries as
 // launch_miso_batch; d_beams float32 [frames][beams][beam_stride], rows of rejected offsets never read.  d_residual may equal d_signals.
 constexpr int kRemoveMaxBeams = 64;

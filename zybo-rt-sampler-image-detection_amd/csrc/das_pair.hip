@@ -226,13 +226,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
                     float* row = lds + (wave * DW + j) * kPark;
                     const f32x2 a0 = acc[j][f][0], a1 = acc[j][f][1];
                     float o0, o1, o2, o3;
-                    if constexpr (decltype(mul_c)::value) {
-                        o0 = a0.x * a.inv_n; o1 = a0.y * a.inv_n; o2 = a1.x * a.inv_n; o3 = a1.y * a.inv_n;
-                    } else {
-                        float fm = (float)M;
-                        asm volatile("" : "+v"(fm));   // not speculatable: keeps this path behind its branch
-                        o0 = a0.x / fm; o1 = a0.y / fm; o2 = a1.x / fm; o3 = a1.y / fm;
-                    }
+                    mic_mean<decltype(mul_c)::value>(a0.x, a0.y, a1.x, a1.y, M, a.inv_n, o0, o1, o2, o3);
                     reinterpret_cast<float4*>(row)[lane] = make_float4(o0 * o0, o1 * o1, o2 * o2, o3 * o3);
                 }
             };
@@ -245,19 +239,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
             if (g < kGroup && d < tile_end && (f == 0 || two)) {
                 // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
                 const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
-                const float* row = lds + g * kPark;
-                const float4* row4 = reinterpret_cast<const float4*>(row);
-                float sum = 0.0f;
-                int k = 0;
-                for (; k + 32 <= N; k += 32) {
-                    float4 v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = row4[(k >> 2) + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
-                }
-                for (; k < N; ++k) sum += row[k];
-                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
+                (f == 0 ? img0 : img1)[dd - a.image_origin] = row_mean_power<false>(lds + g * kPark, N);
             }
         }
     }
@@ -542,13 +524,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
                     const float x0 = f == 0 ? acc[j][0].x : acc[j][0].y, x1 = f == 0 ? acc[j][1].x : acc[j][1].y;
                     const float x2 = f == 0 ? acc[j][2].x : acc[j][2].y, x3 = f == 0 ? acc[j][3].x : acc[j][3].y;
                     float o0, o1, o2, o3;
-                    if constexpr (decltype(mul_c)::value) {
-                        o0 = x0 * a.inv_n; o1 = x1 * a.inv_n; o2 = x2 * a.inv_n; o3 = x3 * a.inv_n;
-                    } else {
-                        float fm = (float)M;
-                        asm volatile("" : "+v"(fm));   // not speculatable: keeps this path behind its branch
-                        o0 = x0 / fm; o1 = x1 / fm; o2 = x2 / fm; o3 = x3 / fm;
-                    }
+                    mic_mean<decltype(mul_c)::value>(x0, x1, x2, x3, M, a.inv_n, o0, o1, o2, o3);
                     reinterpret_cast<float2*>(row)[lane] = make_float2(o0 * o0, o1 * o1);             // samples 2l, 2l+1
                     reinterpret_cast<float2*>(row + 128)[lane] = make_float2(o2 * o2, o3 * o3);       // samples 128+2l, 128+2l+1
                 }
@@ -563,20 +539,8 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
             if (g < kGroup && d < tile_end && (f == 0 || two)) {
                 // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
                 const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
-                const float* row = lds + g * kPark;
-                const float4* row4 = reinterpret_cast<const float4*>(row);
-                float sum = 0.0f;
-                int k = 0;
-#pragma unroll 1                                           // (eight reads in flight, as ever: two trips' worth spill the staged quads)
-                for (; k + 32 <= N; k += 32) {
-                    float4 v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = row4[(k >> 2) + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
-                }
-                for (; k < N; ++k) sum += row[k];
-                (f == 0 ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
+                // (ONE_TRIP: eight reads in flight, as ever: two trips' worth spill the staged quads)
+                (f == 0 ? img0 : img1)[dd - a.image_origin] = row_mean_power<true>(lds + g * kPark, N);
             }
         }
     }
