@@ -429,6 +429,114 @@ int bf_fuse_boxes_device(const float *d_power, int frames, int image_stride, int
                          int *d_peak_offsets, float *d_peak_power, int *d_center_offsets, int *d_rects,
                          int *d_src_box, int *d_counts, void *stream);
 
+/* ---- track detector boxes across frames: bf_nms_device's [frames][max_boxes][6] rows -> [frames][slots][6] rows with identity over time ----
+ * bf_nms_device orders a frame's rows by score, so row b of one frame and row b of the next are not the same object, and a one-frame
+ * false alarm takes a row.  The reference's running detector (image-detection/src/yolo_smooth_tracking.py,
+ * process_video_track_boxes_only, :275-347) therefore hands every frame's detections to SORT (Bewley, Ge, Ott, Ramos, Upcroft,
+ * "Simple online and realtime tracking", ICIP 2016): a constant-velocity Kalman filter per box, association by the assignment of
+ * maximal total IoU, and max_age / min_hits birth and death; the tracked box is what PC/sensorfusion/decider.py steers the beam at.
+ * This call is that tracker on the device, written from the paper and from the behaviour of the reference's call, one frame after
+ * another on a carried state.  It is to boxes what bf_track_sources_device is to map sources.
+ *
+ * d_boxes   : HIP device pointer, float32 [frames][max_boxes][6] = x1, y1, x2, y2, score, cls: what bf_nms_device writes.
+ * d_n_boxes : HIP device pointer, int32 [frames], or NULL.  n = clamp(d_n_boxes[f], 0, max_boxes); NULL: n = max_boxes.
+ * conf      : row j is a DETECTION iff j < n, its four coordinates are finite, x2 > x1, y2 > y1, and its score is finite and
+ *             > conf (strictly: the reference skips confl < conf, :304; its conf is 0.1).  Every other row below n is ignored and
+ *             counted in d_counts[f][3].  The detections of a frame keep their row order.
+ * slots     : tracks held at once, at most BF_BOX_TRACK_MAX_SLOTS.  iou_threshold, max_age, min_hits: SORT's (0.3, 1, 3).
+ * d_state   : HIP device pointer, bf_box_track_state_words(slots) = 4 + 20 * slots 32-bit words, read and written: the tracks
+ *             carried from one call to the next.  All zero is a fresh stream (hipMemset it once).  Integer fields int32, the rest
+ *             float32 by their bits:
+ *                 word 0                 next_id (ids start at 1 and are never reused; it wraps like an int32)
+ *                 word 1                 frame_count
+ *                 words 2..3             0
+ *                 words 4 + 20*s ..      slot s: id (0 = free), time_since_update, hits, hit_streak,
+ *                                        u, v, s, r, du, dv, ds       centre, area, aspect w/h, and the rates of the first three
+ *                                        a00, a01, a11                the covariance of (u, du), which is also that of (v, dv)
+ *                                        b00, b01, b11                the covariance of (s, ds)
+ *                                        c                            the variance of r
+ *                                        0, 0
+ *             A free slot is written as twenty zeros.
+ * d_tracks  : HIP device pointer, float32 [frames][slots][6]: a REPORTED slot (step 6) holds its state box, then the score and cls
+ *             of the detection it took in this frame; every other slot six zeros.  The layout is d_boxes' own, so
+ *             bf_fuse_boxes_device reads it with d_box_counts = NULL: a zero score is not a box for any conf > 0.
+ * d_ids     : int32 [frames][slots], or NULL: the slot's id, 0 for a free slot; live tracks that are not reported show theirs.
+ * d_match   : int32 [frames][slots], or NULL: the row of d_boxes the slot took in this frame or was born from; otherwise -1.
+ * d_live    : float32 [frames][slots][4], or NULL: the state box of every live slot, coasting ones included; zeros for a free slot.
+ *             This is what keeps a beam on an object through a missed detection.
+ * d_counts  : int32 [frames][4], or NULL: tracks born, tracks ended, detections dropped because no slot was free, rows ignored.
+ * Every entry of every given output is written by every call.
+ *
+ * The filter.  SORT's is a 7-state (u, v, s, r, du, dv, ds) / 4-measurement (u, v, s, r) Kalman filter with F = I plus the
+ * couplings (u, du), (v, dv), (s, ds), H = the first four states, R = diag(1, 1, 10, 10), Q = diag(1, 1, 1, 1, .01, .01, .0001),
+ * P0 = diag(10, 10, 10, 10, 1e4, 1e4, 1e4) and the Joseph-form covariance update.  None of these couples (u, du), (v, dv), (s, ds)
+ * and r with one another, so P stays block diagonal for ever: one 2x2 block A for (u, du) and (v, dv) alike (q = (1, .01), r = 1),
+ * one 2x2 block B for (s, ds) (q = (1, 1e-4), r = 10) and one scalar c for r (q = 1, r = 10) -- the reduction
+ * bf_track_sources_device makes for kf.hpp.  For a block p = (p00, p01, p11) with process noise (q0, q1) and measurement noise r:
+ *     PREDICT(p):  a = p00 + p01;  b = p01 + p11;  p00 = (a + b) + q0;  p01 = b;  p11 = p11 + q1
+ *     UPDATE(p):   S = p00 + r;  k0 = p00 / S;  k1 = p01 / S;  m = 1 - k0;  then, from the old p00, p01, p11:
+ *                  p00 = (m * m) * p00 + (k0 * k0) * r
+ *                  t = p01 - k1 * p00;                    p01 = m * t + (k0 * k1) * r
+ *                  kk = k1 * k1;                          p11 = ((p11 - (2 * k1) * p01) + kk * p00) + kk * r
+ *                  a state pair (x, dx) measured as z:    e = z - x;  x = x + k0 * e;  dx = dx + k1 * e
+ *     the scalar:  predict c = c + 1;   update S = c + 10;  k = c / S;  e = z - r;  r = r + k * e;  m = 1 - k;
+ *                  c = (m * m) * c + (k * k) * 10
+ *     BOX(state):  w = sqrtf(s * r);  h = s / w;  hw = 0.5f * w;  hh = 0.5f * h;  (u - hw, v - hh, u + hw, v + hh)
+ *     Z(row):      w = x2 - x1;  h = y2 - y1;  z = (x1 + 0.5f * w, y1 + 0.5f * h, w * h, w / h)
+ *
+ * Definition.  Frames in order f = 0 .. frames-1.  float32, every operation rounded once and none contracted, plain division and a
+ * correctly rounded sqrtf; max(a, b) = a > b ? a : b and min(a, b) = a < b ? a : b.  A slot is live iff its id != 0.  Per frame:
+ *   1. frame_count += 1.  Every live slot: if ds + s <= 0 then ds = 0;  u = u + du;  v = v + dv;  s = s + ds;  PREDICT(A), PREDICT(B),
+ *      c = c + 1;  if time_since_update > 0 then hit_streak = 0;  time_since_update += 1.  Its box is BOX(state); a slot whose box has
+ *      a coordinate that is not finite becomes free (counted as ended) and is available to step 5 of this frame.
+ *   2. Gain of (live slot with box t, detection d), in the order of SORT's iou_batch:
+ *          xx1 = max(d.x1, t.x1);  yy1 = max(d.y1, t.y1);  xx2 = min(d.x2, t.x2);  yy2 = min(d.y2, t.y2)
+ *          w = max(0, xx2 - xx1);  h = max(0, yy2 - yy1);  wh = w * h
+ *          o = wh / (((d.x2 - d.x1) * (d.y2 - d.y1) + (t.x2 - t.x1) * (t.y2 - t.y1)) - wh);   g = o > 0 ? o : 0    (a NaN counts as 0)
+ *   3. Associate.  With no live slot or no detection nothing is matched.  If no slot and no detection has more than one pair with
+ *      g > iou_threshold, the matches are exactly the pairs with g > iou_threshold.  Otherwise the ASSIGNMENT below gives every live
+ *      slot a column, and the slot is matched to it iff the column is a detection and not g < iou_threshold.  (A pair with
+ *      g == iou_threshold is therefore kept by the assignment and not by the shortcut: the reference's own asymmetry.)
+ *      ASSIGNMENT.  Rows i = 0 .. R-1: the live slots in slot order.  Columns j = 0 .. C-1, C = D + R: the D detections in row
+ *      order, then one dummy per row.  cost(i, j) = -(double)g for a detection, 0.0 for a dummy.  float64 potentials U[i], V[j],
+ *      all 0.0; row_of[j] = none.  For i = 0 .. R-1 in order:
+ *          minv[j] = +inf, used[j] = false, way[j] = none for every j;  i0 = i;  j0 = none;  repeat:
+ *              for every j not used:  cur = (cost(i0, j) - U[i0]) - V[j];  if cur < minv[j] then minv[j] = cur, way[j] = j0
+ *              j1 = the lowest j not used whose minv[j] equals the minimum over the j not used;  delta = minv[j1]
+ *              U[i] = U[i] + delta;  for every used j:  U[row_of[j]] = U[row_of[j]] + delta,  V[j] = V[j] - delta;
+ *              for every j not used:  minv[j] = minv[j] - delta
+ *              used[j1] = true;  j0 = j1;  stop if row_of[j0] is none, else i0 = row_of[j0]
+ *          then walk back:  repeat { jp = way[j0];  row_of[j0] = (jp is none ? i : row_of[jp]);  j0 = jp } until j0 is none.
+ *      Row i's column is the j with row_of[j] = i.  This is the shortest-augmenting-path method; it maximises the total gain, and
+ *      the order above gives ties one answer.
+ *   4. Every matched slot, from its predicted state and its detection's Z:  time_since_update = 0;  hits += 1;  hit_streak += 1;
+ *      UPDATE(A) with (u, du) then (v, dv);  UPDATE(B) with (s, ds);  the scalar update of r.
+ *   5. Birth.  Every detection no slot took, in row order, takes the lowest free slot:  next_id += 1;  id = next_id;
+ *      time_since_update = hits = hit_streak = 0 (a track's first hit is its first update);  (u, v, s, r) = Z;  du = dv = ds = 0;
+ *      A = B = (10, 0, 1e4);  c = 10.  With no free slot the detection is dropped and counted.
+ *   6. Report, then retire.  The frame's outputs are written from the state as it now stands.  A live slot is REPORTED iff
+ *      time_since_update < 1 and (hit_streak >= min_hits or frame_count <= min_hits); its box and d_live's are BOX(state).  Then a
+ *      slot with time_since_update > max_age becomes free (counted as ended); it is free from the next frame on.
+ * Three deliberate differences from the reference's call: (a) it deletes a track whose predicted box has a NaN but mis-indexes on an
+ * infinity (sort.py masks rows with any invalid entry, yet lists only NaN rows for deletion); here either frees the slot.  (b) It
+ * re-finds a track's confidence by scanning the detections for one with IoU > 0.5 (:319-324); d_tracks passes on the matched
+ * detection's.  (c) When NO pair exceeds the threshold it still runs the assignment and can keep a pair with g == iou_threshold
+ * exactly; here that frame takes the shortcut and matches nothing.
+ * One call over F frames equals two calls over F1 + F2 frames on the same d_state, bit for bit; a graph replay advances the state
+ * like any other call.  The result does not depend on the workgroup size the launch uses.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: one launch of one workgroup, no allocation, no synchronisation, no
+ *             workspace; graph-capturable from the first call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_boxes, d_state or d_tracks null; frames < 1;
+ * max_boxes < 1 or > BF_BOX_TRACK_MAX_BOXES; slots < 1 or > BF_BOX_TRACK_MAX_SLOTS; conf not finite; iou_threshold not finite or
+ * outside [0, 1]; max_age < 0; min_hits < 0; no GPU.  All arguments are checked before device bring-up.
+ * bf_box_track_state_words(slots) returns 4 + 20 * slots, or -1 for slots outside [1, BF_BOX_TRACK_MAX_SLOTS] (it records no error). */
+#define BF_BOX_TRACK_MAX_SLOTS 64
+#define BF_BOX_TRACK_MAX_BOXES 1024
+int bf_box_track_state_words(int slots);
+int bf_track_boxes_device(const float *d_boxes, const int *d_n_boxes, int frames, int max_boxes,
+                          float conf, int slots, float iou_threshold, int max_age, int min_hits,
+                          void *d_state, float *d_tracks, int *d_ids, int *d_match, float *d_live, int *d_counts, void *stream);
+
 /* ---- continuous-stream mode of the device path (BF_PAD, BF_LERP): delays read the previous window ----
  * Every other entry point treats a window as if the world began at its first sample: a microphone delayed by p samples gives
  * nothing to the first p outputs (out[p + i] += s[i], zero prefix), as the reference does.  That is the first item of the reference

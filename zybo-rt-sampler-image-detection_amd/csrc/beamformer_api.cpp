@@ -1451,6 +1451,30 @@ int bf_fuse_boxes_device(const float* d_power, int frames, int image_stride, int
                                         d_src_offsets, n_src, d_peak_offsets, d_peak_power, d_center_offsets, d_rects, d_src_box, d_counts, as_stream(stream)));
 }
 
+int bf_box_track_state_words(int slots)
+{
+    return slots >= 1 && slots <= BF_BOX_TRACK_MAX_SLOTS ? 4 + 20 * slots : -1;
+}
+
+int bf_track_boxes_device(const float* d_boxes, const int* d_n_boxes, int frames, int max_boxes, float conf, int slots, float iou_threshold, int max_age,
+                          int min_hits, void* d_state, float* d_tracks, int* d_ids, int* d_match, float* d_live, int* d_counts, void* stream)
+{
+    static const char* who = "bf_track_boxes_device";
+    static_assert(BF_BOX_TRACK_MAX_SLOTS == bf::kBoxTrackMaxSlots && BF_BOX_TRACK_MAX_BOXES == bf::kBoxTrackMaxBoxes, "the header's limits are the kernel's");
+    Entered in;
+    if (!need_ptrs(who, {{d_boxes, "d_boxes"}, {d_state, "d_state"}, {d_tracks, "d_tracks"}})) return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "max_boxes", max_boxes, 1) || !need_max(who, "max_boxes", max_boxes, BF_BOX_TRACK_MAX_BOXES)) return -1;
+    if (!need_min(who, "slots", slots, 1) || !need_max(who, "slots", slots, BF_BOX_TRACK_MAX_SLOTS) || !need_finite(who, "conf", conf)) return -1;
+    if (!std::isfinite(iou_threshold) || iou_threshold < 0.0f || iou_threshold > 1.0f) {
+        set_error("%s: iou_threshold = %g is not in [0, 1]", who, (double)iou_threshold);
+        return -1;
+    }
+    if (!need_min(who, "max_age", max_age, 0) || !need_min(who, "min_hits", min_hits, 0)) return -1;
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_track_boxes(d_boxes, d_n_boxes, frames, max_boxes, conf, slots, iou_threshold, max_age, min_hits, static_cast<int*>(d_state),
+                                         d_tracks, d_ids, d_match, d_live, d_counts, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- band selection on the time-domain path
 
 int bf_band_filter_device(const float* d_signals, int rows, int frames, int hop, const float* d_prev, const float* d_taps, int n_taps, int bands, float* d_out,

@@ -164,6 +164,15 @@ hipError_t launch_fuse_boxes(const float* d_power, int frames, int image_stride,
                              const int* d_box_counts, int max_boxes, int img_w, int img_h, float conf, const int* d_src_offsets, int n_src,
                              int* d_peak_offsets, float* d_peak_power, int* d_center_offsets, int* d_rects, int* d_src_box, int* d_counts, hipStream_t stream);
 
+// bf_track_boxes_device (box_track.hip): the detector's [frames][max_boxes][6] rows -> [frames][slots][6] rows whose slot s is one object
+// over time (SORT: a constant-velocity Kalman filter per box, IoU association by the optimal assignment, max_age / min_hits).  One
+// launch of one workgroup; d_state (4 + 20 * slots words) carries the tracks from call to call; d_n_boxes and the four outputs after
+// d_tracks may be null; no workspace.
+constexpr int kBoxTrackMaxSlots = 64;
+constexpr int kBoxTrackMaxBoxes = 1024;
+hipError_t launch_track_boxes(const float* d_boxes, const int* d_n_boxes, int frames, int max_boxes, float conf, int slots, float iou_threshold, int max_age,
+                              int min_hits, int* d_state, float* d_tracks, int* d_ids, int* d_match, float* d_live, int* d_counts, hipStream_t stream);
+
 // bf_band_filter_device (band_filter.hip): `bands` FIRs of n_taps taps (d_taps float32 [bands][n_taps]) on every row of d_signals float32
 // [frames][rows][n_samples] -> d_out float32 [bands][frames][rows][n_samples].  The n_taps - 1 samples before a row come from the
 // frame before it (`hop` samples earlier; d_prev float32 [rows][n_samples] for frame 0, null = silence), hop 0 = zeros for every frame.

@@ -4,8 +4,10 @@ PyTorch-ROCm -- its 60 convolutions (+ bias + SiLU) in the implicit-GEMM MFMA ke
 reference's predict call or float16 -- and the head decode + candidate selection + NMS in the HIP kernels of csrc/nms_kernels.hip.
 
 `model_path` may name a state_dict saved from `image_detection.model.yolov5s.YOLOv5s`; with None (the reference's
-weights are not in its repository) a seeded random-init network is used.  SORT tracking (sort/sort.py, GPL, CPU) and the
-OpenCV drawing of `process_video_track_boxes_only` stay with the reference; `split_detections` is its banding logic."""
+weights are not in its repository) a seeded random-init network is used.  The SORT tracking of
+`process_video_track_boxes_only` (:275-347; sort/sort.py, GPL, is not vendored) is `boxtrack.BoxTracker` on `detect`'s output:
+bf_track_boxes_device, written from the published algorithm, one launch on the device.  The OpenCV drawing of that function stays
+with the reference; `split_detections` is its banding logic."""
 import ctypes as C
 import os
 

@@ -114,6 +114,9 @@ _sig("bf_track_sources_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, 
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("bf_fuse_boxes_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("bf_box_track_state_words", C.c_int, C.c_int)
+_sig("bf_track_boxes_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("bf_band_filter_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
 _sig("bf_filter_sum_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, IP, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
      C.c_void_p)

@@ -60,6 +60,11 @@ class FusedPipeline:
         d_windows, status = ingest.frames(d_packets)
         return self.step(d_windows, d_camera, conf_thres) + (status,)
 
+    def track(self, boxes, counts, tracker):
+        """step's boxes and counts -> tracker.update (a boxtrack.BoxTracker): rows whose slot s is one object over time, which
+        `focus` takes as boxes with counts None (tracks, ids, match, live, counts)."""
+        return tracker.update(boxes, counts)
+
     def focus(self, power, boxes, counts, fusion, sources=None):
         """step's power maps, boxes and counts -> fusion.focus (a fuse.SensorFusion) at this pipeline's frame size: per box the
         loudest direction under it as a table offset for listen(), per source of `sources` the box it lies in."""
