@@ -7,7 +7,9 @@ Compiles the unit to gfx950 assembly with the build's flags (HIPCC_FLAGS of __gr
   (b) the instructions of every kind between one mic's `;BF_S2_BEGIN` and the next one's in the text, the out-of-line `.subsection 1`
       re-read stubs excluded: a mic's steps 1..7, the next mic's address, reads, waits and step 0, and the table loads between;
   (c) VGPRs, SGPRs, spilled SGPRs and scratch bytes from the code-object metadata, and the v_readlane / v_writelane (SGPR spill
-      traffic) between the barriers of the half loop.
+      traffic) between the barriers of the half loop;
+  (d) the k-ordered mean-power pass of the power-of-two path (`;BF_POWER_POW2` to `;BF_POWER_END`): what every wave issues to park
+      its squares, by kind, and the reads, adds and waits of each ordered-sum loop.
 
 usage: python scripts/dev/pair2_instruction_budget.py [das_pair.hip]      (default: the unit in csrc/; another path: a variant of it
        with the same markers, e.g. an older revision)"""
@@ -182,11 +184,68 @@ def lane_spills_in_half_loop(lines):
     return sum(1 for l in lines[lo:hi] if re.match(r"v_(readlane|writelane)_b32", l.split(";")[0].strip()))
 
 
+POWER_KINDS = ("packed multiply", "multiply", "lds store", "lds read", "vector", "scalar", "wait", "test/branch")
+
+
+def power_kind_of(text):
+    op = text.split()[0]
+    if op.startswith("v_pk_mul_f32"):
+        return "packed multiply"
+    if op.startswith("v_mul_f32"):
+        return "multiply"
+    if op.startswith("ds_write"):
+        return "lds store"
+    if op.startswith("ds_read"):
+        return "lds read"
+    k = kind_of(text)
+    return k if k in ("wait", "test/branch", "scalar") else "vector"
+
+
+def power_pass(lines):
+    """(d): the mean-power pass of the power-of-two path, the text from the source's `;BF_POWER_POW2` marker to the next
+    `;BF_POWER_END`; None where the source has no such markers.
+      parking: {kind: count} of what every wave issues to park its squares: the text before the pass's first barrier (round 0: the
+               means, the squares, the stores) and between its second and its third (round 1), barriers excluded;
+      loops:   one entry per loop of the text that reads LDS and adds (the ordered sum of a round): its 16-byte reads, its v_add_f32,
+               the lgkmcnt of every wait in it in order -- a 0 among them is a full wait, an LDS round trip the chain sits through."""
+    begin = [i for i, l in enumerate(lines) if "BF_POWER_POW2" in l]
+    if not begin:
+        return None
+    end = next((i for i in range(begin[0], len(lines)) if "BF_POWER_END" in lines[i]), len(lines))   # (laid out before the pass: to the kernel's end)
+    text = []                                               # instructions and labels of the pass, in text order
+    for line in lines[begin[0] + 1:end]:
+        l = line.split(";")[0].strip()
+        if not l:
+            continue
+        if l.startswith(".") and not l.endswith(":"):
+            continue
+        text.append(l)
+    bars = [i for i, l in enumerate(text) if l == "s_barrier"]
+    parking = dict.fromkeys(POWER_KINDS, 0)
+    if len(bars) >= 3:
+        for l in text[:bars[0]] + text[bars[1] + 1:bars[2]]:
+            if not l.endswith(":"):
+                parking[power_kind_of(l)] += 1
+    loops = []
+    where = {l[:-1]: i for i, l in enumerate(text) if l.endswith(":")}
+    for i, l in enumerate(text):
+        m = re.match(r"s_cbranch_\w+\s+(\S+)", l)
+        if m and m.group(1) in where and where[m.group(1)] < i:
+            body = [t for t in text[where[m.group(1)]:i] if not t.endswith(":")]
+            reads = sum(t.startswith("ds_read_b128") for t in body)
+            adds = sum(t.startswith("v_add_f32") for t in body)
+            if reads and adds and "s_barrier" not in body:
+                waits = [int(w) for t in body if t.startswith("s_waitcnt") for w in re.findall(r"lgkmcnt\((\d+)\)", t)]
+                loops.append(dict(reads=reads, adds=adds, waits=waits))
+    return dict(parking=parking, barriers=len(bars), loops=loops)
+
+
 def budget(src=None):
     txt = compile_asm(src)
     lines = kernel_lines(txt)
     items, labels = parse(lines)
-    return dict(staging=staging_path(items, labels), gaps=mic_gaps(lines), resources=resources(txt), lane_spills=lane_spills_in_half_loop(lines))
+    return dict(staging=staging_path(items, labels), gaps=mic_gaps(lines), resources=resources(txt), lane_spills=lane_spills_in_half_loop(lines),
+                power=power_pass(lines))
 
 
 def report(b):
@@ -206,6 +265,16 @@ def report(b):
     r = b["resources"]
     out.append("(c) VGPRs %d, SGPRs %d, spilled SGPRs %d, scratch %d bytes; v_readlane / v_writelane inside the half loop: %s" %
                (r["vgprs"], r["sgprs"], r["sgpr_spills"], r["scratch"], b["lane_spills"]))
+    p = b.get("power")
+    if p is None:
+        out.append("(d) mean-power pass: no BF_POWER_POW2 / BF_POWER_END markers in this source")
+    else:
+        pk = p["parking"]
+        out.append("(d) mean-power pass, power-of-two path: %d barriers; parking, both rounds: %d instructions  (%s)" %
+                   (p["barriers"], sum(pk.values()), ", ".join("%s %d" % (k, pk[k]) for k in POWER_KINDS if pk[k])))
+        for i, lp in enumerate(p["loops"]):
+            out.append("      ordered-sum loop %d: %d reads of 16 bytes, %d adds, waits lgkmcnt(%s)%s" %
+                       (i, lp["reads"], lp["adds"], ", ".join(map(str, lp["waits"])), "  <- a full wait inside the loop" if 0 in lp["waits"] else ""))
     return "\n".join(out)
 
 

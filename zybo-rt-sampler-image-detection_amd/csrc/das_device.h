@@ -182,6 +182,45 @@ __device__ __forceinline__ float row_mean_power(const float* row, int n)
     return sum / (float)n;
 }
 
+// sum + the first 4 * `quads` (quads = 1..32) squares of a half row parked at LDS byte address `ad`, in k order.
+// The row holds its 128 samples as [the 64 even ones][the 64 odd ones] (that is how a lane that owns samples 2l, 2l+1 stores them
+// without a bank conflict: one dword per lane, side by side, twice), so samples 8p .. 8p+7 are the p-th 16-byte quad of each part,
+// E and O, added E0 O0 E1 O1 E2 O2 E3 O3.
+// Rolling: the reads of four such pairs are in flight, and a pair is requested again, four pairs on, right behind the eight adds that
+// consumed it -- after the first wait the chain never meets an LDS latency, and no wait inside the loop is a full one.  The last 1..8
+// quads of samples drain without refills.  The reads run up to 7 quads of samples past `quads`, never past the row's 128 samples.
+// One statement, because the adds name the registers of a read tuple singly, which asm operands cannot express: the reads land in
+// HARD-WIRED v96..v111 (E) and v112..v127 (O), named as clobbers (tests/test_isa_hazards.py: nothing touches a register between a
+// read into it and its wait).
+#define BF_R_ADD4(e0, o0, e1, o1) "v_add_f32 %[s], %[s], v" #e0 "\n\tv_add_f32 %[s], %[s], v" #o0 "\n\tv_add_f32 %[s], %[s], v" #e1 "\n\tv_add_f32 %[s], %[s], v" #o1 "\n\t"
+#define BF_R_READ(e0, e3, o0, o3, off) "ds_read_b128 v[" #e0 ":" #e3 "], %[ad] offset:" #off "\n\tds_read_b128 v[" #o0 ":" #o3 "], %[ad] offset:256 + " #off "\n\t"
+#define BF_R_ROLL(e0, e1, e2, e3, o0, o1, o2, o3, off) "s_waitcnt lgkmcnt(6)\n\t" BF_R_ADD4(e0, o0, e1, o1) BF_R_ADD4(e2, o2, e3, o3) BF_R_READ(e0, e3, o0, o3, off)
+#define BF_R_DONE(n) "s_cmp_eq_u32 %[nq], " #n "\n\ts_cbranch_scc1 .Le_%=\n\t"
+#define BF_R_DRAIN(e0, e1, e2, e3, o0, o1, o2, o3, left, n) "s_waitcnt lgkmcnt(" #left ")\n\t" BF_R_ADD4(e0, o0, e1, o1) BF_R_DONE(n) BF_R_ADD4(e2, o2, e3, o3)
+__device__ __forceinline__ float add_in_order_rolling(unsigned ad, int quads, float sum)
+{
+    asm volatile(BF_R_READ(96, 99, 112, 115, 0) BF_R_READ(100, 103, 116, 119, 16) BF_R_READ(104, 107, 120, 123, 32) BF_R_READ(108, 111, 124, 127, 48)
+                 "s_cmp_le_u32 %[nq], 8\n\ts_cbranch_scc1 .Ld_%=\n"
+                 ".Lt_%=:\n\t"      // a trip of four pairs (32 samples), each requested again from 64 bytes on
+                 BF_R_ROLL(96, 97, 98, 99, 112, 113, 114, 115, 64) BF_R_ROLL(100, 101, 102, 103, 116, 117, 118, 119, 80)
+                 BF_R_ROLL(104, 105, 106, 107, 120, 121, 122, 123, 96) BF_R_ROLL(108, 109, 110, 111, 124, 125, 126, 127, 112)
+                 "v_add_u32 %[ad], 64, %[ad]\n\ts_sub_u32 %[nq], %[nq], 8\n\ts_cmp_gt_u32 %[nq], 8\n\ts_cbranch_scc1 .Lt_%=\n"
+                 ".Ld_%=:\n\t"      // the drain: 1..8 quads of samples are left, all of them requested; it ends behind any half pair
+                 BF_R_DRAIN(96, 97, 98, 99, 112, 113, 114, 115, 6, 1) BF_R_DONE(2) BF_R_DRAIN(100, 101, 102, 103, 116, 117, 118, 119, 4, 3) BF_R_DONE(4)
+                 BF_R_DRAIN(104, 105, 106, 107, 120, 121, 122, 123, 2, 5) BF_R_DONE(6) BF_R_DRAIN(108, 109, 110, 111, 124, 125, 126, 127, 0, 7)
+                 ".Le_%=:\n\ts_waitcnt lgkmcnt(0)"      // (an early end: the reads beyond it land before the registers are anyone else's)
+                 : [s] "+v"(sum), [ad] "+v"(ad), [nq] "+s"(quads)
+                 :
+                 : "memory", "scc", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111",
+                   "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
+    return sum;
+}
+#undef BF_R_ADD4
+#undef BF_R_READ
+#undef BF_R_ROLL
+#undef BF_R_DONE
+#undef BF_R_DRAIN
+
 namespace copies {
 
 __device__ __forceinline__ float dpp_prev(float x)   // lane-1's value, 0 in lane 0

@@ -40,6 +40,7 @@ struct Geo {
     static constexpr int kLead = NSEG == 1 ? 56 : 64;                // zero prefix of the fixed-stride variant (56: the as-shipped array's delays, up to 47 samples, still fit; 32 lerp mics x 4 rows x 312 floats = 156 KiB)
     static constexpr int kRs = NSEG * 256 + kLead;                   // its row stride
     static constexpr int kPark = NSEG * 256 + 4;                     // floats per parked row of squares
+    static constexpr int kParkHalf = 128 + 4;                        // ... of the kernels that park a row in two halves of 128 samples (das_pair2_kernel); 4 (mod 64) dwords like kPark
     static constexpr int kFirTail = 8;                               // 8-tap FIR rows: the reference's zero padding after the block
     static constexpr int kRsFir = kRs + kFirTail;
 };

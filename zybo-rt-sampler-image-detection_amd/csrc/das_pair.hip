@@ -336,7 +336,8 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
 {
     static_assert(ALGO == ALGO_LERP, "das_pair2_kernel: lerp (pad runs das_pair_kernel)");
     using G = Pair2Geo;
-    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kPark = Geo<1>::kPark;
+    constexpr int C = G::kC, RS = G::kRs, LEAD = G::kLead, HC = G::kHalf, W = 16, DW = 8, kGroup = DW * W, kParkHalf = Geo<1>::kParkHalf;
+    static_assert(2 * kGroup * kParkHalf <= G::kMc * G::kSlot, "both frames' parked half rows fit the LDS image they alias");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & (kWave - 1);               // (set-up only: inside the group loop lane_id() recomputes it, a register less to carry through the sweep)
     auto lane_id = []() -> int {
@@ -508,41 +509,86 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
             BF_STAMP(h + 1 < n_half ? 3 : 4);
         }
 
-        // ---- k-ordered mean power (pad_and_sum.c:120-128), one frame at a time: the 16 waves park the squared means of their
-        // directions (row = direction, k in order; the rows alias the LDS image), then one direction per lane runs the sequential sum.
+        // ---- k-ordered mean power (pad_and_sum.c:120-128), both frames at once, one HALF of the samples at a time.  A frame's 128 rows
+        // of 256 squares fill the LDS image the rows alias, but 256 rows of 128 do not: so the 16 waves park the squared means of samples
+        // 0..127 of their directions for both frames (row 128 f + direction of the group, Geo<1>::kParkHalf floats apart), one (frame,
+        // direction) per lane of waves 0..3 adds its row to a running sum, and a second round does the same for samples 128..N-1.  A
+        // direction's additions stay strictly in k order; the chain of a round is 128 adds instead of a frame's 256, on four waves
+        // instead of two.
+        // (the whole pass once per way of dividing, behind the real branch on a.n_is_pow2 -- DESIGN.md 4.1: hipcc speculates the division
+        //  sequence otherwise -- and not the divisions alone: where the two ways meet again hipcc moves all 64 values to other registers
+        //  and spills.  For the same reason a round squares its own half: all 64 squares pinned before round 0 spill too)
+        auto power_pass = [&](auto mul_c) __attribute__((always_inline)) {
+        constexpr bool MUL = decltype(mul_c)::value;
+        if constexpr (MUL) asm volatile(";BF_POWER_POW2"); else asm volatile(";BF_POWER_DIV");      // (;BF_POWER_*: markers for scripts/dev/pair2_instruction_budget.py, comments in the assembly)
+        // (the wave's number behind an empty statement: what the pass derives from it -- row addresses, who sums, which frame -- is then
+        //  computed here, a few scalar instructions per group, not hoisted out of the group loop into SGPRs the sweep has none of to spare)
+        int wv = wave;
+        asm volatile("" : "+s"(wv));
+        float sum = 0.0f;               // of this lane's (frame, direction), carried from round 0 to round 1 (waves 0..3)
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            if (f == 1) {
-                __syncthreads();        // frame 0's rows have been summed
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1) {
+                __syncthreads();        // round 0's rows have been summed
                 BF_STAMP(4);
             }
-            auto park = [&](auto mul_c) __attribute__((always_inline)) {
-                const int lane = lane_id();
+            {
+                // out[k] /= n and the squares of direction j's half, both frames at once: a register pair is one sample of frames 0 and 1,
+                // and v_pk_mul_f32 rounds each component as v_mul_f32 does
+                auto squares = [&](int j, f32x2& s0, f32x2& s1) __attribute__((always_inline)) {
+                    if constexpr (MUL) {
+                        const f32x2 inv2 = {a.inv_n, a.inv_n};
+                        s0 = acc[j][2 * r] * inv2; s1 = acc[j][2 * r + 1] * inv2;
+                    } else {
+                        float o0, o1, o2, o3;
+                        mic_mean<false>(acc[j][2 * r].x, acc[j][2 * r + 1].x, acc[j][2 * r].y, acc[j][2 * r + 1].y, M, a.inv_n, o0, o1, o2, o3);
+                        s0 = f32x2{o0, o2}; s1 = f32x2{o1, o3};
+                    }
+                    s0 = s0 * s0; s1 = s1 * s1;
+                };
+                // lane l holds samples 2l, 2l+1 of the half, one frame's two floats in two register pairs.  ds_write2_b32 stores them from
+                // where they are (as a float2 they are moved together first), and each to a part of its own: a row is [64 even samples]
+                // [64 odd samples], so that the lanes of either store cover 64 banks (side by side at 8 l: two lanes per bank, measured).
+                // add_in_order_rolling reads the two parts back into k order.  The offsets, 8 bits of dwords, reach two rows.
+                static_assert(kParkHalf + 64 < 256, "a row and the next one off one address");
+                const unsigned rows = (unsigned)(size_t)((__attribute__((address_space(3))) char*)lds) + (unsigned)((wv * DW) * kParkHalf + lane_id()) * 4u;
+                auto park2 = [](unsigned ad, const f32x2& s0, const f32x2& s1, const f32x2& t0, const f32x2& t1, auto fc) __attribute__((always_inline)) {
+                    constexpr bool F1 = decltype(fc)::value;
+                    asm volatile("ds_write2_b32 %[ad], %[s0], %[s1] offset1:64\n\tds_write2_b32 %[ad], %[t0], %[t1] offset0:%[o0] offset1:%[o1]"
+                                 : : [ad] "v"(ad), [s0] "v"(F1 ? s0.y : s0.x), [s1] "v"(F1 ? s1.y : s1.x), [t0] "v"(F1 ? t0.y : t0.x), [t1] "v"(F1 ? t1.y : t1.x),
+                                     [o0] "n"(kParkHalf), [o1] "n"(kParkHalf + 64) : "memory");
+                };
 #pragma unroll
-                for (int j = 0; j < DW; ++j) {
-                    float* row = lds + (wave * DW + j) * kPark;
-                    const float x0 = f == 0 ? acc[j][0].x : acc[j][0].y, x1 = f == 0 ? acc[j][1].x : acc[j][1].y;
-                    const float x2 = f == 0 ? acc[j][2].x : acc[j][2].y, x3 = f == 0 ? acc[j][3].x : acc[j][3].y;
-                    float o0, o1, o2, o3;
-                    mic_mean<decltype(mul_c)::value>(x0, x1, x2, x3, M, a.inv_n, o0, o1, o2, o3);
-                    reinterpret_cast<float2*>(row)[lane] = make_float2(o0 * o0, o1 * o1);             // samples 2l, 2l+1
-                    reinterpret_cast<float2*>(row + 128)[lane] = make_float2(o2 * o2, o3 * o3);       // samples 128+2l, 128+2l+1
+                for (int j = 0; j < DW; j += 2) {
+                    f32x2 s0, s1, t0, t1;
+                    squares(j, s0, s1);
+                    squares(j + 1, t0, t1);
+                    const unsigned ad = rows + (unsigned)j * (kParkHalf * 4u);
+                    park2(ad, s0, s1, t0, t1, std::false_type{});
+                    park2(ad + kGroup * kParkHalf * 4u, s0, s1, t0, t1, std::true_type{});
                 }
-            };
-            if (__builtin_expect(a.n_is_pow2, 1)) park(std::true_type{}); else park(std::false_type{});
+            }
             BF_STAMP(5);                // -> waiting
             __syncthreads();
-            BF_STAMP(6);                // -> ordered sum (two waves; the others go on to the next barrier)
-            const int lane_o = lane_id();                 // (recomputed: keeps the per-lane row address out of the registers the sweep needs)
-            const int g = wave * kWave + lane_o;          // parked row of this lane
-            const int d = g0 + g;
-            if (g < kGroup && d < tile_end && (f == 0 || two)) {
-                // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the two summing waves)
-                const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
-                // (ONE_TRIP: eight reads in flight, as ever: two trips' worth spill the staged quads)
-                (f == 0 ? img0 : img1)[dd - a.image_origin] = row_mean_power<true>(lds + g * kPark, N);
+            BF_STAMP(6);                // -> ordered sum (four waves; the others go on to the next barrier)
+            if (wv < 2 * (kGroup / kWave)) {
+                const int lane_o = lane_id();                 // (recomputed: keeps the per-lane row address out of the registers the sweep needs)
+                const int g = (wv & 1) * kWave + lane_o;    // this lane's direction of the group; its parked row is wave * 64 + lane: frame 1's rows follow frame 0's
+                const int d = g0 + g;
+                if (d < tile_end && (wv < kGroup / kWave || two)) {
+                    const unsigned row = (unsigned)(size_t)((__attribute__((address_space(3))) char*)lds) + (unsigned)(wv * kWave + lane_o) * (kParkHalf * 4u);
+                    sum = add_in_order_rolling(row, r == 0 ? 32 : (N - 128) >> 2, sum);     // round 1 stops at N
+                    if (r == 1) {
+                        // the direction swept at position d - dir_begin (wave-uniform branch; one 4-byte load in the four summing waves)
+                        const int dd = a.digest_o_off != 0 ? dig[a.digest_o_off + (d - a.dir_begin)] : d;
+                        (wv < kGroup / kWave ? img0 : img1)[dd - a.image_origin] = sum / (float)N;
+                    }
+                }
             }
         }
+        asm volatile(";BF_POWER_END");
+        };
+        if (__builtin_expect(a.n_is_pow2, 1)) power_pass(std::true_type{}); else power_pass(std::false_type{});
     }
     BF_STAMP(7);
     BF_STAMP_FLUSH;
