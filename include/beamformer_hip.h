@@ -156,6 +156,10 @@ int bf_sweep_order(const int *whole, int n_dirs, int n_mics, int dir_begin, int 
  * summed over all waves since the last clear: out16[0..7] = sweep, wait, staging, wait, wait, parking, wait, ordered power sum
  * (s_memtime ticks), out16[8] = waves counted.  All zero in the production build.  Returns 0 or -1. */
 int bf_read_phase_stamps(unsigned long long *out16, int clear);
+/* The same build's per-wave rows: out128[8 w + 0..7] for wave index w = 0..15 of the workgroup = its sweep ticks, its ticks waiting
+ * for the staged chunk, the number of workgroups in which it ran on SIMD 0, 1, 2, 3 (HW_ID), and of the last launch's recorded
+ * workgroups ([7]) those in which it ran on the SIMD of wave w & 3 ([6]).  All zero in the production build. */
+int bf_read_wave_stamps(unsigned long long *out128, int clear);
 /* Select the HIP device (default 0, or $BF_DEVICE) before the first load_* call. */
 int bf_set_device(int device);
 

@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """Dev tool: where the waves of the batched pad / lerp kernel spend their time.
 
-  build (here or on the GPU box):  python3 scripts/dev/phase_stamps.py build     -> scripts/dev/bin/libbeamformer_hip_stamps.so
+  build (here or on the GPU box):  python3 scripts/dev/phase_stamps.py build [hipcc flags]   -> scripts/dev/bin/libbeamformer_hip_stamps.so
   run (GPU box):                   python3 scripts/dev/phase_stamps.py run [lerp|pad] [workload] [frames]
 
 The profiling library is the production source compiled with -DBF_STAMPS: every wave of das_pair_kernel reads s_memtime at
-its phase boundaries (all next to barriers) and the per-phase totals are summed over the launch."""
+its phase boundaries (all next to barriers) and the per-phase totals are summed over the launch.  Beside the totals the run prints
+one row per wave index of the workgroup: the SIMDs it ran on (HW_ID; the first wave's SIMD differs from workgroup to workgroup),
+in how many workgroups it shared the SIMD of wave (index & 3), its sweep and its wait for the staged chunk, each as a share of the
+mean wave lifetime, and the waits of the waves w, w + 4, w + 8, w + 12 side by side -- whether the four waves of a SIMD finish a
+half as a staircase.
+$BF_STAMPS_LIB: another path for the profiling library (to keep two builds side by side)."""
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-OUT = os.path.join(ROOT, "scripts", "dev", "bin", "libbeamformer_hip_stamps.so")
+OUT = os.environ.get("BF_STAMPS_LIB") or os.path.join(ROOT, "scripts", "dev", "bin", "libbeamformer_hip_stamps.so")
 sys.path.insert(0, ROOT)
 
 
@@ -19,7 +24,7 @@ def build():
     import __graft_entry__ as ge
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     srcs = [os.path.join(ge.CSRC, s) for s in ge.SOURCES]
-    cmd = ["/opt/rocm/bin/hipcc"] + ge.HIPCC_FLAGS + ["-shared", "-DBF_STAMPS"] + srcs + ["-o", OUT]
+    cmd = ["/opt/rocm/bin/hipcc"] + ge.HIPCC_FLAGS + ["-shared", "-DBF_STAMPS"] + sys.argv[2:] + srcs + ["-o", OUT]
     subprocess.check_call(cmd)
     print("built", OUT)
 
@@ -72,7 +77,30 @@ def run(algo="lerp", workload="cfg2", frames=190):
     for n, x in zip(names, v[:8]):
         print("  %-26s %6.2f %%" % (n, 100.0 * x / max(tot, 1)))
     print("  mean wave lifetime %.1f ticks; ticks per ms of launch per wave slot: %.0f" % (tot / max(v[8], 1), tot / reps / ms / 4096.0))
-
+    if getattr(nat.lib, "bf_read_wave_stamps", None) is None:
+        return
+    wbuf = (C.c_ulonglong * 128)()
+    assert nat.lib.bf_read_wave_stamps(wbuf, 1) == 0
+    rows = [[int(x) for x in wbuf[8 * w:8 * w + 8]] for w in range(16)]
+    life = tot / max(v[8], 1)                 # every wave of a workgroup lives as long as the workgroup: the mean is each row's lifetime
+    print("  per wave index (sweep and wait: shares of the mean wave lifetime; SIMD 0/1/2/3: where HW_ID placed it, by workgroups;")
+    print("  with w & 3: the recorded workgroups in which it ran on the SIMD of wave (index & 3)):")
+    print("  wave   on SIMD 0 / 1 / 2 / 3 (%)    with w & 3    sweep    wait (chunk staged)")
+    waits = {}
+    for w, r in enumerate(rows):
+        n = sum(r[2:6])
+        if n == 0:
+            continue
+        waits[w] = 100.0 * r[1] / n / life
+        print("  %4d   %5.1f %5.1f %5.1f %5.1f       %6.1f %%     %6.2f %%   %6.2f %%" % (
+            (w,) + tuple(100.0 * x / n for x in r[2:6]) + (100.0 * r[6] / max(r[7], 1), 100.0 * r[0] / n / life, waits[w])))
+    if waits:
+        mean = sum(waits.values()) / len(waits)
+        print("  waits: mean %.2f %%, min %.2f %%, max %.2f %%, (max - min) / mean = %.2f  (%d workgroups of the last launch recorded)" % (
+            mean, min(waits.values()), max(waits.values()), (max(waits.values()) - min(waits.values())) / mean, rows[0][7]))
+    for q in range(4):
+        ws = [w for w in range(q, 16, 4) if w in waits]
+        print("  waves %s (oldest first): waits %s" % (", ".join("%d" % w for w in ws), ", ".join("%.2f %%" % waits[w] for w in ws)))
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "build":

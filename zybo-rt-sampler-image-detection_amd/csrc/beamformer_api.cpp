@@ -850,6 +850,12 @@ int bf_read_phase_stamps(unsigned long long* out16, int clear)
     if (!out16 || !ensure_device()) return -1;
     return HIP_OK(hipDeviceSynchronize()) && HIP_OK(bf::read_phase_stamps(out16, clear != 0)) ? 0 : -1;
 }
+int bf_read_wave_stamps(unsigned long long* out128, int clear)
+{
+    std::lock_guard<std::mutex> lock(S().mu);
+    if (!out128 || !ensure_device()) return -1;
+    return HIP_OK(hipDeviceSynchronize()) && HIP_OK(bf::read_wave_stamps(out128, clear != 0)) ? 0 : -1;
+}
 
 int bf_gpu_available(void)
 {

@@ -253,6 +253,7 @@ hipError_t launch_fd_mvdr_power(const float* lire_t, const float* liim_t, const 
 
 // Profiling build only (-DBF_STAMPS): phase totals of das_pair_kernel, see das_pair.hip (zeros in a production build).
 hipError_t read_phase_stamps(unsigned long long* out16, bool clear);
+hipError_t read_wave_stamps(unsigned long long* out128, bool clear);      // one row of 8 per wave index of the workgroup
 
 // detector post-processing (nms_kernels.hip): YOLOv5 head decode + confidence filter, greedy NMS over score-sorted candidates
 hipError_t launch_yolo_decode(const void* const raw[3], const int hs[3], const int ws[3], const int strides[3], const float* anchors,

@@ -88,7 +88,17 @@ __device__ unsigned long long g_stamps[64 * 16];         // (sums over all waves
                                                          //  line would make the flush longer than the kernel)
 #define BF_STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_prev = __builtin_amdgcn_s_memtime();
 #define BF_STAMP(k) do { const unsigned long long st_now = __builtin_amdgcn_s_memtime(); st_acc[k] += st_now - st_prev; st_prev = st_now; } while (0)
-#define BF_STAMP_FLUSH do { if (lane == 0) { unsigned long long* gs = g_stamps + 16 * (blockIdx.x & 63); for (int i = 0; i < 8; ++i) atomicAdd(&gs[i], st_acc[i]); atomicAdd(&gs[8], 1ull); } } while (0)
+// Beside the totals, one row per wave index of the workgroup (16 rows of 8): its sweep (0) and its wait for the staged chunk (1),
+// summed over the workgroups, and how often it ran on SIMD 0..3 (2..5; HW_ID[5:4], read once: a wave stays where it was placed).
+// g_wave_simd keeps the SIMDs of the 16 waves of one workgroup side by side (0x80 | SIMD; the last launch's workgroups, 4096 of
+// them at the most): which wave indices share a SIMD is read off these.
+__device__ unsigned long long g_wave_stamps[64 * 16 * 8];
+__device__ unsigned char g_wave_simd[4096 * 16];
+#define BF_STAMP_FLUSH do { if (lane == 0) { unsigned long long* gs = g_stamps + 16 * (blockIdx.x & 63); for (int i = 0; i < 8; ++i) atomicAdd(&gs[i], st_acc[i]); atomicAdd(&gs[8], 1ull); \
+                            unsigned simd; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 4, 2)" : "=s"(simd)); \
+                            unsigned long long* gw = g_wave_stamps + 128 * (blockIdx.x & 63) + 8 * (wave & 15); \
+                            atomicAdd(&gw[0], st_acc[0]); atomicAdd(&gw[1], st_acc[3]); atomicAdd(&gw[2 + (simd & 3)], 1ull); \
+                            g_wave_simd[16 * (blockIdx.x & 4095) + (wave & 15)] = (unsigned char)(0x80 | (simd & 3)); } } while (0)
 #else
 #define BF_STAMP_DECL
 #define BF_STAMP(k)
@@ -168,6 +178,9 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
         BF_STAMP(3);
 
         for (int h = 0; h < n_half; ++h) {
+            // the priority ladder of das_pair2_kernel (see there), on this kernel's trips of three mics: 3 from the barrier on, 1 behind
+            // either trip (mics 3 and 6), 0 for the last two mics (-9.3 %)
+            asm volatile("s_setprio 3");
             if (h + 1 < n_half) {
                 stage(h + 1, st, h == 0);                       // into the half whose sweeps ended before the last barrier
                 // request what is staged an iteration from now: half h + 2, or the next group's first half (the same rows)
@@ -203,7 +216,9 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
                 for (int t = 0; t < 2; ++t) {
                     mic(0, I0{}); mic(1, I1{}); mic(2, I2{});
                     et += 3 * DW;
+                    asm volatile("s_setprio 1");
                 }
+                asm volatile("s_setprio 0");
                 mic(0, I0{});
                 mic(1, I1{});
             }
@@ -211,6 +226,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair_kernel(BF_TABLE_PARAMS, KArg
             __syncthreads();   // half h is free, half h + 1 is staged
             BF_STAMP(h + 1 < n_half ? 3 : 4);
         }
+        asm volatile("s_setprio 0");    // (a wave without directions of its own kept 3; every wave enters the power pass at 0)
 
         // ---- k-ordered mean power (pad_and_sum.c:120-128), one frame at a time: the 16 waves park the squared means of their
         // directions (row = direction; the rows alias the chunk buffer), then one direction per lane runs the sequential sum.
@@ -469,6 +485,13 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
         const float* __restrict__ htg = reinterpret_cast<const float*>(dig) + a.digest_h_off + grp * M * DW;
         int row_next = row1;                                    // where the next half is staged: halves alternate
         for (int h = 0; h < n_half; ++h) {
+            // The priority ladder.  A SIMD issues by priority, then by age, so at one priority its four waves (w, w + 4, w + 8, w + 12:
+            // measured) end every half as a staircase, the youngest sweeping the last stretch alone with nobody to fill the slots
+            // its scalar work and LDS round trips leave.  Keyed to progress -- 3 from the barrier on (the staging included), 2, 1,
+            // 0 at mics 2, 4, 6 -- a wave that is behind outranks one that is ahead and the four converge on the barrier
+            // (the wait for the staged chunk 23.7 % -> 8.9 % of a wave's life, the launch -7.1 %).  One scalar
+            // instruction where it changes, before a mic's first statement: never while the hard-wired quads are in flight.
+            asm volatile("s_setprio 3");
             asm volatile(";BF_STAGE_BEGIN");                    // (;BF_STAGE_*: path markers for scripts/dev/pair2_instruction_budget.py, comments in the assembly)
             if (h + 1 < n_half) {
                 stage(row_next, st);                            // into the half whose sweeps ended before the last barrier
@@ -501,13 +524,20 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_kernel(BF_TABLE_PARAMS, KAr
                 };
                 using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
                 static_assert(HC == 8, "eight mics, the three entry sets in rotation");
-                mic(0, I0{}); mic(1, I1{}); mic(2, I2{}); mic(3, I0{}); mic(4, I1{}); mic(5, I2{}); mic(6, I0{}); mic(7, I1{});
+                mic(0, I0{}); mic(1, I1{});
+                asm volatile("s_setprio 2");
+                mic(2, I2{}); mic(3, I0{});
+                asm volatile("s_setprio 1");
+                mic(4, I1{}); mic(5, I2{});
+                asm volatile("s_setprio 0");
+                mic(6, I0{}); mic(7, I1{});
                 __builtin_amdgcn_s_waitcnt(0xC07F);             // the entries requested past the half's end have landed (and are dropped)
             }
             BF_STAMP(0);       // sweep -> waiting for the others
             __syncthreads();   // half h is free, half h + 1 is staged
             BF_STAMP(h + 1 < n_half ? 3 : 4);
         }
+        asm volatile("s_setprio 0");    // (a wave without directions of its own kept 3 from barrier to barrier, where it issues next to nothing)
 
         // ---- k-ordered mean power (pad_and_sum.c:120-128), both frames at once, one HALF of the samples at a time.  A frame's 128 rows
         // of 256 squares fill the LDS image the rows alias, but 256 rows of 128 do not: so the 16 waves park the squared means of samples
@@ -635,6 +665,38 @@ hipError_t read_phase_stamps(unsigned long long* out16, bool clear)
     return hipMemcpyToSymbol(HIP_SYMBOL(copies::g_stamps), all, sizeof(all));
 #else
     for (int i = 0; i < 16; ++i) out16[i] = 0;
+    (void)clear;
+    return hipSuccess;
+#endif
+}
+
+// Profiling build only: the per-wave rows beside the totals (16 wave indices x 8 counters; zeros in a production build).
+hipError_t read_wave_stamps(unsigned long long* out128, bool clear)
+{
+#ifdef BF_STAMPS
+    static unsigned long long all[64 * 128];
+    hipError_t e = hipMemcpyFromSymbol(all, HIP_SYMBOL(copies::g_wave_stamps), sizeof(all));
+    if (e != hipSuccess) return e;
+    for (int i = 0; i < 128; ++i) { out128[i] = 0; for (int r = 0; r < 64; ++r) out128[i] += all[128 * r + i]; }
+    // [6]: the recorded workgroups in which wave w ran on the SIMD of wave w & 3, [7]: the workgroups recorded (all 16 waves seen)
+    static unsigned char simd[4096 * 16];
+    e = hipMemcpyFromSymbol(simd, HIP_SYMBOL(copies::g_wave_simd), sizeof(simd));
+    if (e != hipSuccess) return e;
+    for (int g = 0; g < 4096; ++g) {
+        const unsigned char* s = simd + 16 * g;
+        bool whole = true;
+        for (int w = 0; w < 16; ++w) whole = whole && (s[w] & 0x80);
+        if (!whole) continue;
+        for (int w = 0; w < 16; ++w) { out128[8 * w + 6] += s[w] == s[w & 3]; out128[8 * w + 7] += 1; }
+    }
+    if (!clear) return e;
+    for (int i = 0; i < 64 * 128; ++i) all[i] = 0;
+    for (int i = 0; i < 4096 * 16; ++i) simd[i] = 0;
+    e = hipMemcpyToSymbol(HIP_SYMBOL(copies::g_wave_simd), simd, sizeof(simd));
+    if (e != hipSuccess) return e;
+    return hipMemcpyToSymbol(HIP_SYMBOL(copies::g_wave_stamps), all, sizeof(all));
+#else
+    for (int i = 0; i < 128; ++i) out128[i] = 0;
     (void)clear;
     return hipSuccess;
 #endif

@@ -93,6 +93,7 @@ _sig("bf_last_das_reloads", C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_long
 _sig("bf_sweep_order", C.c_int, IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP)
 _sig("bf_set_device", C.c_int, C.c_int)
 _sig("bf_read_phase_stamps", C.c_int, C.POINTER(C.c_ulonglong), C.c_int)
+_sig("bf_read_wave_stamps", C.c_int, C.POINTER(C.c_ulonglong), C.c_int)
 _sig("bf_publish_frame", None, FP)
 _sig("bf_miso_listen_block", C.c_int, FP, C.c_float)
 _sig("bf_get_steer", C.c_int, IP)
