@@ -585,6 +585,47 @@ int bf_miso_stream_device(int algo, const float *d_signals, int m_total, int fra
 int bf_das_stream_device(int algo, const float *d_signals, int m_total, float *d_images, int image_stride, int frames, int hop,
                          const float *d_prev, const int *adaptive_array, int n, int dir_begin, int dir_end, void *stream);
 
+/* ---- map values at listed directions: the power map evaluated at a device list of table offsets, one enqueue ----
+ * Every consumer of a power map reads a few cells of it (bf_peaks_device's window maxima, a tracker's slots, the loudest cell under a
+ * detector box), and bf_das_device / bf_das_stream_device give a cell's value only as part of a contiguous direction range.  These
+ * two calls give the map at the directions a list names; the list lives on the device and may differ from frame to frame, so a
+ * coarse scan, its peaks and a fine scan around them chain without a host round trip.
+ *
+ * Definition.  d_power[f][b] is the mean-power rule of the matching map call applied to the beam miso_* forms at offset d_offsets[f][b]
+ * of frame f (bf_das_select_device: the beam of bf_miso_device with mic_gain 0; bf_das_select_stream_device: that of
+ * bf_miso_stream_device, the definition above).  The rule: out[t] /= (float)n, the squares summed in t order in float32, the sum
+ * / N_SAMPLES.  The window-local call fuses square and add for the last N_SAMPLES % 4 samples, as bf_das_device and the compiled
+ * reference do; the stream call rounds every square, as bf_das_stream_device does.  So for an accepted offset d * n (BF_FIR_VEC:
+ * d * n * N_TAPS) d_power[f][b] equals the float bf_das_device (bf_das_stream_device) writes for direction d of frame f BIT FOR BIT,
+ * whichever kernel family bf_das_device chose.  The value does not depend on the list's order or length, on count or on frames.
+ *
+ * algo      : bf_das_select_device: BF_PAD, BF_LERP, BF_HYBRID, BF_FIR_VEC (bf_miso_device's set; BF_FIR_NAIVE is refused);
+ *             bf_das_select_stream_device: BF_PAD, BF_LERP.  The table is the one the matching load_coefficients_* loaded.
+ * d_signals / m_total / frames / adaptive_array / n : as bf_miso_device; hop / d_prev : as bf_miso_stream_device
+ * d_offsets : HIP device pointer, int32 [frames][count] when per_frame != 0, [count] shared by all frames when per_frame == 0 (the
+ *             lattice of a coarse scan).  Table offsets exactly as bf_miso_device takes them; unsorted lists and repeated entries are fine.
+ * d_power   : HIP device pointer, float32 [frames][power_stride], power_stride >= count; floats [count, power_stride) of every row are
+ *             left untouched.
+ * d_status  : HIP device pointer, int32 [frames][count], or NULL.  When given, every entry is written with bf_miso_device's codes: 0 ok,
+ *             1 offset negative or past the loaded table, 2 BF_FIR_VEC offset not a multiple of N_TAPS.  A rejected entry reads nothing
+ *             from the table and its power is a quiet NaN (0x7fc00000); the other entries are unaffected.  bf_peaks_device's and the
+ *             trackers' empty slots (-1) are such entries.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only, one launch, no atomics, no allocation after the first call -- except a
+ *             call with a new adaptive array, which synchronises the device as bf_das_device does; graph-capturable after one warm-up
+ *             call.  No digest is built.  Does not change bf_last_das_variant.
+ * Return 0, or -1 (bf_last_error names the value; nothing enqueued) for: everything bf_miso_device refuses (the stream call:
+ * everything bf_miso_stream_device refuses); count < 1; power_stride < count; d_offsets or d_power null; d_power or d_status
+ * sharing a byte with d_signals, d_prev, d_offsets or each other.  All arguments are checked before device bring-up; the table checks
+ * need the device the table lives on.
+ * bf_plan_das_select: the launch geometry of such a call (no GPU needed), out[0..9] as bf_plan_das; stream_mode != 0 plans the
+ * stream call.  The rows always take the strided layout, so n_chunks may differ from bf_plan_das's for the same sizes. */
+int bf_das_select_device(int algo, const float *d_signals, int m_total, int frames, const int *adaptive_array, int n,
+                         const int *d_offsets, int count, int per_frame, float *d_power, int power_stride, int *d_status, void *stream);
+int bf_das_select_stream_device(int algo, const float *d_signals, int m_total, int frames, int hop, const float *d_prev,
+                                const int *adaptive_array, int n, const int *d_offsets, int count, int per_frame,
+                                float *d_power, int power_stride, int *d_status, void *stream);
+int bf_plan_das_select(int algo, int n, int frames, int count, int max_whole, int stream_mode, int n_cus, long long out[10]);
+
 /* ---- band selection on the time-domain path: one FIR per band on every row of a frame batch, continuous across windows ----
  * The time-domain maps and beams are broadband; delay-and-sum is linear, so ONE filter applied to every microphone row leaves all
  * inter-microphone delays intact: a band-limited map is bf_das_device on filtered frames, band-limited audio is the same filter on

@@ -1383,6 +1383,80 @@ int bf_das_stream_device(int algo, const float* d_signals, int m_total, float* d
     return 0;
 }
 
+// ---------------------------------------------------------------- map values at listed directions
+
+// What both select calls check before device bring-up, after their algorithm.
+static bool select_args_ok(const char* who, const float* d_signals, int m_total, int frames, const float* d_prev, const int* adaptive_array, int n,
+                           const int* d_offsets, int count, int per_frame, const float* d_power, int power_stride, const int* d_status)
+{
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_offsets, "d_offsets"}, {d_power, "d_power"}})) return false;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "count", count, 1) || !need_min(who, "n", n, 1)) return false;
+    if (!need_min(who, "power_stride", power_stride, "count", count) || !need_rows(who, adaptive_array, n, m_total)) return false;
+    const u64 frame_bytes = sat_mul(sat_mul((u64)m_total, (u64)S().sz.n_samples), sizeof(float));
+    const u64 list_bytes = sat_mul(sat_mul((u64)(per_frame ? frames : 1), (u64)count), sizeof(int));
+    return need_disjoint(who, {{d_power, sat_mul(sat_mul((u64)frames, (u64)power_stride), sizeof(float)), "d_power"},
+                               {d_status, sat_mul(sat_mul((u64)frames, (u64)count), sizeof(int)), "d_status"},
+                               {d_signals, sat_mul((u64)frames, frame_bytes), "d_signals"},
+                               {d_prev, frame_bytes, "d_prev"},
+                               {d_offsets, list_bytes, "d_offsets"}}, 2);
+}
+
+// The launch both describe: the list is the direction range, d_power the images.  The adaptive array is already uploaded.
+static bool plan_select_launch(const char* who, int algo, const TableSet& t, bool stream_mode, int n, int m_total, int frames, const float* d_signals, int count,
+                               float* d_power, int power_stride, bf::DasLaunch* L, bf::DasPlan* plan)
+{
+    State& s = S();
+    *L = bf::DasLaunch{};
+    L->algo = algo;
+    L->tab = t.device();
+    L->n_mics = n; L->m_total = m_total; L->n_samples = s.sz.n_samples; L->n_taps = s.sz.n_taps; L->n_dirs = s.sz.dirs();
+    L->dir_begin = 0; L->dir_end = count; L->image_stride = power_stride; L->image_origin = 0; L->frames = frames;
+    L->signals = d_signals; L->images = d_power; L->mics = s.d_mics.p;
+    const char* why = "";
+    if (bf::plan_select(*L, stream_mode, s.n_cus, plan, &why) != 0) { set_error("%s: unsupported shape: %s", who, why); return false; }
+    return true;
+}
+
+int bf_das_select_device(int algo, const float* d_signals, int m_total, int frames, const int* adaptive_array, int n, const int* d_offsets, int count,
+                         int per_frame, float* d_power, int power_stride, int* d_status, void* stream)
+{
+    static const char* who = "bf_das_select_device";
+    Entered in;
+    if (algo == bf::ALGO_FIR_NAIVE) { set_error("%s: algo BF_FIR_NAIVE has no MISO form in the reference", who); return -1; }
+    const int slot = slot_of(algo);
+    if (slot < 0) { set_error("%s: unknown algo %d", who, algo); return -1; }
+    if (!select_args_ok(who, d_signals, m_total, frames, nullptr, adaptive_array, n, d_offsets, count, per_frame, d_power, power_stride, d_status)) return -1;
+    if (!ensure_device()) return -1;
+    const TableSet& t = in.s.tab[slot];
+    if (!t.loaded) { set_error("%s: %s has not been called", who, loader_name(slot)); return -1; }
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    bf::DasLaunch L{};
+    bf::DasPlan plan{};
+    if (!plan_select_launch(who, algo, t, false, n, m_total, frames, d_signals, count, d_power, power_stride, &L, &plan)) return -1;
+    return HIP_RC(bf::launch_select(L, plan, d_offsets, per_frame, t.entries, d_status, as_stream(stream)));
+}
+
+int bf_das_select_stream_device(int algo, const float* d_signals, int m_total, int frames, int hop, const float* d_prev, const int* adaptive_array, int n,
+                                const int* d_offsets, int count, int per_frame, float* d_power, int power_stride, int* d_status, void* stream)
+{
+    static const char* who = "bf_das_select_stream_device";
+    Entered in;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}})) return -1;
+    if (!stream_args_ok(who, algo, m_total, frames, hop, adaptive_array, n)) return -1;
+    if (!select_args_ok(who, d_signals, m_total, frames, d_prev, adaptive_array, n, d_offsets, count, per_frame, d_power, power_stride, d_status)) return -1;
+    if (!ensure_device()) return -1;
+    const int slot = slot_of(algo);
+    const TableSet& t = in.s.tab[slot];
+    if (!stream_table_ok(who, algo, t, slot, hop)) return -1;
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    bf::DasLaunch L{};
+    bf::DasPlan plan{};
+    if (!plan_select_launch(who, algo, t, true, n, m_total, frames, d_signals, count, d_power, power_stride, &L, &plan)) return -1;
+    return HIP_RC(bf::launch_select_stream(L, plan, d_prev, hop, d_offsets, per_frame, t.entries, d_status, as_stream(stream)));
+}
+
 int bf_peak_offsets_device(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, void* stream)
 {
     static const char* who = "bf_peak_offsets_device";
@@ -2043,6 +2117,20 @@ int bf_plan_das(int algo, int n, int frames, int dir_begin, int dir_end, int max
     bf::DasPlan p{};
     const char* why = "";
     if (bf::plan_das(L, n_cus > 0 ? n_cus : 256, &p, &why) != 0) { set_error("bf_plan_das: %s", why); return -1; }
+    out[0] = p.nc; out[1] = p.lead; out[2] = p.row_stride; out[3] = p.mic_chunk; out[4] = p.n_chunks;
+    out[5] = p.waves; out[6] = p.dpw; out[7] = p.tile_dirs; out[8] = p.n_tiles; out[9] = (long long)p.lds_bytes;
+    return 0;
+}
+
+int bf_plan_das_select(int algo, int n, int frames, int count, int max_whole, int stream_mode, int n_cus, long long out[10])
+{
+    Entered in;
+    bf::DasLaunch L{};
+    L.algo = algo; L.n_mics = n; L.m_total = n; L.n_samples = in.s.sz.n_samples; L.n_taps = in.s.sz.n_taps; L.n_dirs = in.s.sz.dirs();
+    L.dir_begin = 0; L.dir_end = count; L.frames = frames; L.tab.max_whole = max_whole;
+    bf::DasPlan p{};
+    const char* why = "";
+    if (bf::plan_select(L, stream_mode != 0, n_cus > 0 ? n_cus : 256, &p, &why) != 0) { set_error("bf_plan_das_select: %s", why); return -1; }
     out[0] = p.nc; out[1] = p.lead; out[2] = p.row_stride; out[3] = p.mic_chunk; out[4] = p.n_chunks;
     out[5] = p.waves; out[6] = p.dpw; out[7] = p.tile_dirs; out[8] = p.n_tiles; out[9] = (long long)p.lds_bytes;
     return 0;

@@ -112,6 +112,17 @@ hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const flo
 hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
                                long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream);
 
+// Map values at listed directions (bf_das_select_device / bf_das_select_stream_device; das_select_kernel): the mean power of the beam at
+// every table offset of a device list, d_offsets int32 [L.frames][count] (per_frame != 0) or [count] for all frames, judged in the kernel
+// as launch_miso_batch judges them (d_status int32 [L.frames][count] or null; a rejected entry's power is NaN).  The launch describes the
+// LIST: L.dir_begin = 0, L.dir_end = count, L.images float32 [L.frames][L.image_stride] with list index b at column b, L.image_origin = 0.
+// `plan` comes from plan_select: the strided layout at every N, tiles of the list.  stream = true sizes the rows for launch_select_stream
+// (pad and lerp; d_prev / hop as launch_stream_maps), false for launch_select (pad, lerp, hybrid, the vectorized FIR).
+int plan_select(const DasLaunch& L, bool stream, int n_cus, DasPlan* plan, const char** why);
+hipError_t launch_select(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int per_frame, long long entries, int* d_status, hipStream_t stream);
+hipError_t launch_select_stream(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int per_frame, long long entries,
+                                int* d_status, hipStream_t stream);
+
 // bf_remove_sources_device (remove_sources.hip; pad and lerp): d_residual = d_signals - c * (adjoint of the delay operator)(beams), rows of the frames
 // named by d_row_slot int32 [m_total] (slot m of the adaptive array, or -1: the row is copied).  d_offsets / d_status / entries as
 // launch_miso_batch; d_beams float32 [frames][beams][beam_stride], rows of rejected offsets never read.  d_residual may equal d_signals.

@@ -246,6 +246,25 @@ int stream_history(int algo, int max_whole)
     return algo == ALGO_PAD ? max_whole : algo == ALGO_LERP ? max_whole + 1 : -1;
 }
 
+// Tiles of a strided launch that has no table affinity to keep (the stream maps, the listed directions): whole wave groups, about four
+// workgroups per CU; a launch too small for that gives every CU a tile.  With one chunk a tile stages its frame once, so more groups per
+// tile save staging; with several chunks every group restages anyway.
+static void tile_strided(DasPlan& p, long long dirs, int frames, int n_cus)
+{
+    const int group = p.waves * p.dpw;
+    const long long work = dirs * frames;
+    long long td;
+    if (work < (long long)n_cus * group) {
+        td = round_up((int)std::max<long long>(1, (work + n_cus - 1) / n_cus), p.dpw);
+    } else {
+        long long k = p.n_chunks > 1 ? 1 : work / ((long long)n_cus * 4 * group);
+        k = std::min<long long>(std::max<long long>(k, 1), 8);
+        td = k * group;
+    }
+    p.tile_dirs = (int)td;
+    p.n_tiles = (int)((dirs + td - 1) / td);
+}
+
 // Maps in stream mode always take the strided layout (lane l owns samples l, l + 64, ..), whatever N: the sizing is plan_das's
 // for that layout -- one 16-wave workgroup with the whole LDS, mic rows (or a chunk of them) beside the per-wave power scratch.
 int plan_stream_maps(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
@@ -258,20 +277,31 @@ int plan_stream_maps(const DasLaunch& L, int n_cus, DasPlan* plan, const char** 
     p.nf = 1;
     if (!size_strided(p, L.n_samples, L.n_mics, round_up(L.tab.max_whole + 1, 4), 0))      // lead >= the history of either flavour
         return fail("one microphone row does not fit in LDS");
-    // Tiles: whole wave groups, about four workgroups per CU; a launch too small for that gives every CU a tile.  With one chunk a
-    // tile stages its frame once, so more groups per tile save staging; with several chunks every group restages anyway.
-    const int group = p.waves * p.dpw;
-    const long long dirs = (long long)(L.dir_end - L.dir_begin), work = dirs * L.frames;
-    long long td;
-    if (work < (long long)n_cus * group) {
-        td = round_up((int)std::max<long long>(1, (work + n_cus - 1) / n_cus), p.dpw);
-    } else {
-        long long k = p.n_chunks > 1 ? 1 : work / ((long long)n_cus * 4 * group);
-        k = std::min<long long>(std::max<long long>(k, 1), 8);
-        td = k * group;
-    }
-    p.tile_dirs = (int)td;
-    p.n_tiles = (int)((dirs + td - 1) / td);
+    tile_strided(p, (long long)(L.dir_end - L.dir_begin), L.frames, n_cus);
+    *plan = p;
+    if (why) *why = "";
+    return 0;
+}
+
+// The listed directions (das_select_kernel) take the strided layout too, whatever N and the algorithm: plan_das's rows for the
+// window-local call (zero columns for the delay and the taps), plan_stream_maps's for the stream call; the LIST [0, L.dir_end) is tiled.
+int plan_select(const DasLaunch& L, bool stream, int n_cus, DasPlan* plan, const char** why)
+{
+    auto fail = [&](const char* msg) { if (why) *why = msg; return -1; };
+    if (stream ? !is_plain(L.algo) : (L.algo != ALGO_PAD && L.algo != ALGO_LERP && L.algo != ALGO_HYBRID && L.algo != ALGO_FIR_VEC))
+        return fail(stream ? "continuous mode exists for pad and lerp only" : "no map at listed directions for this algorithm");
+    if (L.n_samples < 1 || L.n_samples > 1024) return fail("N_SAMPLES must be in [1, 1024]");
+    const bool fir = is_fir(L.algo);
+    if (fir && (L.n_taps < 1 || L.n_taps > 64 || (L.algo == ALGO_FIR_VEC && (L.n_taps % 8) != 0)))
+        return fail("N_TAPS must be in [1, 64] (multiple of 8 for the vectorized FIR)");
+    if (L.n_mics < 1 || L.frames < 1 || L.dir_begin != 0 || L.dir_end < 1) return fail("empty launch");
+    DasPlan p{};
+    p.nf = 1;
+    const int T = fir ? L.n_taps : 0;
+    const int shift = L.algo == ALGO_FIR_VEC ? 0 : L.tab.max_whole;
+    if (!size_strided(p, L.n_samples, L.n_mics, round_up(shift + 1 + T / 2, 4), round_up(T, 4))) return fail("one microphone row does not fit in LDS");
+    if (p.dpw == 4 && L.algo == ALGO_HYBRID && p.nc == 16) p.dpw = 2;   // das_select_kernel<HYBRID, 16, 4> would spill (the value does not depend on dpw)
+    tile_strided(p, L.dir_end, L.frames, n_cus);
     *plan = p;
     if (why) *why = "";
     return 0;

@@ -1,5 +1,6 @@
 // das_strided.hip -- the strided delay-and-sum kernels (lane l owns samples l, l+64, ...): maps (das_mimo_kernel), steered beams
-// (das_miso_kernel) and their continuous-stream twins (stream_map_kernel, stream_beam_kernel).  das_kernels.hip has the overview.
+// (das_miso_kernel), their continuous-stream twins (stream_map_kernel, stream_beam_kernel) and the map at listed directions
+// (das_select_kernel).  das_kernels.hip has the overview.
 #include "das_device.h"
 
 namespace bf {
@@ -444,6 +445,131 @@ __global__ void __launch_bounds__(1024) stream_map_kernel(BF_TABLE_PARAMS, KArgs
     if (filled > 0) flush_powers(scratch, filled, img, a, lane);
 }
 
+// ---- map values at listed directions (bf_das_select_device / bf_das_select_stream_device) ---------------------------------
+// das_mimo_kernel (HIST = false) / stream_map_kernel (HIST = true) with one indirection: a workgroup owns one frame and one tile of
+// the LIST [a.dir_begin, a.dir_end) = [0, count), and the table row of list index b is offsets[b] -- read wave-uniformly and judged
+// as das_miso_kernel judges a beam's offset (1: outside the table, 2: FIR_VEC offset not a multiple of T).  A rejected entry reads
+// nothing from the table and its power is a quiet NaN.  park_squares carries the list index where the map kernels carry the
+// direction, so flush_powers writes out[frame][b]; a value is one wave's sum in microphone order and one lane's in sample order,
+// whatever the tiling, DPW and the wave count are.
+// Prefetch: the entries of a wave's NEXT group are requested when the current group starts (a group later they cost no wait), and
+// the table-row head of item i + 1 before item i is computed, as in das_mimo_kernel.
+struct ListedRow {
+    long long row = 0;   // table row start, in entries (FIR_VEC: in rows of T floats)
+    int verdict = 0;
+};
+
+template <int ALGO>
+__device__ __forceinline__ ListedRow judge_offset(int raw, const KArgs& a, long long entries)
+{
+    ListedRow r;
+    const int off = __builtin_amdgcn_readfirstlane(raw);
+    const int per = ALGO == ALGO_FIR_VEC ? a.n_taps : 1;
+    if (off < 0 || (long long)off + (long long)a.n_mics * per > entries) r.verdict = 1;
+    else if (ALGO == ALGO_FIR_VEC && off % per != 0) r.verdict = 2;
+    r.row = off / per;
+    return r;
+}
+
+template <int ALGO, int NC, int DPW, bool HIST>
+__global__ void __launch_bounds__(1024) das_select_kernel(BF_TABLE_PARAMS, KArgs a, const int32_t* __restrict__ offsets, int per_frame,
+                                                          int* __restrict__ status, long long entries, const float* __restrict__ prev0, int hop, int hist)
+{
+    static_assert(!HIST || ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = (int)(blockDim.x >> 6);
+    const int tile = (int)(blockIdx.x % (unsigned)a.n_tiles);
+    const int frame = (int)(blockIdx.x / (unsigned)a.n_tiles);
+    const int count = a.dir_end;
+    const int tile_begin = tile * a.tile_dirs;
+    if (tile_begin >= count) return;
+    const int tile_end = min(tile_begin + a.tile_dirs, count);
+
+    {
+        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
+        float4* z = reinterpret_cast<float4*>(lds);
+        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+
+    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
+    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
+    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
+    const int32_t* __restrict__ list = offsets + (per_frame ? (size_t)frame * count : 0);
+    float* __restrict__ out = images + (size_t)frame * a.image_stride;
+    int* __restrict__ verdicts = status != nullptr ? status + (size_t)frame * count : nullptr;
+    const int group = nwaves * DPW;
+    float* scratch = lds + a.scratch_off + wave * (a.pbw * a.srow);
+    int filled = 0;   // wave-uniform
+
+    auto item_index = [&](int g0_, int j_) { return g0_ + j_ * nwaves + wave; };
+    auto request_entries = [&](int g0_, int (&raw)[DPW]) {   // every lane loads the same word: the value comes back through readfirstlane
+#pragma unroll
+        for (int j = 0; j < DPW; ++j) raw[j] = item_index(g0_, j) < tile_end ? list[item_index(g0_, j)] : -1;
+    };
+    auto head_of = [&](const ListedRow& r, int m0) {
+        return r.verdict == 0 ? request_row_head<ALGO>(whole, frac, (size_t)r.row + m0, min(a.mic_chunk, a.n_mics - m0), lane) : RowHead();
+    };
+
+    int raw[DPW];
+    request_entries(tile_begin, raw);
+    ListedRow rows[DPW];
+#pragma unroll
+    for (int j = 0; j < DPW; ++j) rows[j] = judge_offset<ALGO>(raw[j], a, entries);
+    RowHead head;
+    if (item_index(tile_begin, 0) < tile_end) head = head_of(rows[0], 0);
+
+    for (int g0 = tile_begin; g0 < tile_end; g0 += group) {
+        request_entries(g0 + group, raw);
+        float acc[DPW][NC];
+#pragma unroll
+        for (int j = 0; j < DPW; ++j)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) acc[j][c] = 0.0f;
+
+        for (int ch = 0; ch < a.n_chunks; ++ch) {
+            const int m0 = ch * a.mic_chunk;
+            const int mc = min(a.mic_chunk, a.n_mics - m0);
+            if (a.n_chunks > 1 || g0 == tile_begin) {
+                if (a.n_chunks > 1 && (ch > 0 || g0 != tile_begin)) __syncthreads();  // previous readers done
+                if constexpr (HIST) stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);
+                else stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
+                __syncthreads();
+            }
+#pragma unroll
+            for (int j = 0; j < DPW; ++j) {
+                const int b = item_index(g0, j);  // wave-uniform
+                // successor of (g0, ch, j): the next entry of this group, its first entry at the next chunk, or the next group's first
+                const bool last = j + 1 == DPW && ch + 1 == a.n_chunks;
+                const int nj = j + 1 == DPW ? 0 : j + 1;
+                const int nm0 = j + 1 == DPW ? (last ? 0 : m0 + a.mic_chunk) : m0;
+                const RowHead cur = head;
+                head = RowHead();
+                if (item_index(last ? g0 + group : g0, nj) < tile_end) head = head_of(last ? judge_offset<ALGO>(raw[0], a, entries) : rows[nj], nm0);
+                if (b < tile_end && rows[j].verdict == 0)
+                    accumulate<ALGO, NC, HIST>(acc[j], lds, a, whole, frac, taps, (size_t)rows[j].row, m0, mc, lane, cur);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DPW; ++j) {
+            const int b = item_index(g0, j);
+            if (b >= tile_end) continue;
+            if (verdicts != nullptr && lane == 0) verdicts[b] = rows[j].verdict;
+            if (rows[j].verdict != 0) {
+                if (lane == 0) out[b] = __int_as_float(0x7fc00000);
+                continue;
+            }
+            park_squares<NC, !HIST>(acc[j], scratch + filled * a.srow, a, b, lane);
+            if (++filled == a.pbw) { flush_powers<!HIST>(scratch, filled, out, a, lane); filled = 0; }
+        }
+#pragma unroll
+        for (int j = 0; j < DPW; ++j) rows[j] = judge_offset<ALGO>(raw[j], a, entries);
+    }
+    if (filled > 0) flush_powers<!HIST>(scratch, filled, out, a, lane);
+}
+
 // Workgroup id = frame * groups + group, one wave per beam, offsets / status / gain / NaN beams as das_miso_kernel's device path.
 template <int ALGO, int NC>
 __global__ void __launch_bounds__(1024) stream_beam_kernel(BF_TABLE_PARAMS, float* __restrict__ beam_out, KArgs a, const int32_t* __restrict__ offsets,
@@ -633,6 +759,67 @@ hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const flo
         case 16: return by_dpw(std::integral_constant<int, 16>());
         default: return hipErrorInvalidValue;
     }
+}
+
+namespace {
+
+// das_select_kernel<ALGO, nc, dpw, HIST> of a plan_select plan; `hist` is 0 for the window-local call.
+template <int ALGO, bool HIST>
+hipError_t launch_select_algo(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, int hist, const int32_t* d_offsets, int per_frame,
+                              long long entries, int* d_status, hipStream_t stream)
+{
+    const KArgs a = make_args(L, plan);
+    auto go = [&](auto kernel) -> hipError_t {
+        return launch_with_lds(kernel, dim3((unsigned)plan.n_tiles * (unsigned)L.frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream, nullptr,
+                               L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a, d_offsets, per_frame, d_status, entries, d_prev, hop, hist);
+    };
+    auto by_dpw = [&](auto nc) -> hipError_t {
+        constexpr int NC = decltype(nc)::value;
+        if (plan.dpw == 1) return go(das_select_kernel<ALGO, NC, 1, HIST>);
+        if constexpr (ALGO == ALGO_HYBRID && NC == 16) {   // four directions' accumulators of 16 segments beside the taps would spill: plan_select gives two
+            if (plan.dpw == 2) return go(das_select_kernel<ALGO, NC, 2, HIST>);
+        } else {
+            if (plan.dpw == 4) return go(das_select_kernel<ALGO, NC, 4, HIST>);
+        }
+        return hipErrorInvalidValue;
+    };
+    switch (plan.nc) {
+        case 1: return by_dpw(std::integral_constant<int, 1>());
+        case 2: return by_dpw(std::integral_constant<int, 2>());
+        case 4: return by_dpw(std::integral_constant<int, 4>());
+        case 8: return by_dpw(std::integral_constant<int, 8>());
+        case 16: return by_dpw(std::integral_constant<int, 16>());
+        default: return hipErrorInvalidValue;
+    }
+}
+
+bool select_launch_ok(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets)
+{
+    return L.frames >= 1 && L.dir_begin == 0 && L.dir_end >= 1 && L.image_origin == 0 && L.image_stride >= L.dir_end && d_offsets != nullptr &&
+           L.images != nullptr && plan.layout == 0;
+}
+
+}  // namespace
+
+hipError_t launch_select(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int per_frame, long long entries, int* d_status, hipStream_t stream)
+{
+    if (!select_launch_ok(L, plan, d_offsets)) return hipErrorInvalidValue;
+    switch (L.algo) {
+        case ALGO_PAD: return launch_select_algo<ALGO_PAD, false>(L, plan, nullptr, 0, 0, d_offsets, per_frame, entries, d_status, stream);
+        case ALGO_LERP: return launch_select_algo<ALGO_LERP, false>(L, plan, nullptr, 0, 0, d_offsets, per_frame, entries, d_status, stream);
+        case ALGO_HYBRID: return launch_select_algo<ALGO_HYBRID, false>(L, plan, nullptr, 0, 0, d_offsets, per_frame, entries, d_status, stream);
+        case ALGO_FIR_VEC: return launch_select_algo<ALGO_FIR_VEC, false>(L, plan, nullptr, 0, 0, d_offsets, per_frame, entries, d_status, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_select_stream(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int per_frame, long long entries,
+                                int* d_status, hipStream_t stream)
+{
+    const int hist = stream_history(L.algo, L.tab.max_whole);
+    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist || !select_launch_ok(L, plan, d_offsets)) return hipErrorInvalidValue;
+    if (L.algo == ALGO_PAD) return launch_select_algo<ALGO_PAD, true>(L, plan, d_prev, hop, hist, d_offsets, per_frame, entries, d_status, stream);
+    return launch_select_algo<ALGO_LERP, true>(L, plan, d_prev, hop, hist, d_offsets, per_frame, entries, d_status, stream);
 }
 
 hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,

@@ -6,7 +6,8 @@ detection box (`focus_beam`, sensorfusion/decider.py:70-88).  `BeamListener` is 
 already in HBM (bf_ingest_device output, FusedPipeline's batch) -> the beams of every frame at any number of offsets in one
 enqueue (bf_miso_device), and `loudest` aims one beam per frame at the frame's loudest direction of a power map without a
 host round trip (bf_peak_offsets_device); `sources` gives up to k beams per frame, one per separated source of the map
-(bf_peaks_device).  `maps` makes the power maps themselves (bf_das_device), `remove` takes beams back out of the frames
+(bf_peaks_device).  `maps` makes the power maps themselves (bf_das_device), `powers` only their values at listed offsets
+(bf_das_select_device), `remove` takes beams back out of the frames
 (bf_remove_sources_device) and `separate` runs the two in a loop -- map, loudest direction, beam, subtract -- so that a source
 under a stronger one's sidelobes is found and heard: time-domain CLEAN.  All only enqueue on the current torch stream, so maps,
 peaks, beams and residuals can be captured as one graph.  Raw beams (mic_gain 0) are bit-identical to the reference's miso_* calls."""
@@ -36,11 +37,14 @@ class BeamListener:
         # the table offset of direction d: d * n, or d * n * N_TAPS floats for the vectorized FIR (miso_convolve_vectorized)
         self.offset_per_dir = self.n * (config.N_TAPS if algo == "fir_vec" else 1)
 
-    def _offsets(self, offsets, frames):
+    def _offsets(self, offsets, frames, shared=False):
+        """[B] or [F, B] offsets, host or device -> int32 cuda [F, B]; shared: a [B] list stays [B] (one list for every frame)."""
         torch = _torch()
         o = offsets if isinstance(offsets, torch.Tensor) else torch.as_tensor(np.asarray(offsets, dtype=np.int32))
         o = o.to(device=self.device, dtype=torch.int32)
         if o.dim() == 1:
+            if shared and o.shape[0] >= 1:
+                return o.contiguous()
             o = o.unsqueeze(0).expand(frames, -1)
         if o.dim() != 2 or o.shape[0] != frames or o.shape[1] < 1:
             raise ValueError("offsets must be [B] or [%d, B], got %s" % (frames, tuple(o.shape)))
@@ -60,6 +64,24 @@ class BeamListener:
         call("bf_miso_device", ALGOS[self.algo], frames.data_ptr(), m_total, F, nat.iptr(self.mics), self.n, offs.data_ptr(), B, float(mic_gain),
              out.data_ptr(), N, status.data_ptr())
         return out, status
+
+    def powers(self, d_frames, offsets):
+        """d_frames float32 cuda [F, M_total, N_SAMPLES]; offsets [B] (one list for every frame) or [F, B] table offsets as listen()
+        takes them -> (power float32 [F, B], status int32 [F, B]): the power map's value at every listed offset, bit for bit what
+        maps() writes for that direction, without the rest of the map (bf_das_select_device).  Status as listen(); a rejected
+        offset -- the -1 of an empty sources() slot -- gives NaN."""
+        return self._powers(check_frames(d_frames), offsets, "bf_das_select_device")
+
+    def _powers(self, frames, offsets, entry, *stream_args):
+        torch = _torch()
+        F, m_total, N = frames.shape
+        offs = self._offsets(offsets, F, shared=True)
+        B = offs.shape[-1]
+        power = torch.empty((F, B), dtype=torch.float32, device=self.device)
+        status = torch.empty((F, B), dtype=torch.int32, device=self.device)
+        call(entry, ALGOS[self.algo], frames.data_ptr(), m_total, F, *stream_args, nat.iptr(self.mics), self.n, offs.data_ptr(), B, int(offs.dim() == 2),
+             power.data_ptr(), B, status.data_ptr())
+        return power, status
 
     def loudest(self, d_power):
         """d_power float32 cuda [F, D] power maps -> int32 cuda [F, 1]: the table offset of each map's loudest direction

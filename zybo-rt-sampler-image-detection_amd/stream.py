@@ -70,6 +70,11 @@ class StreamBeamformer(CarriedBeams, BeamListener):
              offs.data_ptr(), B, float(mic_gain), out.data_ptr(), N, status.data_ptr())
         return out, status
 
+    def powers(self, d_frames, offsets):
+        """As BeamListener.powers -> (power float32 [F, B], status int32 [F, B]): the values maps() writes at the listed offsets
+        (bf_das_select_stream_device).  Does not change the carried state."""
+        return self._powers(self._frames(d_frames), offsets, "bf_das_select_stream_device", self.hop, self._prev_ptr())
+
     def remove(self, *args, **kwargs):
         raise NotImplementedError("StreamBeamformer.remove: stream beams read the previous window, and the adjoint BeamListener.remove applies is "
                                   "that of the zero-prefix delay: it does not match them")
