@@ -541,6 +541,103 @@ int bf_track_boxes_device(const float *d_boxes, const int *d_n_boxes, int frames
                           float conf, int slots, float iou_threshold, int max_age, int min_hits,
                           void *d_state, float *d_tracks, int *d_ids, int *d_match, float *d_live, int *d_counts, void *stream);
 
+/* ---- follow boxes by the camera image: a box of the previous image re-found in the current one by template match ----
+ * The reference's detector (image-detection/src/yolo_smooth_tracking.py, process_video, :87-143) trusts detections above confh = 0.7
+ * and, in a frame that has none, keeps a low-score candidate only if a box of the previous frame can be re-found in the current
+ * image: track_with_correlation (:59-69) takes the previous frame's patch around the box (extract_patch, scale 1.2), locates it with
+ * cv2.matchTemplate(..., TM_CCOEFF_NORMED) inside the current frame's search area (scale 1.5) and reports the moved box and the
+ * correlation.  bf_track_boxes_device bridges a missed detection by a Kalman prediction, which looks at no pixel; this call looks at
+ * the pixels.  bf_smooth_boxes_device below is the hysteresis on top of it.
+ *
+ * d_images  : HIP device pointer, uint8 [frames][height][width][3], the camera batch.
+ * d_prev    : HIP device pointer, uint8 [height][width][3], or NULL.  The previous image of frame f is image f - 1; for f = 0 it is d_prev.
+ * d_boxes   : HIP device pointer, float32 [frames][max_boxes][box_stride], box_stride >= 4, x1, y1, x2, y2 first: a stride of 6 reads
+ *             detector or tracker rows, a stride of 4 d_live and the smoother's state rows.  The boxes of frame f are positions in the
+ *             previous image and are sought in image f.
+ * d_n_boxes : HIP device pointer, int32 [frames], or NULL.  n = clamp(d_n_boxes[f], 0, max_boxes); NULL: n = max_boxes.
+ * t_pct, s_pct : the template and search scales in percent (the reference's 1.2 and 1.5 are 120 and 150), 100 <= t_pct <= s_pct <= 400.
+ * d_moved   : float32 [frames][max_boxes][4];  d_score : float32 [frames][max_boxes];  d_shift : int32 [frames][max_boxes][2], or NULL;
+ * d_status  : int32 [frames][max_boxes].  Every entry of every given output is written by every call.
+ *
+ * Definition.  Integer arithmetic up to the last three float64 operations; `/` on integers truncates (every operand is >= 0 where it
+ * matters).
+ *   1. Row j of frame f is a BOX iff j < n, its four coordinates are finite and of magnitude < 2^20, and with ix = (int)x (truncation
+ *      toward zero, the reference's map(int, box)) w = ix2 - ix1 >= 1 and h = iy2 - iy1 >= 1.  Otherwise status 1.
+ *   2. PATCH(pct):  nw = w * pct / 100;  nh = h * pct / 100;  cx = ix1 + w / 2;  cy = iy1 + h / 2;  columns
+ *      [max(0, cx - nw / 2), min(width, cx + nw / 2)), rows [max(0, cy - nh / 2), min(height, cy + nh / 2)): the reference's extract_patch
+ *      (int(w * 1.2) == w * 120 / 100 and int(w * 1.5) == w * 150 / 100 for every w in 1..8192).
+ *   3. The template is PATCH(t_pct) of the previous image: columns [ta, tb), rows [tc, td), tw = tb - ta, th = td - tc.  The search
+ *      area is PATCH(s_pct) of image f: [sa, sb) x [sc, sd), sw, sh; it contains the template's rectangle because s_pct >= t_pct.  The
+ *      zero displacement is dx0 = ta - sa, dy0 = tc - sc.  tw < 1 or th < 1 (the box is off the image): status 2.  Otherwise f = 0 with
+ *      d_prev NULL: status 4.
+ *   4. Decimation.  q = the smallest integer >= 1 with pw * ph <= BF_MATCH_MAX_PIXELS, pw = ceil(tw / q), ph = ceil(th / q);  P = pw * ph.
+ *      Template samples are the pixels (ta + q i, tc + q j), i < pw, j < ph.  Window positions are dx = (dx0 mod q) + q u <= sw - tw
+ *      and dy = (dy0 mod q) + q v <= sh - th, u, v >= 0: the zero displacement is always one of them.  Window samples are
+ *      (sa + dx + q i, sc + dy + q j).
+ *   5. Over the P samples and the three channels c, as exact integers:  S_T[c], S_I[c] the sums of the template and of the window,
+ *      Q_T, Q_I the sums of squares over all channels, X the sum of the products.  Then
+ *          N = P X - sum_c S_T[c] S_I[c];   A = P Q_T - sum_c S_T[c]^2;   B = P Q_I - sum_c S_I[c]^2
+ *      which is TM_CCOEFF_NORMED as OpenCV publishes it (per-channel means) multiplied through by P.  X <= 16384 * 3 * 255^2 < 2^32
+ *      and |N|, A, B < 2^46: exact in int64, and exactly convertible to float64.
+ *   6. A == 0 (a flat template): status 3.  Otherwise the score of a position is r = B == 0 ? 0.0 : (double)N / sqrt((double)A * (double)B),
+ *      the product, the correctly rounded square root and the correctly rounded division each rounded once.  The match is the
+ *      position with the greatest r, the first one in (dy, dx) row-major order on ties (minMaxLoc's rule).
+ *   7. Status 0:  shift = (dx - dx0, dy - dy0);  moved = (x1 + (float)shift_x, y1 + (float)shift_y, x2 + (float)shift_x,
+ *      y2 + (float)shift_y), float32 additions;  score = (float)r.  Status 3: moved = the box unchanged, score 0, shift 0.  Status 1, 2,
+ *      4: zeros.
+ * Four deliberate differences from the reference's call: (a) it adds max_loc itself to the box; max_loc is measured from the search
+ * area's corner, so its predicted box is offset by (dx0, dy0), about 0.15 of the box, even for a still object: here the shift is
+ * measured from the zero displacement.  (b) Where the template is larger than the search area cv2 raises; here the clipping of both
+ * patches to the image makes that impossible.  (c) Templates above BF_MATCH_MAX_PIXELS pixels are decimated, not refused.  (d) The
+ * score is restated from the published formula rather than computed by cv2, as the heat-map's resize is.
+ * One call over F frames equals F one-frame calls that pass the previous image as d_prev.  The result does not depend on how the
+ * launch tiles the search area.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: one launch, no allocation, no synchronisation, no workspace;
+ *             graph-capturable from the first call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_images, d_boxes, d_moved, d_score or d_status null;
+ * frames < 1; height or width outside [1, BF_MATCH_MAX_SIDE]; max_boxes outside [1, BF_MATCH_MAX_BOXES]; box_stride < 4; t_pct < 100,
+ * s_pct < t_pct or s_pct > 400; frames * max_boxes not fitting an int; no GPU.  All arguments are checked before device bring-up. */
+#define BF_MATCH_MAX_PIXELS 16384      /* template pixels after decimation */
+#define BF_MATCH_MAX_BOXES 1024
+#define BF_MATCH_MAX_SIDE 8192
+int bf_match_boxes_device(const unsigned char *d_images, const unsigned char *d_prev, int frames, int height, int width,
+                          const float *d_boxes, int box_stride, const int *d_n_boxes, int max_boxes, int t_pct, int s_pct,
+                          float *d_moved, float *d_score, int *d_shift, int *d_status, void *stream);
+
+/* ---- the reference's confidence hysteresis (process_video, :100-143), one frame per call ----
+ * d_boxes   : HIP device pointer, float32 [max_boxes][6] = x1, y1, x2, y2, score, cls: one frame of detector rows.
+ * d_n_boxes : HIP device pointer, int32 [1], or NULL (n = max_boxes); clamped to [0, max_boxes].
+ * d_state   : HIP device pointer, bf_smooth_state_words(slots) = 4 + 4 * slots 32-bit words, read and written: word 0 = the number m of
+ *             previous boxes (int32), words 1..3 = 0, then `slots` rows of four float32, the previous frame's kept boxes (rows from m
+ *             on are zeros).  All zero is a fresh stream.
+ * d_moved, d_score, d_status : float32 [slots][4], float32 [slots], int32 [slots]: the results of bf_match_boxes_device run on d_state's
+ *             rows (frames = 1, d_boxes = d_state + 4 words, box_stride = 4, d_n_boxes = d_state, max_boxes = slots).  Previous box p
+ *             TAKES PART iff p < clamp(m, 0, slots) and d_status[p] == 0.
+ * Definition.  A row j < n whose four coordinates are finite, with x2 > x1, y2 > y1 and a finite score, is VALID iff score > conf_high
+ * and a CANDIDATE iff conf_low < score <= conf_high.
+ *   If any row is valid:  d_out = the rows with every non-valid row's score set to 0; the kept rows are the valid ones.
+ *   Otherwise:  a candidate is BOOSTED iff some previous box p that takes part has IoU(d_moved[p], candidate) > iou_threshold OR
+ *   d_score[p] > corr_threshold; a boosted row's score becomes conf_high, every other row's 0; the kept rows are the boosted ones
+ *   (the reference's >= confh).
+ *   IoU is compute_iou (:26-37) in float32, every operation rounded once: iw = max(0, min(x2, x2g) - max(x1, x1g)), ih likewise,
+ *   inter = iw * ih, union = ((x2 - x1) * (y2 - y1) + (x2g - x1g) * (y2g - y1g)) - inter, union > 0 ? inter / union : 0, max(0, v) = v > 0 ? v : 0.
+ *   The first `slots` kept rows' boxes, in row order, become the state's rows and m their number; the kept rows beyond are counted.
+ * The `OR d_score[p] > corr_threshold` arm is the reference's, and it is indiscriminate: one well-correlated previous box boosts EVERY
+ * candidate of the frame, wherever the candidate lies.  A corr_threshold > 1 switches that arm off, so that overlap is required.
+ * d_out     : float32 [max_boxes][6]: coordinates and class pass through unchanged (rows from n on included, with score 0).  A zero
+ *             score is not a box to bf_track_boxes_device and bf_fuse_boxes_device, so d_out feeds both with d_n_boxes = NULL.
+ * d_boosted : int32 [max_boxes], or NULL: 1 for a boosted row.  d_counts : int32 [4], or NULL: valid rows, candidates (boosted ones
+ *             included), boosted rows, kept rows dropped for want of a slot.
+ * stream    : enqueue only, one launch of one workgroup; graph-capturable from the first call.
+ * Returns 0, or -1 for: d_boxes, d_moved, d_score, d_status, d_state or d_out null; max_boxes outside [1, BF_MATCH_MAX_BOXES]; slots
+ * outside [1, BF_SMOOTH_MAX_SLOTS]; conf_low, conf_high, iou_threshold or corr_threshold not finite; no GPU.  All arguments are checked
+ * before device bring-up.  bf_smooth_state_words(slots) returns 4 + 4 * slots, or -1 for slots outside that range (it records no error). */
+#define BF_SMOOTH_MAX_SLOTS 64
+int bf_smooth_state_words(int slots);
+int bf_smooth_boxes_device(const float *d_boxes, const int *d_n_boxes, int max_boxes, float conf_low, float conf_high,
+                           float iou_threshold, float corr_threshold, int slots, const float *d_moved, const float *d_score,
+                           const int *d_status, void *d_state, float *d_out, int *d_boosted, int *d_counts, void *stream);
+
 /* ---- continuous-stream mode of the device path (BF_PAD, BF_LERP): delays read the previous window ----
  * Every other entry point treats a window as if the world began at its first sample: a microphone delayed by p samples gives
  * nothing to the first p outputs (out[p + i] += s[i], zero prefix), as the reference does.  That is the first item of the reference

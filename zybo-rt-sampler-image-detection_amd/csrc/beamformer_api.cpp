@@ -1555,6 +1555,53 @@ int bf_track_boxes_device(const float* d_boxes, const int* d_n_boxes, int frames
                                          d_tracks, d_ids, d_match, d_live, d_counts, as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- boxes followed by the camera image, and the detector's hysteresis
+
+int bf_match_boxes_device(const unsigned char* d_images, const unsigned char* d_prev, int frames, int height, int width, const float* d_boxes, int box_stride,
+                          const int* d_n_boxes, int max_boxes, int t_pct, int s_pct, float* d_moved, float* d_score, int* d_shift, int* d_status, void* stream)
+{
+    static const char* who = "bf_match_boxes_device";
+    static_assert(BF_MATCH_MAX_PIXELS == bf::kMatchMaxPixels && BF_MATCH_MAX_BOXES == bf::kMatchMaxBoxes && BF_MATCH_MAX_SIDE == bf::kMatchMaxSide,
+                  "the header's limits are the kernel's");
+    Entered in;
+    if (!need_ptrs(who, {{d_images, "d_images"}, {d_boxes, "d_boxes"}, {d_moved, "d_moved"}, {d_score, "d_score"}, {d_status, "d_status"}})) return -1;
+    if (!need_min(who, "frames", frames, 1)) return -1;
+    if (!need_min(who, "height", height, 1) || !need_max(who, "height", height, BF_MATCH_MAX_SIDE)) return -1;
+    if (!need_min(who, "width", width, 1) || !need_max(who, "width", width, BF_MATCH_MAX_SIDE)) return -1;
+    if (!need_min(who, "max_boxes", max_boxes, 1) || !need_max(who, "max_boxes", max_boxes, BF_MATCH_MAX_BOXES) || !need_min(who, "box_stride", box_stride, 4)) return -1;
+    if (!need_min(who, "t_pct", t_pct, 100) || !need_min(who, "s_pct", s_pct, "t_pct", t_pct) || !need_max(who, "s_pct", s_pct, 400)) return -1;
+    if ((long long)frames * max_boxes > std::numeric_limits<int>::max()) {
+        set_error("%s: frames * max_boxes = %lld does not fit an int", who, (long long)frames * max_boxes);
+        return -1;
+    }
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_match_boxes(d_images, d_prev, frames, height, width, d_boxes, box_stride, d_n_boxes, max_boxes, t_pct, s_pct, d_moved, d_score,
+                                         d_shift, d_status, as_stream(stream)));
+}
+
+int bf_smooth_state_words(int slots)
+{
+    return slots >= 1 && slots <= BF_SMOOTH_MAX_SLOTS ? 4 + 4 * slots : -1;
+}
+
+int bf_smooth_boxes_device(const float* d_boxes, const int* d_n_boxes, int max_boxes, float conf_low, float conf_high, float iou_threshold, float corr_threshold,
+                           int slots, const float* d_moved, const float* d_score, const int* d_status, void* d_state, float* d_out, int* d_boosted, int* d_counts,
+                           void* stream)
+{
+    static const char* who = "bf_smooth_boxes_device";
+    static_assert(BF_SMOOTH_MAX_SLOTS == bf::kSmoothMaxSlots, "the header's limit is the kernel's");
+    Entered in;
+    if (!need_ptrs(who, {{d_boxes, "d_boxes"}, {d_moved, "d_moved"}, {d_score, "d_score"}, {d_status, "d_status"}, {d_state, "d_state"}, {d_out, "d_out"}})) return -1;
+    if (!need_min(who, "max_boxes", max_boxes, 1) || !need_max(who, "max_boxes", max_boxes, BF_MATCH_MAX_BOXES)) return -1;
+    if (!need_min(who, "slots", slots, 1) || !need_max(who, "slots", slots, BF_SMOOTH_MAX_SLOTS)) return -1;
+    if (!need_finite(who, "conf_low", conf_low) || !need_finite(who, "conf_high", conf_high) || !need_finite(who, "iou_threshold", iou_threshold) ||
+        !need_finite(who, "corr_threshold", corr_threshold))
+        return -1;
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_smooth_boxes(d_boxes, d_n_boxes, max_boxes, conf_low, conf_high, iou_threshold, corr_threshold, slots, d_moved, d_score, d_status,
+                                          static_cast<int*>(d_state), d_out, d_boosted, d_counts, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- band selection on the time-domain path
 
 int bf_band_filter_device(const float* d_signals, int rows, int frames, int hop, const float* d_prev, const float* d_taps, int n_taps, int bands, float* d_out,

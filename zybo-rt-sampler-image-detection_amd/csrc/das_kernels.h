@@ -184,6 +184,22 @@ constexpr int kBoxTrackMaxBoxes = 1024;
 hipError_t launch_track_boxes(const float* d_boxes, const int* d_n_boxes, int frames, int max_boxes, float conf, int slots, float iou_threshold, int max_age,
                               int min_hits, int* d_state, float* d_tracks, int* d_ids, int* d_match, float* d_live, int* d_counts, hipStream_t stream);
 
+// bf_match_boxes_device (patch_match.hip): every box of d_boxes float32 [frames][max_boxes][box_stride] sought in image f of d_images uint8
+// [frames][height][width][3] by the normalised cross-correlation of its patch of image f - 1 (d_prev for f = 0, null = none) -> the moved box,
+// the score, the shift and a status per row.  One launch of frames * max_boxes workgroups, all of a CU's LDS to each; no workspace, no atomics.
+constexpr int kMatchMaxPixels = 16384;
+constexpr int kMatchMaxBoxes = 1024;
+constexpr int kMatchMaxSide = 8192;
+hipError_t launch_match_boxes(const unsigned char* d_images, const unsigned char* d_prev, int frames, int height, int width, const float* d_boxes, int box_stride,
+                              const int* d_n_boxes, int max_boxes, int t_pct, int s_pct, float* d_moved, float* d_score, int* d_shift, int* d_status,
+                              hipStream_t stream);
+// bf_smooth_boxes_device (patch_match.hip): one frame of detector rows and the match results of the previous frame's kept boxes (d_state, 4 + 4 * slots
+// words) -> the rows with the reference's hysteresis applied to their scores, and the new kept boxes in d_state.  One launch of one workgroup.
+constexpr int kSmoothMaxSlots = 64;
+hipError_t launch_smooth_boxes(const float* d_boxes, const int* d_n_boxes, int max_boxes, float conf_low, float conf_high, float iou_threshold, float corr_threshold,
+                               int slots, const float* d_moved, const float* d_score, const int* d_status, int* d_state, float* d_out, int* d_boosted,
+                               int* d_counts, hipStream_t stream);
+
 // bf_band_filter_device (band_filter.hip): `bands` FIRs of n_taps taps (d_taps float32 [bands][n_taps]) on every row of d_signals float32
 // [frames][rows][n_samples] -> d_out float32 [bands][frames][rows][n_samples].  The n_taps - 1 samples before a row come from the
 // frame before it (`hop` samples earlier; d_prev float32 [rows][n_samples] for frame 0, null = silence), hop 0 = zeros for every frame.

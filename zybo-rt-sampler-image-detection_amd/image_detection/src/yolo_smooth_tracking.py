@@ -7,7 +7,13 @@ reference's predict call or float16 -- and the head decode + candidate selection
 weights are not in its repository) a seeded random-init network is used.  The SORT tracking of
 `process_video_track_boxes_only` (:275-347; sort/sort.py, GPL, is not vendored) is `boxtrack.BoxTracker` on `detect`'s output:
 bf_track_boxes_device, written from the published algorithm, one launch on the device.  The OpenCV drawing of that function stays
-with the reference; `split_detections` is its banding logic."""
+with the reference; `split_detections` is its banding logic.
+
+The rule the file is named for -- `process_video` (:87-143): detections above 0.7 are trusted, and a frame without one keeps a
+low-score candidate only if `track_with_correlation` (:59-69) re-finds a box of the previous frame in the current image -- is
+`smooth.SmoothDetections` on `detect`'s output and the camera batch: bf_match_boxes_device (the template match, on the device's
+packed byte dot product) and bf_smooth_boxes_device (the hysteresis), one launch each per frame; `FusedPipeline.smooth` forwards to
+it.  include/beamformer_hip.h holds both definitions and the deliberate differences from the reference's call."""
 import ctypes as C
 import os
 

@@ -65,6 +65,12 @@ class FusedPipeline:
         `focus` takes as boxes with counts None (tracks, ids, match, live, counts)."""
         return tracker.update(boxes, counts)
 
+    def smooth(self, d_camera, boxes, counts, smoother):
+        """The camera batch with step's boxes and counts -> smoother.update (a smooth.SmoothDetections): the reference's confidence
+        hysteresis, low-score rows kept only where the previous frame's boxes are re-found in the image; its `out` feeds `track`
+        and `focus` with counts None (out, boosted, counts, moved, score)."""
+        return smoother.update(d_camera, boxes, counts)
+
     def focus(self, power, boxes, counts, fusion, sources=None):
         """step's power maps, boxes and counts -> fusion.focus (a fuse.SensorFusion) at this pipeline's frame size: per box the
         loudest direction under it as a table offset for listen(), per source of `sources` the box it lies in."""
