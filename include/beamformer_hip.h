@@ -934,6 +934,63 @@ int bf_mvdr_learn_device(const float *d_signals, int m_total, int frames, const 
                          double *d_snap, double *d_cov, double *d_chol, double *d_gains,
                          float *d_taps, int *d_status, int *d_fallback, void *stream);
 
+/* ---- the output stage: rational sample-rate conversion on the device, beams at a sound card's rate ----
+ * Every listening path ends in float32 rows at the array's own rate (48828 Hz, an FPGA clock divider's by-product), which no sound card,
+ * codec or file format takes.  This call converts the rows of a window stream by up / down (48828 -> 48000 Hz is 4000 / 4069) with a
+ * polyphase FIR, continuous across windows and across calls, to float32 and / or interleaved 16-bit PCM.  Its phase lives on the device,
+ * so a captured graph keeps converting correctly when it is replayed.  The configured sizes (bf_configure) and the loaded tables play no
+ * part: the window length is the argument n.
+ * d_in      : HIP device pointer, float32 [frames][rows][in_stride], in_stride >= n: what bf_miso_device / bf_miso_stream_device /
+ *             bf_filter_sum_device write ([frames][beams][N_SAMPLES]).  A flat stream is frames = 1, hop = 0, n = its length.
+ * d_prev    : HIP device pointer, float32 [rows][in_stride], or NULL: the last window of the call before.
+ * d_taps    : HIP DEVICE pointer, float32 [up][n_taps]: h[p][t], tap t of phase p (audio_out.design_resampler makes one).
+ * d_state   : HIP device pointer, int32 [4], read and written: it carries from call to call.  All zeros: the start of a stream.
+ * Definition (builder-defined; the reference has no rate conversion).  Let len = hop > 0 ? hop : n, first = n - len, S = frames * len,
+ * L = up, M = down, T = n_taps.
+ *   Stream.  The call's input stream of row r is
+ *       x[s] = d_in[s / len][r][first + s % len]                        for 0 <= s < S
+ *       x[s] = d_prev[r][n + s], or 0.0f when d_prev is NULL            for -(T-1) <= s < 0
+ *     -- the last `hop` samples of every window, the samples CarriedBeams.audio joins, behind the end of the window before.
+ *   State.  d_state[0] = o >= 0 is the input index, relative to this call's x[0], of the next output; d_state[1] = phi, 0 <= phi < L,
+ *     its phase.  d_state[2..3] are reserved and written 0.
+ *   Outputs.  For k = 0, 1, .. with a_k = phi + k * M (64-bit): i_k = o + a_k / L, p_k = a_k % L.  Output k exists while i_k < S:
+ *       count = o < S ? ceil(((S - o) * L - phi) / M) : 0
+ *       y[r][k] = acc_T,   acc_0 = 0.0f,   acc_{t+1} = fmaf(h[p_k][t], x[i_k - t], acc_t)   for t = 0 .. T-1
+ *     in that order, one float32 rounding per step (a single-rounding fused multiply-add, libm's fmaf).  Subnormals are kept.
+ *   Gain.  v = y * gain, one float32 multiply.
+ *   Float output.  d_out float32 [rows][out_stride]: d_out[r][k] = v for k < count, 0.0f for count <= k < cap with
+ *     cap = bf_resample_capacity(S, L, M) = ceil(S * L / M) >= count; elements past cap are left untouched.
+ *   PCM output.  d_pcm int16, interleaved [cap][rows]: d_pcm[k * rows + r] = clamp(rintf(v * 32768.0f), -32768, 32767), ties to even; a NaN
+ *     gives 0; slots count <= k < cap get 0.  A sample is CLIPPED if v is NaN or the rounded value left the range (1.0f gives 32767 and
+ *     is clipped, -1.0f gives -32768 and is not).  d_clip int32 [rows]: d_clip[r] is INCREASED by the row's clipped samples -- a meter
+ *     that accumulates over calls; the caller zeroes it.  (Integer atomic adds: a sum of integers does not depend on the order.)
+ *   Either of d_out and d_pcm may be NULL, not both; d_clip may be NULL, and is not touched by a call without d_pcm.
+ *   New state.  With A = phi + count * M: o' = o + A / L - S, phi' = A % L (for o >= S: count = 0, o' = o - S, phi' = phi).
+ *   d_count int32 [2] = (count, status).  A state with o < 0 or phi outside [0, L) gives status = 1, count = 0 and all-zero outputs
+ *     (slots [0, cap)); the state and d_clip are left as they were.  Otherwise status = 0.
+ * Two calls on F1 and F - F1 windows, the second with the first's state and last window, give the outputs of one call on F windows bit
+ * for bit.  The result does not depend on the internal blocking (a workgroup takes a run of consecutive outputs of one row and stages
+ * their contiguous input span in LDS), on the alignment of the pointers, on T % 4 or on out_stride: taps past the last are skipped,
+ * not multiplied by zero.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: two launches -- the conversion, which only reads d_state, then one thread
+ *             that writes d_state and d_count; no allocation, no workspace, no synchronisation; graph-capturable from the first call,
+ *             and a replay advances the state like any other call.  Nothing else is carried on the device: the sample history is the
+ *             caller's previous window.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_in, d_taps, d_state or d_count null; d_out and d_pcm both
+ * null; rows, frames, n, up, down or n_taps < 1; up > BF_RESAMPLE_MAX_PHASES; n_taps > BF_RESAMPLE_MAX_TAPS; up * n_taps > 1 << 20;
+ * down > 64 * up; hop < 0; hop > n; in_stride < n; n_taps - 1 > len (the history must be stream samples); frames * len > INT_MAX / 2;
+ * cap > INT_MAX; d_out given with out_stride < cap; gain not finite; a written range (d_out, d_pcm, d_clip, d_state, d_count; each
+ * from its first element to the last one touched) sharing a byte with a read range (d_in, d_prev, d_taps) or with another written
+ * one; no GPU.  All arguments are checked before device bring-up.
+ * bf_resample_capacity: ceil(samples_in * up / down), the slots a call on samples_in stream samples fills; -1 for samples_in < 0, up or
+ * down < 1, or a product past 64 bits.  No GPU needed. */
+#define BF_RESAMPLE_MAX_PHASES 16384
+#define BF_RESAMPLE_MAX_TAPS   128
+long long bf_resample_capacity(long long samples_in, int up, int down);
+int bf_resample_device(const float *d_in, int rows, int frames, int n, int in_stride, int hop, const float *d_prev,
+                       const float *d_taps, int up, int down, int n_taps, int *d_state, float gain,
+                       float *d_out, int out_stride, short *d_pcm, int *d_clip, int *d_count, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

@@ -274,9 +274,9 @@ bool need_dir_range(const char* who, int dir_begin, int dir_end, int n_dirs, int
 }
 
 // A window may continue the one before it by `hop` samples, and no further than its own length.
-bool need_hop_max(const char* who, int hop, int N)
+bool need_hop_max(const char* who, int hop, int N, const char* window = "N_SAMPLES")   // (window: what the call names its window length)
 {
-    if (hop > N) { set_error("%s: hop = %d > N_SAMPLES = %d (the windows would leave gaps in the stream)", who, hop, N); return false; }
+    if (hop > N) { set_error("%s: hop = %d > %s = %d (the windows would leave gaps in the stream)", who, hop, window, N); return false; }
     return true;
 }
 
@@ -1794,6 +1794,54 @@ int bf_mvdr_learn_device(const float* d_signals, int m_total, int frames, const 
     return HIP_RC(bf::launch_mvdr_learn(d_signals, m_total, frames, N, in.s.d_mics.p, n, seg_first, seg_hop, segs, d_window, d_weights, forget, d_tau, dirs, d_offsets,
                                         sources, offset_per_dir, n_taps, bin_lo, bin_hi, loading, d_acc, d_mass, d_used, d_snap, d_cov, d_chol, d_gains, d_taps,
                                         d_status, d_fallback, as_stream(stream)));
+}
+
+// ---------------------------------------------------------------- the output stage: beams at a sound card's rate
+
+long long bf_resample_capacity(long long samples_in, int up, int down) { return bf::resample_capacity(samples_in, up, down); }
+
+int bf_resample_device(const float* d_in, int rows, int frames, int n, int in_stride, int hop, const float* d_prev, const float* d_taps, int up, int down, int n_taps,
+                       int* d_state, float gain, float* d_out, int out_stride, short* d_pcm, int* d_clip, int* d_count, void* stream)
+{
+    static const char* who = "bf_resample_device";
+    static_assert(BF_RESAMPLE_MAX_PHASES == bf::kResampleMaxPhases && BF_RESAMPLE_MAX_TAPS == bf::kResampleMaxTaps, "the header's limits are the kernel's");
+    constexpr int kMaxTable = 1 << 20, kMaxStream = std::numeric_limits<int>::max() / 2;
+    Entered in;
+    if (!need_ptrs(who, {{d_in, "d_in"}, {d_taps, "d_taps"}, {d_state, "d_state"}, {d_count, "d_count"}})) return -1;
+    if (!d_out && !d_pcm) { set_error("%s: d_out and d_pcm are both null", who); return -1; }
+    if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "n", n, 1) || !need_min(who, "up", up, 1) ||
+        !need_min(who, "down", down, 1) || !need_min(who, "n_taps", n_taps, 1))
+        return -1;
+    if (!need_max(who, "up", up, BF_RESAMPLE_MAX_PHASES) || !need_max(who, "n_taps", n_taps, BF_RESAMPLE_MAX_TAPS)) return -1;
+    if (up * n_taps > kMaxTable) { set_error("%s: up * n_taps = %d > %d", who, up * n_taps, kMaxTable); return -1; }
+    if (down > 64LL * up) { set_error("%s: down = %d > 64 * up = %d", who, down, 64 * up); return -1; }
+    if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, n, "n") || !need_min(who, "in_stride", in_stride, "n", n)) return -1;
+    const int len = hop > 0 ? hop : n;
+    if (n_taps - 1 > len) {
+        set_error("%s: the filter needs n_taps - 1 = %d samples of history but a window adds %d to the stream (the history must be stream samples)", who,
+                  n_taps - 1, len);
+        return -1;
+    }
+    const long long S = (long long)frames * len;
+    if (S > kMaxStream) { set_error("%s: frames * %s = %lld > %d", who, hop > 0 ? "hop" : "n", S, kMaxStream); return -1; }
+    const long long cap = bf::resample_capacity(S, up, down);
+    if (cap > std::numeric_limits<int>::max()) { set_error("%s: cap = %lld does not fit an int", who, cap); return -1; }
+    if (d_out && !need_min(who, "out_stride", out_stride, "cap", (int)cap)) return -1;
+    if (!need_finite(who, "gain", gain)) return -1;
+    // every span runs from its first element to the last one touched: the floats behind a last row's n (or cap) are not part of it
+    const u64 in_rows = (u64)frames * rows;
+    if (!need_disjoint(who, {{d_out, sat_add(sat_mul(sat_mul((u64)rows - 1, (u64)out_stride), sizeof(float)), (u64)cap * sizeof(float)), "d_out"},
+                             {d_pcm, sat_mul((u64)cap * rows, sizeof(short)), "d_pcm"},
+                             {d_clip, (u64)rows * sizeof(int), "d_clip"},
+                             {d_state, 4 * sizeof(int), "d_state"},
+                             {d_count, 2 * sizeof(int), "d_count"},
+                             {d_in, sat_add(sat_mul(sat_mul(in_rows - 1, (u64)in_stride), sizeof(float)), (u64)n * sizeof(float)), "d_in"},
+                             {d_prev, sat_add(sat_mul(sat_mul((u64)rows - 1, (u64)in_stride), sizeof(float)), (u64)n * sizeof(float)), "d_prev"},
+                             {d_taps, (u64)up * n_taps * sizeof(float), "d_taps"}}, 5))   // five written ranges (the state and the meter among them), three read
+        return -1;
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_resample(d_in, rows, frames, n, in_stride, hop, d_prev, d_taps, up, down, n_taps, d_state, gain, d_out, out_stride, d_pcm, d_clip,
+                                      d_count, as_stream(stream)));
 }
 
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)

@@ -255,6 +255,19 @@ hipError_t launch_mvdr_learn(const float* d_signals, int m_total, int frames, in
                              double* d_snap, double* d_cov, double* d_chol, double* d_gains, float* d_taps, int32_t* d_status, int32_t* d_fallback,
                              hipStream_t stream);
 
+// bf_resample_device (resample.hip): the rows of a window stream (d_in float32 [frames][rows][in_stride], the last hop samples of every
+// window of n, hop 0 = whole windows; d_prev float32 [rows][in_stride], the window before, null = silence) converted by up / down through
+// the polyphase table d_taps float32 [up][n_taps] -> d_out float32 [rows][out_stride] and / or d_pcm int16 [cap][rows], cap =
+// resample_capacity(frames * len, up, down).  d_state int32 [4] carries (input index of the next output, phase, 0, 0) between calls;
+// d_clip int32 [rows] is added to (PCM samples out of range), d_count int32 [2] = (count, status).  Two launches: the conversion, which
+// only reads the state, then one thread that advances it.  No workspace.  The written ranges must not overlap the read ones.
+constexpr int kResampleMaxPhases = 16384;
+constexpr int kResampleMaxTaps = 128;
+long long resample_capacity(long long samples_in, int up, int down);      // ceil(samples_in * up / down); -1 on bad arguments
+hipError_t launch_resample(const float* d_in, int rows, int frames, int n, int in_stride, int hop, const float* d_prev, const float* d_taps, int up, int down,
+                           int n_taps, int32_t* d_state, float gain, float* d_out, int out_stride, short* d_pcm, int32_t* d_clip, int32_t* d_count,
+                           hipStream_t stream);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);

@@ -75,3 +75,8 @@ class FusedPipeline:
         """step's power maps, boxes and counts -> fusion.focus (a fuse.SensorFusion) at this pipeline's frame size: per box the
         loudest direction under it as a table offset for listen(), per source of `sources` the box it lies in."""
         return fusion.focus(power, boxes, counts, sources=sources, image_size=(self.size, self.size))
+
+    def audio_out(self, out, ao):
+        """listen's beams [F, B, N_SAMPLES] -> ao.push (an audio_out.AudioOut): the beams at a sound card's rate, float32 and 16-bit PCM,
+        continuous across batches (audio, pcm, count)."""
+        return ao.push(out)
