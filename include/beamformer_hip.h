@@ -1167,6 +1167,20 @@ int bf_conv1x1_cat_nhwc_f16_device(const void *d_x1, int ld1, int c1, int up1, c
                                    int ldy, const void *d_res, int ldr, int batch, int h, int w, int c, int n, int silu, void *stream);
 int bf_conv1x1_cat_nhwc_f32_device(const void *d_x1, int ld1, int c1, int up1, const void *d_x2, int ld2, const void *d_w, const float *d_bias, void *d_y,
                                    int ldy, const void *d_res, int ldr, int batch, int h, int w, int c, int n, int silu, void *stream);
+/*   bf_plan_conv2d: what a convolution call like the above would launch (no GPU needed).  The layer as the entry points take it: elem_bytes 2 (float16) or
+ *       4 (float32); batch, h, w, c, n, kh, kw, stride, pad; ldy; has_res != 0 and ldr for a residual; the sources as bf_conv1x1_cat_nhwc_* names them
+ *       (c1, ld1, up1, has_x2 != 0, ld2 -- c1 = ld1 = c, up1 = has_x2 = 0 for the one dense source of bf_conv2d_nhwc_*); misaligned: bit 0 / 1 / 2 / 3 / 4 set
+ *       when d_x / d_w / d_x2 / d_y / d_res is NOT 16-byte aligned (0: all are).  use_dma_kernel / f32_mode: the two process switches above as a setter
+ *       would store them, < 0 = as they stand now; n_cus: compute units of the device (<= 0: 256).
+ *       out[0..15] = elem_bytes, family (0 register-staged, 1 LDS-DMA, 2 patch kernel), tile pixels (bm), tile channels (bn), 16-byte chunks per staged
+ *       row (4 or 8; 0 for the patch kernel), virtual concatenation (every 1x1 / stride 1 / unpadded layer), bfloat16 split, fast window taps, 16-byte
+ *       store epilogue, grid x, grid y, dynamic LDS bytes (the patch kernel; 0 otherwise), $BF_CONV_ROW / $BF_CONV_TAP / $BF_CONV_PATCH as the
+ *       process read them at its first plan (0 / 1 / -1 when unset), n_cus.  Returns 0, or -1 with bf_last_error for a layer the entry points refuse
+ *       (out untouched).
+ *   bf_last_conv2d_plan: the same array as the most recent convolution launch of this process dispatched on it (-1 before the first). */
+int bf_plan_conv2d(int elem_bytes, int batch, int h, int w, int c, int n, int kh, int kw, int stride, int pad, int ldy, int has_res, int ldr, int c1, int ld1,
+                   int up1, int has_x2, int ld2, int misaligned, int use_dma_kernel, int f32_mode, int n_cus, long long out[16]);
+int bf_last_conv2d_plan(long long out[16]);
 /*   bf_letterbox_bgr8_device: what ultralytics' predict does to a frame before the network (yolo_smooth_tracking.py:13-23): d_frame uint8 [h][w][3]
  *       resized with cv2.resize(INTER_LINEAR) semantics (8-bit fixed-point bilinear, half-pixel centres) to new_w x new_h and placed at (top, left) of
  *       d_out uint8 [out_h][out_w][3], whose other pixels get the border value (114 in ultralytics).  new_h == h and new_w == w copies. */

@@ -505,3 +505,60 @@ def test_plan_das_refuses_taps(native, lib):
         assert lib.bf_plan_das(native.HYBRID, M, 1, 0, D, 0, 256, out) == 0 and _err(lib) == ""
     finally:
         assert lib.bf_configure(M, N, X, Y, T) == 0
+
+
+# ------------------------------------------------------------------ the convolutions' planner
+
+def _plan_conv(lib, out, eb=2, batch=1, h=8, w=8, c=32, n=32, kh=3, kw=3, stride=1, pad=1, ldy=32, has_res=0, ldr=0, c1=None, ld1=None, up1=0, has_x2=0, ld2=0,
+               misaligned=0, dma=1, mode=1, n_cus=256):
+    return lib.bf_plan_conv2d(eb, batch, h, w, c, n, kh, kw, stride, pad, ldy, has_res, ldr, c if c1 is None else c1, c if ld1 is None else ld1, up1, has_x2, ld2,
+                              misaligned, dma, mode, n_cus, out)
+
+
+@pytest.mark.parametrize("eb", [2, 4])
+def test_plan_conv2d_refuses_what_the_entry_points_refuse(lib, eb):
+    """bf_plan_conv2d runs the entry points' own argument checks (one copy of them), so a refused layer gives -1, the same sentence with the planner's
+    name in front, and an untouched array; bf_last_conv2d_plan has nothing to report in a process that launched no convolution."""
+    E, name = 16 // eb, "bf_plan_conv2d"
+    out = (C.c_longlong * 16)(*([-7] * 16))
+    sizes = name + ": batch %d, %d x %d, window %d x %d, stride %d, pad %d"
+    src = (name + ": sources of %d (pitch %d%s) + %d (pitch %d) channels for 32: whole 16-byte chunks of " + str(E) + " elements, 16-byte aligned; an upsampled "
+           "source needs even h and w")
+    one = dict(kh=1, kw=1, pad=0)
+    for kwargs, text in [
+        (dict(batch=0), sizes % (0, 8, 8, 3, 3, 1, 1)),
+        (dict(n=0), sizes % (1, 8, 8, 3, 3, 1, 1)),
+        (dict(stride=0), sizes % (1, 8, 8, 3, 3, 0, 1)),
+        (dict(h=2, kh=5), sizes % (1, 2, 8, 5, 3, 1, 1)),
+        (dict(c=2), CHANNELS % (name, 2, 3, 1, 1, 8, E)),
+        (dict(c=24), CHANNELS % (name, 24, 3, 1, 1, 8, E)),
+        (dict(ldy=31), name + ": row strides 31 / 0 under 32 output channels"),
+        (dict(ldy=64, has_res=1, ldr=16), name + ": row strides 64 / 16 under 32 output channels"),
+        (dict(misaligned=1), name + ": x and w must be 16-byte aligned"),
+        (dict(misaligned=2), name + ": x and w must be 16-byte aligned"),
+        (dict(one, c1=E // 2, ld1=16, has_x2=1, ld2=16), src % (E // 2, 16, "", 32 - E // 2, 16)),
+        (dict(one, c1=16, ld1=18, has_x2=1, ld2=16), src % (16, 18, "", 16, 16)),
+        (dict(one, c1=16, ld1=16, has_x2=0, ld2=16), src % (16, 16, "", 16, 16)),
+        (dict(one, c1=16, ld1=16, has_x2=1, ld2=8), src % (16, 16, "", 16, 8)),
+        (dict(one, c1=16, ld1=16, has_x2=1, ld2=16, misaligned=4), src % (16, 16, "", 16, 16)),
+        (dict(one, c1=16, ld1=16, has_x2=1, ld2=16, up1=1, h=7), src % (16, 16, ", upsampled", 16, 16)),
+        (dict(c1=16, ld1=16, has_x2=1, ld2=16), name + ": two sources / a pitch / upsampling under a 3 x 3 window, stride 1, pad 1: 1x1 layers only"),
+        (dict(one, batch=3, h=32768, w=32768), name + ": the launch refuses this layer (invalid argument)"),          # more than 2^31 - 1 pixels
+    ]:
+        _refused(lib, _plan_conv(lib, out, eb=eb, **kwargs), text)
+        assert list(out) == [-7] * 16
+    _refused(lib, _plan_conv(lib, out, eb=3), name + ": element size 3 (2 = float16, 4 = float32)")
+    _refused(lib, _plan_conv(lib, None, eb=eb), name + ": out is null")
+    if eb == 2:
+        _refused(lib, _plan_conv(lib, out, eb=2, c=4, kw=2, kh=2, pad=0, stride=1), CHANNELS % (name, 4, 2, 1, 0, 8, E))
+    assert list(out) == [-7] * 16
+    _refused(lib, lib.bf_last_conv2d_plan(None), "bf_last_conv2d_plan: out is null")
+    if lib.bf_last_conv2d_plan(out) == -1:                 # (0 where GPU tests of the same process launched one before this test)
+        assert _err(lib) == "bf_last_conv2d_plan: no convolution was launched in this process" and list(out) == [-7] * 16
+    else:
+        assert out[0] in (2, 4) and out[1] in (0, 1, 2)
+    # the same layer, taken: the switches as given, < 0 as they stand (the library's defaults: LDS-DMA, the split)
+    assert _plan_conv(lib, out, eb=eb) == 0 and _err(lib) == "" and list(out)[:9] == [eb, 1, 128, 32, 4, 0, int(eb == 4), 1, 1]
+    assert _plan_conv(lib, out, eb=eb, dma=-1, mode=-1) == 0 and list(out)[:9] == [eb, 1, 128, 32, 4, 0, int(eb == 4), 1, 1]
+    assert _plan_conv(lib, out, eb=eb, dma=0) == 0 and list(out)[:9] == [eb, 0, 128, 32, 4, 0, 0, 0, 1]
+    assert _plan_conv(lib, out, eb=eb, misaligned=8) == 0 and list(out)[8] == 0          # an output off 16 bytes: the scalar store epilogue

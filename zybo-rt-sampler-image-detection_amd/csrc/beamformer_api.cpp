@@ -2123,37 +2123,100 @@ int bf_fd_gemm_f32_mode(int mode) { return bf::gemm_f32_mode(mode); }
 int bf_conv2d_weight_row(int kh, int kw, int c) { return kh > 0 && kw > 0 && c > 0 ? bf::conv_weight_row(2, kh, kw, c) : -1; }
 int bf_conv2d_weight_row_f32(int kh, int kw, int c) { return kh > 0 && kw > 0 && c > 0 ? bf::conv_weight_row(4, kh, kw, c) : -1; }
 
+// The argument checks of the convolution entry points and of bf_plan_conv2d (pointers as "not 16-byte aligned" flags: bf::kConvMisaligned*).
+static bool conv2d_args_ok(const char* who, int eb, int batch, int h, int w, int c, int n, int kh, int kw, int stride, int pad, int ldy, bool has_res, int ldr,
+                           unsigned misaligned, bool cat, bool has_x2, int c1, int ld1, int ld2, int up1)
+{
+    const int E = 16 / eb;
+    if (batch < 1 || h < 1 || w < 1 || n < 1 || kh < 1 || kw < 1 || stride < 1 || pad < 0 || h + 2 * pad < kh || w + 2 * pad < kw) {
+        set_error("%s: batch %d, %d x %d, window %d x %d, stride %d, pad %d", who, batch, h, w, kh, kw, stride, pad);
+        return false;
+    }
+    if (c < 4 || (c & (c - 1)) != 0 || ((kw * c) % E) != 0 || (c < E && ((stride & 1) || (pad & 1) || (w & 1)))) {
+        set_error("%s: %d input channels, window width %d, stride %d, pad %d, width %d: channels must be a power of two >= 4 with "
+                  "kw * c a multiple of %d; float16 with 4 channels needs even stride, pad and width", who, c, kw, stride, pad, w, E);
+        return false;
+    }
+    if (ldy < n || (has_res && ldr < n)) { set_error("%s: row strides %d / %d under %d output channels", who, ldy, ldr, n); return false; }
+    if (misaligned & (bf::kConvMisalignedX | bf::kConvMisalignedW)) { set_error("%s: x and w must be 16-byte aligned", who); return false; }
+    if (cat) {
+        if (c1 < E || c1 > c || (c1 % E) || (ld1 % E) || ld1 < c1 || (c1 < c && (!has_x2 || (ld2 % E) || ld2 < c - c1 || (misaligned & bf::kConvMisalignedX2))) ||
+            (up1 && ((h & 1) || (w & 1)))) {
+            set_error("%s: sources of %d (pitch %d%s) + %d (pitch %d) channels for %d: whole 16-byte chunks of %d elements, 16-byte aligned; an upsampled "
+                      "source needs even h and w", who, c1, ld1, up1 ? ", upsampled" : "", c - c1, ld2, c, E);
+            return false;
+        }
+    }
+    return true;
+}
+
+static unsigned conv2d_misaligned(const void* x, const void* w, const void* x2, const void* y, const void* res)
+{
+    const auto bit = [](const void* p, unsigned b) { return (reinterpret_cast<uintptr_t>(p) & 15) ? b : 0u; };
+    return bit(x, bf::kConvMisalignedX) | bit(w, bf::kConvMisalignedW) | bit(x2, bf::kConvMisalignedX2) | bit(y, bf::kConvMisalignedY) | bit(res, bf::kConvMisalignedRes);
+}
+
 static int conv2d_checked(const char* who, int eb, const void* d_x, const void* d_w, const float* d_bias, void* d_y, int batch, int h, int w, int c, int n, int kh,
                           int kw, int stride, int pad, int silu, int ldy, const void* d_res, int ldr, void* stream, bool cat = false, const void* d_x2 = nullptr,
                           int c1 = 0, int ld1 = 0, int ld2 = 0, int up1 = 0)
 {
     std::lock_guard<std::mutex> lock(S().mu);
-    const int E = 16 / eb;
     if (!d_x || !d_w || !d_y) { set_error("%s: null pointer", who); return -1; }
-    if (batch < 1 || h < 1 || w < 1 || n < 1 || kh < 1 || kw < 1 || stride < 1 || pad < 0 || h + 2 * pad < kh || w + 2 * pad < kw) {
-        set_error("%s: batch %d, %d x %d, window %d x %d, stride %d, pad %d", who, batch, h, w, kh, kw, stride, pad);
-        return -1;
-    }
-    if (c < 4 || (c & (c - 1)) != 0 || ((kw * c) % E) != 0 || (c < E && ((stride & 1) || (pad & 1) || (w & 1)))) {
-        set_error("%s: %d input channels, window width %d, stride %d, pad %d, width %d: channels must be a power of two >= 4 with "
-                  "kw * c a multiple of %d; float16 with 4 channels needs even stride, pad and width", who, c, kw, stride, pad, w, E);
-        return -1;
-    }
-    if (ldy < n || (d_res && ldr < n)) { set_error("%s: row strides %d / %d under %d output channels", who, ldy, ldr, n); return -1; }
-    if ((reinterpret_cast<uintptr_t>(d_x) & 15) || (reinterpret_cast<uintptr_t>(d_w) & 15)) { set_error("%s: x and w must be 16-byte aligned", who); return -1; }
-    if (cat) {
-        if (c1 < E || c1 > c || (c1 % E) || (ld1 % E) || ld1 < c1 || (c1 < c && (!d_x2 || (ld2 % E) || ld2 < c - c1 || (reinterpret_cast<uintptr_t>(d_x2) & 15))) ||
-            (up1 && ((h & 1) || (w & 1)))) {
-            set_error("%s: sources of %d (pitch %d%s) + %d (pitch %d) channels for %d: whole 16-byte chunks of %d elements, 16-byte aligned; an upsampled "
-                      "source needs even h and w", who, c1, ld1, up1 ? ", upsampled" : "", c - c1, ld2, c, E);
-            return -1;
-        }
-        if (c1 == c) d_x2 = nullptr;
-    }
+    if (!conv2d_args_ok(who, eb, batch, h, w, c, n, kh, kw, stride, pad, ldy, d_res != nullptr, ldr, conv2d_misaligned(d_x, d_w, d_x2, d_y, d_res), cat,
+                        d_x2 != nullptr, c1, ld1, ld2, up1)) return -1;
+    if (cat && c1 == c) d_x2 = nullptr;
     if (!ensure_device()) return -1;
     // (a plain dense source through the cat entry still takes the 1x1 path: ld1 = c selects it only when something differs -- force it with up1 / x2 / ld1)
     return HIP_RC(bf::launch_conv2d_nhwc(eb, d_x, d_w, d_bias, d_y, batch, h, w, c, n, kh, kw, stride, pad, silu, ldy, d_res, ldr, cat ? d_x2 : nullptr,
                                          cat ? c1 : c, cat ? ld1 : c, cat ? ld2 : 0, cat ? up1 : 0, as_stream(stream)));
+}
+
+static void conv2d_plan_out(const bf::ConvPlan& p, long long out[16])
+{
+    out[0] = p.elem_bytes; out[1] = p.family; out[2] = p.bm; out[3] = p.bn; out[4] = p.cpr; out[5] = p.cat; out[6] = p.split; out[7] = p.fast_tap;
+    out[8] = p.wide; out[9] = p.grid_x; out[10] = p.grid_y; out[11] = p.lds_bytes; out[12] = p.row_env; out[13] = p.tap_env; out[14] = p.patch_env;
+    out[15] = p.n_cus;
+}
+
+int bf_plan_conv2d(int elem_bytes, int batch, int h, int w, int c, int n, int kh, int kw, int stride, int pad, int ldy, int has_res, int ldr, int c1, int ld1,
+                   int up1, int has_x2, int ld2, int misaligned, int use_dma_kernel, int f32_mode, int n_cus, long long out[16])
+{
+    std::lock_guard<std::mutex> lock(S().mu);
+    const char* who = "bf_plan_conv2d";
+    if (!out) { set_error("%s: out is null", who); return -1; }
+    if (elem_bytes != 2 && elem_bytes != 4) { set_error("%s: element size %d (2 = float16, 4 = float32)", who, elem_bytes); return -1; }
+    // the layer names a concatenation (the bf_conv1x1_cat_* entry) when anything differs from one dense source of c channels
+    const bool cat = has_x2 != 0 || up1 != 0 || c1 != c || ld1 != c;
+    if (cat && (kh != 1 || kw != 1 || stride != 1 || pad != 0)) {
+        set_error("%s: two sources / a pitch / upsampling under a %d x %d window, stride %d, pad %d: 1x1 layers only", who, kh, kw, stride, pad);
+        return -1;
+    }
+    if (!conv2d_args_ok(who, elem_bytes, batch, h, w, c, n, kh, kw, stride, pad, ldy, has_res != 0, ldr, (unsigned)misaligned, cat, has_x2 != 0, c1, ld1, ld2, up1))
+        return -1;
+    const bool x2 = has_x2 != 0 && !(cat && c1 == c);
+    bf::ConvLayer L;
+    L.elem_bytes = elem_bytes; L.B = batch; L.H = h; L.W = w; L.C = c; L.N = n; L.KH = kh; L.KW = kw; L.stride = stride; L.pad = pad;
+    L.ldy = ldy; L.ldr = ldr; L.c1 = cat ? c1 : c; L.ld1 = cat ? ld1 : c; L.ld2 = cat ? ld2 : 0; L.up1 = cat ? up1 : 0;
+    L.has_res = has_res != 0; L.has_x2 = x2; L.misaligned = (unsigned)misaligned & ~(x2 ? 0u : (unsigned)bf::kConvMisalignedX2);
+    const int dma = use_dma_kernel < 0 ? bf::conv_dma_switch(-1) : (use_dma_kernel > 2 ? 1 : use_dma_kernel);       // (as the setters store them)
+    const int mode = f32_mode < 0 ? bf::conv_f32_mode(-1) : (f32_mode != 0 ? 1 : 0);
+    bf::ConvPlan p;
+    if (bf::plan_conv2d(L, dma, mode, n_cus > 0 ? n_cus : 256, &p) != hipSuccess) {
+        set_error("%s: the launch refuses this layer (%s)", who, hipGetErrorString(hipErrorInvalidValue));
+        return -1;
+    }
+    conv2d_plan_out(p, out);
+    return 0;
+}
+
+int bf_last_conv2d_plan(long long out[16])
+{
+    std::lock_guard<std::mutex> lock(S().mu);
+    if (!out) { set_error("bf_last_conv2d_plan: out is null"); return -1; }
+    bf::ConvPlan p;
+    if (!bf::last_conv2d_plan(&p)) { set_error("bf_last_conv2d_plan: no convolution was launched in this process"); return -1; }
+    conv2d_plan_out(p, out);
+    return 0;
 }
 
 int bf_conv2d_nhwc_f16_device(const void* d_x, const void* d_w, const float* d_bias, void* d_y, int batch, int h, int w, int c, int n, int kh, int kw, int stride,

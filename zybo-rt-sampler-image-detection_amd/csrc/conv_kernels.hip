@@ -879,53 +879,27 @@ inline DmaTile pick_dma_tile(long long M, int N, int n_cus, bool f32, bool split
     return best;
 }
 
+// Dispatches on the plan (plan_conv2d below decides; nothing is decided here).
 template <typename T>
-hipError_t launch_conv_t(const ConvArgs& a, const void* x, const void* w, const float* bias, void* y, bool cat, bool dma, unsigned x_bytes, unsigned x2_bytes,
-                         unsigned w_bytes, hipStream_t stream)
+hipError_t launch_conv_t(const ConvArgs& a, const ConvPlan& p, const void* x, const void* w, const float* bias, void* y, hipStream_t stream)
 {
     const T* xp = static_cast<const T*>(x);
     const T* wp = static_cast<const T*>(w);
     T* yp = static_cast<T*>(y);
-    if (dma) {
-        static int n_cus = 0;
-        if (n_cus == 0) {
-            int dev = 0, v = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cus = v; else n_cus = 256;
-        }
-        // the stem's shape: a 4-channel input under a wide window -- the patch kernel, in float16 (0.27 -> 0.19 ms at batch 64; in float32 both kernels sit
-        // on the 72 MFMAs per wave of the 4-channel K and the patch form measured 5 % slower: 0.68 against 0.64 ms).  $BF_CONV_PATCH=0 / 1: never / always (A/B).
-        static const int patch_env = [] { const char* e = getenv("BF_CONV_PATCH"); return e ? atoi(e) : -1; }();
-        const bool patch_wanted = conv_dma_switch(-1) == 2 ? true : (patch_env < 0 ? sizeof(T) == 2 : patch_env != 0);
-        if (patch_wanted && !cat && a.C == 4 && a.N <= 32 && a.KH * a.KW >= 16 && (a.KW & 1) == 0 && ((a.KH * a.KW * 4 / (16 / (int)sizeof(T))) & 1) == 0 &&
-            (sizeof(T) == 4 || ((a.stride & 1) == 0 && (a.pad & 1) == 0 && (a.W & 1) == 0))) {
-            const int PH = 7 * a.stride + a.KH, PW = 15 * a.stride + a.KW;
-            const int patch_bytes = (PH * PW * 4 * (int)sizeof(T) + 1023) & ~1023, w_lds = 32 * (a.wld * (int)sizeof(T) + 16);
-            const int lds = patch_bytes + ((w_lds + 1023) & ~1023) + 256, tile = 128 * (32 + 16 / (int)sizeof(T)) * (int)sizeof(T);
-            const int need = lds > tile ? lds : tile;
-            if (need <= 64 * 1024) {
-                auto kernel = conv_patch_kernel<T>;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, need);
-                if (e != hipSuccess) return e;
-                const unsigned grid = (unsigned)a.B * (unsigned)((a.Ho + 7) / 8) * (unsigned)((a.Wo + 15) / 16);
-                hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), (size_t)need, stream, xp, wp, bias, yp, a, x_bytes, w_bytes);
-                return hipGetLastError();
-            }
-        }
-        const bool split = sizeof(T) == 4 && conv_f32_mode(-1) == 1;
-        const DmaTile t = pick_dma_tile(a.M, a.N, n_cus, sizeof(T) == 4 && !split, split);
-        // Rows of 128 bytes (full cache lines per row, half the barriers per MFMA) pay where stages are many and the tile is 128 channels wide: float16
-        // layers of 128+ channels with K >= 1024, or 1x1 layers with K >= 512 (profiles/r03_conv_layers_f16.csv; the stem and the 32- / 64-channel layers
-        // lose to the coarser K padding and the smaller ring).  float32 stages are long as they are: 64-byte rows.  $BF_CONV_ROW=64|128 forces either.
-        static const int row_env = [] { const char* e = getenv("BF_CONV_ROW"); return e ? atoi(e) : 0; }();
-        const int K = a.KH * a.KW * a.C;
-        bool wide_rows = row_env == 128 ? true : (row_env == 64 ? false : (sizeof(T) == 2 && a.N >= 128 && (K >= 1024 || (a.KH == 1 && K >= 512))));
-        if (cat && a.x2 && (a.c1 % (8 * (16 / (int)sizeof(T)))) != 0) wide_rows = false;
-        ConvArgs af = a;                                       // (see ConvArgs::fast_tap; $BF_CONV_TAP=0 keeps the general address form, for A/B runs)
-        static const int tap_env = [] { const char* e = getenv("BF_CONV_TAP"); return e ? atoi(e) : 1; }();
-        af.fast_tap = (tap_env != 0 && !cat && a.C / (16 / (int)sizeof(T)) >= ((wide_rows && !split) ? 8 : 4) && a.KH * a.KW <= 32) ? 1 : 0;
-#define BF_DMA_LAUNCH(BM, BN, CPR, CAT, SPLIT)                                                                                                                          \
-        hipLaunchKernelGGL((conv_dma_kernel<T, BM, BN, CPR, CAT, SPLIT>), dim3((unsigned)((a.M + BM - 1) / BM), (unsigned)((a.N + BN - 1) / BN)), dim3(256), 0, stream,  \
-                           xp, wp, bias, yp, af, x_bytes, x2_bytes, w_bytes)
+    const unsigned x_bytes = p.x_bytes, x2_bytes = p.x2_bytes, w_bytes = p.w_bytes;
+    const bool cat = p.cat != 0;
+    if (p.family == kConvPatch) {
+        auto kernel = conv_patch_kernel<T>;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid_x), dim3(256), (size_t)p.lds_bytes, stream, xp, wp, bias, yp, a, x_bytes, w_bytes);
+        return hipGetLastError();
+    }
+    if (p.family == kConvDma) {
+        const bool split = p.split != 0, wide_rows = p.cpr == 8;
+#define BF_DMA_LAUNCH(BM, BN, CPR, CAT, SPLIT)                                                                                                \
+        hipLaunchKernelGGL((conv_dma_kernel<T, BM, BN, CPR, CAT, SPLIT>), dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(256), 0, stream,  \
+                           xp, wp, bias, yp, a, x_bytes, x2_bytes, w_bytes)
 #define BF_DMA_PICK(BM, BN)                                                                                                    \
         do {                                                                                                                   \
             if constexpr (sizeof(T) == 4) {                                                                                    \
@@ -934,24 +908,26 @@ hipError_t launch_conv_t(const ConvArgs& a, const void* x, const void* w, const 
             if (wide_rows) { if (cat) BF_DMA_LAUNCH(BM, BN, 8, true, false); else BF_DMA_LAUNCH(BM, BN, 8, false, false); }    \
             else { if (cat) BF_DMA_LAUNCH(BM, BN, 4, true, false); else BF_DMA_LAUNCH(BM, BN, 4, false, false); }              \
         } while (0)
-        if (t.bm == 128 && t.bn == 128) BF_DMA_PICK(128, 128);
-        else if (t.bm == 128 && t.bn == 64) BF_DMA_PICK(128, 64);
-        else if (t.bm == 128) BF_DMA_PICK(128, 32);
-        else if (t.bn == 128) BF_DMA_PICK(64, 128);
+        if (p.bm == 128 && p.bn == 128) BF_DMA_PICK(128, 128);
+        else if (p.bm == 128 && p.bn == 64) BF_DMA_PICK(128, 64);
+        else if (p.bm == 128) BF_DMA_PICK(128, 32);
+        else if (p.bn == 128) BF_DMA_PICK(64, 128);
         else BF_DMA_PICK(64, 64);
 #undef BF_DMA_PICK
 #undef BF_DMA_LAUNCH
         return hipGetLastError();
     }
-    const long long gx = (a.M + kBM - 1) / kBM;
 #define BF_CONV_LAUNCH(BN, CAT) \
-    hipLaunchKernelGGL((conv_igemm_kernel<T, BN, CAT>), dim3((unsigned)gx, (unsigned)((a.N + BN - 1) / BN)), dim3(256), 0, stream, xp, wp, bias, yp, a)
-    if (a.N >= 128) { if (cat) BF_CONV_LAUNCH(128, true); else BF_CONV_LAUNCH(128, false); }
-    else if (a.N <= 32) { if (cat) BF_CONV_LAUNCH(32, true); else BF_CONV_LAUNCH(32, false); }
+    hipLaunchKernelGGL((conv_igemm_kernel<T, BN, CAT>), dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(256), 0, stream, xp, wp, bias, yp, a)
+    if (p.bn == 128) { if (cat) BF_CONV_LAUNCH(128, true); else BF_CONV_LAUNCH(128, false); }
+    else if (p.bn == 32) { if (cat) BF_CONV_LAUNCH(32, true); else BF_CONV_LAUNCH(32, false); }
     else { if (cat) BF_CONV_LAUNCH(64, true); else BF_CONV_LAUNCH(64, false); }
 #undef BF_CONV_LAUNCH
     return hipGetLastError();
 }
+
+ConvPlan g_last_plan;                                          // last_conv2d_plan: what the most recent launch of this process dispatched on
+bool g_have_last_plan = false;
 
 }  // namespace
 
@@ -1020,14 +996,18 @@ int conv_f32_mode(int value)
     return old;
 }
 
-// elem_bytes: 2 (float16) or 4 (float32).  x2 != nullptr or ld1 != C or up1: the 1x1 window over a virtual concatenation (ConvArgs).
-hipError_t launch_conv2d_nhwc(int elem_bytes, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int N, int KH, int KW,
-                              int stride, int pad, int act, int ldy, const void* res, int ldr, const void* x2, int c1, int ld1, int ld2, int up1,
-                              hipStream_t stream)
+// Everything launch_conv2d_nhwc decides about a layer, with no GPU call: whether the layer is taken at all (hipErrorInvalidValue otherwise -- what
+// the launch then returns), the kernel family, the LDS-DMA kernel's tile / row length / concatenation / split / tap form, the store epilogue, the
+// grid and the patch kernel's LDS.  dma_switch / f32_mode: conv_dma_switch / conv_f32_mode as set; n_cus: compute units of the device.
+// $BF_CONV_PATCH, $BF_CONV_ROW, $BF_CONV_TAP (A/B switches) are read once per process and reported in the plan.
+// x2 or ld1 != C or up1: the 1x1 window over a virtual concatenation (ConvArgs).
+hipError_t plan_conv2d(const ConvLayer& L, int dma_switch, int f32_mode, int n_cus, ConvPlan* p)
 {
-    const int E = 16 / elem_bytes;
+    const int elem_bytes = L.elem_bytes, B = L.B, H = L.H, W = L.W, C = L.C, N = L.N, KH = L.KH, KW = L.KW, stride = L.stride, pad = L.pad;
+    const int ldy = L.ldy, ldr = L.ldr, c1 = L.c1, ld1 = L.ld1, ld2 = L.ld2, up1 = L.up1;
     if (elem_bytes != 2 && elem_bytes != 4) return hipErrorInvalidValue;
-    if (ldy < N || (res && ldr < N)) return hipErrorInvalidValue;
+    const int E = 16 / elem_bytes;
+    if (ldy < N || (L.has_res && ldr < N)) return hipErrorInvalidValue;
     if (B <= 0 || H <= 0 || W <= 0 || N <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0) return hipErrorInvalidValue;
     if (C < 4 || (C & (C - 1)) != 0 || ((KW * C) % E) != 0) return hipErrorInvalidValue;       // whole 16-byte chunks per window row
     // float16, C = 4: a chunk is two pixels, which must leave the image together -- even window starts, even width
@@ -1035,45 +1015,119 @@ hipError_t launch_conv2d_nhwc(int elem_bytes, const void* x, const void* w, cons
     // every 1x1 / stride 1 / unpadded layer takes the "virtual concatenation" kernel, also with one dense source: its addresses are the pixel's base plus
     // a stage offset -- no pixel decomposition (two integer divisions per piece), no window arithmetic; the short layers are bound by exactly such
     // vector instructions (a 64 -> 32 channel 1x1 layer: 460 VALU instructions per wave around 4 MFMAs, vector issue 63 % busy)
-    const bool cat = x2 != nullptr || up1 != 0 || ld1 != C || (KH == 1 && KW == 1 && stride == 1 && pad == 0);
+    const bool cat = L.has_x2 || up1 != 0 || ld1 != C || (KH == 1 && KW == 1 && stride == 1 && pad == 0);
     if (cat) {
         if (KH != 1 || KW != 1 || stride != 1 || pad != 0 || c1 < E || c1 > C || (c1 % E) || (ld1 % E) || ld1 < c1) return hipErrorInvalidValue;
-        if (c1 < C && (!x2 || (ld2 % E) || ld2 < C - c1 || (reinterpret_cast<uintptr_t>(x2) & 15))) return hipErrorInvalidValue;
+        if (c1 < C && (!L.has_x2 || (ld2 % E) || ld2 < C - c1 || (L.misaligned & kConvMisalignedX2))) return hipErrorInvalidValue;
         if (up1 && ((H & 1) || (W & 1))) return hipErrorInvalidValue;
     }
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return hipErrorInvalidValue;
+    if (L.misaligned & (kConvMisalignedX | kConvMisalignedW)) return hipErrorInvalidValue;
+    ConvPlan q{};
+    q.elem_bytes = elem_bytes; q.n_cus = n_cus; q.cat = cat ? 1 : 0;
+    q.Ho = (H + 2 * pad - KH) / stride + 1;
+    q.Wo = (W + 2 * pad - KW) / stride + 1;
+    if (q.Ho <= 0 || q.Wo <= 0) return hipErrorInvalidValue;
+    q.wide = ((N % E) == 0 && (ldy % E) == 0 && (L.misaligned & kConvMisalignedY) == 0 &&
+              (!L.has_res || ((ldr % E) == 0 && (L.misaligned & kConvMisalignedRes) == 0))) ? 1 : 0;
+    q.M = (long long)B * q.Ho * q.Wo;
+    if (q.M > 0x7fffffffLL) return hipErrorInvalidValue;       // (the kernel splits pixel indices in 32 bits)
+    q.c1 = cat ? c1 : C;
+    // The LDS-DMA kernel addresses its operands through 32-bit buffer offsets with the top bit as the out-of-range mark: every operand tensor
+    // below 2 GiB, and a two-source layer switching source on a stage boundary.  BF_CONV_DMA=0 selects the register-staged kernel (A/B runs).
+    const unsigned long long eb = (unsigned long long)elem_bytes;
+    const unsigned long long src1_pixels = cat && up1 ? (unsigned long long)B * (H / 2) * (W / 2) : (unsigned long long)B * H * W;
+    const unsigned long long xb = cat ? ((src1_pixels - 1) * (unsigned long long)ld1 + (unsigned long long)q.c1) * eb : src1_pixels * (unsigned long long)C * eb;
+    const unsigned long long x2b = (cat && L.has_x2) ? (((unsigned long long)B * H * W - 1) * (unsigned long long)ld2 + (unsigned long long)(C - q.c1)) * eb : 0ull;
+    q.wld = conv_weight_row(elem_bytes, KH, KW, C);
+    const unsigned long long wb = (unsigned long long)N * (unsigned long long)q.wld * eb;
+    const bool dma = dma_switch != 0 && xb < 0x7ffffff0ull && x2b < 0x7ffffff0ull && wb < 0x7ffffff0ull && (!(cat && L.has_x2) || (q.c1 % (4 * E)) == 0);
+    q.x_bytes = (unsigned)xb; q.x2_bytes = (unsigned)x2b; q.w_bytes = (unsigned)wb;
+    static const int patch_env = [] { const char* e = getenv("BF_CONV_PATCH"); return e ? atoi(e) : -1; }();
+    static const int row_env = [] { const char* e = getenv("BF_CONV_ROW"); return e ? atoi(e) : 0; }();
+    static const int tap_env = [] { const char* e = getenv("BF_CONV_TAP"); return e ? atoi(e) : 1; }();
+    q.patch_env = patch_env; q.row_env = row_env; q.tap_env = tap_env;
+    if (!dma) {                                                // the register-staged kernel: 128-pixel tiles, 64-byte stages
+        q.family = kConvRegStaged; q.bm = kBM; q.bn = N >= 128 ? 128 : (N <= 32 ? 32 : 64); q.cpr = 4;
+        q.grid_x = (q.M + kBM - 1) / kBM; q.grid_y = (N + q.bn - 1) / q.bn;
+        *p = q;
+        return hipSuccess;
+    }
+    // the stem's shape: a 4-channel input under a wide window -- the patch kernel, in float16 (0.27 -> 0.19 ms at batch 64; in float32 both kernels sit
+    // on the 72 MFMAs per wave of the 4-channel K and the patch form measured 5 % slower: 0.68 against 0.64 ms).  $BF_CONV_PATCH=0 / 1: never / always (A/B).
+    const bool patch_wanted = dma_switch == 2 ? true : (patch_env < 0 ? elem_bytes == 2 : patch_env != 0);
+    if (patch_wanted && !cat && C == 4 && N <= 32 && KH * KW >= 16 && (KW & 1) == 0 && ((KH * KW * 4 / E) & 1) == 0 &&
+        (elem_bytes == 4 || ((stride & 1) == 0 && (pad & 1) == 0 && (W & 1) == 0))) {
+        const int PH = 7 * stride + KH, PW = 15 * stride + KW;
+        const int patch_bytes = (PH * PW * 4 * elem_bytes + 1023) & ~1023, w_lds = 32 * (q.wld * elem_bytes + 16);
+        const int lds = patch_bytes + ((w_lds + 1023) & ~1023) + 256, tile = 128 * (32 + E) * elem_bytes;
+        const int need = lds > tile ? lds : tile;
+        if (need <= 64 * 1024) {
+            q.family = kConvPatch; q.bm = 128; q.bn = 32; q.cpr = 0; q.lds_bytes = need;   // tiles of 8 x 16 pixels x 32 channels
+            q.grid_x = (long long)((unsigned)B * (unsigned)((q.Ho + 7) / 8) * (unsigned)((q.Wo + 15) / 16)); q.grid_y = 1;
+            *p = q;
+            return hipSuccess;
+        }
+    }
+    const bool split = elem_bytes == 4 && f32_mode == 1;
+    const DmaTile t = pick_dma_tile(q.M, N, n_cus, elem_bytes == 4 && !split, split);
+    // Rows of 128 bytes (full cache lines per row, half the barriers per MFMA) pay where stages are many and the tile is 128 channels wide: float16
+    // layers of 128+ channels with K >= 1024, or 1x1 layers with K >= 512 (profiles/r03_conv_layers_f16.csv; the stem and the 32- / 64-channel layers
+    // lose to the coarser K padding and the smaller ring).  float32 stages are long as they are: 64-byte rows.  $BF_CONV_ROW=64|128 forces either.
+    const int K = KH * KW * C;
+    bool wide_rows = row_env == 128 ? true : (row_env == 64 ? false : (elem_bytes == 2 && N >= 128 && (K >= 1024 || (KH == 1 && K >= 512))));
+    if (cat && L.has_x2 && (q.c1 % (8 * E)) != 0) wide_rows = false;
+    // (see ConvArgs::fast_tap; $BF_CONV_TAP=0 keeps the general address form, for A/B runs)
+    q.fast_tap = (tap_env != 0 && !cat && C / E >= ((wide_rows && !split) ? 8 : 4) && KH * KW <= 32) ? 1 : 0;
+    q.family = kConvDma; q.bm = t.bm; q.bn = t.bn; q.split = split ? 1 : 0;
+    q.cpr = (wide_rows && !split) ? 8 : 4;                     // (the split kernels exist with 64-byte rows only)
+    q.grid_x = (q.M + t.bm - 1) / t.bm; q.grid_y = (N + t.bn - 1) / t.bn;
+    *p = q;
+    return hipSuccess;
+}
+
+bool last_conv2d_plan(ConvPlan* p)
+{
+    if (g_have_last_plan) *p = g_last_plan;
+    return g_have_last_plan;
+}
+
+// elem_bytes: 2 (float16) or 4 (float32).  Decides by plan_conv2d, fills the kernels' arguments and dispatches.
+hipError_t launch_conv2d_nhwc(int elem_bytes, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int N, int KH, int KW,
+                              int stride, int pad, int act, int ldy, const void* res, int ldr, const void* x2, int c1, int ld1, int ld2, int up1,
+                              hipStream_t stream)
+{
+    static int n_cus = 0;
+    if (n_cus == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cus = v; else n_cus = 256;
+    }
+    const auto mis = [](const void* ptr, unsigned bit) { return (reinterpret_cast<uintptr_t>(ptr) & 15) ? bit : 0u; };
+    ConvLayer L;
+    L.elem_bytes = elem_bytes; L.B = B; L.H = H; L.W = W; L.C = C; L.N = N; L.KH = KH; L.KW = KW; L.stride = stride; L.pad = pad;
+    L.ldy = ldy; L.ldr = ldr; L.c1 = c1; L.ld1 = ld1; L.ld2 = ld2; L.up1 = up1; L.has_res = res != nullptr; L.has_x2 = x2 != nullptr;
+    L.misaligned = mis(x, kConvMisalignedX) | mis(w, kConvMisalignedW) | mis(x2, kConvMisalignedX2) | mis(y, kConvMisalignedY) | mis(res, kConvMisalignedRes);
+    ConvPlan p;
+    const hipError_t e = plan_conv2d(L, conv_dma_switch(-1), conv_f32_mode(-1), n_cus, &p);
+    if (e != hipSuccess) return e;
     ConvArgs a;
     a.B = B; a.H = H; a.W = W; a.C = C; a.N = N; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.act = act;
-    a.Ho = (H + 2 * pad - KH) / stride + 1;
-    a.Wo = (W + 2 * pad - KW) / stride + 1;
-    if (a.Ho <= 0 || a.Wo <= 0) return hipErrorInvalidValue;
-    a.ldy = ldy; a.ldr = ldr; a.res = res; a.fast_tap = 0;
-    a.wide = ((N % E) == 0 && (ldy % E) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-              (!res || ((ldr % E) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0))) ? 1 : 0;
+    a.Ho = p.Ho; a.Wo = p.Wo;
+    a.ldy = ldy; a.ldr = ldr; a.res = res; a.fast_tap = p.fast_tap;
+    a.wide = p.wide;
     a.c_shift = 0;
     while ((1 << a.c_shift) < C) ++a.c_shift;
-    a.M = (long long)B * a.Ho * a.Wo;
-    if (a.M > 0x7fffffffLL) return hipErrorInvalidValue;       // (the kernel splits pixel indices in 32 bits)
-    a.x2 = x2; a.c1 = cat ? c1 : C; a.ld1 = cat ? ld1 : C; a.ld2 = ld2; a.up1 = up1;
+    a.M = p.M;
+    a.x2 = x2; a.c1 = p.c1; a.ld1 = p.cat ? ld1 : C; a.ld2 = ld2; a.up1 = up1;
     a.d_img = make_fastdiv((unsigned)(a.Ho * a.Wo)); a.d_row = make_fastdiv((unsigned)a.Wo);
     {
         const int tx = (a.Wo + 15) / 16, ty = (a.Ho + 7) / 8, ppc = 16 / (4 * elem_bytes), pw = 15 * stride + KW;
         a.d_p0 = make_fastdiv((unsigned)(tx * ty)); a.d_p1 = make_fastdiv((unsigned)tx);
         a.d_p2 = make_fastdiv((unsigned)(pw / ppc > 0 ? pw / ppc : 1));
     }
-    // The LDS-DMA kernel addresses its operands through 32-bit buffer offsets with the top bit as the out-of-range mark: every operand tensor
-    // below 2 GiB, and a two-source layer switching source on a stage boundary.  BF_CONV_DMA=0 selects the register-staged kernel (A/B runs).
-    const int want_dma = conv_dma_switch(-1);
-    const unsigned long long eb = (unsigned long long)elem_bytes;
-    const unsigned long long src1_pixels = cat && up1 ? (unsigned long long)B * (H / 2) * (W / 2) : (unsigned long long)B * H * W;
-    const unsigned long long xb = cat ? ((src1_pixels - 1) * (unsigned long long)ld1 + (unsigned long long)a.c1) * eb : src1_pixels * (unsigned long long)C * eb;
-    const unsigned long long x2b = (cat && x2) ? (((unsigned long long)B * H * W - 1) * (unsigned long long)ld2 + (unsigned long long)(C - a.c1)) * eb : 0ull;
-    a.wld = conv_weight_row(elem_bytes, KH, KW, C);
+    a.wld = p.wld;
     a.d_p3 = make_fastdiv((unsigned)(a.wld * elem_bytes + 16));
-    const unsigned long long wb = (unsigned long long)N * (unsigned long long)a.wld * eb;
-    const bool dma = want_dma != 0 && xb < 0x7ffffff0ull && x2b < 0x7ffffff0ull && wb < 0x7ffffff0ull && (!(cat && x2) || (a.c1 % (4 * E)) == 0);
-    return elem_bytes == 4 ? launch_conv_t<float>(a, x, w, bias, y, cat, dma, (unsigned)xb, (unsigned)x2b, (unsigned)wb, stream)
-                           : launch_conv_t<_Float16>(a, x, w, bias, y, cat, dma, (unsigned)xb, (unsigned)x2b, (unsigned)wb, stream);
+    g_last_plan = p; g_have_last_plan = true;
+    return elem_bytes == 4 ? launch_conv_t<float>(a, p, x, w, bias, y, stream) : launch_conv_t<_Float16>(a, p, x, w, bias, y, stream);
 }
 
 }  // namespace bf

@@ -316,6 +316,32 @@ int conv_weight_row(int elem_bytes, int kh, int kw, int c);
 hipError_t launch_conv2d_nhwc(int elem_bytes, const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int N, int KH, int KW,
                               int stride, int pad, int act, int ldy, const void* res, int ldr, const void* x2, int c1, int ld1, int ld2, int up1,
                               hipStream_t stream);
+// The layer as launch_conv2d_nhwc is given it, without the pointers: which exist, and which are not 16-byte aligned.
+enum { kConvMisalignedX = 1, kConvMisalignedW = 2, kConvMisalignedX2 = 4, kConvMisalignedY = 8, kConvMisalignedRes = 16 };
+struct ConvLayer {
+    int elem_bytes, B, H, W, C, N, KH, KW, stride, pad, ldy, ldr, c1, ld1, ld2, up1;
+    bool has_res, has_x2;
+    unsigned misaligned;
+};
+// What the launch does with it (plan_conv2d decides, launch_conv2d_nhwc only dispatches on the result).
+enum { kConvRegStaged = 0, kConvDma = 1, kConvPatch = 2 };
+struct ConvPlan {
+    int elem_bytes, family;
+    int bm, bn;              // output tile: pixels x channels per workgroup
+    int cpr;                 // 16-byte chunks per staged row: 4 (64-byte rows) or 8 (128-byte rows, LDS-DMA only); 0 for the patch kernel
+    int cat, split, fast_tap;   // the kernels' kCat, kSplit (LDS-DMA, float32) and ConvArgs::fast_tap (LDS-DMA, window path)
+    int wide;                // 16-byte stores in the epilogue (ConvArgs::wide)
+    long long grid_x, grid_y;
+    int lds_bytes;           // dynamic LDS (the patch kernel; 0 otherwise)
+    int row_env, tap_env, patch_env;   // $BF_CONV_ROW / $BF_CONV_TAP / $BF_CONV_PATCH as this process read them (0 / 1 / -1 when unset)
+    int n_cus;
+    // derived sizes the kernels' arguments are filled from
+    int Ho, Wo, wld, c1;
+    long long M;
+    unsigned x_bytes, x2_bytes, w_bytes;
+};
+hipError_t plan_conv2d(const ConvLayer& layer, int dma_switch, int f32_mode, int n_cus, ConvPlan* plan);
+bool last_conv2d_plan(ConvPlan* plan);      // the plan of this process's most recent convolution launch; false before the first
 hipError_t launch_topk_candidates(const float* d_scores, const float* d_boxes, const int* d_cls, int batch, int total, int K, float* d_top_scores,
                                   float* d_top_boxes, int* d_top_cls, int* d_counts, hipStream_t stream);
 hipError_t launch_nms(const float* d_boxes, const float* d_scores, const int* d_cls, const int* d_counts, int batch, int K, float iou_thres,
