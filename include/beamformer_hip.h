@@ -723,6 +723,18 @@ int bf_das_select_stream_device(int algo, const float *d_signals, int m_total, i
                                 float *d_power, int power_stride, int *d_status, void *stream);
 int bf_plan_das_select(int algo, int n, int frames, int count, int max_whole, int stream_mode, int n_cus, long long out[10]);
 
+/* The plans of the stream and listed-direction launches, for tests that have to know which kernel instantiation a shape reaches.
+ * bf_plan_das_stream: the launch geometry bf_das_stream_device gives directions [dir_begin, dir_end) of `frames` frames (no GPU
+ *   needed), out[0..9] as bf_plan_das.  It is the map planner's own answer, not bf_plan_das_select's with stream_mode != 0.
+ *   -1 for out == NULL and for what the planner refuses (BF_HYBRID and the FIRs, an empty launch).
+ * bf_last_strided_plan: what the most recent launch of this process among bf_das_stream_device, bf_das_select_device,
+ *   bf_das_select_stream_device and bf_miso_stream_device dispatched on: out[0..9] the plan as above (for bf_miso_stream_device
+ *   the one-beam plan of bf_plan_das(algo, n, 1, 0, 1, max_whole)), out[10] the kernel (0 stream_map_kernel, 1 das_select_kernel,
+ *   2 das_select_kernel with history, 3 stream_beam_kernel), out[11] the algorithm.  The kernel's template arguments are
+ *   (out[11], out[0], out[6]).  -1 for out == NULL and before the first such launch; a call that was refused leaves the record alone. */
+int bf_plan_das_stream(int algo, int n, int frames, int dir_begin, int dir_end, int max_whole, int n_cus, long long out[10]);
+int bf_last_strided_plan(long long out[12]);
+
 /* ---- band selection on the time-domain path: one FIR per band on every row of a frame batch, continuous across windows ----
  * The time-domain maps and beams are broadband; delay-and-sum is linear, so ONE filter applied to every microphone row leaves all
  * inter-microphone delays intact: a band-limited map is bf_das_device on filtered frames, band-limited audio is the same filter on

@@ -381,6 +381,17 @@ void oracle_mimo_range(int algo, const float *signals, float *image, const int *
     free(out);
 }
 
+/* the raw steered blocks of one frame at many table offsets in one call: out[b][0..N) is what oracle_miso_pad (algo 0) /
+ * oracle_miso_lerp (algo 1) gives at offsets[b], through those very functions -- the per-beam entries stay the pinned ones, and
+ * tests/test_strided_cases_host.py holds this loop equal to them.  For tests that want tens of thousands of beams. */
+void oracle_miso_many(int algo, const float *signals, const int *mics, int n, const int *offsets, int count, float *out)
+{
+    for (int b = 0; b < count; b++) {
+        if (algo == 0) oracle_miso_pad(signals, out + (size_t)b * g_nsamp, mics, n, offsets[b]);
+        else           oracle_miso_lerp(signals, out + (size_t)b * g_nsamp, mics, n, offsets[b]);
+    }
+}
+
 void oracle_unload_all(void)
 {
     free(g_pad_whole); free(g_pad2_whole); free(g_lerp_whole); free(g_lerp_h); free(g_fir_taps); free(g_hyb_whole); free(g_hyb_taps);

@@ -187,6 +187,16 @@ class Oracle(_Base):
         self._fn("mimo_range")(C.c_int(algo), _f(s), _f(img), _i(m), C.c_int(m.size), C.c_int(d0), C.c_int(d1))
         return img
 
+    def miso_many(self, algo, signals, mics, offsets):
+        """miso_pad (algo 0) / miso_lerp (algo 1) of one frame at every offset of `offsets`, with the table loaded by `load`:
+        float32 [len(offsets), N], one C call."""
+        assert algo in (0, 1)
+        s, m = _prep(signals, mics)
+        o = np.ascontiguousarray(offsets, dtype=np.int32).ravel()
+        out = np.zeros((o.size, self.N), dtype=np.float32)
+        self._fn("miso_many")(C.c_int(algo), _f(s), _i(m), C.c_int(m.size), _i(o), C.c_int(o.size), _f(out))
+        return out
+
     def lerp_tables(self, delays_f32):
         d = np.ascontiguousarray(delays_f32, dtype=np.float32).ravel()
         self._fn("load_coefficients_lerp")(_f(d), C.c_int(d.size))

@@ -507,6 +507,23 @@ def test_plan_das_refuses_taps(native, lib):
         assert lib.bf_configure(M, N, X, Y, T) == 0
 
 
+def test_strided_plan_exports_refuse(lib):
+    """bf_plan_das_stream and bf_last_strided_plan: a null array, what the map planner refuses, and nothing to report in a process that launched
+    no stream or listed-direction call; the array stays untouched."""
+    out = (C.c_longlong * 12)(*([-7] * 12))
+    _refused(lib, lib.bf_plan_das_stream(0, M, 1, 0, D, 3, 256, None), "bf_plan_das_stream: out is null")
+    _refused(lib, lib.bf_plan_das_stream(2, M, 1, 0, D, 3, 256, out), "bf_plan_das_stream: continuous mode exists for pad and lerp only")
+    _refused(lib, lib.bf_plan_das_stream(1, M, 0, 0, D, 3, 256, out), "bf_plan_das_stream: empty launch")
+    _refused(lib, lib.bf_plan_das_stream(0, M, 1, 7, 7, 3, 256, out), "bf_plan_das_stream: empty launch")
+    assert list(out) == [-7] * 12
+    _refused(lib, lib.bf_last_strided_plan(None), "bf_last_strided_plan: out is null")
+    if lib.bf_last_strided_plan(out) == -1:                # (0 where GPU tests of the same process launched one before this test)
+        assert _err(lib) == "bf_last_strided_plan: no stream or listed-direction call was launched in this process" and list(out) == [-7] * 12
+    else:
+        assert out[10] in (0, 1, 2, 3) and out[11] in (0, 1, 2, 4) and out[0] in (1, 2, 4, 8, 16)
+    assert lib.bf_plan_das_stream(1, M, 3, 2, D, 3, 256, out) == 0 and _err(lib) == "" and list(out)[:2] == [1, 4]
+
+
 # ------------------------------------------------------------------ the convolutions' planner
 
 def _plan_conv(lib, out, eb=2, batch=1, h=8, w=8, c=32, n=32, kh=3, kw=3, stride=1, pad=1, ldy=32, has_res=0, ldr=0, c1=None, ld1=None, up1=0, has_x2=0, ld2=0,

@@ -158,6 +158,8 @@ struct State {
     std::vector<int> listen_mics;        // load_pa(): microphones of the listening beam (api.c:553-567); empty before load_miso / load_pa
     int last_variant = -1;               // bf_last_das_variant
     long long last_changes = -1, last_steps = 0;   // bf_last_das_reloads
+    long long last_strided[12] = {0};    // bf_last_strided_plan: the plan, the kernel and the algorithm of the most recent strided stream / select launch
+    bool last_strided_set = false;
     std::string err;
 };
 
@@ -538,6 +540,27 @@ bool plan_one_beam(int algo, const TableSet& t, int n, int m_total, const float*
     L->signals = d_signals; L->images = nullptr; L->mics = s.d_mics.p;
     return plan_or_error(*L, plan);
 }
+
+// out[0..9] of the plan exports (bf_plan_das, bf_plan_das_select, bf_plan_das_stream, bf_last_strided_plan).
+void export_plan(const bf::DasPlan& p, long long* out)
+{
+    out[0] = p.nc; out[1] = p.lead; out[2] = p.row_stride; out[3] = p.mic_chunk; out[4] = p.n_chunks;
+    out[5] = p.waves; out[6] = p.dpw; out[7] = p.tile_dirs; out[8] = p.n_tiles; out[9] = (long long)p.lds_bytes;
+}
+
+// bf_last_strided_plan's record of a launch that was enqueued: kernel 0 = stream_map_kernel, 1 = das_select_kernel, 2 = das_select_kernel with
+// history, 3 = stream_beam_kernel.
+enum StridedKernel { STRIDED_STREAM_MAP = 0, STRIDED_SELECT, STRIDED_SELECT_HIST, STRIDED_STREAM_BEAM };
+int launched_strided(hipError_t e, const char* call, StridedKernel kernel, int algo, const bf::DasPlan& plan)
+{
+    if (e != hipSuccess) { set_error("%s -> %s", call, hipGetErrorString(e)); return -1; }
+    State& s = S();
+    export_plan(plan, s.last_strided);
+    s.last_strided[10] = kernel; s.last_strided[11] = algo;
+    s.last_strided_set = true;
+    return 0;
+}
+#define STRIDED_RC(kernel, algo, plan, expr) launched_strided((expr), #expr, kernel, algo, plan)
 
 // The sweep order of a launch (bf::sweep_order on the whole-sample rows of its direction range, fetched once), stored at d_order
 // padded to whole groups by repeating the last entry.  *stored = false when the rule gave the identity: nothing is written then.
@@ -1354,7 +1377,8 @@ int bf_miso_stream_device(int algo, const float* d_signals, int m_total, int fra
     bf::DasPlan plan{};
     if (!plan_one_beam(algo, t, n, m_total, d_signals, &L, &plan)) return -1;
     L.frames = frames;
-    return HIP_RC(bf::launch_stream_beams(L, plan, d_prev, hop, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status, as_stream(stream)));
+    return STRIDED_RC(STRIDED_STREAM_BEAM, algo, plan,
+                      bf::launch_stream_beams(L, plan, d_prev, hop, d_offsets, beams, t.entries, mic_gain, d_out, out_stride, d_status, as_stream(stream)));
 }
 
 int bf_das_stream_device(int algo, const float* d_signals, int m_total, float* d_images, int image_stride, int frames, int hop, const float* d_prev,
@@ -1378,7 +1402,7 @@ int bf_das_stream_device(int algo, const float* d_signals, int m_total, float* d
     bf::DasPlan plan{};
     const char* why = "";
     if (bf::plan_stream_maps(L, s.n_cus, &plan, &why) != 0) { set_error("%s: unsupported shape: %s", who, why); return -1; }
-    if (!HIP_OK(bf::launch_stream_maps(L, plan, d_prev, hop, as_stream(stream)))) return -1;
+    if (STRIDED_RC(STRIDED_STREAM_MAP, algo, plan, bf::launch_stream_maps(L, plan, d_prev, hop, as_stream(stream))) != 0) return -1;
     s.last_variant = 9;
     return 0;
 }
@@ -1434,7 +1458,7 @@ int bf_das_select_device(int algo, const float* d_signals, int m_total, int fram
     bf::DasLaunch L{};
     bf::DasPlan plan{};
     if (!plan_select_launch(who, algo, t, false, n, m_total, frames, d_signals, count, d_power, power_stride, &L, &plan)) return -1;
-    return HIP_RC(bf::launch_select(L, plan, d_offsets, per_frame, t.entries, d_status, as_stream(stream)));
+    return STRIDED_RC(STRIDED_SELECT, algo, plan, bf::launch_select(L, plan, d_offsets, per_frame, t.entries, d_status, as_stream(stream)));
 }
 
 int bf_das_select_stream_device(int algo, const float* d_signals, int m_total, int frames, int hop, const float* d_prev, const int* adaptive_array, int n,
@@ -1454,7 +1478,8 @@ int bf_das_select_stream_device(int algo, const float* d_signals, int m_total, i
     bf::DasLaunch L{};
     bf::DasPlan plan{};
     if (!plan_select_launch(who, algo, t, true, n, m_total, frames, d_signals, count, d_power, power_stride, &L, &plan)) return -1;
-    return HIP_RC(bf::launch_select_stream(L, plan, d_prev, hop, d_offsets, per_frame, t.entries, d_status, as_stream(stream)));
+    return STRIDED_RC(STRIDED_SELECT_HIST, algo, plan,
+                      bf::launch_select_stream(L, plan, d_prev, hop, d_offsets, per_frame, t.entries, d_status, as_stream(stream)));
 }
 
 int bf_peak_offsets_device(const float* d_power, int frames, int image_stride, int n_dirs, int offset_per_dir, int* d_offsets, void* stream)
@@ -2275,8 +2300,7 @@ int bf_plan_das(int algo, int n, int frames, int dir_begin, int dir_end, int max
     bf::DasPlan p{};
     const char* why = "";
     if (bf::plan_das(L, n_cus > 0 ? n_cus : 256, &p, &why) != 0) { set_error("bf_plan_das: %s", why); return -1; }
-    out[0] = p.nc; out[1] = p.lead; out[2] = p.row_stride; out[3] = p.mic_chunk; out[4] = p.n_chunks;
-    out[5] = p.waves; out[6] = p.dpw; out[7] = p.tile_dirs; out[8] = p.n_tiles; out[9] = (long long)p.lds_bytes;
+    export_plan(p, out);
     return 0;
 }
 
@@ -2289,8 +2313,30 @@ int bf_plan_das_select(int algo, int n, int frames, int count, int max_whole, in
     bf::DasPlan p{};
     const char* why = "";
     if (bf::plan_select(L, stream_mode != 0, n_cus > 0 ? n_cus : 256, &p, &why) != 0) { set_error("bf_plan_das_select: %s", why); return -1; }
-    out[0] = p.nc; out[1] = p.lead; out[2] = p.row_stride; out[3] = p.mic_chunk; out[4] = p.n_chunks;
-    out[5] = p.waves; out[6] = p.dpw; out[7] = p.tile_dirs; out[8] = p.n_tiles; out[9] = (long long)p.lds_bytes;
+    export_plan(p, out);
+    return 0;
+}
+
+int bf_plan_das_stream(int algo, int n, int frames, int dir_begin, int dir_end, int max_whole, int n_cus, long long out[10])
+{
+    Entered in;
+    if (!need_ptrs("bf_plan_das_stream", {{out, "out"}})) return -1;
+    bf::DasLaunch L{};
+    L.algo = algo; L.n_mics = n; L.m_total = n; L.n_samples = in.s.sz.n_samples; L.n_taps = in.s.sz.n_taps; L.n_dirs = in.s.sz.dirs();
+    L.dir_begin = dir_begin; L.dir_end = dir_end; L.frames = frames; L.tab.max_whole = max_whole;
+    bf::DasPlan p{};
+    const char* why = "";
+    if (bf::plan_stream_maps(L, n_cus > 0 ? n_cus : 256, &p, &why) != 0) { set_error("bf_plan_das_stream: %s", why); return -1; }
+    export_plan(p, out);
+    return 0;
+}
+
+int bf_last_strided_plan(long long out[12])
+{
+    Entered in;
+    if (!need_ptrs("bf_last_strided_plan", {{out, "out"}})) return -1;
+    if (!in.s.last_strided_set) { set_error("bf_last_strided_plan: no stream or listed-direction call was launched in this process"); return -1; }
+    std::copy(in.s.last_strided, in.s.last_strided + 12, out);
     return 0;
 }
 

@@ -112,6 +112,8 @@ _sig("bf_das_select_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, IP,
 _sig("bf_das_select_stream_device", C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, IP, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
      C.c_int, C.c_void_p, C.c_void_p)
 _sig("bf_plan_das_select", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))
+_sig("bf_plan_das_stream", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))
+_sig("bf_last_strided_plan", C.c_int, C.POINTER(C.c_longlong))
 _sig("bf_peak_offsets_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
 _sig("bf_peaks_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p)
