@@ -1003,6 +1003,70 @@ int bf_resample_device(const float *d_in, int rows, int frames, int n, int in_st
                        const float *d_taps, int up, int down, int n_taps, int *d_state, float gain,
                        float *d_out, int out_stride, short *d_pcm, int *d_clip, int *d_count, void *stream);
 
+/* ---- spectral frames of beam audio: windowed STFT power through a filterbank, linear or on a log scale, on the device ----
+ * What an audio model reads (log-mel frames) and what a user watching a beam wants (its spectrum, its band levels), computed from a
+ * continuous float32 stream such as bf_resample_device's d_out, frame after frame across calls: the samples a frame still needs and
+ * the position of the next frame live on the device, so a captured graph keeps framing correctly when it is replayed.  The configured
+ * sizes (bf_configure) and the loaded tables play no part.
+ * d_in      : HIP device pointer, float32 [rows][in_stride], in_stride >= len: the next `len` samples of every row's stream.
+ * d_len     : HIP device pointer, int32 [1], or NULL: how many of the `len` samples are there, read on the device -- what
+ *             bf_resample_device leaves in its d_count[0], so the two calls chain inside one graph although the count differs from push
+ *             to push.
+ * d_hist    : HIP device pointer, float32 [rows][n_win - 1], read and written: the samples before x[0].  The caller zeroes it at the
+ *             start of a stream.
+ * d_state   : HIP device pointer, int32 [4], read and written.  All zeros: the start of a stream (the first frame starts at the first
+ *             sample).
+ * d_window  : HIP DEVICE pointer, float32 [n_win] (features.hann makes one).
+ * d_bank    : HIP DEVICE pointer, float32 [n_bands][n_fft / 2 + 1], or NULL: the power spectrum itself, n_bands == n_fft / 2 + 1.
+ * d_support : HIP DEVICE pointer, int32 [n_bands][2] = [lo_b, hi_b), or NULL: whole rows.  (features.design_mel and design_bands make
+ *             both.)  A range is clipped to [0, n_fft / 2 + 1]; lo_b >= hi_b is an empty band.
+ * Definition (builder-defined; the reference has no spectral frames).  Let H = n_win - 1.
+ *   Stream.  L = len when d_len is NULL, else min(max(d_len[0], 0), len).  Row r's samples are
+ *       x[s] = d_in[r][s]                    for 0 <= s < L
+ *       x[s] = d_hist[r][H + s]              for -H <= s < 0
+ *   State.  d_state[0] = s0 >= -H is the start of the next frame relative to x[0]; d_state[1..3] are reserved and written 0.
+ *   Frames.  Frame j starts at s_j = s0 + j * hop_s and exists while s_j + n_win <= L:
+ *       count = s0 + n_win <= L ? (L - n_win - s0) / hop_s + 1 : 0            (64-bit; count <= cap)
+ *   Values, float32 throughout:
+ *       u[t] = d_window[t] * x[s_j + t] for t < n_win, one multiply; u[t] = 0 for n_win <= t < n_fft
+ *       X_k  = sum_t u[t] exp(-2 pi i k t / n_fft),  k = 0 .. n_fft / 2
+ *       P_k  = re(X_k)^2 + im(X_k)^2
+ *       E_b  = sum over lo_b <= k < hi_b of d_bank[b][k] * P_k, in ascending k from 0.0f, product and sum each rounded;
+ *              weights outside the support are not read; E_k = P_k without a bank
+ *       out  = E_b where scale == 0, else scale * log10f(E_b < floor_ ? floor_ : E_b)   (1: the usual log-mel input; 10: dB; a NaN
+ *              stays a NaN)
+ *     The transform is a radix-2 decimation-in-time FFT with computed twiddles; its rounding is not part of the definition, these
+ *     promises are: a frame's values depend only on its own n_win samples, the window, the bank and the scalars -- not on rows, on
+ *     the other rows, on the frame's index j, on the alignment of any pointer, or on how the stream was cut into calls.  Two calls on
+ *     L1 and L - L1 samples, the second with the first's d_hist and d_state, give the frames of one call on L samples bit for bit, and
+ *     the counts add up.  A non-finite sample affects only the frames that contain it.
+ *   Outputs.  d_out float32 [rows][out_frames][n_bands]: frames j < count; frames count <= j < cap are written 0.0f, with cap =
+ *     bf_spectrogram_capacity(len, hop_s) = ceil(len / hop_s); frames past cap are left untouched.
+ *   d_count int32 [2] = (count, status).  A state with s0 < -H gives status = 1, count = 0 and zeros in the frames [0, cap); the state
+ *     and the history are left as they were.  Otherwise status = 0.
+ *   New state.  s0' = s0 + count * hop_s - L (hop_s > n_win skips samples: s0' may be positive), and d_hist' = the last H samples of
+ *     d_hist || x[0 .. L) (L < H shifts the history inside itself).
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: two launches -- the transform (a workgroup per frame; one wave up to n_fft =
+ *             512, four above), which only reads d_state, d_hist and d_len, then a workgroup per row that writes d_hist, d_state and
+ *             d_count (len == 0: that one alone); no allocation, no workspace, no table, no synchronisation, no atomics on floats;
+ *             graph-capturable from the first call, and a replay advances the state like any other call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_in, d_hist, d_state, d_window, d_out or d_count null;
+ * rows < 1; len < 0; in_stride < len; n_fft not a power of two in [32, 4096]; n_win < 1 or > n_fft; hop_s < 1; n_bands < 1 or >
+ * BF_SPECTROGRAM_MAX_BANDS; d_bank null with n_bands != n_fft / 2 + 1; out_frames < cap; scale not finite; scale != 0 with floor_ not
+ * finite or <= 0; a written range (d_out, d_hist, d_state, d_count; each from its first element to the last one touched) sharing a
+ * byte with a read range (d_in, d_len, d_window, d_bank, d_support) or with another written one; no GPU.  All arguments are checked
+ * before device bring-up.
+ * bf_spectrogram_capacity: ceil(len / hop_s), the most frames one call on len samples can complete; -1 for len < 0 or hop_s < 1.  No
+ * GPU needed. */
+#define BF_SPECTROGRAM_MAX_BANDS 4096
+long long bf_spectrogram_capacity(long long len, int hop_s);
+int bf_spectrogram_device(const float *d_in, int rows, int in_stride, int len, const int *d_len,
+                          float *d_hist, int *d_state,
+                          const float *d_window, int n_win, int n_fft, int hop_s,
+                          const float *d_bank, const int *d_support, int n_bands,
+                          float scale, float floor_,
+                          float *d_out, int out_frames, int *d_count, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

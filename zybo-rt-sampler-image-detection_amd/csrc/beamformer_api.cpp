@@ -1869,6 +1869,52 @@ int bf_resample_device(const float* d_in, int rows, int frames, int n, int in_st
                                       d_count, as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- spectral frames of beam audio
+
+long long bf_spectrogram_capacity(long long len, int hop_s) { return bf::spectrogram_capacity(len, hop_s); }
+
+int bf_spectrogram_device(const float* d_in, int rows, int in_stride, int len, const int* d_len, float* d_hist, int* d_state, const float* d_window, int n_win,
+                          int n_fft, int hop_s, const float* d_bank, const int* d_support, int n_bands, float scale, float floor_, float* d_out, int out_frames,
+                          int* d_count, void* stream)
+{
+    static const char* who = "bf_spectrogram_device";
+    static_assert(BF_SPECTROGRAM_MAX_BANDS == bf::kSpectrogramMaxBands, "the header's limit is the kernel's");
+    Entered in;
+    if (!need_ptrs(who, {{d_in, "d_in"}, {d_hist, "d_hist"}, {d_state, "d_state"}, {d_window, "d_window"}, {d_out, "d_out"}, {d_count, "d_count"}})) return -1;
+    if (!need_min(who, "rows", rows, 1) || !need_min(who, "len", len, 0) || !need_min(who, "in_stride", in_stride, "len", len)) return -1;
+    if (n_fft < bf::kSpectrogramMinFft || n_fft > bf::kSpectrogramMaxFft || (n_fft & (n_fft - 1)) != 0) {
+        set_error("%s: n_fft = %d is not a power of two in [%d, %d]", who, n_fft, bf::kSpectrogramMinFft, bf::kSpectrogramMaxFft);
+        return -1;
+    }
+    if (!need_min(who, "n_win", n_win, 1)) return -1;
+    if (n_win > n_fft) { set_error("%s: n_win = %d > n_fft = %d", who, n_win, n_fft); return -1; }
+    if (!need_min(who, "hop_s", hop_s, 1) || !need_min(who, "n_bands", n_bands, 1) || !need_max(who, "n_bands", n_bands, BF_SPECTROGRAM_MAX_BANDS)) return -1;
+    const int n_bins = n_fft / 2 + 1;
+    if (!d_bank && n_bands != n_bins) {
+        set_error("%s: d_bank is null (the power spectrum) but n_bands = %d != n_fft / 2 + 1 = %d", who, n_bands, n_bins);
+        return -1;
+    }
+    const long long cap = bf::spectrogram_capacity(len, hop_s);     // (<= len: it fits an int)
+    if (!need_min(who, "out_frames", out_frames, "cap", (int)cap)) return -1;
+    if (!need_finite(who, "scale", scale)) return -1;
+    if (scale != 0.0f && !need_finite(who, "floor_", floor_, FINITE_GT0)) return -1;
+    // every span runs from its first element to the last one touched
+    const u64 out_slots = sat_add(sat_mul((u64)rows - 1, (u64)out_frames), (u64)cap);
+    if (!need_disjoint(who, {{d_out, sat_mul(sat_mul(out_slots, (u64)n_bands), sizeof(float)), "d_out"},
+                             {d_hist, sat_mul(sat_mul((u64)rows, (u64)(n_win - 1)), sizeof(float)), "d_hist"},
+                             {d_state, 4 * sizeof(int), "d_state"},
+                             {d_count, 2 * sizeof(int), "d_count"},
+                             {d_in, sat_add(sat_mul(sat_mul((u64)rows - 1, (u64)in_stride), sizeof(float)), (u64)len * sizeof(float)), "d_in"},
+                             {d_len, sizeof(int), "d_len"},
+                             {d_window, (u64)n_win * sizeof(float), "d_window"},
+                             {d_bank, (u64)n_bands * n_bins * sizeof(float), "d_bank"},
+                             {d_support, (u64)n_bands * 2 * sizeof(int), "d_support"}}, 4))   // four written ranges (history and state among them), five read
+        return -1;
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_spectrogram(d_in, rows, in_stride, len, d_len, d_hist, d_state, d_window, n_win, n_fft, hop_s, d_bank, d_support, n_bands, scale,
+                                         floor_, d_out, out_frames, d_count, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

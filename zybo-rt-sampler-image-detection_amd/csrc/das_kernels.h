@@ -268,6 +268,20 @@ hipError_t launch_resample(const float* d_in, int rows, int frames, int n, int i
                            int n_taps, int32_t* d_state, float gain, float* d_out, int out_stride, short* d_pcm, int32_t* d_clip, int32_t* d_count,
                            hipStream_t stream);
 
+// bf_spectrogram_device (spectrogram.hip): the rows of a flat stream (d_in float32 [rows][in_stride], `len` new samples each, or d_len[0] of
+// them, read on the device) as frames of n_win samples every `hop`, windowed, transformed at n_fft points, |.|^2, through the filterbank
+// d_bank float32 [n_bands][n_fft / 2 + 1] (null: the power spectrum) over d_support int32 [n_bands][2] (null: whole rows), linear
+// (scale == 0) or scale * log10f(max(., floor_)) -> d_out float32 [rows][out_frames][n_bands].  d_hist float32 [rows][n_win - 1] and
+// d_state int32 [4] (start of the next frame, 0, 0, 0) carry between calls; d_count int32 [2] = (count, status).  Two launches: the
+// transform, which only reads them, then one workgroup per row that advances them.  No workspace, no table: the twiddles are computed.
+constexpr int kSpectrogramMinFft = 32;
+constexpr int kSpectrogramMaxFft = 4096;
+constexpr int kSpectrogramMaxBands = 4096;
+long long spectrogram_capacity(long long len, int hop);      // ceil(len / hop); -1 on bad arguments
+hipError_t launch_spectrogram(const float* d_in, int rows, int in_stride, int len, const int32_t* d_len, float* d_hist, int32_t* d_state, const float* d_window,
+                              int n_win, int n_fft, int hop, const float* d_bank, const int32_t* d_support, int n_bands, float scale, float floor_,
+                              float* d_out, int out_frames, int32_t* d_count, hipStream_t stream);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);

@@ -80,3 +80,9 @@ class FusedPipeline:
         """listen's beams [F, B, N_SAMPLES] -> ao.push (an audio_out.AudioOut): the beams at a sound card's rate, float32 and 16-bit PCM,
         continuous across batches (audio, pcm, count)."""
         return ao.push(out)
+
+    def features(self, out, ao, bfeat):
+        """listen's beams [F, B, N_SAMPLES] -> bfeat.push_from(ao, out) (a features.BeamFeatures behind an audio_out.AudioOut): the
+        beams as spectral frames at the model's rate, log-mel or band levels, continuous across batches and without a host round
+        trip (feat, count)."""
+        return bfeat.push_from(ao, out)
