@@ -729,8 +729,8 @@ int bf_plan_das_select(int algo, int n, int frames, int count, int max_whole, in
  *   -1 for out == NULL and for what the planner refuses (BF_HYBRID and the FIRs, an empty launch).
  * bf_last_strided_plan: what the most recent launch of this process among bf_das_stream_device, bf_das_select_device,
  *   bf_das_select_stream_device and bf_miso_stream_device dispatched on: out[0..9] the plan as above (for bf_miso_stream_device
- *   the one-beam plan of bf_plan_das(algo, n, 1, 0, 1, max_whole)), out[10] the kernel (0 stream_map_kernel, 1 das_select_kernel,
- *   2 das_select_kernel with history, 3 stream_beam_kernel), out[11] the algorithm.  The kernel's template arguments are
+ *   the one-beam plan of bf_plan_das(algo, n, 1, 0, 1, max_whole)), out[10] the kernel (0 das_mimo_kernel with history, 1 das_select_kernel,
+ *   2 das_select_kernel with history, 3 das_miso_kernel with history), out[11] the algorithm.  The kernel's template arguments are
  *   (out[11], out[0], out[6]).  -1 for out == NULL and before the first such launch; a call that was refused leaves the record alone. */
 int bf_plan_das_stream(int algo, int n, int frames, int dir_begin, int dir_end, int max_whole, int n_cus, long long out[10]);
 int bf_last_strided_plan(long long out[12]);

@@ -1,10 +1,10 @@
 """Cases for test_strided_cases.py (GPU) and test_strided_cases_host.py (CPU): one row per instantiation and tiling class of the three
 kernel templates of csrc/das_strided.hip that the stream and listed-direction calls run on,
 
-    stream_map_kernel<ALGO, NC, DPW>        pad / lerp, NC 1 2 4 8 16, DPW 1 4                                           20
+    das_mimo_kernel<ALGO, NC, DPW, true>    pad / lerp, NC 1 2 4 8 16, DPW 1 4 (HIST = true: the stream maps)            20
     das_select_kernel<ALGO, NC, DPW, HIST>  pad / lerp / hybrid / fir_vec without HIST, pad / lerp with it; DPW 1 4,
                                             2 in place of 4 for hybrid at NC 16                                     40 + 20
-    stream_beam_kernel<ALGO, NC>            pad / lerp                                                                   10
+    das_miso_kernel<ALGO, NC, true>         pad / lerp (HIST = true: the stream beams)                                   10
 
 with the sizes that reach each, a restatement of the two planner functions they depend on (size_strided and tile_strided of
 csrc/das_plan.cpp), the deterministic inputs of every row and their expected outputs from the committed C checker.
@@ -63,7 +63,7 @@ def _rows():
             dpw = 2 if (algo == "hybrid" and NC == 16) else 4
             rows.append(_row("sel_%s_nc%d_dpw1" % (algo, NC), "select", algo, NC, 1, "one", "k2+", 5, 12, 16, 2100))
             rows.append(_row("sel_%s_nc%d_dpw%d" % (algo, NC, dpw), "select", algo, NC, dpw, "several", "k1", CHUNKED_N[NC], 12, 8, 2053))
-        # ---- stream_beam_kernel: NC 1 / 2 on the strided geometry, NC 4 .. 16 on the shifted-copies geometry (chunks of at most 16 microphones;
+        # ---- das_miso_kernel<.., true>: NC 1 / 2 on the strided geometry, NC 4 .. 16 on the shifted-copies geometry (chunks of at most 16 microphones;
         # lerp at NC 16 holds 4 rows per chunk unless n is a multiple of 4, so one chunk is 3 microphones)
         for algo in PLAIN:
             rows.append(_row("beam_%s_nc%d_one" % (algo, NC), "beam", algo, NC, None, "one", None, 3, 6, 2, None, "all"))

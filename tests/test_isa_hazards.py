@@ -134,6 +134,79 @@ def test_renumbered_comparison_forgives_register_numbers_and_nothing_else(iseq):
         assert len(diffs) == 1 and needle in diffs[0], diffs
 
 
+FAKE_RENAMED = """
+%(name)s:
+	s_load_dwordx2 s[10:11], %(ptr)s, 0x0
+	s_load_dword s12, %(ptr)s, %(implicit)s
+	s_load_dword s13, s[10:11], %(other)s
+	s_endpgm
+	.amdhsa_kernel %(name)s
+		.amdhsa_kernarg_size %(size)d
+		.amdhsa_user_sgpr_dispatch_ptr %(dispatch)d
+		.amdhsa_user_sgpr_queue_ptr %(queue)d
+		.amdhsa_user_sgpr_kernarg_segment_ptr 1
+	.end_amdhsa_kernel
+.Lfunc_end0:
+	.size	%(name)s, .Lfunc_end0-%(name)s
+	.amdgpu_metadata
+---
+amdhsa.kernels:
+  - .agpr_count:     0
+    .group_segment_fixed_size: 0
+    .name:           %(name)s
+    .private_segment_fixed_size: 0
+    .sgpr_count:     12
+    .vgpr_count:     4
+    .vgpr_spill_count: 0
+...
+	.end_amdgpu_metadata
+"""
+
+
+@pytest.mark.parametrize("dispatch,queue,ptr", [(0, 0, "s[0:1]"), (1, 0, "s[2:3]"), (0, 1, "s[2:3]"), (1, 1, "s[4:5]")])
+def test_renamed_comparison_forgives_symbol_argument_size_and_argument_offsets_only(iseq, dispatch, queue, ptr):
+    """(the kernel-argument pointer follows the dispatch and queue pointers where the descriptor enables them)"""
+    base = dict(dispatch=dispatch, queue=queue, ptr=ptr)
+    old = FAKE_RENAMED % dict(base, name="_Z5alphaPf", implicit="0xb4", other="0x10", size=424)
+    moved = dict(base, name="_Z5alphaPfi", implicit="0xc4", other="0x10", size=440)
+    new = FAKE_RENAMED % moved
+    assert iseq.kernarg_pointer(old, "_Z5alphaPf") == ptr
+    if ptr != "s[0:1]":    # the same loads through a pair that is NOT the entry pair of this descriptor keep their offsets
+        wrong = dict(moved, dispatch=0, queue=0)
+        assert iseq.compare(FAKE_RENAMED % dict(wrong, name="_Z5alphaPf", implicit="0xb4", size=424), FAKE_RENAMED % wrong, renamed={"_Z5alphaPf": "_Z5alphaPfi"})[0]
+    diffs, common = iseq.compare(old, new)
+    assert common == 0 and len(diffs) == 2, diffs                                  # without the map: two unrelated kernels
+    counts = {}
+    diffs, common = iseq.compare(old, new, renamed={"_Z5alphaPf": "_Z5alphaPfi"}, argument_offsets=counts)
+    assert common == 1 and not diffs, diffs
+    assert counts == {"_Z5alphaPfi": 1}                                            # reported apart: one load, its offset only
+    for mode in (False, True):
+        # a load through any other pointer keeps its offset, and so does everything else
+        diffs, _ = iseq.compare(old, FAKE_RENAMED % dict(moved, other="0x14"), renumbered=mode, renamed={"_Z5alphaPf": "_Z5alphaPfi"})
+        assert len(diffs) == 1 and "0x10" in diffs[0] and "0x14" in diffs[0], diffs
+    same_name = FAKE_RENAMED % dict(moved, name="_Z5alphaPf")
+    assert len(iseq.compare(old, same_name)[0]) == 1                               # a kernel that was not renamed gets none of this
+
+
+@pytest.mark.parametrize("text,needle", [
+    ("alpha<0> -> alpha<0, true>\n# a comment\n\nbeta -> beta2  # another\n", None),
+    ("alpha<0> alpha<0, true>\n", "not `OLD -> NEW`"),
+    ("gamma -> beta2\n", "OLD has no kernel gamma"),
+    ("beta -> gamma\n", "NEW has no kernel gamma"),
+    ("beta -> beta2\nalpha<0> -> beta2\n", "named twice"),
+])
+def test_rename_file_errors_name_the_line(iseq, tmp_path, text, needle):
+    p = tmp_path / "renamed.txt"
+    p.write_text(text)
+    demangle = lambda names: [{"_a": "alpha<0>", "_b": "beta", "_a2": "alpha<0, true>", "_b2": "beta2"}[n] for n in names]
+    if needle is None:
+        assert iseq.load_renamed(str(p), ["_a", "_b"], ["_a2", "_b2"], demangle) == {"_a": "_a2", "_b": "_b2"}
+    else:
+        with pytest.raises(ValueError, match=needle) as e:
+            iseq.load_renamed(str(p), ["_a", "_b"], ["_a2", "_b2"], demangle)
+        assert "line %d" % (text.count("\n")) in str(e.value)
+
+
 def test_no_register_with_a_read_in_flight_is_touched(chk, asm):
     kernels, bad = chk.scan(asm)
     assert kernels >= 43
@@ -171,12 +244,18 @@ def test_every_default_plan_instantiation_is_scanned_and_none_that_pipelines_rea
 
 def test_no_instantiation_outside_the_default_plan_is_compiled(chk, asm):
     """Nothing plan_das cannot choose is compiled: the other algorithm of each pair kernel (das_pair_kernel is pad, das_pair2_kernel
-    lerp), the quad + DPP strided kernel, and the strided kernel for pad / lerp beyond 128 samples (4 / 8 / 16 segments)."""
+    lerp), the quad + DPP strided kernel (it was a trailing `true` where HIST now stands; the exact list below leaves it no room),
+    and the strided map kernel for pad / lerp beyond 128 samples (4 / 8 / 16 segments) WITHOUT history -- with it
+    (das_mimo_kernel<.., HIST = true>, the continuous-stream maps) every size is the strided kernel's.  No das_mimo_kernel exists
+    outside the 58 listed: 38 without history (pad / lerp at NC 1, 2; the three FIR flavours at every NC; DPW 1 and 4) and 20 with."""
     every = chk.demangle(list(chk.metadata(asm)))
     retired = [n for n in every if n in ("bf::copies::das_pair_kernel<1>", "bf::copies::das_pair2_kernel<0>") or
-               n.startswith("bf::das_mimo_kernel<") and (n.endswith(", true>") or re.match(r"bf::das_mimo_kernel<[01], (4|8|16),", n))]
+               re.match(r"bf::das_mimo_kernel<[01], (4|8|16), \d+, false>", n)]
     assert not retired, retired
-    assert "bf::das_mimo_kernel<0, 2, 1>" in every and "bf::das_mimo_kernel<2, 4, 1>" in every   # (the names are matched as demangled)
+    want = ["bf::das_mimo_kernel<%d, %d, %d, false>" % (a, nc, dpw) for a in range(5) for nc in (1, 2, 4, 8, 16) for dpw in (1, 4) if a >= 2 or nc <= 2]
+    want += ["bf::das_mimo_kernel<%d, %d, %d, true>" % (a, nc, dpw) for a in (0, 1) for nc in (1, 2, 4, 8, 16) for dpw in (1, 4)]
+    assert len(want) == 38 + 20
+    assert sorted(n for n in every if n.startswith("bf::das_mimo_kernel<")) == sorted(want)     # (the names are matched as demangled)
 
 
 def test_hardwired_quads_survive_between_the_two_statements_of_a_mic(chk, asm):

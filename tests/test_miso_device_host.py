@@ -134,8 +134,9 @@ def asm(tmp_path_factory):
 
 
 def test_every_miso_instantiation_fits_sixteen_waves_without_scratch(asm):
-    """das_miso_kernel<ALGO, NC>, 5 algorithms x NC 1, 2, 4, 8, 16: compiled, no scratch, a 1024-thread workgroup allowed and at most
-    128 VGPRs (16 waves of one workgroup share the CU's four SIMDs: four waves per SIMD)."""
+    """das_miso_kernel<ALGO, NC, HIST>, 5 algorithms x NC 1, 2, 4, 8, 16 without history and pad / lerp x NC with it (25 + 10, and no
+    other): compiled, no scratch, a 1024-thread workgroup allowed and at most 128 VGPRs (16 waves of one workgroup share the CU's four
+    SIMDs: four waves per SIMD)."""
     chk, path = asm
     md = chk.metadata(path)
     text = open(path).read()
@@ -145,10 +146,11 @@ def test_every_miso_instantiation_fits_sixteen_waves_without_scratch(asm):
         size = re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk)
         if name and size:
             wg[name.group(1)] = int(size.group(1))
-    names = [n for n in md if "das_miso_kernel" in n]
+    names = list(md)
     short = dict(zip(chk.demangle(names), names))
-    want = ["bf::das_miso_kernel<%d, %d>" % (a, nc) for a in range(5) for nc in (1, 2, 4, 8, 16)]
-    assert sorted(short) == sorted(want)
+    want = ["bf::das_miso_kernel<%d, %d, false>" % (a, nc) for a in range(5) for nc in (1, 2, 4, 8, 16)]
+    want += ["bf::das_miso_kernel<%d, %d, true>" % (a, nc) for a in (0, 1) for nc in (1, 2, 4, 8, 16)]
+    assert sorted(n for n in short if n.startswith("bf::das_miso_kernel<")) == sorted(want)
     for w in want:
         m = md[short[w]]
         assert m["spill"] == 0 and m["scratch"] == 0, (w, m)

@@ -1,5 +1,5 @@
 """CPU: the host-side contract of the continuous-stream calls (bf_stream_history, bf_miso_stream_device, bf_das_stream_device,
-bf_get_pad_table), StreamBeamformer's argument checks and the gfx950 resources of stream_beam_kernel / stream_map_kernel.
+bf_get_pad_table), StreamBeamformer's argument checks and the gfx950 resources of das_miso_kernel / das_mimo_kernel with HIST.
 
 Every argument is checked before device bring-up, so the refusals run without a GPU.  One refusal is not here: `H > hop` (and the
 clamped-table refusal) needs a loaded table, and a table can only be loaded onto a device -- tests/test_stream.py has both."""
@@ -158,8 +158,9 @@ def asm(tmp_path_factory):
 
 
 def test_stream_kernels_fit_sixteen_waves_without_scratch(asm):
-    """stream_beam_kernel<ALGO, NC> and stream_map_kernel<ALGO, NC, DPW>, pad and lerp only, NC 1, 2, 4, 8, 16 (maps: DPW 1 and 4):
-    compiled with the build's flags, no scratch, no spills, at most 128 VGPRs, and a 1024-thread workgroup allowed."""
+    """das_miso_kernel<ALGO, NC, true> and das_mimo_kernel<ALGO, NC, DPW, true> (HIST: the continuous-stream mode), pad and lerp only,
+    NC 1, 2, 4, 8, 16 (maps: DPW 1 and 4): compiled with the build's flags, no scratch, no spills, at most 128 VGPRs, and a 1024-thread
+    workgroup allowed."""
     chk, path = asm
     md = chk.metadata(path)
     text = open(path).read()
@@ -169,11 +170,12 @@ def test_stream_kernels_fit_sixteen_waves_without_scratch(asm):
         size = re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk)
         if name and size:
             wg[name.group(1)] = int(size.group(1))
-    names = [n for n in md if "stream_beam_kernel" in n or "stream_map_kernel" in n]
+    names = list(md)
     short = dict(zip(chk.demangle(names), names))
-    want = ["bf::stream_beam_kernel<%d, %d>" % (a, nc) for a in (0, 1) for nc in (1, 2, 4, 8, 16)]
-    want += ["bf::stream_map_kernel<%d, %d, %d>" % (a, nc, dpw) for a in (0, 1) for nc in (1, 2, 4, 8, 16) for dpw in (1, 4)]
-    assert sorted(short) == sorted(want)
+    want = ["bf::das_miso_kernel<%d, %d, true>" % (a, nc) for a in (0, 1) for nc in (1, 2, 4, 8, 16)]
+    want += ["bf::das_mimo_kernel<%d, %d, %d, true>" % (a, nc, dpw) for a in (0, 1) for nc in (1, 2, 4, 8, 16) for dpw in (1, 4)]
+    hist = [n for n in short if re.match(r"bf::das_mi[sm]o_kernel<.*, true>$", n)]
+    assert sorted(hist) == sorted(want)                 # the exact list: no other instantiation with history exists
     for w in want:
         m = md[short[w]]
         assert m["spill"] == 0 and m["scratch"] == 0, (w, m)

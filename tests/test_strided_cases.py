@@ -1,5 +1,5 @@
-"""GPU (-m gpu): every row of tests/strided_cases.py -- each instantiation and tiling class of stream_map_kernel, das_select_kernel and
-stream_beam_kernel (csrc/das_strided.hip) -- through bf_das_stream_device, bf_das_select_device, bf_das_select_stream_device and
+"""GPU (-m gpu): every row of tests/strided_cases.py -- each instantiation and tiling class of das_mimo_kernel<.., true>, das_select_kernel and
+das_miso_kernel<.., true> (csrc/das_strided.hip; true = HIST, the continuous-stream mode) -- through bf_das_stream_device, bf_das_select_device, bf_das_select_stream_device and
 bf_miso_stream_device.  Each row asserts
 
   1. what ran: bf_last_strided_plan after the launch names the row's kernel, algorithm, NC, DPW, chunk count and tile size, and
@@ -127,7 +127,7 @@ def _equal(got, want, row):
     assert util.bits_differ(got, want, nan_is_nan=hostile) == ""
 
 
-# ------------------------------------------------------------------ stream_map_kernel
+# ------------------------------------------------------------------ das_mimo_kernel<.., true>
 
 @_rows("map")
 def test_stream_map_row(nat, oracle_lib, row):
@@ -190,7 +190,7 @@ def test_select_stream_row(nat, oracle_lib, row):
         _equal(shared, want0, row)
 
 
-# ------------------------------------------------------------------ stream_beam_kernel
+# ------------------------------------------------------------------ das_miso_kernel<.., true>
 
 @_rows("beam")
 def test_stream_beam_row(nat, oracle_lib, row):
@@ -222,7 +222,7 @@ def test_stream_beam_row(nat, oracle_lib, row):
 def test_every_instantiation_ran(capsys):
     ran = set(RAN.values())
     with capsys.disabled():
-        print("\n[strided cases] %d rows ran %d of the 90 instantiations of stream_map_kernel, das_select_kernel and stream_beam_kernel" % (len(RAN), len(ran)))
+        print("\n[strided cases] %d rows ran %d of the 90 instantiations of das_mimo_kernel<.., true>, das_select_kernel and das_miso_kernel<.., true>" % (len(RAN), len(ran)))
     assert ran <= sc.all_instantiations()
     if len(RAN) == len(sc.ROWS):                                                 # (a run of a few rows, -k, has nothing to claim)
         assert sorted(map(str, sc.all_instantiations() - ran)) == []

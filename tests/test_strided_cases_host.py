@@ -1,7 +1,7 @@
 """CPU: tests/strided_cases.py against the library's planner exports (bf_plan_das_stream, bf_plan_das_select, bf_plan_das; no GPU).
 
   * every row's declared (NC, DPW, chunks, tile class) is what the export returns for its sizes at 256 compute units;
-  * the rows cover all 90 instantiations of stream_map_kernel, das_select_kernel and stream_beam_kernel and every class
+  * the rows cover all 90 instantiations of das_mimo_kernel<.., true>, das_select_kernel and das_miso_kernel<.., true> and every class
     strided_cases.all_classes lists; what is missing fails with its name;
   * size_strided and tile_strided restated in Python equal the two exports on a few thousand random legal shapes, no shape leaves the
     90 tuples, DPW > 1 exactly when there are several chunks, LDS <= 160 KiB, lead >= history in stream mode;

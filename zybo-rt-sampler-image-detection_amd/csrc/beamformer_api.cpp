@@ -548,8 +548,8 @@ void export_plan(const bf::DasPlan& p, long long* out)
     out[5] = p.waves; out[6] = p.dpw; out[7] = p.tile_dirs; out[8] = p.n_tiles; out[9] = (long long)p.lds_bytes;
 }
 
-// bf_last_strided_plan's record of a launch that was enqueued: kernel 0 = stream_map_kernel, 1 = das_select_kernel, 2 = das_select_kernel with
-// history, 3 = stream_beam_kernel.
+// bf_last_strided_plan's record of a launch that was enqueued: kernel 0 = das_mimo_kernel with history, 1 = das_select_kernel, 2 = das_select_kernel with
+// history, 3 = das_miso_kernel with history.
 enum StridedKernel { STRIDED_STREAM_MAP = 0, STRIDED_SELECT, STRIDED_SELECT_HIST, STRIDED_STREAM_BEAM };
 int launched_strided(hipError_t e, const char* call, StridedKernel kernel, int algo, const bf::DasPlan& plan)
 {

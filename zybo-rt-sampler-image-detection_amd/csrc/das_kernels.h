@@ -105,10 +105,10 @@ hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int3
 // samples earlier; null = silence).  stream_history: samples of history a table needs (max_whole for pad, max_whole + 1 for lerp,
 // -1 for the other flavours); the launches want history <= hop <= N.
 int stream_history(int algo, int max_whole);
-// Maps: always the strided layout (stream_map_kernel); `plan` comes from plan_stream_maps, never from plan_das.
+// Maps: always the strided layout (das_mimo_kernel<.., HIST = true>); `plan` comes from plan_stream_maps, never from plan_das.
 int plan_stream_maps(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why);
 hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, hipStream_t stream);
-// Beams (stream_beam_kernel): `plan` is the one-direction, one-frame plan launch_miso_batch takes.
+// Beams (das_miso_kernel<.., HIST = true>): `plan` is the one-direction, one-frame plan launch_miso_batch takes.
 hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
                                long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream);
 

@@ -12,7 +12,8 @@
 //     LDS, one lane per direction), so the images are bit-identical to the CPU result.
 // Two families of kernels (DESIGN.md section 4.1 has the measurements behind each choice):
 //   * das_strided.hip: das_mimo_kernel / das_miso_kernel ("strided": lane l owns samples l, l+64, ...): any N <= 1024, any tap count,
-//     single beams; table entries by vector load + v_readlane.  The first implementation; now the general fallback.
+//     single beams; table entries by vector load + v_readlane.  The first implementation; now the general fallback.  With their
+//     `bool HIST` (and das_select_kernel's) they are also the continuous-stream maps and beams: history in front of every staged row.
 //   * copies::das_copies_kernel ("shifted copies": every staged row kept in copies shifted by one sample each, lane l owns
 //     the quad 4l..4l+3): pad / lerp for 128 < N <= 1024 and the 8-tap FIR flavours for N <= 256.  pad / lerp sweep a mic
 //     over the wave's 8 directions and re-read its quad from LDS only when the delay changes from one direction to the

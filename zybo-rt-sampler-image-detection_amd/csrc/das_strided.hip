@@ -1,6 +1,6 @@
 // das_strided.hip -- the strided delay-and-sum kernels (lane l owns samples l, l+64, ...): maps (das_mimo_kernel), steered beams
-// (das_miso_kernel), their continuous-stream twins (stream_map_kernel, stream_beam_kernel) and the map at listed directions
-// (das_select_kernel).  das_kernels.hip has the overview.
+// (das_miso_kernel) and the map at listed directions (das_select_kernel), each with a `bool HIST` for the continuous-stream mode.
+// das_kernels.hip has the overview.
 #include "das_device.h"
 
 namespace bf {
@@ -198,9 +198,35 @@ __device__ __forceinline__ void accumulate(float (&acc)[NC], const float* lds, c
     }
 }
 
-template <int ALGO, int NC, int DPW>
-__global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a)
+// ---- continuous-stream mode (bf_das_stream_device / bf_miso_stream_device / bf_das_select_stream_device): HIST = true ------------
+// The kernels below with one change: the `hist` columns in front of every staged row, [lead - hist, lead), hold the samples that
+// precede the window -- row[hop - hist, hop) of the previous frame (frame f - 1 of the launch; `prev0` for frame 0, zeros when that
+// is null) -- instead of zeros, and accumulate<.., HIST = true> drops lerp's i >= 0 guard.  A delayed read lead - p (- 1) + k then
+// finds x(k - p) for every k in [0, N): the first p outputs of a window are no longer sums over a growing subset of the
+// microphones.  hist = max_whole (pad) or max_whole + 1 (lerp); the host checks hist <= hop <= N and hist <= lead
+// (stream_launch_ok), so the slice lies inside the previous frame's row and inside the row's lead.  The slice starts at an arbitrary
+// sample (hop - hist), so it is copied with plain dword loads; it is hist / N of the row's bytes.
+__device__ __forceinline__ void stage_chunk_stream(float* lds, const KArgs& a, const int32_t* __restrict__ mics, const float* __restrict__ frame,
+                                                   const float* __restrict__ prev, int hop, int hist, int m0, int mc, int wave, int nwaves, int lane)
 {
+    stage_chunk(lds, a, mics, frame, m0, mc, wave, nwaves, lane);
+    for (int r = wave; r < mc; r += nwaves) {
+        float* dst = lds + r * a.row_stride + (a.lead - hist);
+        if (prev != nullptr) {   // (workgroup-uniform)
+            const float* src = prev + (size_t)mics[m0 + r] * a.n_samples + (hop - hist);
+            for (int i = lane; i < hist; i += kWave) dst[i] = src[i];
+        } else {
+            for (int i = lane; i < hist; i += kWave) dst[i] = 0.0f;
+        }
+    }
+}
+
+// Maps: a workgroup owns one frame and one tile of the directions [a.dir_begin, a.dir_end).  HIST = false is the window-local map
+// (prev0 / hop / hist unused, the reference's tail rule for the mean power), HIST = true the continuous-stream map.
+template <int ALGO, int NC, int DPW, bool HIST>
+__global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a, const float* __restrict__ prev0, int hop, int hist)
+{
+    static_assert(!HIST || ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -211,7 +237,8 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
     if (tile_begin >= a.dir_end) return;  // padding tile (n_tiles is rounded up to a multiple of 8)
     const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
 
-    // zero the whole LDS image once: the lead/tail columns and unused rows stay zero for the kernel's lifetime
+    // zero the whole LDS image once: the lead / tail columns (HIST: the columns in front of the history and behind the samples) and
+    // the unused rows stay zero for the kernel's lifetime
     {
         const int total4 = (a.mic_chunk * a.row_stride) >> 2;
         float4* z = reinterpret_cast<float4*>(lds);
@@ -219,7 +246,9 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
     }
     __syncthreads();
 
-    const float* __restrict__ frame_sig = signals + (size_t)frame * a.m_total * a.n_samples;
+    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
+    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
+    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
     float* __restrict__ img = images + (size_t)frame * a.image_stride;
     const int group = nwaves * DPW;
     float* scratch = lds + a.scratch_off + wave * (a.pbw * a.srow);
@@ -244,7 +273,8 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
             const int mc = min(a.mic_chunk, a.n_mics - m0);
             if (a.n_chunks > 1 || g0 == tile_begin) {
                 if (a.n_chunks > 1 && (ch > 0 || g0 != tile_begin)) __syncthreads();  // previous readers done
-                stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
+                if constexpr (HIST) stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);   // the history is refilled with every chunk
+                else stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
                 __syncthreads();
             }
 #pragma unroll
@@ -260,19 +290,19 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
                     const int nm0 = nch * a.mic_chunk;
                     head = request_row_head<ALGO>(whole, frac, (size_t)nd * a.n_mics + nm0, min(a.mic_chunk, a.n_mics - nm0), lane);
                 }
-                if (d < tile_end) accumulate<ALGO, NC>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
+                if (d < tile_end) accumulate<ALGO, NC, HIST>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
             }
         }
 #pragma unroll
         for (int j = 0; j < DPW; ++j) {
             const int d = g0 + j * nwaves + wave;
             if (d < tile_end) {
-                park_squares<NC, true>(acc[j], scratch + filled * a.srow, a, d, lane);
-                if (++filled == a.pbw) { flush_powers<true>(scratch, filled, img, a, lane); filled = 0; }
+                park_squares<NC, !HIST>(acc[j], scratch + filled * a.srow, a, d, lane);
+                if (++filled == a.pbw) { flush_powers<!HIST>(scratch, filled, img, a, lane); filled = 0; }
             }
         }
     }
-    if (filled > 0) flush_powers<true>(scratch, filled, img, a, lane);
+    if (filled > 0) flush_powers<!HIST>(scratch, filled, img, a, lane);
 }
 
 // Steered beams, raw out[N] (miso_pad / miso_lerp / miso_convolve_*, pad_and_sum.c:54-70 ...).  Workgroup id = frame * groups +
@@ -285,11 +315,14 @@ __global__ void __launch_bounds__(1024) das_mimo_kernel(BF_TABLE_PARAMS, KArgs a
 //                                 against `entries` (status 1: outside the table, 2: FIR_VEC offset not a multiple of T);
 //                                 a rejected beam reads no table entry and its N samples are NaN.  gain != 0 scales the
 //                                 beam as api.c:519-523 does, (out / n) * gain, two float32 roundings.
-template <int ALGO, int NC>
+//   stream path (launch_stream_beams): HIST = true, the device path with the history staged in front of every row; it has
+//                                 neither a.miso_row nor `miso_init`, and `offsets` is never null.
+template <int ALGO, int NC, bool HIST>
 __global__ void __launch_bounds__(1024) das_miso_kernel(BF_TABLE_PARAMS, const float* __restrict__ miso_init, float* __restrict__ miso_out, KArgs a,
                                                         const int32_t* __restrict__ offsets, int beams, int* __restrict__ status,
-                                                        long long entries, float gain, int out_stride)
+                                                        long long entries, float gain, int out_stride, const float* __restrict__ prev0, int hop, int hist)
 {
+    static_assert(!HIST || ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -300,10 +333,13 @@ __global__ void __launch_bounds__(1024) das_miso_kernel(BF_TABLE_PARAMS, const f
     const bool live = beam < beams;                                           // the last group may be partial
     const size_t slot = (size_t)frame * beams + beam;
 
-    // this wave's table row (wave-uniform) and its verdict
-    long long row = a.miso_row;
+    // This wave's table row (wave-uniform) and its verdict.  judge_offset's rule (below), written out in 64 bits as these kernels
+    // always had it: taken from judge_offset (32-bit, or with the width as a template argument) the same rule compiles to other
+    // code -- in all 35 instantiations, or in the five of FIR_VEC -- and this text keeps each of them, instruction for instruction,
+    // what it was as two kernels (profiles/strided_fold_isa_equal.txt).
+    long long row = HIST ? 0 : a.miso_row;
     int verdict = 0;
-    if (offsets != nullptr && live) {
+    if ((HIST || offsets != nullptr) && live) {
         const long long off = __builtin_amdgcn_readfirstlane(offsets[slot]);
         const long long per = ALGO == ALGO_FIR_VEC ? a.n_taps : 1;
         if (off < 0 || off + (long long)a.n_mics * per > entries) verdict = 1;
@@ -312,24 +348,28 @@ __global__ void __launch_bounds__(1024) das_miso_kernel(BF_TABLE_PARAMS, const f
     }
     const bool run = live && verdict == 0;
 
+    // zero the whole LDS image once, as das_mimo_kernel does
     {
         const int total4 = (a.mic_chunk * a.row_stride) >> 2;
         float4* z = reinterpret_cast<float4*>(lds);
         for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
-    const float* __restrict__ frame_sig = signals + (size_t)frame * a.m_total * a.n_samples;
+    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
+    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
+    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
     float acc[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c)
-        acc[c] = (miso_init != nullptr && lane + c * kWave < a.n_samples) ? miso_init[lane + c * kWave] : 0.0f;
+        acc[c] = (!HIST && miso_init != nullptr && lane + c * kWave < a.n_samples) ? miso_init[lane + c * kWave] : 0.0f;
     for (int ch = 0; ch < a.n_chunks; ++ch) {
         const int m0 = ch * a.mic_chunk;
         const int mc = min(a.mic_chunk, a.n_mics - m0);
         if (ch > 0) __syncthreads();
-        stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
+        if constexpr (HIST) stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);
+        else stage_chunk(lds, a, mics, frame_sig, m0, mc, wave, nwaves, lane);
         __syncthreads();
-        if (run) accumulate<ALGO, NC>(acc, lds, a, whole, frac, taps, (size_t)row, m0, mc, lane);
+        if (run) accumulate<ALGO, NC, HIST>(acc, lds, a, whole, frac, taps, (size_t)row, m0, mc, lane);
     }
     if (!live) return;
     if (status != nullptr && lane == 0) status[slot] = verdict;
@@ -344,119 +384,18 @@ __global__ void __launch_bounds__(1024) das_miso_kernel(BF_TABLE_PARAMS, const f
     }
 }
 
-// ---- continuous-stream mode (bf_das_stream_device / bf_miso_stream_device) ----------------------------------------------
-// das_mimo_kernel / das_miso_kernel with one change: the `hist` columns in front of every staged row, [lead - hist, lead), hold
-// the samples that precede the window -- row[hop - hist, hop) of the previous frame (frame f - 1 of the launch; `prev0` for
-// frame 0, zeros when that is null) -- instead of zeros, and accumulate<.., HIST = true> drops lerp's i >= 0 guard.  A delayed
-// read lead - p (- 1) + k then finds x(k - p) for every k in [0, N): the first p outputs of a window are no longer sums over a
-// growing subset of the microphones.  hist = max_whole (pad) or max_whole + 1 (lerp); the host checks hist <= hop <= N and
-// hist <= lead, so the slice lies inside the previous frame's row and inside the row's lead.  The slice starts at an arbitrary
-// sample (hop - hist), so it is copied with plain dword loads; it is hist / N of the row's bytes.
-__device__ __forceinline__ void stage_chunk_stream(float* lds, const KArgs& a, const int32_t* __restrict__ mics, const float* __restrict__ frame,
-                                                   const float* __restrict__ prev, int hop, int hist, int m0, int mc, int wave, int nwaves, int lane)
-{
-    stage_chunk(lds, a, mics, frame, m0, mc, wave, nwaves, lane);
-    for (int r = wave; r < mc; r += nwaves) {
-        float* dst = lds + r * a.row_stride + (a.lead - hist);
-        if (prev != nullptr) {   // (workgroup-uniform)
-            const float* src = prev + (size_t)mics[m0 + r] * a.n_samples + (hop - hist);
-            for (int i = lane; i < hist; i += kWave) dst[i] = src[i];
-        } else {
-            for (int i = lane; i < hist; i += kWave) dst[i] = 0.0f;
-        }
-    }
-}
-
-template <int ALGO, int NC, int DPW>
-__global__ void __launch_bounds__(1024) stream_map_kernel(BF_TABLE_PARAMS, KArgs a, const float* __restrict__ prev0, int hop, int hist)
-{
-    static_assert(ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nwaves = (int)(blockDim.x >> 6);
-    const int tile = (int)(blockIdx.x % (unsigned)a.n_tiles);
-    const int frame = (int)(blockIdx.x / (unsigned)a.n_tiles);
-    const int tile_begin = a.dir_begin + tile * a.tile_dirs;
-    if (tile_begin >= a.dir_end) return;
-    const int tile_end = min(tile_begin + a.tile_dirs, a.dir_end);
-
-    // zero the whole LDS image once: the columns in front of the history and behind the samples stay zero
-    {
-        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
-        float4* z = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-
-    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
-    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
-    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
-    float* __restrict__ img = images + (size_t)frame * a.image_stride;
-    const int group = nwaves * DPW;
-    float* scratch = lds + a.scratch_off + wave * (a.pbw * a.srow);
-    int filled = 0;   // wave-uniform
-
-    // work items and the table-row head requested one item ahead: as das_mimo_kernel
-    auto item_dir = [&](int g0_, int j_) { return g0_ + j_ * nwaves + wave; };
-    RowHead head;
-    if (item_dir(tile_begin, 0) < tile_end)
-        head = request_row_head<ALGO>(whole, frac, (size_t)item_dir(tile_begin, 0) * a.n_mics, min(a.mic_chunk, a.n_mics), lane);
-
-    for (int g0 = tile_begin; g0 < tile_end; g0 += group) {
-        float acc[DPW][NC];
-#pragma unroll
-        for (int j = 0; j < DPW; ++j)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[j][c] = 0.0f;
-
-        for (int ch = 0; ch < a.n_chunks; ++ch) {
-            const int m0 = ch * a.mic_chunk;
-            const int mc = min(a.mic_chunk, a.n_mics - m0);
-            if (a.n_chunks > 1 || g0 == tile_begin) {
-                if (a.n_chunks > 1 && (ch > 0 || g0 != tile_begin)) __syncthreads();  // previous readers done
-                stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);   // the history is refilled with every chunk
-                __syncthreads();
-            }
-#pragma unroll
-            for (int j = 0; j < DPW; ++j) {
-                const int d = g0 + j * nwaves + wave;  // wave-uniform
-                int ng0 = g0, nch = ch, nj = j + 1;
-                if (nj == DPW) { nj = 0; nch = ch + 1; if (nch == a.n_chunks) { nch = 0; ng0 = g0 + group; } }
-                const int nd = item_dir(ng0, nj);
-                const RowHead cur = head;
-                head = RowHead();
-                if (nd < tile_end) {
-                    const int nm0 = nch * a.mic_chunk;
-                    head = request_row_head<ALGO>(whole, frac, (size_t)nd * a.n_mics + nm0, min(a.mic_chunk, a.n_mics - nm0), lane);
-                }
-                if (d < tile_end) accumulate<ALGO, NC, true>(acc[j], lds, a, whole, frac, taps, (size_t)d * a.n_mics, m0, mc, lane, cur);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < DPW; ++j) {
-            const int d = g0 + j * nwaves + wave;
-            if (d < tile_end) {
-                park_squares<NC>(acc[j], scratch + filled * a.srow, a, d, lane);
-                if (++filled == a.pbw) { flush_powers(scratch, filled, img, a, lane); filled = 0; }
-            }
-        }
-    }
-    if (filled > 0) flush_powers(scratch, filled, img, a, lane);
-}
-
 // ---- map values at listed directions (bf_das_select_device / bf_das_select_stream_device) ---------------------------------
-// das_mimo_kernel (HIST = false) / stream_map_kernel (HIST = true) with one indirection: a workgroup owns one frame and one tile of
-// the LIST [a.dir_begin, a.dir_end) = [0, count), and the table row of list index b is offsets[b] -- read wave-uniformly and judged
-// as das_miso_kernel judges a beam's offset (1: outside the table, 2: FIR_VEC offset not a multiple of T).  A rejected entry reads
-// nothing from the table and its power is a quiet NaN.  park_squares carries the list index where the map kernels carry the
+// das_mimo_kernel<.., HIST> with one indirection: a workgroup owns one frame and one tile of the LIST [a.dir_begin, a.dir_end) =
+// [0, count), and the table row of list index b is offsets[b] -- read wave-uniformly and judged as das_miso_kernel judges a beam's
+// offset (judge_offset: 1 outside the table, 2 a FIR_VEC offset that is no multiple of T).  A rejected entry reads nothing
+// from the table and its power is a quiet NaN.  park_squares carries the list index where the map kernels carry the
 // direction, so flush_powers writes out[frame][b]; a value is one wave's sum in microphone order and one lane's in sample order,
 // whatever the tiling, DPW and the wave count are.
 // Prefetch: the entries of a wave's NEXT group are requested when the current group starts (a group later they cost no wait), and
 // the table-row head of item i + 1 before item i is computed, as in das_mimo_kernel.
 struct ListedRow {
     long long row = 0;   // table row start, in entries (FIR_VEC: in rows of T floats)
-    int verdict = 0;
+    int verdict = 0;     // 1: outside the table, 2: FIR_VEC offset not a multiple of T
 };
 
 template <int ALGO>
@@ -570,97 +509,51 @@ __global__ void __launch_bounds__(1024) das_select_kernel(BF_TABLE_PARAMS, KArgs
     if (filled > 0) flush_powers<!HIST>(scratch, filled, out, a, lane);
 }
 
-// Workgroup id = frame * groups + group, one wave per beam, offsets / status / gain / NaN beams as das_miso_kernel's device path.
-template <int ALGO, int NC>
-__global__ void __launch_bounds__(1024) stream_beam_kernel(BF_TABLE_PARAMS, float* __restrict__ beam_out, KArgs a, const int32_t* __restrict__ offsets,
-                                                           int beams, int* __restrict__ status, long long entries, float gain, int out_stride,
-                                                           const float* __restrict__ prev0, int hop, int hist)
+// plan.nc as a template argument: f(std::integral_constant<int, NC>()).
+template <typename F>
+hipError_t dispatch_nc(int nc, F f)
 {
-    static_assert(ALGO == ALGO_PAD || ALGO == ALGO_LERP, "the FIR flavours read ahead of the window's end");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nwaves = (int)(blockDim.x >> 6);
-    const int groups = (beams + nwaves - 1) / nwaves;
-    const int frame = (int)(blockIdx.x / (unsigned)groups);
-    const int beam = (int)(blockIdx.x % (unsigned)groups) * nwaves + wave;   // wave-uniform
-    const bool live = beam < beams;                                           // the last group may be partial
-    const size_t slot = (size_t)frame * beams + beam;
-
-    long long row = 0;
-    int verdict = 0;
-    if (live) {
-        const long long off = __builtin_amdgcn_readfirstlane(offsets[slot]);
-        if (off < 0 || off + (long long)a.n_mics > entries) verdict = 1;
-        row = off;
-    }
-    const bool run = live && verdict == 0;
-
-    {
-        const int total4 = (a.mic_chunk * a.row_stride) >> 2;
-        float4* z = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < total4; i += blockDim.x) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-    const size_t frame_floats = (size_t)a.m_total * a.n_samples;
-    const float* __restrict__ frame_sig = signals + (size_t)frame * frame_floats;
-    const float* __restrict__ prev_sig = frame > 0 ? frame_sig - frame_floats : prev0;
-    float acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.0f;
-    for (int ch = 0; ch < a.n_chunks; ++ch) {
-        const int m0 = ch * a.mic_chunk;
-        const int mc = min(a.mic_chunk, a.n_mics - m0);
-        if (ch > 0) __syncthreads();
-        stage_chunk_stream(lds, a, mics, frame_sig, prev_sig, hop, hist, m0, mc, wave, nwaves, lane);
-        __syncthreads();
-        if (run) accumulate<ALGO, NC, true>(acc, lds, a, whole, frac, taps, (size_t)row, m0, mc, lane);
-    }
-    if (!live) return;
-    if (status != nullptr && lane == 0) status[slot] = verdict;
-    float* __restrict__ out = beam_out + slot * (size_t)out_stride;
-    const float nan = __int_as_float(0x7fc00000);
-    const float fn = (float)a.n_mics;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        float v = acc[c];
-        if (gain != 0.0f) v = (v / fn) * gain;   // as das_miso_kernel: true division, two roundings
-        if (lane + c * kWave < a.n_samples) out[lane + c * kWave] = run ? v : nan;
-    }
-}
-
-template <int ALGO, int NC>
-hipError_t launch_mimo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
-{
-    if constexpr (!is_fir(ALGO) && NC >= 4) {
-        return hipErrorInvalidValue;                    // pad / lerp beyond 128 samples: shifted copies only (plan_das gives them no other layout)
-    } else {
-        auto go = [&](auto kernel) -> hipError_t {
-            return launch_with_lds(kernel, dim3((unsigned)plan.n_tiles * (unsigned)frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream, nullptr,
-                                   L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a);
-        };
-        switch (plan.dpw) {
-            case 1: return go(das_mimo_kernel<ALGO, NC, 1>);
-            case 4: return go(das_mimo_kernel<ALGO, NC, 4>);
-            default: return hipErrorInvalidValue;
-        }
-    }
-}
-
-template <int ALGO>
-hipError_t launch_mimo_algo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, int frames, hipStream_t stream)
-{
-    switch (plan.nc) {
-        case 1: return launch_mimo<ALGO, 1>(L, a, plan, frames, stream);
-        case 2: return launch_mimo<ALGO, 2>(L, a, plan, frames, stream);
-        case 4: return launch_mimo<ALGO, 4>(L, a, plan, frames, stream);
-        case 8: return launch_mimo<ALGO, 8>(L, a, plan, frames, stream);
-        case 16: return launch_mimo<ALGO, 16>(L, a, plan, frames, stream);
+    switch (nc) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 8: return f(std::integral_constant<int, 8>());
+        case 16: return f(std::integral_constant<int, 16>());
         default: return hipErrorInvalidValue;
     }
 }
 
+// The history the table needs (*hist) and whether a continuous-stream launch can supply it: pad or lerp, hist <= hop <= N, and rows
+// whose lead holds it.
+bool stream_launch_ok(const DasLaunch& L, const DasPlan& plan, int hop, int* hist)
+{
+    *hist = stream_history(L.algo, L.tab.max_whole);
+    return *hist >= 0 && hop >= *hist && hop <= L.n_samples && plan.lead >= *hist;
+}
+
+// das_mimo_kernel<ALGO, nc, dpw, HIST> of a plan_das (strided layout) or plan_stream_maps plan; d_prev / hop / hist are for HIST.
+template <int ALGO, bool HIST>
+hipError_t launch_mimo_algo(const DasLaunch& L, const DasPlan& plan, int frames, const float* d_prev, int hop, int hist, hipStream_t stream)
+{
+    const KArgs a = make_args(L, plan);
+    auto go = [&](auto kernel) -> hipError_t {
+        return launch_with_lds(kernel, dim3((unsigned)plan.n_tiles * (unsigned)frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream, nullptr,
+                               L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a, d_prev, hop, hist);
+    };
+    return dispatch_nc(plan.nc, [&](auto nc) -> hipError_t {
+        constexpr int NC = decltype(nc)::value;
+        if constexpr (!HIST && !is_fir(ALGO) && NC >= 4) {
+            return hipErrorInvalidValue;                    // pad / lerp beyond 128 samples: shifted copies only (plan_das gives them no other layout)
+        } else {
+            if (plan.dpw == 1) return go(das_mimo_kernel<ALGO, NC, 1, HIST>);
+            if (plan.dpw == 4) return go(das_mimo_kernel<ALGO, NC, 4, HIST>);
+            return hipErrorInvalidValue;
+        }
+    });
+}
+
 // The beams of one das_miso_kernel launch (MisoBatch{} = the host path: one frame, one beam at KArgs::miso_row, one wave).
+// prev / hop / hist are the stream path's.
 struct MisoBatch {
     const int32_t* offsets = nullptr;
     int frames = 1, beams = 1, waves = 1;
@@ -668,26 +561,21 @@ struct MisoBatch {
     long long entries = 0;
     float gain = 0.0f;
     int out_stride = 0;
+    const float* prev = nullptr;
+    int hop = 0, hist = 0;
 };
 
-template <int ALGO>
+template <int ALGO, bool HIST = false>
 hipError_t launch_miso_algo(const DasLaunch& L, const KArgs& a, const DasPlan& plan, const float* init_dev, float* out_dev, const MisoBatch& B,
                             hipStream_t stream)
 {
     const unsigned groups = (unsigned)((B.beams + B.waves - 1) / B.waves);
     const int out_stride = B.out_stride > 0 ? B.out_stride : L.n_samples;
-    auto go = [&](auto kernel) -> hipError_t {
-        return launch_with_lds(kernel, dim3((unsigned)B.frames * groups), dim3((unsigned)B.waves * kWave), plan.lds_bytes, stream, nullptr, L.signals, L.images,
-                               L.mics, L.tab.whole, L.tab.frac, L.tab.taps, init_dev, out_dev, a, B.offsets, B.beams, B.status, B.entries, B.gain, out_stride);
-    };
-    switch (plan.nc) {
-        case 1: return go(das_miso_kernel<ALGO, 1>);
-        case 2: return go(das_miso_kernel<ALGO, 2>);
-        case 4: return go(das_miso_kernel<ALGO, 4>);
-        case 8: return go(das_miso_kernel<ALGO, 8>);
-        case 16: return go(das_miso_kernel<ALGO, 16>);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_nc(plan.nc, [&](auto nc) -> hipError_t {
+        return launch_with_lds(das_miso_kernel<ALGO, decltype(nc)::value, HIST>, dim3((unsigned)B.frames * groups), dim3((unsigned)B.waves * kWave), plan.lds_bytes,
+                               stream, nullptr, L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, init_dev, out_dev, a, B.offsets, B.beams,
+                               B.status, B.entries, B.gain, out_stride, B.prev, B.hop, B.hist);
+    });
 }
 
 hipError_t launch_miso_any(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev, const MisoBatch& B,
@@ -705,63 +593,13 @@ hipError_t launch_miso_any(const DasLaunch& L, const DasPlan& plan, long long ro
     }
 }
 
-}  // namespace
-
-hipError_t launch_strided(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
+// The device path's batch (launch_miso_batch, launch_stream_beams); false: a batch neither launches.
+bool make_batch(const DasLaunch& L, const int32_t* d_offsets, int beams, long long entries, float gain, int out_stride, int* d_status, MisoBatch* B)
 {
-    const KArgs a = make_args(L, plan);
-    switch (L.algo) {
-        case ALGO_PAD: return launch_mimo_algo<ALGO_PAD>(L, a, plan, frames, stream);
-        case ALGO_LERP: return launch_mimo_algo<ALGO_LERP>(L, a, plan, frames, stream);
-        case ALGO_HYBRID: return launch_mimo_algo<ALGO_HYBRID>(L, a, plan, frames, stream);
-        case ALGO_FIR_NAIVE: return launch_mimo_algo<ALGO_FIR_NAIVE>(L, a, plan, frames, stream);
-        case ALGO_FIR_VEC: return launch_mimo_algo<ALGO_FIR_VEC>(L, a, plan, frames, stream);
-        default: return hipErrorInvalidValue;
-    }
+    B->offsets = d_offsets; B->frames = L.frames; B->beams = beams; B->waves = std::min(beams, kMisoWaves);
+    B->status = d_status; B->entries = entries; B->gain = gain; B->out_stride = out_stride;
+    return L.frames >= 1 && beams >= 1 && out_stride >= L.n_samples;
 }
-
-hipError_t launch_miso(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev,
-                       hipStream_t stream)
-{
-    return launch_miso_any(L, plan, row_offset, init_dev, out_dev, MisoBatch{}, stream);
-}
-
-hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int beams, long long entries, float gain,
-                             float* d_out, int out_stride, int* d_status, hipStream_t stream)
-{
-    if (L.frames < 1 || beams < 1 || out_stride < L.n_samples) return hipErrorInvalidValue;
-    MisoBatch B;
-    B.offsets = d_offsets; B.frames = L.frames; B.beams = beams; B.waves = std::min(beams, kMisoWaves);
-    B.status = d_status; B.entries = entries; B.gain = gain; B.out_stride = out_stride;
-    return launch_miso_any(L, plan, 0, nullptr, d_out, B, stream);
-}
-
-hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, hipStream_t stream)
-{
-    const int hist = stream_history(L.algo, L.tab.max_whole);
-    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist || plan.layout != 0) return hipErrorInvalidValue;
-    const KArgs a = make_args(L, plan);
-    auto go = [&](auto kernel) -> hipError_t {
-        return launch_with_lds(kernel, dim3((unsigned)plan.n_tiles * (unsigned)L.frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream, nullptr,
-                               L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a, d_prev, hop, hist);
-    };
-    auto by_dpw = [&](auto nc) -> hipError_t {
-        constexpr int NC = decltype(nc)::value;
-        if (plan.dpw == 1) return L.algo == ALGO_PAD ? go(stream_map_kernel<ALGO_PAD, NC, 1>) : go(stream_map_kernel<ALGO_LERP, NC, 1>);
-        if (plan.dpw == 4) return L.algo == ALGO_PAD ? go(stream_map_kernel<ALGO_PAD, NC, 4>) : go(stream_map_kernel<ALGO_LERP, NC, 4>);
-        return hipErrorInvalidValue;
-    };
-    switch (plan.nc) {
-        case 1: return by_dpw(std::integral_constant<int, 1>());
-        case 2: return by_dpw(std::integral_constant<int, 2>());
-        case 4: return by_dpw(std::integral_constant<int, 4>());
-        case 8: return by_dpw(std::integral_constant<int, 8>());
-        case 16: return by_dpw(std::integral_constant<int, 16>());
-        default: return hipErrorInvalidValue;
-    }
-}
-
-namespace {
 
 // das_select_kernel<ALGO, nc, dpw, HIST> of a plan_select plan; `hist` is 0 for the window-local call.
 template <int ALGO, bool HIST>
@@ -773,7 +611,7 @@ hipError_t launch_select_algo(const DasLaunch& L, const DasPlan& plan, const flo
         return launch_with_lds(kernel, dim3((unsigned)plan.n_tiles * (unsigned)L.frames), dim3((unsigned)plan.waves * kWave), plan.lds_bytes, stream, nullptr,
                                L.signals, L.images, L.mics, L.tab.whole, L.tab.frac, L.tab.taps, a, d_offsets, per_frame, d_status, entries, d_prev, hop, hist);
     };
-    auto by_dpw = [&](auto nc) -> hipError_t {
+    return dispatch_nc(plan.nc, [&](auto nc) -> hipError_t {
         constexpr int NC = decltype(nc)::value;
         if (plan.dpw == 1) return go(das_select_kernel<ALGO, NC, 1, HIST>);
         if constexpr (ALGO == ALGO_HYBRID && NC == 16) {   // four directions' accumulators of 16 segments beside the taps would spill: plan_select gives two
@@ -782,15 +620,7 @@ hipError_t launch_select_algo(const DasLaunch& L, const DasPlan& plan, const flo
             if (plan.dpw == 4) return go(das_select_kernel<ALGO, NC, 4, HIST>);
         }
         return hipErrorInvalidValue;
-    };
-    switch (plan.nc) {
-        case 1: return by_dpw(std::integral_constant<int, 1>());
-        case 2: return by_dpw(std::integral_constant<int, 2>());
-        case 4: return by_dpw(std::integral_constant<int, 4>());
-        case 8: return by_dpw(std::integral_constant<int, 8>());
-        case 16: return by_dpw(std::integral_constant<int, 16>());
-        default: return hipErrorInvalidValue;
-    }
+    });
 }
 
 bool select_launch_ok(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets)
@@ -800,6 +630,52 @@ bool select_launch_ok(const DasLaunch& L, const DasPlan& plan, const int32_t* d_
 }
 
 }  // namespace
+
+hipError_t launch_strided(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
+{
+    switch (L.algo) {
+        case ALGO_PAD: return launch_mimo_algo<ALGO_PAD, false>(L, plan, frames, nullptr, 0, 0, stream);
+        case ALGO_LERP: return launch_mimo_algo<ALGO_LERP, false>(L, plan, frames, nullptr, 0, 0, stream);
+        case ALGO_HYBRID: return launch_mimo_algo<ALGO_HYBRID, false>(L, plan, frames, nullptr, 0, 0, stream);
+        case ALGO_FIR_NAIVE: return launch_mimo_algo<ALGO_FIR_NAIVE, false>(L, plan, frames, nullptr, 0, 0, stream);
+        case ALGO_FIR_VEC: return launch_mimo_algo<ALGO_FIR_VEC, false>(L, plan, frames, nullptr, 0, 0, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, hipStream_t stream)
+{
+    int hist;
+    if (!stream_launch_ok(L, plan, hop, &hist) || plan.layout != 0) return hipErrorInvalidValue;
+    if (L.algo == ALGO_PAD) return launch_mimo_algo<ALGO_PAD, true>(L, plan, L.frames, d_prev, hop, hist, stream);
+    return launch_mimo_algo<ALGO_LERP, true>(L, plan, L.frames, d_prev, hop, hist, stream);
+}
+
+hipError_t launch_miso(const DasLaunch& L, const DasPlan& plan, long long row_offset, const float* init_dev, float* out_dev,
+                       hipStream_t stream)
+{
+    return launch_miso_any(L, plan, row_offset, init_dev, out_dev, MisoBatch{}, stream);
+}
+
+hipError_t launch_miso_batch(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int beams, long long entries, float gain,
+                             float* d_out, int out_stride, int* d_status, hipStream_t stream)
+{
+    MisoBatch B;
+    if (!make_batch(L, d_offsets, beams, entries, gain, out_stride, d_status, &B)) return hipErrorInvalidValue;
+    return launch_miso_any(L, plan, 0, nullptr, d_out, B, stream);
+}
+
+hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
+                               long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream)
+{
+    MisoBatch B;
+    if (!stream_launch_ok(L, plan, hop, &B.hist) || !make_batch(L, d_offsets, beams, entries, gain, out_stride, d_status, &B) || d_offsets == nullptr)
+        return hipErrorInvalidValue;
+    B.prev = d_prev; B.hop = hop;
+    const KArgs a = make_args(L, plan);
+    if (L.algo == ALGO_PAD) return launch_miso_algo<ALGO_PAD, true>(L, a, plan, nullptr, d_out, B, stream);
+    return launch_miso_algo<ALGO_LERP, true>(L, a, plan, nullptr, d_out, B, stream);
+}
 
 hipError_t launch_select(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets, int per_frame, long long entries, int* d_status, hipStream_t stream)
 {
@@ -816,34 +692,10 @@ hipError_t launch_select(const DasLaunch& L, const DasPlan& plan, const int32_t*
 hipError_t launch_select_stream(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int per_frame, long long entries,
                                 int* d_status, hipStream_t stream)
 {
-    const int hist = stream_history(L.algo, L.tab.max_whole);
-    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist || !select_launch_ok(L, plan, d_offsets)) return hipErrorInvalidValue;
+    int hist;
+    if (!stream_launch_ok(L, plan, hop, &hist) || !select_launch_ok(L, plan, d_offsets)) return hipErrorInvalidValue;
     if (L.algo == ALGO_PAD) return launch_select_algo<ALGO_PAD, true>(L, plan, d_prev, hop, hist, d_offsets, per_frame, entries, d_status, stream);
     return launch_select_algo<ALGO_LERP, true>(L, plan, d_prev, hop, hist, d_offsets, per_frame, entries, d_status, stream);
-}
-
-hipError_t launch_stream_beams(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, const int32_t* d_offsets, int beams,
-                               long long entries, float gain, float* d_out, int out_stride, int* d_status, hipStream_t stream)
-{
-    const int hist = stream_history(L.algo, L.tab.max_whole);
-    if (hist < 0 || hop < hist || hop > L.n_samples || plan.lead < hist) return hipErrorInvalidValue;
-    if (L.frames < 1 || beams < 1 || out_stride < L.n_samples || d_offsets == nullptr) return hipErrorInvalidValue;
-    const KArgs a = make_args(L, plan);
-    const int waves = std::min(beams, kMisoWaves);
-    const unsigned groups = (unsigned)((beams + waves - 1) / waves);
-    auto go = [&](auto kernel) -> hipError_t {
-        return launch_with_lds(kernel, dim3((unsigned)L.frames * groups), dim3((unsigned)waves * kWave), plan.lds_bytes, stream, nullptr, L.signals, L.images,
-                               L.mics, L.tab.whole, L.tab.frac, L.tab.taps, d_out, a, d_offsets, beams, d_status, entries, gain, out_stride, d_prev, hop, hist);
-    };
-    const bool pad = L.algo == ALGO_PAD;
-    switch (plan.nc) {
-        case 1: return pad ? go(stream_beam_kernel<ALGO_PAD, 1>) : go(stream_beam_kernel<ALGO_LERP, 1>);
-        case 2: return pad ? go(stream_beam_kernel<ALGO_PAD, 2>) : go(stream_beam_kernel<ALGO_LERP, 2>);
-        case 4: return pad ? go(stream_beam_kernel<ALGO_PAD, 4>) : go(stream_beam_kernel<ALGO_LERP, 4>);
-        case 8: return pad ? go(stream_beam_kernel<ALGO_PAD, 8>) : go(stream_beam_kernel<ALGO_LERP, 8>);
-        case 16: return pad ? go(stream_beam_kernel<ALGO_PAD, 16>) : go(stream_beam_kernel<ALGO_LERP, 16>);
-        default: return hipErrorInvalidValue;
-    }
 }
 
 }  // namespace bf
