@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 import util
+from support import FAKE
 
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
 M, N, X, Y, T = 16, 64, 5, 5, 8
 D = X * Y
 NO_FRAME = "get_data: no frame published (call bf_publish_frame first)"

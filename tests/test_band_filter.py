@@ -8,63 +8,21 @@ import pytest
 
 import band_np
 import util
+from support import nat_restoring as nat
+from util import CANARY, CANARY_VALUE
 
 pytestmark = pytest.mark.gpu
-
-CANARY = 64                 # floats (256 bytes) in front of and behind every device output
-CANARY_VALUE = -1234.5
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    yield native
-    util.configure("cfg1")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _same(got, want):
-    assert got.shape == want.shape
-    assert np.array_equal(_bits(got), _bits(want)), np.argwhere(_bits(got) != _bits(want))[:8]
-
-
-def _wild(rng, shape):
-    return (rng.standard_normal(shape) * np.exp2(rng.integers(-12, 13, size=shape))).astype(np.float32)
-
-
-def _sizes(N):
-    from interface import config
-    config.configure(N_MICROPHONES=4, N_SAMPLES=N, MAX_RES_X=2, MAX_RES_Y=1, N_TAPS=8)
-
-
-def _place(a, off):
-    """A device copy of `a` that starts `off` floats past a 16-byte boundary (torch allocations are 256-byte aligned)."""
-    torch = _torch()
-    buf = torch.zeros(a.size + 4, dtype=torch.float32, device="cuda")
-    assert buf.data_ptr() % 16 == 0
-    view = buf[off:off + a.size]
-    view.copy_(torch.from_numpy(np.ascontiguousarray(a).ravel()))
-    return buf, view
 
 
 def _filter(nat, x, taps, hop, prev=None, off_in=0, off_out=0, expect_rc=0):
     """bf_band_filter_device on device copies -> float32 [K, F, R, N]; the canaries around the output are checked."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, R, N = x.shape
     K, T = taps.shape
     total = K * F * R * N
-    keep_x, d_x = _place(x, off_in)
-    keep_h, d_h = _place(taps, 0)
-    keep_p, d_p = (None, None) if prev is None else _place(prev, off_in)
+    keep_x, d_x = util.place(x, off_in)
+    keep_h, d_h = util.place(taps, 0)
+    keep_p, d_p = (None, None) if prev is None else util.place(prev, off_in)
     buf = torch.full((CANARY + 4 + total + CANARY,), CANARY_VALUE, dtype=torch.float32, device="cuda")
     out = buf[CANARY + off_out:CANARY + off_out + total]
     assert out.data_ptr() % 16 == 4 * off_out and d_x.data_ptr() % 16 == 4 * off_in
@@ -81,14 +39,6 @@ def _filter(nat, x, taps, hop, prev=None, off_in=0, off_out=0, expect_rc=0):
     assert rc == 0, nat.lib.bf_last_error()
     assert (host[:lo] == np.float32(CANARY_VALUE)).all() and (host[hi:] == np.float32(CANARY_VALUE)).all()
     return host[lo:hi].reshape(K, F, R, N).copy()
-
-
-def _stream(rng, R, N, hop, F):
-    """A stream cut into F windows of N every `hop` samples, and the window that began `hop` samples before the first."""
-    step = hop if hop > 0 else N
-    S = _wild(rng, (R, step * F + N))
-    frames = np.ascontiguousarray(np.stack([S[:, (f + 1) * step:(f + 1) * step + N] for f in range(F)]))
-    return frames, np.ascontiguousarray(S[:, :N])
 
 
 # ------------------------------------------------------------------ the definition, every shape the kernel treats differently
@@ -123,42 +73,42 @@ CASES = [
 
 @pytest.mark.parametrize("N,T,hop,R,F,K,with_prev,off_in,off_out", CASES)
 def test_matches_the_definition(nat, N, T, hop, R, F, K, with_prev, off_in, off_out):
-    _sizes(N)
+    util.configure_small(N)
     rng = np.random.default_rng([N, T, hop, R, F, K])
-    x, prev = _stream(rng, R, N, hop, F)
+    x, prev = util.stream_windows(rng, R, N, hop, F)
     if not with_prev:
         prev = None
-    h = _wild(rng, (K, T))
+    h = util.wild(rng, (K, T))
     got = _filter(nat, x, h, hop, prev, off_in, off_out)
-    _same(got, band_np.band_filter(x, h, hop, prev))
+    util.same_bits(got, band_np.band_filter(x, h, hop, prev))
 
 
 @pytest.mark.parametrize("N,T,hop,off", [(64, 5, 16, 0), (256, 65, 64, 0), (100, 9, 50, 0), (99, 9, 50, 0), (256, 65, 64, 1)])
 def test_overlap_and_split_batch_identities(nat, N, T, hop, off):
-    _sizes(N)
+    util.configure_small(N)
     rng = np.random.default_rng([N, T, hop, 99])
     F, F1, R, K = 5, 2, 3, 3
-    x, prev = _stream(rng, R, N, hop, F)
-    h = _wild(rng, (K, T))
+    x, prev = util.stream_windows(rng, R, N, hop, F)
+    h = util.wild(rng, (K, T))
     whole = _filter(nat, x, h, hop, prev, off, off)
     for f in range(1, F):                                            # overlapping windows agree where both exist
-        _same(whole[:, f, :, :N - hop], whole[:, f - 1, :, hop:])
+        util.same_bits(whole[:, f, :, :N - hop], whole[:, f - 1, :, hop:])
     a = _filter(nat, x[:F1], h, hop, prev, off, off)
     b = _filter(nat, x[F1:], h, hop, x[F1 - 1], off, off)            # the carried window
-    _same(np.concatenate([a, b], axis=1), whole)
+    util.same_bits(np.concatenate([a, b], axis=1), whole)
 
 
 # ------------------------------------------------------------------ refusals that are worth a device: nothing may be enqueued
 
 def test_refused_calls_enqueue_nothing_and_touching_ranges_are_fine(nat):
-    torch = _torch()
-    _sizes(64)
+    torch = util.torch_gpu()
+    util.configure_small(64)
     rng = np.random.default_rng(5)
-    x, prev = _stream(rng, 3, 64, 32, 2)
-    h = _wild(rng, (2, 9))
+    x, prev = util.stream_windows(rng, 3, 64, 32, 2)
+    h = util.wild(rng, (2, 9))
     for kw in (dict(hop=7), dict(hop=65), dict(hop=-1)):
         assert _filter(nat, x, h, kw["hop"], prev, expect_rc=-1) is None
-    assert _filter(nat, x, _wild(rng, (17, 9)), 32, prev, expect_rc=-1) is None
+    assert _filter(nat, x, util.wild(rng, (17, 9)), 32, prev, expect_rc=-1) is None
     # one allocation: [prev | frames | out], every range touching the next; then in place, which is refused and leaves the buffer as it was
     n_in, n_prev, n_out = x.size, prev.size, 2 * x.size
     buf = torch.full((n_prev + n_in + n_out + CANARY,), CANARY_VALUE, dtype=torch.float32, device="cuda")
@@ -171,19 +121,19 @@ def test_refused_calls_enqueue_nothing_and_touching_ranges_are_fine(nat):
     assert call(n_prev + n_in) == 0, nat.lib.bf_last_error()
     torch.cuda.synchronize()
     host = buf.cpu().numpy()
-    _same(host[n_prev + n_in:n_prev + n_in + n_out].reshape(2, 2, 3, 64), band_np.band_filter(x, h, 32, prev))
+    util.same_bits(host[n_prev + n_in:n_prev + n_in + n_out].reshape(2, 2, 3, 64), band_np.band_filter(x, h, 32, prev))
     assert (host[n_prev + n_in + n_out:] == np.float32(CANARY_VALUE)).all()
     for out_at in (n_prev, n_prev + n_in - 1, n_prev - 1, 0):
         assert call(out_at) == -1 and b"overlaps" in nat.lib.bf_last_error()
         nat.lib.bf_clear_error()
     torch.cuda.synchronize()
-    assert np.array_equal(_bits(buf.cpu().numpy()), _bits(host))
+    assert np.array_equal(util.bits(buf.cpu().numpy()), util.bits(host))
 
 
 # ------------------------------------------------------------------ one captured graph: filter -> bf_das_device -> bf_peaks_device
 
 def test_graph_filter_maps_peaks(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import band
     import synth
     c = util.configure("cfg1")
@@ -228,14 +178,14 @@ def test_graph_filter_maps_peaks(nat):
     torch.cuda.synchronize()
     for a, t in zip(got, (y, img, offs, vals, cnt)):
         assert a.tobytes() == t.cpu().numpy().tobytes()
-    _same(got[0], band_np.band_filter(second, h, 128, None)[0])
+    util.same_bits(got[0], band_np.band_filter(second, h, 128, None)[0])
     assert (got[4][:, 0] >= 1).all()
 
 
 # ------------------------------------------------------------------ band.BandFilter
 
 def test_band_filter_class(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import band
     from listen import BeamListener
     c = util.configure("cfg1")
@@ -244,22 +194,22 @@ def test_band_filter_class(nat):
     nat.lib.load_coefficients_lerp(nat.fptr(table), table.size); nat.check()
     rng = np.random.default_rng(11)
     hop, F = 128, 4
-    x, prev = _stream(rng, M, N, hop, F)
+    x, prev = util.stream_windows(rng, M, N, hop, F)
     bf = band.BandFilter([(3000.0, 8000.0), (0.0, 2000.0), (6000.0, 1e9)], n_taps=65, hop=hop)
     assert bf.taps.shape == (3, 65) and bf.taps.dtype == np.float32
     d_x = torch.from_numpy(x).cuda()
     # a batch in two halves with advance() == the batch in one call behind the same carried window
     bf.advance(torch.from_numpy(prev[None]).cuda())
     whole = bf.frames(d_x).cpu().numpy()
-    _same(whole, band_np.band_filter(x, bf.taps, hop, prev))
+    util.same_bits(whole, band_np.band_filter(x, bf.taps, hop, prev))
     a = bf.frames(d_x[:2]).cpu().numpy()
     carried = bf._prev.data_ptr()
     bf.advance(d_x[:2])
     assert bf._prev.data_ptr() == carried               # copied in place: a captured graph's pointer stays valid
     b = bf.frames(d_x[2:]).cpu().numpy()
-    _same(np.concatenate([a, b], axis=1), whole)
+    util.same_bits(np.concatenate([a, b], axis=1), whole)
     bf.reset()
-    _same(bf.frames(d_x).cpu().numpy(), band_np.band_filter(x, bf.taps, hop, None))
+    util.same_bits(bf.frames(d_x).cpu().numpy(), band_np.band_filter(x, bf.taps, hop, None))
     # maps: one bl.maps call on the [K * F, R, N] view of the filtered frames; a band's maps on their own may take another of the
     # map kernels (the planner looks at the frame count), which agree to the project's map tolerance, not in the bits
     bl = BeamListener("lerp", mics=np.arange(M, dtype=np.int32))
@@ -272,7 +222,7 @@ def test_band_filter_class(nat):
     # taps= instead of a design; independent windows
     ready = band.BandFilter(taps=bf.taps[:1])
     assert ready.hop == 0 and ready.K == 1
-    _same(ready.frames(d_x).cpu().numpy(), band_np.band_filter(x, bf.taps[:1], 0, None))
+    util.same_bits(ready.frames(d_x).cpu().numpy(), band_np.band_filter(x, bf.taps[:1], 0, None))
     with pytest.raises(ValueError):
         band.BandFilter([(3000.0, 8000.0)], n_taps=65, hop=32)      # 64 samples of history do not fit a hop of 32
     with pytest.raises(ValueError):
@@ -284,7 +234,7 @@ def test_filter_commutes_with_the_beam_exactly(nat):
     an integer far below 2^24, so float32 makes no rounding and the two orders must give the same bits.  Pad beams, independent
     windows (hop = 0).  The restriction taken here: the REAL cfg1 pad table (non-zero delays), compared from sample
     T - 1 + max_whole on -- the samples at which every microphone's delayed, filtered window is fully inside the window."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import band
     from listen import BeamListener
     c = util.configure("cfg1")
@@ -308,6 +258,6 @@ def test_filter_commutes_with_the_beam_exactly(nat):
     assert 0 < start < N // 2
     for k in range(2):
         before, st = bl.listen(y[k], offsets)
-        _same(before.cpu().numpy()[:, :, start:], after[k][:, :, start:])
+        util.same_bits(before.cpu().numpy()[:, :, start:], after[k][:, :, start:])
     assert np.abs(after).max() > 100 and np.array_equal(after, np.round(after))
-    _same(after, band_np.band_filter(raw.cpu().numpy().reshape(1, F * 3, N), h)[:, 0].reshape(2, F, 3, N))
+    util.same_bits(after, band_np.band_filter(raw.cpu().numpy().reshape(1, F * 3, N), h)[:, 0].reshape(2, F, 3, N))

@@ -8,18 +8,9 @@ import pytest
 
 import band_np
 import util
+from support import FAKE, lib_16x64 as lib
 
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
 M, N, X, Y, T = 16, 64, 5, 5, 8
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _wild(rng, shape):
-    """Floats whose magnitudes spread over 2^-12 .. 2^12: a chain summed in another order rounds differently."""
-    return (rng.standard_normal(shape) * np.exp2(rng.integers(-12, 13, size=shape))).astype(np.float32)
 
 
 # ------------------------------------------------------------------ the restatement is consistent with itself
@@ -28,44 +19,44 @@ def _wild(rng, shape):
 def test_overlapping_windows_agree(n, taps, hop):
     rng = np.random.default_rng(n + taps + hop)
     F, R = 4, 3
-    S = _wild(rng, (R, hop * F + n))
+    S = util.wild(rng, (R, hop * F + n))
     frames = np.stack([S[:, (f + 1) * hop:(f + 1) * hop + n] for f in range(F)])
     prev = np.ascontiguousarray(S[:, :n])
-    h = _wild(rng, (2, taps))
+    h = util.wild(rng, (2, taps))
     y = band_np.band_filter(frames, h, hop, prev)
     assert taps - 1 <= hop < n
     for f in range(1, F):
-        assert np.array_equal(_bits(y[:, f, :, :n - hop]), _bits(y[:, f - 1, :, hop:]))
+        assert np.array_equal(util.bits(y[:, f, :, :n - hop]), util.bits(y[:, f - 1, :, hop:]))
 
 
 @pytest.mark.parametrize("n,taps,hop,F,F1", [(64, 5, 16, 5, 2), (64, 64, 64, 3, 1), (100, 9, 100, 4, 3)])
 def test_split_batch_equals_one_call(n, taps, hop, F, F1):
     rng = np.random.default_rng(7 * n + taps)
     R = 3
-    S = _wild(rng, (R, hop * F + n))
+    S = util.wild(rng, (R, hop * F + n))
     frames = np.stack([S[:, (f + 1) * hop:(f + 1) * hop + n] for f in range(F)])
     prev = np.ascontiguousarray(S[:, :n])
-    h = _wild(rng, (3, taps))
+    h = util.wild(rng, (3, taps))
     whole = band_np.band_filter(frames, h, hop, prev)
     a = band_np.band_filter(frames[:F1], h, hop, prev)
     b = band_np.band_filter(frames[F1:], h, hop, frames[F1 - 1])       # the carried window: the last frame of the first call
-    assert np.array_equal(_bits(whole), _bits(np.concatenate([a, b], axis=1)))
+    assert np.array_equal(util.bits(whole), util.bits(np.concatenate([a, b], axis=1)))
     # and silence before the stream differs from a real history exactly in the first taps - 1 outputs of frame 0
     cold = band_np.band_filter(frames, h, hop, None)
-    assert np.array_equal(_bits(cold[:, 1:]), _bits(whole[:, 1:])) and np.array_equal(_bits(cold[:, 0, :, taps - 1:]), _bits(whole[:, 0, :, taps - 1:]))
-    assert not np.array_equal(_bits(cold[:, 0, :, :taps - 1]), _bits(whole[:, 0, :, :taps - 1]))
+    assert np.array_equal(util.bits(cold[:, 1:]), util.bits(whole[:, 1:])) and np.array_equal(util.bits(cold[:, 0, :, taps - 1:]), util.bits(whole[:, 0, :, taps - 1:]))
+    assert not np.array_equal(util.bits(cold[:, 0, :, :taps - 1]), util.bits(whole[:, 0, :, :taps - 1]))
 
 
 def test_identity_and_impulse():
     rng = np.random.default_rng(3)
-    x = _wild(rng, (2, 3, 64))
+    x = util.wild(rng, (2, 3, 64))
     one = band_np.band_filter(x, np.ones((1, 1), np.float32))
-    assert np.array_equal(_bits(one[0]), _bits(x))                   # T = 1, h = [1]: the identity on the bits
-    h = _wild(rng, (3, 9))
+    assert np.array_equal(util.bits(one[0]), util.bits(x))                   # T = 1, h = [1]: the identity on the bits
+    h = util.wild(rng, (3, 9))
     imp = np.zeros((1, 1, 64), np.float32)
     imp[0, 0, 0] = 1.0
     y = band_np.band_filter(imp, h)
-    assert np.array_equal(_bits(y[:, 0, 0, :9]), _bits(h)) and not y[:, 0, 0, 9:].any()    # a unit impulse gives the taps back
+    assert np.array_equal(util.bits(y[:, 0, 0, :9]), util.bits(h)) and not y[:, 0, 0, 9:].any()    # a unit impulse gives the taps back
 
 
 # ------------------------------------------------------------------ the design
@@ -75,7 +66,7 @@ def test_design(native):
     fs = 48828.0
     h = band.design([(3000.0, 8000.0), (0.0, 4000.0), (6000.0, fs)], n_taps=65, fs=fs)
     assert h.dtype == np.float32 and h.shape == (3, 65)
-    assert np.array_equal(_bits(h), _bits(h[:, ::-1]))                # symmetric: linear phase, one delay for every microphone and band
+    assert np.array_equal(util.bits(h), util.bits(h[:, ::-1]))                # symmetric: linear phase, one delay for every microphone and band
     # A Hamming-windowed low-pass ripples 53 dB under its pass band (0.0022) outside the transition band, which is 3.3 fs / T = 2.5 kHz
     # wide: DC lies 3 kHz below the edge.  A band-pass is the difference of two low-passes, so its stop band is bounded by twice that.
     stop = 2 * 10 ** (-53 / 20)
@@ -86,7 +77,7 @@ def test_design(native):
     for k, fc in ((0, 5500.0), (2, fs / 2)):
         assert abs(abs(np.sum(h[k].astype(np.float64) * np.exp(-2j * np.pi * fc / fs * m))) - 1.0) < 1e-6    # unit gain mid-band
     y = band_np.band_filter(np.eye(1, 256, dtype=np.float32)[None], h)
-    assert np.array_equal(_bits(y[:, 0, 0, :65]), _bits(h))
+    assert np.array_equal(util.bits(y[:, 0, 0, :65]), util.bits(h))
     with pytest.raises(ValueError):
         band.design([(6000.0, fs)], n_taps=64, fs=fs)                # an even-length high-pass
     with pytest.raises(ValueError):
@@ -96,15 +87,6 @@ def test_design(native):
 
 
 # ------------------------------------------------------------------ refusals before device bring-up
-
-@pytest.fixture(scope="module")
-def lib(native):
-    L = native.lib
-    assert L.bf_configure(M, 32, X, Y, T) == 0 and L.bf_configure(M, N, X, Y, T) == 0
-    L.bf_clear_error()
-    yield L
-    L.bf_clear_error()
-    util.configure("cfg1")
 
 
 def _call(lib, d_signals=FAKE, rows=M, frames=2, hop=32, d_prev=None, d_taps=FAKE + 0x100000, n_taps=9, bands=2, d_out=FAKE + 0x200000):

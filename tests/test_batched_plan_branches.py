@@ -21,24 +21,13 @@ import pytest
 import batched_cases as BC
 import sweep_order_np as SO
 import util
+from support import nat
 from test_gpu_parity import run_product
 from util import ALGOS, REL_TOL, max_rel
 
 pytestmark = pytest.mark.gpu
 
 PAD_COLS = 5
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 def _configure(c):
@@ -48,7 +37,7 @@ def _configure(c):
 
 def _das(nat, c, algo, d_sig, mics, lo, hi, stride=None, spare_rows=0):
     """bf_das_device on the frames of d_sig over directions [lo, hi) -> float32 [frames + spare_rows, stride], NaN where nothing was written."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F = d_sig.shape[0]
     stride = hi - lo if stride is None else stride
     out = torch.full((F + spare_rows, stride), float("nan"), dtype=torch.float32, device="cuda")
@@ -74,7 +63,7 @@ def _same_bits(got, want, what):
 
 @pytest.mark.parametrize("case,algo", BC.PARAMS)
 def test_batch_reaches_its_family_and_matches_the_oracle(nat, oracle_lib, case, algo):
-    torch = _torch()
+    torch = util.torch_gpu()
     c, d = BC.BY_NAME[case], BC.data(case)
     D, F = c.X * c.Y, c.F
     lo, hi = BC.shard(c)
@@ -136,7 +125,7 @@ def test_hostile_frames_match_the_oracle(nat, oracle_lib, case, algo):
     """The seven frames of BC.hostile -- subnormal maps, one NaN that half of the directions read, partners that are loud, saturated
     or signed zeros, NaN in every sample and row the oracle never reads -- inside a NaN-filled allocation: the batched call over the
     shard and over the full range and the host-pointer one-frame call give the oracle's NaNs and the oracle's bits, frame by frame."""
-    torch = _torch()
+    torch = util.torch_gpu()
     c, d = BC.BY_NAME[case], BC.data(case)
     h = BC.hostile(case, algo)
     D, F = c.X * c.Y, BC.HOSTILE_FRAMES
@@ -186,7 +175,7 @@ def test_digest_cache_eviction(nat, oracle_lib, algo):
     """Six direction ranges through the four digest slots of one table, then the first two again (both evicted by then) and a
     one-frame call: every result is the matching slice of the full maps bit for bit, and a rebuilt digest counts the re-reads it
     counted the first time."""
-    torch = _torch()
+    torch = util.torch_gpu()
     case = BC.EVICT_PLAIN if algo in BC.PLAIN else BC.EVICT_FIR
     c, d = BC.BY_NAME[case], BC.data(case)
     D, F = c.X * c.Y, c.F

@@ -8,24 +8,13 @@ import pytest
 import box_track_cases as cases
 import box_track_np as bt
 import util
+from support import nat
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL_I, SENTINEL_F, TAIL = -77, -123.5, 16
 NAMES = ("tracks", "ids", "match", "live", "counts", "state")
 FLOAT = (True, False, False, True, False)
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 def _shapes(F, slots):
@@ -36,7 +25,7 @@ def _call(nat, boxes, n, slots, conf=0.1, iou_threshold=0.3, max_age=1, min_hits
     """bf_track_boxes_device into sentinel-filled buffers with a tail -> (tracks, ids, match, live, counts, state) as host arrays
     (None for the optional outputs when optional is False); the tails, the state's included, are checked here, and that no input
     was written."""
-    torch = _torch()
+    torch = util.torch_gpu()
     boxes = np.ascontiguousarray(boxes, dtype=np.float32)
     F, B = boxes.shape[:2]
     words = bt.state_words(slots)
@@ -68,16 +57,6 @@ def _call(nat, boxes, n, slots, conf=0.1, iou_threshold=0.3, max_age=1, min_hits
     return out
 
 
-def _same(got, want, what):
-    for name, g, w in zip(NAMES, got, want):
-        if g is None:
-            continue
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
-        bad = np.argwhere(g.view(np.int32) != w.view(np.int32))
-        assert bad.size == 0, (what, name, len(bad), bad[:4].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
-        assert g.tobytes() == w.tobytes()
-
-
 # ------------------------------------------------------------------ a - g, i: parity with the restatement, one case per branch
 
 @pytest.mark.parametrize("case", sorted(cases.CASES))
@@ -86,7 +65,7 @@ def test_parity_with_restatement(nat, case):
     cases.check_reaches(case, want, br)
     print(case, "born/ended/dropped/ignored", want[4].sum(axis=0).tolist(), "branches", {b: br.count(b) for b in sorted(set(br))})
     got = _call(nat, c["boxes"], c["n"], c["slots"], state=c["state"], **c["kw"])
-    _same(got, want, case)
+    util.same_named(NAMES, got, want, case)
 
 
 # ------------------------------------------------------------------ h. d_n_boxes = NULL and every optional output NULL
@@ -97,10 +76,10 @@ def test_null_count_and_null_outputs(nat):
     want = bt.track_boxes_np(c["boxes"], None, c["slots"], **kw)
     assert want[4][:, 3].min() >= 3 and want[4][:, 2].sum() > 0            # every row is a candidate: the rows beyond n_boxes too
     full = _call(nat, c["boxes"], None, c["slots"], **kw)
-    _same(full, want, "n_boxes NULL")
+    util.same_named(NAMES, full, want, "n_boxes NULL")
     bare = _call(nat, c["boxes"], None, c["slots"], optional=False, **kw)
     assert all(b is None for b in bare[1:5])
-    _same(bare, want, "optional outputs NULL")
+    util.same_named(NAMES, bare, want, "optional outputs NULL")
 
 
 # ------------------------------------------------------------------ j. one call of 33 frames against calls of 1 + 15 + 17 on one state
@@ -115,13 +94,13 @@ def test_state_carry(nat):
         state = parts[-1][5]
         assert state[1] == b and state[4] != 0                             # frame_count carried, tracks alive at the cut
     joined = [np.concatenate([p[i] for p in parts]) for i in range(5)] + [state]
-    _same(joined, want, "1 + 15 + 17")
+    util.same_named(NAMES, joined, want, "1 + 15 + 17")
 
 
 # ------------------------------------------------------------------ k. a captured graph replayed three times against three eager calls
 
 def test_graph_replays_advance_the_state(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     c, _, _ = cases.reference("long_stream")
     slots, kw = c["slots"], c["kw"]
     boxes, n = c["boxes"][:11], c["n"][:11]
@@ -134,7 +113,7 @@ def test_graph_replays_advance_the_state(nat):
     for r in range(3):
         want.append(bt.track_boxes_np(boxes, n, slots, state=wstate, **kw))
         wstate = want[-1][5]
-        _same(eager[r], want[r], "eager call %d" % r)
+        util.same_named(NAMES, eager[r], want[r], "eager call %d" % r)
     assert want[2][5][1] == 33 and want[1][0].tobytes() != want[0][0].tobytes()
     # a shape no call has had before: this launch is captured without a warm-up of its own
     slots2 = slots + 1
@@ -154,13 +133,13 @@ def test_graph_replays_advance_the_state(nat):
         torch.cuda.synchronize()
         w = bt.track_boxes_np(boxes, n, slots2, state=wstate, **kw)
         wstate = w[5]
-        _same([t.cpu().numpy() for t in bufs + [d_state]], w, "graph replay %d" % r)
+        util.same_named(NAMES, [t.cpu().numpy() for t in bufs + [d_state]], w, "graph replay %d" % r)
 
 
 # ------------------------------------------------------------------ l. the front end: BoxTracker.update -> SensorFusion.focus -> listen
 
 def test_tracker_feeds_focus_and_listen(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import boxtrack
     import fuse
     import listen
@@ -186,7 +165,7 @@ def test_tracker_feeds_focus_and_listen(nat):
     assert tracks.shape == (F, S, 6) and tracks.dtype == torch.float32 and live.shape == (F, S, 4) and counts.shape == (F, 4) and ids.dtype == torch.int32
     got = [t.cpu().numpy() for t in (tracks, ids, match, live, counts, tr.state)]
     want = bt.track_boxes_np(boxes, n, S)
-    _same(got, want, "front end")
+    util.same_named(NAMES, got, want, "front end")
     peak, rects, status, out = (t.cpu().numpy() for t in (peak, rects, status, out))
     reported = want[0][:, :, 4] > 0
     assert reported[:, :2].sum() > 40 and not reported[:, 2:].any()

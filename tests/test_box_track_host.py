@@ -12,22 +12,11 @@ import pytest
 import box_track_cases as cases
 import box_track_np as bt
 import util
-
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
-
-
-def _track(nat, **kw):
-    a = dict(d_boxes=FAKE, d_n_boxes=FAKE, frames=2, max_boxes=300, conf=0.1, slots=16, iou_threshold=0.3, max_age=1, min_hits=3, d_state=FAKE,
-             d_tracks=FAKE, d_ids=FAKE, d_match=FAKE, d_live=FAKE, d_counts=FAKE)
-    a.update(kw)
-    return nat.lib.bf_track_boxes_device(a["d_boxes"], a["d_n_boxes"], a["frames"], a["max_boxes"], a["conf"], a["slots"], a["iou_threshold"], a["max_age"],
-                                         a["min_hits"], a["d_state"], a["d_tracks"], a["d_ids"], a["d_match"], a["d_live"], a["d_counts"], None)
+from support import entry, FAKE, refused
 
 
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
+_track = entry("bf_track_boxes_device", d_boxes=FAKE, d_n_boxes=FAKE, frames=2, max_boxes=300, conf=0.1, slots=16, iou_threshold=0.3, max_age=1,
+               min_hits=3, d_state=FAKE, d_tracks=FAKE, d_ids=FAKE, d_match=FAKE, d_live=FAKE, d_counts=FAKE)
 
 
 def test_symbols_are_exported_bound_and_declared(native):
@@ -69,17 +58,17 @@ def test_state_words(native):
 ])
 def test_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _track(native, **kw), match)
+    refused(native, _track(native, **kw), match)
 
 
 def test_valid_arguments_without_gpu(native):
     if native.gpu_available():
         pytest.skip("without a GPU only: with one, valid arguments would enqueue")
-    _refused(native, _track(native), "no usable HIP device")
+    refused(native, _track(native), "no usable HIP device")
     # the edges of every range pass the checks; the count and the optional outputs may be null
-    _refused(native, _track(native, slots=64, max_boxes=1024, iou_threshold=1.0, max_age=0, min_hits=0, conf=-1e30), "no usable HIP device")
-    _refused(native, _track(native, slots=1, max_boxes=1, frames=1, iou_threshold=0.0, conf=1e30, max_age=2 ** 31 - 1, min_hits=2 ** 31 - 1), "no usable HIP device")
-    _refused(native, _track(native, d_n_boxes=None, d_ids=None, d_match=None, d_live=None, d_counts=None), "no usable HIP device")
+    refused(native, _track(native, slots=64, max_boxes=1024, iou_threshold=1.0, max_age=0, min_hits=0, conf=-1e30), "no usable HIP device")
+    refused(native, _track(native, slots=1, max_boxes=1, frames=1, iou_threshold=0.0, conf=1e30, max_age=2 ** 31 - 1, min_hits=2 ** 31 - 1), "no usable HIP device")
+    refused(native, _track(native, d_n_boxes=None, d_ids=None, d_match=None, d_live=None, d_counts=None), "no usable HIP device")
 
 
 def test_tracker_without_gpu(native):

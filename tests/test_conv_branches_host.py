@@ -13,13 +13,9 @@ import random
 import pytest
 
 import conv_cases as cc
+from support import lib
 
 CUS = 256
-
-
-@pytest.fixture(scope="module")
-def lib(native):
-    return native.lib
 
 
 def _check_plan(p, eb, M, N, ldy, has_res, ldr, misaligned, n_cus):

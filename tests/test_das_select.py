@@ -12,6 +12,7 @@ import pytest
 
 import select_np
 import util
+from support import nat
 from test_miso_device import Tables
 from test_stream import Case, Stream
 
@@ -21,18 +22,6 @@ ALGOS = ["pad", "lerp", "hybrid", "fir_vec"]
 CANARY = 64
 CANARY_BITS = 0x7FA5A5A5            # a NaN no kernel writes
 NAN_BITS = select_np.NAN_BITS
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 class Setup:
@@ -62,7 +51,7 @@ class Setup:
 def _call(nat, algo, frames, mics, offsets, gap=0, status=True, stream=None):
     """One select call on device copies: offsets [B] (shared list) or [F, B]; stream = (hop, prev or None) for the stream call.
     -> (power [F, B] host, status [F, B] host or None), after checking the canaries and the untouched gap of every row."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, M, N = frames.shape
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     B = offsets.shape[-1]
@@ -201,7 +190,7 @@ def test_hostile_samples(nat, oracle_lib, algo):
 
 
 def test_unloaded_table_is_an_error(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     Setup(nat, "pad", 7, 5, 64, 12, 20.0)
     nat.lib.unload_coefficients_lerp()
     nat.lib.bf_clear_error()
@@ -228,7 +217,7 @@ FAMILY = {"cfg1": {"pad": 2, "lerp": 2, "hybrid": 7}, "g41x23": {"pad": 5, "lerp
 def test_equals_the_map_kernels_image(nat, grid, algo, F):
     """cfg1 and the 41 x 23 grid (64 x 256) with 2 and 3 frames, where bf_das_device takes the families above: powers at every
     direction in a shuffled order, another one per frame, is its image byte for byte.  The select call leaves bf_last_das_variant alone."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import directions_np
     import listen
     from interface import config
@@ -274,7 +263,7 @@ def test_equals_the_map_kernels_image(nat, grid, algo, F):
 def test_stream_call(nat, oracle_lib, algo, N, hop_kind, with_prev):
     """3 frames, 9 of 16 microphones, hop N and N / 2, with and without a previous frame: equal to the extended-window restatement
     and to what bf_das_stream_device writes at the same directions; rejected entries NaN."""
-    torch = _torch()
+    torch = util.torch_gpu()
     M_total, D, F = 16, 12, 3
     rng = np.random.default_rng([9, N, len(algo)])
     mics = rng.choice(M_total, 9, replace=False).astype(np.int32)
@@ -341,7 +330,7 @@ def _same_locate(got, want):
 def test_locate_equals_the_restatement(nat, oracle_lib, name):
     """The 41 x 23 grid (3 frames, one of them silent: fewer than k peaks) and the issue's 101 x 101 scene, lattice step 4, window
     radius 4: offsets, values and counts of the restatement on the C checker's full map."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     import zoom
     z, delays, frames = _zoom_setup(nat, name)
@@ -359,7 +348,7 @@ def test_locate_equals_the_restatement(nat, oracle_lib, name):
 
 def test_locate_on_a_stream(nat, oracle_lib):
     """The 41 x 23 scene's frames as back-to-back windows of one stream (hop = N, silence before it) through a StreamBeamformer."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import stream
     import zoom
     name = "g41x23"
@@ -384,7 +373,7 @@ def test_locate_on_a_stream(nat, oracle_lib):
 
 def test_locate_in_a_graph(nat):
     """locate captured after one warm-up call; the frames overwritten in place; the replay equals the eager call on the new frames."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     import zoom
     z, delays, frames = _zoom_setup(nat, "g41x23")

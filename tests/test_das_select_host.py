@@ -13,6 +13,7 @@ import pytest
 import peaks_np
 import select_np
 import util
+from support import nat_cfg1 as nat, refused
 
 FAKE, N, M_TOTAL = 0x100000, 256, 8       # cfg1: 256 samples; frames of 8 rows are 8 KiB each
 FRAME = M_TOTAL * N * 4
@@ -33,19 +34,6 @@ def _local(nat, **kw):
 
 def _stream(nat, **kw):
     return nat.lib.bf_das_select_stream_device(*_args(nat, True, **kw))
-
-
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
-
-
-@pytest.fixture()
-def nat(native):
-    util.configure("cfg1")                 # 64 x 256, 11 x 11 directions
-    native.lib.bf_clear_error()
-    return native
 
 
 # ------------------------------------------------------------------ symbols and prototypes
@@ -103,7 +91,7 @@ COMMON = [
     (dict(algo=3), "algo BF_FIR_NAIVE has no MISO form in the reference"),
 ])
 def test_select_argument_errors(nat, kw, match):
-    _refused(nat, _local(nat, **kw), "bf_das_select_device: " + match)
+    refused(nat, _local(nat, **kw), "bf_das_select_device: " + match)
 
 
 CAUSAL = "reads ahead of the window's end, which a causal stream cannot supply"
@@ -119,7 +107,7 @@ CAUSAL = "reads ahead of the window's end, which a causal stream cannot supply"
     (dict(d_prev=0x200000 + 36), "d_power overlaps d_prev"),
 ])
 def test_select_stream_argument_errors(nat, kw, match):
-    _refused(nat, _stream(nat, **kw), "bf_das_select_stream_device: " + match)
+    refused(nat, _stream(nat, **kw), "bf_das_select_stream_device: " + match)
 
 
 def test_neighbouring_buffers_are_not_an_overlap(nat):
@@ -127,8 +115,8 @@ def test_neighbouring_buffers_are_not_an_overlap(nat):
     nat.lib.unload_coefficients_lerp()
     nat.lib.bf_clear_error()
     late = "no usable HIP device|has not been called"
-    _refused(nat, _local(nat, d_power=FAKE + 2 * FRAME, d_status=FAKE + 2 * FRAME + 40, d_offsets=FAKE + 2 * FRAME + 80), late)
-    _refused(nat, _stream(nat, d_prev=FAKE - FRAME, d_power=FAKE - FRAME - 40), late)
+    refused(nat, _local(nat, d_power=FAKE + 2 * FRAME, d_status=FAKE + 2 * FRAME + 40, d_offsets=FAKE + 2 * FRAME + 80), late)
+    refused(nat, _stream(nat, d_prev=FAKE - FRAME, d_power=FAKE - FRAME - 40), late)
 
 
 def test_valid_arguments_reach_the_device_checks(nat):
@@ -138,12 +126,12 @@ def test_valid_arguments_reach_the_device_checks(nat):
     nat.lib.bf_clear_error()
     late = "no usable HIP device|has not been called"
     for algo in (nat.PAD, nat.LERP, nat.HYBRID, nat.FIR_VEC):
-        _refused(nat, _local(nat, algo=algo), late)
-    _refused(nat, _local(nat, per_frame=0, count=1, power_stride=1, d_status=None, frames=1), late)
-    _refused(nat, _local(nat, count=130321, power_stride=130400, d_power=0x10000000, d_status=0x20000000, d_offsets=0x30000000), late)
+        refused(nat, _local(nat, algo=algo), late)
+    refused(nat, _local(nat, per_frame=0, count=1, power_stride=1, d_status=None, frames=1), late)
+    refused(nat, _local(nat, count=130321, power_stride=130400, d_power=0x10000000, d_status=0x20000000, d_offsets=0x30000000), late)
     for algo in (nat.PAD, nat.LERP):
-        _refused(nat, _stream(nat, algo=algo), late)
-    _refused(nat, _stream(nat, hop=1, d_prev=0x500000, d_status=None, per_frame=0), late)
+        refused(nat, _stream(nat, algo=algo), late)
+    refused(nat, _stream(nat, hop=1, d_prev=0x500000, d_status=None, per_frame=0), late)
 
 
 def test_plan_is_strided_and_chunks_where_plan_das_chunks(nat):

@@ -7,16 +7,9 @@ import pytest
 
 import fd_cases as FC
 import util
+from support import gemm_mode
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(params=[0, 1], ids=["f32_mfma", "bf16_split"])
-def gemm_mode(request, native):
-    """bf_fd_gemm_f32_mode for the test, as in test_freqdomain.py: the float32 matrix instruction and the three-way bfloat16 split, same bounds."""
-    initial = native.lib.bf_fd_gemm_f32_mode(request.param)
-    yield request.param
-    native.lib.bf_fd_gemm_f32_mode(initial)
 
 
 def _dev(v):

@@ -10,17 +10,9 @@ import pytest
 import band_np
 import filtersum_np as fsn
 import util
+from util import CANARY, CANARY_VALUE
 
 pytestmark = pytest.mark.gpu
-
-CANARY = 64                 # floats (256 bytes) in front of and behind every device output
-CANARY_VALUE = -1234.5
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -31,44 +23,16 @@ def nat(native):
     util.configure("cfg1")
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _same(got, want):
-    assert got.shape == want.shape
-    assert np.array_equal(_bits(got), _bits(want)), np.argwhere(_bits(got) != _bits(want))[:8]
-
-
-def _wild(rng, shape):
-    return (rng.standard_normal(shape) * np.exp2(rng.integers(-12, 13, size=shape))).astype(np.float32)
-
-
-def _sizes(N):
-    from interface import config
-    config.configure(N_MICROPHONES=4, N_SAMPLES=N, MAX_RES_X=2, MAX_RES_Y=1, N_TAPS=8)
-
-
-def _place(a, off):
-    """A device copy of `a` that starts `off` floats past a 16-byte boundary (torch allocations are 256-byte aligned)."""
-    torch = _torch()
-    buf = torch.zeros(a.size + 4, dtype=torch.float32, device="cuda")
-    assert buf.data_ptr() % 16 == 0
-    view = buf[off:off + a.size]
-    view.copy_(torch.from_numpy(np.ascontiguousarray(a).ravel()))
-    return buf, view
-
-
 def _beams(nat, x, mics, taps, hop, prev=None, off_in=0, off_out=0, gap=0, expect_rc=0):
     """bf_filter_sum_device on device copies -> float32 [F, B, N]; the canaries around the output and in its rows' gaps are checked."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, m_total, N = x.shape
     B, n, T = taps.shape
     stride = N + gap
     total = F * B * stride
-    keep_x, d_x = _place(x, off_in)
-    keep_g, d_g = _place(taps, off_in)
-    keep_p, d_p = (None, None) if prev is None else _place(prev, off_in)
+    keep_x, d_x = util.place(x, off_in)
+    keep_g, d_g = util.place(taps, off_in)
+    keep_p, d_p = (None, None) if prev is None else util.place(prev, off_in)
     buf = torch.full((CANARY + 4 + total + CANARY,), CANARY_VALUE, dtype=torch.float32, device="cuda")
     out = buf[CANARY + off_out:CANARY + off_out + total]
     assert out.data_ptr() % 16 == 4 * off_out and d_x.data_ptr() % 16 == 4 * off_in
@@ -88,14 +52,6 @@ def _beams(nat, x, mics, taps, hop, prev=None, off_in=0, off_out=0, gap=0, expec
     rows = host[lo:hi].reshape(F, B, stride)
     assert (rows[:, :, N:] == np.float32(CANARY_VALUE)).all()       # floats past N_SAMPLES in a row are left untouched
     return rows[:, :, :N].copy()
-
-
-def _stream(rng, R, N, hop, F):
-    """A stream cut into F windows of N every `hop` samples, and the window that began `hop` samples before the first."""
-    step = hop if hop > 0 else N
-    S = _wild(rng, (R, step * F + N))
-    frames = np.ascontiguousarray(np.stack([S[:, (f + 1) * step:(f + 1) * step + N] for f in range(F)]))
-    return frames, np.ascontiguousarray(S[:, :N])
 
 
 def _mics(rng, n, m_total):
@@ -137,57 +93,57 @@ CASES = [
 
 @pytest.mark.parametrize("N,T,hop,n,m_total,B,F,with_prev,off_in,off_out,gap", CASES)
 def test_matches_the_definition(nat, N, T, hop, n, m_total, B, F, with_prev, off_in, off_out, gap):
-    _sizes(N)
+    util.configure_small(N)
     rng = np.random.default_rng([N, T, hop, n, B, F])
-    x, prev = _stream(rng, m_total, N, hop, F)
+    x, prev = util.stream_windows(rng, m_total, N, hop, F)
     if not with_prev:
         prev = None
     mics = _mics(rng, n, m_total)
-    g = _wild(rng, (B, n, T))
+    g = util.wild(rng, (B, n, T))
     got = _beams(nat, x, mics, g, hop, prev, off_in, off_out, gap)
-    _same(got, fsn.filter_sum(x, mics, g, hop, prev))
+    util.same_bits(got, fsn.filter_sum(x, mics, g, hop, prev))
 
 
 def test_result_does_not_depend_on_the_waves_or_on_the_beams_launched_together(nat):
     """Pinned to 1, 2, 4, 8 and 16 waves a workgroup deals its microphones differently each time; a beam launched alone, among 3 and
     among 16 sits in another workgroup of another grid.  All give the bits of the restatement."""
-    _sizes(256)
+    util.configure_small(256)
     rng = np.random.default_rng(31)
     n, m_total, T, hop, F = 70, 72, 33, 128, 2
-    x, prev = _stream(rng, m_total, 256, hop, F)
+    x, prev = util.stream_windows(rng, m_total, 256, hop, F)
     mics = _mics(rng, n, m_total)
-    g = _wild(rng, (16, n, T))
+    g = util.wild(rng, (16, n, T))
     want = fsn.filter_sum(x, mics, g, hop, prev)
     try:
         for waves in (1, 2, 4, 8, 16):
             nat.lib.bf_filter_sum_waves(waves)
-            _same(_beams(nat, x, mics, g[9:10], hop, prev), want[:, 9:10])
-            _same(_beams(nat, x, mics, g[7:10], hop, prev), want[:, 7:10])
-            _same(_beams(nat, x, mics, g, hop, prev), want)
+            util.same_bits(_beams(nat, x, mics, g[9:10], hop, prev), want[:, 9:10])
+            util.same_bits(_beams(nat, x, mics, g[7:10], hop, prev), want[:, 7:10])
+            util.same_bits(_beams(nat, x, mics, g, hop, prev), want)
     finally:
         assert nat.lib.bf_filter_sum_waves(0) == 16
 
 
 @pytest.mark.parametrize("N,T,hop,off", [(64, 5, 16, 0), (256, 65, 64, 0), (100, 9, 50, 0), (99, 9, 50, 0), (256, 65, 64, 1)])
 def test_overlap_and_split_batch_identities(nat, N, T, hop, off):
-    _sizes(N)
+    util.configure_small(N)
     rng = np.random.default_rng([N, T, hop, 98])
     F, F1, n, m_total, B = 5, 2, 5, 7, 3
-    x, prev = _stream(rng, m_total, N, hop, F)
+    x, prev = util.stream_windows(rng, m_total, N, hop, F)
     mics = _mics(rng, n, m_total)
-    g = _wild(rng, (B, n, T))
+    g = util.wild(rng, (B, n, T))
     whole = _beams(nat, x, mics, g, hop, prev, off, off)
     for f in range(1, F):                                            # overlapping windows agree where both exist
-        _same(whole[f, :, :N - hop], whole[f - 1, :, hop:])
+        util.same_bits(whole[f, :, :N - hop], whole[f - 1, :, hop:])
     a = _beams(nat, x[:F1], mics, g, hop, prev, off, off)
     b = _beams(nat, x[F1:], mics, g, hop, x[F1 - 1], off, off)       # the carried window
-    _same(np.concatenate([a, b], axis=0), whole)
+    util.same_bits(np.concatenate([a, b], axis=0), whole)
 
 
 # ------------------------------------------------------------------ delta taps are the delay-and-sum beams of a loaded pad table
 
 def test_delta_taps_equal_the_pad_beams(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     c = util.configure("cfg1")
     M, N, D = c["M"], c["N"], c["X"] * c["Y"]
     table = np.ascontiguousarray(util.table_for("pad", "cfg1"), dtype=np.int32).reshape(D, M)
@@ -196,7 +152,7 @@ def test_delta_taps_equal_the_pad_beams(nat):
     assert 0 < max_whole < 64
     rng = np.random.default_rng(17)
     hop, F = 128, 3
-    x, prev = _stream(rng, M, N, hop, F)
+    x, prev = util.stream_windows(rng, M, N, hop, F)
     x[0, 5, :4] = [-0.0, 0.0, -1e-45, 1e-45]
     mics = rng.permutation(M).astype(np.int32)                       # entry m of a table row belongs to frame row mics[m]
     dirs = np.array([0, D // 2 + 3, D - 1], dtype=np.int32)
@@ -210,29 +166,29 @@ def test_delta_taps_equal_the_pad_beams(nat):
     torch.cuda.synchronize()
     assert (status.cpu().numpy() == 0).all()
     for T in (max_whole + 1, max_whole + 6):                         # the shortest filter that holds every delay, and one with taps to skip
-        _same(_beams(nat, x, mics, fsn.delta_taps(table[dirs], T), 0), want.cpu().numpy())
+        util.same_bits(_beams(nat, x, mics, fsn.delta_taps(table[dirs], T), 0), want.cpu().numpy())
     # with a hop: the continuous-stream beams, every sample of them
     assert nat.lib.bf_miso_stream_device(util.ALGOS["pad"], d_x.data_ptr(), M, F, hop, d_prev.data_ptr(), nat.iptr(mics), M, d_off.data_ptr(), 3, 0.0,
                                          want.data_ptr(), N, status.data_ptr(), s) == 0, nat.lib.bf_last_error()
     torch.cuda.synchronize()
     assert (status.cpu().numpy() == 0).all()
     for T in (max_whole + 1, hop + 1):
-        _same(_beams(nat, x, mics, fsn.delta_taps(table[dirs], T), hop, prev), want.cpu().numpy())
+        util.same_bits(_beams(nat, x, mics, fsn.delta_taps(table[dirs], T), hop, prev), want.cpu().numpy())
 
 
 # ------------------------------------------------------------------ refusals that are worth a device: nothing may be enqueued
 
 def test_refused_calls_enqueue_nothing_and_touching_ranges_are_fine(nat):
-    torch = _torch()
-    _sizes(64)
+    torch = util.torch_gpu()
+    util.configure_small(64)
     rng = np.random.default_rng(5)
     m_total, n, B, T, hop, F = 5, 3, 2, 9, 32, 2
-    x, prev = _stream(rng, m_total, 64, hop, F)
+    x, prev = util.stream_windows(rng, m_total, 64, hop, F)
     mics = np.array([4, 0, 2], dtype=np.int32)
-    g = _wild(rng, (B, n, T))
+    g = util.wild(rng, (B, n, T))
     for bad_hop in (7, 65, -1):
         assert _beams(nat, x, mics, g, bad_hop, prev, expect_rc=-1) is None
-    assert _beams(nat, x, mics, _wild(rng, (17, n, T)), hop, prev, expect_rc=-1) is None
+    assert _beams(nat, x, mics, util.wild(rng, (17, n, T)), hop, prev, expect_rc=-1) is None
     assert _beams(nat, x, np.array([4, 5, 2]), g, hop, prev, expect_rc=-1) is None
     assert _beams(nat, x, mics, g, hop, prev, gap=-1, expect_rc=-1) is None
     # one allocation: [prev | frames | taps | out], every range touching the next; then overlapping, which is refused and leaves the buffer as it was
@@ -248,19 +204,19 @@ def test_refused_calls_enqueue_nothing_and_touching_ranges_are_fine(nat):
     assert call(at_out) == 0, nat.lib.bf_last_error()
     torch.cuda.synchronize()
     host = buf.cpu().numpy()
-    _same(host[at_out:at_out + n_out].reshape(F, B, 64), fsn.filter_sum(x, mics, g, hop, prev))
+    util.same_bits(host[at_out:at_out + n_out].reshape(F, B, 64), fsn.filter_sum(x, mics, g, hop, prev))
     assert (host[at_out + n_out:] == np.float32(CANARY_VALUE)).all()
     for out_at in (at_out - 1, n_prev + n_in, n_prev + n_in - 1, n_prev, n_prev - 1, 0):
         assert call(out_at) == -1 and b"overlaps" in nat.lib.bf_last_error()
         nat.lib.bf_clear_error()
     torch.cuda.synchronize()
-    assert np.array_equal(_bits(buf.cpu().numpy()), _bits(host))
+    assert np.array_equal(util.bits(buf.cpu().numpy()), util.bits(host))
 
 
 # ------------------------------------------------------------------ one captured graph: filter-and-sum -> band filter on its beams
 
 def test_graph_beams_then_band_filter(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import band
     import synth
     c = util.configure("cfg1")
@@ -268,7 +224,7 @@ def test_graph_beams_then_band_filter(nat):
     mics = np.arange(M, dtype=np.int32)[::-1].copy()
     rng = np.random.default_rng(73)
     F, B, T, hop = 3, 3, 33, 128
-    g = _wild(rng, (B, M, T))
+    g = util.wild(rng, (B, M, T))
     h = band.design([(3000.0, 8000.0)], n_taps=65)
     first = synth.frame_batch(M, N, F)
     second = np.ascontiguousarray(util.inputs("cfg1")["s3"][None].repeat(F, 0) + (rng.standard_normal((F, M, N)) * 0.05).astype(np.float32))
@@ -300,8 +256,8 @@ def test_graph_beams_then_band_filter(nat):
     for a, t in zip(got, (beams, y)):
         assert a.tobytes() == t.cpu().numpy().tobytes()
     want = fsn.filter_sum(second, mics, g, hop, None)
-    _same(got[0], want)
-    _same(got[1], band_np.band_filter(want.reshape(1, F * B, N), h)[0, 0].reshape(F, B, N))
+    util.same_bits(got[0], want)
+    util.same_bits(got[1], band_np.band_filter(want.reshape(1, F * B, N), h)[0, 0].reshape(F, B, N))
 
 
 # ------------------------------------------------------------------ filtersum.FilterSumListener on the two-talker scene
@@ -310,7 +266,7 @@ def test_listener_nulls_the_second_talker(nat):
     """The scene of tests/test_filter_sum_host.py as float32 frames cut from the stream (hop 128): cross_null's two beams are the
     restatement bit for bit, and the interferer alone through the device beam aimed at the look source comes out at least 20 dB
     below what the same designer's delay-and-sum beam (no nulls) lets through."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import filtersum
     from interface import config
     from lib import directions
@@ -331,27 +287,27 @@ def test_listener_nulls_the_second_talker(nat):
     fl = filtersum.FilterSumListener.cross_null(tau, offsets, M, hop=hop, n_taps=T, band=fsn.BAND, fs=fsn.FS)
     assert fl.dirs == [look, null] and fl.B == 2 and fl.taps.shape == (2, M, T) and fl.delay == 32.0 and fl.kept.all()
     want_taps, _ = filtersum.design_lcmv(tau, [look, null], [[null], [look]], n_taps=T, band=fsn.BAND, fs=fsn.FS)
-    _same(fl.taps, want_taps)
+    util.same_bits(fl.taps, want_taps)
     mics = fl.mics
     assert np.array_equal(mics, np.arange(M))
 
     d_both = torch.from_numpy(both).cuda()
     cold = fl.listen(d_both).cpu().numpy()
-    _same(cold, fsn.filter_sum(both, mics, fl.taps, hop, None))
+    util.same_bits(cold, fsn.filter_sum(both, mics, fl.taps, hop, None))
     fl.advance(torch.from_numpy(both_prev[None]).cuda())
     whole = fl.listen(d_both).cpu().numpy()
-    _same(whole, fsn.filter_sum(both, mics, fl.taps, hop, both_prev))
+    util.same_bits(whole, fsn.filter_sum(both, mics, fl.taps, hop, both_prev))
     a = fl.listen(d_both[:5]).cpu().numpy()
     carried = fl._prev.data_ptr()
     fl.advance(d_both[:5])
     assert fl._prev.data_ptr() == carried               # copied in place: a captured graph's pointer stays valid
     b = fl.listen(d_both[5:])
-    _same(np.concatenate([a, b.cpu().numpy()], axis=0), whole)
+    util.same_bits(np.concatenate([a, b.cpu().numpy()], axis=0), whole)
     audio = fl.audio(torch.from_numpy(whole).cuda()).cpu().numpy()
     assert audio.shape == (2, F * hop)
-    _same(audio, whole[:, :, N - hop:].transpose(1, 0, 2).reshape(2, F * hop))
+    util.same_bits(audio, whole[:, :, N - hop:].transpose(1, 0, 2).reshape(2, F * hop))
     fl.reset()
-    _same(fl.listen(d_both).cpu().numpy(), cold)
+    util.same_bits(fl.listen(d_both).cpu().numpy(), cold)
 
     # the interferer alone: through the null-steered beam, and through the same designer's beam without nulls
     das_taps, _ = filtersum.design_lcmv(tau, [look], None, n_taps=T, band=fsn.BAND, fs=fsn.FS)

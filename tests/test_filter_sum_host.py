@@ -8,18 +8,9 @@ import pytest
 
 import filtersum_np as fsn
 import util
+from support import FAKE, grid_tau as tau, lib_16x64 as lib
 
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
 M, N, X, Y, T = 16, 64, 5, 5, 8
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _wild(rng, shape):
-    """Floats whose magnitudes spread over 2^-12 .. 2^12: a chain summed in another order rounds differently."""
-    return (rng.standard_normal(shape) * np.exp2(rng.integers(-12, 13, size=shape))).astype(np.float32)
 
 
 # ------------------------------------------------------------------ the restatement
@@ -28,7 +19,7 @@ def _wild(rng, shape):
 def test_delta_taps_are_miso_pad(n_samples, taps, n, m_total):
     rng = np.random.default_rng([n_samples, taps, n])
     F, B = 2, 3
-    x = _wild(rng, (F, m_total, n_samples))
+    x = util.wild(rng, (F, m_total, n_samples))
     x[0, 0, :4] = [-0.0, 0.0, -1e-45, 1e-45]                         # signed zeros and denormals pass through a delta chain
     mics = rng.permutation(m_total)[:n]
     delays = rng.integers(0, taps, size=(B, n))
@@ -36,38 +27,29 @@ def test_delta_taps_are_miso_pad(n_samples, taps, n, m_total):
     got = fsn.filter_sum(x, mics, fsn.delta_taps(delays, taps))
     for f in range(F):
         for b in range(B):
-            assert np.array_equal(_bits(got[f, b]), _bits(fsn.miso_pad(x[f], mics, delays[b])))
+            assert np.array_equal(util.bits(got[f, b]), util.bits(fsn.miso_pad(x[f], mics, delays[b])))
 
 
 def test_restatement_overlap_and_order():
     rng = np.random.default_rng(4)
     n_samples, taps, hop, F, m_total = 64, 9, 16, 4, 6
-    S = _wild(rng, (m_total, hop * F + n_samples))
+    S = util.wild(rng, (m_total, hop * F + n_samples))
     frames = np.stack([S[:, (f + 1) * hop:(f + 1) * hop + n_samples] for f in range(F)])
     prev = np.ascontiguousarray(S[:, :n_samples])
     mics = np.array([4, 0, 5, 2])
-    g = _wild(rng, (2, 4, taps))
+    g = util.wild(rng, (2, 4, taps))
     y = fsn.filter_sum(frames, mics, g, hop, prev)
     for f in range(1, F):                                            # overlapping windows agree where both exist
-        assert np.array_equal(_bits(y[f, :, :n_samples - hop]), _bits(y[f - 1, :, hop:]))
+        assert np.array_equal(util.bits(y[f, :, :n_samples - hop]), util.bits(y[f - 1, :, hop:]))
     a = fsn.filter_sum(frames[:2], mics, g, hop, prev)
     b = fsn.filter_sum(frames[2:], mics, g, hop, frames[1])           # the carried window
-    assert np.array_equal(_bits(np.concatenate([a, b])), _bits(y))
+    assert np.array_equal(util.bits(np.concatenate([a, b])), util.bits(y))
     # the microphone order is part of the definition: the same rows and taps summed backwards round differently somewhere
     back = fsn.filter_sum(frames, mics[::-1], g[:, ::-1], hop, prev)
-    assert not np.array_equal(_bits(back), _bits(y)) and np.allclose(back, y, rtol=1e-3, atol=1e-3 * np.abs(y).max())
+    assert not np.array_equal(util.bits(back), util.bits(y)) and np.allclose(back, y, rtol=1e-3, atol=1e-3 * np.abs(y).max())
 
 
 # ------------------------------------------------------------------ refusals before device bring-up
-
-@pytest.fixture(scope="module")
-def lib(native):
-    L = native.lib
-    assert L.bf_configure(M, 32, X, Y, T) == 0 and L.bf_configure(M, N, X, Y, T) == 0
-    L.bf_clear_error()
-    yield L
-    L.bf_clear_error()
-    util.configure("cfg1")
 
 
 MICS = np.array([3, 0, 15, 7], dtype=np.int32)
@@ -140,11 +122,6 @@ def test_accepted_arguments_reach_the_device_check(native, lib):
 
 
 # ------------------------------------------------------------------ the designer
-
-@pytest.fixture(scope="module")
-def tau():
-    import directions_np as D
-    return D.calculate_delays(fsn.GRID[0], fsn.GRID[1], arrays=1).reshape(-1, 64)
 
 
 def _in_band_rho(tau, a, b, T):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import util
+from support import gemm_mode
 
 TOL_OF_PEAK = 2e-5
 
@@ -191,14 +192,6 @@ GEMM_SHAPES = [
     (190,  64, 333, 23),    # the bench shape in miniature: several bin groups + the plane reduction
     (8,   130,  64,  3),    # K > 128: three panels
 ]
-
-
-@pytest.fixture(params=[0, 1], ids=["f32_mfma", "bf16_split"])
-def gemm_mode(request, native):
-    """bf_fd_gemm_f32_mode for the test: the float32 matrix instruction, and the exact three-way bfloat16 split (same bounds for both)."""
-    initial = native.lib.bf_fd_gemm_f32_mode(request.param)
-    yield request.param
-    native.lib.bf_fd_gemm_f32_mode(initial)
 
 
 @pytest.mark.gpu

@@ -8,6 +8,7 @@ import fuse_cases
 import fuse_np
 import separate_np as snp
 import util
+from support import nat
 
 pytestmark = pytest.mark.gpu
 
@@ -16,22 +17,10 @@ NAMES = ("peak", "power", "center", "rects", "src_box", "counts")
 ALL = frozenset(NAMES)
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
-
-
 def _call(nat, c, given=ALL, use_counts=True, use_sources=True):
     """bf_fuse_boxes_device on a case of fuse_cases into sentinel-filled buffers with a tail -> the six outputs as host arrays (None
     for the ones not in `given`); the tails are checked here, and that no input was written."""
-    torch = _torch()
+    torch = util.torch_gpu()
     power, boxes = np.ascontiguousarray(c["power"], dtype=np.float32), np.ascontiguousarray(c["boxes"], dtype=np.float32)
     F, B = boxes.shape[:2]
     sources = c["sources"] if use_sources else None
@@ -155,7 +144,7 @@ def _cfg1_batch(c, F, seed, W=64, H=36, B=5):
 
 
 def test_front_end(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import fuse
     import pipeline
     c, bl = _cfg1_listener(nat)
@@ -200,7 +189,7 @@ def test_front_end(nat):
 # ------------------------------------------------------------------ 5. maps -> focus -> listen as one captured graph
 
 def test_runs_in_a_captured_graph(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import fuse
     c, bl = _cfg1_listener(nat)
     W, H, F = 64, 36, 2
@@ -251,7 +240,7 @@ def test_boxes_hear_their_sources(nat, oracle_lib):
     meet that bound on a plain map: measured on the CPU (tests/test_fuse_host.py::test_scene_boxes_on_the_plain_map), the loudest
     cell under it is the box's corner towards the strong source, at distance 2 in both frames -- the strong one's skirt.  For that
     box the restatement's own answer is the expected value."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import fuse
     import listen
     from interface import config

@@ -11,24 +11,12 @@ import fuse_cases
 import fuse_np
 import separate_np as snp
 import visual_np
-
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
-
-
-def _fuse(nat, **kw):
-    a = dict(d_power=FAKE, frames=2, image_stride=1000, rows=41, cols=23, offset_per_dir=4, d_boxes=FAKE, d_box_counts=FAKE, max_boxes=300, img_w=640,
-             img_h=360, conf=0.5, d_src_offsets=FAKE, n_src=4, d_peak_offsets=FAKE, d_peak_power=FAKE, d_center_offsets=FAKE, d_rects=FAKE,
-             d_src_box=FAKE, d_counts=FAKE)
-    a.update(kw)
-    return nat.lib.bf_fuse_boxes_device(a["d_power"], a["frames"], a["image_stride"], a["rows"], a["cols"], a["offset_per_dir"], a["d_boxes"],
-                                        a["d_box_counts"], a["max_boxes"], a["img_w"], a["img_h"], a["conf"], a["d_src_offsets"], a["n_src"],
-                                        a["d_peak_offsets"], a["d_peak_power"], a["d_center_offsets"], a["d_rects"], a["d_src_box"], a["d_counts"], None)
+from support import entry, FAKE, refused
 
 
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
+_fuse = entry("bf_fuse_boxes_device", d_power=FAKE, frames=2, image_stride=1000, rows=41, cols=23, offset_per_dir=4, d_boxes=FAKE, d_box_counts=FAKE,
+              max_boxes=300, img_w=640, img_h=360, conf=0.5, d_src_offsets=FAKE, n_src=4, d_peak_offsets=FAKE, d_peak_power=FAKE,
+              d_center_offsets=FAKE, d_rects=FAKE, d_src_box=FAKE, d_counts=FAKE)
 
 
 def test_symbol_is_exported(native):
@@ -60,18 +48,18 @@ def test_symbol_is_exported(native):
 ])
 def test_fuse_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _fuse(native, **kw), match)
+    refused(native, _fuse(native, **kw), match)
 
 
 def test_valid_arguments_without_gpu(native):
     if native.gpu_available():
         pytest.skip("without a GPU only: with one, valid arguments would enqueue")
-    _refused(native, _fuse(native), "no usable HIP device")
-    _refused(native, _fuse(native, n_src=0, d_src_offsets=None, d_src_box=None), "no usable HIP device")
-    _refused(native, _fuse(native, n_src=64), "no usable HIP device")
-    _refused(native, _fuse(native, max_boxes=1), "no usable HIP device")
-    _refused(native, _fuse(native, d_box_counts=None, d_peak_power=None, d_center_offsets=None, d_rects=None, d_counts=None), "no usable HIP device")
-    _refused(native, _fuse(native, rows=361, cols=361, offset_per_dir=2048, image_stride=361 * 361), "no usable HIP device")
+    refused(native, _fuse(native), "no usable HIP device")
+    refused(native, _fuse(native, n_src=0, d_src_offsets=None, d_src_box=None), "no usable HIP device")
+    refused(native, _fuse(native, n_src=64), "no usable HIP device")
+    refused(native, _fuse(native, max_boxes=1), "no usable HIP device")
+    refused(native, _fuse(native, d_box_counts=None, d_peak_power=None, d_center_offsets=None, d_rects=None, d_counts=None), "no usable HIP device")
+    refused(native, _fuse(native, rows=361, cols=361, offset_per_dir=2048, image_stride=361 * 361), "no usable HIP device")
 
 
 def test_fusion_without_gpu(native):

@@ -9,15 +9,10 @@ import numpy as np
 import pytest
 
 import util
+from support import nat
 from util import ALGOS, CONFIGS, REL_TOL, golden, max_rel
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 def run_product(nat, algo, table, sig, mics):
@@ -315,11 +310,6 @@ def test_delay_helpers_bit_exact(nat, oracle_lib):
 
 # ------------------------------------------------------------------ device-resident batched entry point
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
 
 def batch_variant(algo, frames):
     """bf_last_das_variant() of a batch on geometric tables at N <= 256, M % 16 == 0 (include/beamformer_hip.h)"""
@@ -329,7 +319,7 @@ def batch_variant(algo, frames):
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
 def test_batched_device_path(nat, algo):
     """bf_das_device on HBM-resident frames: every frame equals the host-pointer call; direction shards equal slices."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import synth
     c = util.configure("cfg2")
     M, N, D = c["M"], c["N"], c["X"] * c["Y"]
@@ -360,7 +350,7 @@ def test_batched_device_path(nat, algo):
 def test_batched_frame_pairs(nat, oracle_lib, algo, cfg, n_active, F):
     """The two-frames-per-workgroup kernel: odd frame counts (the last workgroup row owns a single frame), a subset of the
     microphone rows (adaptive_array), the as-shipped 256-microphone array (16 chunks): bit-identical to the CPU oracle, frame by frame, and to the one-frame kernel."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import synth
     c = util.configure(cfg)
     M, N, X, Y = c["M"], c["N"], c["X"], c["Y"]
@@ -391,7 +381,7 @@ def test_batched_hybrid_frame_pairs(nat, oracle_lib, algo, cfg, n_active, F):
     shared between neighbouring directions, guard masks rebuilt with the window; naive / vectorized-order: one window per mic):
     odd frame counts, a subset of the microphone rows, the as-shipped 256-microphone array, a grid smaller than one workgroup
     pass -- bit-identical to the CPU oracle, frame by frame, and to the one-frame kernel."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import synth
     c = util.configure(cfg)
     M, N, X, Y = c["M"], c["N"], c["X"], c["Y"]
@@ -434,7 +424,7 @@ def test_batched_hybrid_frame_pairs(nat, oracle_lib, algo, cfg, n_active, F):
 def test_batched_frame_pairs_short_block(nat, oracle_lib, algo):
     """The pair kernel on a block that does not fill its 256-sample rows (N = 200) and a grid that is not a multiple of the
     128 directions a workgroup pass carries: bit-identical to the CPU oracle."""
-    torch = _torch()
+    torch = util.torch_gpu()
     from interface import config
     from lib import directions
     M, N, X, Y, T, F = 64, 200, 37, 31, 8, 3
@@ -466,7 +456,7 @@ def test_batched_frame_pairs_short_block(nat, oracle_lib, algo):
 def test_batched_large_tables_frame_inner_mapping(nat, cfg, algo, F):
     """Tables beyond the L2s (cfg2's 21 MB of hybrid taps, cfg5's 268 MB digest): the launch maps workgroup ids so that an
     XCD runs all frames of a direction tile back to back.  Every frame of the batch must equal the one-frame call."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import synth
     c = util.configure(cfg)
     try:
@@ -490,7 +480,7 @@ def test_full_size_properties(nat):
        * scaling a block by 2 scales its map by exactly 4 (power-of-two scaling is exact in float32);
        * frames are independent: permuting the batch permutes the maps;
        * a batch of identical frames gives identical maps."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import synth
     c = util.configure("cfg2")
     M, N, D, F = c["M"], c["N"], c["X"] * c["Y"], 190
@@ -626,7 +616,7 @@ def test_beamformer_producer_loops(nat, oracle_lib):
 def test_batched_random_tables_every_step_reloads(nat, oracle_lib, algo):
     """A table with no structure (independent random delays per direction and mic): the sweep kernel's worst case, every
     direction step re-reads its quads.  Batched device path, 5 frames, against the oracle frame by frame."""
-    torch = _torch()
+    torch = util.torch_gpu()
     from interface import config
     M, N, X, Y, T, F = 64, 256, 24, 23, 8, 5
     config.configure(N_MICROPHONES=M, N_SAMPLES=N, MAX_RES_X=X, MAX_RES_Y=Y, N_TAPS=T)

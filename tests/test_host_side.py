@@ -62,6 +62,49 @@ def test_every_declared_symbol_is_exported(native):
     assert not missing, missing
 
 
+def _c_kind(decl):
+    """The kind of a C parameter or return type as the header spells it."""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    for kind in ("long long", "int", "float", "double", "bool", "void"):
+        if words[:len(kind.split())] == kind.split() and len(words) <= len(kind.split()) + 1:    # the type, then at most a name
+            return kind
+    raise AssertionError("a type this test does not know: %r" % decl)
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "pointer"
+    return {C.c_longlong: "long long", C.c_int: "int", C.c_float: "float", C.c_double: "double", C.c_bool: "bool"}[t]
+
+
+def test_every_binding_matches_its_prototype(native):
+    """lib/_native.py against include/beamformer_hip.h: return type and every argument of every prototype, kind by kind (pointer or array,
+    int, float, double, long long, bool), and no binding of a name the header does not declare."""
+    text = open(os.path.join(util.ROOT, "include", "beamformer_hip.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    protos = re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b([A-Za-z_][A-Za-z0-9_]*)\s*\(([^;{()]*)\)\s*;", text)
+    assert len(protos) > 50
+    wrong = []
+    for ret, name, params in protos:
+        want = [_c_kind(ret)] + [_c_kind(p) for p in params.split(",") if p.split() not in ([], ["void"])]
+        fn = getattr(native.lib, name)
+        if fn.argtypes is None:
+            wrong.append((name, "not bound"))
+            continue
+        got = [_ctypes_kind(fn.restype)] + [_ctypes_kind(t) for t in fn.argtypes]
+        if got != want:
+            wrong.append((name, got, want))
+    assert not wrong, wrong
+    bound = {n for n, fn in vars(native.lib).items() if isinstance(fn, C._CFuncPtr) and fn.argtypes is not None}
+    assert len(bound) > 50
+    undeclared = sorted(bound - {name for _, name, _ in protos})
+    assert not undeclared, undeclared
+
+
 def test_api_h_management_symbols(native):
     """PC/src/api.h:6-9,41-45: exported so that the reference's main.pyx links unchanged.  steer / load_pa / load_miso keep the
     listen state (api.c:461-489, 553-581); the receiver child is out of scope, so load() fails loudly."""

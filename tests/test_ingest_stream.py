@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import util
+from support import nat
 
 pytestmark = pytest.mark.gpu
 
@@ -15,18 +16,6 @@ PROBES = [2 ** 31 - 1, -2 ** 31, 16777217, -16777217, 33554433, 1, -1, 0]      #
 VER = 2
 CANARY = 0x5A5AA5A5
 GUARD = 1024                                                                    # 4-byte elements: 4 KiB on either side
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 @pytest.fixture(autouse=True)
@@ -109,7 +98,7 @@ def numpy_status(pk, N, n_arrays, hop, F, ver=VER):
 
 
 def run(nat, d_pk, T, n_arrays, hop, F, m_total, d_mask, d_frames, d_status, ver=VER):
-    torch = _torch()
+    torch = util.torch_gpu()
     rc = nat.lib.bf_ingest_stream_device(d_pk.data_ptr(), T, n_arrays, 8, 8, hop, F, m_total, None if d_mask is None else d_mask.data_ptr(), ver,
                                          d_frames.data_ptr(), None if d_status is None else d_status.data_ptr(), torch.cuda.current_stream().cuda_stream)
     assert rc == 0, nat.lib.bf_last_error()
@@ -159,7 +148,7 @@ def test_cases_cover_what_the_issue_lists():
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d-a%d-F%d-hop%s-m%d-%s-o%d.%d" % c)
 def test_frames_match_oracle(nat, oracle_lib, case):
-    torch = _torch()
+    torch = util.torch_gpu()
     M, N, n_arrays, F, hop_text, m_total, mask_kind, off_in, off_out = case
     sizes(M, N)
     hop = hop_of(hop_text, N)
@@ -188,7 +177,7 @@ def test_frames_match_oracle(nat, oracle_lib, case):
 def test_past_the_datagram_element_is_zero_in_a_stream(nat, oracle_lib):
     """All four arrays present: row 248 (last array, last row, x = 0) reads stream[256], which in a stream is the next datagram's header.
     It comes out as 0 whatever that header holds, and the rows around it are data."""
-    torch = _torch()
+    torch = util.torch_gpu()
     M = N = 256
     sizes(M, N)
     F, T = 2, 2 * N
@@ -205,7 +194,7 @@ def test_past_the_datagram_element_is_zero_in_a_stream(nat, oracle_lib):
 
 @pytest.mark.parametrize("hop_text", ["N", "N/2", "N+37", "1"])
 def test_status_counts(nat, hop_text):
-    torch = _torch()
+    torch = util.torch_gpu()
     M, N, n_arrays = 256, 256, 3
     sizes(M, N)
     hop = hop_of(hop_text, N)
@@ -255,7 +244,7 @@ def test_status_counts(nat, hop_text):
 def test_stream_kernel_stays_inside_its_buffers(nat, shape):
     """d_frames and d_status each between two 4 KiB canary blocks inside one allocation, at the largest and the oddest shapes: the
     canaries are intact and the results equal a run on plain buffers."""
-    torch = _torch()
+    torch = util.torch_gpu()
     M, N, n_arrays, F, hop, m_total = shape
     sizes(M, N)
     T = (F - 1) * hop + N
@@ -287,7 +276,7 @@ def test_stream_kernel_stays_inside_its_buffers(nat, shape):
 
 @pytest.mark.parametrize("M,N,n_arrays,F", [(256, 256, 4, 7), (64, 256, 1, 7), (256, 1024, 4, 2), (128, 100, 2, 3)])
 def test_equals_per_frame_ingest(nat, M, N, n_arrays, F):
-    torch = _torch()
+    torch = util.torch_gpu()
     sizes(M, N)
     m_total = n_arrays * 64
     T = F * N
@@ -313,7 +302,7 @@ def _cfg2_lerp(nat):
 
 
 def test_chain_packets_to_beams(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     import ingest
     import listen
     c, table = _cfg2_lerp(nat)
@@ -350,7 +339,7 @@ def test_chain_packets_to_beams(nat, oracle_lib):
 
 
 def test_fused_pipeline_step_packets(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     import ingest
     import visual
     from pipeline import FusedPipeline
@@ -378,7 +367,7 @@ def test_fused_pipeline_step_packets(nat, oracle_lib):
 # ------------------------------------------------------------------ 6. ingest + delay-and-sum as one captured graph
 
 def test_graph_ingest_then_maps(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     c, table = _cfg2_lerp(nat)
     M, N, X, Y, T_ = c["M"], c["N"], c["X"], c["Y"], c["T"]
     D, F, hop = X * Y, 3, N // 2

@@ -10,23 +10,13 @@ import numpy as np
 import pytest
 
 import util
+from support import entry, FAKE, refused
 
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer": every call below is refused before anything could dereference it
 M, N = 256, 256         # the as-shipped sizes
 
 
-def _stream(nat, **kw):
-    a = dict(d_packets=FAKE, n_datagrams=4 * N, n_arrays=4, rows=8, columns=8, hop=N, frames=4, m_total=M, d_row_mask=None, protocol_ver=2,
-             d_frames=FAKE, d_status=None)
-    a.update(kw)
-    return nat.lib.bf_ingest_stream_device(a["d_packets"], a["n_datagrams"], a["n_arrays"], a["rows"], a["columns"], a["hop"], a["frames"], a["m_total"],
-                                           a["d_row_mask"], a["protocol_ver"], a["d_frames"], a["d_status"], None)
-
-
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
+_stream = entry("bf_ingest_stream_device", d_packets=FAKE, n_datagrams=4 * N, n_arrays=4, rows=8, columns=8, hop=N, frames=4, m_total=M,
+                d_row_mask=None, protocol_ver=2, d_frames=FAKE, d_status=None)
 
 
 @pytest.mark.parametrize("kw,match", [
@@ -56,16 +46,16 @@ def _refused(nat, rc, match):
 def test_ingest_stream_argument_errors(native, kw, match):
     util.configure("shipped")
     native.lib.bf_clear_error()
-    _refused(native, _stream(native, **kw), match)
+    refused(native, _stream(native, **kw), match)
 
 
 def test_ingest_stream_checks_follow_the_configured_sizes(native):
     """N_MICROPHONES and N_SAMPLES of the checks are the run-time sizes (bf_configure), not the as-shipped ones."""
     util.configure("cfg2")                         # 64 microphones x 256 samples
     native.lib.bf_clear_error()
-    _refused(native, _stream(native, n_arrays=2, m_total=128), r"n_arrays\*rows\*columns = 128 > N_MICROPHONES = 64")
+    refused(native, _stream(native, n_arrays=2, m_total=128), r"n_arrays\*rows\*columns = 128 > N_MICROPHONES = 64")
     util.configure("cfg5")                         # 256 x 1024
-    _refused(native, _stream(native, frames=1, n_datagrams=1023), r"\(frames - 1\) \* hop \+ N_SAMPLES = 1024 > n_datagrams = 1023")
+    refused(native, _stream(native, frames=1, n_datagrams=1023), r"\(frames - 1\) \* hop \+ N_SAMPLES = 1024 > n_datagrams = 1023")
     util.configure("shipped")
 
 
@@ -75,10 +65,10 @@ def test_ingest_stream_valid_arguments_without_gpu(native):
         pytest.skip("without a GPU only: with one, valid arguments would enqueue")
     util.configure("shipped")
     native.lib.bf_clear_error()
-    _refused(native, _stream(native), "no usable HIP device")
-    _refused(native, _stream(native, d_packets=FAKE + 4, d_frames=FAKE + 12, d_row_mask=FAKE, d_status=FAKE, hop=1, frames=190, n_datagrams=N + 189),
+    refused(native, _stream(native), "no usable HIP device")
+    refused(native, _stream(native, d_packets=FAKE + 4, d_frames=FAKE + 12, d_row_mask=FAKE, d_status=FAKE, hop=1, frames=190, n_datagrams=N + 189),
              "no usable HIP device")
-    _refused(native, _stream(native, n_arrays=1, m_total=64, hop=N + 37, frames=2, n_datagrams=2 * N + 37), "no usable HIP device")
+    refused(native, _stream(native, n_arrays=1, m_total=64, hop=N + 37, frames=2, n_datagrams=2 * N + 37), "no usable HIP device")
 
 
 def test_default_disabled_mics_are_what_get_data_zeroes(native):

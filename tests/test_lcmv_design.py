@@ -11,58 +11,27 @@ import pytest
 import filtersum_np as fsn
 import lcmv_np
 import util
+from support import nat_restoring as nat
+from util import CANARY_VALUE
 
 pytestmark = pytest.mark.gpu
-
-CANARY = 64                 # elements in front of and behind every device output
-CANARY_VALUE = -1234.5      # floats; the int outputs carry int(CANARY_VALUE) = -1234
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    yield native
-    util.configure("cfg1")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _canaried(shape, dtype):
-    torch = _torch()
-    total = int(np.prod(shape))
-    buf = torch.full((CANARY + total + CANARY,), CANARY_VALUE if dtype.is_floating_point else int(CANARY_VALUE), dtype=dtype, device="cuda")
-    return buf, buf[CANARY:CANARY + total]
-
-
-def _intact(buf, total):
-    host = buf.cpu().numpy()
-    want = host.dtype.type(CANARY_VALUE)
-    return bool((host[:CANARY] == want).all() and (host[CANARY + total:] == want).all())
 
 
 def _design(nat, tau, offsets, step, T, bins, rho, expect_rc=0):
     """One call on device copies -> (gains complex128 [S, K, n], taps float32 [S, n, T], kept int32 [S, K, S], status int32 [S])."""
-    torch = _torch()
+    torch = util.torch_gpu()
     tau = np.ascontiguousarray(tau, dtype=np.float64)
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     dirs, n = tau.shape
     S, K = offsets.size, len(bins)
     d_tau, d_off = torch.from_numpy(tau).cuda(), torch.from_numpy(offsets).cuda()
     shapes = [((S, K, n, 2), torch.float64), ((S, n, T), torch.float32), ((S, K, S), torch.int32), ((S,), torch.int32)]
-    bufs = [_canaried(shape, dtype) for shape, dtype in shapes]
+    bufs = [util.canaried(shape, dtype) for shape, dtype in shapes]
     rc = nat.lib.bf_lcmv_design_device(d_tau.data_ptr(), dirs, n, d_off.data_ptr(), S, step, T, int(bins[0]), int(bins[-1]), rho,
                                        *[view.data_ptr() for _, view in bufs], torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     for (buf, view), (shape, _) in zip(bufs, shapes):
-        assert _intact(buf, view.numel()), shape
+        assert util.intact(buf, view.numel()), shape
     if expect_rc != 0:
         assert rc == expect_rc and nat.lib.bf_last_error()
         nat.lib.bf_clear_error()
@@ -132,7 +101,7 @@ def test_matches_the_host_design(nat, host_table, n, S, T, band, rho, seed):
             worst_g, worst_t = max(worst_g, float(err_g.max())), max(worst_t, float(err_t.max()))
             assert np.isfinite(gains[i]).all() and (err_g <= 1e-9).all(), (name, i, float(err_g.max()))
             assert (err_t <= 2.0 ** -23).all(), (name, i, float(err_t.max()))
-        differ += int((_bits(taps) != _bits(want_taps)).sum())
+        differ += int((util.bits(taps) != util.bits(want_taps)).sum())
         total += taps.size
     print("n %d S %d T %d: %d of %d taps differ in bits; worst gain error %.3g of the bin's largest, worst tap error %.3g of the beam's largest"
           % (n, S, T, differ, total, worst_g, worst_t))
@@ -187,7 +156,7 @@ def test_all_slots_valid_are_the_cross_null_beams(nat, scene_tau):
     offsets = np.array([fsn.flat(c) for c in SCENE[:3]], dtype=np.int32) * M
     fl = filtersum.FilterSumListener.cross_null(scene_tau, offsets, M, n_taps=T, band=fsn.BAND, fs=fsn.FS)
     host, _, _ = filtersum.design_slots(scene_tau, offsets, M, n_taps=T, band=fsn.BAND, fs=fsn.FS)
-    assert np.array_equal(_bits(host), _bits(fl.taps))
+    assert np.array_equal(util.bits(host), util.bits(fl.taps))
     _, dev, _, _ = _design(nat, scene_tau, offsets, M, T, filtersum.band_bins(T, fsn.BAND, fsn.FS), 0.95)
     assert (np.abs(dev.astype(np.float64) - host) <= 2.0 ** -23 * np.abs(host).max(axis=(1, 2), keepdims=True)).all()
 
@@ -220,7 +189,7 @@ def test_graph_retarget_then_listen(nat):
     the beams follow without a host design.  The replayed beams are an eager run's bytes, and filtersum_np.filter_sum with
     design_slots' taps for the swapped offsets to within the taps' difference carried through the sum, sum|dg| max|x| per output;
     the interferer alone through beam 0 comes out at least 20 dB below the no-null design's (that test's own threshold)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import filtersum
     from interface import config
     from lib import directions
@@ -275,17 +244,17 @@ def test_graph_retarget_then_listen(nat):
     step()                                              # eager, on the same offsets and windows
     torch.cuda.synchronize()
     assert got.tobytes() == out[0].cpu().numpy().tobytes() and got_taps.tobytes() == fl.taps_host().tobytes()
-    assert not np.array_equal(got, as_captured) and np.array_equal(_bits(got[:, 0]), _bits(as_captured[:, 1]))      # the beams swapped with the talkers
+    assert not np.array_equal(got, as_captured) and np.array_equal(util.bits(got[:, 0]), util.bits(as_captured[:, 1]))      # the beams swapped with the talkers
 
     want_taps, _, _ = filtersum.design_slots(tau, swapped, M, n_taps=T, band=fsn.BAND, fs=fsn.FS)
     dg = np.abs(got_taps.astype(np.float64) - want_taps.astype(np.float64)).sum(axis=(1, 2))                        # per beam
-    print("taps that differ from the host design in bits: %d of %d; sum|dg| per beam %s" % (int((_bits(got_taps) != _bits(want_taps)).sum()), got_taps.size, dg))
+    print("taps that differ from the host design in bits: %d of %d; sum|dg| per beam %s" % (int((util.bits(got_taps) != util.bits(want_taps)).sum()), got_taps.size, dg))
     want = fsn.filter_sum(both, fl.mics, want_taps, hop, both_prev)
     err = np.abs(got.astype(np.float64) - want.astype(np.float64)).max(axis=(0, 2))
     bound = dg * float(np.abs(both).max())
     print("beams against filter_sum of the host design: worst difference per beam %s, bound %s" % (err, bound))
     assert (err <= bound).all()
-    assert np.array_equal(_bits(got), _bits(fsn.filter_sum(both, fl.mics, got_taps, hop, both_prev)))               # and the device's own taps: bit for bit
+    assert np.array_equal(util.bits(got), util.bits(fsn.filter_sum(both, fl.mics, got_taps, hop, both_prev)))               # and the device's own taps: bit for bit
 
     # the interferer alone, through the same graph: beam 0 against the same designer's beam without nulls
     das_taps, _ = filtersum.design_lcmv(tau, [look], None, n_taps=T, band=fsn.BAND, fs=fsn.FS)

@@ -8,18 +8,8 @@ import pytest
 
 import filtersum_np as fsn
 import lcmv_np
-
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-@pytest.fixture(scope="module")
-def tau():
-    import directions_np as D
-    return D.calculate_delays(fsn.GRID[0], fsn.GRID[1], arrays=1).reshape(-1, 64)
+import util
+from support import FAKE, grid_tau as tau
 
 
 SCENE = [fsn.LOOK, fsn.INTERFERER, fsn.NEAR, (5, 3)]
@@ -39,7 +29,7 @@ def test_all_slots_valid_is_the_cross_null_design(native, tau):
     want, want_kept = filtersum.design_lcmv(tau, dirs, nulls, n_taps=65, band=fsn.BAND, fs=fsn.FS)
     K = filtersum.band_bins(65, fsn.BAND, fsn.FS).size
     assert taps.dtype == np.float32 and taps.shape == (4, M, 65) and kept.dtype == np.int32 and kept.shape == (4, K, 4) and status.dtype == np.int32
-    assert np.array_equal(_bits(taps), _bits(want)) and (status == 0).all()
+    assert np.array_equal(util.bits(taps), util.bits(want)) and (status == 0).all()
     for i in range(4):
         others = [j for j in range(4) if j != i]
         assert np.array_equal(kept[i][:, others], want_kept[i].astype(np.int32))        # column j of kept is SLOT j, not position j of the list
@@ -63,7 +53,7 @@ def test_slots_that_are_no_source(native, tau):
     taps, kept, status = filtersum.design_slots(tau, offsets, M, n_taps=33, band=fsn.BAND, fs=fsn.FS)
     want, want_kept = filtersum.design_lcmv(tau, [look, null], [[null], [look]], n_taps=33, band=fsn.BAND, fs=fsn.FS)
     assert status.tolist() == [1, 0, 1, 1, 0]
-    assert np.array_equal(_bits(taps[[1, 4]]), _bits(want)) and not taps[[0, 2, 3]].any()
+    assert np.array_equal(util.bits(taps[[1, 4]]), util.bits(want)) and not taps[[0, 2, 3]].any()
     assert want_kept.all() and (kept[1, :, 4] == 1).all() and (kept[4, :, 1] == 1).all() and kept.sum() == 2 * kept.shape[1]
     # no source at all: every beam silent, nothing designed
     taps, kept, status = filtersum.design_slots(tau, [-1, 3], M, n_taps=33, band=fsn.BAND, fs=fsn.FS)
@@ -91,9 +81,9 @@ def test_a_duplicated_direction_is_dropped_as_a_null_everywhere(native, tau):
     assert not kept[0, :, 2].any() and not kept[2, :, 0].any()
     assert kept[1, :, 0].all() and not kept[1, :, 2].any()
     assert kept[0, :, 1].all() and kept[2, :, 1].all()
-    assert np.array_equal(_bits(taps[0]), _bits(taps[2]))
+    assert np.array_equal(util.bits(taps[0]), util.bits(taps[2]))
     want, _ = filtersum.design_lcmv(tau, [look, null], [[null], [look]], n_taps=33, band=fsn.BAND, fs=fsn.FS)
-    assert np.array_equal(_bits(taps[:2]), _bits(want))
+    assert np.array_equal(util.bits(taps[:2]), util.bits(want))
 
 
 @pytest.mark.parametrize("n,S,T,band,rho,seed", lcmv_np.TABLE)
@@ -107,7 +97,7 @@ def test_the_restatement_with_intermediates_is_design_slots(native, n, S, T, ban
         taps, kept, status = filtersum.design_slots(tau_r, row, step, n_taps=T, band=band, rho=rho, fs=lcmv_np.FS)
         r = lcmv_np.slot_gains(tau_r, row, step, T, band, rho)
         assert np.array_equal(kept, r["kept"]) and np.array_equal(status, r["status"]), name
-        assert np.array_equal(_bits(taps), _bits(lcmv_np.taps_of(r["gains"], r["bins"], T))), name
+        assert np.array_equal(util.bits(taps), util.bits(lcmv_np.taps_of(r["gains"], r["bins"], T))), name
         silent = status == 1
         assert not r["gains"][silent].any() and not kept[silent].any() and not kept[:, :, silent].any()
 

@@ -8,24 +8,14 @@ import pytest
 
 import match_cases as cases
 import match_np as mn
+import util
+from support import nat
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL_I, SENTINEL_F, TAIL = -77, -123.5, 16
 MATCH_NAMES = ("moved", "score", "shift", "status")
 SMOOTH_NAMES = ("out", "boosted", "counts", "state")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 def _buf(torch, shape, flt):
@@ -53,7 +43,7 @@ def _same(names, got, want, what):
 def _match(nat, images, prev, boxes, n=None, t_pct=120, s_pct=150, stride=4, shift=True):
     """bf_match_boxes_device into sentinel-filled buffers with a tail -> (moved, score, shift or None, status) as host arrays; the
     tails are checked here, and that no input was written.  stride > 4 pads the rows with a score, a class and more."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, B = boxes.shape[:2]
     H, W = images.shape[1:3]
     rows = np.full((F, B, stride), 0.625, dtype=np.float32)
@@ -108,7 +98,7 @@ def test_one_call_equals_one_call_per_frame(nat):
 # ------------------------------------------------------------------ the smoother against its restatement
 
 def _smooth(nat, c):
-    torch = _torch()
+    torch = util.torch_gpu()
     B, S = c["boxes"].shape[0], c["slots"]
     words = mn.state_words(S)
     d_boxes = torch.from_numpy(c["boxes"]).cuda()
@@ -148,7 +138,7 @@ def _scene_tensors(torch):
 def test_scene_through_the_front_end(nat, corr):
     """The object's row leaves every frame kept; with corr = 2.0 the stray candidate is dropped, with the reference's 0.8 it is boosted
     as well (the header says why).  One pass equals the same frames split over two update calls, state words included."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import pipeline
     import smooth
     want = cases.scene_reference(corr)
@@ -185,7 +175,7 @@ def test_scene_through_the_front_end(nat, corr):
 def test_graph_replays_on_images_overwritten_in_place(nat):
     """A captured update (one match and one smooth launch, and the copy of the image) replayed frame after frame on the same two
     tensors, overwritten in place, equals the stream's eager result."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import smooth
     want = cases.scene_reference(2.0)
     d_images, d_boxes = _scene_tensors(torch)

@@ -12,30 +12,15 @@ import pytest
 import match_cases as cases
 import match_np as mn
 import util
-
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
-
-
-def _match(nat, **kw):
-    a = dict(d_images=FAKE, d_prev=FAKE, frames=2, height=96, width=128, d_boxes=FAKE, box_stride=6, d_n_boxes=FAKE, max_boxes=300, t_pct=120, s_pct=150,
-             d_moved=FAKE, d_score=FAKE, d_shift=FAKE, d_status=FAKE)
-    a.update(kw)
-    return nat.lib.bf_match_boxes_device(a["d_images"], a["d_prev"], a["frames"], a["height"], a["width"], a["d_boxes"], a["box_stride"], a["d_n_boxes"],
-                                         a["max_boxes"], a["t_pct"], a["s_pct"], a["d_moved"], a["d_score"], a["d_shift"], a["d_status"], None)
+from support import entry, FAKE, refused
 
 
-def _smooth(nat, **kw):
-    a = dict(d_boxes=FAKE, d_n_boxes=FAKE, max_boxes=300, conf_low=0.3, conf_high=0.7, iou_threshold=0.5, corr_threshold=0.8, slots=16, d_moved=FAKE,
-             d_score=FAKE, d_status=FAKE, d_state=FAKE, d_out=FAKE, d_boosted=FAKE, d_counts=FAKE)
-    a.update(kw)
-    return nat.lib.bf_smooth_boxes_device(a["d_boxes"], a["d_n_boxes"], a["max_boxes"], a["conf_low"], a["conf_high"], a["iou_threshold"], a["corr_threshold"],
-                                          a["slots"], a["d_moved"], a["d_score"], a["d_status"], a["d_state"], a["d_out"], a["d_boosted"], a["d_counts"], None)
+_match = entry("bf_match_boxes_device", d_images=FAKE, d_prev=FAKE, frames=2, height=96, width=128, d_boxes=FAKE, box_stride=6, d_n_boxes=FAKE,
+               max_boxes=300, t_pct=120, s_pct=150, d_moved=FAKE, d_score=FAKE, d_shift=FAKE, d_status=FAKE)
 
 
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
+_smooth = entry("bf_smooth_boxes_device", d_boxes=FAKE, d_n_boxes=FAKE, max_boxes=300, conf_low=0.3, conf_high=0.7, iou_threshold=0.5,
+                corr_threshold=0.8, slots=16, d_moved=FAKE, d_score=FAKE, d_status=FAKE, d_state=FAKE, d_out=FAKE, d_boosted=FAKE, d_counts=FAKE)
 
 
 def test_symbols_are_exported_bound_and_declared(native):
@@ -79,7 +64,7 @@ def test_state_words(native):
 ])
 def test_match_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _match(native, **kw), match)
+    refused(native, _match(native, **kw), match)
 
 
 @pytest.mark.parametrize("kw,match", [
@@ -100,19 +85,19 @@ def test_match_argument_errors(native, kw, match):
 ])
 def test_smooth_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _smooth(native, **kw), match)
+    refused(native, _smooth(native, **kw), match)
 
 
 def test_valid_arguments_without_gpu(native):
     if native.gpu_available():
         pytest.skip("without a GPU only: with one, valid arguments would enqueue")
-    _refused(native, _match(native), "no usable HIP device")
+    refused(native, _match(native), "no usable HIP device")
     # the edges of every range pass the checks; the previous image, the count and the shift may be null
-    _refused(native, _match(native, height=8192, width=8192, max_boxes=1024, box_stride=4, t_pct=100, s_pct=400, frames=1), "no usable HIP device")
-    _refused(native, _match(native, height=1, width=1, max_boxes=1, t_pct=400, s_pct=400), "no usable HIP device")
-    _refused(native, _match(native, d_prev=None, d_n_boxes=None, d_shift=None), "no usable HIP device")
-    _refused(native, _smooth(native), "no usable HIP device")
-    _refused(native, _smooth(native, slots=64, max_boxes=1024, corr_threshold=2.0, conf_low=-1e30, d_n_boxes=None, d_boosted=None, d_counts=None), "no usable HIP device")
+    refused(native, _match(native, height=8192, width=8192, max_boxes=1024, box_stride=4, t_pct=100, s_pct=400, frames=1), "no usable HIP device")
+    refused(native, _match(native, height=1, width=1, max_boxes=1, t_pct=400, s_pct=400), "no usable HIP device")
+    refused(native, _match(native, d_prev=None, d_n_boxes=None, d_shift=None), "no usable HIP device")
+    refused(native, _smooth(native), "no usable HIP device")
+    refused(native, _smooth(native, slots=64, max_boxes=1024, corr_threshold=2.0, conf_low=-1e30, d_n_boxes=None, d_boosted=None, d_counts=None), "no usable HIP device")
     import smooth
     with pytest.raises(native.BeamformerError, match="no usable HIP device"):
         smooth.SmoothDetections(slots=4)

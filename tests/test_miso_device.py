@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import util
+from support import nat
 from test_miso_parity import MISO_CASES, _configure, case_id, case_tables
 
 pytestmark = pytest.mark.gpu
@@ -15,18 +16,6 @@ pytestmark = pytest.mark.gpu
 DEVICE_ALGOS = ["pad", "lerp", "hybrid", "fir_vec"]
 SENTINEL = 16
 MIC_GAIN = 128.0        # PC/src/config.json:62
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 class Tables:
@@ -73,7 +62,7 @@ def _frames(case, F):
 
 def _run(nat, algo, frames, mics, offsets, gain=0.0, out_stride=None, status=True, out=None):
     """bf_miso_device on device copies of frames [F, M, N] and offsets [F, B] -> (out tensor, status tensor or None)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, M, N = frames.shape
     B = offsets.shape[1]
     out_stride = out_stride or N
@@ -225,7 +214,7 @@ def test_invalid_offsets_are_nan_with_status(nat, oracle_lib, algo):
 
 
 def test_unloaded_table_is_an_error(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     case = MISO_CASES[0]
     _configure(case)
     N = case[2]
@@ -244,7 +233,7 @@ def test_unloaded_table_is_an_error(nat):
 # ------------------------------------------------------------------ 6. the loudest direction
 
 def _peaks(nat, power, stride, n_dirs, per):
-    torch = _torch()
+    torch = util.torch_gpu()
     F = power.shape[0]
     d_p = torch.from_numpy(np.ascontiguousarray(power, dtype=np.float32)).cuda()
     d_o = torch.full((F, 1), -5, dtype=torch.int32, device="cuda")
@@ -277,7 +266,7 @@ def test_peak_offsets_follow_argmax(nat):
 
 
 def test_peak_of_plane_wave_map(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     c = util.configure("cfg2")
     M, N, D = c["M"], c["N"], c["X"] * c["Y"]
     mics = np.arange(M, dtype=np.int32)
@@ -296,7 +285,7 @@ def test_peak_of_plane_wave_map(nat):
 # ------------------------------------------------------------------ 7. maps -> peak -> beams as one captured graph
 
 def test_graph_maps_peak_beams(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     import synth
     c = util.configure("cfg2")
     M, N, X, Y, T = c["M"], c["N"], c["X"], c["Y"], c["T"]
@@ -400,7 +389,7 @@ def test_long_blocks_five_directions(nat, oracle_lib, algo):
 # ------------------------------------------------------------------ 9. the Python front-end
 
 def test_beam_listener(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     case = MISO_CASES[2]
     M_total, n, N, T, D = case[:5]

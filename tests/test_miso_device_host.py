@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 import util
-
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
+from support import entry, FAKE, refused
 
 
 def _miso(nat, **kw):
@@ -24,16 +23,7 @@ def _miso(nat, **kw):
                                   a["beams"], a["mic_gain"], a["d_out"], stride, a["d_status"], None)
 
 
-def _peak(nat, **kw):
-    a = dict(d_power=FAKE, frames=2, image_stride=10, n_dirs=10, offset_per_dir=4, d_offsets=FAKE)
-    a.update(kw)
-    return nat.lib.bf_peak_offsets_device(a["d_power"], a["frames"], a["image_stride"], a["n_dirs"], a["offset_per_dir"], a["d_offsets"], None)
-
-
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
+_peak = entry("bf_peak_offsets_device", d_power=FAKE, frames=2, image_stride=10, n_dirs=10, offset_per_dir=4, d_offsets=FAKE)
 
 
 def _n_samples(nat):
@@ -61,13 +51,13 @@ def _n_samples(nat):
 ])
 def test_miso_device_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _miso(native, **kw), match)
+    refused(native, _miso(native, **kw), match)
 
 
 def test_miso_device_out_stride_and_n(native):
     N = _n_samples(native)
-    _refused(native, _miso(native, out_stride=N - 1), "out_stride = %d < N_SAMPLES = %d" % (N - 1, N))
-    _refused(native, _miso(native, n=0), "n = 0 < 1")
+    refused(native, _miso(native, out_stride=N - 1), "out_stride = %d < N_SAMPLES = %d" % (N - 1, N))
+    refused(native, _miso(native, n=0), "n = 0 < 1")
 
 
 @pytest.mark.parametrize("kw,match", [
@@ -81,22 +71,22 @@ def test_miso_device_out_stride_and_n(native):
 ])
 def test_peak_offsets_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _peak(native, **kw), match)
+    refused(native, _peak(native, **kw), match)
 
 
 def test_peak_offsets_largest_offset_that_fits_passes_the_checks(native):
     """(n_dirs - 1) * offset_per_dir == INT_MAX is accepted by the argument checks (and then needs a device)."""
     if native.gpu_available():
         pytest.skip("without a GPU only: with one, valid arguments would enqueue")
-    _refused(native, _peak(native, n_dirs=2, image_stride=2, offset_per_dir=2 ** 31 - 1), "no usable HIP device")
+    refused(native, _peak(native, n_dirs=2, image_stride=2, offset_per_dir=2 ** 31 - 1), "no usable HIP device")
 
 
 def test_valid_arguments_without_gpu(native):
     if native.gpu_available():
         pytest.skip("without a GPU only")
-    _refused(native, _miso(native), "no usable HIP device")
-    _refused(native, _miso(native, algo=native.FIR_VEC, d_status=None, mic_gain=128.0), "no usable HIP device")
-    _refused(native, _peak(native), "no usable HIP device")
+    refused(native, _miso(native), "no usable HIP device")
+    refused(native, _miso(native, algo=native.FIR_VEC, d_status=None, mic_gain=128.0), "no usable HIP device")
+    refused(native, _peak(native), "no usable HIP device")
 
 
 def test_beam_listener_without_gpu(native):

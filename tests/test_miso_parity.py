@@ -13,6 +13,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from support import nat
+
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 16
@@ -84,12 +86,6 @@ def _assert_written(buf, want, n):
     """All n samples written, bit for bit; the 16-float tail still NaN."""
     assert buf[:n].tobytes() == want.tobytes(), np.flatnonzero(buf[:n].view(np.int32) != want.view(np.int32))[:8]
     assert buf[n:].tobytes() == np.full(SENTINEL, np.nan, dtype=np.float32).tobytes()
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 # ------------------------------------------------------------------ miso_*: every NC, one and several chunks

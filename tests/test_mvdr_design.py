@@ -11,51 +11,15 @@ import filtersum_np as fsn
 import lcmv_np
 import mvdr_np
 import util
+from support import nat_restoring as nat, scene_tau
+from util import CANARY_VALUE
 
 pytestmark = pytest.mark.gpu
-
-CANARY = 64                 # elements in front of and behind every device output
-CANARY_VALUE = -1234.5      # floats; the int outputs carry int(CANARY_VALUE) = -1234
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    yield native
-    util.configure("cfg1")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _sizes(N):
-    from interface import config
-    config.configure(N_MICROPHONES=4, N_SAMPLES=N, MAX_RES_X=2, MAX_RES_Y=1, N_TAPS=8)
 
 
 def _scene_sizes():
     from interface import config
     config.configure(N_MICROPHONES=64, ACTIVE_TILES=1, N_SAMPLES=mvdr_np.N, MAX_RES_X=fsn.GRID[0], MAX_RES_Y=fsn.GRID[1], N_TAPS=8)
-
-
-def _canaried(shape, dtype):
-    torch = _torch()
-    total = int(np.prod(shape))
-    buf = torch.full((CANARY + total + CANARY,), CANARY_VALUE if dtype.is_floating_point else int(CANARY_VALUE), dtype=dtype, device="cuda")
-    return buf, buf[CANARY:CANARY + total]
-
-
-def _intact(buf, total):
-    host = buf.cpu().numpy()
-    want = host.dtype.type(CANARY_VALUE)
-    return bool((host[:CANARY] == want).all() and (host[CANARY + total:] == want).all())
 
 
 def _cplx(a):
@@ -65,13 +29,13 @@ def _cplx(a):
 def _design(nat, frames, mics, tau, offsets, step, T, bins, loading, seg_first, seg_hop, segs, window=None, expect_rc=0, n=None):
     """One call on device copies (N_SAMPLES configured to the frames') -> dict(snap complex128 [P, K, n], cov, chol [K, n, n], gains
     [S, K, n], taps float32 [S, n, T], status int32 [S], fallback int32 [K], raw = the float64 (re, im) arrays as the device wrote them)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     frames = np.ascontiguousarray(frames, dtype=np.float32)
     tau = np.ascontiguousarray(tau, dtype=np.float64)
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     mics = np.ascontiguousarray(mics, dtype=np.int32)
     F, m_total, N = frames.shape
-    _sizes(N)
+    util.configure_small(N)
     dirs, n = tau.shape[0], (tau.shape[1] if n is None else n)
     S, K, P = offsets.size, len(bins), F * max(segs, 1)
     d_x, d_tau, d_off = torch.from_numpy(frames).cuda(), torch.from_numpy(tau).cuda(), torch.from_numpy(offsets).cuda()
@@ -80,13 +44,13 @@ def _design(nat, frames, mics, tau, offsets, step, T, bins, loading, seg_first, 
     names = ["snap", "cov", "chol", "gains", "taps", "status", "fallback"]
     shapes = [((P, K, m, 2), torch.float64), ((K, m, m, 2), torch.float64), ((K, m, m, 2), torch.float64), ((S, K, m, 2), torch.float64),
               ((S, m, T), torch.float32), ((S,), torch.int32), ((K,), torch.int32)]
-    bufs = [_canaried(shape, dtype) for shape, dtype in shapes]
+    bufs = [util.canaried(shape, dtype) for shape, dtype in shapes]
     rc = nat.lib.bf_mvdr_design_device(d_x.data_ptr(), m_total, F, nat.iptr(mics), n, seg_first, seg_hop, segs, None if d_win is None else d_win.data_ptr(),
                                        d_tau.data_ptr(), dirs, d_off.data_ptr(), S, step, T, int(bins[0]), int(bins[-1]), loading,
                                        *[view.data_ptr() for _, view in bufs], torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     for (buf, view), (shape, _) in zip(bufs, shapes):
-        assert _intact(buf, view.numel()), shape
+        assert util.intact(buf, view.numel()), shape
     if expect_rc != 0:
         assert rc == expect_rc and nat.lib.bf_last_error()
         nat.lib.bf_clear_error()
@@ -191,7 +155,7 @@ def _check_stages(got, r, loading, what):
         at, ratio = _worst(np.abs(got["taps"][i].astype(np.float64) - want), np.full(want.shape, 2.0 ** -23 * np.abs(want).max()))
         assert ratio <= 1.0, (what, "taps: beam %d, worst entry (mic, t) %s at %.3g of the bound" % (i, at, ratio))
         ratio_t = max(ratio_t, ratio)
-    return ratio_s, ratio_c, ratio_l, ratio_g, ratio_t, int((_bits(got["taps"]) != _bits(r["taps"])).sum()), got["taps"].size
+    return ratio_s, ratio_c, ratio_l, ratio_g, ratio_t, int((util.bits(got["taps"]) != util.bits(r["taps"])).sum()), got["taps"].size
 
 
 @pytest.mark.parametrize("case", mvdr_np.TABLE, ids=mvdr_np.case_id)
@@ -215,7 +179,7 @@ def test_matches_the_host_design_stage_by_stage(nat, host_table, case):
 def test_silence_and_a_nan_fall_back_to_the_beam_without_nulls(nat):
     """All-zero frames: every bin falls back, L = I, and the taps are the device's own bf_lcmv_design_device with that slot alone (no
     nulls) to 2^-23 of the largest.  One NaN sample: the same fallback and the same taps; the factor, the gains and the taps stay finite."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import filtersum
     case = mvdr_np.TABLE[4]                                           # n = 70 of 72 rows, T = 33
     n, m_total, S, T, N, F = case[:6]
@@ -267,21 +231,13 @@ def test_same_bits_from_call_to_call_and_whatever_is_designed_together(nat):
 
 # ------------------------------------------------------------------ 4. function: an interferer no slot names
 
-@pytest.fixture(scope="module")
-def scene_tau():
-    return mvdr_np.scene_tau()
-
-
-def _audio_power(listener, out):
-    return mvdr_np.power(listener.audio(out).cpu().numpy()[0])
-
 
 def test_the_unnamed_interferer_is_suppressed(nat, scene_tau):
     """The scene of tests/mvdr_np.py; ONE slot, on the look direction, so the geometric designer (retarget) can only give delay-and-sum.
     adapt() on the interferer + noise windows, then the interferer alone through listen(): its power is within 1 dB of what the host
     design's taps leak (filtersum_np.filter_sum), at least 20 dB below the retarget beam's, and the device taps' response towards the
     look direction is f0 within n T 2^-24 max|g| (what the float32 rounding of the taps allows).  The README's three rows are printed."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import filtersum
     _scene_sizes()
     M, N, hop, T = mvdr_np.M, mvdr_np.N, mvdr_np.HOP, mvdr_np.T
@@ -296,7 +252,7 @@ def test_the_unnamed_interferer_is_suppressed(nat, scene_tau):
     for listener in (fl, geo):
         listener.advance(torch.from_numpy(alone_prev[None]).cuda())
     geo.retarget(d_off)
-    leak_geo = fsn.db(_audio_power(geo, geo.listen(d_alone)))
+    leak_geo = fsn.db(util.audio_power(geo, geo.listen(d_alone)))
     bins = fl.bins
     w = 2.0 * np.pi * bins / T
     rows = []
@@ -306,7 +262,7 @@ def test_the_unnamed_interferer_is_suppressed(nat, scene_tau):
         torch.cuda.synchronize()
         assert status.cpu().numpy().tolist() == [0] and not fallback.cpu().numpy().any() and fl.taps is None
         dev = fl.taps_host().copy()
-        leak_dev = fsn.db(_audio_power(fl, fl.listen(d_alone)))
+        leak_dev = fsn.db(util.audio_power(fl, fl.listen(d_alone)))
         rows.append(mvdr_np.row(sc, dev[0]))
         print("device design, covariance from %s: interferer %.1f dB, white-noise gain %.1f dB, look %+.2f dB; through listen() %.1f dB (retarget: %.1f dB)"
               % ((name,) + rows[-1] + (leak_dev, leak_geo)))
@@ -318,7 +274,7 @@ def test_the_unnamed_interferer_is_suppressed(nat, scene_tau):
             want = fsn.filter_sum(alone, fl.mics, host, hop, alone_prev)
             leak_host = fsn.db(mvdr_np.power(want[:, 0, N - hop:]))
             print("interferer alone: host design %.2f dB, device design %.2f dB, retarget (delay-and-sum) %.2f dB: %.1f dB better; %d of %d taps differ in bits"
-                  % (leak_host, leak_dev, leak_geo, leak_geo - leak_dev, int((_bits(dev) != _bits(host)).sum()), dev.size))
+                  % (leak_host, leak_dev, leak_geo, leak_geo - leak_dev, int((util.bits(dev) != util.bits(host)).sum()), dev.size))
             assert abs(leak_dev - leak_host) <= 1.0
             assert leak_geo - leak_dev >= 20.0
     with pytest.raises(ValueError):
@@ -346,7 +302,7 @@ def test_graph_adapt_then_listen(nat, scene_tau):
     ON THE DEVICE with windows whose interferer sits at NEAR instead of INTERFERER and the graph replayed: the beam adapts without a
     host design.  The replay's bytes are an eager run's, the taps stay where they were, the beams are filtersum_np.filter_sum with the
     device's own taps bit for bit, and the new interferer alone comes out at least 20 dB below delay-and-sum's leak."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import filtersum
     _scene_sizes()
     M, N, hop, T = mvdr_np.M, mvdr_np.N, mvdr_np.HOP, mvdr_np.T
@@ -393,15 +349,15 @@ def test_graph_adapt_then_listen(nat, scene_tau):
     step()                                              # eager, on the same windows
     torch.cuda.synchronize()
     assert got.tobytes() == out[0].cpu().numpy().tobytes() and got_taps.tobytes() == fl.taps_host().tobytes()
-    assert np.array_equal(_bits(got), _bits(fsn.filter_sum(train_near, fl.mics, got_taps, hop, prev_near)))
+    assert np.array_equal(util.bits(got), util.bits(fsn.filter_sum(train_near, fl.mics, got_taps, hop, prev_near)))
 
     das_taps, _ = filtersum.design_lcmv(tau, [look], None, n_taps=T, band=fsn.BAND, fs=fsn.FS)
     das = filtersum.FilterSumListener(das_taps, hop=hop)
     d_alone, d_alone_prev = torch.from_numpy(alone).cuda(), torch.from_numpy(alone_prev[None]).cuda()
     fl.advance(d_alone_prev)
     das.advance(d_alone_prev)
-    leak_mvdr = fsn.db(_audio_power(fl, fl.listen(d_alone)))          # listen() alone: the taps are the replay's
-    leak_das = fsn.db(_audio_power(das, das.listen(d_alone)))
+    leak_mvdr = fsn.db(util.audio_power(fl, fl.listen(d_alone)))          # listen() alone: the taps are the replay's
+    leak_das = fsn.db(util.audio_power(das, das.listen(d_alone)))
     print("the interferer moved to NEAR, through the replayed design: delay-and-sum %.1f dB, adapted %.1f dB (%.1f dB better)" % (leak_das, leak_mvdr, leak_das - leak_mvdr))
     assert leak_das - leak_mvdr >= 20.0
 

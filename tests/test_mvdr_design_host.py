@@ -11,26 +11,7 @@ import filtersum_np as fsn
 import lcmv_np
 import mvdr_np
 import util
-
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-@pytest.fixture(scope="module")
-def tau():
-    return mvdr_np.scene_tau()
-
-
-@pytest.fixture(scope="module")
-def sized(native):
-    """The refusals compare with N_SAMPLES = 256."""
-    from interface import config
-    config.configure(N_MICROPHONES=64, ACTIVE_TILES=1, N_SAMPLES=256, MAX_RES_X=fsn.GRID[0], MAX_RES_Y=fsn.GRID[1], N_TAPS=8)
-    yield native
-    util.configure("cfg1")
+from support import FAKE, scene_tau as tau, sized
 
 
 # ------------------------------------------------------------------ the host design
@@ -52,7 +33,7 @@ def test_the_restatement_with_intermediates_is_design_mvdr_slots(native, case):
                                                              seg_hop=seg_hop, segs=segs, window=win, fs=mvdr_np.FS)
         r = mvdr_np.slot_stages(frames, mics, tau_r, row, step, T, band, loading, seg_first, seg_hop, segs, win)
         assert np.array_equal(fallback, r["fallback"]) and not fallback.any() and np.array_equal(status, r["status"]), name
-        assert taps.dtype == np.float32 and taps.shape == (S, n, T) and np.array_equal(_bits(taps), _bits(r["taps"])), name
+        assert taps.dtype == np.float32 and taps.shape == (S, n, T) and np.array_equal(util.bits(taps), util.bits(r["taps"])), name
         assert not taps[status == 1].any() and not r["gains"][status == 1].any() and all(taps[i].any() for i in np.flatnonzero(status == 0))
         assert r["conds"].max() <= n / loading + 1.0 + 1e-6 and r["conds"].max() <= 1e4
         L = r["chol"]
@@ -63,7 +44,7 @@ def test_the_restatement_with_intermediates_is_design_mvdr_slots(native, case):
                                     loading=loading, seg_first=seg_first, seg_hop=seg_hop, segs=segs, window=win, fs=mvdr_np.FS)
     first = filtersum.design_mvdr_slots(frames, mics, tau_r, lcmv_np.offset_rows(n, S, T, 0)[0][1], step, n_taps=T, band=band, loading=loading,
                                         seg_first=seg_first, seg_hop=seg_hop, segs=segs, window=win, fs=mvdr_np.FS)[0]
-    assert np.array_equal(_bits(look[0]), _bits(first[0]))            # design_mvdr is the same design without the slot semantics
+    assert np.array_equal(util.bits(look[0]), util.bits(first[0]))            # design_mvdr is the same design without the slot semantics
 
 
 def test_silence_and_a_huge_loading_give_the_beam_without_nulls(native, tau):

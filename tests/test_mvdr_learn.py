@@ -13,35 +13,28 @@ import mvdr_learn_np as mln
 import mvdr_np
 import test_mvdr_design as design_tests
 import util
+from support import nat_restoring as nat, scene_tau
+from util import CANARY_VALUE
 
 pytestmark = pytest.mark.gpu
 
-CANARY_VALUE = design_tests.CANARY_VALUE
-_torch, _canaried, _intact, _cplx, _bits, _worst = (design_tests._torch, design_tests._canaried, design_tests._intact, design_tests._cplx, design_tests._bits,
-                                                     design_tests._worst)
+_cplx, _worst = design_tests._cplx, design_tests._worst
 NAMES = ["used", "snap", "cov", "chol", "gains", "taps", "status", "fallback"]
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    yield native
-    util.configure("cfg1")
 
 
 class State:
     """d_acc and d_mass between canaries, empty (zero) to begin with."""
 
     def __init__(self, K, m):
-        torch = _torch()
+        torch = util.torch_gpu()
         self.K, self.m = K, m
-        (self.acc_buf, self.acc), (self.mass_buf, self.mass) = _canaried((K, m, m, 2), torch.float64), _canaried((1,), torch.float64)
+        (self.acc_buf, self.acc), (self.mass_buf, self.mass) = util.canaried((K, m, m, 2), torch.float64), util.canaried((1,), torch.float64)
         self.acc.zero_()
         self.mass.zero_()
 
     def host(self):
         """-> (raw float64 [K, m, m, 2], mass float), the canaries checked."""
-        assert _intact(self.acc_buf, self.acc.numel()) and _intact(self.mass_buf, 1)
+        assert util.intact(self.acc_buf, self.acc.numel()) and util.intact(self.mass_buf, 1)
         return self.acc.cpu().numpy().reshape(self.K, self.m, self.m, 2), float(self.mass.cpu().numpy()[0])
 
     def bytes(self):
@@ -53,7 +46,7 @@ def _learn(nat, st, frames, mics, tau, offsets, step, T, bins, loading, seg_firs
            null_snap=False):
     """One call on device copies; frames None is the re-aim (N then says what N_SAMPLES is; d_snap points at canaries that must survive).
     -> test_mvdr_design._design's dict plus used int32 [2], acc complex128 [K, n, n], total (the mass), raw["acc"]."""
-    torch = _torch()
+    torch = util.torch_gpu()
     tau = np.ascontiguousarray(tau, dtype=np.float64)
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     mics = np.ascontiguousarray(mics, dtype=np.int32)
@@ -64,7 +57,7 @@ def _learn(nat, st, frames, mics, tau, offsets, step, T, bins, loading, seg_firs
         frames = np.ascontiguousarray(frames, dtype=np.float32)
         F, m_total, N = frames.shape
         d_x = torch.from_numpy(frames).cuda()
-    design_tests._sizes(N)
+    util.configure_small(N)
     dirs, m = tau.shape
     S, K, P = offsets.size, len(bins), max(F, 1) * max(segs, 1)
     d_tau, d_off = torch.from_numpy(tau).cuda(), torch.from_numpy(offsets).cuda()
@@ -72,7 +65,7 @@ def _learn(nat, st, frames, mics, tau, offsets, step, T, bins, loading, seg_firs
     d_w = None if weights is None or F == 0 else torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).cuda()
     shapes = [((2,), torch.int32), ((P, K, m, 2), torch.float64), ((K, m, m, 2), torch.float64), ((K, m, m, 2), torch.float64), ((S, K, m, 2), torch.float64),
               ((S, m, T), torch.float32), ((S,), torch.int32), ((K,), torch.int32)]
-    bufs = [_canaried(shape, dtype) for shape, dtype in shapes]
+    bufs = [util.canaried(shape, dtype) for shape, dtype in shapes]
     before = st.bytes()
     ptr = [view.data_ptr() for _, view in bufs]
     rc = nat.lib.bf_mvdr_learn_device(None if d_x is None else d_x.data_ptr(), m_total, F, nat.iptr(mics), m, seg_first, seg_hop, segs,
@@ -81,7 +74,7 @@ def _learn(nat, st, frames, mics, tau, offsets, step, T, bins, loading, seg_firs
                                       None if null_snap else ptr[1], *ptr[2:], torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     for (buf, view), (shape, _) in zip(bufs, shapes):
-        assert _intact(buf, view.numel()), shape
+        assert util.intact(buf, view.numel()), shape
     untouched = lambda view: bool((view.cpu().numpy() == view.cpu().numpy().dtype.type(CANARY_VALUE)).all())
     if expect_rc != 0:
         assert rc == expect_rc and nat.lib.bf_last_error()
@@ -226,7 +219,7 @@ def test_skipped_frames_leave_the_state_alone_and_an_empty_state_falls_back(nat)
     """Weights 0, -0.0, NaN, Inf, -1, 0 on a learned state: d_acc and d_mass keep their bytes, d_used = (0, 3), the snapshots are written
     all the same and the taps are the re-aim's on that state.  The same batch on the EMPTY state: still all-zero bytes, fallback at every
     bin, and the taps within 2^-23 of bf_lcmv_design_device's beam without nulls (as test_silence_and_a_nan... compares)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     case = mln.by_n(3)
     n, S, T, N, forget = case[0], case[2], case[3], case[4], case[13]
     first, frames, mics, tau, win, _ = mln.case_inputs(case)
@@ -312,21 +305,13 @@ def test_reaim_designs_from_the_state_as_it_stands(nat):
 
 # ------------------------------------------------------------------ 6. function, through FilterSumListener
 
-@pytest.fixture(scope="module")
-def scene_tau():
-    return mvdr_np.scene_tau()
-
-
-def _audio_power(listener, out):
-    return mvdr_np.power(listener.audio(out).cpu().numpy()[0])
-
 
 def test_weights_cure_self_cancellation_and_forgetting_follows_a_moved_interferer(nat, scene_tau):
     """The two scenes of tests/mvdr_learn_np.py, ONE slot on LOOK.  Each design starts from forget_all(); the interferer alone then goes
     through listen(): its power is within 1 dB of what the host design's taps leak (filtersum_np.filter_sum), the response towards
     LOOK is f0 within M T 2^-24 max|g|.  Learned from the look-free windows the beam is at least 6 dB better than learned from all
     fourteen; with forget 0.7 at least 3 dB better on the moved interferer than with forget 1.  The README's rows are printed."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import filtersum
     design_tests._scene_sizes()
     M, N, hop, T = mln.M, mln.N, mln.HOP, mln.T
@@ -340,7 +325,7 @@ def test_weights_cure_self_cancellation_and_forgetting_follows_a_moved_interfere
         """-> the device design's leak of sc's interferer through listen(), checked against the host design's."""
         alone, alone_prev = mvdr_np.cut(sc["interferer"])
         fl.advance(torch.from_numpy(alone_prev[None]).cuda())
-        leak_dev = fsn.db(_audio_power(fl, fl.listen(torch.from_numpy(alone).cuda())))
+        leak_dev = fsn.db(util.audio_power(fl, fl.listen(torch.from_numpy(alone).cuda())))
         dev = fl.taps_host().copy()
         host = mln.host_taps(host_state, tau)
         leak_host = fsn.db(mvdr_np.power(fsn.filter_sum(alone, fl.mics, host, hop, alone_prev)[:, 0, N - hop:]))
@@ -398,7 +383,7 @@ def test_graph_learn_then_listen(nat, scene_tau):
     the warm-up learned too).  Replayed, d_frames overwritten ON THE DEVICE with the moved interferer's windows, replayed again: a replay
     advances the state, so state and taps are, byte for byte, those of two eager calls from an empty state on a second listener; no
     tensor moved; the beams are filtersum_np.filter_sum with the device's own taps bit for bit."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import filtersum
     design_tests._scene_sizes()
     M, N, hop, T = mln.M, mln.N, mln.HOP, mln.T
@@ -447,7 +432,7 @@ def test_graph_learn_then_listen(nat, scene_tau):
     for name in ("d_acc", "d_mass", "d_taps", "d_cov"):
         assert getattr(fl, name).cpu().numpy().tobytes() == getattr(eager, name).cpu().numpy().tobytes(), name
     assert got.tobytes() == out[0].cpu().numpy().tobytes()
-    assert np.array_equal(_bits(got), _bits(fsn.filter_sum(frames_new, fl.mics, got_taps, hop, prev_new)))
+    assert np.array_equal(util.bits(got), util.bits(fsn.filter_sum(frames_new, fl.mics, got_taps, hop, prev_new)))
 
 
 # ------------------------------------------------------------------ 8. refusals worth a device: nothing may be enqueued

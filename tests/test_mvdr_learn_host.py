@@ -12,32 +12,13 @@ import lcmv_np
 import mvdr_learn_np as mln
 import mvdr_np
 import util
-
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+from support import FAKE, scene_tau as tau, sized
 
 
 def _close(taps, want):
     """Every beam within 2^-23 of its largest tap."""
     want = want.astype(np.float64)
     return all((np.abs(taps[i].astype(np.float64) - want[i]) <= 2.0 ** -23 * np.abs(want[i]).max()).all() for i in range(want.shape[0]))
-
-
-@pytest.fixture(scope="module")
-def tau():
-    return mvdr_np.scene_tau()
-
-
-@pytest.fixture(scope="module")
-def sized(native):
-    """The refusals compare with N_SAMPLES = 256."""
-    from interface import config
-    config.configure(N_MICROPHONES=64, ACTIVE_TILES=1, N_SAMPLES=256, MAX_RES_X=fsn.GRID[0], MAX_RES_Y=fsn.GRID[1], N_TAPS=8)
-    yield native
-    util.configure("cfg1")
 
 
 # ------------------------------------------------------------------ 1, 2. the settings at which it is the existing design
@@ -62,7 +43,7 @@ def test_empty_state_unit_weights_and_no_forgetting_are_design_mvdr_slots(native
         assert np.array_equal(fallback, want_fallback) and np.array_equal(status, want_status), name
         assert taps.dtype == np.float32 and taps.shape == want.shape and _close(taps, want), name
         r = mln.state_stages(acc, mass, tau_r, row, step, T, band, loading)
-        assert np.array_equal(_bits(r["taps"]), _bits(taps)) and np.array_equal(r["fallback"], fallback) and np.array_equal(r["status"], status), name
+        assert np.array_equal(util.bits(r["taps"]), util.bits(taps)) and np.array_equal(r["fallback"], fallback) and np.array_equal(r["status"], status), name
         assert r["conds"].max() <= n / loading + 1.0 + 1e-6 and r["conds"].max() <= 1e4
 
 
@@ -144,7 +125,7 @@ def test_invalid_and_zero_weights_are_skipped_and_an_empty_mass_falls_back(nativ
     want, _ = filtersum.design_lcmv(tau_r, [int(o) // step for o in row], None, n_taps=T, band=band, fs=mln.FS)
     assert fallback.tolist() == [1] * fallback.size and status.tolist() == [0] * S and _close(taps, want)
     taps_a, fallback_a, _ = filtersum.design_mvdr_learned(a, 0.0, tau_r, row, step, n_taps=T, band=band, loading=loading, fs=mln.FS)    # a state, but no mass
-    assert fallback_a.all() and np.array_equal(_bits(taps_a), _bits(taps))
+    assert fallback_a.all() and np.array_equal(util.bits(taps_a), util.bits(taps))
     for bad in (dict(forget=0.0), dict(forget=1.0000001), dict(forget=float("nan")), dict(forget=-0.5)):
         with pytest.raises(ValueError):
             filtersum.mvdr_learn(None, 0.0, frames, mics, None, **dict(kw, **bad))

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import util
+from support import nat
 from util import ALGOS
 
 pytestmark = pytest.mark.gpu
@@ -84,12 +85,6 @@ def _split_sum_differs(orc, c, frames, mics, delays, want0):
         if halves.tobytes() != ordered.tobytes():
             differ.append(d)
     return differ
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])

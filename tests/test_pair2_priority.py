@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import util
+from support import nat
 from util import ALGOS
 
 pytestmark = pytest.mark.gpu
@@ -38,12 +39,6 @@ CASES = [
     Case("mics48_of_56_f3", 56, 48, 256, 3, 3, 392),
     Case("group_of_5_f171", 64, 16, 256, 171, 3, 392),
 ]
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 @pytest.fixture(scope="module")

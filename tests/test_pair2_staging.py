@@ -22,6 +22,7 @@ import collections
 import numpy as np
 import pytest
 
+from support import nat
 from util import ALGOS
 
 pytestmark = pytest.mark.gpu
@@ -56,12 +57,6 @@ def _data(c):
     delays = np.float32(delays)
     assert delays.min() == 0.0 and delays.max() == 54.75
     return frames, mics, delays
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])

@@ -8,6 +8,7 @@ import pytest
 
 import peaks_np
 import util
+from support import nat
 
 pytestmark = pytest.mark.gpu
 
@@ -16,22 +17,10 @@ SHAPES = [(11, 11), (57, 32), (101, 101), (361, 361), (1, 300), (300, 1)]
 RADII = [0, 1, 4, 12, 400]                     # 400 >= max(rows, cols) of every shape
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
-
-
 def _call(nat, d_power, F, stride, rows, cols, radius, k, floor_rel, floor_abs, per, values=True, counts=True):
     """bf_peaks_device into sentinel-filled buffers with a tail -> (offsets, values or None, counts or None) as host arrays; the tails
     are checked here."""
-    torch = _torch()
+    torch = util.torch_gpu()
     d_o = torch.full((F * k + TAIL,), SENTINEL_I, dtype=torch.int32, device="cuda")
     d_v = torch.full((F * k + TAIL,), SENTINEL_F, dtype=torch.float32, device="cuda") if values else None
     d_c = torch.full((F * 3 + TAIL,), SENTINEL_I, dtype=torch.int32, device="cuda") if counts else None
@@ -104,7 +93,7 @@ class CachedCandidates:
 @pytest.mark.parametrize("radius", RADII)
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
 def test_parity_with_restatement(nat, shape, radius):
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, cols = shape
     D = rows * cols
     rng = np.random.default_rng([rows, cols, radius])
@@ -146,7 +135,7 @@ def test_parity_with_restatement(nat, shape, radius):
 
 
 def test_radius_zero_is_a_plain_top_k(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, cols, k = 101, 101, 64
     D = rows * cols
     rng = np.random.default_rng(3)
@@ -162,7 +151,7 @@ def test_radius_zero_is_a_plain_top_k(nat):
 
 @pytest.mark.parametrize("shape,radius", [((57, 32), 4), ((101, 101), 4)], ids=["shipped", "cfg2"])
 def test_one_poisoned_frame_of_a_batch(nat, shape, radius):
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, cols = shape
     D, F, bad = rows * cols, 190, 97
     rng = np.random.default_rng([F, rows, cols])
@@ -186,7 +175,7 @@ def test_one_poisoned_frame_of_a_batch(nat, shape, radius):
 
 @pytest.mark.parametrize("shape", [(57, 32), (361, 361)], ids=["one_workgroup", "tiled"])
 def test_null_outputs_and_repeatability(nat, shape):
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, cols = shape
     D, F = rows * cols, 5
     rng = np.random.default_rng(17)
@@ -204,7 +193,7 @@ def test_null_outputs_and_repeatability(nat, shape):
 
 @pytest.mark.parametrize("shape", [(11, 11), (57, 32), (101, 101), (361, 361), (1, 300)], ids=lambda s: "%dx%d" % s)
 def test_one_source_whole_grid_is_the_argmax_call(nat, shape):
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, cols = shape
     D, F, per = rows * cols, 6, 64
     rng = np.random.default_rng([9, rows, cols])
@@ -222,7 +211,7 @@ def test_one_source_whole_grid_is_the_argmax_call(nat, shape):
 
 @pytest.mark.parametrize("shape", [(101, 101), (361, 361)], ids=["one_workgroup", "tiled"])
 def test_runs_in_a_captured_graph(nat, shape):
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, cols = shape
     D, F, k, radius, per = rows * cols, 4, 4, 4, 64
     rng = np.random.default_rng(23)
@@ -254,7 +243,7 @@ def test_runs_in_a_captured_graph(nat, shape):
 
 
 def test_sources_front_end(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     from interface import config
     util.configure("cfg1")
@@ -289,7 +278,7 @@ def two_source_frame():
 
 
 def test_two_sources_end_to_end(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     c = util.configure("shipped")
     M, N, X, Y, T = c["M"], c["N"], c["X"], c["Y"], c["T"]

@@ -7,22 +7,11 @@ import numpy as np
 import pytest
 
 import peaks_np
-
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
-
-
-def _peaks(nat, **kw):
-    a = dict(d_power=FAKE, frames=2, image_stride=60, rows=6, cols=10, radius=2, k=4, floor_rel=0.5, floor_abs=0.0, offset_per_dir=4,
-             d_offsets=FAKE, d_values=FAKE, d_counts=FAKE)
-    a.update(kw)
-    return nat.lib.bf_peaks_device(a["d_power"], a["frames"], a["image_stride"], a["rows"], a["cols"], a["radius"], a["k"], a["floor_rel"],
-                                   a["floor_abs"], a["offset_per_dir"], a["d_offsets"], a["d_values"], a["d_counts"], None)
+from support import entry, FAKE, refused
 
 
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
+_peaks = entry("bf_peaks_device", d_power=FAKE, frames=2, image_stride=60, rows=6, cols=10, radius=2, k=4, floor_rel=0.5, floor_abs=0.0,
+               offset_per_dir=4, d_offsets=FAKE, d_values=FAKE, d_counts=FAKE)
 
 
 def test_symbol_is_exported(native):
@@ -54,17 +43,17 @@ def test_symbol_is_exported(native):
 ])
 def test_peaks_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _peaks(native, **kw), match)
+    refused(native, _peaks(native, **kw), match)
 
 
 def test_valid_arguments_without_gpu(native):
     if native.gpu_available():
         pytest.skip("without a GPU only: with one, valid arguments would enqueue")
-    _refused(native, _peaks(native), "no usable HIP device")
+    refused(native, _peaks(native), "no usable HIP device")
     # the edges of every range pass the checks; the optional outputs may be null
-    _refused(native, _peaks(native, k=64, radius=0, floor_rel=0.0, floor_abs=-1e30, d_values=None, d_counts=None), "no usable HIP device")
-    _refused(native, _peaks(native, k=1, radius=2 ** 31 - 1, floor_rel=1.0, rows=1, cols=2, image_stride=2, offset_per_dir=2 ** 31 - 1), "no usable HIP device")
-    _refused(native, _peaks(native, rows=361, cols=361, image_stride=361 * 361), "no usable HIP device")
+    refused(native, _peaks(native, k=64, radius=0, floor_rel=0.0, floor_abs=-1e30, d_values=None, d_counts=None), "no usable HIP device")
+    refused(native, _peaks(native, k=1, radius=2 ** 31 - 1, floor_rel=1.0, rows=1, cols=2, image_stride=2, offset_per_dir=2 ** 31 - 1), "no usable HIP device")
+    refused(native, _peaks(native, rows=361, cols=361, image_stride=361 * 361), "no usable HIP device")
 
 
 def test_sources_without_gpu(native):

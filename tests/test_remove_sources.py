@@ -8,6 +8,7 @@ import pytest
 
 import separate_np as snp
 import util
+from support import nat
 from test_miso_device import Tables, _run as miso_run, _rows as miso_rows
 from test_remove_sources_host import MICS, exact_case
 
@@ -16,18 +17,6 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 16
 SENTINEL_BITS = 0x7fc0beef      # a NaN with a payload nobody computes
 ALGO_ID = {"pad": snp.PAD, "lerp": snp.LERP}
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 def _flat(torch, count, shift_floats):
@@ -39,7 +28,7 @@ def _flat(torch, count, shift_floats):
 
 def _remove(nat, algo, x, mics, offs, beams, gain, inplace=False, shift=0, status=True):
     """bf_remove_sources_device on device copies -> (residual [F, M, N] as numpy, status numpy or None).  Checks the sentinel tail."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, M, N = x.shape
     B, stride = beams.shape[1], beams.shape[2]
     src = _flat(torch, x.size, shift)
@@ -117,7 +106,7 @@ def test_null_status_and_unloaded_table(nat, oracle_lib):
     got, st = _remove(nat, "lerp", x, MICS, offs, beams, 1.0, status=False)
     assert st is None
     _same(got, snp.remove(snp.LERP, x, MICS, whole, h, offs, beams, 1.0)[0])
-    torch = _torch()
+    torch = util.torch_gpu()
     nat.lib.unload_coefficients_pad()
     nat.lib.bf_clear_error()
     d = torch.zeros((M_total * N,), dtype=torch.float32, device="cuda")
@@ -133,7 +122,7 @@ def test_null_status_and_unloaded_table(nat, oracle_lib):
 
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
 def test_cfg1_tables_and_listener(nat, oracle_lib, algo):
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     import synth
     c = util.configure("cfg1")
@@ -247,7 +236,7 @@ def test_64_beams_in_order(nat, oracle_lib, algo):
 # ------------------------------------------------------------------ 6. maps -> sources -> listen -> remove as one captured graph
 
 def test_graph_of_one_iteration(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     import synth
     c = util.configure("cfg1")
@@ -301,7 +290,7 @@ def test_graph_of_one_iteration(nat, oracle_lib):
 # ------------------------------------------------------------------ 7. end to end: the weak source under the strong one's response
 
 def test_separate_finds_the_weak_source(nat, oracle_lib):
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     from interface import config
     s = snp.SCENE

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 import separate_np as snp
+from support import FAKE, refused
 
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
 MICS = np.array([4, 0, 3, 1], dtype=np.int32)
 
 
@@ -25,12 +25,6 @@ def _remove(nat, **kw):
     stride = a["beam_stride"] if a["beam_stride"] is not None else cfg[1]
     return nat.lib.bf_remove_sources_device(a["algo"], a["d_signals"], a["m_total"], a["frames"], None if mics is None else nat.iptr(mics), n,
                                             a["d_offsets"], a["beams"], a["d_beams"], stride, a["gain"], a["d_residual"], a["d_status"], None)
-
-
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
 
 
 @pytest.fixture()
@@ -75,7 +69,7 @@ def test_symbol_and_prototype(native):
     (dict(gain=math.nan), "gain = -?nan is not finite"),
 ])
 def test_argument_errors(nat32, kw, match):
-    _refused(nat32, _remove(nat32, **kw), match)
+    refused(nat32, _remove(nat32, **kw), match)
 
 
 def test_valid_arguments_reach_the_device_checks(nat32):
@@ -84,9 +78,9 @@ def test_valid_arguments_reach_the_device_checks(nat32):
     nat32.lib.unload_coefficients_pad()
     nat32.lib.bf_clear_error()
     late = "no usable HIP device|has not been called"
-    _refused(nat32, _remove(nat32), late)
-    _refused(nat32, _remove(nat32, algo=0, beams=64, gain=0.0, d_status=None, beam_stride=32), late)
-    _refused(nat32, _remove(nat32, gain=-64.0, beams=1, frames=1, d_residual=FAKE, d_signals=FAKE, beam_stride=4096), late)
+    refused(nat32, _remove(nat32), late)
+    refused(nat32, _remove(nat32, algo=0, beams=64, gain=0.0, d_status=None, beam_stride=32), late)
+    refused(nat32, _remove(nat32, gain=-64.0, beams=1, frames=1, d_residual=FAKE, d_signals=FAKE, beam_stride=4096), late)
 
 
 def test_front_end_surface(native):

@@ -9,6 +9,7 @@ import pytest
 
 import resample_np as R
 import util
+from support import nat_restoring as nat
 
 pytestmark = pytest.mark.gpu
 
@@ -18,44 +19,12 @@ CANARY_I = 0x5A5A
 N = 64
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    yield native
-    util.configure("cfg1")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _wild(rng, shape):
-    return (rng.standard_normal(shape) * np.exp2(rng.integers(-12, 13, size=shape))).astype(np.float32)
-
-
-def _windows(rng, rows, n, hop, F, make=_wild):
+def _windows(rng, rows, n, hop, F, make=util.wild):
     """A stream cut into F windows of n every `hop` samples (0: back to back), and the window before the first."""
     step = hop if hop > 0 else n
     S = make(rng, (rows, step * F + n))
     frames = np.ascontiguousarray(np.stack([S[:, (f + 1) * step:(f + 1) * step + n] for f in range(F)]))
     return frames, np.ascontiguousarray(S[:, :n])
-
-
-def _place(a, off):
-    """A device copy of `a` that starts `off` 4-byte words past a 16-byte boundary (torch allocations are 256-byte aligned)."""
-    torch = _torch()
-    t = torch.from_numpy(np.ascontiguousarray(a).ravel())
-    buf = torch.zeros(t.numel() + 4, dtype=t.dtype, device="cuda")
-    view = buf[off:off + t.numel()]
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 * off
-    return view
 
 
 def _strided(x, stride):
@@ -67,7 +36,7 @@ def _strided(x, stride):
 
 def _convert(nat, x, h, L, M, state=(0, 0), hop=0, prev=None, gain=1.0, off=0, want_out=True, want_pcm=True, clip0=None, with_clip=True, expect_rc=0):
     """bf_resample_device on device copies -> what the restatement returns, plus the meter `clip`.  The canaries are checked."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, rows, n = x.shape
     T = h.shape[1]
     stride = n + 3
@@ -75,13 +44,13 @@ def _convert(nat, x, h, L, M, state=(0, 0), hop=0, prev=None, gain=1.0, off=0, w
     cap = R.capacity(S, L, M)
     assert nat.lib.bf_resample_capacity(S, L, M) == cap
     out_stride = cap + 5
-    d_x = _place(_strided(x, stride), off)
-    d_p = None if prev is None else _place(_strided(prev, stride), off)
-    d_h = _place(h, off)
-    d_state = _place(np.array([state[0], state[1], 77, -5], dtype=np.int32), off)        # the reserved words are written 0
-    d_count = _place(np.array([-9, -9], dtype=np.int32), off)
+    d_x = util.place_words(_strided(x, stride), off)
+    d_p = None if prev is None else util.place_words(_strided(prev, stride), off)
+    d_h = util.place_words(h, off)
+    d_state = util.place_words(np.array([state[0], state[1], 77, -5], dtype=np.int32), off)        # the reserved words are written 0
+    d_count = util.place_words(np.array([-9, -9], dtype=np.int32), off)
     clip0 = np.zeros(rows, np.int32) if clip0 is None else np.asarray(clip0, dtype=np.int32)
-    d_clip = _place(clip0, off)
+    d_clip = util.place_words(clip0, off)
     fbuf = torch.full((CANARY + 4 + rows * out_stride + CANARY,), CANARY_F, dtype=torch.float32, device="cuda")
     ibuf = torch.full((CANARY + 4 + cap * rows + CANARY,), CANARY_I, dtype=torch.int16, device="cuda")
     f_lo, i_lo = CANARY + off, CANARY + 2 * off
@@ -148,7 +117,7 @@ def test_the_cases_cover_the_shapes():
 def test_matches_the_definition(nat, L, M, T, hop, rows, frames):
     rng = np.random.default_rng([L, M, T, hop, rows, frames])
     x, prev = _windows(rng, rows, N, hop, frames)
-    h = _wild(rng, (L, T))
+    h = util.wild(rng, (L, T))
     state = (int(rng.integers(0, 3)), int(rng.integers(0, L)))
     if (L + hop) % 2:
         prev = None                                                      # silence before the stream
@@ -163,7 +132,7 @@ def test_every_pointer_one_float_off(nat, L, M, T, hop):
     """... a 16-byte boundary: the table's rows are then read with dword loads although T % 4 == 0, and the bits are the same."""
     rng = np.random.default_rng([L, M, T, hop, 1])
     x, prev = _windows(rng, 3, N, hop, 3)
-    h = _wild(rng, (L, T))
+    h = util.wild(rng, (L, T))
     state = (1, L // 3)
     got = _convert(nat, x, h, L, M, state, hop, prev, 0.001, off=1)
     want = R.resample(x, h, L, M, state, hop, prev, 0.001)
@@ -177,7 +146,7 @@ def _subnormal(rng, shape):
 
 
 def _hostile(rng, shape):
-    x = _wild(rng, shape)
+    x = util.wild(rng, shape)
     flat = x.reshape(-1)
     idx = rng.choice(flat.size, size=max(8, flat.size // 16), replace=False)
     flat[idx] = rng.choice(np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 3e38, -3e38, 1e-45], dtype=np.float32), size=idx.size)
@@ -188,8 +157,8 @@ def _hostile(rng, shape):
 @pytest.mark.parametrize("L,M,T,hop", [(7, 5, 8, 16), (3, 2, 5, 33)])
 def test_input_kinds(nat, kind, L, M, T, hop):
     rng = np.random.default_rng([L, M, T, hop, len(kind)])
-    x, prev = _windows(rng, 3, N, hop, 3, make=_subnormal if kind == "subnormal_samples" else _hostile if kind == "hostile" else _wild)
-    h = _subnormal(rng, (L, T)) if kind == "subnormal_taps" else _wild(rng, (L, T))
+    x, prev = _windows(rng, 3, N, hop, 3, make=_subnormal if kind == "subnormal_samples" else _hostile if kind == "hostile" else util.wild)
+    h = _subnormal(rng, (L, T)) if kind == "subnormal_taps" else util.wild(rng, (L, T))
     gain = 1.0 if kind != "hostile" else 0.01
     if kind == "subnormal_taps":
         x, prev = (x / np.float32(4096.0)).astype(np.float32), (prev / np.float32(4096.0)).astype(np.float32)
@@ -212,7 +181,7 @@ def test_split_calls_equal_one_call(nat, L, M, T, hop):
     rng = np.random.default_rng([L, M, T, hop, 2])
     F, F1, rows = 5, 2, 3
     x, prev = _windows(rng, rows, N, hop, F)
-    h = _wild(rng, (L, T))
+    h = util.wild(rng, (L, T))
     state = (1, L // 2)
     whole = _convert(nat, x, h, L, M, state, hop, prev, 0.01)
     a = _convert(nat, x[:F1], h, L, M, state, hop, prev, 0.01)
@@ -227,10 +196,10 @@ def test_sparse_outputs(nat):
     """down = 200: one output every 50 samples (up = 4; the call refuses down > 64 * up, so 200 / 1 is the restatement's alone, in
     tests/test_resample_host.py) from windows that add 16 samples each: calls that emit nothing still move the state."""
     rng = np.random.default_rng(200)
-    h = _wild(rng, (4, 8))
+    h = util.wild(rng, (4, 8))
     state, prev, seen = (0, 0), None, []
     for call in range(4):
-        x = _wild(rng, (1, 2, N))
+        x = util.wild(rng, (1, 2, N))
         got = _convert(nat, x, h, 4, 200, state, 16, prev, 1.0)
         _check(got, R.resample(x, h, 4, 200, state, 16, prev, 1.0))
         assert got["cap"] == 1
@@ -243,7 +212,7 @@ def test_sparse_outputs(nat):
 def test_corrupt_state(nat, state):
     rng = np.random.default_rng(9)
     x, prev = _windows(rng, 3, N, 16, 3)
-    h = _wild(rng, (3, 5))
+    h = util.wild(rng, (3, 5))
     clip0 = np.array([4, 0, 9], np.int32)
     got = _convert(nat, x, h, 3, 2, state, 16, prev, 1e6, clip0=clip0)       # a gain that would clip, were anything converted
     assert (got["count"], got["status"]) == (0, 1) and got["words"] == [state[0], state[1], 77, -5]
@@ -280,7 +249,7 @@ def test_pcm_rounding_clipping_and_the_meter(nat):
 def test_either_output_alone(nat):
     rng = np.random.default_rng(12)
     x, prev = _windows(rng, 3, N, 33, 3)
-    h = _wild(rng, (7, 8))
+    h = util.wild(rng, (7, 8))
     want = R.resample(x, h, 7, 5, (2, 3), 33, prev, 0.01)
     assert want["clipped"].sum() > 0
     _check(_convert(nat, x, h, 7, 5, (2, 3), 33, prev, 0.01, want_pcm=False), want, want_pcm=False)      # the meter counts PCM samples: untouched
@@ -295,15 +264,11 @@ def test_either_output_alone(nat):
 
 # ------------------------------------------------------------------ audio_out.AudioOut: a captured push, and the chain end to end
 
-def _sizes(n):
-    from interface import config
-    config.configure(N_MICROPHONES=4, N_SAMPLES=n, MAX_RES_X=2, MAX_RES_Y=1, N_TAPS=8)
-
 
 def test_graph_replay_advances_the_state(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import audio_out
-    _sizes(N)
+    util.configure_small(N)
     rng = np.random.default_rng(48)
     hop, F, B = 33, 2, 3
     step = hop * F
@@ -339,7 +304,7 @@ def test_graph_replay_advances_the_state(nat):
         state, prev, clipped = want["state"], batches[c][-1], clipped + want["clipped"]
     assert ao.state.cpu().numpy().tolist() == [state[0], state[1], 0, 0]
     assert np.array_equal(ao.clip.cpu().numpy(), clipped) and clipped.sum() >= 1
-    assert np.array_equal(_bits(ao._prev.cpu().numpy()), _bits(batches[3][-1]))
+    assert np.array_equal(util.bits(ao._prev.cpu().numpy()), util.bits(batches[3][-1]))
     ao.reset()
     assert not ao.state.cpu().numpy().any() and not ao.clip.cpu().numpy().any() and not ao._prev.cpu().numpy().any() and ao._prev.data_ptr() == carried
     audio, pcm, count = ao.push(x)                                       # a new stream: silence before it
@@ -348,7 +313,7 @@ def test_graph_replay_advances_the_state(nat):
 
 
 def test_push_flat_and_float_only(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import audio_out
     rng = np.random.default_rng(44)
     ao = audio_out.AudioOut(44100, taps=16, pcm=False, gain=0.5)
@@ -371,7 +336,7 @@ def test_push_flat_and_float_only(nat):
 def test_stream_beams_to_a_sound_card(nat):
     """StreamBeamformer.listen -> AudioOut.push on a 1 kHz plane wave, two batches: the converted beams are the restatement applied to
     the joined beams sb.audio(out), byte for byte."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import audio_out
     import stream
     c = util.configure("cfg1")

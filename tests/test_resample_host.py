@@ -10,24 +10,16 @@ import numpy as np
 import pytest
 
 import resample_np as R
+import util
+from support import FAKE, lib_clearing as lib
 
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
 RATIOS = [(2, 3, 4), (3, 2, 5), (7, 5, 8), (4000, 4069, 32)]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _wild(rng, shape):
-    """Floats whose magnitudes spread over 2^-12 .. 2^12: a chain summed in another order rounds differently."""
-    return (rng.standard_normal(shape) * np.exp2(rng.integers(-12, 13, size=shape))).astype(np.float32)
 
 
 def _windows(rng, rows, n, hop, F):
     """A stream cut into F windows of n every `hop` samples (0: back to back), and the window before the first."""
     step = hop if hop > 0 else n
-    S = _wild(rng, (rows, step * F + n))
+    S = util.wild(rng, (rows, step * F + n))
     frames = np.ascontiguousarray(np.stack([S[:, (f + 1) * step:(f + 1) * step + n] for f in range(F)]))
     return frames, np.ascontiguousarray(S[:, :n])
 
@@ -40,7 +32,7 @@ def test_split_calls_equal_one_call(hop, L, M, T):
     n, F, F1, rows = 64, 5, 2, 3
     rng = np.random.default_rng([hop, L, M, T])
     x, prev = _windows(rng, rows, n, hop, F)
-    h = _wild(rng, (L, T))
+    h = util.wild(rng, (L, T))
     state = (1, L // 2)                     # the first output reads the history, for every T > 1 here
     whole = R.resample(x, h, L, M, state, hop, prev, gain=0.5)
     a = R.resample(x[:F1], h, L, M, state, hop, prev, gain=0.5)
@@ -48,16 +40,16 @@ def test_split_calls_equal_one_call(hop, L, M, T):
     assert a["count"] + b["count"] == whole["count"] and b["state"] == whole["state"] and whole["status"] == a["status"] == b["status"] == 0
     assert whole["count"] > 0 and a["count"] <= a["cap"] and whole["count"] <= whole["cap"]
     joined = np.concatenate([a["y"][:, :a["count"]], b["y"][:, :b["count"]]], axis=1)
-    assert np.array_equal(_bits(joined), _bits(whole["y"][:, :whole["count"]]))
+    assert np.array_equal(util.bits(joined), util.bits(whole["y"][:, :whole["count"]]))
     joined = np.concatenate([a["pcm"][:a["count"]], b["pcm"][:b["count"]]], axis=0)
     assert joined.tobytes() == whole["pcm"][:whole["count"]].tobytes()
     assert np.array_equal(a["clipped"] + b["clipped"], whole["clipped"])
     assert not whole["y"][:, whole["count"]:].any() and not whole["pcm"][whole["count"]:].any()
     if T > 1:      # silence before the stream differs from the real history, and only where the history is read
         cold = R.resample(x, h, L, M, state, hop, None, gain=0.5)
-        assert not np.array_equal(_bits(cold["y"]), _bits(whole["y"]))
+        assert not np.array_equal(util.bits(cold["y"]), util.bits(whole["y"]))
         late = [k for k, (i, _) in enumerate(R.positions(state[0], state[1], F * (hop or n), L, M)) if i >= T - 1]
-        assert np.array_equal(_bits(cold["y"][:, late]), _bits(whole["y"][:, late]))
+        assert np.array_equal(util.bits(cold["y"][:, late]), util.bits(whole["y"][:, late]))
 
 
 def test_count_and_state_closed_form_against_the_loop():
@@ -90,17 +82,17 @@ def test_count_and_state_closed_form_against_the_loop():
 
 def test_identity_on_the_bits():
     rng = np.random.default_rng(3)
-    x = _wild(rng, (3, 2, 64))
+    x = util.wild(rng, (3, 2, 64))
     x[0, 0, :5] = [np.nan, np.inf, -np.inf, 1e-40, -1e-45]
     for hop in (0, 16, 64):
         got = R.resample(x, np.ones((1, 1), np.float32), 1, 1, (0, 0), hop)
         S = 3 * (hop or 64)
         assert got["count"] == got["cap"] == S and got["state"] == (0, 0)
         want = x[:, :, 64 - (hop or 64):].transpose(1, 0, 2).reshape(2, S)
-        assert np.array_equal(_bits(got["y"]), _bits(want))
+        assert np.array_equal(util.bits(got["y"]), util.bits(want))
     # the one exception: the chain starts at +0.0f, and fmaf(1, -0, +0) is +0
     zero = R.resample(np.full((1, 1, 4), -0.0, np.float32), np.ones((1, 1), np.float32), 1, 1)
-    assert np.array_equal(_bits(zero["y"]), np.zeros((1, 4), np.uint32))
+    assert np.array_equal(util.bits(zero["y"]), np.zeros((1, 4), np.uint32))
 
 
 def test_corrupt_state_is_reported():
@@ -126,7 +118,7 @@ def test_design_symmetry_and_dc_gain(native):
         h = audio_out.design_resampler(L, M, T)
         assert h.dtype == np.float32 and h.shape == (L, T)
         g = h.T.reshape(-1)                                              # g[t * up + p] = h[p][t]
-        assert np.array_equal(_bits(g), _bits(g[::-1]))                  # symmetric: linear phase, the delay is (Q - 1) / (2 up)
+        assert np.array_equal(util.bits(g), util.bits(g[::-1]))                  # symmetric: linear phase, the delay is (Q - 1) / (2 up)
         # A phase's DC gain is the prototype's response at 0 plus its images at the multiples of the input rate, which lie in the stop
         # band: the pass-band ripple and two images of 80 dB each bound the error by 3e-4 for any design; the audio designs (rate
         # changes near 1 at 32 taps, whose images sit far down the stop band) keep it within 1e-4
@@ -173,13 +165,6 @@ def test_tones_keep_their_frequency(native, rate_out):
 
 
 # ------------------------------------------------------------------ refusals before device bring-up
-
-@pytest.fixture(scope="module")
-def lib(native):
-    L = native.lib
-    L.bf_clear_error()
-    yield L
-    L.bf_clear_error()
 
 
 D_IN, D_TAPS, D_STATE, D_OUT, D_PCM, D_CLIP, D_COUNT = (FAKE + i * 0x100000 for i in range(7))

@@ -10,6 +10,7 @@ import pytest
 
 import spectrogram_np as S
 import util
+from support import nat_restoring as nat
 
 pytestmark = pytest.mark.gpu
 
@@ -20,39 +21,15 @@ FLOOR3, FLOOR6, FLOOR10 = (float(np.float32(v)) for v in (1e-3, 1e-6, 1e-10))   
 RATIOS = {}                 # kind of output -> the largest |error| / bound seen (printed by the last test)
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    yield native
-    util.configure("cfg1")
-
-
 def _wild(rng, rows, n, stretch):
     """[rows, n]: normal samples whose magnitude changes by a power of two in 2^-12 .. 2^12 every `stretch` samples."""
     e = rng.integers(-12, 13, size=(rows, n // max(stretch, 1) + 1))
     return (rng.standard_normal((rows, n)) * np.exp2(np.repeat(e, max(stretch, 1), axis=1)[:, :n])).astype(np.float32)
 
 
-def _place(a, off):
-    """A device copy of `a` that starts `off` 4-byte words past a 16-byte boundary (torch allocations are 256-byte aligned)."""
-    torch = _torch()
-    t = torch.from_numpy(np.ascontiguousarray(a).ravel())
-    buf = torch.zeros(t.numel() + 4, dtype=t.dtype, device="cuda")
-    view = buf[off:off + t.numel()]
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 * off
-    return view
-
-
 def _between_canaries(a, off, value):
     """(buffer, lo): a device buffer of canaries with `a` at [lo, lo + a.size), off words past a 16-byte boundary."""
-    torch = _torch()
+    torch = util.torch_gpu()
     a = np.ascontiguousarray(a).ravel()
     buf = torch.full((CANARY + 4 + a.size + CANARY,), value, dtype=torch.from_numpy(a).dtype, device="cuda")
     lo = CANARY + off
@@ -70,7 +47,7 @@ def _inner(buf, lo, size, value):
 
 def _run(nat, x, hist, s0, window, n_fft, hop, bank=None, support=None, scale=0.0, floor=1e-10, d_len=None, off=0, expect_rc=0):
     """bf_spectrogram_device on device copies -> dict(out, count, status, s0, words, hist, cap).  The canaries are checked."""
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, length = x.shape
     n_win = window.shape[0]
     H = n_win - 1
@@ -82,11 +59,11 @@ def _run(nat, x, hist, s0, window, n_fft, hop, bank=None, support=None, scale=0.
     L = length if d_len is None else min(max(d_len, 0), length)
     xs = np.full((rows, stride), np.nan, dtype=np.float32)
     xs[:, :L] = x[:, :L]                                                 # NaN behind every row, and where no sample is
-    d_x = _place(xs, off)
-    d_w = _place(window, off)
-    d_b = None if bank is None else _place(bank, off)
-    d_s = None if support is None else _place(support.astype(np.int32), off)
-    d_l = None if d_len is None else _place(np.array([d_len], dtype=np.int32), off)
+    d_x = util.place_words(xs, off)
+    d_w = util.place_words(window, off)
+    d_b = None if bank is None else util.place_words(bank, off)
+    d_s = None if support is None else util.place_words(support.astype(np.int32), off)
+    d_l = None if d_len is None else util.place_words(np.array([d_len], dtype=np.int32), off)
     words0 = np.array([s0, 77, -5, 9], dtype=np.int32)                   # the reserved words are written 0
     obuf, o_lo = _between_canaries(np.full(rows * out_frames * n_bands, CANARY_F, np.float32), off, CANARY_F)
     hbuf, h_lo = _between_canaries(hist.astype(np.float32), off, CANARY_F)
@@ -328,19 +305,15 @@ def test_a_corrupt_state_is_reported_and_nothing_moves(nat):
 
 # ------------------------------------------------------------------ features.BeamFeatures: a captured chain, and a tone end to end
 
-def _sizes(n):
-    from interface import config
-    config.configure(N_MICROPHONES=4, N_SAMPLES=n, MAX_RES_X=2, MAX_RES_Y=1, N_TAPS=8)
-
 
 def test_graph_replay_of_audio_out_and_features(nat):
     """AudioOut.push then BeamFeatures.push on its device count, captured as the objects' first call and replayed three times over fresh
     beams, against three eager pushes on a second pair: bytes and counts.  The counts differ from push to push (4000 / 4069)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import audio_out
     import features
     N, hop, F, B = 64, 33, 2, 3
-    _sizes(N)
+    util.configure_small(N)
     rng = np.random.default_rng(58)
     step = hop * F
     stream = (rng.standard_normal((B, step * 4 + N)) * 0.3).astype(np.float32)
@@ -383,12 +356,12 @@ def test_graph_replay_of_audio_out_and_features(nat):
 def test_a_tone_peaks_in_its_mel_band(nat):
     """1 kHz at 48828 Hz through AudioOut(16000) and BeamFeatures' defaults with 80 mel bands -- the shape speech models take -- in two
     pushes: every complete frame peaks in the band whose triangle holds 1 kHz (bin 32 of 512 at 16 kHz)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import audio_out
     import features
     import pipeline
     N, hop, F = 256, 128, 40
-    _sizes(N)
+    util.configure_small(N)
     t = np.arange(hop * (F + 1), dtype=np.float64)
     tone = (0.5 * np.sin(2 * np.pi * 1000.0 * t / 48828.0)).astype(np.float32)
     frames = np.ascontiguousarray(np.stack([tone[f * hop:f * hop + N] for f in range(F)]))[:, None, :]          # [F, 1, N]

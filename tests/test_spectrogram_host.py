@@ -9,8 +9,7 @@ import numpy as np
 import pytest
 
 import spectrogram_np as S
-
-FAKE = 0x10000          # a non-null, 16-byte aligned "device pointer"
+from support import FAKE, lib_clearing as lib
 
 
 # ------------------------------------------------------------------ symbols
@@ -38,13 +37,6 @@ def test_capacity(native):
 
 
 # ------------------------------------------------------------------ refusals before device bring-up
-
-@pytest.fixture(scope="module")
-def lib(native):
-    L = native.lib
-    L.bf_clear_error()
-    yield L
-    L.bf_clear_error()
 
 
 D_IN, D_LEN, D_HIST, D_STATE, D_WINDOW, D_BANK, D_SUPPORT, D_OUT, D_COUNT = (FAKE + i * 0x100000 for i in range(9))

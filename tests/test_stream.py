@@ -16,30 +16,10 @@ import numpy as np
 import pytest
 
 import util
+from support import nat
 from test_miso_device import MIC_GAIN, SENTINEL, Tables
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _same(got, want):
-    assert got.shape == want.shape
-    assert np.array_equal(_bits(got), _bits(want)), np.argwhere(_bits(got) != _bits(want))[:8]
 
 
 # ------------------------------------------------------------------ the stream, its windows and the extended-window oracle
@@ -114,7 +94,7 @@ class Case:
 
 
 def _dev(a):
-    torch = _torch()
+    torch = util.torch_gpu()
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
@@ -124,7 +104,7 @@ def _ptr(t):
 
 def _beams(nat, case, frames, hop, prev, offsets, gain=0.0, status=True, expect_rc=0):
     """bf_miso_stream_device -> (out [F, B, N] host array, the 16-float tail behind it, status host array or None)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, M, N = frames.shape
     offsets = np.ascontiguousarray(offsets, dtype=np.int32)
     B = offsets.shape[1]
@@ -144,7 +124,7 @@ def _beams(nat, case, frames, hop, prev, offsets, gain=0.0, status=True, expect_
 
 def _maps(nat, case, frames, hop, prev, d0, d1, pad=3):
     """bf_das_stream_device on directions [d0, d1) with image_stride = d1 - d0 + pad -> (maps [F, d1 - d0], the untouched rest)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, M, N = frames.shape
     stride = d1 - d0 + pad
     d_sig, d_prev = _dev(frames), _dev(prev)
@@ -213,7 +193,7 @@ def test_beams_match_extended_window_oracle(nat, oracle_lib, name, algo, hop_kin
             if gain:
                 want = (want / np.float32(case.n)) * np.float32(gain)
                 assert want.dtype == np.float32
-            _same(got[f, b], want)
+            util.same_bits(got[f, b], want)
 
 
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
@@ -231,7 +211,7 @@ def test_long_windows(nat, oracle_lib, algo):
     assert (status == 0).all() and np.isnan(tail).all()
     for f in range(F):
         for b in range(dirs.shape[1]):
-            _same(got[f, b], case.want(st, f, offs[f, b]))
+            util.same_bits(got[f, b], case.want(st, f, offs[f, b]))
 
 
 # ------------------------------------------------------------------ 2. maps equal the k-ordered power of the oracle's beams
@@ -246,7 +226,7 @@ def test_maps_cfg1_grid(nat, oracle_lib, algo, with_prev):
     assert np.isnan(rest).all()
     want = np.array([[case.want_power(st, f, d) for d in range(D)] for f in range(F)], dtype=np.float32)
     assert np.isfinite(want).all() and (want > 0).all()
-    _same(got, want)
+    util.same_bits(got, want)
 
 
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
@@ -260,7 +240,7 @@ def test_maps_direction_shard_chunked(nat, oracle_lib, algo):
     got, rest = _maps(nat, case, st.frames(), hop, st.prev(), d0, d1)
     assert np.isnan(rest).all()
     want = np.array([[case.want_power(st, f, d) for d in range(d0, d1)] for f in range(F)], dtype=np.float32)
-    _same(got, want)
+    util.same_bits(got, want)
 
 
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
@@ -273,17 +253,17 @@ def test_maps_n_not_a_power_of_two(nat, oracle_lib, algo):
     st = Stream([23, len(algo)], case.M_total, N, hop, F, with_prev=True)
     got, _ = _maps(nat, case, st.frames(), hop, st.prev(), 0, D)
     want = np.array([[case.want_power(st, f, d) for d in range(D)] for f in range(F)], dtype=np.float32)
-    _same(got, want)
+    util.same_bits(got, want)
     # and a shard of it
     got, _ = _maps(nat, case, st.frames(), hop, st.prev(), 17, 60)
-    _same(got, want[:, 17:60])
+    util.same_bits(got, want[:, 17:60])
 
 
 # ------------------------------------------------------------------ 3. batch-split invariance (StreamBeamformer)
 
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
 def test_batch_split_invariance(nat, oracle_lib, algo):
-    torch = _torch()
+    torch = util.torch_gpu()
     import stream
     case = Case(nat, oracle_lib, algo, name="cfg1")
     N, D, F, hop = case.N, case.D, 7, case.N // 2
@@ -313,17 +293,17 @@ def test_batch_split_invariance(nat, oracle_lib, algo):
     assert whole_b.shape == (F, 3, N) and whole_m.shape == (F, D)
     for splits in ([1] * F, [3, 1, 2, 1], [1, 4, 2]):
         b, m = run(splits)
-        _same(b, whole_b)
-        _same(m, whole_m)
+        util.same_bits(b, whole_b)
+        util.same_bits(m, whole_m)
     # the split results are the oracle's, not merely each other's
-    _same(whole_b[4, 1], case.want(st, 4, offs[1]))
-    _same(whole_m[5, 7], np.float32(case.want_power(st, 5, 7)))
+    util.same_bits(whole_b[4, 1], case.want(st, 4, offs[1]))
+    util.same_bits(whole_m[5, 7], np.float32(case.want_power(st, 5, 7)))
     # reset(): the next batch starts from silence again
     sb = stream.StreamBeamformer(algo, hop=hop, mics=case.mics)
     sb.advance(d_frames[:2])
     sb.reset()
     out, _ = sb.listen(d_frames[:1], offs)
-    _same(out.cpu().numpy()[0], whole_b[0])
+    util.same_bits(out.cpu().numpy()[0], whole_b[0])
 
 
 # ------------------------------------------------------------------ 4. anchor to the pinned path
@@ -331,7 +311,7 @@ def test_batch_split_invariance(nat, oracle_lib, algo):
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
 def test_anchor_to_bf_miso_device(nat, oracle_lib, algo):
     """From sample H on, a stream beam IS bf_miso_device's beam of the same window; for pad from silence, frame 0 is it entirely."""
-    torch = _torch()
+    torch = util.torch_gpu()
     case = Case(nat, oracle_lib, algo, name="shipped")
     N, D, F, hop, H = case.N, case.D, 6, case.N // 2, case.H
     assert 0 < H < hop
@@ -349,10 +329,10 @@ def test_anchor_to_bf_miso_device(nat, oracle_lib, algo):
     torch.cuda.synchronize()
     assert nat.lib.bf_last_das_variant() == before
     plain = plain.cpu().numpy()
-    _same(got[:, :, H:], plain[:, :, H:])
-    assert not np.array_equal(_bits(got[1:, :, :H]), _bits(plain[1:, :, :H]))       # the head of a later window differs: that is the feature
+    util.same_bits(got[:, :, H:], plain[:, :, H:])
+    assert not np.array_equal(util.bits(got[1:, :, :H]), util.bits(plain[1:, :, :H]))       # the head of a later window differs: that is the feature
     if algo == "pad":
-        _same(got[0], plain[0])
+        util.same_bits(got[0], plain[0])
 
 
 def test_beam_call_leaves_last_variant_alone(nat, oracle_lib):
@@ -360,7 +340,7 @@ def test_beam_call_leaves_last_variant_alone(nat, oracle_lib):
     st = Stream([42], case.M_total, case.N, case.N, 2, with_prev=False)
     _maps(nat, case, st.frames(), case.N, None, 0, 5)
     assert nat.lib.bf_last_das_variant() == 9
-    torch = _torch()
+    torch = util.torch_gpu()
     d_sig = _dev(st.frames())
     img = torch.empty((2, case.D), dtype=torch.float32, device="cuda")
     assert nat.lib.bf_das_device(util.ALGOS["pad"], d_sig.data_ptr(), case.M_total, img.data_ptr(), case.D, 2, nat.iptr(case.mics), case.n, 0, case.D,
@@ -391,16 +371,16 @@ def test_invalid_offsets_are_nan_with_status(nat, oracle_lib, algo):
             if s:
                 assert np.isnan(got[f, b]).all()
             else:
-                _same(got[f, b], case.want(st, f, offs[f, b]))
+                util.same_bits(got[f, b], case.want(st, f, offs[f, b]))
     # without a status array the beams are the same
     again, _, none = _beams(nat, case, st.frames(), hop, st.prev(), offs, status=False)
     assert none is None
-    _same(again, got)
+    util.same_bits(again, got)
 
 
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
 def test_history_longer_than_hop_is_refused(nat, oracle_lib, algo):
-    torch = _torch()
+    torch = util.torch_gpu()
     case = Case(nat, oracle_lib, algo, name="shipped")
     H = case.H
     assert H > 1
@@ -430,7 +410,7 @@ def test_clamped_and_unloaded_tables_are_refused(nat, oracle_lib):
     x = _dev(np.zeros((1, M, N), dtype=np.float32))
     offs = _dev(np.zeros((1, 1), dtype=np.int32))
     out = _dev(np.zeros((1, 1, N), dtype=np.float32))
-    s = _torch().cuda.current_stream().cuda_stream
+    s = util.torch_gpu().cuda.current_stream().cuda_stream
     rc = nat.lib.bf_miso_stream_device(util.ALGOS["pad"], x.data_ptr(), M, 1, N, None, nat.iptr(mics), M, offs.data_ptr(), 1, 0.0, out.data_ptr(), N, None, s)
     assert rc == -1
     with pytest.raises(nat.BeamformerError, match="1 entries of the loaded table lie beyond N_SAMPLES = 64"):
@@ -473,4 +453,4 @@ def test_audio_of_two_batches_is_the_beam_of_the_stream(nat, oracle_lib, algo, h
     case.tab.orc = orc
     for b, off in enumerate(offs):
         want = case.tab.want(ext, case.mics, int(off))[P:]
-        _same(audio[b], want[N - hop:])
+        util.same_bits(audio[b], want[N - hop:])

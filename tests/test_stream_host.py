@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 import util
+from support import FAKE, nat_cfg1 as nat, refused
 
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
 N = 256
 
 
@@ -34,19 +34,6 @@ def _das(nat, **kw):
     mics = a["adaptive_array"]
     return nat.lib.bf_das_stream_device(a["algo"], a["d_signals"], a["m_total"], a["d_images"], a["image_stride"], a["frames"], a["hop"], a["d_prev"],
                                         None if mics is None else nat.iptr(mics), a["n"], a["dir_begin"], a["dir_end"], None)
-
-
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
-
-
-@pytest.fixture()
-def nat(native):
-    util.configure("cfg1")                 # 64 x 256, 11 x 11 directions
-    native.lib.bf_clear_error()
-    return native
 
 
 def test_new_symbols_exist(native):
@@ -82,7 +69,7 @@ COMMON = [
     (dict(mic_gain=math.nan), "mic_gain = -?nan is not finite"),
 ])
 def test_miso_stream_argument_errors(nat, kw, match):
-    _refused(nat, _miso(nat, **kw), "bf_miso_stream_device: " + match)
+    refused(nat, _miso(nat, **kw), "bf_miso_stream_device: " + match)
 
 
 @pytest.mark.parametrize("kw,match", COMMON + [
@@ -93,7 +80,7 @@ def test_miso_stream_argument_errors(nat, kw, match):
     (dict(image_stride=120), "image_stride 120 < 121 directions"),
 ])
 def test_das_stream_argument_errors(nat, kw, match):
-    _refused(nat, _das(nat, **kw), "bf_das_stream_device: " + match)
+    refused(nat, _das(nat, **kw), "bf_das_stream_device: " + match)
 
 
 def test_history_of_nothing_loaded(nat):
@@ -103,17 +90,17 @@ def test_history_of_nothing_loaded(nat):
         assert nat.lib.bf_stream_history(algo) == -1
     nat.check()                            # a query, not a failure: no error recorded
     one = np.zeros(1, dtype=np.int32)
-    _refused(nat, nat.lib.bf_get_pad_table(nat.iptr(one), 1), "bf_get_pad_table: 1 requested, 0 loaded")
-    _refused(nat, nat.lib.bf_get_pad_table(None, 1), "bf_get_pad_table: whole is null")
+    refused(nat, nat.lib.bf_get_pad_table(nat.iptr(one), 1), "bf_get_pad_table: 1 requested, 0 loaded")
+    refused(nat, nat.lib.bf_get_pad_table(None, 1), "bf_get_pad_table: whole is null")
 
 
 def test_valid_arguments_without_gpu(nat):
     if nat.gpu_available():
         pytest.skip("without a GPU only")
-    _refused(nat, _miso(nat), "no usable HIP device")
-    _refused(nat, _miso(nat, algo=nat.LERP, hop=1, d_prev=FAKE, d_status=None, mic_gain=128.0), "no usable HIP device")
-    _refused(nat, _das(nat), "no usable HIP device")
-    _refused(nat, _das(nat, algo=nat.PAD, hop=N // 2, d_prev=None, dir_begin=100, dir_end=121, image_stride=21), "no usable HIP device")
+    refused(nat, _miso(nat), "no usable HIP device")
+    refused(nat, _miso(nat, algo=nat.LERP, hop=1, d_prev=FAKE, d_status=None, mic_gain=128.0), "no usable HIP device")
+    refused(nat, _das(nat), "no usable HIP device")
+    refused(nat, _das(nat, algo=nat.PAD, hop=N // 2, d_prev=None, dir_begin=100, dir_end=121, image_stride=21), "no usable HIP device")
 
 
 def test_stream_beamformer_arguments(nat):

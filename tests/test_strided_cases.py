@@ -20,6 +20,7 @@ import pytest
 
 import strided_cases as sc
 import util
+from support import nat
 from test_das_select import CANARY, CANARY_BITS, _call
 from test_miso_device import MIC_GAIN, Tables
 
@@ -27,18 +28,6 @@ pytestmark = pytest.mark.gpu
 
 NAN_BITS = 0x7FC00000
 RAN = {}            # row name -> the instantiation bf_last_strided_plan reported
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
 
 
 def _rows(kernel):
@@ -72,7 +61,7 @@ def _ran(nat, row, want_plan):
 
 
 def _canaried(words):
-    torch = _torch()
+    torch = util.torch_gpu()
     return torch.full((CANARY + words + CANARY,), CANARY_BITS, dtype=torch.int32, device="cuda")
 
 
@@ -86,12 +75,12 @@ def _payload(buf, rows, stride, used):
 
 
 def _dev(a):
-    return None if a is None else _torch().from_numpy(np.ascontiguousarray(a)).cuda()
+    return None if a is None else util.torch_gpu().from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _map_call(nat, row, mics, frames, hop, prev, gap=3):
     """bf_das_stream_device on directions [d0, d0 + count) into rows of count + gap floats -> float32 [F, count]."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, stride = frames.shape[0], row.count + gap
     d_sig, d_prev = _dev(frames), _dev(prev)
     buf = _canaried(F * stride)
@@ -106,7 +95,7 @@ def _map_call(nat, row, mics, frames, hop, prev, gap=3):
 
 def _beam_call(nat, row, mics, frames, hop, prev, offsets, gain, gap=5):
     """bf_miso_stream_device with out_stride = N + gap -> (float32 [F, B, N], status int32 [F, B])."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, B, stride = frames.shape[0], offsets.shape[1], row.N + gap
     d_sig, d_prev, d_off = _dev(frames), _dev(prev), _dev(np.ascontiguousarray(offsets, dtype=np.int32))
     buf, st = _canaried(F * B * stride), _canaried(F * B)

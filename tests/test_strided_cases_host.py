@@ -13,12 +13,8 @@ import pytest
 
 import strided_cases as sc
 import util
+from support import lib
 from util import ALGOS
-
-
-@pytest.fixture(scope="module")
-def lib(native):
-    return native.lib
 
 
 # ------------------------------------------------------------------ the rows against the exports

@@ -12,24 +12,14 @@ import pytest
 
 import sweep_order_np as SO
 from util import ALGOS, REL_TOL, max_rel
+import util
+from support import nat
 
 pytestmark = pytest.mark.gpu
 
 M_TOTAL, EVERY, T = 64, 4, 8
 MICS = (np.arange(M_TOTAL // EVERY) * EVERY).astype(np.int32)
 GRIDS = {"9x45": (9, 45), "13x21": (13, 21)}
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 def _tables(algo, X, Y):
@@ -78,7 +68,7 @@ def _want(oracle_lib, algo, table, N, X, Y, key):
 
 
 def _das(nat, algo, d_sig, F, lo, hi):
-    torch = _torch()
+    torch = util.torch_gpu()
     out = torch.full((F, hi - lo), float("nan"), dtype=torch.float32, device="cuda")
     assert nat.lib.bf_das_device(ALGOS[algo], d_sig.data_ptr(), M_TOTAL, out.data_ptr(), hi - lo, F, nat.iptr(MICS), MICS.size, lo, hi,
                                  torch.cuda.current_stream().cuda_stream) == 0, nat.check()
@@ -110,7 +100,7 @@ def _check_count(nat, whole, lo, hi):
 @pytest.mark.parametrize("grid", sorted(GRIDS))
 @pytest.mark.parametrize("algo", ["pad", "lerp"])
 def test_ordered_sweep_is_bit_identical(nat, oracle_lib, algo, grid, N, F):
-    torch = _torch()
+    torch = util.torch_gpu()
     X, Y = GRIDS[grid]
     D = X * Y
     table, whole = _tables(algo, X, Y)
@@ -141,7 +131,7 @@ def test_ordered_sweep_is_bit_identical(nat, oracle_lib, algo, grid, N, F):
 def test_second_geometry_rebuilds_the_order(nat, oracle_lib, algo):
     """Two tables of one size (405 directions as 9x45, then as 15x27) loaded one after the other: same launch geometry, so the same
     digest key -- the second load must rebuild the order with the digest (the serpentine of rows of 45 would scatter the 15x27 maps)."""
-    torch = _torch()
+    torch = util.torch_gpu()
     N, F = 256, 2
     d_sig = torch.from_numpy(_frames(N)[:F].copy()).cuda()
     for X, Y in ((9, 45), (15, 27)):
@@ -159,7 +149,7 @@ def test_second_geometry_rebuilds_the_order(nat, oracle_lib, algo):
 def test_random_table_still_takes_the_direction_outer_variant(nat, oracle_lib, algo):
     """Independent random delays: the rule returns the identity, more than half of the steps re-read, the digest build picks the
     direction-outer variant (3) as before -- images against the oracle under the bound that variant has always been held to."""
-    torch = _torch()
+    torch = util.torch_gpu()
     X, Y, N, F = 24, 23, 256, 2
     rng = np.random.default_rng(77)
     delays = rng.uniform(0, 40.0, size=(X * Y, MICS.size))

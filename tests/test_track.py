@@ -7,6 +7,7 @@ import pytest
 
 import track_np
 import util
+from support import nat
 
 pytestmark = pytest.mark.gpu
 
@@ -14,22 +15,10 @@ SENTINEL_I, SENTINEL_F, TAIL = -77, -123.5, 16
 NAMES = ("offsets", "ids", "pos", "match", "counts", "state")
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
-def nat(native):
-    assert native.gpu_available(), "these tests need the MI355X"
-    return native
-
-
 def _call(nat, offs, rows, cols, per, slots, gate=3.0, max_miss=5, min_hits=3, q=0.1, r=0.1, state=None, optional=True):
     """bf_track_sources_device into sentinel-filled buffers with a tail -> (offsets, ids, pos, match, counts, state) as host arrays
     (None for the optional outputs when optional is False); the tails, the state's included, are checked here."""
-    torch = _torch()
+    torch = util.torch_gpu()
     F, k = offs.shape
     words = track_np.state_words(slots)
     d_in = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.int32)).cuda()
@@ -56,16 +45,6 @@ def _call(nat, offs, rows, cols, per, slots, gate=3.0, max_miss=5, min_hits=3, q
     assert (h[words:] == SENTINEL_I).all()
     out.append(h[:words])
     return out
-
-
-def _same(got, want, what):
-    for name, g, w in zip(NAMES, got, want):
-        if g is None:
-            continue
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
-        bad = np.argwhere(g.view(np.int32) != w.view(np.int32))
-        assert bad.size == 0, (what, name, len(bad), bad[:4].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
-        assert g.tobytes() == w.tobytes()
 
 
 # ------------------------------------------------------------------ 1. parity with the restatement, one case per branch
@@ -125,7 +104,7 @@ def test_parity_with_restatement(nat, case):
     want = track_np.track(offs, rows, cols, per, slots, **kw)
     counts = want[4].sum(axis=0)
     print(case, "born/ended/dropped/ignored", counts.tolist(), "matches", int((want[3] >= 0).sum()), "next_id", int(want[5][0]))
-    _same(got, want, case)
+    util.same_named(NAMES, got, want, case)
     # each case reaches what it is there for
     if case == "dense_ties":
         assert counts[1] > 0 and counts[2] > 0 and (want[3] >= 0).sum(axis=1).max() > 32
@@ -168,13 +147,13 @@ def test_null_outputs_and_repeatability(nat):
 # ------------------------------------------------------------------ 4. graph capture from the first call
 
 def test_runs_in_a_captured_graph(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     rows, cols, per, slots = 41, 23, 3, 4
     offs = track_np.scripted_scene(40, 4, rows, cols, per)
     F, k = offs.shape
     want = track_np.track(offs, rows, cols, per, slots)
     eager = _call(nat, offs, rows, cols, per, slots)        # (its own buffers; also brings the library's device up outside the capture)
-    _same(eager, want, "eager")
+    util.same_named(NAMES, eager, want, "eager")
     # a shape no call has had before: this launch is captured without a warm-up of its own
     slots2 = 5
     want2 = track_np.track(offs, rows, cols, per, slots2)
@@ -195,13 +174,13 @@ def test_runs_in_a_captured_graph(nat):
         d_p.fill_(SENTINEL_F)
         g.replay()
         torch.cuda.synchronize()
-        _same([t.cpu().numpy() for t in (d_o, d_i, d_p, d_m, d_c, d_state)], want2, "graph replay")
+        util.same_named(NAMES, [t.cpu().numpy() for t in (d_o, d_i, d_p, d_m, d_c, d_state)], want2, "graph replay")
 
 
 # ------------------------------------------------------------------ 5. the front end: sources -> SourceTracker
 
 def test_tracker_front_end(nat):
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     import track
     util.configure("cfg1")
@@ -230,7 +209,7 @@ def test_tracker_front_end(nat):
     assert (got[1][:, 0] == 1).all() and (got[1][:, 1] == 2).all() and (got[1][:, 2:] == 0).all()
     assert (got[3][:12, 0] == 0).all() and (got[3][12:, 0] == 1).all()
     want = track_np.track(src_h, rows, cols, per, 4, min_hits=2)
-    _same(got, want, "front end")
+    util.same_named(NAMES, got, want, "front end")
     # a second batch continues the tracks; reset forgets them
     offsets2, ids2, _, _, counts2 = tr.update(src[-3:])
     torch.cuda.synchronize()
@@ -252,7 +231,7 @@ def test_tracker_front_end(nat):
 def test_tracked_beams_follow_one_source(nat):
     """Two plane waves at the as-shipped size, the second one scaled per frame so that the louder of the two alternates: `sources`
     swaps them from frame to frame, the tracker's slots do not, and each slot's beam is bf_miso_device's at that source's offset."""
-    torch = _torch()
+    torch = util.torch_gpu()
     import listen
     import synth
     import track

@@ -7,23 +7,11 @@ import numpy as np
 import pytest
 
 import track_np
-
-FAKE = 0x10000          # a non-null "device pointer": every call below is refused before anything could dereference it
-
-
-def _track(nat, **kw):
-    a = dict(d_offsets=FAKE, frames=2, k=4, rows=41, cols=23, offset_per_dir=4, slots=4, gate=3.0, max_miss=5, min_hits=3, q=0.1, r=0.1,
-             d_state=FAKE, d_track_offsets=FAKE, d_track_ids=FAKE, d_track_pos=FAKE, d_match=FAKE, d_counts=FAKE)
-    a.update(kw)
-    return nat.lib.bf_track_sources_device(a["d_offsets"], a["frames"], a["k"], a["rows"], a["cols"], a["offset_per_dir"], a["slots"], a["gate"],
-                                           a["max_miss"], a["min_hits"], a["q"], a["r"], a["d_state"], a["d_track_offsets"], a["d_track_ids"],
-                                           a["d_track_pos"], a["d_match"], a["d_counts"], None)
+from support import entry, FAKE, refused
 
 
-def _refused(nat, rc, match):
-    assert rc == -1
-    with pytest.raises(nat.BeamformerError, match=match):
-        nat.check()
+_track = entry("bf_track_sources_device", d_offsets=FAKE, frames=2, k=4, rows=41, cols=23, offset_per_dir=4, slots=4, gate=3.0, max_miss=5,
+               min_hits=3, q=0.1, r=0.1, d_state=FAKE, d_track_offsets=FAKE, d_track_ids=FAKE, d_track_pos=FAKE, d_match=FAKE, d_counts=FAKE)
 
 
 def test_symbols_are_exported(native):
@@ -70,18 +58,18 @@ def test_state_words(native):
 ])
 def test_track_argument_errors(native, kw, match):
     native.lib.bf_clear_error()
-    _refused(native, _track(native, **kw), match)
+    refused(native, _track(native, **kw), match)
 
 
 def test_valid_arguments_without_gpu(native):
     if native.gpu_available():
         pytest.skip("without a GPU only: with one, valid arguments would enqueue")
-    _refused(native, _track(native), "no usable HIP device")
+    refused(native, _track(native), "no usable HIP device")
     # the edges of every range pass the checks; the optional outputs may be null
-    _refused(native, _track(native, slots=64, k=64, gate=0.0, max_miss=0, min_hits=1, q=0.0), "no usable HIP device")
-    _refused(native, _track(native, d_track_ids=None, d_track_pos=None, d_match=None, d_counts=None), "no usable HIP device")
-    _refused(native, _track(native, slots=1, k=1, rows=1, cols=2, offset_per_dir=2 ** 31 - 1, r=1e-30, gate=1e30), "no usable HIP device")
-    _refused(native, _track(native, rows=361, cols=361, offset_per_dir=256 * 8), "no usable HIP device")
+    refused(native, _track(native, slots=64, k=64, gate=0.0, max_miss=0, min_hits=1, q=0.0), "no usable HIP device")
+    refused(native, _track(native, d_track_ids=None, d_track_pos=None, d_match=None, d_counts=None), "no usable HIP device")
+    refused(native, _track(native, slots=1, k=1, rows=1, cols=2, offset_per_dir=2 ** 31 - 1, r=1e-30, gate=1e30), "no usable HIP device")
+    refused(native, _track(native, rows=361, cols=361, offset_per_dir=256 * 8), "no usable HIP device")
 
 
 def test_tracker_without_gpu(native):

@@ -84,6 +84,97 @@ def bits_differ(got, want, nan_is_nan=False):
         d, g[d], float(got[d]), w[d], float(want[d]), int(bad.sum()), bad.size, int(np.abs(line(g[bad]) - line(w[bad])).max()))
 
 
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def same_bits(got, want):
+    assert got.shape == want.shape, (got.shape, want.shape)
+    diff = bits_differ(got, want)
+    assert not diff, diff
+
+
+def same_named(names, got, want, what):
+    """Tuples of 4-byte arrays, one per name, equal in dtype, shape and every bit; an entry of `got` that is None is not compared."""
+    for name, g, w in zip(names, got, want):
+        if g is None:
+            continue
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
+        bad = np.argwhere(g.view(np.int32) != w.view(np.int32))
+        assert bad.size == 0, (what, name, len(bad), bad[:4].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
+        assert g.tobytes() == w.tobytes()
+
+
+def wild(rng, shape):
+    """Floats whose magnitudes spread over 2^-12 .. 2^12: a chain summed in another order rounds differently."""
+    return (rng.standard_normal(shape) * np.exp2(rng.integers(-12, 13, size=shape))).astype(np.float32)
+
+
+def stream_windows(rng, R, N, hop, F):
+    """A stream cut into F windows of N every `hop` samples, and the window that began `hop` samples before the first."""
+    step = hop if hop > 0 else N
+    S = wild(rng, (R, step * F + N))
+    frames = np.ascontiguousarray(np.stack([S[:, (f + 1) * step:(f + 1) * step + N] for f in range(F)]))
+    return frames, np.ascontiguousarray(S[:, :N])
+
+
+def torch_gpu():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def place(a, off):
+    """A device copy of `a` that starts `off` floats past a 16-byte boundary (torch allocations are 256-byte aligned)."""
+    torch = torch_gpu()
+    buf = torch.zeros(a.size + 4, dtype=torch.float32, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    view = buf[off:off + a.size]
+    view.copy_(torch.from_numpy(np.ascontiguousarray(a).ravel()))
+    return buf, view
+
+
+def place_words(a, off):
+    """A device copy of `a`, in its own 4-byte dtype, that starts `off` words past a 16-byte boundary; the view keeps its buffer alive."""
+    torch = torch_gpu()
+    t = torch.from_numpy(np.ascontiguousarray(a).ravel())
+    buf = torch.zeros(t.numel() + 4, dtype=t.dtype, device="cuda")
+    view = buf[off:off + t.numel()]
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 4 * off
+    return view
+
+
+CANARY = 64                 # elements in front of and behind every device output
+CANARY_VALUE = -1234.5      # floats; the int outputs carry int(CANARY_VALUE) = -1234
+
+
+def canaried(shape, dtype):
+    """A device buffer of canaries and the view of `shape` elements in its middle that a kernel is to write."""
+    torch = torch_gpu()
+    total = int(np.prod(shape))
+    buf = torch.full((CANARY + total + CANARY,), CANARY_VALUE if dtype.is_floating_point else int(CANARY_VALUE), dtype=dtype, device="cuda")
+    return buf, buf[CANARY:CANARY + total]
+
+
+def intact(buf, total):
+    """Whether the canaries on both sides of canaried()'s view of `total` elements survived."""
+    host = buf.cpu().numpy()
+    want = host.dtype.type(CANARY_VALUE)
+    return bool((host[:CANARY] == want).all() and (host[CANARY + total:] == want).all())
+
+
+def audio_power(listener, out):
+    import mvdr_np
+    return mvdr_np.power(listener.audio(out).cpu().numpy()[0])
+
+
+def configure_small(N):
+    """The smallest sizes the row-wise kernels' tests need: 4 microphones, 2 x 1 directions, 8 taps and N samples."""
+    from interface import config
+    config.configure(N_MICROPHONES=4, N_SAMPLES=N, MAX_RES_X=2, MAX_RES_Y=1, N_TAPS=8)
+
+
 def configure(name, **extra):
     """Switch the product package (interface.config + native library) to a size of oracle/configs.py."""
     from interface import config
