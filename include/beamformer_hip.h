@@ -1179,8 +1179,13 @@ int bf_yolo_decode_device(const void *const raw[3], const int h[3], const int w[
                           int format, float conf_thres, float *d_boxes, float *d_scores, int *d_cls, void *stream);
 /*   bf_topk_candidates_device: the k (<= 1024) best-scoring boxes of every image in descending score order (ties: lower box index
  *       first) -- d_top_scores [batch][k], d_top_boxes [batch][k][4], d_top_cls [batch][k], d_counts [batch] = entries with a
- *       positive score (decode marks rejected boxes with -1).  One workgroup per image: radix select, ordered tie admission,
- *       bitonic sort in LDS.  This is the candidate list bf_nms_device walks. */
+ *       positive score (decode marks rejected boxes with -1).  The order in full: scores compare as floats, so +0.0 and -0.0 tie
+ *       (lower index first); a NaN of either sign and any payload ranks below every number, -inf included, and among NaNs the
+ *       lower index comes first.  The first min(k, total) slots are copies of the selected entries bit for bit (a -0.0 or a NaN
+ *       payload comes out as it went in); slots past min(k, total) hold score -1, a zero box and class 0.  d_boxes and d_top_boxes
+ *       are read and written as 16-byte vectors and must be 16-byte aligned (not checked).
+ *       One workgroup per image: radix select, ordered tie admission, bitonic sort in LDS.  This is the candidate list
+ *       bf_nms_device walks. */
 int bf_topk_candidates_device(const float *d_scores, const float *d_boxes, const int *d_cls, int batch, int total, int k, float *d_top_scores,
                               float *d_top_boxes, int *d_top_cls, int *d_counts, void *stream);
 /*   bf_upsample_concat_device: the head's torch.cat((nn.Upsample(2, "nearest")(a), b), 1) in one pass -- a float16 NHWC [batch][h/2][w/2][ca],

@@ -631,10 +631,64 @@ def test_gpu_preprocess_kernel_matches_torch(native, half):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("half", [True, False])
-@pytest.mark.parametrize("B,C,H,W", [(2, 256, 20, 20), (1, 64, 12, 20), (3, 8, 5, 3), (1, 64, 40, 40), (2, 24, 9, 7)])
+@pytest.mark.parametrize("B,H,W,cpad", [(3, 64, 96, 3), (3, 64, 96, 8), (2, 37, 53, 3), (1, 4097, 4096, 4)])
+def test_gpu_preprocess_kernel_channel_pads_and_second_grid_trip(native, half, B, H, W, cpad):
+    """bf_preprocess_bgr8(_f32)_device called directly: cpad 3 and 8 take the scalar stores (cpad 4 the one vector store), and
+    4097 x 4096 pixels are 4096 more than the 65536 workgroups of 256 cover at once, so the grid-stride loop takes its second trip
+    (as it does on the shipped 64 frames of 640 x 640).  Against frames.flip(-1) / 255 in the output's type; channels 3.. zero;
+    nothing written outside the output."""
+    import torch
+    from lib import _native as nat
+    g = torch.Generator(device="cuda").manual_seed(B * H + cpad)
+    frames = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device="cuda", generator=g)
+    dt = torch.float16 if half else torch.float32
+    buf, x = util.canaried((B, H, W, cpad), dt)
+    assert x.data_ptr() % 16 == 0 and (B * H * W > 65536 * 256) == (H == 4097)
+    fn = nat.lib.bf_preprocess_bgr8_device if half else nat.lib.bf_preprocess_bgr8_f32_device
+    assert fn(frames.data_ptr(), x.data_ptr(), B, H, W, cpad, torch.cuda.current_stream().cuda_stream) == 0, nat.check()
+    torch.cuda.synchronize()
+    x = x.view(B, H, W, cpad)
+    want = frames.flip(-1)
+    want = (want.half() if half else want.float()) / 255
+    assert torch.equal(x[..., :3], want)
+    assert cpad == 3 or bool((x[..., 3:] == 0).all())
+    edge = torch.cat((buf[:util.CANARY], buf[-util.CANARY:]))
+    assert torch.equal(edge, torch.full_like(edge, util.CANARY_VALUE))          # (the same rounding of the canary value in float16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("half", [True, False])
+def test_gpu_sppf_pool_kernel_carries_infinities(native, half):
+    """+inf and -inf through the three cascaded pools as nn.MaxPool2d carries them: a +inf spreads by two pixels a level, and a corner
+    block of -inf (10 x 10 of a 12 x 12 plane, clipped windows) shrinks by two a level and is still there after the third.  (NaN
+    stays out: the kernel's a > b ? a : b does not propagate it uniformly and the header promises nothing.)"""
+    import torch
+    from lib import _native as nat
+    g = torch.Generator(device="cpu").manual_seed(41)
+    dt = torch.float16 if half else torch.float32
+    B, C, H, W = 2, 16, 12, 12
+    x = torch.randn((B, C, H, W), generator=g)
+    x[:, ::2, :10, :10] = float("-inf")
+    x[0, 1, 11, 11] = float("inf"); x[1, 0, 3, 4] = float("inf"); x[1, 3, 0, 7] = float("-inf")
+    x = x.cuda().to(dt)
+    buf = torch.zeros((B, 4 * C, H, W), dtype=dt, device="cuda").contiguous(memory_format=torch.channels_last)
+    buf[:, :C] = x
+    fn = nat.lib.bf_sppf_pool_device if half else nat.lib.bf_sppf_pool_f32_device
+    assert fn(buf.data_ptr(), B, H, W, C, torch.cuda.current_stream().cuda_stream) == 0, nat.check()
+    m = torch.nn.MaxPool2d(5, 1, 2)
+    y1 = m(x); y2 = m(y1); y3 = m(y2)
+    assert bool((y3[0, 0, :4, :4] == float("-inf")).all()) and bool((y3[1, 0] == float("inf")).any()) and bool(torch.isfinite(y3[0, 0, 5:, 5:]).all())
+    assert torch.equal(buf, torch.cat((x, y1, y2, y3), 1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("half", [True, False])
+@pytest.mark.parametrize("B,C,H,W", [(2, 256, 20, 20), (1, 64, 12, 20), (3, 8, 5, 3), (1, 64, 40, 40), (2, 24, 9, 7), (2, 32, 1, 1), (1, 32, 1, 2048), (1, 32, 2048, 1)])
 def test_gpu_sppf_pool_kernel_matches_torch(native, B, C, H, W, half):
     """bf_sppf_pool(_f32)_device against nn.MaxPool2d(5, 1, 2) applied once, twice, three times: exact; the first quarter untouched.
-    (The shapes walk the kernel's chunks-per-workgroup choice: 4, 2 and 1 by channel count, 1 by the LDS bound at 40 x 40.)"""
+    (The shapes walk the kernel's chunks-per-workgroup choice: 4, 2 and 1 by channel count, 1 by the LDS bound at 40 x 40; 1 x 1 is the
+    smallest plane, 1 x 2048 and 2048 x 1 are the entry point's pixel limit with every window clipped on both sides of one axis: 64 KiB of
+    LDS, one chunk per workgroup though 32 channels would allow four.)"""
     import torch
     from lib import _native as nat
     g = torch.Generator(device="cpu").manual_seed(C + H)

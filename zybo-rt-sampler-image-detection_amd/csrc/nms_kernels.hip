@@ -121,7 +121,8 @@ __global__ void __launch_bounds__(64) nms_scan_kernel(const float* __restrict__ 
 __device__ __forceinline__ unsigned score_key(float x)
 {
     unsigned u = __float_as_uint(x);
-    if (x != x) return 0u;                                       // NaN: below everything
+    if (x != x) return 0u;                                       // NaN: below everything, -inf (key 0x007FFFFF) included
+    if (u == 0x80000000u) u = 0u;                                // -0.0 == +0.0: one key for both (as peak_code in heatmap_kernels.hip), so the lower index wins
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // monotone: a > b  <=>  key(a) > key(b)
 }
 
@@ -189,8 +190,8 @@ __global__ void __launch_bounds__(1024) topk_select_kernel(const float* __restri
         __syncthreads();
     }
     __syncthreads();
-    // bitonic sort, descending, of the 1024 pairs (empty slots are 0 = below every real pair: a real pair's low word is >= 1 only
-    // if its index is < 2^32 - 1, and its high word is >= 1 unless the score is NaN or -inf... both sort last together with the padding)
+    // bitonic sort, descending, of the 1024 pairs (empty slots are 0 = below every real pair: a real pair's low word is >= 1, its
+    // index being < 2^31, so even a NaN's pair -- high word 0 -- lies above the padding, and NaNs come out in index order)
     for (unsigned k2 = 2; k2 <= 1024; k2 <<= 1) {
         for (unsigned j = k2 >> 1; j > 0; j >>= 1) {
             const unsigned partner = tid ^ j;
