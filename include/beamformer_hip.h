@@ -768,6 +768,52 @@ int bf_last_strided_plan(long long out[12]);
 int bf_band_filter_device(const float *d_signals, int rows, int frames, int hop, const float *d_prev,
                           const float *d_taps, int n_taps, int bands, float *d_out, void *stream);
 
+/* ---- phase-transform (SRP-PHAT) frames: every in-band DFT bin of every row weighted by |X_k|^-beta, K bands in one launch ----
+ * A power map weighs a frequency by how loud it is, so a loud narrow-band interferer owns it.  The phase transform gives every in-band
+ * bin of every microphone unit magnitude and keeps its phase: each frequency votes once, by its inter-microphone delays.  The weighting
+ * is per row and zero-phase, so it leaves every delay intact: a PHAT map is bf_das_device on whitened frames, and peaks, listed
+ * directions and tracking work on it unchanged.  Whitened audio is noise-like: listen on the RAW frames at the offsets the map gave.
+ * The windows are whitened independently of each other: there is no hop and no carried state.
+ * d_signals : HIP device pointer, float32 [frames][rows][N_SAMPLES] (N = N_SAMPLES, a power of two in [32, 4096]; bf_configure
+ *             itself stops at N_SAMPLES = 1024 today, so 2048 and 4096 cannot be reached and are not tested).
+ * d_window  : HIP DEVICE pointer, float32 [N] (features.hann makes one), or NULL: a rectangular window.  With a rectangular window the
+ *             leakage of strong low tones carries their phase into every bin; Hann is the sensible default.
+ * bins      : HOST pointer, int32 [bands][2] = [lo_b, hi_b), clipped to [0, N / 2 + 1].
+ * beta, gain: HOST pointers, float32 [bands].  bins, beta and gain are copied into the launch's arguments: a captured graph keeps them.
+ * d_out     : HIP device pointer, float32 [bands][frames][rows][N].  Every element is written.
+ * Definition (builder-defined; the reference has no such weighting).  For every row x of N samples:
+ *     u[t] = d_window[t] * x[t]                       one float32 multiply; u = x without a window
+ *     X_k  = sum_t u[t] exp(-2 pi i k t / N)          k = 0 .. N / 2
+ *   and for band b, lo <= k < hi after clipping:
+ *     rms_b   = sqrt(mean over lo <= k < hi of |X_k|^2)
+ *     floor_b = max(floor_abs, floor_rel * rms_b)
+ *     d_k     = max(|X_k|, floor_b)
+ *     W_k     = X_k                  beta == 0        (no floor is formed)
+ *     W_k     = X_k / d_k            beta == 1        (IEEE division of both components)
+ *     W_k     = d_k^-beta X_k        otherwise
+ *     W_k     = 0                    where d_k == 0 (beta > 0), and outside the band
+ *     out[b][f][r][j] = gain_b / N * (Re W_0 + (-1)^j Re W_{N/2} + 2 Re sum over 0 < k < N / 2 of W_k exp(+2 pi i j k / N))
+ *   Both transforms are radix-2 decimation-in-time FFTs in float32 with twiddles rounded once from double; their rounding is not part of
+ *   the definition (tests/whiten_np.py derives the tolerance: norm-wise, eta = 5 sqrt 2 per pass), these promises are:
+ *   - a row's N outputs depend only on that row's N samples, the window and that band's scalars -- not on rows, on frames, on the row's
+ *     position, on the other rows, on the other bands of the call or on the alignment of any pointer: band b of a K-band call equals
+ *     the single-band call, bit for bit;
+ *   - a row of zeros gives N outputs equal to 0 for every beta (ingest zeroes the dead microphones' rows; they stay silent);
+ *   - with floor_abs == 0, multiplying a row by 2^e leaves a beta == 1 output bit for bit unchanged and multiplies a beta == 0 output
+ *     by 2^e exactly, while nothing overflows or goes subnormal: the map does not depend on a microphone's gain;
+ *   - a non-finite sample affects only its own (frame, row).
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: one launch (a workgroup per (frame, row), walking when there are more than
+ *             2048; one wave up to N = 512, four above; 4.5 N + 8 floats of LDS); no allocation, no workspace, no atomics, no
+ *             synchronisation; graph-capturable from the first call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_signals, bins, beta, gain or d_out null; rows, frames or
+ * bands < 1; bands > BF_WHITEN_MAX_BANDS; N_SAMPLES not a power of two in [32, 4096]; a band with lo >= hi after clipping; a beta not
+ * finite or outside [0, 1]; a gain not finite; floor_rel or floor_abs negative or not finite; d_out's byte range sharing a byte with
+ * d_signals or d_window; no GPU.  All arguments are checked before device bring-up. */
+#define BF_WHITEN_MAX_BANDS 16
+int bf_whiten_device(const float *d_signals, int rows, int frames, const float *d_window,
+                     const int *bins, const float *beta, const float *gain, int bands,
+                     float floor_rel, float floor_abs, float *d_out, void *stream);
+
 /* ---- filter-and-sum beams: one FIR per (beam, microphone), then a sum over the microphones ----
  * Every beam of bf_miso_device / bf_miso_stream_device is delay-and-sum: one whole-sample or lerp delay per microphone from the loaded
  * table, which has no gain control over any direction but its own.  Any FIXED beamformer -- null steering (LCMV), superdirective, MVDR

@@ -1915,6 +1915,54 @@ int bf_spectrogram_device(const float* d_in, int rows, int in_stride, int len, c
                                          floor_, d_out, out_frames, d_count, as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- phase-transform (PHAT) frames: every in-band bin weighted by |X_k|^-beta
+
+int bf_whiten_device(const float* d_signals, int rows, int frames, const float* d_window, const int* bins, const float* beta, const float* gain, int bands,
+                     float floor_rel, float floor_abs, float* d_out, void* stream)
+{
+    static const char* who = "bf_whiten_device";
+    static_assert(BF_WHITEN_MAX_BANDS == bf::kWhitenMaxBands, "the header's limit is the kernel's");
+    Entered in;
+    const int N = in.s.sz.n_samples;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {bins, "bins"}, {beta, "beta"}, {gain, "gain"}, {d_out, "d_out"}})) return -1;
+    if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "bands", bands, 1)) return -1;
+    if (!need_max(who, "bands", bands, BF_WHITEN_MAX_BANDS)) return -1;
+    if (N < bf::kWhitenMinN || N > bf::kWhitenMaxN || (N & (N - 1)) != 0) {
+        set_error("%s: N_SAMPLES = %d is not a power of two in [%d, %d]", who, N, bf::kWhitenMinN, bf::kWhitenMaxN);
+        return -1;
+    }
+    const int n_bins = N / 2 + 1;
+    bf::WhitenBands wb = {};
+    for (int b = 0; b < bands; ++b) {
+        wb.lo[b] = std::min(std::max(bins[2 * b], 0), n_bins);
+        wb.hi[b] = std::min(std::max(bins[2 * b + 1], 0), n_bins);
+        if (wb.lo[b] >= wb.hi[b]) {
+            set_error("%s: band %d: bins [%d, %d) hold no bin of [0, N_SAMPLES / 2 + 1 = %d)", who, b, bins[2 * b], bins[2 * b + 1], n_bins);
+            return -1;
+        }
+    }
+    char name[32];
+    for (int b = 0; b < bands; ++b) {
+        snprintf(name, sizeof(name), "beta[%d]", b);
+        if (!need_finite(who, name, beta[b], FINITE_GE0)) return -1;
+        if (beta[b] > 1.0f) { set_error("%s: %s = %g > 1", who, name, (double)beta[b]); return -1; }
+        wb.beta[b] = beta[b];
+    }
+    for (int b = 0; b < bands; ++b) {
+        snprintf(name, sizeof(name), "gain[%d]", b);
+        if (!need_finite(who, name, gain[b])) return -1;
+        wb.gain[b] = gain[b];
+    }
+    if (!need_finite(who, "floor_rel", floor_rel, FINITE_GE0) || !need_finite(who, "floor_abs", floor_abs, FINITE_GE0)) return -1;
+    const u64 in_bytes = sat_mul(sat_mul(sat_mul((u64)frames, (u64)rows), (u64)N), sizeof(float));
+    if (!need_disjoint(who, {{d_out, sat_mul(in_bytes, (u64)bands), "d_out"},
+                             {d_signals, in_bytes, "d_signals"},
+                             {d_window, (u64)N * sizeof(float), "d_window"}}, 1))
+        return -1;
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_whiten(d_signals, (long long)frames * rows, N, d_window, wb, bands, floor_rel, floor_abs, d_out, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- ingest (receiver.c:94-151)
 
 static int ingest_common(const void* d_packets, int n_arrays, int rows, int columns, float* d_frame, hipStream_t stream)

@@ -282,6 +282,21 @@ hipError_t launch_spectrogram(const float* d_in, int rows, int in_stride, int le
                               int n_win, int n_fft, int hop, const float* d_bank, const int32_t* d_support, int n_bands, float scale, float floor_,
                               float* d_out, int out_frames, int32_t* d_count, hipStream_t stream);
 
+// bf_whiten_device (whiten.hip): every row of d_signals float32 [items][n_samples] (items = frames * rows; n_samples a power of two in
+// [kWhitenMinN, kWhitenMaxN]) windowed by d_window float32 [n_samples] (null: rectangular), transformed, and per band b the bins
+// [lo[b], hi[b]) (already clipped to [0, n_samples / 2 + 1], lo < hi) weighted by max(|X_k|, floor)^-beta[b] and transformed back ->
+// d_out float32 [n_bands][items][n_samples], scaled by gain[b] / n_samples.  The bands travel in the launch's arguments.  One launch;
+// no workspace, no table: the twiddles are computed.
+constexpr int kWhitenMinN = 32;
+constexpr int kWhitenMaxN = 4096;
+constexpr int kWhitenMaxBands = 16;
+struct WhitenBands {
+    int lo[kWhitenMaxBands], hi[kWhitenMaxBands];
+    float beta[kWhitenMaxBands], gain[kWhitenMaxBands];
+};
+hipError_t launch_whiten(const float* d_signals, long long items, int n_samples, const float* d_window, const WhitenBands& bands, int n_bands, float floor_rel,
+                         float floor_abs, float* d_out, hipStream_t stream);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);

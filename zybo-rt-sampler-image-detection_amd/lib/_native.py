@@ -131,6 +131,7 @@ _sig("bf_smooth_state_words", C.c_int, C.c_int)
 _sig("bf_smooth_boxes_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("bf_band_filter_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
+_sig("bf_whiten_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, IP, FP, FP, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p)
 _sig("bf_filter_sum_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, IP, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
      C.c_void_p)
 _sig("bf_filter_sum_waves", C.c_int, C.c_int)

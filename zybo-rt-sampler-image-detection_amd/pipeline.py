@@ -86,3 +86,8 @@ class FusedPipeline:
         beams as spectral frames at the model's rate, log-mel or band levels, continuous across batches and without a host round
         trip (feat, count)."""
         return bfeat.push_from(ao, out)
+
+    def whiten(self, frames, whitener):
+        """A frame batch [F, R, N_SAMPLES] -> whitener.frames (a whiten.Whitener): [K, F, R, N_SAMPLES], every in-band bin of every row
+        at unit magnitude (the phase transform), for maps and peaks; listen on the raw frames at the offsets those maps give."""
+        return whitener.frames(frames)
