@@ -1113,6 +1113,95 @@ int bf_spectrogram_device(const float *d_in, int rows, int in_stride, int len, c
                           float scale, float floor_,
                           float *d_out, int out_frames, int *d_count, void *stream);
 
+/* ---- noise suppression of beam audio: STFT analysis, a gain per (frame, bin), overlap-add synthesis, on the device ----
+ * A beam carries the noise that arrives from its look direction and the sensors' own (a 64-microphone delay-and-sum beam has a white-
+ * noise gain of about -24.7 dB, the adaptive designs less, and nothing below a few kHz is attenuated spatially on a 14 cm aperture).
+ * This call is the single-channel spectral post-filter behind the beamformer: frames of the stream are transformed, every bin is
+ * multiplied by a gain in [g_min, 1] -- a decision-directed Wiener rule over a recursively tracked noise spectrum, or gains the caller
+ * supplies (a model's mask, say) -- and the frames are transformed back and overlap-added into an audio stream again, continuous
+ * across windows and calls with all state on the device.  The configured sizes (bf_configure) and the loaded tables play no part.
+ * d_in      : HIP device pointer, float32 [frames][rows][in_stride], in_stride >= n: as bf_resample_device reads it.  A flat stream is
+ *             frames = 1, hop = 0, n = its length.
+ * d_hist    : HIP device pointer, float32 [rows][n_fft - 1], read and written: the samples before x[0].
+ * d_ola     : HIP device pointer, float32 [rows][n_fft], read and written: the partial sums of y for the n_fft positions before x[0].
+ * d_noise   : HIP device pointer, float32 [rows][n_fft / 2 + 1], read and written: lam, the tracked noise power of every bin.
+ * d_prior   : HIP device pointer, float32 [rows][n_fft / 2 + 1], read and written: G^2 P of the bin's last frame.
+ * d_state   : HIP device pointer, int32 [4], read and written.  The caller zeroes d_hist, d_ola, d_noise, d_prior and d_state at the
+ *             start of a stream.  d_noise and d_prior may be NULL where d_gain_in is given.
+ * d_win_a, d_win_s : HIP DEVICE pointers, float32 [n_fft]: the analysis and the synthesis window (enhance.design_cola makes a pair
+ *             whose products overlap-add to 1).
+ * d_gain_in : HIP DEVICE pointer, float32 [rows][cap][n_fft / 2 + 1], or NULL: the caller's gains, frame i of the call in slot i.
+ * d_work    : HIP device pointer, bf_enhance_workspace(rows, S, n_fft, hop_s) floats, written; its contents carry nothing.
+ * Definition (builder-defined; the reference has no post-filter).  Let len = hop > 0 ? hop : n, S = frames * len, H = n_fft - 1,
+ * B = n_fft / 2 + 1, cap = (hop_s - 1 + S) / hop_s.
+ *   Stream.  x[s] = d_in[s / len][r][n - len + s % len]     for 0 <= s < S        (bf_resample_device's stream)
+ *            x[s] = d_hist[r][H + s]                        for -H <= s < 0
+ *   State.  d_state[0] = c, 0 <= c < hop_s: the stream samples since the last frame end.  d_state[1] = seen >= 0: the frames the noise
+ *     tracker has seen, saturating at n_init.  d_state[2..3] are reserved and written 0.
+ *   Frames.  count = (c + S) / hop_s.  Frame i < count ends at e_i = (i + 1) * hop_s - c - 1 and covers x[e_i - H .. e_i]: the first
+ *     frames of a stream reach into the zeroed history, so every stream sample is covered by n_fft / hop_s frames; there is no fade-in.
+ *   Analysis, float32:  u[t] = d_win_a[t] * x[e_i - H + t], one multiply;  X_k = sum_t u[t] exp(-2 pi i k t / n_fft), k = 0 .. n_fft / 2;
+ *     P_k = re * re + im * im, two products and one add, each rounded.
+ *   Gains.  With d_gain_in: G = d_gain_in[r][i][k]; d_noise, d_prior and seen are neither read nor written.  Otherwise, per (row, bin)
+ *     over the call's frames in ascending order, with s = min(seen + i, n_init) for frame i (one counter for all bins), lam = d_noise,
+ *     prior = d_prior, every operation one float32 operation in the order written, divisions IEEE-rounded, fmaf with one rounding,
+ *     subnormals kept, max(a, b) = a < b ? b : a and min(a, b) = a > b ? b : a:
+ *       if P is not finite:  G = NaN; lam and prior stay as they are (the frame comes out non-finite)
+ *       else
+ *         if s < n_init:  lam = (s == 0) ? P : lam + (P - lam) / (float)(s + 1)          -- the stream's first frames are taken as noise
+ *         else:           g = P / max(lam, FLT_MIN);  p = min(max((g - g0) / (g1 - g0), 0), 1)
+ *                         a = a_noise + (1 - a_noise) * p;  lam = fmaf(1 - a, P - lam, lam)
+ *         den = max(lam, FLT_MIN);  gam = P / den
+ *         xi  = fmaf(alpha, min(prior / den, FLT_MAX), (1 - alpha) * max(gam - 1, 0))    -- the clamp keeps alpha = 0 times an
+ *                                                                                           overflowed ratio at 0
+ *         G   = max(1 - 1 / (1 + xi), g_min)                                              -- 1, not NaN, at xi = inf
+ *         prior = (G * G) * P
+ *     1 - alpha, 1 - a_noise and g1 - g0 are float32 differences.  No operation of the else branch yields a NaN from finite P, lam >= 0
+ *     and prior >= 0.  New state: seen' = min(seen + count, n_init); d_noise and d_prior hold lam and prior behind the last frame.
+ *   Synthesis.  Y_k = G * X_k (one multiply per component; the imaginary parts of Y_0 and Y_{n_fft/2} are taken as 0);
+ *     v[t] = (d_win_s[t] * (1.0f / n_fft)) * z[t] with z the unnormalised inverse real transform of Y.  The enhanced stream is
+ *       y[t] = the sum over the frames covering t of v_frame[t - start], added in ascending frame order starting from 0.0f,
+ *     and d_ola[r][j] carries that partial sum for position j - n_fft over the frames of earlier calls.
+ *   Both transforms are radix-2 decimation-in-time FFTs with twiddles rounded once from double; their rounding is not part of the
+ *     definition (tests/enhance_np.py derives the tolerance), these promises are: a frame's values depend only on its own n_fft
+ *     samples, the windows, its gains and the scalars -- not on rows, on the other rows, on the frame's index in the call, on the
+ *     alignment of any pointer, or on how the stream was cut into calls.  Two calls on F1 and F - F1 windows, the second with the
+ *     first's state, give d_out and all state of one call on F windows bit for bit.  A row of zeros gives zeros.  A non-finite sample
+ *     makes non-finite at most the outputs at the positions its covering frames span; d_noise and d_prior stay finite.
+ *   Output.  d_out float32 [rows][out_stride]: d_out[r][s] = y[s - n_fft] for 0 <= s < S: a call on S samples emits exactly S samples,
+ *     whatever c is; the stream is delayed by n_fft samples (a position is emitted once every frame that covers it has ended), and the
+ *     first n_fft samples of a stream hold the zeros of d_ola plus what the first frames, which reach into the zeroed history, put in
+ *     front of the stream: rounding at G = 1, the spread of the gains otherwise.  Elements past S are left untouched.
+ *   Observables.  d_power_out and d_gain_out, float32 [rows][cap][B], either may be NULL: P and G of the frames i < count, 0.0f in the
+ *     slots count <= i < cap.
+ *   New state.  c' = (c + S) % hop_s; d_hist' = the last H samples of d_hist || x[0 .. S); d_ola'[j] = the partial sum of position
+ *     S - n_fft + j.
+ *   d_count int32 [2] = (count, status).  A state with c outside [0, hop_s) or seen < 0 gives status = 1, count = 0, zeros in
+ *     d_out[r][0 .. S) and in the observables; d_hist, d_ola, d_noise, d_prior and d_state are left as they were.  Otherwise status = 0.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: four launches -- analysis (a workgroup per frame; one wave up to n_fft =
+ *             512, four above), the gain recursion (a thread per (row, bin), which reads and then writes its own d_noise / d_prior
+ *             element), synthesis into d_work, and the overlap-add, which alone writes d_hist, d_ola, d_state and d_count; no
+ *             allocation, no synchronisation, no atomics on floats; graph-capturable from the first call, and a replay advances the
+ *             stream like any other call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: d_in, d_hist, d_ola, d_state, d_win_a, d_win_s, d_work, d_out
+ * or d_count null; d_noise or d_prior null without d_gain_in; rows, frames or n < 1; hop < 0; hop > n; in_stride < n; n_fft not a power
+ * of two in [32, 4096]; hop_s < 1, not a divisor of n_fft, or n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP; S > INT_MAX / 2; out_stride < S;
+ * without d_gain_in: alpha or a_noise not finite or outside [0, 1), g0 not finite or < 0, g1 not finite or <= g0, g_min not finite or
+ * outside [0, 1], n_init < 1; a written range (d_out, d_work, d_power_out, d_gain_out, d_hist, d_ola, d_noise, d_prior, d_state, d_count;
+ * each from its first element to the last one touched) sharing a byte with a read range (d_in, d_win_a, d_win_s, d_gain_in) or with
+ * another written one; no GPU.  All arguments are checked before device bring-up.
+ * bf_enhance_workspace: the floats of d_work for a call on `samples` stream samples per row, 4 + rows * cap * (4 * B + n_fft); -1 for
+ * rows < 1, samples < 1 or > INT_MAX / 2, or n_fft / hop_s outside the rules above.  No GPU needed. */
+#define BF_ENHANCE_MAX_OVERLAP 8
+long long bf_enhance_workspace(int rows, long long samples, int n_fft, int hop_s);
+int bf_enhance_device(const float *d_in, int rows, int frames, int n, int in_stride, int hop,
+                      float *d_hist, float *d_ola, float *d_noise, float *d_prior, int *d_state,
+                      const float *d_win_a, const float *d_win_s, int n_fft, int hop_s,
+                      const float *d_gain_in,
+                      float alpha, float a_noise, float g0, float g1, float g_min, int n_init,
+                      float *d_work, float *d_out, int out_stride,
+                      float *d_power_out, float *d_gain_out, int *d_count, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

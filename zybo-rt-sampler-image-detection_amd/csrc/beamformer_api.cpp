@@ -1915,6 +1915,74 @@ int bf_spectrogram_device(const float* d_in, int rows, int in_stride, int len, c
                                          floor_, d_out, out_frames, d_count, as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- noise suppression of beam audio: STFT analysis, gains, overlap-add synthesis
+
+long long bf_enhance_workspace(int rows, long long samples, int n_fft, int hop_s) { return bf::enhance_workspace(rows, samples, n_fft, hop_s); }
+
+int bf_enhance_device(const float* d_in, int rows, int frames, int n, int in_stride, int hop, float* d_hist, float* d_ola, float* d_noise, float* d_prior,
+                      int* d_state, const float* d_win_a, const float* d_win_s, int n_fft, int hop_s, const float* d_gain_in, float alpha, float a_noise, float g0,
+                      float g1, float g_min, int n_init, float* d_work, float* d_out, int out_stride, float* d_power_out, float* d_gain_out, int* d_count,
+                      void* stream)
+{
+    static const char* who = "bf_enhance_device";
+    static_assert(BF_ENHANCE_MAX_OVERLAP == bf::kEnhanceMaxOverlap, "the header's limit is the kernel's");
+    constexpr int kMaxStream = std::numeric_limits<int>::max() / 2;
+    Entered in;
+    if (!need_ptrs(who, {{d_in, "d_in"}, {d_hist, "d_hist"}, {d_ola, "d_ola"}, {d_state, "d_state"}, {d_win_a, "d_win_a"}, {d_win_s, "d_win_s"},
+                         {d_work, "d_work"}, {d_out, "d_out"}, {d_count, "d_count"}}))
+        return -1;
+    const bool tracks = d_gain_in == nullptr;
+    if (tracks && !need_ptrs(who, {{d_noise, "d_noise"}, {d_prior, "d_prior"}})) return -1;
+    if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "n", n, 1)) return -1;
+    if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, n, "n") || !need_min(who, "in_stride", in_stride, "n", n)) return -1;
+    if (n_fft < bf::kEnhanceMinFft || n_fft > bf::kEnhanceMaxFft || (n_fft & (n_fft - 1)) != 0) {
+        set_error("%s: n_fft = %d is not a power of two in [%d, %d]", who, n_fft, bf::kEnhanceMinFft, bf::kEnhanceMaxFft);
+        return -1;
+    }
+    if (!need_min(who, "hop_s", hop_s, 1)) return -1;
+    if (hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP) {
+        set_error("%s: hop_s = %d does not divide n_fft = %d into 1 .. %d frames a sample", who, hop_s, n_fft, BF_ENHANCE_MAX_OVERLAP);
+        return -1;
+    }
+    const int len = hop > 0 ? hop : n;
+    const long long S = (long long)frames * len;
+    if (S > kMaxStream) { set_error("%s: frames * %s = %lld > %d", who, hop > 0 ? "hop" : "n", S, kMaxStream); return -1; }
+    if (!need_min(who, "out_stride", out_stride, "S", (int)S)) return -1;
+    if (tracks) {
+        if (!need_finite(who, "alpha", alpha, FINITE_GE0) || !need_finite(who, "a_noise", a_noise, FINITE_GE0) || !need_finite(who, "g0", g0, FINITE_GE0) ||
+            !need_finite(who, "g1", g1) || !need_finite(who, "g_min", g_min, FINITE_GE0))
+            return -1;
+        if (alpha >= 1.0f) { set_error("%s: alpha = %g >= 1", who, (double)alpha); return -1; }
+        if (a_noise >= 1.0f) { set_error("%s: a_noise = %g >= 1", who, (double)a_noise); return -1; }
+        if (g1 <= g0) { set_error("%s: g1 = %g <= g0 = %g", who, (double)g1, (double)g0); return -1; }
+        if (g_min > 1.0f) { set_error("%s: g_min = %g > 1", who, (double)g_min); return -1; }
+        if (!need_min(who, "n_init", n_init, 1)) return -1;
+    }
+    const long long work = bf::enhance_workspace(rows, S, n_fft, hop_s);
+    if (work < 0) { set_error("%s: no workspace for rows = %d, S = %lld, n_fft = %d, hop_s = %d", who, rows, S, n_fft, hop_s); return -1; }
+    // every span runs from its first element to the last one touched
+    const u64 n_bins = (u64)n_fft / 2 + 1, cap = ((u64)S + hop_s - 1) / hop_s;
+    const u64 cells = sat_mul(sat_mul(sat_mul((u64)rows, cap), n_bins), sizeof(float)), per_bin = (u64)rows * n_bins * sizeof(float);
+    if (!need_disjoint(who, {{d_out, sat_add(sat_mul(sat_mul((u64)rows - 1, (u64)out_stride), sizeof(float)), (u64)S * sizeof(float)), "d_out"},
+                             {d_work, sat_mul((u64)work, sizeof(float)), "d_work"},
+                             {d_power_out, cells, "d_power_out"},
+                             {d_gain_out, cells, "d_gain_out"},
+                             {d_hist, (u64)rows * (n_fft - 1) * sizeof(float), "d_hist"},
+                             {d_ola, (u64)rows * n_fft * sizeof(float), "d_ola"},
+                             {tracks ? d_noise : nullptr, per_bin, "d_noise"},
+                             {tracks ? d_prior : nullptr, per_bin, "d_prior"},
+                             {d_state, 4 * sizeof(int), "d_state"},
+                             {d_count, 2 * sizeof(int), "d_count"},
+                             {d_in, sat_add(sat_mul(sat_mul((u64)frames * rows - 1, (u64)in_stride), sizeof(float)), (u64)n * sizeof(float)), "d_in"},
+                             {d_win_a, (u64)n_fft * sizeof(float), "d_win_a"},
+                             {d_win_s, (u64)n_fft * sizeof(float), "d_win_s"},
+                             {d_gain_in, cells, "d_gain_in"}}, 10))   // ten written ranges (the carried state among them), four read
+        return -1;
+    if (!ensure_device()) return -1;
+    return HIP_RC(bf::launch_enhance(d_in, rows, frames, n, in_stride, hop, d_hist, d_ola, d_noise, d_prior, d_state, d_win_a, d_win_s, n_fft, hop_s, d_gain_in, alpha,
+                                     a_noise, g0, g1, g_min, n_init, d_work, d_out, out_stride, d_power_out, d_gain_out, d_count, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- phase-transform (PHAT) frames: every in-band bin weighted by |X_k|^-beta
 
 int bf_whiten_device(const float* d_signals, int rows, int frames, const float* d_window, const int* bins, const float* beta, const float* gain, int bands,

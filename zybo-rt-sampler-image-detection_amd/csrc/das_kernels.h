@@ -297,6 +297,21 @@ struct WhitenBands {
 hipError_t launch_whiten(const float* d_signals, long long items, int n_samples, const float* d_window, const WhitenBands& bands, int n_bands, float floor_rel,
                          float floor_abs, float* d_out, hipStream_t stream);
 
+// bf_enhance_device (enhance.hip): the rows of a window stream (as launch_resample reads it) through analysis frames of n_fft samples every
+// hop_s under d_win_a, a gain per (frame, bin) -- the decision-directed Wiener recursion over d_noise / d_prior float32 [rows][n_fft / 2 + 1],
+// or d_gain_in float32 [rows][cap][n_fft / 2 + 1] -- and overlap-add synthesis under d_win_s -> d_out float32 [rows][out_stride], the stream
+// delayed by n_fft.  d_hist float32 [rows][n_fft - 1], d_ola float32 [rows][n_fft] and d_state int32 [4] carry between calls; d_count int32
+// [2] = (count, status); d_power_out / d_gain_out (null: not wanted) as d_gain_in.  Four launches: analysis, gains, synthesis, and the
+// overlap-add that also writes the history, the partial sums and the state.  d_work: enhance_workspace floats.
+constexpr int kEnhanceMinFft = 32;
+constexpr int kEnhanceMaxFft = 4096;
+constexpr int kEnhanceMaxOverlap = 8;                      // n_fft / hop_s
+long long enhance_workspace(int rows, long long samples, int n_fft, int hop_s);      // -1 on bad arguments
+hipError_t launch_enhance(const float* d_in, int rows, int frames, int n, int in_stride, int hop, float* d_hist, float* d_ola, float* d_noise, float* d_prior,
+                          int32_t* d_state, const float* d_win_a, const float* d_win_s, int n_fft, int hop_s, const float* d_gain_in, float alpha, float a_noise,
+                          float g0, float g1, float g_min, int n_init, float* d_work, float* d_out, int out_stride, float* d_power_out, float* d_gain_out,
+                          int32_t* d_count, hipStream_t stream);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);

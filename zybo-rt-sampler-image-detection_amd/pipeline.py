@@ -87,6 +87,12 @@ class FusedPipeline:
         trip (feat, count)."""
         return bfeat.push_from(ao, out)
 
+    def enhance(self, out, en):
+        """listen's beams [F, B, N_SAMPLES] -> en.push (an enhance.Enhancer): the beams' stream with its noise suppressed by short-time
+        spectral gains, float32 [B, S], en.delay samples late and continuous across batches (clean, count); AudioOut.push_flat and
+        BeamFeatures take it from there."""
+        return en.push(out)
+
     def whiten(self, frames, whitener):
         """A frame batch [F, R, N_SAMPLES] -> whitener.frames (a whiten.Whitener): [K, F, R, N_SAMPLES], every in-band bin of every row
         at unit magnitude (the phase transform), for maps and peaks; listen on the raw frames at the offsets those maps give."""
