@@ -134,6 +134,10 @@ int bf_gpu_available(void);
  * 8-tap FIR flavours), 8 the two-frame sweep on frame-interleaved rows (batched lerp), 9 strided with the previous window's tail in
  * front of every row (bf_das_stream_device); -1 before the first launch. */
 int bf_last_das_variant(void);
+/* The row layout of the last delay-and-sum launch where the family comes in more than one: family 8 (two frames interleaved in the
+ * rows) runs das_pair2_kernel on rows of sample pairs in two shifted copies (1), or, where the microphone count is a multiple of 32,
+ * das_pair2_cells_kernel on rows of 16-byte cells (2).  0 for every other family and before the first launch. */
+int bf_last_das_rows(void);
 /* The digest the last delay-and-sum launch used (families 2, 3, 5, 8 of bf_last_das_variant: pad / lerp with 16 waves): *steps =
  * direction steps inside a wave's run over which the sweep could share its reads (7 of every 8 positions, times the microphones),
  * *changes = those of them at which the whole-sample delay changes, i.e. the sweep re-reads -- counted in the order the launch

@@ -24,6 +24,9 @@ MAX_QUEUE = 24          # lgkmcnt is a 4-bit counter; older entries than this ca
 
 
 UNITS = ["das_kernels.hip", "das_strided.hip", "das_pair.hip"]
+# das_pair2_cells_kernel (das_cells.hip), checked through scan_cells below
+CELLS_UNITS = ["das_cells.hip"]
+CELLS_KERNEL_RE = re.compile(r"^(_ZN2bf\S*(das_pair2_cells_kernel)\S*):")
 
 
 def compile_asm(out, units=None):
@@ -68,11 +71,11 @@ def all_vregs(text):
     return regs
 
 
-def parse_kernels(path):
+def parse_kernels(path, kernel_re=KERNEL_RE):
     """-> {mangled name: [instruction dict ...]} with `next` (fall-through index or None) and `targets` (label names)."""
     kernels, name, subs, cur = {}, None, None, 0
     for lineno, line in enumerate(open(path), 1):
-        m = KERNEL_RE.match(line)
+        m = kernel_re.match(line)
         if m:
             name, subs, cur = m.group(1), {0: [], 1: []}, 0
             kernels[name] = subs
@@ -227,10 +230,22 @@ def metadata(path):
     return out
 
 
-def scan(path):
+def scan_cells(path=None):
+    """scan + hardwired_gaps + the metadata for das_pair2_cells_kernel: path = the assembly of CELLS_UNITS (None: compiled first).
+    -> dict(kernels=, bad=[(kernel, line, instruction)], pairs=S1/S2 gaps seen, gaps=[(line, instruction)], spills={kernel: metadata that spills})"""
+    if path is None:
+        path = os.path.join(tempfile.mkdtemp(), "das_cells.s")
+        compile_asm(path, CELLS_UNITS)
+    kernels, bad = scan(path, CELLS_KERNEL_RE)
+    pairs, gaps = hardwired_gaps(path)
+    md = {n: d for n, d in metadata(path).items() if "das_pair2_cells_kernel" in n}
+    return dict(kernels=kernels, bad=bad, pairs=pairs, gaps=gaps, spills={n: d for n, d in md.items() if d["spill"] or d["scratch"]}, metadata=md)
+
+
+def scan(path, kernel_re=KERNEL_RE):
     """-> (kernels seen, [(kernel, line number, instruction), ...])"""
     bad = []
-    ks = parse_kernels(path)
+    ks = parse_kernels(path, kernel_re)
     for name, (insts, labels) in ks.items():
         for line, desc in scan_kernel(insts, labels):
             bad.append((name, line, desc))

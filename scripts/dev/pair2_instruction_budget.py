@@ -26,11 +26,11 @@ OFF_PATH = ("BF_STAGE_MASKED", "BF_STAGE_PART0", "BF_STAGE_WIPE", "BF_STAGE_OTHE
 KINDS = ("packed", "test/branch", "lds", "wait", "table load", "scalar", "vector")
 
 
-def compile_asm(src=None):
+def compile_asm(src=None, unit="das_pair.hip"):
     """gfx950 assembly text of the unit (device side only), built with the flags the library is built with."""
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
-    src = src or os.path.join(CSRC, "das_pair.hip")
+    src = src or os.path.join(CSRC, unit)
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "das_pair.s")
         cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + [f for f in ge.HIPCC_FLAGS if f != "-fPIC"] + [
@@ -39,10 +39,10 @@ def compile_asm(src=None):
         return open(out).read()
 
 
-def kernel_lines(txt):
-    """The text lines of das_pair2_kernel, from its symbol to its .Lfunc_end."""
+def kernel_lines(txt, kernel=KERNEL):
+    """The text lines of das_pair2_kernel (or of `kernel`), from its symbol to its .Lfunc_end."""
     lines = txt.split("\n")
-    start = next(i for i, l in enumerate(lines) if re.match(r"_ZN\S*%s\S*:" % KERNEL, l))
+    start = next(i for i, l in enumerate(lines) if re.match(r"_ZN\S*%s\S*:" % kernel, l))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     return lines[start + 1:end]
 
@@ -166,9 +166,9 @@ def mic_gaps(lines):
     return gaps
 
 
-def resources(txt):
+def resources(txt, kernel=KERNEL):
     """(c): the metadata entry of the kernel."""
-    blk = next(b for b in re.split(r"\n\s+- (?=\.agpr_count:)", txt)[1:] if KERNEL in re.search(r"\.name:\s+(\S+)", b).group(1))
+    blk = next(b for b in re.split(r"\n\s+- (?=\.agpr_count:)", txt)[1:] if kernel in re.search(r"\.name:\s+(\S+)", b).group(1))
     g = lambda key: int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
     return dict(vgprs=g("vgpr_count"), sgprs=g("sgpr_count"), sgpr_spills=g("sgpr_spill_count"), scratch=g("private_segment_fixed_size"))
 
@@ -248,6 +248,109 @@ def budget(src=None):
                 power=power_pass(lines))
 
 
+# ---- das_pair2_cells_kernel (csrc/das_cells.hip): the same report for the kernel of the same family on rows of 16-byte cells ----
+CELLS_UNIT, CELLS_KERNEL = "das_cells.hip", "das_pair2_cells_kernel"
+
+
+def half_loop_lines(lines):
+    """The lines of the half loop, wherever the compiler laid its blocks out (it rotates the loop: the barrier that ends an iteration
+    stands in front of the first mic in the text): the compiler's own comment on every block label says which loop the block belongs
+    to, and the half loop is the one of depth 2 that holds the mics.  A block without a label belongs to the loop of the one it falls
+    out of.  None where the text has no mic."""
+    out, inner = [], False
+    for i, l in enumerate(lines):
+        if re.match(r"\.LBB\d+_\d+:", l):
+            note = l + (lines[i + 1] if i + 1 < len(lines) and lines[i + 1].strip().startswith(";") else "")   # (a header's comment takes two lines)
+            inner = "Depth=2" in note
+        if inner:
+            out.append(l)
+    return out if any("BF_S2_BEGIN" in l for l in out) else None
+
+
+def sgpr_spill_traffic_in_half_loop(lines):
+    """lane_spills_in_half_loop for a kernel whose staging reads lanes of its own (the cells kernel takes lane 0 of the next register with
+    v_readlane) and whose loop is laid out rotated: the registers SGPRs are spilled to are those some v_writelane of the kernel writes;
+    counted are, in half_loop_lines, every v_writelane and every v_readlane out of such a register.  None where the text has no mic."""
+    loop = half_loop_lines(lines)
+    if loop is None:
+        return None
+    code = lambda ls: [l.split(";")[0].strip() for l in ls]
+    spill_regs = set(m.group(1) for m in (re.match(r"v_writelane_b32\s+(v\d+)\s*,", l) for l in code(lines)) if m)
+    n = 0
+    for l in code(loop):
+        m = re.match(r"v_readlane_b32\s+\S+\s*(v\d+)\s*,", l)
+        n += 1 if l.startswith("v_writelane_b32") or (m and m.group(1) in spill_regs) else 0
+    return n
+
+
+def barriers_in_half_loop(lines):
+    loop = half_loop_lines(lines)
+    return None if loop is None else sum(l.split(";")[0].strip() == "s_barrier" for l in loop)
+
+
+def setprio_sequence_of_a_half(lines):
+    """The s_setprio immediates of half_loop_lines in text order from the loop's header on, each with the number of BF_S2_BEGIN markers
+    (mics) passed before it: [(immediate, mics before)], the out-of-line `.subsection 1` blocks excluded."""
+    loop = half_loop_lines(lines)
+    head = next(i for i, l in enumerate(loop) if l.startswith(".LBB") and i + 1 < len(loop) and "Inner Loop Header" in loop[i + 1])
+    seq, mics, stub = [], 0, False
+    for l in loop[head:] + loop[:head]:
+        c = l.split(";")[0].strip()
+        if "BF_S2_BEGIN" in l:
+            mics += 1
+        if re.match(r"\.subsection\s+1", c):
+            stub = True
+        elif re.match(r"\.subsection\s+0", c):
+            stub = False
+        elif not stub and c.startswith("s_setprio"):
+            seq.append((int(c.split()[1]), mics))
+    return seq
+
+
+def priorities_entering_the_power_pass(items, labels):
+    """The priorities a wave can hold where it passes `;BF_POWER_POW2` or `;BF_POWER_DIV`, over every path of the control-flow graph from
+    the kernel's entry (priority 0): a set."""
+    seen, found, work = set(), set(), [(0, 0)]
+    while work:
+        i, prio = work.pop()
+        while i is not None and (i, prio) not in seen:
+            seen.add((i, prio))
+            it = items[i]
+            if it.get("marker") in ("BF_POWER_POW2", "BF_POWER_DIV"):
+                found.add(prio)
+            m = re.match(r"s_setprio\s+(\d+)$", it.get("text", ""))
+            if m:
+                prio = int(m.group(1))
+            for t in it["targets"]:
+                if labels.get(t) is not None:
+                    work.append((labels[t], prio))
+            i = it["next"]
+    return found
+
+
+def setprio_between_a_mics_statements(lines):
+    """The s_setprio instructions between a `;BF_S1_END` and the next `;BF_S2_BEGIN` (where a mic's cells are in flight): a list."""
+    bad, inside = [], False
+    for l in lines:
+        if "BF_S1_END" in l:
+            inside = True
+        elif "BF_S2_BEGIN" in l:
+            inside = False
+        elif inside and l.split(";")[0].strip().startswith("s_setprio"):
+            bad.append(l.strip())
+    return bad
+
+
+def budget_cells(src=None):
+    txt = compile_asm(src, CELLS_UNIT)
+    lines = kernel_lines(txt, CELLS_KERNEL)
+    items, labels = parse(lines)
+    return dict(staging=staging_path(items, labels), gaps=mic_gaps(lines), resources=resources(txt, CELLS_KERNEL),
+                lane_spills=sgpr_spill_traffic_in_half_loop(lines), power=power_pass(lines), ladder=setprio_sequence_of_a_half(lines),
+                prio_in_flight=setprio_between_a_mics_statements(lines), power_entry=priorities_entering_the_power_pass(items, labels),
+                loop_barriers=barriers_in_half_loop(lines))
+
+
 def report(b):
     out = []
     st = b["staging"]
@@ -279,4 +382,10 @@ def report(b):
 
 
 if __name__ == "__main__":
-    print(report(budget(sys.argv[1] if len(sys.argv) > 1 else None)))
+    if len(sys.argv) > 1 and sys.argv[1] == "--cells":
+        b = budget_cells(sys.argv[2] if len(sys.argv) > 2 else None)
+        print(report(b))
+        print("(e) s_setprio in the half loop, (immediate, mics before): %s; between a mic's two statements: %d; priorities entering the power pass: %s; "
+              "barriers in the half loop: %d" % (b["ladder"], len(b["prio_in_flight"]), sorted(b["power_entry"]), b["loop_barriers"]))
+    else:
+        print(report(budget(sys.argv[1] if len(sys.argv) > 1 else None)))

@@ -55,10 +55,11 @@ struct DigestKey {
     bool valid = false;
     int mic_chunk = 0, row_stride = 0, lead = 0, algo = 0, dpw = 0, dir_begin = 0, dir_end = 0, n_mics = 0, nf = 0;
     bool ordered = false;   // built for a kernel that sweeps in the table's own order (bf::sweep_order) rather than in flat order
+    int cells = 0;          // the row layout the offsets address: 1 = rows of 16-byte cells (plan.cells), which the geometry fields above do not show
     bool operator==(const DigestKey& o) const
     {
         return valid && o.valid && mic_chunk == o.mic_chunk && row_stride == o.row_stride && lead == o.lead && algo == o.algo && dpw == o.dpw &&
-               dir_begin == o.dir_begin && dir_end == o.dir_end && n_mics == o.n_mics && nf == o.nf && ordered == o.ordered;
+               dir_begin == o.dir_begin && dir_end == o.dir_end && n_mics == o.n_mics && nf == o.nf && ordered == o.ordered && cells == o.cells;
     }
 };
 
@@ -157,6 +158,7 @@ struct State {
     int steer_offset = 0;                // steer(): flat table offset of the listening beam (api.c:576-581)
     std::vector<int> listen_mics;        // load_pa(): microphones of the listening beam (api.c:553-567); empty before load_miso / load_pa
     int last_variant = -1;               // bf_last_das_variant
+    int last_rows = 0;                   // bf_last_das_rows
     long long last_changes = -1, last_steps = 0;   // bf_last_das_reloads
     long long last_strided[12] = {0};    // bf_last_strided_plan: the plan, the kernel and the algorithm of the most recent strided stream / select launch
     bool last_strided_set = false;
@@ -585,12 +587,12 @@ bool store_sweep_order(const bf::DasLaunch& L, const bf::DasPlan& plan, int32_t*
 bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t stream)
 {
     S().last_variant = plan.layout == 2 ? (plan.nf == 2 ? 7 : 4) : plan.layout;   // refined below for the digest-driven kernels
-    S().last_changes = -1; S().last_steps = 0;
+    S().last_changes = -1; S().last_steps = 0; S().last_rows = 0;
     const bool plain_fir = L.algo == bf::ALGO_FIR_NAIVE || L.algo == bf::ALGO_FIR_VEC;
     if (plan.layout != 2 || (plain_fir && plan.nf != 2)) return true;   // the plain FIRs have no whole-sample table (their pair kernel wants the taps regrouped)
     // everything the digest depends on: the plan's geometry, the algorithm and (grouped layouts) the direction range
     const long long want_order = bf::digest_order_offset(L, plan);   // (non-zero: the plan's kernel stores by an order table)
-    const DigestKey key{true, plan.mic_chunk, plan.row_stride, plan.lead, L.algo, plan.dpw, L.dir_begin, L.dir_end, L.n_mics, plan.nf, want_order != 0};
+    const DigestKey key{true, plan.mic_chunk, plan.row_stride, plan.lead, L.algo, plan.dpw, L.dir_begin, L.dir_end, L.n_mics, plan.nf, want_order != 0, plan.cells};
     TableSet::DigestSlot* slot = nullptr;
     for (auto& d : t.digests)
         if (d.buf.p && d.key == key) slot = &d;
@@ -645,6 +647,7 @@ bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t
     L.tab.digest_order_off = slot->order_off;
     S().last_changes = slot->changes; S().last_steps = slot->steps;
     S().last_variant = (L.algo == bf::ALGO_PAD || L.algo == bf::ALGO_LERP) ? (slot->direct ? 3 : plan.nf == 2 ? (plan.interleaved ? 8 : 5) : plan.long_rows ? 6 : 2) : plan.nf == 2 ? 7 : 4;
+    S().last_rows = S().last_variant == 8 ? (plan.cells ? 2 : 1) : 0;
     return true;
 }
 
@@ -846,6 +849,7 @@ void bf_clear_error(void) { S().err.clear(); }
 // Which kernel family the last delay-and-sum launch used, -1 before the first one (the values are listed at its declaration in
 // include/beamformer_hip.h).  For tests and tuning.
 int bf_last_das_variant(void) { return S().last_variant; }
+int bf_last_das_rows(void) { return S().last_rows; }
 
 int bf_last_das_reloads(long long* changes, long long* steps)
 {
@@ -1403,7 +1407,7 @@ int bf_das_stream_device(int algo, const float* d_signals, int m_total, float* d
     const char* why = "";
     if (bf::plan_stream_maps(L, s.n_cus, &plan, &why) != 0) { set_error("%s: unsupported shape: %s", who, why); return -1; }
     if (STRIDED_RC(STRIDED_STREAM_MAP, algo, plan, bf::launch_stream_maps(L, plan, d_prev, hop, as_stream(stream))) != 0) return -1;
-    s.last_variant = 9;
+    s.last_variant = 9; s.last_rows = 0;
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// What the host planner (das_plan.cpp) and the delay-and-sum kernel units (das_kernels.hip, das_strided.hip, das_pair.hip) share, and nothing of the device:
+// What the host planner (das_plan.cpp) and the delay-and-sum kernel units (das_kernels.hip, das_strided.hip, das_pair.hip, das_cells.hip) share, and nothing of the device:
 // the compile-time geometry of every kernel family, stated once, and the per-family launchers launch_das chooses between.
 // Not installed; das_device.h includes it.
 #pragma once
@@ -61,6 +61,16 @@ struct Pair2Geo {
     static constexpr int kDoff = kC * kRs * 4;           // bytes from a sample quad to its difference quad
 };
 
+// das_pair2_cells_kernel (das_cells.hip): a mic is one row of 16-byte cells (s f0, s f1, D f0, D f1), one per sample, no shifted copies
+struct CellGeo {
+    static constexpr int kLead = Geo<1>::kLead, kCells = 256 + kLead;   // zero cells in front, cells per row
+    static constexpr int kSlot = 4 * kCells;             // floats per staged mic (both frames, samples and differences)
+#ifndef BF_CELLS_HC
+#define BF_CELLS_HC 16                                   // (8: the measuring aid of das_cells.hip, never the shipped build)
+#endif
+    static constexpr int kHalf = BF_CELLS_HC, kMc = 2 * kHalf;   // mic slots of the LDS image (the digest's slot count: 32), swept and re-staged in halves of 16
+};
+
 // das_hybrid_pair_kernel (das_kernels.hip)
 struct HybridGeo {
     static constexpr int kC = 2, kLead = Geo<1>::kLead, kRs = 2 * Geo<1>::kRsFir;   // floats per row: two frames interleaved
@@ -85,6 +95,7 @@ struct LongGeo {
 hipError_t launch_strided(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream);       // das_strided.hip: das_mimo_kernel<.., HIST = false>
 hipError_t launch_copies(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream);        // das_kernels.hip: das_copies_kernel
 hipError_t launch_pair(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream);          // das_pair.hip: das_pair_kernel (pad), das_pair2_kernel (lerp)
+hipError_t launch_pair_cells(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream);    // das_cells.hip: das_pair2_cells_kernel (lerp, plan.cells)
 hipError_t launch_hybrid_pair(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream);   // das_kernels.hip: das_hybrid_pair_kernel
 hipError_t launch_long(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream);          // das_kernels.hip: das_long_kernel
 

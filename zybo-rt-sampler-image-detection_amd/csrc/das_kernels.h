@@ -66,6 +66,8 @@ struct DasPlan {
     int tile_dirs;   // directions per workgroup
     int n_tiles;     // padded to a multiple of 8 (XCD affinity: tile % 8 == workgroup id % 8) unless the launch's table fits every XCD's L2
     size_t lds_bytes;
+    int cells;       // internal (no plan export carries it): 1 = the interleaved lerp pair family runs on rows of 16-byte cells (das_pair2_cells_kernel: a multiple of
+                     // 32 mics).  The digest is then built for 32 slots of CellGeo::kSlot floats; mic_chunk, row_stride and lds_bytes stay das_pair2_kernel's.
 };
 
 // Returns 0 and fills `plan`, or a negative value when the shape is unsupported (message in `why`).

@@ -21,6 +21,8 @@
 //     at every step (four copies, 16-byte reads).
 //   * das_pair.hip: copies::das_pair_kernel (pad) / das_pair2_kernel (lerp): the same sweep with TWO frames per workgroup -- batched launches
 //     at N <= 256, what the bench and every multi-frame caller run: the per-step scalar work is shared by both frames.
+//   * das_cells.hip: copies::das_pair2_cells_kernel (lerp, a multiple of 32 mics): das_pair2_kernel's sweep on rows of 16-byte cells,
+//     one per sample -- no shifted copies, half the staging stores, halves of 16 mics.
 // This unit holds the shifted-copies kernels that are not the pad / lerp pair: das_copies_kernel, the 8-tap FIR pair kernel
 // (das_hybrid_pair_kernel), the long-row kernel (das_long_kernel) and the digests all of them read.  das_plan.cpp (host only) sizes a
 // launch and picks its family; das_device.h / das_geometry.h hold what the units share -- the mean-power rule every kernel ends with among it.
@@ -1853,6 +1855,14 @@ hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_dig
                            arrays, plan.row_stride, plan.lead, bias, plan.copies);
     } else {
         const long long entries = grouped_entries_for_args(L, plan);
+        if (plan.cells) {
+            // rows of 16-byte cells (das_pair2_cells_kernel): 32 slots of one row each, no shifted copies, a sample is four floats wide
+            using CG = copies::CellGeo;
+            hipLaunchKernelGGL(digest_grouped_kernel, dim3(1024), dim3(256), 0, stream, L.tab.whole, L.tab.frac, d_digest, entries, entries, L.n_mics, plan.dpw,
+                               L.dir_begin, L.dir_end, CG::kMc, 1, CG::kSlot, CG::kLead, bias, 1, d_reload_count, 0, 4, nullptr, 0,
+                               order_off != 0 ? d_digest + order_off : nullptr);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL(digest_grouped_kernel, dim3(1024), dim3(256), 0, stream, L.algo == ALGO_HYBRID || !fir_pair ? L.tab.whole : nullptr,
                            L.algo == ALGO_LERP ? L.tab.frac : nullptr, d_digest,
                            entries, entries, L.n_mics, plan.dpw, L.dir_begin, L.dir_end, plan.mic_chunk, arrays, plan.row_stride, plan.lead, bias,

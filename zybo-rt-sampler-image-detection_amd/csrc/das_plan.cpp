@@ -103,6 +103,11 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why)
             if (L.algo == ALGO_LERP) {
                 p.interleaved = 1;
                 p.row_stride = 2 * copies::Geo<1>::kRs;         // the two frames of a mic share a row, sample by sample
+                // whole halves of 16 mics, an even number of them: rows of 16-byte cells (das_pair2_cells_kernel), half the staging
+                // stores per mic and half the barriers.  The plan's exported fields stay those of das_pair2_kernel's image, which
+                // is the same 159,744 bytes.
+                static_assert(copies::CellGeo::kMc * copies::CellGeo::kSlot <= copies::Pair2Geo::kMc * copies::Pair2Geo::kSlot, "one LDS image for both row layouts");
+                p.cells = (L.n_mics % copies::CellGeo::kMc) == 0 && L.n_samples > 128 ? 1 : 0;
             }
         }
         // The hybrid beamformer's two-frame sweep (das_hybrid_pair_kernel) under the same conditions.
@@ -234,7 +239,8 @@ hipError_t launch_das(const DasLaunch& L, const DasPlan& plan, hipStream_t strea
     const bool needs_digest = L.algo != ALGO_FIR_NAIVE && L.algo != ALGO_FIR_VEC;
     if (needs_digest && L.tab.digest == nullptr) return hipErrorInvalidValue;   // launch_digest first
     if (fir && L.n_taps != 8) return hipErrorInvalidValue;
-    if (plan.nf == 2 && (fir || nseg == 1)) return fir ? launch_hybrid_pair(L, plan, L.frames, stream) : launch_pair(L, plan, L.frames, stream);
+    if (plan.nf == 2 && (fir || nseg == 1))
+        return fir ? launch_hybrid_pair(L, plan, L.frames, stream) : plan.cells ? launch_pair_cells(L, plan, L.frames, stream) : launch_pair(L, plan, L.frames, stream);
     if (!fir && nseg > 1 && plan.long_rows) return launch_long(L, plan, L.frames, stream);
     return launch_copies(L, plan, L.frames, stream);
 }

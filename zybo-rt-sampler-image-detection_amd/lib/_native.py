@@ -89,6 +89,7 @@ _sig("bf_last_error", C.c_char_p)
 _sig("bf_clear_error", None)
 _sig("bf_gpu_available", C.c_int)
 _sig("bf_last_das_variant", C.c_int)
+_sig("bf_last_das_rows", C.c_int)
 _sig("bf_last_das_reloads", C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
 _sig("bf_sweep_order", C.c_int, IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP)
 _sig("bf_set_device", C.c_int, C.c_int)
