@@ -4,13 +4,17 @@ restatement of the routing rule so that a case's expected family is checked on t
 gives every case a second batch, of samples that N(0, 0.25) never draws.
 TEST INFRASTRUCTURE ONLY.
 
-Two table kinds:
+Three table kinds:
   random   independent uniform delays per (direction, microphone), as test_gpu_parity._random_case draws them: the whole-sample
            delay changes at nearly every direction step, so pad / lerp with 16 waves replan to the direction-outer variant (3)
   smooth   delays[d, m] = c_m + s_m * d / D over the flat direction index d, c_m uniform in [0, pmax - span], s_m uniform in
            [-span, span], clipped at 0, with span = min(D / 8, pmax / 2).  A microphone's whole-sample delay then changes at most
            span + 1 times over the D - 1 steps (under 1/4 of them at every D used here, span / 2D on average), so the sweep
-           kernels (2, 5, 6, 8) are what runs."""
+           kernels (2, 5, 6, 8) are what runs.
+  folded   (tests/pair_cases.py) smooth along a grid row of Y directions, delays[d, m] = c_m + s_m * (d % Y) / Y with span = min(Y / 4,
+           pmax / 2), and back to c_m at every row end, as a real grid's delays are: most microphones change there at once, so where no
+           run of 8 divides Y the sweep-order rule (csrc/sweep_order.h) walks every other row backwards and the pad / lerp pair kernels
+           store through an order that is not the identity."""
 import collections
 import functools
 import zlib
@@ -64,16 +68,36 @@ CASES = [
     _c("fir_pair_divided_mean", 7, FIRS, 56, 48, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),
     # ---- two frames: the smallest batch the pair kernels take, no workgroup row with a single frame
     _c("pair_two_frames", {"pad": 5, "lerp": 8}, PLAIN, 20, 16, 256, 17, 16, 8, 30.0, "smooth", F=2),
+    # ---- 8 on rows of 16-byte cells (das_pair2_cells_kernel, bf_last_das_rows() == 2): lerp with a multiple of 32 microphones
+    _c("cells_reversed_rows", 8, ("lerp",), 40, 32, 256, 17, 16, 8, 30.0, "smooth", rows="reversed"),   # two halves of 16
+    _c("cells_divided_mean_masked", 8, ("lerp",), 100, 96, 252, 17, 16, 8, 30.0, "smooth"),           # six halves, the mean divides, sample 252 .. 255 masked
+    _c("cells_two_frames_short", 8, ("lerp",), 40, 32, 132, 17, 16, 8, 30.0, "smooth", F=2),           # round 1 of the power pass is one quad
 ]
 BY_NAME = {c.name: c for c in CASES}
 PARAMS = [(c.name, a) for c in CASES for a in c.algos]
 
 # the cases of the digest-cache eviction tests
-EVICT_PLAIN, EVICT_FIR = "pair_reversed_rows", "fir_pair_reversed_rows"
+EVICT_PLAIN, EVICT_FIR, EVICT_CELLS = "pair_reversed_rows", "fir_pair_reversed_rows", "cells_reversed_rows"
+
+# Cases of other modules (tests/pair_cases.py) that draw their data with the generators below: name -> Case.  They are no part of
+# CASES, PARAMS or the hostile batch.
+EXTRA = {}
+
+
+def case_of(name):
+    return BY_NAME[name] if name in BY_NAME else EXTRA[name]
 
 
 def family_of(case, algo):
     return case.family[algo] if isinstance(case.family, dict) else case.family
+
+
+def rows_of(case, algo):
+    """bf_last_das_rows() of the batched call: 2 where the lerp pair sweep runs on cell rows, 1 on rows of sample pairs, 0 for every
+    other family."""
+    if family_of(case, algo) != 8:
+        return 0
+    return 2 if case.name.startswith("cells_") else 1
 
 
 def shard(case):
@@ -92,7 +116,7 @@ Data = collections.namedtuple("Data", "frames mics delays taps")
 def data(name):
     """frames float32 [F, M_total, N], mics int32 [n] (rows of a frame; column i of a table pairs with mics[i]), delays float64
     [D, n], taps float32 [D, n, T].  Seeded by the case's name; read-only, shared by every test that asks."""
-    c = BY_NAME[name]
+    c = case_of(name)
     D = c.X * c.Y
     rng = np.random.default_rng(zlib.crc32(name.encode()))
     frames = (rng.standard_normal((c.F, c.M_total, c.N)) * 0.25).astype(np.float32)
@@ -101,6 +125,11 @@ def data(name):
         mics = np.ascontiguousarray(mics[::-1])
     if c.kind == "random":
         delays = rng.uniform(0, c.pmax, size=(D, c.n))
+    elif c.kind == "folded":
+        span = min(c.Y / 4.0, c.pmax / 2.0)
+        c_m = rng.uniform(0, c.pmax - span, size=c.n)
+        s_m = rng.uniform(-span, span, size=c.n)
+        delays = np.maximum(c_m[None, :] + s_m[None, :] * ((np.arange(D) % c.Y)[:, None] / c.Y), 0.0)
     else:
         span = span_of(c)
         c_m = rng.uniform(0, c.pmax - span, size=c.n)
@@ -116,7 +145,7 @@ def _oracle_maps(name, algo, frames):
     """Oracle maps float32 [len(frames), D] over the full direction range (oracle/libdas_oracle.so has to be built: the tests
     that come here ask for the oracle_lib fixture first)."""
     import das_oracle
-    c, d = BY_NAME[name], data(name)
+    c, d = case_of(name), data(name)
     orc = das_oracle.Oracle(c.N, c.X, c.Y, c.T)
     orc.load(ALGOS[algo], table(name, algo))
     return np.stack([orc.mimo_range(ALGOS[algo], f, d.mics, 0, c.X * c.Y) for f in frames])
@@ -209,7 +238,7 @@ def hostile(name, algo):
 
 def table(name, algo):
     """What load_coefficients_* takes for `algo`, shaped [X, Y, n(, T)]."""
-    c, d = BY_NAME[name], data(name)
+    c, d = case_of(name), data(name)
     if algo == "pad":
         t = d.delays.astype(int).astype(np.int32)
     elif algo in ("lerp", "hybrid"):
@@ -221,7 +250,7 @@ def table(name, algo):
 
 def whole(name, algo):
     """The whole-sample rows int32 [D, n] the library keeps for `algo` (values beyond N clamp to N); None for the plain FIRs."""
-    c, d = BY_NAME[name], data(name)
+    c, d = case_of(name), data(name)
     if algo in ("fir_naive", "fir_vec"):
         return None
     w = d.delays.astype(int).astype(np.int32) if algo == "pad" else SO.whole_of(d.delays)
@@ -244,7 +273,8 @@ def _round_up(v, m):
 
 
 def plan(algo, n, N, T, dirs, frames, max_whole):
-    """What plan_das decides before any digest is counted: dict(nc, layout, lead, waves, dpw, pair, long_rows)."""
+    """What plan_das decides before any digest is counted: dict(nc, layout, lead, waves, dpw, pair, cells, long_rows).  cells: the
+    lerp pair sweep runs on rows of 16-byte cells (das_pair2_cells_kernel), which takes whole pairs of 16-microphone halves."""
     nc = -(-N // 64)
     nc = 1 if nc <= 1 else 2 if nc <= 2 else 4 if nc <= 4 else 8 if nc <= 8 else 16
     plain = algo in PLAIN
@@ -257,12 +287,13 @@ def plan(algo, n, N, T, dirs, frames, max_whole):
     waves = 8 if plain and nseg == 1 and dirs < 256 else 16
     dpw = 4 if nseg == 4 else 8
     pair = nseg == 1 and waves == 16 and lead == fixed_lead and n % 16 == 0 and N % 4 == 0 and frames >= 2
+    cells = pair and algo == "lerp" and n % 32 == 0 and N > 128
     long_rows = False
     if plain and nseg > 1:
         half = 16 // nseg
         slot_bytes = (2 if algo == "lerp" else 1) * 2 * (lead + nseg * 256) * 4      # two shifted copies of a microphone's row(s)
         long_rows = n % half == 0 and N % 4 == 0 and slot_bytes * 2 * half <= 160 * 1024
-    return dict(nc=nc, layout=2, lead=lead, waves=waves, dpw=dpw, pair=pair, long_rows=long_rows)
+    return dict(nc=nc, layout=2, lead=lead, waves=waves, dpw=dpw, pair=pair, cells=cells, long_rows=long_rows)
 
 
 def predict_family(algo, n, N, T, w, lo, hi, frames):
@@ -292,7 +323,7 @@ _WANT = {}
 def want(oracle_lib, name, algo):
     """Oracle maps float32 [F, D] of every frame over the full direction range: computed once per (case, algo), read-only."""
     if (name, algo) not in _WANT:
-        c, d = BY_NAME[name], data(name)
+        c, d = case_of(name), data(name)
         orc = oracle_lib.Oracle(c.N, c.X, c.Y, c.T)
         orc.load(ALGOS[algo], table(name, algo))
         w = np.stack([orc.mimo_range(ALGOS[algo], d.frames[f], d.mics, 0, c.X * c.Y) for f in range(c.F)])

@@ -48,6 +48,20 @@ def test_every_family_has_out_of_order_rows():
     for fam, rows in fams.items():
         assert "reversed" in rows, fam
     assert {c.F for c in BC.CASES} == {2, 3}
+    assert len(BC.CASES) == 24 and len(BC.PARAMS) == 56
+    # lerp's pair sweep (8) on both row layouts, each with rows out of order, with a count that is no power of two, and with two frames
+    layouts = {}
+    for name, algo in BC.PARAMS:
+        c = BC.BY_NAME[name]
+        if BC.family_of(c, algo) == 8:
+            layouts.setdefault(BC.rows_of(c, algo), []).append(c)
+        else:
+            assert BC.rows_of(c, algo) == 0
+    assert sorted(layouts) == [1, 2]
+    assert sorted(c.name for c in layouts[2]) == ["cells_divided_mean_masked", "cells_reversed_rows", "cells_two_frames_short"]
+    for rows, cases in layouts.items():
+        assert any(c.rows == "reversed" for c in cases) and any(c.n & (c.n - 1) for c in cases) and any(c.F == 2 for c in cases), rows
+    assert {BC.BY_NAME[n].algos for n in (BC.EVICT_PLAIN, BC.EVICT_FIR, BC.EVICT_CELLS)} == {BC.PLAIN, BC.FIRS, ("lerp",)}
 
 
 def _shares(name, algo):
@@ -102,6 +116,9 @@ def test_expected_family_follows_the_routing_rule(native, case, algo):
                     assert mc == 2 * 16 // (nc // 4)
                 if p["pair"]:
                     assert mc == (16 if algo in BC.PLAIN else 32)
+                # the row layout beside the case: cells for whole pairs of 16-microphone halves beyond 128 samples
+                assert BC.rows_of(c, algo) == ((2 if p["cells"] else 1) if BC.family_of(c, algo) == 8 else 0)
+                assert bool(p["cells"]) == (p["pair"] and algo == "lerp" and c.n % 32 == 0 and c.N > 128)
         # the one-frame call of the GPU test's first step walks no frames; where it takes another family the test says so
         one = BC.predict_family(algo, c.n, c.N, c.T, w, 0, D, 1)
         fam = BC.family_of(c, algo)
@@ -136,7 +153,7 @@ def test_hostile_batch_is_deterministic(oracle_lib):
 @pytest.mark.parametrize("case,algo", BC.PARAMS)
 def test_hostile_frames_on_the_oracle(oracle_lib, case, algo):
     """What each of the seven frames is for, on the oracle alone: the GPU test then only has to ask for the same NaNs and bits.
-    Measured over the 50 (case, algorithm) pairs: quiet exponents -62 .. -65, loud exponents 63 .. 66, the loud frames' largest sum
+    Measured over the first 50 (case, algorithm) pairs: quiet exponents -62 .. -65, loud exponents 63 .. 66, the loud frames' largest sum
     of squares 2^126.1 .. 2^127.99 with a map's largest entry at most 2.54 times its smallest, NaN share of the one bad sample
     0.51 .. 0.60 (pad / lerp), 0.56 .. 0.87 (hybrid at 8 taps), 1 for hybrid at 16 taps and the plain FIRs."""
     c, d = BC.BY_NAME[case], BC.data(case)

@@ -48,7 +48,7 @@ def _das(nat, c, algo, d_sig, mics, lo, hi, stride=None, spare_rows=0):
 
 
 # (case, algo) of BC.PARAMS whose maps are not the oracle's bit for bit, each with its cause, the number of differing entries and the
-# largest distance in float32 steps as measured.  Empty: all 53 are held to bits, on plain frames and on the hostile ones.  An entry
+# largest distance in float32 steps as measured.  Empty: all 56 are held to bits, on plain frames and on the hostile ones.  An entry
 # has to bring its own bound with it: the kernel's distance from a float64 evaluation of the same sum at most twice the oracle's own,
 # both measured and written beside the entry.
 NOT_BIT_IDENTICAL = {}
@@ -79,12 +79,13 @@ def test_batch_reaches_its_family_and_matches_the_oracle(nat, oracle_lib, case, 
     # 2. the batch: a direction shard into image rows 5 columns wider than it, one spare row behind the last frame
     d_sig = torch.from_numpy(d.frames.copy()).cuda()
     got = _das(nat, c, algo, d_sig, mics, lo, hi, stride=W + PAD_COLS, spare_rows=1)
-    family = nat.lib.bf_last_das_variant()
+    family, layout = nat.lib.bf_last_das_variant(), nat.lib.bf_last_das_rows()
     err = [max_rel(got[f, :W], want[f, lo:hi]) if np.isfinite(got[f, :W]).all() else float("nan") for f in range(F)]
-    print("%s %s: family %d (one frame: %d), max rel err per frame %s" % (case, algo, family, one_family, " ".join("%.3g" % e for e in err)))
+    print("%s %s: family %d rows %d (one frame: %d), max rel err per frame %s" % (case, algo, family, layout, one_family, " ".join("%.3g" % e for e in err)))
 
-    # 3. the family the case is written for
+    # 3. the family the case is written for, and for lerp's pair sweep the kernel: rows of sample pairs (1) or of cells (2)
     assert family == BC.family_of(c, algo)
+    assert layout == BC.rows_of(c, algo)
     # 4. every frame against the oracle
     for f in range(F):
         assert np.isfinite(got[f, :W]).all(), f
@@ -100,6 +101,7 @@ def test_batch_reaches_its_family_and_matches_the_oracle(nat, oracle_lib, case, 
         assert got[F - 1, :W].tobytes() == one[lo:hi].tobytes()
     # 7. the full range, image rows back to back
     full = _das(nat, c, algo, d_sig, mics, 0, D)
+    assert nat.lib.bf_last_das_rows() == layout
     assert full[:, lo:hi].tobytes() == got[:F, :W].tobytes()
     for f in range(F):
         assert max_rel(full[f], want[f]) <= REL_TOL, f
@@ -143,13 +145,14 @@ def test_hostile_frames_match_the_oracle(nat, oracle_lib, case, algo):
     d_sig = buf[GUARD:GUARD + h.frames.size].view(F, c.M_total, c.N)
     d_sig.copy_(torch.from_numpy(h.frames.copy()))
     got = _das(nat, c, algo, d_sig, mics, lo, hi, stride=W + PAD_COLS, spare_rows=1)
-    family = nat.lib.bf_last_das_variant()
+    family, layout = nat.lib.bf_last_das_variant(), nat.lib.bf_last_das_rows()
     full = _das(nat, c, algo, d_sig, mics, 0, D, stride=D)
-    assert nat.lib.bf_last_das_variant() == family
-    print("%s %s: family %d (one frame: %d), quiet * 2^%d, loud * 2^%d, NaN at %s, %d samples poisoned"
-          % (case, algo, family, one_family, h.info["e_quiet"], h.info["e_loud"], h.info["bad"], h.info["poisoned"]))
+    assert (nat.lib.bf_last_das_variant(), nat.lib.bf_last_das_rows()) == (family, layout)
+    print("%s %s: family %d rows %d (one frame: %d), quiet * 2^%d, loud * 2^%d, NaN at %s, %d samples poisoned"
+          % (case, algo, family, layout, one_family, h.info["e_quiet"], h.info["e_loud"], h.info["bad"], h.info["poisoned"]))
 
     assert family == BC.family_of(c, algo)
+    assert layout == BC.rows_of(c, algo)
     wrong = []                                                  # every frame is compared before any fails: the kinds tell the cause apart
     for f, kind in enumerate(BC.KINDS):
         what = "%s %s, frame %d (%s)" % (case, algo, f, kind)
@@ -170,13 +173,13 @@ def _reloads(nat):
     return rc, ch.value, st.value
 
 
-@pytest.mark.parametrize("algo", ["pad", "lerp", "hybrid"])
-def test_digest_cache_eviction(nat, oracle_lib, algo):
+@pytest.mark.parametrize("algo,case", [("pad", BC.EVICT_PLAIN), ("lerp", BC.EVICT_PLAIN), ("hybrid", BC.EVICT_FIR), ("lerp", BC.EVICT_CELLS)],
+                         ids=["pad", "lerp", "hybrid", "lerp_cells"])
+def test_digest_cache_eviction(nat, oracle_lib, algo, case):
     """Six direction ranges through the four digest slots of one table, then the first two again (both evicted by then) and a
     one-frame call: every result is the matching slice of the full maps bit for bit, and a rebuilt digest counts the re-reads it
-    counted the first time."""
+    counted the first time.  lerp_cells: the pair launches run on cell rows, whose summing waves store through the digest's sweep order."""
     torch = util.torch_gpu()
-    case = BC.EVICT_PLAIN if algo in BC.PLAIN else BC.EVICT_FIR
     c, d = BC.BY_NAME[case], BC.data(case)
     D, F = c.X * c.Y, c.F
     want = BC.want(oracle_lib, case, algo)
@@ -184,10 +187,10 @@ def test_digest_cache_eviction(nat, oracle_lib, algo):
     _configure(c)
     run_product(nat, algo, BC.table(case, algo), d.frames[0], mics)         # loads the table (and takes a slot for its one-frame geometry)
     d_sig = torch.from_numpy(d.frames.copy()).cuda()
-    pair = {"pad": 5, "lerp": 8, "hybrid": 7}[algo]
+    pair, layout = {"pad": 5, "lerp": 8, "hybrid": 7}[algo], BC.rows_of(c, algo)
 
     full = _das(nat, c, algo, d_sig, mics, 0, D)
-    assert nat.lib.bf_last_das_variant() == pair
+    assert (nat.lib.bf_last_das_variant(), nat.lib.bf_last_das_rows()) == (pair, layout)
     for f in range(F):
         assert max_rel(full[f], want[f]) <= REL_TOL, f
 
@@ -196,7 +199,8 @@ def test_digest_cache_eviction(nat, oracle_lib, algo):
     for lo, hi in shards + shards[:2]:
         part = _das(nat, c, algo, d_sig, mics, lo, hi)
         fam, counted = nat.lib.bf_last_das_variant(), _reloads(nat)
-        print("%s [%d, %d): family %d, re-reads (rc, changes, steps) %s" % (algo, lo, hi, fam, counted))
+        assert nat.lib.bf_last_das_rows() == (layout if fam == pair else 0), (lo, hi)
+        print("%s %s [%d, %d): family %d rows %d, re-reads (rc, changes, steps) %s" % (case, algo, lo, hi, fam, nat.lib.bf_last_das_rows(), counted))
         assert part.tobytes() == np.ascontiguousarray(full[:, lo:hi]).tobytes(), (lo, hi)
         if (lo, hi) in seen:
             assert (fam, counted) == seen[(lo, hi)], (lo, hi)               # the rebuilt digest is the one built first
