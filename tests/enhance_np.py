@@ -22,8 +22,8 @@ import functools
 
 import numpy as np
 
-EPS = 2.0 ** -24            # the unit roundoff of float32
-ETA = 5.0 * np.sqrt(2.0) * 1.01
+from stft_np import EPS, ETA, two_sided, windowed
+
 FLT_MIN = float(np.finfo(np.float32).tiny)
 FLT_MAX = float(np.finfo(np.float32).max)
 MAX_OVERLAP = 8
@@ -61,12 +61,7 @@ def new_history(hist, x):
     return np.ascontiguousarray(np.concatenate([hist, x], axis=1)[:, x.shape[1]:x.shape[1] + H]) if H else hist.copy()
 
 
-# ------------------------------------------------------------------ float32, as defined
-
-def windowed(frames, win_a):
-    """u[t] = win_a[t] * x[t]: one float32 multiply."""
-    return (np.asarray(frames, dtype=np.float32) * np.asarray(win_a, dtype=np.float32)).astype(np.float32)
-
+# ------------------------------------------------------------------ float32, as defined (u = win_a * x: stft_np.windowed)
 
 def fmaf(a, b, c):
     """fmaf on float32 arrays with ONE rounding: the product is exact in float64, the float64 sum is brought to round-to-odd with its
@@ -120,12 +115,6 @@ def gains(P, lam, prior, seen, alpha=0.98, a_noise=0.9, g0=1.5, g1=5.0, g_min=0.
 
 # ------------------------------------------------------------------ the call in float64, with its tolerance
 
-def _two_sided(n):
-    w = np.full(n // 2 + 1, 2.0)
-    w[0] = w[-1] = 1.0
-    return w
-
-
 def analysis(x, hist, c, win_a, hop_s):
     """-> (u float32 [R, count, n_fft], X complex128 [R, count, B], starts): the call's frames of hist || x."""
     n_fft = win_a.shape[0]
@@ -141,7 +130,7 @@ def synthesis_bound(u, X, G, win_s, v):
     """dv [R, count, n_fft]: the tolerance of every frame's v (module docstring)."""
     n = u.shape[-1]
     t = int(np.log2(n))
-    two = _two_sided(n)
+    two = two_sided(n)
     e = t * ETA * EPS * np.sqrt(n) * np.sqrt((u.astype(np.float64) ** 2).sum(axis=-1))[..., None]
     absG = np.abs(G)
     dY = absG * e + np.sqrt(2.0) * EPS * absG * (np.abs(X) + e)

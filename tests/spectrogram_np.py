@@ -3,7 +3,7 @@ it in float64; Python ints for the state; and the bound a float32 implementation
 algorithm and summation orders are."""
 import numpy as np
 
-EPS = 2.0 ** -24            # the unit roundoff of float32
+from stft_np import EPS, windowed
 
 
 def capacity(length, hop):
@@ -31,11 +31,6 @@ def framed(x, hist, s0, L, n_win, hop, shift=0):
     idx = (H + s0 + shift + hop * np.arange(count))[:, None] + np.arange(n_win)[None, :]
     idx = np.clip(idx, 0, max(stream.shape[1] - 1, 0))                   # (only a shifted start can leave the stream)
     return stream[:, idx] if count else np.zeros((x.shape[0], 0, n_win), np.float32)
-
-
-def windowed(frames, window):
-    """u[t] = window[t] * x[s_j + t]: one float32 multiply."""
-    return (frames.astype(np.float32) * window.astype(np.float32)[None, None, :]).astype(np.float32)
 
 
 def spectrum(u, n_fft):

@@ -27,25 +27,11 @@ The order-agnostic 2 (N + 2) u sum |u| bound of spectrogram_np.py is vacuous her
 small d_k it reaches 86 times a row's RMS at N = 1024); the norm-wise bound is not."""
 import numpy as np
 
-EPS = 2.0 ** -24            # the unit roundoff of float32
-ETA = 5.0 * np.sqrt(2.0) * 1.01
+from stft_np import EPS, ETA, two_sided, windowed
 
 
 def clip_bins(bins, n):
     return [(min(max(int(lo), 0), n // 2 + 1), min(max(int(hi), 0), n // 2 + 1)) for lo, hi in np.asarray(bins).reshape(-1, 2)]
-
-
-def windowed(x, window):
-    """u[t] = window[t] * x[t]: one float32 multiply (u = x without a window)."""
-    x = np.asarray(x, dtype=np.float32)
-    return x if window is None else (x * np.asarray(window, dtype=np.float32)).astype(np.float32)
-
-
-def _two_sided(n):
-    """Weights of the half-spectrum bins in a sum over all n bins: 1 for bins 0 and n / 2, 2 for the others."""
-    w = np.full(n // 2 + 1, 2.0)
-    w[0] = w[-1] = 1.0
-    return w
 
 
 def whiten(x, window, bins, beta, gain, floor_rel=1e-3, floor_abs=0.0, with_tol=False):
@@ -57,7 +43,7 @@ def whiten(x, window, bins, beta, gain, floor_rel=1e-3, floor_abs=0.0, with_tol=
     X = np.fft.rfft(u.astype(np.float64), axis=-1)
     mag = np.abs(X)
     k = np.arange(n // 2 + 1)
-    two = _two_sided(n)
+    two = two_sided(n)
     e = t * ETA * EPS * np.sqrt(n) * np.sqrt((u.astype(np.float64) ** 2).sum(axis=-1))[..., None]
     outs, tols = [], []
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):

@@ -18,29 +18,13 @@
 #include <hip/hip_runtime.h>
 
 #include "das_kernels.h"
+#include "fir_window.h"
 
 namespace bf {
 namespace {
 
 constexpr int kBandWaves = 4;
 constexpr int kLanes = 64;
-
-template <int KB>
-__device__ __forceinline__ void band_taps4(float (&acc)[KB][4], const float (&w)[8], const float* const (&hk)[KB], int t0, int n_u)
-{
-    // w[4 + d] = x~[j0 - t0 + d]; output o at tap t0 + u reads x~[j0 + o - t0 - u]
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (u < n_u) {   // (wave-uniform; n_u = 4 in the main loop)
-#pragma unroll
-            for (int k = 0; k < KB; ++k) {
-                const float h = hk[k][t0 + u];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) acc[k][o] = __fmaf_rn(h, w[4 + o - u], acc[k][o]);
-            }
-        }
-    }
-}
 
 template <int KB>
 __global__ void __launch_bounds__(kBandWaves * kLanes)
@@ -105,13 +89,13 @@ band_filter_kernel(const float* __restrict__ signals, const float* __restrict__ 
         for (int q = 0; q < full; ++q) {
             const float4 a = *reinterpret_cast<const float4*>(p - 4 * q - 4);
             w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-            band_taps4<KB>(acc, w, hk, 4 * q, 4);
+            fir_taps4<KB>(acc, w, hk, 4 * q, 4);
             w[4] = w[0]; w[5] = w[1]; w[6] = w[2]; w[7] = w[3];
         }
         if (rem) {
             const float4 a = *reinterpret_cast<const float4*>(p - 4 * full - 4);
             w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-            band_taps4<KB>(acc, w, hk, 4 * full, rem);
+            fir_taps4<KB>(acc, w, hk, 4 * full, rem);
         }
 #pragma unroll
         for (int k = 0; k < KB; ++k) {

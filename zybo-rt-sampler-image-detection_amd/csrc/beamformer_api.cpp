@@ -227,6 +227,13 @@ bool need_min(const char* who, const char* name, int v, const char* bound, int l
     return true;
 }
 
+// (a transform length)
+bool need_pow2(const char* who, const char* name, int v, int lo, int hi)
+{
+    if (v < lo || v > hi || (v & (v - 1)) != 0) { set_error("%s: %s = %d is not a power of two in [%d, %d]", who, name, v, lo, hi); return false; }
+    return true;
+}
+
 enum Finite { FINITE, FINITE_GE0, FINITE_GT0 };
 bool need_finite(const char* who, const char* name, float v, Finite range = FINITE)
 {
@@ -1886,10 +1893,7 @@ int bf_spectrogram_device(const float* d_in, int rows, int in_stride, int len, c
     Entered in;
     if (!need_ptrs(who, {{d_in, "d_in"}, {d_hist, "d_hist"}, {d_state, "d_state"}, {d_window, "d_window"}, {d_out, "d_out"}, {d_count, "d_count"}})) return -1;
     if (!need_min(who, "rows", rows, 1) || !need_min(who, "len", len, 0) || !need_min(who, "in_stride", in_stride, "len", len)) return -1;
-    if (n_fft < bf::kSpectrogramMinFft || n_fft > bf::kSpectrogramMaxFft || (n_fft & (n_fft - 1)) != 0) {
-        set_error("%s: n_fft = %d is not a power of two in [%d, %d]", who, n_fft, bf::kSpectrogramMinFft, bf::kSpectrogramMaxFft);
-        return -1;
-    }
+    if (!need_pow2(who, "n_fft", n_fft, bf::kSpectrogramMinFft, bf::kSpectrogramMaxFft)) return -1;
     if (!need_min(who, "n_win", n_win, 1)) return -1;
     if (n_win > n_fft) { set_error("%s: n_win = %d > n_fft = %d", who, n_win, n_fft); return -1; }
     if (!need_min(who, "hop_s", hop_s, 1) || !need_min(who, "n_bands", n_bands, 1) || !need_max(who, "n_bands", n_bands, BF_SPECTROGRAM_MAX_BANDS)) return -1;
@@ -1939,10 +1943,7 @@ int bf_enhance_device(const float* d_in, int rows, int frames, int n, int in_str
     if (tracks && !need_ptrs(who, {{d_noise, "d_noise"}, {d_prior, "d_prior"}})) return -1;
     if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "n", n, 1)) return -1;
     if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, n, "n") || !need_min(who, "in_stride", in_stride, "n", n)) return -1;
-    if (n_fft < bf::kEnhanceMinFft || n_fft > bf::kEnhanceMaxFft || (n_fft & (n_fft - 1)) != 0) {
-        set_error("%s: n_fft = %d is not a power of two in [%d, %d]", who, n_fft, bf::kEnhanceMinFft, bf::kEnhanceMaxFft);
-        return -1;
-    }
+    if (!need_pow2(who, "n_fft", n_fft, bf::kEnhanceMinFft, bf::kEnhanceMaxFft)) return -1;
     if (!need_min(who, "hop_s", hop_s, 1)) return -1;
     if (hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP) {
         set_error("%s: hop_s = %d does not divide n_fft = %d into 1 .. %d frames a sample", who, hop_s, n_fft, BF_ENHANCE_MAX_OVERLAP);
@@ -1999,10 +2000,7 @@ int bf_whiten_device(const float* d_signals, int rows, int frames, const float* 
     if (!need_ptrs(who, {{d_signals, "d_signals"}, {bins, "bins"}, {beta, "beta"}, {gain, "gain"}, {d_out, "d_out"}})) return -1;
     if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "bands", bands, 1)) return -1;
     if (!need_max(who, "bands", bands, BF_WHITEN_MAX_BANDS)) return -1;
-    if (N < bf::kWhitenMinN || N > bf::kWhitenMaxN || (N & (N - 1)) != 0) {
-        set_error("%s: N_SAMPLES = %d is not a power of two in [%d, %d]", who, N, bf::kWhitenMinN, bf::kWhitenMaxN);
-        return -1;
-    }
+    if (!need_pow2(who, "N_SAMPLES", N, bf::kWhitenMinN, bf::kWhitenMaxN)) return -1;
     const int n_bins = N / 2 + 1;
     bf::WhitenBands wb = {};
     for (int b = 0; b < bands; ++b) {

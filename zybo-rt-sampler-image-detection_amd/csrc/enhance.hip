@@ -9,16 +9,15 @@
 // Four launches on the stream.  d_work holds, behind a header of four ints, X [rows][cap][2][n_bins], P and G [rows][cap][n_bins] and
 // v [rows][cap][n_fft].
 //   enhance_analysis_kernel : a workgroup takes one (row, frame) item (the grid walks the items): one wave up to n_fft = 512, four waves
-//       above.  LDS (dynamic, 3 n_fft floats: 3 KiB at n_fft = 256, 48 KiB at 4096): re[n_fft], im[n_fft] and the twiddles, computed
-//       in double and rounded once as in whiten.hip (the error budget of tests/enhance_np.py rests on that).  The transform is the
-//       radix-2 decimation-in-time pass routine of whiten.hip.  X and P go to d_work.  Reads d_state and d_hist only.
+//       above.  LDS (dynamic, 3 n_fft floats: 3 KiB at n_fft = 256, 48 KiB at 4096): re[n_fft], im[n_fft] and the twiddles, from double.
+//       The transform is lds_fft.h's (its header states the rounding model that the error budget of tests/enhance_np.py rests on, and
+//       why the bank conflicts of the passes stay).  X and P go to d_work.  Reads d_state and d_hist only.
 //   enhance_gain_kernel : a thread per (row, bin) walks the call's frames in order: the recursion in the header's float32 operations
 //       (the build has -ffp-contract=off; the fused steps are written __fmaf_rn, the divisions __fdiv_rn), G to d_work and the
 //       observables.  The thread reads its own d_noise / d_prior element first and writes it last; nothing else touches them.  Thread 0
 //       also copies (c, count, valid) into the header of d_work, which is what the last launch reads: that launch writes d_state.
 //   enhance_synthesis_kernel : a workgroup per (row, frame) again: Y = G X staged with its Hermitian extension at the bit-reversed
-//       index, the inverse passes at n_fft complex points (as in whiten.hip: twice the arithmetic of a half-length real transform, for
-//       one pass routine and one rounding model), v to d_work.
+//       index, the inverse passes at n_fft complex points, v to d_work.
 //   enhance_overlap_kernel : a lane per output sample gathers the <= 8 frames that cover it, in ascending frame order, behind the
 //       carried partial sum where the position lies before the call's x[0].  The first workgroup of every row (the `tail`) takes the
 //       n_fft outputs that read d_ola, the row's new d_ola and its new d_hist: all three are staged in LDS (2 n_fft floats) before
@@ -27,13 +26,12 @@
 // Every value is computed by one fixed sequence of float32 operations on its own frame's samples and its own bin's state: the lane
 // count depends on n_fft alone, and the row count, the frame's index in the call and the alignment of the pointers do not enter.  The
 // bit promises of the definition rest on that.
-// Passes with a half-length under 64 read LDS at a stride of 2 * half floats within a wave (2-way to 32-way bank conflicts on the first
-// five passes); as in spectrogram.hip and whiten.hip they are not padded away.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 
 #include "das_kernels.h"
+#include "lds_fft.h"
 
 namespace bf {
 namespace {
@@ -66,38 +64,6 @@ __device__ __forceinline__ float enhance_sample(const float* __restrict__ in, co
     return in[((size_t)f * rows + r) * in_stride + (n - len) + (s - f * len)];
 }
 
-// One in-place radix-2 decimation-in-time transform over re / im (staged at the bit-reversed index), a barrier behind every pass.
-// sign = +1: exp(-2 pi i ..) (forward); -1: the conjugate twiddles (inverse, unnormalised).
-__device__ __forceinline__ void enhance_passes(float* re, float* im, const float* twc, const float* tws, int log2n, int half_n, int lane, int lanes, float sign)
-{
-    for (int p = 0; p < log2n; ++p) {
-        const int half = 1 << p, tw_shift = log2n - 1 - p;
-        for (int i = lane; i < half_n; i += lanes) {
-            const int pos = i & (half - 1);
-            const int a = ((i >> p) << (p + 1)) + pos, b = a + half;
-            const float wr = twc[pos << tw_shift], wi = sign * tws[pos << tw_shift];
-            const float br = re[b], bi = im[b], ar = re[a], ai = im[a];
-            const float tr = wr * br - wi * bi;
-            const float ti = wr * bi + wi * br;
-            re[a] = ar + tr;
-            im[a] = ai + ti;
-            re[b] = ar - tr;
-            im[b] = ai - ti;
-        }
-        __syncthreads();                        // the next pass (or the reader behind the last one) sees this pass's butterflies
-    }
-}
-
-__device__ __forceinline__ void enhance_twiddles(float* twc, float* tws, int n_fft, int lane, int lanes)
-{
-    for (int m = lane; m < (n_fft >> 1); m += lanes) {
-        double s, c;
-        sincospi((double)m * (2.0 / (double)n_fft), &s, &c);     // (the argument is exact: m / 2^k)
-        twc[m] = (float)c;
-        tws[m] = (float)-s;
-    }
-}
-
 __global__ void __launch_bounds__(256)
 enhance_analysis_kernel(const float* __restrict__ in, int rows, int n, int in_stride, int len, int S, const float* __restrict__ hist,
                         const int* __restrict__ state, const float* __restrict__ win_a, int n_fft, int log2n, int hop_s, float* __restrict__ spec,
@@ -112,7 +78,7 @@ enhance_analysis_kernel(const float* __restrict__ in, int rows, int n, int in_st
     const int H = n_fft - 1, half_n = n_fft >> 1, n_bins = half_n + 1;
     const EnhanceState st = enhance_state(state, S, hop_s);
 
-    enhance_twiddles(twc, tws, n_fft, lane, lanes);
+    fft_twiddles(twc, tws, n_fft, half_n, lane, lanes);
 
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int r = (int)(item / cap);
@@ -121,12 +87,12 @@ enhance_analysis_kernel(const float* __restrict__ in, int rows, int n, int in_st
         const long long start = ((long long)i + 1) * hop_s - st.c - n_fft;         // >= -H, and start + n_fft <= S
         for (int t = lane; t < n_fft; t += lanes) {
             const float u = win_a[t] * enhance_sample(in, hist, r, rows, n, in_stride, len, H, start + t);
-            const int rev = (int)(__brev((unsigned)t) >> (32 - log2n));
+            const int rev = fft_rev(t, log2n);
             re[rev] = u;
             im[rev] = 0.0f;
         }
         __syncthreads();                        // u is staged (also: the twiddles are there)
-        enhance_passes(re, im, twc, tws, log2n, half_n, lane, lanes, 1.0f);
+        fft_passes(re, im, twc, tws, log2n, half_n, lane, lanes, 1.0f);
         float* x = spec + (size_t)item * 2 * n_bins;
         float* pw = power + (size_t)item * n_bins;
         for (int k = lane; k < n_bins; k += lanes) {
@@ -221,7 +187,7 @@ enhance_synthesis_kernel(const int* __restrict__ state, int S, const float* __re
     const EnhanceState st = enhance_state(state, S, hop_s);
     const float inv_n = 1.0f / (float)n_fft;    // (a power of two)
 
-    enhance_twiddles(twc, tws, n_fft, lane, lanes);
+    fft_twiddles(twc, tws, n_fft, half_n, lane, lanes);
 
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int i = (int)(item % cap);
@@ -230,20 +196,10 @@ enhance_synthesis_kernel(const int* __restrict__ state, int S, const float* __re
         const float* g = gain + (size_t)item * n_bins;
         for (int k = lane; k < n_bins; k += lanes) {
             const float G = g[k];
-            const float yr = G * x[k];
-            float yi = G * x[n_bins + k];
-            if (k == 0 || k == half_n) yi = 0.0f;                // only Re Y_0 and Re Y_{n/2} enter a real signal
-            const int rev = (int)(__brev((unsigned)k) >> (32 - log2n));
-            re[rev] = yr;
-            im[rev] = yi;
-            if (k != 0 && k != half_n) {
-                const int rev2 = (int)(__brev((unsigned)(n_fft - k)) >> (32 - log2n));
-                re[rev2] = yr;
-                im[rev2] = -yi;
-            }
+            fft_stage_hermitian(re, im, k, G * x[k], G * x[n_bins + k], n_fft, half_n, log2n);
         }
         __syncthreads();                        // Y is staged (also: the twiddles are there)
-        enhance_passes(re, im, twc, tws, log2n, half_n, lane, lanes, -1.0f);
+        fft_passes(re, im, twc, tws, log2n, half_n, lane, lanes, -1.0f);
         float* v = frames + (size_t)item * n_fft;
         for (int t = lane; t < n_fft; t += lanes) v[t] = (win_s[t] * inv_n) * re[t];
         __syncthreads();                        // the next item restages re and im
@@ -329,7 +285,7 @@ long long enhance_cap(long long S, int hop_s) { return (S + hop_s - 1) / hop_s; 
 
 long long enhance_workspace(int rows, long long samples, int n_fft, int hop_s)
 {
-    if (rows < 1 || samples < 1 || samples > 0x7fffffff / 2 || n_fft < kEnhanceMinFft || n_fft > kEnhanceMaxFft || (n_fft & (n_fft - 1)) != 0 || hop_s < 1 ||
+    if (rows < 1 || samples < 1 || samples > 0x7fffffff / 2 || n_fft < kEnhanceMinFft || n_fft > kEnhanceMaxFft || fft_log2(n_fft) < 0 || hop_s < 1 ||
         hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > kEnhanceMaxOverlap)
         return -1;
     const long long slots = (long long)rows * enhance_cap(samples, hop_s);           // < 2^61
@@ -345,8 +301,7 @@ hipError_t launch_enhance(const float* d_in, int rows, int frames, int n, int in
     const int len = hop > 0 ? hop : n;
     const long long S = (long long)frames * len;
     if (enhance_workspace(rows, S, n_fft, hop_s) < 0 || out_stride < S) return hipErrorInvalidValue;
-    int log2n = 0;
-    while ((1 << log2n) < n_fft) ++log2n;
+    const int log2n = fft_log2(n_fft);
     const int n_bins = n_fft / 2 + 1;
     const long long cap = enhance_cap(S, hop_s), items = cap * rows;
     int32_t* header = reinterpret_cast<int32_t*>(d_work);
@@ -355,7 +310,7 @@ hipError_t launch_enhance(const float* d_in, int rows, int frames, int n, int in
     float* gain = power + (size_t)items * n_bins;
     float* v = gain + (size_t)items * n_bins;
     const unsigned grid = (unsigned)(items < kEnhanceMaxGrid ? items : kEnhanceMaxGrid);
-    const unsigned lanes = n_fft <= 512 ? 64 : 256;
+    const unsigned lanes = fft_lanes(n_fft);
     const size_t lds = 3 * (size_t)n_fft * sizeof(float);
 
     hipLaunchKernelGGL(enhance_analysis_kernel, dim3(grid), dim3(lanes), lds, stream, d_in, rows, n, in_stride, len, (int)S, d_hist, d_state, d_win_a, n_fft,

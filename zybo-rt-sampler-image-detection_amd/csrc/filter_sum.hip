@@ -24,6 +24,7 @@
 #include <atomic>
 
 #include "das_kernels.h"
+#include "fir_window.h"
 
 namespace bf {
 namespace {
@@ -34,19 +35,6 @@ constexpr int kMaxWaves = 16;
 constexpr int kLdsRowBytes = 32 * 1024;   // the staged rows of a workgroup
 
 std::atomic<int> g_waves{0};              // filter_sum_waves: 0 = the launch decides
-
-__device__ __forceinline__ void fs_taps4(float (&acc)[4], const float (&w)[8], const float* gm, int t0, int n_u)
-{
-    // w[4 + d] = x~[j0 - t0 + d]; output o at tap t0 + u reads x~[j0 + o - t0 - u]
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (u < n_u) {   // (wave-uniform; n_u = 4 in the main loop)
-            const float g = gm[t0 + u];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) acc[o] = __fmaf_rn(g, w[4 + o - u], acc[o]);
-        }
-    }
-}
 
 __global__ void __launch_bounds__(kMaxWaves * kLanes)
 filter_sum_kernel(const float* __restrict__ signals, const float* __restrict__ prev0, const int32_t* __restrict__ mics, const float* __restrict__ taps,
@@ -92,8 +80,8 @@ filter_sum_kernel(const float* __restrict__ signals, const float* __restrict__ p
         }
         __syncthreads();     // the row is staged; every owner is done with the quads parked in the pass before
         if (live) {
-            const float* __restrict__ gm = taps + ((size_t)b * n + m) * T;
-            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            const float* const gm[1] = {taps + ((size_t)b * n + m) * T};
+            float acc[1][4] = {{0.0f, 0.0f, 0.0f, 0.0f}};
             const float* p = s + hp + 4 * lane;
             float w[8];
             {
@@ -104,15 +92,15 @@ filter_sum_kernel(const float* __restrict__ signals, const float* __restrict__ p
             for (int q = 0; q < full; ++q) {
                 const float4 a = *reinterpret_cast<const float4*>(p - 4 * q - 4);
                 w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-                fs_taps4(acc, w, gm, 4 * q, 4);
+                fir_taps4<1>(acc, w, gm, 4 * q, 4);
                 w[4] = w[0]; w[5] = w[1]; w[6] = w[2]; w[7] = w[3];
             }
             if (rem) {
                 const float4 a = *reinterpret_cast<const float4*>(p - 4 * full - 4);
                 w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-                fs_taps4(acc, w, gm, 4 * full, rem);
+                fir_taps4<1>(acc, w, gm, 4 * full, rem);
             }
-            *reinterpret_cast<float4*>(park + (wave * kChunk + 4 * lane)) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            *reinterpret_cast<float4*>(park + (wave * kChunk + 4 * lane)) = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
         }
         __syncthreads();     // the pass's quads are parked
         if (wave == 0) {     // the owner of the workgroup's outputs

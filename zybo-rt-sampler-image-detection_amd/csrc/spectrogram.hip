@@ -6,16 +6,12 @@
 // support; out = E or scale * log10f(max(E, floor)).
 //
 //   spectrogram_kernel : a workgroup takes one (row, frame) slot (a work item; the grid walks the items): one wave up to n_fft = 512, four
-//       waves above.  LDS (dynamic, 3 n_fft floats: 1.5 KiB at n_fft = 128, 48 KiB at 4096): re[n_fft], im[n_fft], and the twiddles
-//       exp(-2 pi i m / n_fft), m < n_fft / 2, which every workgroup computes once with sincospif before it walks its items.  u is staged
-//       at the bit-reversed index, so the radix-2 decimation-in-time butterflies run in place, log2(n_fft) passes of n_fft / 2 butterflies
-//       with a barrier behind each; a butterfly is the four multiplies and six adds of the textbook, each rounded on its own (the build
-//       has -ffp-contract=off).  P overwrites re[0 .. n_fft / 2].  Then a lane owns a band and walks its support in ascending k, one
-//       multiply and one add per bin.  Every value of a frame is computed by one fixed sequence of float32 operations on the frame's own
-//       n_win samples: the workgroup size, the frame's index, the row count and the alignment of the pointers do not enter it, which is
-//       what the bit-exact promises of the definition rest on.
-//       Passes with a half-length under 64 read LDS at a stride of 2 * half floats within a wave (2-way to 32-way bank conflicts on
-//       the first five passes); they are not padded away.
+//       waves above.  LDS (dynamic, 3 n_fft floats: 1.5 KiB at n_fft = 128, 48 KiB at 4096): re[n_fft], im[n_fft], and the twiddles,
+//       from sincospif.  The transform is lds_fft.h's (its header states the rounding model that the error budget of
+//       tests/spectrogram_np.py rests on, and why the bank conflicts of the passes stay).  P overwrites re[0 .. n_fft / 2].  Then a lane
+//       owns a band and walks its support in ascending k, one multiply and one add per bin.  Every value of a frame is computed by one
+//       fixed sequence of float32 operations on the frame's own n_win samples: the workgroup size, the frame's index, the row count and
+//       the alignment of the pointers do not enter it, which is what the bit-exact promises of the definition rest on.
 //       The kernel only READS d_state, d_hist and d_len: every workgroup derives count from them.
 //   spectrogram_advance_kernel : one workgroup per row behind it on the same stream: the row's new history, staged whole in LDS before
 //       any of it is written (with L < n_win - 1 the history shifts inside itself); workgroup 0 also writes the state and (count, status).
@@ -25,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "das_kernels.h"
+#include "lds_fft.h"
 
 namespace bf {
 namespace {
@@ -61,12 +58,7 @@ spectrogram_kernel(const float* __restrict__ in, int rows, int in_stride, int le
     const int L = spectrogram_len(d_len, len);
     const int count = s0 >= -H ? spectrogram_count(s0, L, n_win, hop) : 0;
 
-    for (int m = lane; m < half_n; m += lanes) {
-        float s, c;
-        sincospif((float)m * (2.0f / (float)n_fft), &s, &c);     // (the argument is exact: m / 2^k)
-        twc[m] = c;
-        tws[m] = -s;
-    }
+    fft_twiddles_f32(twc, tws, n_fft, half_n, lane, lanes);
 
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int r = (int)(item / cap);
@@ -85,27 +77,12 @@ spectrogram_kernel(const float* __restrict__ in, int rows, int in_stride, int le
                 const long long s = sj + t;
                 u = window[t] * (s < 0 ? h[H + s] : x[s]);
             }
-            const int rev = (int)(__brev((unsigned)t) >> (32 - log2n));
+            const int rev = fft_rev(t, log2n);
             re[rev] = u;
             im[rev] = 0.0f;
         }
         __syncthreads();                        // (also: the twiddles are there)
-        for (int p = 0; p < log2n; ++p) {
-            const int half = 1 << p, tw_shift = log2n - 1 - p;
-            for (int i = lane; i < half_n; i += lanes) {
-                const int pos = i & (half - 1);
-                const int a = ((i >> p) << (p + 1)) + pos, b = a + half;
-                const float wr = twc[pos << tw_shift], wi = tws[pos << tw_shift];
-                const float br = re[b], bi = im[b], ar = re[a], ai = im[a];
-                const float tr = wr * br - wi * bi;
-                const float ti = wr * bi + wi * br;
-                re[a] = ar + tr;
-                im[a] = ai + ti;
-                re[b] = ar - tr;
-                im[b] = ai - ti;
-            }
-            __syncthreads();
-        }
+        fft_passes(re, im, twc, tws, log2n, half_n, lane, lanes, 1.0f);
         for (int k = lane; k < n_bins; k += lanes) re[k] = re[k] * re[k] + im[k] * im[k];     // P_k, each by the lane that read it
         __syncthreads();
         for (int b = lane; b < n_bands; b += lanes) {
@@ -175,9 +152,8 @@ hipError_t launch_spectrogram(const float* d_in, int rows, int in_stride, int le
                               int n_win, int n_fft, int hop, const float* d_bank, const int32_t* d_support, int n_bands, float scale, float floor_,
                               float* d_out, int out_frames, int32_t* d_count, hipStream_t stream)
 {
-    int log2n = 0;
-    while ((1 << log2n) < n_fft) ++log2n;
-    if (rows < 1 || len < 0 || in_stride < len || n_fft < kSpectrogramMinFft || n_fft > kSpectrogramMaxFft || (1 << log2n) != n_fft || n_win < 1 ||
+    const int log2n = fft_log2(n_fft);
+    if (rows < 1 || len < 0 || in_stride < len || n_fft < kSpectrogramMinFft || n_fft > kSpectrogramMaxFft || log2n < 0 || n_win < 1 ||
         n_win > n_fft || hop < 1 || n_bands < 1 || n_bands > kSpectrogramMaxBands || (d_bank == nullptr && n_bands != n_fft / 2 + 1))
         return hipErrorInvalidValue;
     const long long cap = spectrogram_capacity(len, hop);
@@ -185,8 +161,7 @@ hipError_t launch_spectrogram(const float* d_in, int rows, int in_stride, int le
     if (cap > 0) {
         const long long items = cap * rows;
         const unsigned grid = (unsigned)(items < kSpectrogramMaxGrid ? items : kSpectrogramMaxGrid);
-        const unsigned lanes = n_fft <= 512 ? 64 : 256;
-        hipLaunchKernelGGL(spectrogram_kernel, dim3(grid), dim3(lanes), 3 * (size_t)n_fft * sizeof(float), stream, d_in, rows, in_stride, len, d_len, d_hist,
+        hipLaunchKernelGGL(spectrogram_kernel, dim3(grid), dim3(fft_lanes(n_fft)), 3 * (size_t)n_fft * sizeof(float), stream, d_in, rows, in_stride, len, d_len, d_hist,
                            d_state, d_window, n_win, n_fft, log2n, hop, d_bank, d_support, n_bands, scale, floor_, d_out, out_frames, (int)cap, items);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

@@ -9,54 +9,26 @@
 //   whiten_kernel : a workgroup takes one (frame, row) item (the grid walks the items): one wave up to N = 512, four waves above.
 //       LDS (dynamic, 4.5 N + 8 floats: 4.6 KiB at N = 256, 18 KiB at N = 1024, 72 KiB at N = 4096):
 //           re[N], im[N]           the working arrays of both transforms
-//           twc[N / 2], tws[N / 2] cos and -sin of 2 pi m / N, which every workgroup computes once before it walks its items: in double
-//                                  (sincospi), rounded once to float32, so each component is within half a float32 step of the true
-//                                  value; the error budget of tests/whiten_np.py rests on that
+//           twc[N / 2], tws[N / 2] the twiddles, from double
 //           xr, xi, mag [N / 2 + 1] the kept half spectrum and |X_k|, shared by all bands of the item
 //           red[4]                 a band's power sum, one partial per wave
-//       Both transforms are the radix-2 decimation-in-time passes of spectrogram.hip (staged at the bit-reversed index, in place, log2 N
-//       passes of N / 2 butterflies with a barrier behind each; four multiplies and six adds per butterfly, each rounded on its own), the
-//       inverse with the conjugate twiddle.  The inverse runs at N complex points on the Hermitian extension of W (Y_k = W_k, Y_{N-k} =
-//       conj W_k, im Y_0 = im Y_{N/2} = 0) and its real part is the output: twice the arithmetic a real-output transform of half length
-//       would need, for one pass routine and one rounding model.
+//       Both transforms are lds_fft.h's (its header states the rounding model that the error budget of tests/whiten_np.py rests on,
+//       and why the bank conflicts of the passes stay): the inverse runs at N complex points on the Hermitian extension of W and its
+//       real part is the output.
 //       Every value of a row is computed by one fixed sequence of float32 operations on the row's own N samples and the band's own
 //       scalars: the lane count depends on N alone, the band's power sum has a fixed shape (lane-strided partials in ascending k, an
 //       xor butterfly over the wave, then the waves' partials in order), and nothing is shared between bands but X.  The bit promises
 //       of the definition rest on that.  Scaling a row by 2^e scales X, |X| (a correctly rounded sqrtf of an exactly scaled sum), the
 //       rms (an IEEE division by the bin count) and the floor exactly, so X_k / d_k keeps its bits.
-//       Passes with a half-length under 64 read LDS at a stride of 2 * half floats within a wave (2-way to 32-way bank conflicts on
-//       the first five passes), and the bit-reversed staging writes scatter the same way; as in spectrogram.hip they are not padded
-//       away: the whole call is a small fraction of the map launch it feeds (profiles/whiten_time.json).
 #include <hip/hip_runtime.h>
 
 #include "das_kernels.h"
+#include "lds_fft.h"
 
 namespace bf {
 namespace {
 
 constexpr int kWhitenMaxGrid = 2048;            // workgroups of a launch; more items than that are walked
-
-// One in-place radix-2 decimation-in-time transform over re / im (staged at the bit-reversed index), a barrier behind every pass.
-// sign = +1: exp(-2 pi i ..) (forward); -1: the conjugate twiddles (inverse, unnormalised).
-__device__ __forceinline__ void whiten_passes(float* re, float* im, const float* twc, const float* tws, int log2n, int half_n, int lane, int lanes, float sign)
-{
-    for (int p = 0; p < log2n; ++p) {
-        const int half = 1 << p, tw_shift = log2n - 1 - p;
-        for (int i = lane; i < half_n; i += lanes) {
-            const int pos = i & (half - 1);
-            const int a = ((i >> p) << (p + 1)) + pos, b = a + half;
-            const float wr = twc[pos << tw_shift], wi = sign * tws[pos << tw_shift];
-            const float br = re[b], bi = im[b], ar = re[a], ai = im[a];
-            const float tr = wr * br - wi * bi;
-            const float ti = wr * bi + wi * br;
-            re[a] = ar + tr;
-            im[a] = ai + ti;
-            re[b] = ar - tr;
-            im[b] = ai - ti;
-        }
-        __syncthreads();                        // the next pass (or the reader behind the last one) sees this pass's butterflies
-    }
-}
 
 __global__ void __launch_bounds__(256)
 whiten_kernel(const float* __restrict__ in, const float* __restrict__ window, WhitenBands bands, int n_bands, float floor_rel, float floor_abs, int n,
@@ -74,23 +46,18 @@ whiten_kernel(const float* __restrict__ in, const float* __restrict__ window, Wh
     float* red = mag + n_bins;
     const int lane = (int)threadIdx.x, lanes = (int)blockDim.x, wave = lane >> 6, waves = lanes >> 6;
 
-    for (int m = lane; m < half_n; m += lanes) {
-        double s, c;
-        sincospi((double)m * (2.0 / (double)n), &s, &c);         // (the argument is exact: m / 2^k)
-        twc[m] = (float)c;
-        tws[m] = (float)-s;
-    }
+    fft_twiddles(twc, tws, n, half_n, lane, lanes);
 
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const float* x = in + (size_t)item * n;
         for (int t = lane; t < n; t += lanes) {
             const float u = window != nullptr ? window[t] * x[t] : x[t];
-            const int rev = (int)(__brev((unsigned)t) >> (32 - log2n));
+            const int rev = fft_rev(t, log2n);
             re[rev] = u;
             im[rev] = 0.0f;
         }
         __syncthreads();                        // u is staged (also: the twiddles are there)
-        whiten_passes(re, im, twc, tws, log2n, half_n, lane, lanes, 1.0f);
+        fft_passes(re, im, twc, tws, log2n, half_n, lane, lanes, 1.0f);
         for (int k = lane; k < n_bins; k += lanes) {
             const float a = re[k], b = im[k];
             xr[k] = a;
@@ -139,18 +106,10 @@ whiten_kernel(const float* __restrict__ in, const float* __restrict__ window, Wh
                         }
                     }
                 }
-                if (k == 0 || k == half_n) wi = 0.0f;            // only Re W_0 and Re W_{N/2} enter a real signal
-                const int rev = (int)(__brev((unsigned)k) >> (32 - log2n));
-                re[rev] = wr;
-                im[rev] = wi;
-                if (k != 0 && k != half_n) {
-                    const int rev2 = (int)(__brev((unsigned)(n - k)) >> (32 - log2n));
-                    re[rev2] = wr;
-                    im[rev2] = -wi;
-                }
+                fft_stage_hermitian(re, im, k, wr, wi, n, half_n, log2n);
             }
             __syncthreads();                    // Y is staged
-            whiten_passes(re, im, twc, tws, log2n, half_n, lane, lanes, -1.0f);
+            fft_passes(re, im, twc, tws, log2n, half_n, lane, lanes, -1.0f);
             const float scale = bands.gain[b] * (1.0f / (float)n);           // (1 / N is a power of two: gain / N exactly)
             for (int j = lane; j < n; j += lanes) o[j] = scale * re[j];
             __syncthreads();                    // the next band, or the next item, restages re and im
@@ -163,9 +122,8 @@ whiten_kernel(const float* __restrict__ in, const float* __restrict__ window, Wh
 hipError_t launch_whiten(const float* d_signals, long long items, int n_samples, const float* d_window, const WhitenBands& bands, int n_bands, float floor_rel,
                          float floor_abs, float* d_out, hipStream_t stream)
 {
-    int log2n = 0;
-    while ((1 << log2n) < n_samples) ++log2n;
-    if (items < 1 || n_samples < kWhitenMinN || n_samples > kWhitenMaxN || (1 << log2n) != n_samples || n_bands < 1 || n_bands > kWhitenMaxBands)
+    const int log2n = fft_log2(n_samples);
+    if (items < 1 || n_samples < kWhitenMinN || n_samples > kWhitenMaxN || log2n < 0 || n_bands < 1 || n_bands > kWhitenMaxBands)
         return hipErrorInvalidValue;
     for (int b = 0; b < n_bands; ++b)
         if (bands.lo[b] < 0 || bands.hi[b] > n_samples / 2 + 1 || bands.lo[b] >= bands.hi[b]) return hipErrorInvalidValue;
@@ -175,8 +133,7 @@ hipError_t launch_whiten(const float* d_signals, long long items, int n_samples,
         if (e != hipSuccess) return e;
     }
     const unsigned grid = (unsigned)(items < kWhitenMaxGrid ? items : kWhitenMaxGrid);
-    const unsigned lanes = n_samples <= 512 ? 64 : 256;
-    hipLaunchKernelGGL(whiten_kernel, dim3(grid), dim3(lanes), lds, stream, d_signals, d_window, bands, n_bands, floor_rel, floor_abs, n_samples, log2n, d_out,
+    hipLaunchKernelGGL(whiten_kernel, dim3(grid), dim3(fft_lanes(n_samples)), lds, stream, d_signals, d_window, bands, n_bands, floor_rel, floor_abs, n_samples, log2n, d_out,
                        items);
     return hipGetLastError();
 }
