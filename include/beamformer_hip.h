@@ -1206,6 +1206,93 @@ int bf_enhance_device(const float *d_in, int rows, int frames, int n, int in_str
                       float *d_work, float *d_out, int out_stride,
                       float *d_power_out, float *d_gain_out, int *d_count, void *stream);
 
+/* ---- multichannel post-filter gains: the Wiener gain of a steered beam read from the microphones' coherence, on the device ----
+ * bf_enhance_device on its own sees only the beam and has to guess the noise from the beam's history.  The microphones carry what one
+ * channel lacks: behind the steering to the look direction the target is coherent across them and sensor or diffuse noise is not.  The
+ * multichannel post-filter (Zelinski 1988; Simmer's variant; Simmer, Bitzer & Marro, "Post-filtering techniques", 2001) reads the Wiener
+ * gain from that, per frame and bin, with no noise history, no learning stretch and no stationarity assumption.  With n microphones the
+ * cross-spectral sum over all n (n - 1) / 2 pairs is  sum_{i<j} Re(Z_i conj Z_j) = (|sum Z_i|^2 - sum |Z_i|^2) / 2 : no pair loop.  This
+ * call makes the gains bf_enhance_device takes as d_gain_in, on its frame grid, for the slots a tracker names, without a host round trip.
+ * The configured sizes (bf_configure) and the loaded tables play no part.
+ * d_signals : HIP device pointer, float32 [frames][m_total][n_samples].
+ * adaptive_array, n : as bf_filter_sum_device (HOST array of the n active rows r_m, cached on the device; a new array synchronises the
+ *             device once).  2 <= n <= BF_MVDR_MAX_MICS.
+ * d_tau, dirs, d_offsets, slots, offset_per_dir : as bf_lcmv_design_device (float64 [dirs][n], microphone m LEADS by tau[d][m]; ONE row
+ *             of `slots` int32 entries).  A slot is a source iff its entry is >= 0, a multiple of offset_per_dir and entry /
+ *             offset_per_dir < dirs.
+ * d_hist    : HIP device pointer, float32 [n][H], H = n_fft - 1 + lag, read and written: the microphones' samples before x[0].
+ * d_num, d_den : HIP device pointers, float32 [slots][K], K = n_fft / 2 + 1, read and written: the smoothed numerator N and denominator D.
+ * d_state   : HIP device pointer, int32 [2 + slots] = (c, 0, seen_0 .. seen_{slots-1}), read and written.  The caller zeroes d_hist and
+ *             d_state at the start of a stream (d_num and d_den are not read before a slot's first finite frame).
+ * d_window  : HIP DEVICE pointer, float32 [n_fft]: the analysis window (the Enhancer's win_a).
+ * d_work    : HIP device pointer, bf_postfilter_workspace(slots, S, n_fft, hop_s) floats, written; its contents carry nothing.
+ * Definition (builder-defined; the reference has no post-filter).  Let len = hop > 0 ? hop : n_samples, S = frames * len,
+ * cap = (hop_s - 1 + S) / hop_s.
+ *   Stream, per microphone m (bf_enhance_device's convention, a row of the frames as one stream):
+ *            x_m[s] = d_signals[s / len][r_m][n_samples - len + s % len]     for 0 <= s < S
+ *            x_m[s] = d_hist[m][H + s]                                       for -H <= s < 0
+ *   State.  0 <= c < hop_s: the stream samples since the last frame end.  seen_b in {0, 1}: whether slot b has had a finite frame since
+ *     it last became a source.  d_state[1] is reserved and written 0.
+ *   Frames.  count = (c + S) / hop_s (the Enhancer's formulas).  Frame i < count ends at e_i = (i + 1) * hop_s - c - 1 - lag and covers
+ *     x[e_i - (n_fft - 1) .. e_i].  lag >= 0 reads the microphones that many samples late, so that the grid lines up with a beam that is
+ *     itself late by lag (a FilterSumListener's (T - 1) / 2); lag = 0 is for delay-and-sum beams.
+ *   Analysis, float32:  u[t] = d_window[t] * x_m[e_i - (n_fft - 1) + t], one multiply;  X_{m,k} = sum_t u[t] exp(-2 pi i k t / n_fft);
+ *     q_{m,k} = re * re + im * im.
+ *   Steering, computed per call (a moving tracker slot costs device memory only).  For a source slot b with direction d:
+ *     sincospi(2.0 * k * tau[d][m] / n_fft) in double gives a_{b,m,k} = (cos, -sin), rounded once to float32: the conjugate of the
+ *     designers' c[m]; it aligns a microphone that LEADS by tau.  d_steer float32 [slots][n][K][2] holds them (zeros for a slot that is
+ *     no source): an output the caller may inspect, and the analysis launch's input.  Z = a X: four multiplies and two adds.
+ *   Per (slot, frame, bin), float32:  Y = sum_m Z_m, Q = sum_m q_m; the order of the microphone sums is fixed by (n, n_fft) alone and is
+ *     not part of the definition.   |Y|^2 = re * re + im * im;
+ *       num = (|Y|^2 - Q) / (n (n - 1))           -- twice the mean over the pairs of Re(Z_i conj Z_j), halved by the pair count's 2
+ *       den = Q / n             for den_mode 0    (Zelinski: the microphones' mean power)
+ *       den = |Y|^2 / n^2       for den_mode 1    (Simmer: the beam's power)
+ *   Recursion, per (slot, bin) over the call's frames in ascending order, every operation one float32 operation in the order written,
+ *     the division IEEE-rounded, fmaf with one rounding, max(a, b) = a < b ? b : a and min(a, b) = a > b ? b : a.  A frame is finite for
+ *     slot b iff num and den are finite in every one of its K bins.
+ *       if the frame is not finite for the slot:  G = NaN in every bin; N, D and seen_b stay as they were
+ *       else if seen_b == 0:                      N = num; D = den; seen_b = 1
+ *       else:                                     N = fmaf(beta, N - num, num); D = fmaf(beta, D - den, den)
+ *       G = D > 0 ? min(max(max(N, 0) / D, g_min), 1) : g_min
+ *     A slot that is no source gets G = 0.0f in every frame slot of the call, zeros in the observables, d_status[b] = 1 and seen_b' = 0;
+ *     its d_num / d_den are left alone, and when it becomes a source again it starts fresh.  A source slot gets d_status[b] = 0.
+ *   Outputs.  d_gains float32 [slots][cap][K], exactly d_gain_in's layout for rows = slots: G of the frames i < count, 0.0f in the slots
+ *     count <= i < cap.  d_num_out and d_den_out, the same shape, either may be NULL: the raw num and den.  d_count int32 [2] =
+ *     (count, status).  A state with c outside [0, hop_s) or a seen outside {0, 1} gives status = 1, count = 0 and zeros in d_gains and the
+ *     observables; d_hist, d_num, d_den and d_state are left as they were.  Otherwise status = 0.
+ *   New state.  c' = (c + S) % hop_s; d_hist' = the last H samples of d_hist || x[0 .. S).
+ *   The transform is bf_enhance_device's (radix-2, twiddles rounded once from double); its rounding is not part of the definition
+ *     (tests/postfilter_np.py derives the tolerance), these promises are: a frame's gains depend only on its own n_fft samples of the n
+ *     rows, the window, the steering, the scalars and the carried N and D -- not on m_total, on which rows of d_signals the microphones
+ *     occupy, on `slots` (slots behind the last change nothing), on the frame's index, on the alignment of any pointer, or on how the
+ *     stream was cut into calls.  Two calls on F1 and F - F1 windows, the second with the first's state, give one call's outputs and
+ *     state bit for bit.  All-zero rows give G = g_min and finite state.  A non-finite sample makes NaN only the gains of the frames
+ *     that cover it and leaves d_num and d_den finite.
+ * stream    : hipStream_t (0 = null stream).  Enqueue only: four launches -- steering, analysis + reduce (a workgroup per frame walks
+ *             the microphones: four waves with a microphone each up to n_fft = 512, one microphone per workgroup above), the recursion
+ *             (a thread per (slot, bin), which reads and then writes its own d_num / d_den element), and the carry, which alone writes
+ *             d_hist, d_state and d_count; no allocation after the first call (the cached adaptive array), no synchronisation unless the
+ *             adaptive array changed, no atomics on floats; graph-capturable, and a replay advances the stream like any other call.
+ * Returns 0, or -1 (bf_last_error names the value; nothing enqueued) for: a null pointer other than d_num_out and d_den_out; frames or
+ * n_samples < 1; hop < 0 or hop > n_samples; n < 2 or n > BF_MVDR_MAX_MICS; a row outside [0, m_total); slots < 1 or slots >
+ * BF_POSTFILTER_MAX_SLOTS; dirs or offset_per_dir < 1; n_fft not a power of two in [32, 4096]; hop_s < 1, not a divisor of n_fft, or
+ * n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP; lag < 0 or lag > n_fft; den_mode not 0 or 1; beta not finite or outside [0, 1); g_min not finite
+ * or outside [0, 1]; S > INT_MAX / 2; a written range (d_gains, d_num_out, d_den_out, d_steer, d_work, d_status, d_count, d_hist, d_num,
+ * d_den, d_state; each from its first element to the last one touched) sharing a byte with a read range (d_signals, d_tau, d_offsets,
+ * d_window) or with another written one; no GPU.  All arguments are checked before device bring-up.
+ * bf_postfilter_workspace: the floats of d_work for a call on `samples` stream samples, 16 + slots * cap * (1 + 2 * K); -1 for slots
+ * outside 1 .. BF_POSTFILTER_MAX_SLOTS, samples < 1 or > INT_MAX / 2, or n_fft / hop_s outside the rules above.  No GPU needed. */
+#define BF_POSTFILTER_MAX_SLOTS 8          /* = BF_LCMV_MAX_SOURCES */
+long long bf_postfilter_workspace(int slots, long long samples, int n_fft, int hop_s);
+int bf_postfilter_device(const float *d_signals, int m_total, int frames, int n_samples, int hop,
+                         const int *adaptive_array, int n,
+                         const double *d_tau, int dirs, const int *d_offsets, int slots, int offset_per_dir,
+                         float *d_hist, float *d_num, float *d_den, int *d_state,
+                         const float *d_window, int n_fft, int hop_s, int lag,
+                         int den_mode, float beta, float g_min,
+                         float *d_work, float *d_steer,
+                         float *d_gains, float *d_num_out, float *d_den_out, int *d_status, int *d_count, void *stream);
+
 /* ---- ingest: FPGA protocol-v2 datagrams -> the mic-major float32 frame the beamformers read (PC/src/receiver.c:94-151,
  * `receive_and_write_to_buffer`).  `packets` holds N_SAMPLES datagrams back to back, each
  * { u16 frequency; i8 n_arrays; i8 protocol_ver; i32 counter; i32 stream[N_MICROPHONES]; } (receiver.h:51-59).

@@ -1988,6 +1988,71 @@ int bf_enhance_device(const float* d_in, int rows, int frames, int n, int in_str
                                      a_noise, g0, g1, g_min, n_init, d_work, d_out, out_stride, d_power_out, d_gain_out, d_count, as_stream(stream)));
 }
 
+// ---------------------------------------------------------------- multichannel post-filter gains: the microphones' coherence behind the steering
+
+long long bf_postfilter_workspace(int slots, long long samples, int n_fft, int hop_s) { return bf::postfilter_workspace(slots, samples, n_fft, hop_s); }
+
+int bf_postfilter_device(const float* d_signals, int m_total, int frames, int n_samples, int hop, const int* adaptive_array, int n, const double* d_tau, int dirs,
+                         const int* d_offsets, int slots, int offset_per_dir, float* d_hist, float* d_num, float* d_den, int* d_state, const float* d_window,
+                         int n_fft, int hop_s, int lag, int den_mode, float beta, float g_min, float* d_work, float* d_steer, float* d_gains, float* d_num_out,
+                         float* d_den_out, int* d_status, int* d_count, void* stream)
+{
+    static const char* who = "bf_postfilter_device";
+    static_assert(BF_POSTFILTER_MAX_SLOTS == bf::kPostfilterMaxSlots && BF_POSTFILTER_MAX_SLOTS == BF_LCMV_MAX_SOURCES, "the header's limit is the kernel's");
+    constexpr int kMaxStream = std::numeric_limits<int>::max() / 2;
+    Entered in;
+    if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_tau, "d_tau"}, {d_offsets, "d_offsets"}, {d_hist, "d_hist"},
+                         {d_num, "d_num"}, {d_den, "d_den"}, {d_state, "d_state"}, {d_window, "d_window"}, {d_work, "d_work"}, {d_steer, "d_steer"},
+                         {d_gains, "d_gains"}, {d_status, "d_status"}, {d_count, "d_count"}}))
+        return -1;
+    if (!need_min(who, "frames", frames, 1) || !need_min(who, "n_samples", n_samples, 1)) return -1;
+    if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, n_samples, "n_samples")) return -1;
+    if (!need_min(who, "n", n, 2) || !need_max(who, "n", n, BF_MVDR_MAX_MICS) || !need_rows(who, adaptive_array, n, m_total)) return -1;
+    if (!need_min(who, "slots", slots, 1) || !need_max(who, "slots", slots, BF_POSTFILTER_MAX_SLOTS)) return -1;
+    if (!need_min(who, "dirs", dirs, 1) || !need_min(who, "offset_per_dir", offset_per_dir, 1)) return -1;
+    if (!need_pow2(who, "n_fft", n_fft, bf::kEnhanceMinFft, bf::kEnhanceMaxFft)) return -1;
+    if (!need_min(who, "hop_s", hop_s, 1)) return -1;
+    if (hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP) {
+        set_error("%s: hop_s = %d does not divide n_fft = %d into 1 .. %d frames a sample", who, hop_s, n_fft, BF_ENHANCE_MAX_OVERLAP);
+        return -1;
+    }
+    if (!need_min(who, "lag", lag, 0) || !need_max(who, "lag", lag, n_fft)) return -1;
+    if (den_mode != 0 && den_mode != 1) { set_error("%s: den_mode = %d is not 0 (the microphones' mean power) or 1 (the beam's power)", who, den_mode); return -1; }
+    if (!need_finite(who, "beta", beta, FINITE_GE0) || !need_finite(who, "g_min", g_min, FINITE_GE0)) return -1;
+    if (beta >= 1.0f) { set_error("%s: beta = %g >= 1", who, (double)beta); return -1; }
+    if (g_min > 1.0f) { set_error("%s: g_min = %g > 1", who, (double)g_min); return -1; }
+    const int len = hop > 0 ? hop : n_samples;
+    const long long S = (long long)frames * len;
+    if (S > kMaxStream) { set_error("%s: frames * %s = %lld > %d", who, hop > 0 ? "hop" : "n_samples", S, kMaxStream); return -1; }
+    const long long work = bf::postfilter_workspace(slots, S, n_fft, hop_s);
+    if (work < 0) { set_error("%s: no workspace for slots = %d, S = %lld, n_fft = %d, hop_s = %d", who, slots, S, n_fft, hop_s); return -1; }
+    // every span runs from its first element to the last one touched
+    const u64 n_bins = (u64)n_fft / 2 + 1, cap = ((u64)S + hop_s - 1) / hop_s, H = (u64)n_fft - 1 + lag;
+    const u64 cells = sat_mul(sat_mul((u64)slots * cap, n_bins), sizeof(float)), per_bin = (u64)slots * n_bins * sizeof(float);
+    if (!need_disjoint(who, {{d_gains, cells, "d_gains"},
+                             {d_num_out, cells, "d_num_out"},
+                             {d_den_out, cells, "d_den_out"},
+                             {d_steer, (u64)slots * n * n_bins * 2 * sizeof(float), "d_steer"},
+                             {d_work, sat_mul((u64)work, sizeof(float)), "d_work"},
+                             {d_status, (u64)slots * sizeof(int), "d_status"},
+                             {d_count, 2 * sizeof(int), "d_count"},
+                             {d_hist, (u64)n * H * sizeof(float), "d_hist"},
+                             {d_num, per_bin, "d_num"},
+                             {d_den, per_bin, "d_den"},
+                             {d_state, (2 + (u64)slots) * sizeof(int), "d_state"},
+                             {d_signals, sat_mul(sat_mul(sat_mul((u64)frames, (u64)m_total), (u64)n_samples), sizeof(float)), "d_signals"},
+                             {d_tau, sat_mul(sat_mul((u64)dirs, (u64)n), sizeof(double)), "d_tau"},
+                             {d_offsets, (u64)slots * sizeof(int), "d_offsets"},
+                             {d_window, (u64)n_fft * sizeof(float), "d_window"}}, 11))   // eleven written ranges (the carried state among them), four read
+        return -1;
+    if (!ensure_device()) return -1;
+    int max_row = 0;
+    if (!upload_mics(adaptive_array, n, &max_row)) return -1;
+    return HIP_RC(bf::launch_postfilter(d_signals, m_total, frames, n_samples, hop, in.s.d_mics.p, n, d_tau, dirs, d_offsets, slots, offset_per_dir, d_hist, d_num,
+                                        d_den, d_state, d_window, n_fft, hop_s, lag, den_mode, beta, g_min, d_work, d_steer, d_gains, d_num_out, d_den_out, d_status,
+                                        d_count, as_stream(stream)));
+}
+
 // ---------------------------------------------------------------- phase-transform (PHAT) frames: every in-band bin weighted by |X_k|^-beta
 
 int bf_whiten_device(const float* d_signals, int rows, int frames, const float* d_window, const int* bins, const float* beta, const float* gain, int bands,

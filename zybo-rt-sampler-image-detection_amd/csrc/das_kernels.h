@@ -314,6 +314,21 @@ hipError_t launch_enhance(const float* d_in, int rows, int frames, int n, int in
                           float g0, float g1, float g_min, int n_init, float* d_work, float* d_out, int out_stride, float* d_power_out, float* d_gain_out,
                           int32_t* d_count, hipStream_t stream);
 
+// bf_postfilter_device (postfilter.hip): the multichannel (Zelinski / Simmer) post-filter gains of up to kPostfilterMaxSlots look directions,
+// on bf_enhance_device's frame grid, from the n microphone rows d_mics of d_signals float32 [frames][m_total][n_samples] read as one stream
+// each (the last hop, or n_samples, samples of every window behind d_hist float32 [n][n_fft - 1 + lag]).  d_offsets int32 [slots] names the
+// directions (launch_lcmv_design's slot rule over d_tau float64 [dirs][n]); d_steer float32 [slots][n][n_fft / 2 + 1][2] is written per call.
+// d_num / d_den float32 [slots][n_fft / 2 + 1] and d_state int32 [2 + slots] carry between calls; d_gains (and d_num_out / d_den_out, null:
+// not wanted) float32 [slots][cap][n_fft / 2 + 1] as launch_enhance's d_gain_in; d_status int32 [slots]; d_count int32 [2] = (count, status).
+// Four launches: steering, analysis + reduce, the recursion, and the carry that alone writes the history and the state.
+// d_work: postfilter_workspace floats.
+constexpr int kPostfilterMaxSlots = 8;
+long long postfilter_workspace(int slots, long long samples, int n_fft, int hop_s);  // -1 on bad arguments
+hipError_t launch_postfilter(const float* d_signals, int m_total, int frames, int n_samples, int hop, const int32_t* d_mics, int n, const double* d_tau, int dirs,
+                             const int32_t* d_offsets, int slots, int offset_per_dir, float* d_hist, float* d_num, float* d_den, int32_t* d_state,
+                             const float* d_window, int n_fft, int hop_s, int lag, int den_mode, float beta, float g_min, float* d_work, float* d_steer,
+                             float* d_gains, float* d_num_out, float* d_den_out, int32_t* d_status, int32_t* d_count, hipStream_t stream);
+
 // frequency-domain beamformers (freq_kernels.hip): steering phasors, DFT of the selected bins, and the MFMA complex GEMM
 // with its three epilogues (phase-steer DAS power, covariance, MVDR quadratic form) plus the per-bin Cholesky inverse.
 hipError_t launch_fd_steering(const double* d_tau, const double* d_freq, int n_dirs, int n_mics, int n_bins, float* d_are, float* d_aim, hipStream_t stream);

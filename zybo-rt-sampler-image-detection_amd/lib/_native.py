@@ -153,6 +153,10 @@ _sig("bf_enhance_workspace", C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_i
 _sig("bf_enhance_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("bf_postfilter_workspace", C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_int)
+_sig("bf_postfilter_device", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, IP, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("bf_plan_conv2d", C.c_int, *([C.c_int] * 22 + [C.POINTER(C.c_longlong)]))
 _sig("bf_last_conv2d_plan", C.c_int, C.POINTER(C.c_longlong))
 _sig("bf_plan_das", C.c_int,C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))

@@ -93,6 +93,12 @@ class FusedPipeline:
         BeamFeatures take it from there."""
         return en.push(out)
 
+    def postfilter(self, frames, out, offsets, pf, en):
+        """The frame batch [F, M_total, N_SAMPLES], listen's beams of it [F, B, N_SAMPLES] and the one row of B slot offsets they were
+        steered by -> pf.push (a postfilter.SpatialPostFilter in front of an enhance.Enhancer with rows = B): the beams with the gains
+        the microphones' coherence gives every (frame, bin), instead of the Enhancer's own noise tracker (clean, count, status)."""
+        return pf.push(en, frames, out, offsets)
+
     def whiten(self, frames, whitener):
         """A frame batch [F, R, N_SAMPLES] -> whitener.frames (a whiten.Whitener): [K, F, R, N_SAMPLES], every in-band bin of every row
         at unit magnitude (the phase transform), for maps and peaks; listen on the raw frames at the offsets those maps give."""
