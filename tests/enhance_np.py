@@ -22,43 +22,16 @@ import functools
 
 import numpy as np
 
-from stft_np import EPS, ETA, two_sided, windowed
+from stft_np import EPS, ETA, advance, analysis, frame_grid_ok, frame_starts, new_history, stream, two_sided   # (the tests reach the stream's and the grid's here)
 
 FLT_MIN = float(np.finfo(np.float32).tiny)
 FLT_MAX = float(np.finfo(np.float32).max)
-MAX_OVERLAP = 8
-
-
-# ------------------------------------------------------------------ integers
-
-def advance(c, S, hop_s):
-    """(count, c', cap) of a call on S samples with c samples since the last frame end."""
-    return (c + S) // hop_s, (c + S) % hop_s, (hop_s - 1 + S) // hop_s
-
-
-def frame_starts(c, S, n_fft, hop_s):
-    """Start (relative to x[0]) of every frame the call completes: frame i ends at (i + 1) hop_s - c - 1."""
-    count = (c + S) // hop_s
-    return [(i + 1) * hop_s - c - n_fft for i in range(count)]
 
 
 def workspace(rows, samples, n_fft, hop_s):
-    if rows < 1 or samples < 1 or samples > (2 ** 31 - 1) // 2 or n_fft < 32 or n_fft > 4096 or n_fft & (n_fft - 1) or hop_s < 1 or n_fft % hop_s or \
-            n_fft // hop_s > MAX_OVERLAP:
+    if rows < 1 or not frame_grid_ok(samples, n_fft, hop_s):
         return -1
-    return 4 + rows * ((hop_s - 1 + samples) // hop_s) * (4 * (n_fft // 2 + 1) + n_fft)
-
-
-def stream(windows, n, hop):
-    """windows float32 [F, R, stride >= n] -> x float32 [R, S]: the last len = hop or n samples of every window."""
-    length = hop if hop > 0 else n
-    w = np.asarray(windows, dtype=np.float32)
-    return np.ascontiguousarray(np.concatenate([w[f, :, n - length:n] for f in range(w.shape[0])], axis=1))
-
-
-def new_history(hist, x):
-    H = hist.shape[1]
-    return np.ascontiguousarray(np.concatenate([hist, x], axis=1)[:, x.shape[1]:x.shape[1] + H]) if H else hist.copy()
+    return 4 + rows * advance(0, samples, hop_s)[2] * (4 * (n_fft // 2 + 1) + n_fft)
 
 
 # ------------------------------------------------------------------ float32, as defined (u = win_a * x: stft_np.windowed)
@@ -114,17 +87,6 @@ def gains(P, lam, prior, seen, alpha=0.98, a_noise=0.9, g0=1.5, g1=5.0, g_min=0.
 
 
 # ------------------------------------------------------------------ the call in float64, with its tolerance
-
-def analysis(x, hist, c, win_a, hop_s):
-    """-> (u float32 [R, count, n_fft], X complex128 [R, count, B], starts): the call's frames of hist || x."""
-    n_fft = win_a.shape[0]
-    H = n_fft - 1
-    ext = np.concatenate([np.asarray(hist, np.float32), np.asarray(x, np.float32)], axis=1)
-    starts = frame_starts(c, x.shape[1], n_fft, hop_s)
-    fr = np.stack([ext[:, H + s:H + s + n_fft] for s in starts], axis=1) if starts else np.zeros((x.shape[0], 0, n_fft), np.float32)
-    u = windowed(fr, win_a)
-    return u, np.fft.rfft(u.astype(np.float64), axis=-1), starts
-
 
 def synthesis_bound(u, X, G, win_s, v):
     """dv [R, count, n_fft]: the tolerance of every frame's v (module docstring)."""

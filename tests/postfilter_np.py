@@ -30,26 +30,20 @@ import functools
 
 import numpy as np
 
-from enhance_np import advance, db, fmaf, new_history
-from stft_np import EPS, ETA, windowed
+import stft_np
+from enhance_np import db, fmaf
+from stft_np import EPS, ETA, advance, analysis, frame_grid_ok, frame_starts, new_history   # (the tests reach the stream's and the grid's here)
 
 MAX_SLOTS = 8
-MAX_OVERLAP = 8
 HEADER = 16
 
 
 # ------------------------------------------------------------------ integers
 
-def frame_starts(c, S, n_fft, hop_s, lag):
-    """Start (relative to x[0]) of every frame the call completes: frame i ends at (i + 1) hop_s - c - 1 - lag."""
-    return [(i + 1) * hop_s - c - lag - n_fft for i in range((c + S) // hop_s)]
-
-
 def workspace(slots, samples, n_fft, hop_s):
-    if slots < 1 or slots > MAX_SLOTS or samples < 1 or samples > (2 ** 31 - 1) // 2 or n_fft < 32 or n_fft > 4096 or n_fft & (n_fft - 1) or hop_s < 1 or \
-            n_fft % hop_s or n_fft // hop_s > MAX_OVERLAP:
+    if slots < 1 or slots > MAX_SLOTS or not frame_grid_ok(samples, n_fft, hop_s):
         return -1
-    return HEADER + slots * ((hop_s - 1 + samples) // hop_s) * (1 + 2 * (n_fft // 2 + 1))
+    return HEADER + slots * advance(0, samples, hop_s)[2] * (1 + 2 * (n_fft // 2 + 1))
 
 
 def slot_directions(offsets, offset_per_dir, dirs):
@@ -59,9 +53,7 @@ def slot_directions(offsets, offset_per_dir, dirs):
 
 def stream(frames, mics, hop):
     """frames float32 [F, M_total, N] -> x float32 [n, S]: the last len = hop or N samples of every window of the rows `mics`."""
-    w = np.asarray(frames, dtype=np.float32)
-    length = hop if hop > 0 else w.shape[2]
-    return np.ascontiguousarray(np.concatenate([w[f][np.asarray(mics), w.shape[2] - length:] for f in range(w.shape[0])], axis=1))
+    return stft_np.stream(frames, np.shape(frames)[2], hop, rows=mics)
 
 
 # ------------------------------------------------------------------ as defined
@@ -80,17 +72,6 @@ def steering(tau, dirs, n_fft):
         a[b, :, :, 0] = np.cos(np.pi * arg)
         a[b, :, :, 1] = -np.sin(np.pi * arg)
     return a
-
-
-def analysis(x, hist, c, window, hop_s, lag):
-    """-> (u float32 [n, count, n_fft], X complex128 [n, count, K], starts): the call's frames of hist || x, H = n_fft - 1 + lag."""
-    n_fft = window.shape[0]
-    H = n_fft - 1 + lag
-    ext = np.concatenate([np.asarray(hist, np.float32), np.asarray(x, np.float32)], axis=1)
-    starts = frame_starts(c, x.shape[1], n_fft, hop_s, lag)
-    fr = np.stack([ext[:, H + s:H + s + n_fft] for s in starts], axis=1) if starts else np.zeros((x.shape[0], 0, n_fft), np.float32)
-    u = windowed(fr, window)
-    return u, np.fft.rfft(u.astype(np.float64), axis=-1), starts
 
 
 def raw(X, a, den_mode):

@@ -22,6 +22,7 @@
 
 #include "../../include/beamformer_hip.h"
 #include "das_kernels.h"
+#include "stream_grid.h"
 #include "sweep_order.h"
 
 namespace {
@@ -299,6 +300,25 @@ bool need_fir_window(const char* who, int n_taps, int hop, int N, const char* su
     if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, N)) return false;
     if (hop > 0 && n_taps - 1 > hop) {
         set_error("%s: %s n_taps - 1 = %d samples of history but hop = %d (continuous mode wants n_taps - 1 <= hop)", who, subject, n_taps - 1, hop);
+        return false;
+    }
+    return true;
+}
+
+// The stream a call's windows add to (stream_grid.h); `window`: what the call names its window length.
+bool need_stream_len(const char* who, const bf::StreamLen& sl, int hop, const char* window)
+{
+    if (!sl.fits) { set_error("%s: frames * %s = %lld > %d", who, hop > 0 ? "hop" : window, sl.S, bf::kMaxStream); return false; }
+    return true;
+}
+
+// The STFT frame grid (stream_grid.h).
+bool need_frame_grid(const char* who, int n_fft, int hop_s)
+{
+    static_assert(BF_ENHANCE_MAX_OVERLAP == bf::kEnhanceMaxOverlap, "the header's limit is the kernel's");
+    if (!need_pow2(who, "n_fft", n_fft, bf::kEnhanceMinFft, bf::kEnhanceMaxFft) || !need_min(who, "hop_s", hop_s, 1)) return false;
+    if (hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP) {
+        set_error("%s: hop_s = %d does not divide n_fft = %d into 1 .. %d frames a sample", who, hop_s, n_fft, BF_ENHANCE_MAX_OVERLAP);
         return false;
     }
     return true;
@@ -1841,7 +1861,7 @@ int bf_resample_device(const float* d_in, int rows, int frames, int n, int in_st
 {
     static const char* who = "bf_resample_device";
     static_assert(BF_RESAMPLE_MAX_PHASES == bf::kResampleMaxPhases && BF_RESAMPLE_MAX_TAPS == bf::kResampleMaxTaps, "the header's limits are the kernel's");
-    constexpr int kMaxTable = 1 << 20, kMaxStream = std::numeric_limits<int>::max() / 2;
+    constexpr int kMaxTable = 1 << 20;
     Entered in;
     if (!need_ptrs(who, {{d_in, "d_in"}, {d_taps, "d_taps"}, {d_state, "d_state"}, {d_count, "d_count"}})) return -1;
     if (!d_out && !d_pcm) { set_error("%s: d_out and d_pcm are both null", who); return -1; }
@@ -1852,14 +1872,14 @@ int bf_resample_device(const float* d_in, int rows, int frames, int n, int in_st
     if (up * n_taps > kMaxTable) { set_error("%s: up * n_taps = %d > %d", who, up * n_taps, kMaxTable); return -1; }
     if (down > 64LL * up) { set_error("%s: down = %d > 64 * up = %d", who, down, 64 * up); return -1; }
     if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, n, "n") || !need_min(who, "in_stride", in_stride, "n", n)) return -1;
-    const int len = hop > 0 ? hop : n;
-    if (n_taps - 1 > len) {
+    const bf::StreamLen sl = bf::stream_len(frames, hop, n);
+    const long long S = sl.S;
+    if (n_taps - 1 > sl.len) {
         set_error("%s: the filter needs n_taps - 1 = %d samples of history but a window adds %d to the stream (the history must be stream samples)", who,
-                  n_taps - 1, len);
+                  n_taps - 1, sl.len);
         return -1;
     }
-    const long long S = (long long)frames * len;
-    if (S > kMaxStream) { set_error("%s: frames * %s = %lld > %d", who, hop > 0 ? "hop" : "n", S, kMaxStream); return -1; }
+    if (!need_stream_len(who, sl, hop, "n")) return -1;
     const long long cap = bf::resample_capacity(S, up, down);
     if (cap > std::numeric_limits<int>::max()) { set_error("%s: cap = %lld does not fit an int", who, cap); return -1; }
     if (d_out && !need_min(who, "out_stride", out_stride, "cap", (int)cap)) return -1;
@@ -1933,8 +1953,6 @@ int bf_enhance_device(const float* d_in, int rows, int frames, int n, int in_str
                       void* stream)
 {
     static const char* who = "bf_enhance_device";
-    static_assert(BF_ENHANCE_MAX_OVERLAP == bf::kEnhanceMaxOverlap, "the header's limit is the kernel's");
-    constexpr int kMaxStream = std::numeric_limits<int>::max() / 2;
     Entered in;
     if (!need_ptrs(who, {{d_in, "d_in"}, {d_hist, "d_hist"}, {d_ola, "d_ola"}, {d_state, "d_state"}, {d_win_a, "d_win_a"}, {d_win_s, "d_win_s"},
                          {d_work, "d_work"}, {d_out, "d_out"}, {d_count, "d_count"}}))
@@ -1943,15 +1961,9 @@ int bf_enhance_device(const float* d_in, int rows, int frames, int n, int in_str
     if (tracks && !need_ptrs(who, {{d_noise, "d_noise"}, {d_prior, "d_prior"}})) return -1;
     if (!need_min(who, "rows", rows, 1) || !need_min(who, "frames", frames, 1) || !need_min(who, "n", n, 1)) return -1;
     if (!need_min(who, "hop", hop, 0) || !need_hop_max(who, hop, n, "n") || !need_min(who, "in_stride", in_stride, "n", n)) return -1;
-    if (!need_pow2(who, "n_fft", n_fft, bf::kEnhanceMinFft, bf::kEnhanceMaxFft)) return -1;
-    if (!need_min(who, "hop_s", hop_s, 1)) return -1;
-    if (hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP) {
-        set_error("%s: hop_s = %d does not divide n_fft = %d into 1 .. %d frames a sample", who, hop_s, n_fft, BF_ENHANCE_MAX_OVERLAP);
-        return -1;
-    }
-    const int len = hop > 0 ? hop : n;
-    const long long S = (long long)frames * len;
-    if (S > kMaxStream) { set_error("%s: frames * %s = %lld > %d", who, hop > 0 ? "hop" : "n", S, kMaxStream); return -1; }
+    const bf::StreamLen sl = bf::stream_len(frames, hop, n);
+    const long long S = sl.S;
+    if (!need_frame_grid(who, n_fft, hop_s) || !need_stream_len(who, sl, hop, "n")) return -1;
     if (!need_min(who, "out_stride", out_stride, "S", (int)S)) return -1;
     if (tracks) {
         if (!need_finite(who, "alpha", alpha, FINITE_GE0) || !need_finite(who, "a_noise", a_noise, FINITE_GE0) || !need_finite(who, "g0", g0, FINITE_GE0) ||
@@ -1966,7 +1978,7 @@ int bf_enhance_device(const float* d_in, int rows, int frames, int n, int in_str
     const long long work = bf::enhance_workspace(rows, S, n_fft, hop_s);
     if (work < 0) { set_error("%s: no workspace for rows = %d, S = %lld, n_fft = %d, hop_s = %d", who, rows, S, n_fft, hop_s); return -1; }
     // every span runs from its first element to the last one touched
-    const u64 n_bins = (u64)n_fft / 2 + 1, cap = ((u64)S + hop_s - 1) / hop_s;
+    const u64 n_bins = (u64)n_fft / 2 + 1, cap = (u64)bf::frame_cap(S, hop_s);
     const u64 cells = sat_mul(sat_mul(sat_mul((u64)rows, cap), n_bins), sizeof(float)), per_bin = (u64)rows * n_bins * sizeof(float);
     if (!need_disjoint(who, {{d_out, sat_add(sat_mul(sat_mul((u64)rows - 1, (u64)out_stride), sizeof(float)), (u64)S * sizeof(float)), "d_out"},
                              {d_work, sat_mul((u64)work, sizeof(float)), "d_work"},
@@ -1999,7 +2011,6 @@ int bf_postfilter_device(const float* d_signals, int m_total, int frames, int n_
 {
     static const char* who = "bf_postfilter_device";
     static_assert(BF_POSTFILTER_MAX_SLOTS == bf::kPostfilterMaxSlots && BF_POSTFILTER_MAX_SLOTS == BF_LCMV_MAX_SOURCES, "the header's limit is the kernel's");
-    constexpr int kMaxStream = std::numeric_limits<int>::max() / 2;
     Entered in;
     if (!need_ptrs(who, {{d_signals, "d_signals"}, {adaptive_array, "adaptive_array"}, {d_tau, "d_tau"}, {d_offsets, "d_offsets"}, {d_hist, "d_hist"},
                          {d_num, "d_num"}, {d_den, "d_den"}, {d_state, "d_state"}, {d_window, "d_window"}, {d_work, "d_work"}, {d_steer, "d_steer"},
@@ -2010,24 +2021,19 @@ int bf_postfilter_device(const float* d_signals, int m_total, int frames, int n_
     if (!need_min(who, "n", n, 2) || !need_max(who, "n", n, BF_MVDR_MAX_MICS) || !need_rows(who, adaptive_array, n, m_total)) return -1;
     if (!need_min(who, "slots", slots, 1) || !need_max(who, "slots", slots, BF_POSTFILTER_MAX_SLOTS)) return -1;
     if (!need_min(who, "dirs", dirs, 1) || !need_min(who, "offset_per_dir", offset_per_dir, 1)) return -1;
-    if (!need_pow2(who, "n_fft", n_fft, bf::kEnhanceMinFft, bf::kEnhanceMaxFft)) return -1;
-    if (!need_min(who, "hop_s", hop_s, 1)) return -1;
-    if (hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > BF_ENHANCE_MAX_OVERLAP) {
-        set_error("%s: hop_s = %d does not divide n_fft = %d into 1 .. %d frames a sample", who, hop_s, n_fft, BF_ENHANCE_MAX_OVERLAP);
-        return -1;
-    }
+    if (!need_frame_grid(who, n_fft, hop_s)) return -1;
     if (!need_min(who, "lag", lag, 0) || !need_max(who, "lag", lag, n_fft)) return -1;
     if (den_mode != 0 && den_mode != 1) { set_error("%s: den_mode = %d is not 0 (the microphones' mean power) or 1 (the beam's power)", who, den_mode); return -1; }
     if (!need_finite(who, "beta", beta, FINITE_GE0) || !need_finite(who, "g_min", g_min, FINITE_GE0)) return -1;
     if (beta >= 1.0f) { set_error("%s: beta = %g >= 1", who, (double)beta); return -1; }
     if (g_min > 1.0f) { set_error("%s: g_min = %g > 1", who, (double)g_min); return -1; }
-    const int len = hop > 0 ? hop : n_samples;
-    const long long S = (long long)frames * len;
-    if (S > kMaxStream) { set_error("%s: frames * %s = %lld > %d", who, hop > 0 ? "hop" : "n_samples", S, kMaxStream); return -1; }
+    const bf::StreamLen sl = bf::stream_len(frames, hop, n_samples);
+    const long long S = sl.S;
+    if (!need_stream_len(who, sl, hop, "n_samples")) return -1;
     const long long work = bf::postfilter_workspace(slots, S, n_fft, hop_s);
     if (work < 0) { set_error("%s: no workspace for slots = %d, S = %lld, n_fft = %d, hop_s = %d", who, slots, S, n_fft, hop_s); return -1; }
     // every span runs from its first element to the last one touched
-    const u64 n_bins = (u64)n_fft / 2 + 1, cap = ((u64)S + hop_s - 1) / hop_s, H = (u64)n_fft - 1 + lag;
+    const u64 n_bins = (u64)n_fft / 2 + 1, cap = (u64)bf::frame_cap(S, hop_s), H = (u64)n_fft - 1 + lag;
     const u64 cells = sat_mul(sat_mul((u64)slots * cap, n_bins), sizeof(float)), per_bin = (u64)slots * n_bins * sizeof(float);
     if (!need_disjoint(who, {{d_gains, cells, "d_gains"},
                              {d_num_out, cells, "d_num_out"},

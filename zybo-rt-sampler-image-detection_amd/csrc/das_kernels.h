@@ -304,10 +304,8 @@ hipError_t launch_whiten(const float* d_signals, long long items, int n_samples,
 // or d_gain_in float32 [rows][cap][n_fft / 2 + 1] -- and overlap-add synthesis under d_win_s -> d_out float32 [rows][out_stride], the stream
 // delayed by n_fft.  d_hist float32 [rows][n_fft - 1], d_ola float32 [rows][n_fft] and d_state int32 [4] carry between calls; d_count int32
 // [2] = (count, status); d_power_out / d_gain_out (null: not wanted) as d_gain_in.  Four launches: analysis, gains, synthesis, and the
-// overlap-add that also writes the history, the partial sums and the state.  d_work: enhance_workspace floats.
-constexpr int kEnhanceMinFft = 32;
-constexpr int kEnhanceMaxFft = 4096;
-constexpr int kEnhanceMaxOverlap = 8;                      // n_fft / hop_s
+// overlap-add that also writes the history, the partial sums and the state.  d_work: enhance_workspace floats.  The frame grid and its
+// limits (kEnhanceMinFft, kEnhanceMaxFft, kEnhanceMaxOverlap): stream_grid.h.
 long long enhance_workspace(int rows, long long samples, int n_fft, int hop_s);      // -1 on bad arguments
 hipError_t launch_enhance(const float* d_in, int rows, int frames, int n, int in_stride, int hop, float* d_hist, float* d_ola, float* d_noise, float* d_prior,
                           int32_t* d_state, const float* d_win_a, const float* d_win_s, int n_fft, int hop_s, const float* d_gain_in, float alpha, float a_noise,

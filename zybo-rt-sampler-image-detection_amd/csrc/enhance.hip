@@ -2,9 +2,9 @@
 // a decision-directed Wiener rule over a soft-decision recursive noise tracker, or the caller's own -- and overlap-add synthesis,
 // continuous across windows and calls.
 //
-// Definition (include/beamformer_hip.h): with c = d_state[0] stream samples since the last frame end, frame i of the call covers
-// x[(i + 1) hop_s - c - n_fft .. + n_fft) of hist || x; u = win_a * x, X = DFT(u), P = |X|^2; G from the recursion over the frames in
-// order (or d_gain_in); v = win_s / n_fft * IDFT(G X); y = the frames' v added in ascending frame order; d_out = y delayed by n_fft.
+// Definition (include/beamformer_hip.h), on the window stream and the frame grid of stream_grid.h: u = win_a * x, X = DFT(u), P = |X|^2; G
+// from the recursion over the frames in order (or d_gain_in); v = win_s / n_fft * IDFT(G X); y = the frames' v added in ascending frame
+// order; d_out = y delayed by n_fft.
 //
 // Four launches on the stream.  d_work holds, behind a header of four ints, X [rows][cap][2][n_bins], P and G [rows][cap][n_bins] and
 // v [rows][cap][n_fft].
@@ -15,14 +15,13 @@
 //   enhance_gain_kernel : a thread per (row, bin) walks the call's frames in order: the recursion in the header's float32 operations
 //       (the build has -ffp-contract=off; the fused steps are written __fmaf_rn, the divisions __fdiv_rn), G to d_work and the
 //       observables.  The thread reads its own d_noise / d_prior element first and writes it last; nothing else touches them.  Thread 0
-//       also copies (c, count, valid) into the header of d_work, which is what the last launch reads: that launch writes d_state.
+//       also writes the grid's header.
 //   enhance_synthesis_kernel : a workgroup per (row, frame) again: Y = G X staged with its Hermitian extension at the bit-reversed
 //       index, the inverse passes at n_fft complex points, v to d_work.
 //   enhance_overlap_kernel : a lane per output sample gathers the <= 8 frames that cover it, in ascending frame order, behind the
 //       carried partial sum where the position lies before the call's x[0].  The first workgroup of every row (the `tail`) takes the
-//       n_fft outputs that read d_ola, the row's new d_ola and its new d_hist: all three are staged in LDS (2 n_fft floats) before
-//       any of them is written, so nothing is read after it was overwritten; the other workgroups read v only.  Workgroup 0 also writes
-//       d_state and d_count.
+//       n_fft outputs that read d_ola, the row's new d_ola and the history carry, all staged in LDS (2 n_fft floats) before any of them is
+//       written; the other workgroups read v only.  Workgroup 0 also writes d_state and d_count.
 // Every value is computed by one fixed sequence of float32 operations on its own frame's samples and its own bin's state: the lane
 // count depends on n_fft alone, and the row count, the frame's index in the call and the alignment of the pointers do not enter.  The
 // bit promises of the definition rest on that.
@@ -32,36 +31,19 @@
 
 #include "das_kernels.h"
 #include "lds_fft.h"
+#include "stream_grid.h"
 
 namespace bf {
 namespace {
 
 constexpr int kEnhanceMaxGrid = 1 << 20;        // workgroups of a launch; more items than that are walked
 constexpr int kEnhanceLanes = 256;              // of the gain and the overlap-add launches
-constexpr int kEnhanceHeader = 4;               // ints in front of d_work: (c, count, valid, 0)
 
-struct EnhanceState {
-    int c, seen, count;
-    bool ok;
-};
-
-__device__ __forceinline__ EnhanceState enhance_state(const int* __restrict__ state, int S, int hop_s)
+// The grid of a call: d_state = (c, seen, 0, 0), seen >= 0 the frames the tracker has taken so far.
+__device__ __forceinline__ FrameGrid enhance_grid(const int* __restrict__ state, int S, int hop_s)
 {
-    EnhanceState st;
-    st.c = state[0];
-    st.seen = state[1];
-    st.ok = st.c >= 0 && st.c < hop_s && st.seen >= 0;
-    st.count = st.ok ? (int)(((long long)st.c + S) / hop_s) : 0;
-    return st;
-}
-
-// x[s] of row r: the window stream for s >= 0, the carried history for -H <= s < 0.
-__device__ __forceinline__ float enhance_sample(const float* __restrict__ in, const float* __restrict__ hist, int r, int rows, int n, int in_stride, int len, int H,
-                                                long long s)
-{
-    if (s < 0) return hist[(size_t)r * H + (H + s)];
-    const long long f = s / len;
-    return in[((size_t)f * rows + r) * in_stride + (n - len) + (s - f * len)];
+    const int c = state[0], seen = state[1];
+    return frame_grid(c, frame_phase_ok(c, hop_s) && seen >= 0, S, hop_s);
 }
 
 __global__ void __launch_bounds__(256)
@@ -76,7 +58,8 @@ enhance_analysis_kernel(const float* __restrict__ in, int rows, int n, int in_st
     float* tws = twc + (n_fft >> 1);
     const int lane = (int)threadIdx.x, lanes = (int)blockDim.x;
     const int H = n_fft - 1, half_n = n_fft >> 1, n_bins = half_n + 1;
-    const EnhanceState st = enhance_state(state, S, hop_s);
+    const FrameGrid st = enhance_grid(state, S, hop_s);
+    const WindowStream ws = window_stream(in, rows, n, in_stride, len);
 
     fft_twiddles(twc, tws, n_fft, half_n, lane, lanes);
 
@@ -84,13 +67,9 @@ enhance_analysis_kernel(const float* __restrict__ in, int rows, int n, int in_st
         const int r = (int)(item / cap);
         const int i = (int)(item - (long long)r * cap);
         if (i >= st.count) continue;            // (uniform over the workgroup) a slot behind the last frame: the gain launch zeroes it
-        const long long start = ((long long)i + 1) * hop_s - st.c - n_fft;         // >= -H, and start + n_fft <= S
-        for (int t = lane; t < n_fft; t += lanes) {
-            const float u = win_a[t] * enhance_sample(in, hist, r, rows, n, in_stride, len, H, start + t);
-            const int rev = fft_rev(t, log2n);
-            re[rev] = u;
-            im[rev] = 0.0f;
-        }
+        const long long start = frame_start(i, hop_s, st.c, n_fft);                // >= -H, and start + n_fft <= S
+        const float* hist_r = hist + (size_t)r * H;
+        stage_windowed(re, im, win_a, n_fft, log2n, lane, lanes, [&](int t) { return stream_or_history(ws, r, hist_r, H, start + t); });
         __syncthreads();                        // u is staged (also: the twiddles are there)
         fft_passes(re, im, twc, tws, log2n, half_n, lane, lanes, 1.0f);
         float* x = spec + (size_t)item * 2 * n_bins;
@@ -110,14 +89,9 @@ enhance_gain_kernel(const int* __restrict__ state, int rows, int S, int n_bins, 
                     const float* __restrict__ gain_in, float alpha, float a_noise, float g0, float g1, float g_min, int n_init, float* __restrict__ noise,
                     float* __restrict__ prior, float* __restrict__ gain, float* __restrict__ power_out, float* __restrict__ gain_out, int* __restrict__ header)
 {
-    const EnhanceState st = enhance_state(state, S, hop_s);
+    const FrameGrid st = enhance_grid(state, S, hop_s);
     const long long idx = (long long)blockIdx.x * kEnhanceLanes + threadIdx.x;
-    if (idx == 0) {
-        header[0] = st.c;
-        header[1] = st.count;
-        header[2] = st.ok ? 1 : 0;
-        header[3] = 0;
-    }
+    if (idx == 0) grid_header_write(header, st);
     if (idx >= (long long)rows * n_bins) return;
     const int r = (int)(idx / n_bins), k = (int)(idx - (long long)r * n_bins);
     const size_t at = ((size_t)r * cap) * n_bins + k;       // (r, frame 0, k); a frame further is n_bins further
@@ -133,10 +107,10 @@ enhance_gain_kernel(const int* __restrict__ state, int rows, int S, int n_bins, 
         float G;
         if (gain_in != nullptr) {
             G = gain_in[o];
-        } else if (!(fabsf(P) <= FLT_MAX)) {    // not finite: the bin's state stays, the frame comes out non-finite
+        } else if (!finite_f32(P)) {            // not finite: the bin's state stays, the frame comes out non-finite
             G = __builtin_nanf("");
         } else {
-            const long long seen = (long long)st.seen + i;
+            const long long seen = (long long)state[1] + i;
             if (seen < n_init) {
                 lam = seen == 0 ? P : lam + __fdiv_rn(P - lam, (float)(seen + 1));
             } else {
@@ -184,7 +158,7 @@ enhance_synthesis_kernel(const int* __restrict__ state, int S, const float* __re
     float* tws = twc + (n_fft >> 1);
     const int lane = (int)threadIdx.x, lanes = (int)blockDim.x;
     const int half_n = n_fft >> 1, n_bins = half_n + 1;
-    const EnhanceState st = enhance_state(state, S, hop_s);
+    const FrameGrid st = enhance_grid(state, S, hop_s);
     const float inv_n = 1.0f / (float)n_fft;    // (a power of two)
 
     fft_twiddles(twc, tws, n_fft, half_n, lane, lanes);
@@ -218,8 +192,7 @@ __device__ __forceinline__ float enhance_gather(const float* __restrict__ ola_r,
     const int lo = (int)(first < 0 ? 0 : first);
     const int hi = (int)(last < count - 1 ? last : count - 1);
     for (int i = lo; i <= hi; ++i) {
-        const long long start = ((long long)i + 1) * hop_s - c - n_fft;
-        acc = acc + frames_r[(size_t)i * n_fft + (t - start)];
+        acc = acc + frames_r[(size_t)i * n_fft + (t - frame_start(i, hop_s, c, n_fft))];
     }
     return acc;
 }
@@ -231,8 +204,8 @@ enhance_overlap_kernel(const float* __restrict__ in, int rows, int n, int in_str
 {
     extern __shared__ float stage[];            // the tail's: the row's new d_ola [n_fft], then its new d_hist [n_fft - 1]
     const int lane = (int)threadIdx.x, H = n_fft - 1;
-    const int c = header[0], count = header[1];
-    const bool ok = header[2] != 0;
+    const auto [c, count, ok] = grid_header_read(header);
+    const WindowStream ws = window_stream(in, rows, n, in_stride, len);
 
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
         const int r = (int)(item / blocks_per_row);
@@ -252,44 +225,35 @@ enhance_overlap_kernel(const float* __restrict__ in, int rows, int n, int in_str
             float* hist_r = hist + (size_t)r * H;
             float* new_hist = stage + n_fft;
             for (int j = lane; j < n_fft; j += kEnhanceLanes) stage[j] = enhance_gather(ola_r, frames_r, (long long)S - n_fft + j, c, count, n_fft, hop_s);
-            for (int j = lane; j < H; j += kEnhanceLanes) {
-                const long long p = (long long)j + S;            // of hist || x[0 .. S), whose last H samples are kept
-                new_hist[j] = p < H ? hist_r[p] : enhance_sample(in, hist, r, rows, n, in_stride, len, H, p - H);
-            }
+            carry_stage(new_hist, hist_r, H, S, lane, kEnhanceLanes, [&](long long s) { return stream_at(ws, r, s); });
             for (int s = lane; s < head; s += kEnhanceLanes) out_r[s] = enhance_gather(ola_r, frames_r, (long long)s - n_fft, c, count, n_fft, hop_s);
             __syncthreads();                    // everything that reads the old d_ola and d_hist of the row has read them
             for (int j = lane; j < n_fft; j += kEnhanceLanes) ola_r[j] = stage[j];
-            for (int j = lane; j < H; j += kEnhanceLanes) hist_r[j] = new_hist[j];
+            carry_write(hist_r, new_hist, H, lane, kEnhanceLanes);
             __syncthreads();                    // the next item restages
         }
         if (r == 0 && lane == 0) {
             if (!ok) {
-                count_status[0] = 0;
-                count_status[1] = 1;
+                report(count_status, false, 0);
             } else {
                 const long long seen = (long long)state[1] + count;
                 state[0] = (int)(((long long)c + S) % hop_s);
                 if (tracks) state[1] = (int)(seen < n_init ? seen : n_init);
                 state[2] = 0;
                 state[3] = 0;
-                count_status[0] = count;
-                count_status[1] = 0;
+                report(count_status, true, count);
             }
         }
     }
 }
 
-long long enhance_cap(long long S, int hop_s) { return (S + hop_s - 1) / hop_s; }
-
 }  // namespace
 
 long long enhance_workspace(int rows, long long samples, int n_fft, int hop_s)
 {
-    if (rows < 1 || samples < 1 || samples > 0x7fffffff / 2 || n_fft < kEnhanceMinFft || n_fft > kEnhanceMaxFft || fft_log2(n_fft) < 0 || hop_s < 1 ||
-        hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > kEnhanceMaxOverlap)
-        return -1;
-    const long long slots = (long long)rows * enhance_cap(samples, hop_s);           // < 2^61
-    return kEnhanceHeader + slots * (4LL * (n_fft / 2 + 1) + n_fft);
+    if (rows < 1 || !frame_grid_ok(samples, n_fft, hop_s)) return -1;
+    const long long slots = (long long)rows * frame_cap(samples, hop_s);             // < 2^61
+    return kGridHeader + slots * (4LL * (n_fft / 2 + 1) + n_fft);
 }
 
 hipError_t launch_enhance(const float* d_in, int rows, int frames, int n, int in_stride, int hop, float* d_hist, float* d_ola, float* d_noise, float* d_prior,
@@ -298,14 +262,13 @@ hipError_t launch_enhance(const float* d_in, int rows, int frames, int n, int in
                           int32_t* d_count, hipStream_t stream)
 {
     if (rows < 1 || frames < 1 || n < 1 || hop < 0 || hop > n || in_stride < n) return hipErrorInvalidValue;
-    const int len = hop > 0 ? hop : n;
-    const long long S = (long long)frames * len;
-    if (enhance_workspace(rows, S, n_fft, hop_s) < 0 || out_stride < S) return hipErrorInvalidValue;
+    const auto [len, S, fits] = stream_len(frames, hop, n);
+    if (!fits || enhance_workspace(rows, S, n_fft, hop_s) < 0 || out_stride < S) return hipErrorInvalidValue;
     const int log2n = fft_log2(n_fft);
     const int n_bins = n_fft / 2 + 1;
-    const long long cap = enhance_cap(S, hop_s), items = cap * rows;
+    const long long cap = frame_cap(S, hop_s), items = cap * rows;
     int32_t* header = reinterpret_cast<int32_t*>(d_work);
-    float* spec = d_work + kEnhanceHeader;
+    float* spec = d_work + kGridHeader;
     float* power = spec + (size_t)items * 2 * n_bins;
     float* gain = power + (size_t)items * n_bins;
     float* v = gain + (size_t)items * n_bins;

@@ -3,9 +3,9 @@
 // of the n (n - 1) / 2 pairs over the mean power is a Wiener gain per (frame, bin) that needs no noise history; the pair sum is
 // (|sum Z|^2 - sum |Z|^2) / 2, so no pair loop exists.
 //
-// Definition (include/beamformer_hip.h): with c = d_state[0], frame i of the call covers x[(i + 1) hop_s - c - lag - n_fft .. + n_fft) of
-// hist || x for every microphone; u = window * x, X = DFT(u), q = |X|^2, Z = a X with the slot's steering a; Y = sum_m Z, Q = sum_m q;
-// num = (|Y|^2 - Q) / (n (n - 1)), den = Q / n or |Y|^2 / n^2; N and D smooth them per (slot, bin); G = clamp(max(N, 0) / D).
+// Definition (include/beamformer_hip.h), on the frame grid of stream_grid.h, every microphone read `lag` samples late: u = window * x,
+// X = DFT(u), q = |X|^2, Z = a X with the slot's steering a; Y = sum_m Z, Q = sum_m q; num = (|Y|^2 - Q) / (n (n - 1)), den = Q / n or
+// |Y|^2 / n^2; N and D smooth them per (slot, bin); G = clamp(max(N, 0) / D).
 //
 // Four launches on the stream.  d_work holds, behind a header of sixteen ints, the frames' flags int32 [slots][cap] and the raw num and den
 // [slots][cap][n_bins].
@@ -22,10 +22,10 @@
 //       the frame's index do not enter.  A frame's flag says whether all of its num and den are finite.  Reads d_state and d_hist only.
 //   postfilter_gain_kernel : a thread per (slot, bin) walks the call's frames in order: the recursion in the header's float32 operations
 //       (the build has -ffp-contract=off; the fused steps are __fmaf_rn, the division __fdiv_rn).  It reads its own d_num / d_den element
-//       first and writes it last.  The thread of bin 0 also writes d_status and the slot's new `seen` into the header of d_work, thread 0
-//       (c, count, valid): the header is what the last launch reads.
-//   postfilter_carry_kernel : a workgroup per microphone stages the row's new history in LDS before it writes it; workgroup 0 also writes
-//       d_state and d_count.  It alone writes what is carried, so a replayed graph advances the stream.
+//       first and writes it last.  The thread of bin 0 also writes d_status and the slot's new `seen` behind the grid's header, thread 0 the
+//       header.
+//   postfilter_carry_kernel : a workgroup per microphone does the history carry; workgroup 0 also writes d_state and d_count.  It alone
+//       writes what is carried, so a replayed graph advances the stream.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -33,39 +33,23 @@
 #include "das_kernels.h"
 #include "design_device.h"
 #include "lds_fft.h"
+#include "stream_grid.h"
 
 namespace bf {
 namespace {
 
 constexpr int kPostfilterMaxGrid = 1 << 20;     // workgroups of the analysis launch; more frames than that are walked
 constexpr int kPostfilterLanes = 256;
-constexpr int kPostfilterHeader = 16;           // ints in front of d_work: (c, count, valid, 0, seen'[8], 0, 0, 0, 0)
+constexpr int kPostfilterHeader = 16;           // ints in front of d_work: the grid's four, then (seen'[8], 0, 0, 0, 0)
 constexpr int kSplitMaxFft = 512;               // up to here a wave transforms a microphone on its own
 
-struct PostfilterState {
-    int c, count;
-    bool ok;
-};
-
-__device__ __forceinline__ PostfilterState postfilter_state(const int* __restrict__ state, int slots, int S, int hop_s)
+// The grid of a call: d_state = (c, 0, seen[slots]), seen in {0, 1}: whether the slot's N and D hold a frame yet.
+__device__ __forceinline__ FrameGrid postfilter_grid(const int* __restrict__ state, int slots, int S, int hop_s)
 {
-    PostfilterState st;
-    st.c = state[0];
-    st.ok = st.c >= 0 && st.c < hop_s;
-    for (int b = 0; b < slots; ++b) st.ok = st.ok && (state[2 + b] == 0 || state[2 + b] == 1);
-    st.count = st.ok ? (int)(((long long)st.c + S) / hop_s) : 0;
-    return st;
-}
-
-__device__ __forceinline__ bool finite_f32(float v) { return fabsf(v) <= FLT_MAX; }
-
-// x_m[s]: the window stream for s >= 0, the carried history for -H <= s < 0.
-__device__ __forceinline__ float postfilter_sample(const float* __restrict__ in, const float* __restrict__ hist, int m, int row, int m_total, int n_samples, int len,
-                                                   int H, int s)
-{
-    if (s < 0) return hist[(size_t)m * H + (H + s)];
-    const int f = s / len;
-    return in[((size_t)f * m_total + row) * n_samples + (n_samples - len) + (s - f * len)];
+    const int c = state[0];
+    bool ok = frame_phase_ok(c, hop_s);
+    for (int b = 0; b < slots; ++b) ok = ok && (state[2 + b] == 0 || state[2 + b] == 1);
+    return frame_grid(c, ok, S, hop_s);
 }
 
 __global__ void __launch_bounds__(kPostfilterLanes)
@@ -114,7 +98,8 @@ postfilter_analysis_kernel(const float* __restrict__ in, int m_total, int n_samp
     float* im = re + n_fft;
     float* twc = lds + (size_t)kWaves * 2 * n_fft;
     float* tws = twc + half_n;
-    const PostfilterState st = postfilter_state(state, slots, S, hop_s);
+    const FrameGrid st = postfilter_grid(state, slots, S, hop_s);
+    const WindowStream ws = window_stream(in, m_total, n_samples, n_samples, len);
     unsigned src = 0;                           // the slots that are sources
     for (int b = 0; b < slots; ++b) src |= slot_direction(offsets[b], offset_per_dir, dirs) >= 0 ? 1u << b : 0u;
     const float pairs = (float)(n * (n - 1)), den_div = den_mode == 0 ? (float)n : (float)(n * n);     // (exact: n <= 256)
@@ -124,7 +109,7 @@ postfilter_analysis_kernel(const float* __restrict__ in, int m_total, int n_samp
 
     for (int i = (int)blockIdx.x; i < cap; i += (int)gridDim.x) {
         if (i >= st.count) continue;            // (uniform over the workgroup) a slot behind the last frame: the gain launch zeroes it
-        const int start = (i + 1) * hop_s - st.c - lag - n_fft;          // >= -H, and start + n_fft <= S - lag
+        const int start = frame_start<int>(i, hop_s, st.c, n_fft, lag);  // >= -H, and start + n_fft <= S - lag
         float Q[BPL], Yr[kS][BPL], Yi[kS][BPL];
 #pragma unroll
         for (int j = 0; j < BPL; ++j) {
@@ -136,12 +121,8 @@ postfilter_analysis_kernel(const float* __restrict__ in, int m_total, int n_samp
             const int m = r * kWaves + wave;    // (uniform over the wave)
             if (m < n) {
                 const int row = mics[m];
-                for (int t = lane; t < n_fft; t += kRowLanes) {
-                    const float u = window[t] * postfilter_sample(in, hist, m, row, m_total, n_samples, len, H, start + t);
-                    const int rev = fft_rev(t, log2n);
-                    re[rev] = u;
-                    im[rev] = 0.0f;
-                }
+                const float* hist_m = hist + (size_t)m * H;
+                stage_windowed(re, im, window, n_fft, log2n, lane, kRowLanes, [&](int t) { return stream_or_history(ws, row, hist_m, H, start + t); });
             }
             __syncthreads();                    // u is staged (also: the twiddles are there)
             fft_passes(re, im, twc, tws, log2n, half_n, lane, kRowLanes, 1.0f);
@@ -222,14 +203,9 @@ postfilter_gain_kernel(const int32_t* __restrict__ state, const int32_t* __restr
                        float* __restrict__ d_num, float* __restrict__ d_den, float* __restrict__ gains, float* __restrict__ num_out, float* __restrict__ den_out,
                        int32_t* __restrict__ status, int32_t* __restrict__ header)
 {
-    const PostfilterState st = postfilter_state(state, slots, S, hop_s);
+    const FrameGrid st = postfilter_grid(state, slots, S, hop_s);
     const long long idx = (long long)blockIdx.x * kPostfilterLanes + threadIdx.x;
-    if (idx == 0) {
-        header[0] = st.c;
-        header[1] = st.count;
-        header[2] = st.ok ? 1 : 0;
-        header[3] = 0;
-    }
+    if (idx == 0) grid_header_write(header, st);
     if (idx >= (long long)slots * n_bins) return;
     const int b = (int)(idx / n_bins), k = (int)(idx - (long long)b * n_bins);
     const bool source = slot_direction(offsets[b], offset_per_dir, dirs) >= 0;
@@ -280,7 +256,7 @@ postfilter_gain_kernel(const int32_t* __restrict__ state, const int32_t* __restr
     }
     if (k == 0) {
         status[b] = source ? 0 : 1;
-        header[4 + b] = source ? seen : 0;      // (every bin of a slot sees the same flags: `seen` is the slot's)
+        header[kGridHeader + b] = source ? seen : 0;    // (every bin of a slot sees the same flags: `seen` is the slot's)
     }
 }
 
@@ -290,33 +266,26 @@ postfilter_carry_kernel(const float* __restrict__ in, int m_total, int n_samples
 {
     extern __shared__ float stage[];            // the row's new d_hist [H]
     const int lane = (int)threadIdx.x, m = (int)blockIdx.x;
-    const int c = header[0], count = header[1];
-    const bool ok = header[2] != 0;
-    if (ok) {                                   // a corrupt state is reported and everything is left as it was
+    const FrameGrid st = grid_header_read(header);
+    if (st.ok) {                                // a corrupt state is reported and everything is left as it was
         float* hist_m = hist + (size_t)m * H;
         const int row = mics[m];
-        for (int j = lane; j < H; j += kPostfilterLanes) {
-            const long long p = (long long)j + S;                        // of hist || x[0 .. S), whose last H samples are kept
-            stage[j] = p < H ? hist_m[p] : postfilter_sample(in, hist, m, row, m_total, n_samples, len, H, (int)(p - H));
-        }
+        const WindowStream ws = window_stream(in, m_total, n_samples, n_samples, len);
+        carry_stage(stage, hist_m, H, S, lane, kPostfilterLanes, [&](long long s) { return stream_at(ws, row, (int)s); });
         __syncthreads();                        // everything that reads the row's old d_hist has read it
-        for (int j = lane; j < H; j += kPostfilterLanes) hist_m[j] = stage[j];
+        carry_write(hist_m, stage, H, lane, kPostfilterLanes);
     }
     if (m == 0 && lane == 0) {
-        if (!ok) {
-            count_status[0] = 0;
-            count_status[1] = 1;
+        if (!st.ok) {
+            report(count_status, false, 0);
         } else {
-            state[0] = (int)(((long long)c + S) % hop_s);
+            state[0] = (int)(((long long)st.c + S) % hop_s);
             state[1] = 0;
-            for (int b = 0; b < slots; ++b) state[2 + b] = header[4 + b];
-            count_status[0] = count;
-            count_status[1] = 0;
+            for (int b = 0; b < slots; ++b) state[2 + b] = header[kGridHeader + b];
+            report(count_status, true, st.count);
         }
     }
 }
-
-long long postfilter_cap(long long S, int hop_s) { return (S + hop_s - 1) / hop_s; }
 
 template <int BPL, bool SPLIT>
 void launch_analysis(unsigned grid, size_t lds, hipStream_t stream, const float* in, int m_total, int n_samples, int len, int S, const int32_t* mics, int n,
@@ -331,10 +300,8 @@ void launch_analysis(unsigned grid, size_t lds, hipStream_t stream, const float*
 
 long long postfilter_workspace(int slots, long long samples, int n_fft, int hop_s)
 {
-    if (slots < 1 || slots > kPostfilterMaxSlots || samples < 1 || samples > 0x7fffffff / 2 || n_fft < kEnhanceMinFft || n_fft > kEnhanceMaxFft ||
-        fft_log2(n_fft) < 0 || hop_s < 1 || hop_s > n_fft || n_fft % hop_s != 0 || n_fft / hop_s > kEnhanceMaxOverlap)
-        return -1;
-    const long long cells = (long long)slots * postfilter_cap(samples, hop_s);       // < 2^34
+    if (slots < 1 || slots > kPostfilterMaxSlots || !frame_grid_ok(samples, n_fft, hop_s)) return -1;
+    const long long cells = (long long)slots * frame_cap(samples, hop_s);            // < 2^34
     return kPostfilterHeader + cells * (1 + 2LL * (n_fft / 2 + 1));
 }
 
@@ -346,11 +313,10 @@ hipError_t launch_postfilter(const float* d_signals, int m_total, int frames, in
     if (m_total < 1 || frames < 1 || n_samples < 1 || hop < 0 || hop > n_samples || n < 2 || n > kMvdrMaxMics || dirs < 1 || offset_per_dir < 1 || lag < 0 ||
         lag > n_fft || (den_mode != 0 && den_mode != 1))
         return hipErrorInvalidValue;
-    const int len = hop > 0 ? hop : n_samples;
-    const long long S = (long long)frames * len;
-    if (postfilter_workspace(slots, S, n_fft, hop_s) < 0) return hipErrorInvalidValue;
+    const auto [len, S, fits] = stream_len(frames, hop, n_samples);
+    if (!fits || postfilter_workspace(slots, S, n_fft, hop_s) < 0) return hipErrorInvalidValue;
     const int log2n = fft_log2(n_fft), n_bins = n_fft / 2 + 1, H = n_fft - 1 + lag;
-    const long long cap = postfilter_cap(S, hop_s), cells = cap * slots;
+    const long long cap = frame_cap(S, hop_s), cells = cap * slots;
     int32_t* header = reinterpret_cast<int32_t*>(d_work);
     int32_t* flag_w = header + kPostfilterHeader;
     float* num_w = d_work + kPostfilterHeader + cells;

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "das_kernels.h"
+#include "stream_grid.h"
 
 namespace bf {
 namespace {
@@ -47,7 +48,7 @@ resample_kernel(const float* __restrict__ in, const float* __restrict__ prev, co
     __shared__ __attribute__((aligned(16))) float s[kResampleSpan];
     const int o = state[0], phi = state[1];
     const int count = resample_state_ok(o, phi, L) ? (int)resample_count(o, phi, S, L, M) : 0;   // (<= cap, which fits an int)
-    const int first = n - len;
+    const WindowStream ws = window_stream(in, rows, n, in_stride, len);
     const int lane = (int)threadIdx.x;
 
     for (long long item = blockIdx.x; item < items; item += gridDim.x) {
@@ -65,8 +66,7 @@ resample_kernel(const float* __restrict__ in, const float* __restrict__ prev, co
                 const int si = i_lo + j;
                 float v = 0.0f;
                 if (si >= 0) {
-                    const int f = si / len;
-                    v = in[((size_t)f * rows + r) * in_stride + first + (si - f * len)];
+                    v = stream_at(ws, r, si);
                 } else if (prev != nullptr) {
                     v = prev[(size_t)r * in_stride + n + si];
                 }
@@ -125,8 +125,7 @@ __global__ void resample_advance_kernel(int* __restrict__ state, int* __restrict
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const int o = state[0], phi = state[1];
     if (!resample_state_ok(o, phi, L)) {        // a corrupt state is reported and left as it was
-        count_status[0] = 0;
-        count_status[1] = 1;
+        report(count_status, false, 0);
         return;
     }
     const long long count = resample_count(o, phi, S, L, M);
@@ -135,8 +134,7 @@ __global__ void resample_advance_kernel(int* __restrict__ state, int* __restrict
     state[1] = (int)(A % L);
     state[2] = 0;
     state[3] = 0;
-    count_status[0] = (int)count;
-    count_status[1] = 0;
+    report(count_status, true, (int)count);
 }
 
 }  // namespace
@@ -155,9 +153,10 @@ hipError_t launch_resample(const float* d_in, int rows, int frames, int n, int i
     if (rows < 1 || frames < 1 || n < 1 || L < 1 || L > kResampleMaxPhases || M < 1 || M > 64LL * L || T < 1 || T > kResampleMaxTaps || hop < 0 || hop > n ||
         in_stride < n || (d_out == nullptr && d_pcm == nullptr))
         return hipErrorInvalidValue;
-    const int len = hop > 0 ? hop : n;
-    const long long S = (long long)frames * len, cap = resample_capacity(S, L, M);
-    if (T - 1 > len || S > 0x7fffffff / 2 || cap < 1 || cap > 0x7fffffffLL || (d_out != nullptr && out_stride < cap)) return hipErrorInvalidValue;
+    const auto [len, S, fits] = stream_len(frames, hop, n);
+    if (!fits) return hipErrorInvalidValue;
+    const long long cap = resample_capacity(S, L, M);
+    if (T - 1 > len || cap < 1 || cap > 0x7fffffffLL || (d_out != nullptr && out_stride < cap)) return hipErrorInvalidValue;
     int run = kResampleLanes;
     while (run > 1 && ((long long)(run - 1) * M + L - 1) / L + T > kResampleSpan) run >>= 1;      // (run = 1: T <= 128 samples always fit)
     const long long blocks_per_row = (cap + run - 1) / run, items = blocks_per_row * rows;

@@ -22,6 +22,7 @@
 
 #include "das_kernels.h"
 #include "lds_fft.h"
+#include "stream_grid.h"
 
 namespace bf {
 namespace {
@@ -71,7 +72,7 @@ spectrogram_kernel(const float* __restrict__ in, int rows, int in_stride, int le
         const long long sj = (long long)s0 + (long long)j * hop;           // >= -H, and sj + n_win <= L
         const float* x = in + (size_t)r * in_stride;
         const float* h = hist + (size_t)r * H;
-        for (int t = lane; t < n_fft; t += lanes) {
+        for (int t = lane; t < n_fft; t += lanes) {           // (stage_windowed, zero-padded behind n_win)
             float u = 0.0f;
             if (t < n_win) {
                 const long long s = sj + t;
@@ -117,12 +118,9 @@ spectrogram_advance_kernel(const float* __restrict__ in, int in_stride, int len,
     if (ok) {                                   // a corrupt state is reported and everything is left as it was
         float* h = hist + (size_t)r * H;
         const float* x = in + (size_t)r * in_stride;
-        for (int i = lane; i < H; i += kSpectrogramAdvanceLanes) {
-            const long long p = (long long)i + L;                  // of hist || x[0 .. L), whose last H samples are kept
-            stage[i] = p < H ? h[p] : x[p - H];
-        }
-        __syncthreads();
-        for (int i = lane; i < H; i += kSpectrogramAdvanceLanes) h[i] = stage[i];
+        carry_stage(stage, h, H, L, lane, kSpectrogramAdvanceLanes, [&](long long s) { return x[s]; });
+        __syncthreads();                        // everything that reads the row's old d_hist has read it
+        carry_write(h, stage, H, lane, kSpectrogramAdvanceLanes);
     }
     if (r == 0 && lane == 0) {
         if (!ok) {

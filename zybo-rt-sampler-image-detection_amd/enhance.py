@@ -56,6 +56,44 @@ def advance_frames(c, S, hop_s):
     return (c + S) // hop_s, (c + S) % hop_s
 
 
+class FrameGrid:
+    """The frame grid a stream stage walks (csrc/stream_grid.h states it): frames of n_fft samples every hop_s, on the last `hop` samples
+    of every window (None: whole windows).  It holds the host's mirror of the stream's position on the grid -- `c`, the samples since the
+    last frame end, and `last_count`, the frames the last call completed -- and the stage's workspace, which only grows."""
+
+    def __init__(self, n_fft, hop_s, hop, device):
+        self.n_fft, self.hop_s = _check_frames(n_fft, hop_s)
+        self.n_bins, self.hop, self.device = self.n_fft // 2 + 1, 0 if hop is None else int(hop), device
+        if self.hop < 0:
+            raise ValueError("hop must be >= 1 (None: back-to-back windows), got %d" % self.hop)
+        self.shape = (self.n_fft, self.hop_s, self.hop)
+        self._work, self.c, self.last_count = None, 0, 0
+
+    def capacity(self, samples):
+        return (self.hop_s - 1 + int(samples)) // self.hop_s
+
+    def samples(self, F, N):
+        """The stream samples that F windows of N add."""
+        if self.hop > N:
+            raise ValueError("hop = %d > N = %d" % (self.hop, N))
+        return F * (self.hop or N)
+
+    def work(self, entry, lead, what, S):
+        """The workspace of a call on S samples, `entry`(lead, S, n_fft, hop_s) floats; lead: the stage's rows or slots (`what`)."""
+        words = _entry(entry)(lead, S, self.n_fft, self.hop_s)
+        if words < 0:
+            raise ValueError("no workspace for %d %s of %d samples" % (lead, what, S))
+        if self._work is None or self._work.numel() < words:
+            self._work = _torch().empty(words, dtype=_torch().float32, device=self.device)
+        return self._work
+
+    def advance(self, S):
+        self.last_count, self.c = advance_frames(self.c, S, self.hop_s)
+
+    def reset(self):
+        self.c, self.last_count = 0, 0
+
+
 class Enhancer:
     """Spectral noise suppression of `rows` streams of windows every `hop` samples (None: back-to-back windows, or flat blocks): frames
     of n_fft samples every hop_s under design_cola's pair (or `windows` = (win_a, win_s)), the decision-directed Wiener gain with
@@ -68,11 +106,8 @@ class Enhancer:
 
     def __init__(self, rows=None, hop=None, n_fft=256, hop_s=128, alpha=0.98, a_noise=0.9, g0=1.5, g1=5.0, g_min=0.1, n_init=8, windows=None,
                  device="cuda"):
-        self.n_fft, self.hop_s = _check_frames(n_fft, hop_s)
-        self.n_bins = self.n_fft // 2 + 1
-        self.hop = 0 if hop is None else int(hop)
-        if self.hop < 0:
-            raise ValueError("hop must be >= 1 (None: back-to-back windows), got %d" % self.hop)
+        self.grid = FrameGrid(n_fft, hop_s, hop, device)
+        self.n_fft, self.hop_s, self.n_bins, self.hop = self.grid.n_fft, self.grid.hop_s, self.grid.n_bins, self.grid.hop
         self.alpha, self.a_noise, self.g0, self.g1, self.g_min, self.n_init = float(alpha), float(a_noise), float(g0), float(g1), float(g_min), int(n_init)
         if not (0.0 <= self.alpha < 1.0 and 0.0 <= self.a_noise < 1.0 and 0.0 <= self.g0 < self.g1 < np.inf and 0.0 <= self.g_min <= 1.0 and self.n_init >= 1):
             raise ValueError("alpha and a_noise in [0, 1), 0 <= g0 < g1, g_min in [0, 1] and n_init >= 1 must hold")
@@ -92,9 +127,8 @@ class Enhancer:
         self.hist = self.ola = self.noise = self.prior = None
         if self.rows is not None:
             self._allocate(self.rows)
-        self._work = None
-        self._c = 0                      # the host mirror of state[0]
-        self.last_count = 0
+
+    last_count = property(lambda self: self.grid.last_count)
 
     def _allocate(self, rows):
         torch = _torch()
@@ -106,7 +140,7 @@ class Enhancer:
 
     def capacity(self, samples):
         """The frame slots of a push of `samples` stream samples a row: the second dimension of `gains`."""
-        return (self.hop_s - 1 + int(samples)) // self.hop_s
+        return self.grid.capacity(samples)
 
     def push(self, out, gains=None, observe=False):
         """out float32 cuda [F, B, N] as listen() returns it (or [B, S], a flat block of every row's stream) -> (clean float32 [B, S],
@@ -127,27 +161,21 @@ class Enhancer:
             self._allocate(B)
         if B != self.rows:
             raise ValueError("this Enhancer takes %d rows, out has %d" % (self.rows, B))
-        if self.hop > N:
-            raise ValueError("hop = %d > N = %d" % (self.hop, N))
-        S = F * (self.hop or N)
+        S = self.grid.samples(F, N)
         cap = self.capacity(S)
         if gains is not None:
             if gains.dtype != torch.float32 or not gains.is_cuda or tuple(gains.shape) != (B, cap, self.n_bins):
                 raise ValueError("gains must be a float32 cuda tensor %s, got %s %s" % ((B, cap, self.n_bins), gains.dtype, tuple(gains.shape)))
             gains = gains.contiguous()
-        words = _entry("bf_enhance_workspace")(B, S, self.n_fft, self.hop_s)
-        if words < 0:
-            raise ValueError("no workspace for %d rows of %d samples" % (B, S))
-        if self._work is None or self._work.numel() < words:
-            self._work = torch.empty(words, dtype=torch.float32, device=self.device)
+        work = self.grid.work("bf_enhance_workspace", B, "rows", S)
         clean = torch.empty((B, S), dtype=torch.float32, device=self.device)
         power = torch.empty((B, cap, self.n_bins), dtype=torch.float32, device=self.device) if observe else None
         gain = torch.empty((B, cap, self.n_bins), dtype=torch.float32, device=self.device) if observe else None
         call("bf_enhance_device", x.data_ptr(), B, F, N, N, self.hop, self.hist.data_ptr(), self.ola.data_ptr(), self.noise.data_ptr(), self.prior.data_ptr(),
              self.state.data_ptr(), self.d_win_a.data_ptr(), self.d_win_s.data_ptr(), self.n_fft, self.hop_s, None if gains is None else gains.data_ptr(),
-             self.alpha, self.a_noise, self.g0, self.g1, self.g_min, self.n_init, self._work.data_ptr(), clean.data_ptr(), S,
+             self.alpha, self.a_noise, self.g0, self.g1, self.g_min, self.n_init, work.data_ptr(), clean.data_ptr(), S,
              None if power is None else power.data_ptr(), None if gain is None else gain.data_ptr(), self.count.data_ptr())
-        self.last_count, self._c = advance_frames(self._c, S, self.hop_s)
+        self.grid.advance(S)
         return (clean, self.count, power, gain) if observe else (clean, self.count)
 
     def reset(self):
@@ -155,4 +183,4 @@ class Enhancer:
         for t in (self.state, self.count, self.hist, self.ola, self.noise, self.prior):
             if t is not None:
                 t.zero_()
-        self._c, self.last_count = 0, 0
+        self.grid.reset()

@@ -15,9 +15,9 @@ has the definition), and `push` hands them to `Enhancer.push(gains=...)`, which 
 """
 import numpy as np
 
-from enhance import _check_frames, advance_frames, design_cola
+from enhance import FrameGrid, design_cola
 from lib import _native as nat
-from lib._native import _entry, _torch, call
+from lib._native import _torch, call
 
 MAX_SLOTS = 8
 MAX_MICS = 256
@@ -39,8 +39,8 @@ class SpatialPostFilter:
     def __init__(self, tau, mics, slots, offset_per_dir, hop, m_total=None, n_fft=256, hop_s=128, beta=0.8, g_min=0.1, den="mics", lag=0, window=None,
                  device="cuda"):
         torch = _torch()
-        self.n_fft, self.hop_s = _check_frames(n_fft, hop_s)
-        self.n_bins = self.n_fft // 2 + 1
+        self.grid = FrameGrid(n_fft, hop_s, hop, device)
+        self.n_fft, self.hop_s, self.n_bins, self.hop = self.grid.n_fft, self.grid.hop_s, self.grid.n_bins, self.grid.hop
         self.mics = np.ascontiguousarray(np.asarray(mics).astype(np.int32).ravel())
         self.n = int(self.mics.size)
         if self.n < 2 or self.n > MAX_MICS:
@@ -62,9 +62,6 @@ class SpatialPostFilter:
             raise ValueError("1 .. %d slots, got %d" % (MAX_SLOTS, self.slots))
         if self.offset_per_dir < 1:
             raise ValueError("offset_per_dir must be >= 1, got %d" % self.offset_per_dir)
-        self.hop = 0 if hop is None else int(hop)
-        if self.hop < 0:
-            raise ValueError("hop must be >= 1 (None: back-to-back windows), got %d" % self.hop)
         self.m_total = None if m_total is None else int(m_total)
         if self.m_total is not None and (self.mics.min() < 0 or self.mics.max() >= self.m_total):
             raise ValueError("mics names a row outside frames of m_total = %d rows" % self.m_total)
@@ -86,9 +83,8 @@ class SpatialPostFilter:
         self.hist = z((self.n, self.n_fft - 1 + self.lag))
         self.num, self.den_state = z((self.slots, self.n_bins)), z((self.slots, self.n_bins))
         self.steer = z((self.slots, self.n, self.n_bins, 2))
-        self._work = None
-        self._c = 0                      # the host mirror of state[0]
-        self.last_count = 0
+
+    last_count = property(lambda self: self.grid.last_count)
 
     @classmethod
     def for_listener(cls, listener, slots=None, tau=None, offset_per_dir=None, **kw):
@@ -120,7 +116,7 @@ class SpatialPostFilter:
 
     def capacity(self, samples):
         """The frame slots of a call on `samples` stream samples: the second dimension of the gains (the Enhancer's)."""
-        return (self.hop_s - 1 + int(samples)) // self.hop_s
+        return self.grid.capacity(samples)
 
     def gains(self, d_frames, offsets_row, observe=False):
         """d_frames float32 cuda [F, M_total, N]; offsets_row int32 [slots] (a cuda tensor: one row of what SourceTracker.update or
@@ -134,40 +130,33 @@ class SpatialPostFilter:
         F, m_total, N = x.shape
         if self.m_total is not None and m_total != self.m_total:
             raise ValueError("this post-filter takes frames of %d rows, d_frames has %d" % (self.m_total, m_total))
-        if self.hop > N:
-            raise ValueError("hop = %d > N = %d" % (self.hop, N))
+        S = self.grid.samples(F, N)
         offs = offsets_row if isinstance(offsets_row, torch.Tensor) else torch.as_tensor(np.asarray(offsets_row, dtype=np.int32))
         offs = offs.to(device=self.device, dtype=torch.int32).contiguous()
         if tuple(offs.shape) != (self.slots,):
             raise ValueError("offsets_row must hold %d entries, got shape %s" % (self.slots, tuple(offs.shape)))
-        S = F * (self.hop or N)
         cap = self.capacity(S)
-        words = _entry("bf_postfilter_workspace")(self.slots, S, self.n_fft, self.hop_s)
-        if words < 0:
-            raise ValueError("no workspace for %d slots of %d samples" % (self.slots, S))
-        if self._work is None or self._work.numel() < words:
-            self._work = torch.empty(words, dtype=torch.float32, device=self.device)
+        work = self.grid.work("bf_postfilter_workspace", self.slots, "slots", S)
         shape = (self.slots, cap, self.n_bins)
         g = torch.empty(shape, dtype=torch.float32, device=self.device)
         num = torch.empty(shape, dtype=torch.float32, device=self.device) if observe else None
         den = torch.empty(shape, dtype=torch.float32, device=self.device) if observe else None
         call("bf_postfilter_device", x.data_ptr(), m_total, F, N, self.hop, nat.iptr(self.mics), self.n, self.d_tau.data_ptr(), self.n_dirs, offs.data_ptr(),
              self.slots, self.offset_per_dir, self.hist.data_ptr(), self.num.data_ptr(), self.den_state.data_ptr(), self.state.data_ptr(),
-             self.d_window.data_ptr(), self.n_fft, self.hop_s, self.lag, DEN_MODES[self.den], self.beta, self.g_min, self._work.data_ptr(),
+             self.d_window.data_ptr(), self.n_fft, self.hop_s, self.lag, DEN_MODES[self.den], self.beta, self.g_min, work.data_ptr(),
              self.steer.data_ptr(), g.data_ptr(), None if num is None else num.data_ptr(), None if den is None else den.data_ptr(), self.status.data_ptr(),
              self.count.data_ptr())
-        self.last_count, self._c = advance_frames(self._c, S, self.hop_s)
+        self.grid.advance(S)
         return (g, self.count, self.status, num, den) if observe else (g, self.count, self.status)
 
     def push(self, en, d_frames, out, offsets_row):
         """The gains of d_frames for the slots of offsets_row, applied by en (an enhance.Enhancer with rows = slots) to the beams `out`
         float32 [F, slots, N] that a listener made of the same frames -> (clean float32 [slots, S], en's count int32 [2], status int32
         [slots]).  The two must walk one frame grid: the same n_fft, hop_s and hop, and the same position in the stream."""
-        if (en.n_fft, en.hop_s, en.hop) != (self.n_fft, self.hop_s, self.hop):
-            raise ValueError("the Enhancer's frames (n_fft %d, hop_s %d, hop %d) are not the post-filter's (%d, %d, %d)"
-                             % (en.n_fft, en.hop_s, en.hop, self.n_fft, self.hop_s, self.hop))
-        if en._c != self._c:
-            raise ValueError("the Enhancer is %d samples behind its last frame end, the post-filter %d: they were not pushed together" % (en._c, self._c))
+        if en.grid.shape != self.grid.shape:
+            raise ValueError("the Enhancer's frames (n_fft %d, hop_s %d, hop %d) are not the post-filter's (%d, %d, %d)" % (en.grid.shape + self.grid.shape))
+        if en.grid.c != self.grid.c:
+            raise ValueError("the Enhancer is %d samples behind its last frame end, the post-filter %d: they were not pushed together" % (en.grid.c, self.grid.c))
         g, _, status = self.gains(d_frames, offsets_row)
         clean, count = en.push(out, gains=g)
         return clean, count, status
@@ -176,4 +165,4 @@ class SpatialPostFilter:
         """A new stream: all carried state is zeroed in place, so a captured call stays valid and starts the new stream on replay."""
         for t in (self.state, self.count, self.hist, self.num, self.den_state):
             t.zero_()
-        self._c, self.last_count = 0, 0
+        self.grid.reset()
