@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "../../include/beamformer_hip.h"
-#include "das_kernels.h"
+#include "das_geometry.h"      // (das_kernels.h, and what follows from a plan's family)
 #include "stream_grid.h"
 #include "sweep_order.h"
 
@@ -51,16 +51,15 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-// Everything a digest (bf::launch_digest) depends on; compared field by field.
+// Everything a digest (bf::launch_digest) depends on; compared field by field.  The family says what the geometry fields do not: the
+// row layout the offsets address, and whether the digest is grouped in the table's own sweep order (bf::family_traits).
 struct DigestKey {
     bool valid = false;
-    int mic_chunk = 0, row_stride = 0, lead = 0, algo = 0, dpw = 0, dir_begin = 0, dir_end = 0, n_mics = 0, nf = 0;
-    bool ordered = false;   // built for a kernel that sweeps in the table's own order (bf::sweep_order) rather than in flat order
-    int cells = 0;          // the row layout the offsets address: 1 = rows of 16-byte cells (plan.cells), which the geometry fields above do not show
+    int family = 0, mic_chunk = 0, row_stride = 0, lead = 0, algo = 0, dpw = 0, dir_begin = 0, dir_end = 0, n_mics = 0;
     bool operator==(const DigestKey& o) const
     {
-        return valid && o.valid && mic_chunk == o.mic_chunk && row_stride == o.row_stride && lead == o.lead && algo == o.algo && dpw == o.dpw &&
-               dir_begin == o.dir_begin && dir_end == o.dir_end && n_mics == o.n_mics && nf == o.nf && ordered == o.ordered && cells == o.cells;
+        return valid && o.valid && family == o.family && mic_chunk == o.mic_chunk && row_stride == o.row_stride && lead == o.lead && algo == o.algo &&
+               dpw == o.dpw && dir_begin == o.dir_begin && dir_end == o.dir_end && n_mics == o.n_mics;
     }
 };
 
@@ -610,16 +609,13 @@ bool store_sweep_order(const bf::DasLaunch& L, const bf::DasPlan& plan, int32_t*
     return HIP_OK(hipMemcpy(d_order, order.data(), padded * sizeof(int32_t), hipMemcpyHostToDevice));
 }
 
-// Shifted-copies layout with scalar tables: make sure the table set carries a digest built for this plan.
-bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t stream)
+// The families that take a digest: make sure the table set carries one built for this plan.  A slot whose table went to the
+// direction-outer family replans the launch (L.tab.digest_direct, `plan`).
+bool attach_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t stream)
 {
-    S().last_variant = plan.layout == 2 ? (plan.nf == 2 ? 7 : 4) : plan.layout;   // refined below for the digest-driven kernels
-    S().last_changes = -1; S().last_steps = 0; S().last_rows = 0;
-    const bool plain_fir = L.algo == bf::ALGO_FIR_NAIVE || L.algo == bf::ALGO_FIR_VEC;
-    if (plan.layout != 2 || (plain_fir && plan.nf != 2)) return true;   // the plain FIRs have no whole-sample table (their pair kernel wants the taps regrouped)
-    // everything the digest depends on: the plan's geometry, the algorithm and (grouped layouts) the direction range
-    const long long want_order = bf::digest_order_offset(L, plan);   // (non-zero: the plan's kernel stores by an order table)
-    const DigestKey key{true, plan.mic_chunk, plan.row_stride, plan.lead, L.algo, plan.dpw, L.dir_begin, L.dir_end, L.n_mics, plan.nf, want_order != 0, plan.cells};
+    // everything the digest depends on: the plan's family and geometry, the algorithm and (grouped layouts) the direction range
+    const bf::DigestLayout lay = bf::digest_layout(L, plan);
+    const DigestKey key{true, plan.family, plan.mic_chunk, plan.row_stride, plan.lead, L.algo, plan.dpw, L.dir_begin, L.dir_end, L.n_mics};
     TableSet::DigestSlot* slot = nullptr;
     for (auto& d : t.digests)
         if (d.buf.p && d.key == key) slot = &d;
@@ -633,21 +629,20 @@ bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t
         }
         if (victim->buf.p && !HIP_OK(hipDeviceSynchronize())) return false;
         victim->key = DigestKey{};
-        if (!HIP_OK(victim->buf.reserve(bf::digest_elements(L, plan))) || !HIP_OK(s.d_counter.reserve(1))) return false;
+        if (!HIP_OK(victim->buf.reserve(lay.elements)) || !HIP_OK(s.d_counter.reserve(1))) return false;
         victim->direct = false;
         victim->order_off = 0; victim->changes = -1; victim->steps = 0;
-        if (want_order != 0) {
+        if (lay.order_off != 0) {                               // (the plan's kernel stores by an order table)
             bool stored = false;
-            if (!store_sweep_order(L, plan, victim->buf.p + want_order, &stored)) return false;
-            if (stored) victim->order_off = want_order;
+            if (!store_sweep_order(L, plan, victim->buf.p + lay.order_off, &stored)) return false;
+            if (stored) victim->order_off = lay.order_off;
         }
-        const bool plain = L.algo == bf::ALGO_PAD || L.algo == bf::ALGO_LERP;
-        const bool grouped = plain || ((L.algo == bf::ALGO_HYBRID || plain_fir) && plan.nf == 2);
+        const bool grouped = lay.kind == bf::DIGEST_GROUPED;
         if (grouped && !HIP_OK(hipMemsetAsync(s.d_counter.p, 0, sizeof(unsigned long long), stream))) return false;
-        if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, grouped ? s.d_counter.p : nullptr, false, victim->order_off, stream))) return false;
+        if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, grouped ? s.d_counter.p : nullptr, victim->order_off, stream))) return false;
         // once per (table, geometry): wait, so that a later launch on ANOTHER stream cannot overtake the digest's construction
         if (!HIP_OK(hipStreamSynchronize(stream))) return false;
-        if (plain && plan.waves == 16) {
+        if (bf::family_traits(plan.family).reread_handover && plan.waves == 16) {      // (the direction-outer variant exists for 16 waves only)
             // A table without structure (more than half of the direction steps change the delay, counted in sweep order) defeats the
             // sweep: use the direction-outer kernel variant and its [D][M] digest instead.
             unsigned long long reloads = 0;
@@ -657,7 +652,7 @@ bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t
             if (steps > 0 && 2 * (long long)reloads > steps) {
                 L.tab.digest_direct = true;
                 if (!plan_or_error(L, &plan)) return false;     // that variant reads at every step: four shifted copies, its own chunk size
-                if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, nullptr, true, 0, stream)) || !HIP_OK(hipStreamSynchronize(stream))) return false;
+                if (!HIP_OK(bf::launch_digest(L, plan, victim->buf.p, nullptr, 0, stream)) || !HIP_OK(hipStreamSynchronize(stream))) return false;
                 victim->direct = true;
                 victim->order_off = 0;                          // (that variant walks [D][M] in flat order)
             }
@@ -673,9 +668,17 @@ bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t
     L.tab.digest = slot->buf.p;
     L.tab.digest_order_off = slot->order_off;
     S().last_changes = slot->changes; S().last_steps = slot->steps;
-    S().last_variant = (L.algo == bf::ALGO_PAD || L.algo == bf::ALGO_LERP) ? (slot->direct ? 3 : plan.nf == 2 ? (plan.interleaved ? 8 : 5) : plan.long_rows ? 6 : 2) : plan.nf == 2 ? 7 : 4;
-    S().last_rows = S().last_variant == 8 ? (plan.cells ? 2 : 1) : 0;
     return true;
+}
+
+// What a batched launch needs beyond its plan: its digest, where its family takes one, and the record of the family it ends up with.
+bool ensure_digest(TableSet& t, bf::DasLaunch& L, bf::DasPlan& plan, hipStream_t stream)
+{
+    S().last_changes = -1; S().last_steps = 0;
+    const bool ok = bf::digest_layout(L, plan).kind == bf::DIGEST_NONE || attach_digest(t, L, plan, stream);
+    const bf::FamilyTraits ft = bf::family_traits(plan.family);      // (attach_digest may have replanned the launch direction-outer)
+    S().last_variant = ft.variant; S().last_rows = ft.rows;
+    return ok;
 }
 
 // mimo_* with host pointers: one frame in, one image out (PC/src/algorithms/pad_and_sum.c:100-143 and twins).

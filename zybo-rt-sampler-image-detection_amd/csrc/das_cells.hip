@@ -423,7 +423,7 @@ __global__ void __launch_bounds__(1024, 4) das_pair2_cells_kernel(BF_TABLE_PARAM
 hipError_t launch_pair_cells(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
 {
     using G = copies::CellGeo;
-    if (L.algo != ALGO_LERP || !plan.cells || L.tab.digest_direct || plan.waves != copies::kWaves || plan.nf != 2 || plan.interleaved != 1 ||
+    if (L.algo != ALGO_LERP || plan.family != DAS_PAIR_CELLS || L.tab.digest_direct || plan.waves != copies::kWaves ||
         plan.lead != G::kLead || (L.n_mics % G::kMc) != 0 || (L.n_samples % 4) != 0 || L.n_samples <= 128 || L.n_samples > 256 ||
         plan.lds_bytes < (size_t)copies::Pair2Geo::kMc * copies::Pair2Geo::kSlot * sizeof(float))     // the family's image: the rows and the parked rows fit it
         return hipErrorInvalidValue;

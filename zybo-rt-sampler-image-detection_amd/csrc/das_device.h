@@ -301,10 +301,11 @@ inline KArgs make_args(const DasLaunch& L, const DasPlan& plan)
     a.n_is_pow2 = (L.n_mics & (L.n_mics - 1)) == 0;
     a.inv_n = 1.0f / (float)L.n_mics;
     a.n_frames = L.frames;
-    a.wg_frames = plan.nf == 2 ? (L.frames + 1) / 2 : L.frames;
+    a.wg_frames = wg_frames(plan.family, L.frames);
     a.frame_inner = plan.frame_inner;
-    a.digest_h_off = (plan.layout == 2 && (L.algo == ALGO_LERP || (L.algo == ALGO_HYBRID && plan.nf == 2))) ? grouped_entries_for_args(L, plan) : 0;
-    a.digest_t_off = (plan.layout == 2 && L.algo == ALGO_HYBRID && plan.nf == 2) ? 2 * grouped_entries_for_args(L, plan) : 0;
+    const DigestLayout dig = digest_layout(L, plan);
+    a.digest_h_off = dig.h_off;
+    a.digest_t_off = dig.t_off;
     a.digest_o_off = L.tab.digest_order_off;
     return a;
 }

@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI layer (beamformer_api.cpp) and the gfx950 kernels (das_kernels.hip, das_strided.hip, das_pair.hip, planned by das_plan.cpp).
+// Internal interface between the C-ABI layer (beamformer_api.cpp) and the gfx950 kernels (das_kernels.hip, das_strided.hip, das_pair.hip, das_cells.hip, planned by das_plan.cpp).
 // Not installed; the public boundary is include/beamformer_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -45,8 +45,25 @@ struct DasLaunch {
     int frames;
 };
 
+// The kernel family of a batched delay-and-sum launch.  plan_das picks it, once (pick_family, das_plan.cpp); the launchers, the digest and
+// the C-ABI read it.  What follows from a family -- frames per workgroup, digest, the numbers bf_last_das_variant / bf_last_das_rows
+// report -- is family_traits' table (das_geometry.h).
+enum DasFamily : int {
+    DAS_STRIDED = 0,     // das_mimo_kernel: N <= 128; the FIR flavours with other than 8 taps or beyond 256 samples; stream maps, listed directions
+    DAS_COPIES,          // das_copies_kernel: pad / lerp beyond 128 samples that no kernel below takes -- the one-frame sweep
+    DAS_COPIES_DIRECT,   // das_copies_kernel<.., DIRECT>: pad / lerp on a table without structure (DeviceTables::digest_direct) -- direction-outer, four copies
+    DAS_COPIES_FIR,      // das_copies_kernel: the 8-tap FIR flavours at 128 < N <= 256
+    DAS_PAIR_PAD,        // das_pair_kernel: pad at N <= 256, the fixed row stride, a multiple of 16 mics, two or more frames -- two frames per workgroup
+    DAS_PAIR_LERP,       // das_pair2_kernel: lerp under the same conditions -- both frames interleaved in the rows, sample by sample
+    DAS_PAIR_CELLS,      // das_pair2_cells_kernel: ... and a multiple of 32 mics -- rows of 16-byte cells (mic_chunk, row_stride and lds_bytes stay das_pair2_kernel's)
+    DAS_PAIR_FIR,        // das_hybrid_pair_kernel: the 8-tap FIR flavours under the pair conditions
+    DAS_LONG,            // das_long_kernel: pad / lerp at 256 < N <= 1024 whose mics are whole halves of 16 / nseg -- LDS image in two halves
+    DAS_FAMILY_COUNT
+};
+
 // Plan chosen on the host for a launch (exposed so tests can check LDS sizing without a GPU).
 struct DasPlan {
+    DasFamily family;
     int nc;          // 64-sample segments per row (N rounded up to 64*nc)
     int lead;        // zero floats in front of every LDS row
     int row_stride;  // floats per LDS row
@@ -56,18 +73,12 @@ struct DasPlan {
     int scratch_off; // float offset of the per-wave power scratch in LDS
     int srow;        // scratch row stride in floats (64*nc + 4)
     int pbw;         // scratch rows (finished directions) per wave
-    int layout;      // 0 strided (lane-strided samples), 2 shifted copies (pad / lerp at N > 128, the 8-tap FIR flavours at 128 < N <= 256)
     int dpw;         // directions a wave carries across mic chunks
-    int nf;          // frames a workgroup carries (2: das_pair_kernel -- pad / lerp at N <= 256 with the fixed row stride, a multiple of 16 mics and two or more frames)
-    int interleaved; // 1: two-frame kernels whose LDS rows hold both frames interleaved sample by sample (das_pair2_kernel, das_hybrid_pair_kernel)
-    int long_rows;   // 1: das_long_kernel (pad / lerp at 256 < N <= 1024: LDS image in two halves, conflict-free lane mapping)
     int frame_inner; // workgroup id -> (tile, frame): 1 = an XCD runs all frames of a tile back to back (tables beyond the L2s)
-    int copies;      // layout 2: shifted copies per staged array (2: the sweep of pad / lerp, 4: FIR flavours and the DIRECT variant)
+    int copies;      // shifted copies per staged array (0: strided; 2: the sweeps of pad / lerp and the FIR pair kernel, 4: the one-frame FIR flavours and DAS_COPIES_DIRECT)
     int tile_dirs;   // directions per workgroup
     int n_tiles;     // padded to a multiple of 8 (XCD affinity: tile % 8 == workgroup id % 8) unless the launch's table fits every XCD's L2
     size_t lds_bytes;
-    int cells;       // internal (no plan export carries it): 1 = the interleaved lerp pair family runs on rows of 16-byte cells (das_pair2_cells_kernel: a multiple of
-                     // 32 mics).  The digest is then built for 32 slots of CellGeo::kSlot floats; mic_chunk, row_stride and lds_bytes stay das_pair2_kernel's.
 };
 
 // Returns 0 and fills `plan`, or a negative value when the shape is unsupported (message in `why`).
@@ -75,14 +86,13 @@ int plan_das(const DasLaunch& L, int n_cus, DasPlan* plan, const char** why);
 
 // Build DeviceTables::digest for the layout `plan` describes (shifted-copies layout only).
 size_t digest_elements(const DasLaunch& L, const DasPlan& plan);   // 4-byte elements the digest of this launch needs (0: none)
-// `direct`: the [D][M] layout of the direction-outer kernel variant (tables without structure) instead of the grouped one;
+// The layout is digest_layout's (das_geometry.h): flat [D][M] or grouped, as the plan's family takes it.
 // d_reload_count (grouped build, optional) receives the number of direction steps whose delay differs from the previous one's.
 // order_off (grouped build; 0: none): the sweep order already stored at d_digest + order_off -- int32, one entry per position of the
 // launch padded to whole groups of plan.dpw by repeating the last (digest_order_offset says where; sweep_order.h what) -- in which
 // the digest is then grouped and its re-reads counted.
 long long digest_order_offset(const DasLaunch& L, const DasPlan& plan);    // 0: the plan's kernel takes no order (all but the pad / lerp pair kernels)
-hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, bool direct, long long order_off,
-                         hipStream_t stream);
+hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, long long order_off, hipStream_t stream);
 long long digest_shareable_steps(const DasLaunch& L, const DasPlan& plan);
 
 // Enqueue on `stream`; no host synchronisation, no allocation (graph-capturable).

@@ -1765,7 +1765,7 @@ template <int ALGO>
 hipError_t launch_hybrid_pair_algo(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
 {
     using HG = copies::HybridGeo;
-    if (L.tab.digest == nullptr || plan.waves != copies::kWaves || plan.mic_chunk != HG::kMc || plan.row_stride != HG::kRs ||
+    if (plan.family != DAS_PAIR_FIR || L.tab.digest == nullptr || plan.waves != copies::kWaves || plan.mic_chunk != HG::kMc || plan.row_stride != HG::kRs ||
         plan.lead != HG::kLead || (L.n_mics % 16) != 0 || L.n_taps != 8)
         return hipErrorInvalidValue;
     static int hybrid_scratch = -1;
@@ -1778,7 +1778,7 @@ template <int ALGO, int NSEG>
 hipError_t launch_long_seg(const DasLaunch& L, const DasPlan& plan, int frames, hipStream_t stream)
 {
     using LG = copies::LongGeo<ALGO, NSEG>;
-    if (L.tab.digest == nullptr || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != LG::kMc ||
+    if (plan.family != DAS_LONG || L.tab.digest == nullptr || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != LG::kMc ||
         (L.n_mics % LG::kHalf) != 0 || plan.dpw != LG::kDw)
         return hipErrorInvalidValue;
     const bool fixed_rs = plan.row_stride == (LG::kLerp ? 2 : 1) * copies::Geo<NSEG>::kRs && plan.lead == copies::Geo<NSEG>::kLead;
@@ -1829,6 +1829,7 @@ hipError_t launch_copies(const DasLaunch& L, const DasPlan& plan, int frames, hi
             default: return hipErrorInvalidValue;
         }
     };
+    if (plan.family != (is_fir(L.algo) ? DAS_COPIES_FIR : L.tab.digest_direct ? DAS_COPIES_DIRECT : DAS_COPIES)) return hipErrorInvalidValue;
     if (is_fir(L.algo) && plan.nc != 4) return hipErrorInvalidValue;
     switch (L.algo) {
         case ALGO_PAD: return plain(std::integral_constant<int, ALGO_PAD>());
@@ -1840,35 +1841,20 @@ hipError_t launch_copies(const DasLaunch& L, const DasPlan& plan, int frames, hi
     }
 }
 
-hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, bool direct, long long order_off,
-                         hipStream_t stream)
+// Build the digest digest_layout describes: the flat [D][M] offsets, or the grouped ones with whatever the family keeps behind them.
+hipError_t launch_digest(const DasLaunch& L, const DasPlan& plan, int32_t* d_digest, unsigned long long* d_reload_count, long long order_off, hipStream_t stream)
 {
-    // what the kernel looks back by beyond the whole-sample delay: lerp reads s[k - p - 1], hybrid starts its window at
-    // s[k - p - 1 - T/2] (T = 8)
-    // (`arrays`: rows of one staged mic in units of its shifted copies -- samples, lerp's differences, and both frames of the pair kernel)
-    // (the hybrid pair kernel interleaves its two frames inside a row: one array per mic)
-    // (das_long_kernel's lerp rows carry their differences inside: one array)
-    const int arrays = ((L.algo == ALGO_LERP && !(plan.long_rows && plan.interleaved)) ? 2 : 1) * ((plan.nf == 2 && !plan.interleaved) ? 2 : 1), bias = (L.algo == ALGO_LERP) ? 1 : (L.algo == ALGO_HYBRID) ? 5 : 0;
-    const bool fir_pair = plan.nf == 2 && is_fir(L.algo);
-    if ((L.algo == ALGO_HYBRID && plan.nf != 2) || direct) {
-        hipLaunchKernelGGL(digest_kernel, dim3(1024), dim3(256), 0, stream, L.tab.whole, d_digest, (long long)L.n_dirs * L.n_mics, L.n_mics, plan.mic_chunk,
-                           arrays, plan.row_stride, plan.lead, bias, plan.copies);
-    } else {
-        const long long entries = grouped_entries_for_args(L, plan);
-        if (plan.cells) {
-            // rows of 16-byte cells (das_pair2_cells_kernel): 32 slots of one row each, no shifted copies, a sample is four floats wide
-            using CG = copies::CellGeo;
-            hipLaunchKernelGGL(digest_grouped_kernel, dim3(1024), dim3(256), 0, stream, L.tab.whole, L.tab.frac, d_digest, entries, entries, L.n_mics, plan.dpw,
-                               L.dir_begin, L.dir_end, CG::kMc, 1, CG::kSlot, CG::kLead, bias, 1, d_reload_count, 0, 4, nullptr, 0,
-                               order_off != 0 ? d_digest + order_off : nullptr);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL(digest_grouped_kernel, dim3(1024), dim3(256), 0, stream, L.algo == ALGO_HYBRID || !fir_pair ? L.tab.whole : nullptr,
-                           L.algo == ALGO_LERP ? L.tab.frac : nullptr, d_digest,
-                           entries, entries, L.n_mics, plan.dpw, L.dir_begin, L.dir_end, plan.mic_chunk, arrays, plan.row_stride, plan.lead, bias,
-                           plan.copies, d_reload_count, L.algo == ALGO_HYBRID ? 1 : 0, plan.interleaved ? 2 : 1, fir_pair ? L.tab.taps : nullptr,
-                           fir_pair ? (L.algo == ALGO_HYBRID ? 2 * entries : 0) : 0, order_off != 0 ? d_digest + order_off : nullptr);
+    const DigestLayout g = digest_layout(L, plan);
+    if (g.kind == DIGEST_NONE) return hipErrorInvalidValue;
+    if (g.kind == DIGEST_FLAT) {
+        hipLaunchKernelGGL(digest_kernel, dim3(1024), dim3(256), 0, stream, L.tab.whole, d_digest, (long long)L.n_dirs * L.n_mics, L.n_mics, g.slots, g.arrays,
+                           g.slot_stride, g.lead, g.bias, g.copies);
+        return hipGetLastError();
     }
+    const bool fir_pair = plan.family == DAS_PAIR_FIR, hybrid = L.algo == ALGO_HYBRID;   // (the plain FIRs have no whole-sample table: their digest is the regrouped taps)
+    hipLaunchKernelGGL(digest_grouped_kernel, dim3(1024), dim3(256), 0, stream, hybrid || !fir_pair ? L.tab.whole : nullptr, L.algo == ALGO_LERP ? L.tab.frac : nullptr,
+                       d_digest, g.entries, g.entries, L.n_mics, plan.dpw, L.dir_begin, L.dir_end, g.slots, g.arrays, g.slot_stride, g.lead, g.bias, g.copies,
+                       d_reload_count, hybrid ? 1 : 0, g.width, fir_pair ? L.tab.taps : nullptr, g.t_off, order_off != 0 ? d_digest + order_off : nullptr);
     return hipGetLastError();
 }
 

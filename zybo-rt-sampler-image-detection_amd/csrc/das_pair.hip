@@ -631,8 +631,8 @@ hipError_t launch_pair_algo(const DasLaunch& L, const DasPlan& plan, int frames,
 {
     constexpr bool kLerp = ALGO == ALGO_LERP;           // das_pair_kernel (pad) / das_pair2_kernel (lerp: frames interleaved in the rows)
     using PG = std::conditional_t<kLerp, copies::Pair2Geo, copies::PairGeo>;
-    if (L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != PG::kMc || plan.row_stride != PG::kRs ||
-        plan.lead != PG::kLead || plan.interleaved != (kLerp ? 1 : 0) || (L.n_mics % 16) != 0)
+    if (plan.family != (kLerp ? DAS_PAIR_LERP : DAS_PAIR_PAD) || L.tab.digest_direct || plan.waves != copies::kWaves || plan.mic_chunk != PG::kMc ||
+        plan.row_stride != PG::kRs || plan.lead != PG::kLead || (L.n_mics % 16) != 0)
         return hipErrorInvalidValue;
     auto kernel = [] { if constexpr (kLerp) return copies::das_pair2_kernel<ALGO>; else return copies::das_pair_kernel<ALGO>; }();
     static int pair_scratch = -1;

@@ -626,7 +626,7 @@ hipError_t launch_select_algo(const DasLaunch& L, const DasPlan& plan, const flo
 bool select_launch_ok(const DasLaunch& L, const DasPlan& plan, const int32_t* d_offsets)
 {
     return L.frames >= 1 && L.dir_begin == 0 && L.dir_end >= 1 && L.image_origin == 0 && L.image_stride >= L.dir_end && d_offsets != nullptr &&
-           L.images != nullptr && plan.layout == 0;
+           L.images != nullptr && plan.family == DAS_STRIDED;
 }
 
 }  // namespace
@@ -646,7 +646,7 @@ hipError_t launch_strided(const DasLaunch& L, const DasPlan& plan, int frames, h
 hipError_t launch_stream_maps(const DasLaunch& L, const DasPlan& plan, const float* d_prev, int hop, hipStream_t stream)
 {
     int hist;
-    if (!stream_launch_ok(L, plan, hop, &hist) || plan.layout != 0) return hipErrorInvalidValue;
+    if (!stream_launch_ok(L, plan, hop, &hist) || plan.family != DAS_STRIDED) return hipErrorInvalidValue;
     if (L.algo == ALGO_PAD) return launch_mimo_algo<ALGO_PAD, true>(L, plan, L.frames, d_prev, hop, hist, stream);
     return launch_mimo_algo<ALGO_LERP, true>(L, plan, L.frames, d_prev, hop, hist, stream);
 }
